@@ -8,7 +8,11 @@ which is otherwise reported as the second figure `stereo`.  A "step" is one fram
 a keyframe — one pass of LocalMapping::Run including LocalBundleAdjustment (reference timing points: Examples/RGB-D/rgbd_tum.cc:93-109 around
 the track call, src/LocalMapping.cc:82).  Images are resident in HBM when the timed region starts.
 
-Contract: python bench.py --gpus N --steps K --warmup W ; ONE JSON line on rank 0.  `--gpus N` with no RANK in the environment starts
+Contract: python bench.py --gpus N --steps K --warmup W ; ONE JSON line on rank 0.  Such a plain run does only what the headline figure needs: it renders and
+uploads the inputs, advances the maps through a SHORT pre-roll (PLAIN_PREROLL = 40 steps: the 200-step pre-roll of the steady state alone takes 35 s), warms up, times
+exactly K steps and prints the line (`--dump-outputs DIR` also writes what the last timed step returned).  `--full` is the whole measurement: the 200-step
+pre-roll of the steady state (the regime of the figures in README.md / DESIGN.md section 8), the CPU baselines, the second workload, the 32-base leg, host inputs,
+the front-end stage, the local-BA operator alone and the fp64 issue rates.  `--gpus N` with no RANK in the environment starts
 the N ranks itself (child processes, before anything touches the GPU); under torchrun the RANK/LOCAL_RANK/WORLD_SIZE of the
 environment are used.  Multi-GPU = independent sequences sharded over ranks (weak scaling: `--seqs` sequences per GPU), no data-path
 collective; RCCL carries the barriers, the max-over-ranks time and one all-gather of a fixed-size record per rank.
@@ -31,6 +35,10 @@ sys.path.insert(0, ROOT)
 # other (the MapPoint-update operator spent 3.5x its kernels' time waiting).  Must be in the environment before the HIP runtime starts (the first import of
 # torch): measured 24.2 k against 22.7 k frames/s in the steady state (same box); 12 / 16 queues give 24.2 / 24.4 k.  INTEGRATION.md names it for host applications.
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "12")   # (round 4: 8 handles + the 2 streams of the local-BA service; same-box A/B of the deferred schedule: 8 -> 26.4 k, 12 -> 27.3 k, 16 -> 26.6 k)
+
+STEADY_PREROLL = {"rgbd": 200, "stereo": 40}   # untimed steps that bring every map to its steady state (frame >= 200 of the S1 stream)
+PLAIN_PREROLL = {"rgbd": 40, "stereo": 40}     # the pre-roll of a plain run: 8192 RGB-D sequences take ~0.17 s per pre-roll step, so 200 steps alone are 35 s of set-up;
+                                               # after 40 the local-BA windows hold ~11 instead of ~27 keyframes (`lba_windows_timed`, `config.regime` say so in the line)
 
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8 TB/s (spec)
 FP64_PEAK_TFLOPS = 78.6    # MI355X fp64 matrix (= vector) peak, AMD datasheet: 256 CUs x 4 SIMDs x 32 flop/clk x 2.4 GHz (v_mfma_f64_16x16x4_f64: 2048 flop / 64 clk;
@@ -406,6 +414,16 @@ def frontend_stage(frames, Twc, depth, local_rank, steps, B=512, parts=None):
     return out
 
 
+def dump_outputs(directory, last_outputs, rank=0, world=1):
+    """--dump-outputs: what the last timed step returned to its caller — per handle the poses Tcw [S, 4, 4] and the tracking states [S] that
+    oslam_slam_track_* fill (include/oslam_slam.h) — concatenated in handle order: <directory>/Tcw.npy, state.npy, float32 (a rank of a multi-rank job
+    writes Tcw_rank<r>.npy / state_rank<r>.npy).  The inputs are seeded renderings, so two builds run with the same arguments are compared array for array."""
+    os.makedirs(directory, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    np.save(os.path.join(directory, "Tcw%s.npy" % sfx), np.concatenate([t for t, _ in last_outputs], 0).astype(np.float32))
+    np.save(os.path.join(directory, "state%s.npy" % sfx), np.concatenate([s for _, s in last_outputs], 0).astype(np.float32))
+
+
 def _pmc(kernel, field="bytes_per_launch"):
     """Per-launch PMC figure of `kernel` from the committed summary of this round (profiles/r05_pmc_traffic.json: separate rocprofv3 --pmc passes of
     the S2 stage at 512 frames per launch — FETCH_SIZE, WRITE_SIZE, SQ_* — corrected as MI355X_MICROARCH.md §HBM prescribes); None when the summary has
@@ -475,8 +493,14 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", choices=("rgbd", "stereo"), default="rgbd")
-    ap.add_argument("--preroll", type=int, default=-1, help="untimed set-up steps before the warm-up that bring every sequence's map to its steady state (default: 200 for the "
-                                                             "RGB-D stream = SURVEY.md §8(d) frame >= 200, 40 for the stereo street); 0 = the cold-start regime of round 2")
+    ap.add_argument("--full", action="store_true", help="the whole measurement instead of the headline alone: the steady-state pre-roll (200 steps for the RGB-D stream), the "
+                    "CPU baselines, the second workload, the 32-base leg, the host-input leg, the front-end stage, the local-BA operator alone, the fp64 issue rates "
+                    "(minutes instead of seconds; --no-extras / --no-cpu-baseline drop parts of it and select it themselves)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy: "
+                    "Tcw.npy float32 [sequences, 4, 4] (the poses track returns, sequences in handle order) and state.npy float32 [sequences] (the tracking states)")
+    ap.add_argument("--preroll", type=int, default=-1, help="untimed set-up steps before the warm-up that age every sequence's map (default: 40 in a plain run; with --full "
+                    "the steady state: 200 for the RGB-D stream = SURVEY.md §8(d) frame >= 200, 40 for the stereo street); 0 = the cold-start "
+                    "regime of round 2")
     ap.add_argument("--seqs", type=int, default=0, help="sequences per GPU (default: 8192 RGB-D / 2048 stereo)")
     ap.add_argument("--bases", type=int, default=8, help="base renderings per GPU of the headline stream (distinct input streams = bases x 25 frame offsets)")
     ap.add_argument("--lm", choices=("deferred", "sync"), default="sync", help="local-mapping schedule (include/oslam_slam.h): sync (default) = the whole pass right after the frame "
@@ -485,8 +509,8 @@ def main():
                     "On the final code of round 4 sync is the faster one on the headline stream (12 %% fewer keyframes, DESIGN.md section 7.2)")
     ap.add_argument("--handles", type=int, default=0, help="driver handles per GPU, one host thread each (default 8)")
     ap.add_argument("--cpu-frames", type=int, default=0, help="frames of the CPU baseline's timed range (default: the timed steps and what the base sequence holds after them)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only (profiling runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="the --full run without its CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="the --full run without its extra legs: the headline in the steady state only (profiling runs)")
     ap.add_argument("--strict", action="store_true", help="exit non-zero when one of the extra legs (front end, local BA alone, host inputs, second workload ...) failed, instead of "
                     "only recording its error in the line")
     ap.add_argument("--no-bases32", action="store_true", help="skip the second headline figure with 32 base renderings (800 distinct input streams)")
@@ -494,6 +518,9 @@ def main():
                     "inside this process behind the headline (measured in round 5: much slower while the parent process is alive on the card - 4.5 k against 18-22 k stereo frames/s)")
     ap.add_argument("--cold", action="store_true", help="also run the cold-start regime of rounds 1-2 (steps W..W+K of empty maps) on the headline streams")
     args = ap.parse_args()
+    # --no-extras / --no-cpu-baseline name parts of the full run to leave out: they keep selecting it (the steady-state pre-roll with them), as before --full existed
+    full = args.full or args.no_extras or args.no_cpu_baseline or args.cold or args.extras_child_processes
+    t_start = time.perf_counter()
 
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))
@@ -509,7 +536,7 @@ def main():
     from object_slam_amd import seqbench, slam
     cores = os.cpu_count() or 1
     stereo_head = args.workload == "stereo"
-    preroll = args.preroll if args.preroll >= 0 else (40 if stereo_head else 200)
+    preroll = args.preroll if args.preroll >= 0 else (STEADY_PREROLL if full else PLAIN_PREROLL)[args.workload]
     wl_rgbd = seqbench.rgbd_workload(speed=1.0, n_base=args.bases, stagger=24)
     wl_st = seqbench.stereo_workload()
     head, second = (wl_st, wl_rgbd) if stereo_head else (wl_rgbd, wl_st)
@@ -530,11 +557,12 @@ def main():
         except Exception:
             pass
     G = args.handles or 8
-    extras_on = rank == 0 and world == 1 and not args.no_extras
+    extras_on = full and rank == 0 and world == 1 and not args.no_extras
+    cpu_on = full and not args.no_cpu_baseline
     host_phase = extras_on and not stereo_head            # the same warmed sequences continued with host-resident inputs
     post_frames = (2 + args.steps) if host_phase else 0
     n_frames = preroll + args.warmup + args.steps + post_frames
-    log = (lambda m: (sys.stderr.write("[bench] " + m + "\n"), sys.stderr.flush())) if rank == 0 else None
+    log = (lambda m: (sys.stderr.write("[bench %6.1f s] %s\n" % (time.perf_counter() - t_start, m)), sys.stderr.flush())) if rank == 0 else None
     # ---- render the input streams on the host cores BEFORE the process touches the GPU (worker processes are forked) ----
     t_gen = time.perf_counter()
     # OSLAM_BENCH_SHARED_BASES=1 (multi-rank runs): the node's ranks replay ONE set of rendered base streams mapped from a shared-memory segment instead of
@@ -608,6 +636,7 @@ def main():
 
     mem_gb = {}
     rss_gb = {}
+    last_out = {}
 
     def run(wl, seqs, S_, G_, tag, preroll_=0, post_frames_=0, post_=None, drop_host_inputs=(), trim=False):
         snap = {}
@@ -639,6 +668,7 @@ def main():
                     for k in v:
                         a[k] += v[k]
         kt[tag] = tot
+        last_out[tag] = extra["last_outputs"]
         stages, cores_s = stage_totals(systems)
         summ["stage_seconds_sum_over_handles"] = {k: round(v, 4) for k, v in stages.items()}
         summ["stage_core_seconds_sum_over_handles"] = {k: round(v, 4) for k, v in cores_s.items()}
@@ -663,6 +693,8 @@ def main():
             rss_gb[tag] = {"rss": round(vm["VmRSS"] / 1048576.0, 2), "peak_so_far": round(vm["VmHWM"] / 1048576.0, 2)}
         except Exception:
             rss_gb[tag] = None
+        if log:
+            log("leg '%s': results collected" % tag)
         for sy in systems:
             sy.close()
         del systems, extra
@@ -718,10 +750,12 @@ def main():
         return out
 
     summ, rec = run(head, seq_head, S, G, "head", preroll, post_frames, host_inputs_phase if host_phase else None)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_out["head"], rank, world)
+    if log:
+        log("headline done: %.1f frames/s" % summ["frames_per_s"])
     second_out = cold = bases32 = None
     if extras_on:
-        if log:
-            log("headline done: %.1f frames/s" % summ["frames_per_s"])
         if preroll > 0 and args.cold:     # the cold-start regime of rounds 1-2 on the same streams (maps at most warmup + steps frames old)
             c, _ = run(head, seq_head, S, G, "cold")
             cold = {"frames_per_s": round(c["frames_per_s"], 1), "ms_per_step": round(c["ms_per_step"], 3), "lba_windows_timed": c["lba_windows_timed"],
@@ -785,7 +819,7 @@ def main():
                     bases32 = {"error": repr(ex)}; extras_failed.append("bases32")
                 seq_b32 = None
         cpu2 = None
-        if not args.no_cpu_baseline:
+        if cpu_on:
             if log:
                 log("CPU baseline of the second workload ...")
             cpu2 = cpu_baseline(second, seq_second, pre2 + args.warmup, cpu_n2, slam.LM_DEFERRED if args.lm == "deferred" else slam.LM_SYNC, two_thread_streams=2)
@@ -806,7 +840,7 @@ def main():
     if rank == 0:
         roof = roofline_of(kt["head"], summ, head is wl_st)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_on:
             if log:
                 log("CPU baseline ...")
             cpu = cpu_baseline(head, seq_head, preroll + args.warmup, cpu_n, slam.LM_DEFERRED if args.lm == "deferred" else slam.LM_SYNC)
@@ -836,8 +870,12 @@ def main():
                 roof["fp64_peak_measured"] = mfma_f64_rate.measure(local_rank)
             except Exception as ex:
                 roof["fp64_peak_measured"] = {"error": repr(ex)}; extras_failed.append("fp64_peak_measured")
+        steady = preroll >= STEADY_PREROLL[args.workload]
         regime = ("steady state: every sequence is advanced %d untimed steps before the warm-up, so the timed steps are frames %d..%d of every sequence (SURVEY.md §8(d): "
-                  "frame >= 200 of the S1 stream at <= 2 cm / 0.5 deg per frame)" % (preroll, preroll + args.warmup, preroll + args.warmup + args.steps)) if preroll > 0 else \
+                  "frame >= 200 of the S1 stream at <= 2 cm / 0.5 deg per frame)" % (preroll, preroll + args.warmup, preroll + args.warmup + args.steps)) if steady else \
+                 ("short pre-roll: every sequence is advanced %d untimed steps before the warm-up, so the timed steps are frames %d..%d of every sequence; the maps are "
+                  "younger than the steady state's (%d steps, --full): smaller local-BA windows, more keyframes per step"
+                  % (preroll, preroll + args.warmup, preroll + args.warmup + args.steps, STEADY_PREROLL[args.workload])) if preroll > 0 else \
                  ("cold start: steps %d..%d of empty maps" % (args.warmup, args.warmup + args.steps))
         out = {"metric": "frames/sec tracking+localBA", "value": round(summ["frames_per_s"], 1), "unit": "frames/s", "n_gpus": world,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(summ["ms_per_step"], 4), "higher_is_better": True, "scaling": "weak",
@@ -845,7 +883,7 @@ def main():
                "config": {"workload": "%s stream through the oslam_slam driver (Tracking::Track + LocalMapping::Run incl. LocalBundleAdjustment on every keyframe): "
                                       "%d sequences per GPU in %d handles (one host thread + %d workers each), %d ORB features, images resident in HBM; %s; "
                                       "BASELINE.json configs[%s]" % (head.name, S, G, summ["host_threads_per_handle"] - 1, head.nFeatures, regime, "2" if head is wl_rgbd else "3]/[4"),
-                          "regime": "steady_state" if preroll > 0 else "cold_start", "preroll_steps": preroll, "preroll_s": round(summ["preroll_s"], 1),
+                          "regime": "steady_state" if steady else ("short_preroll" if preroll > 0 else "cold_start"), "preroll_steps": preroll, "full": full, "preroll_s": round(summ["preroll_s"], 1),
                           "sequences_per_gpu": S, "sequences_per_gpu_reduced_from_for_host_memory": seqs_reduced_from, "frames_per_step": S * world, "local_mapping_schedule": args.lm,
                           "distinct_streams_per_gpu": min(S, head.n_base * (head.stagger + 1)), "replicas_per_stream": round(S / min(S, head.n_base * (head.stagger + 1)), 1),
                           "inputs_note": "the %d sequences of a GPU replay %d base renderings at %d frame offsets: every distinct input frame of a step is read by ~%.0f sequences "
@@ -873,6 +911,7 @@ def main():
                "host_input_arrays_gb": inputs_host_gb}
         print(json.dumps(out))
         sys.stdout.flush()
+        log("line printed")
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

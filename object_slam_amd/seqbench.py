@@ -309,6 +309,9 @@ def run_rank(wl, make_system, rank, world, seqs_per_rank, handles, steps, warmup
     poses = [[] for _ in range(handles)] if collect_poses else [None] * handles
     calls = [_prepare(systems[h], wl, inp, groups[h], n_frames + post_frames) for h in range(handles)]
 
+    if progress is not None:
+        progress("inputs %s, %d handles created, %d steps marshalled" % ("in HBM" if on_device else "on the host", handles, n_frames + post_frames))
+
     def sync():
         if on_device:
             torch.cuda.synchronize()
@@ -342,6 +345,9 @@ def run_rank(wl, make_system, rank, world, seqs_per_rank, handles, steps, warmup
     if multi:
         dist.barrier()
     elapsed = time.perf_counter() - tstart
+    if progress is not None:
+        progress("%d steps timed: %.3f s" % (steps, elapsed))
+    last_outputs = [(sy.Tcw.copy(), sy.state.copy()) for sy in systems]   # what the last timed step returned to its caller, per handle (bench.py --dump-outputs)
     win1 = _window_totals(systems, per)
     frames = seqs_per_rank * steps
     total_frames, max_elapsed = aggregate_stats(elapsed, frames, device=device if (on_device and coll_on_device) else None)
@@ -363,7 +369,8 @@ def run_rank(wl, make_system, rank, world, seqs_per_rank, handles, steps, warmup
                "keyframes": int(records[:, 4].sum()), "local_bas": int(records[:, 5].sum()), "lost_frames": int(records[:, 6].sum()),
                "ate_rmse_m": float(np.nanmean(records[:, 7])), "map_violations": int(records[:, 8].sum()), "semantic_edges": int(records[:, 9].sum()),
                "preroll_steps": preroll, "preroll_s": t_pre, "lba_windows_timed": window_stats(win1, win0), "lba_windows_all": window_stats(win1, np.zeros(6, np.int64))}
-    extra = {"inputs": inp, "groups": groups, "poses": poses, "calls": calls, "phase": phase, "sync": sync, "n_frames": n_frames, "per": per}
+    extra = {"inputs": inp, "groups": groups, "poses": poses, "calls": calls, "phase": phase, "sync": sync, "n_frames": n_frames, "per": per,
+             "last_outputs": last_outputs}
     if post is not None:
         extra["post"] = post(dict(extra, systems=systems, wl=wl, window_totals=lambda: _window_totals(systems, per)))
     return summary, records, systems, extra

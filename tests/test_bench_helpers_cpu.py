@@ -49,3 +49,18 @@ def test_eight_ranks_on_a_two_socket_node_get_whole_cores_of_one_socket_each():
         assert phys == list(range(16 * r, 16 * r + 16))         # contiguous
         assert len({c // 64 for c in phys}) == 1                # one socket
     assert len(bench.rank_cpu_set(cores, 3, 8, per_rank_cores=8)) == 16
+
+
+def test_dump_outputs_writes_the_last_step_of_every_handle_as_float32(tmp_path):
+    """--dump-outputs: the poses and states the last timed step returned, handles concatenated in order, float32 .npy files a second build's dump is compared with."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    last = [(rng.standard_normal((s, 4, 4)).astype(np.float32), rng.integers(0, 4, s).astype(np.int32)) for s in (3, 2)]
+    bench.dump_outputs(str(tmp_path / "d"), last)
+    T, st = np.load(tmp_path / "d" / "Tcw.npy"), np.load(tmp_path / "d" / "state.npy")
+    assert T.dtype == np.float32 and T.shape == (5, 4, 4) and np.array_equal(T[3:], last[1][0])
+    assert st.dtype == np.float32 and np.array_equal(st, np.concatenate([last[0][1], last[1][1]]))
+    bench.dump_outputs(str(tmp_path / "d"), last, rank=1, world=2)
+    assert sorted(os.listdir(tmp_path / "d")) == ["Tcw.npy", "Tcw_rank1.npy", "state.npy", "state_rank1.npy"]

@@ -145,9 +145,7 @@ def test_tum_layout_round_trip_and_settings(tmp_path):
     px = np.array([[[200, 100, 50]]], np.uint8)
     assert io.to_gray(px, True)[0, 0] == (200 * 4899 + 100 * 9617 + 50 * 1868 + 8192) >> 14 == 124
     assert io.to_gray(px, False)[0, 0] == (50 * 4899 + 100 * 9617 + 200 * 1868 + 8192) >> 14 == 96
-    # the reference's own settings file parses (it is data of the reference tree, read in place when present)
-    ref = "/root/reference/Examples/RGB-D/TUM2.yaml"
-    if os.path.exists(ref):
-        r = io.load_settings(ref)
-        assert r["Camera.fx"] == 520.908620 and r["Camera.k3"] == 0.917205 and r["ORBextractor.nFeatures"] == 1000 and r["DepthMapFactor"] == 5208.0
-        assert io.config_from_settings(r).ndist == 5
+    # the reference's own settings file parses (tests/golden/TUM2.yaml: a copy of its Examples/RGB-D/TUM2.yaml, settings only)
+    r = io.load_settings(os.path.join(G, "TUM2.yaml"))
+    assert r["Camera.fx"] == 520.908620 and r["Camera.k3"] == 0.917205 and r["ORBextractor.nFeatures"] == 1000 and r["DepthMapFactor"] == 5208.0
+    assert io.config_from_settings(r).ndist == 5

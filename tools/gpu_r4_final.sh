@@ -6,7 +6,7 @@ mkdir -p $O
 timeout -k 10 1100 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1 || (tail -40 $O/pytest_gpu.log; exit 1)
 tail -3 $O/pytest_gpu.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-( time python bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/time.txt || (tail -20 $O/bench_default.err; exit 1)
+( time python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/time.txt || (tail -20 $O/bench_default.err; exit 1)
 cat $O/time.txt
 python - <<'PY'
 import json
