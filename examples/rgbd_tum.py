@@ -6,7 +6,8 @@
 Reads the settings YAML (Examples/RGB-D/TUM2.yaml keys), the association file (LoadImages, :144-169), RGB / depth PNGs and — when the settings name a DataSetPath —
 the semantic directory `<DataSetPath>/semantic/<timestamp>/` (src/Tracking.cc:70-74, src/Semantic.cc:57-96); runs ONE sequence through the HIP driver (oslam_slam);
 prints the median / mean tracking time like the reference (:126-134) and writes CameraTrajectory.txt and KeyFrameTrajectory.txt (src/System.cc:378-470).
-path_to_vocabulary is accepted for argv compatibility: the DBoW2 vocabulary is not used (substitute node assignment)."""
+path_to_vocabulary: the DBoW2 text vocabulary (ORBvoc.txt), loaded like src/System.cc:65-76 and handed to the driver; a file that does not parse ends the run
+with exit code 1.  A path that does not exist is not an error here: the run says so in one line and uses the substitute vocabulary of include/oslam_slam.h."""
 import argparse
 import os
 import sys
@@ -16,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
-from object_slam_amd import io, slam  # noqa: E402
+from object_slam_amd import io, slam, vocabulary  # noqa: E402
 
 
 def main(argv=None):
@@ -35,7 +36,11 @@ def main(argv=None):
         return 1
     st = io.load_settings(a.settings)
     cfg = io.config_from_settings(st, 1, slam.RGBD, device=a.device)
-    sysm = slam.System(cfg)
+    try:
+        voc = vocabulary.load_like_system(a.vocabulary)   # System.cc:65-76; a path that does not exist: the substitute vocabulary, and a line that says so
+    except SystemExit as e:
+        return e.code
+    sysm = slam.System(cfg, vocabulary=voc)
     sem_path = (str(st["DataSetPath"]) + "/semantic/") if "DataSetPath" in st else None
     sem_th = float(st.get("MinSemanticConfidence", 0.5))
     rgb_order = bool(int(st.get("Camera.RGB", 1)))

@@ -4,7 +4,8 @@
     python examples/stereo_kitti.py path_to_vocabulary path_to_settings path_to_sequence [--out DIR] [--no-sleep]
 
 times.txt + image_0 / image_1 (LoadImages, :127-158), settings as Examples/Stereo/KITTI00-02.yaml, optional `<DataSetPath>/semantic/<%06d>/` (src/Semantic.cc:14-57);
-ONE sequence through the HIP driver; median / mean tracking time; CameraTrajectory.txt in the KITTI format (src/System.cc:472-528)."""
+ONE sequence through the HIP driver; median / mean tracking time; CameraTrajectory.txt in the KITTI format (src/System.cc:472-528).
+path_to_vocabulary as in examples/rgbd_tum.py: loaded and used when the file exists, the substitute vocabulary (and a line that says so) when it does not."""
 import argparse
 import os
 import sys
@@ -14,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
-from object_slam_amd import io, slam  # noqa: E402
+from object_slam_amd import io, slam, vocabulary  # noqa: E402
 
 
 def main(argv=None):
@@ -27,7 +28,11 @@ def main(argv=None):
     left, right, stamps = io.load_kitti_sequence(a.sequence)
     st = io.load_settings(a.settings)
     cfg = io.config_from_settings(st, 1, slam.STEREO, device=a.device)
-    sysm = slam.System(cfg)
+    try:
+        voc = vocabulary.load_like_system(a.vocabulary)   # System.cc:65-76; a path that does not exist: the substitute vocabulary, and a line that says so
+    except SystemExit as e:
+        return e.code
+    sysm = slam.System(cfg, vocabulary=voc)
     sem_path = (str(st["DataSetPath"]) + "/semantic/") if "DataSetPath" in st else None
     sem_th = float(st.get("MinSemanticConfidence", 0.5))
     rgb_order = bool(int(st.get("Camera.RGB", 1)))

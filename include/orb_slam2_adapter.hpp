@@ -2,7 +2,7 @@
 // ORB_SLAM2::ORBextractor (include/ORBextractor.h:45-110), ORB_SLAM2::ORBmatcher (include/ORBmatcher.h:41-83: both projection searches,
 // SearchByBoW, SearchForTriangulation, Fuse, DescriptorDistance), Frame::ComputeStereoMatches (src/Frame.cc:706), ORB_SLAM2::Optimizer
 // (include/Optimizer.h:38-46: PoseOptimization, LocalBundleAdjustment, BundleAdjustment) and ObjectOptimizer::PoseOptimization2
-// (include/ObjectOptimizer.h:23).  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
+// (include/ObjectOptimizer.h:23), and ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: loadFromTextFile, transform, score).  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
 // "view" of exactly the members it reads and writes (the gather loops are in INTEGRATION.md).  tests/adapter_program.cc uses nothing but
 // these classes; tests/test_adapter_gpu.py builds it, runs it and compares its outputs with the ctypes path.
 //
@@ -13,6 +13,7 @@
 #pragma once
 #include <cstdint>
 #include <cstring>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -198,7 +199,7 @@ public:
         return nf;
     }
 
-    // DBoW2::FeatureVector of one side (node id -> keypoint indices), flattened as oslam_hip.h describes: the vocabulary is not in the reference tree
+    // DBoW2::FeatureVector of one side (node id -> keypoint indices), flattened as oslam_hip.h describes (ORBVocabulary::flatten below builds it)
     struct FeatureVector {
         std::vector<int32_t> q_idx; std::vector<uint32_t> q_node;               // side 1: (node ascending, index order)
         std::vector<uint32_t> nodes; std::vector<int32_t> start, items;        // side 2: CSR over the sorted unique node ids
@@ -245,6 +246,81 @@ private:
     void ensure_bow() { if (!bow_) oslam::throw_on(oslam_bow_create(&bow_, 2400, 0)); }
     oslam_matcher_t* h_ = nullptr;
     oslam_bow_t* bow_ = nullptr;
+};
+
+}  // namespace ORB_SLAM2
+
+namespace DBoW2 {
+typedef std::map<unsigned, double> BowVector;                      // word id -> value (DBoW2/BowVector.h)
+typedef std::map<unsigned, std::vector<unsigned>> FeatureVector;   // node id -> feature indices, ascending (DBoW2/FeatureVector.h)
+}  // namespace DBoW2
+
+namespace ORB_SLAM2 {
+
+// typedef DBoW2::TemplatedVocabulary<DBoW2::FORB::TDescriptor, DBoW2::FORB> ORBVocabulary (include/ORBVocabulary.h): the three members the
+// reference calls — loadFromTextFile (src/System.cc:68), transform(desc, BowVector, FeatureVector, levelsup) (src/Frame.cc:640,
+// src/KeyFrame.cc:66, src/ObjectTypes.cc:30) and score — over the oslam_voc_* functions of oslam_hip.h (see there for the format, the algorithms
+// and the one normalisation).  transform runs the gfx950 kernel; only L1_NORM vocabularies (the reference's ORBvoc.txt) are scored.
+class ORBVocabulary {
+public:
+    ORBVocabulary() {}
+    ~ORBVocabulary() { oslam_voc_destroy(h_); }
+    ORBVocabulary(const ORBVocabulary&) = delete;
+    ORBVocabulary& operator=(const ORBVocabulary&) = delete;
+
+    // false when the file cannot be read or does not parse (oslam_last_error() says which line)
+    bool loadFromTextFile(const std::string& filename) {
+        oslam_voc_destroy(h_);
+        h_ = nullptr;
+        return oslam_voc_load_text(&h_, filename.c_str()) == OSLAM_OK;
+    }
+    bool empty() const { return !h_; }
+    const oslam_voc_t* handle() const { return h_; }   // for oslam_slam_set_vocabulary
+
+    // void transform(const std::vector<TDescriptor>& features, BowVector &v, FeatureVector &fv, int levelsup) const; descriptors N x 32 row-major
+    // (the reference converts mDescriptors with Converter::toDescriptorVector first: the same bytes)
+    void transform(const std::vector<uint8_t>& descriptors, DBoW2::BowVector& v, DBoW2::FeatureVector& fv, int levelsup) const {
+        v.clear();
+        fv.clear();
+        const int n = (int)(descriptors.size() / 32);
+        if (n == 0) return;
+        std::vector<uint32_t> word(n), node(n), bow_ids(n), fv_nodes(n);
+        std::vector<double> weight(n), bow_vals(n);
+        std::vector<int32_t> fv_start(n + 1), fv_items(n);
+        int32_t nb = 0, nf = 0;
+        oslam::throw_on(oslam_voc_transform(h_, descriptors.data(), n, levelsup, word.data(), node.data(), weight.data()));
+        oslam::throw_on(oslam_voc_vectors(h_, n, word.data(), node.data(), weight.data(), bow_ids.data(), bow_vals.data(), &nb, fv_nodes.data(), fv_start.data(),
+                                          fv_items.data(), &nf));
+        for (int j = 0; j < nb; j++) v[bow_ids[j]] = bow_vals[j];
+        for (int r = 0; r < nf; r++) fv[fv_nodes[r]].assign(fv_items.begin() + fv_start[r], fv_items.begin() + fv_start[r + 1]);
+    }
+
+    // double score(const BowVector &a, const BowVector &b) const
+    double score(const DBoW2::BowVector& a, const DBoW2::BowVector& b) const {
+        std::vector<uint32_t> ia, ib;
+        std::vector<double> va, vb;
+        for (const auto& e : a) { ia.push_back(e.first); va.push_back(e.second); }
+        for (const auto& e : b) { ib.push_back(e.first); vb.push_back(e.second); }
+        int rc = OSLAM_OK;
+        const double s = oslam_voc_score(h_, (int)ia.size(), ia.data(), va.data(), (int)ib.size(), ib.data(), vb.data(), &rc);
+        oslam::throw_on(rc);
+        return s;
+    }
+
+    // The flat views ORBmatcher::SearchByBoW / SearchForTriangulation take, from a DBoW2::FeatureVector (std::map order = node ascending)
+    static ORBmatcher::FeatureVector flatten(const DBoW2::FeatureVector& fv) {
+        ORBmatcher::FeatureVector out;
+        for (const auto& e : fv) {
+            out.nodes.push_back(e.first);
+            out.start.push_back((int32_t)out.items.size());
+            for (unsigned i : e.second) { out.items.push_back((int32_t)i); out.q_idx.push_back((int32_t)i); out.q_node.push_back(e.first); }
+        }
+        out.start.push_back((int32_t)out.items.size());
+        return out;
+    }
+
+private:
+    oslam_voc_t* h_ = nullptr;
 };
 
 // void Frame::ComputeStereoMatches() (src/Frame.cc:706-880): reads the two extractors' pyramids (mvImagePyramid) where they are, in HBM

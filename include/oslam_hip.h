@@ -225,8 +225,8 @@ int oslam_match_debug_get_queries(oslam_matcher_t* h, int b, int q_stride, int n
 
 /* ------------------------------------------------------------------------------------------
  * BoW-guided matchers: ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) (src/ORBmatcher.cc:159-288)
- * and ORBmatcher::SearchForTriangulation (:657-823).  DBoW2 and its vocabulary are not in the reference tree:
- * the DBoW2::FeatureVector of each side (node id -> keypoint indices) is an INPUT.  Side 1 is the flat list the
+ * and ORBmatcher::SearchForTriangulation (:657-823).  The DBoW2::FeatureVector of each side (node id -> keypoint indices) is an INPUT
+ * (oslam_voc_transform_device + oslam_voc_vectors below build it from a loaded vocabulary).  Side 1 is the flat list the
  * reference iterates (std::map order: node ascending, indices in vector order); side 2 is CSR over its sorted,
  * unique node ids.  Host pointers, one pair per call.
  * SearchByBoW: side1.flag[i] = pKF map point exists && !isBad(); match_f[k] = keyframe keypoint whose map point is
@@ -631,6 +631,56 @@ int oslam_frame_stereo_from_rgbd_batch_ptrs_u16_device(const oslam_keypoint_t* d
  * d_out[i][k] = 11 + 10 b1 + b2 for descriptor k of array d_desc_ptrs[i] (d_counts[i] of them, at most `stride`), first minimum on ties. */
 int oslam_bow_nodes_device(const uint8_t* const* d_desc_ptrs, const int32_t* d_counts, int n, int stride, const uint64_t* d_top, const uint64_t* d_sub,
                            uint32_t* d_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * ORB vocabulary: the DBoW2 tree the reference loads with mpVocabulary->loadFromTextFile (src/System.cc:64-76) and applies with
+ * mpORBvocabulary->transform(desc, mBowVec, mFeatVec, 4) (src/Frame.cc:635-642, src/KeyFrame.cc:59-68, src/ObjectTypes.cc:27-32).
+ * DBoW2 is not in the reference tree; format and algorithms are restated from its published TemplatedVocabulary (ORB-SLAM2 fork,
+ * FORB: 32-byte descriptors, Hamming distance).  Parity with DBoW2 itself is not pinned by a test.
+ * Text format: line 1 `k L scoring weighting` (0 <= k <= 20, 1 <= L <= 10, scoring 0 L1_NORM 1 L2_NORM 2 CHI_SQUARE 3 KL 4 BHATTACHARYYA
+ *   5 DOT_PRODUCT, weighting 0 TF_IDF 1 TF 2 IDF 3 BINARY); node 0 is the root and has no line; file line i + 1 is node id i:
+ *   `parent_id is_leaf b0 .. b31 weight`, appended to the children of parent_id in file order; a line with is_leaf > 0 is a word whose id is the
+ *   number of leaf lines before it.  Trees may be irregular.  Refused with OSLAM_E_INVALID and a message that names the file line: a short or
+ *   over-long line, parent_id that is not an earlier node, a byte outside 0..255, an inner node without children, a leaf with children, more
+ *   than k children, no node line.  Blank lines at the end of the file are ignored.
+ * transform of one descriptor (levelsup): from the root, repeatedly the child at the smallest Hamming distance — children in file order, first
+ *   minimum — until a leaf: word id and weight of that leaf; node id = the node passed at depth L - levelsup (0, the root, when that is <= 0).
+ *   Normalisation: when the leaf lies above that depth DBoW2 leaves the node id unset; here it is the leaf's own node id.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct oslam_voc oslam_voc_t;
+/* Host only.  oslam_voc_create takes the same tree from arrays: entry j describes node id j + 1 (n_nodes excludes the root). */
+int oslam_voc_load_text(oslam_voc_t** out, const char* path);
+int oslam_voc_create(oslam_voc_t** out, int k, int L, int scoring, int weighting, int n_nodes, const int32_t* parent, const uint8_t* is_leaf,
+                     const uint8_t* desc /* [n_nodes][32] */, const double* weight);
+void oslam_voc_destroy(oslam_voc_t* voc);
+/* out = k, L, scoring, weighting, nodes (without the root), words, depth of the deepest node, most children of one node */
+int oslam_voc_info(const oslam_voc_t* voc, int32_t out[8]);
+/* The nodes as they were read, by node id - 1 (any pointer may be NULL); word_id = -1 for inner nodes. */
+int oslam_voc_get_nodes(const oslam_voc_t* voc, int32_t* parent, uint8_t* is_leaf, uint8_t* desc, double* weight, int32_t* word_id);
+/* Copies the tree to `device` (centres of one node's children contiguous, breadth first).  oslam_voc_transform_device does it at its first call on a
+ * device otherwise — that call then allocates and synchronises. */
+int oslam_voc_upload(const oslam_voc_t* voc, int device);
+/* transform of the descriptors of n arrays on the current device, in the batch layout of oslam_bow_nodes_device: array i = d_desc_ptrs[i] with
+ * d_counts[i] <= stride descriptors; outputs [n][stride] (entries beyond a count are not written; any output may be NULL, not all).  A gfx950
+ * kernel: 16 lanes per descriptor, one child centre per lane, DPP row minimum, top levels of the tree in LDS. */
+int oslam_voc_transform_device(const oslam_voc_t* voc, const uint8_t* const* d_desc_ptrs, const int32_t* d_counts, int n, int stride, int levelsup,
+                               uint32_t* d_word, uint32_t* d_node, double* d_weight, void* stream);
+/* The same for ONE host array desc [n][32] with host outputs (any may be NULL): upload, the kernel above, download, synchronous.  Calls on one vocabulary
+ * are serialised. */
+int oslam_voc_transform(const oslam_voc_t* voc, const uint8_t* desc, int n, int levelsup, uint32_t* word, uint32_t* node, double* weight);
+/* The same descent on the host for n descriptors desc [n][32].  Not a fallback of the call above (which fails without a device): it is what the
+ * tracking driver uses over an operator table that has no device, and for the rare frames whose Frame::ComputeBoW runs on the host. */
+int oslam_voc_transform_host(const oslam_voc_t* voc, const uint8_t* desc, int n, int levelsup, uint32_t* word, uint32_t* node, double* weight);
+/* transform(features, BowVector&, FeatureVector&, levelsup) from the per-feature outputs of one feature set, features in index order.  A feature
+ * whose word weight is <= 0 enters neither vector.  BowVector (word id ascending, capacity n): TF_IDF and TF add the weights of a word, IDF and
+ * BINARY keep the first; then L1-normalised for scoring 0, L2-normalised for scoring 1; for the other scorings TF_IDF / TF values are divided by the
+ * number of entries.  FeatureVector as CSR over its ascending node ids (fv_nodes [n], fv_start [n + 1], fv_items [n]): the form of
+ * oslam_bow_side2_t; fv_items is also q_idx of oslam_bow_side1_t, with q_node[j] = fv_nodes[r] for fv_start[r] <= j < fv_start[r + 1]. */
+int oslam_voc_vectors(const oslam_voc_t* voc, int n, const uint32_t* word, const uint32_t* node, const double* weight, uint32_t* bow_ids, double* bow_vals,
+                      int32_t* n_bow, uint32_t* fv_nodes, int32_t* fv_start, int32_t* fv_items, int32_t* n_fv);
+/* score(a, b) of two BowVectors for L1_NORM, the scoring of the reference's vocabulary: -0.5 * sum over common words of (|a - b| - |a| - |b|).
+ * The other five scorings are not implemented: *rc = OSLAM_E_INVALID with a message (rc may be NULL), return value 0. */
+double oslam_voc_score(const oslam_voc_t* voc, int na, const uint32_t* ids_a, const double* vals_a, int nb, const uint32_t* ids_b, const double* vals_b, int* rc);
 
 #ifdef __cplusplus
 }

@@ -23,9 +23,14 @@
  *                     the trajectory getters call it.
  *   - containers ordered by pointer value (std::map<KeyFrame*,..>, std::set<KeyFrame*>, pair<int,KeyFrame*> sorts)
  *     are ordered by keyframe id;
- *   - DBoW2 and its vocabulary are not in the reference tree: ComputeBoW uses a substitute vocabulary (k = 10, two
- *     levels of seeded random 256-bit words, nearest child by Hamming distance) that yields the same FeatureVector
- *     structure (node id at the 4th level from the leaves -> keypoint indices);
+ *   - DBoW2 is not in the reference tree.  With a vocabulary set (oslam_slam_set_vocabulary: the tree System::System loads from ORBvoc.txt,
+ *     src/System.cc:64-76) ComputeBoW is mpORBvocabulary->transform(.., 4) of oslam_hip.h: the FeatureVector node of a keypoint is the node its
+ *     descriptor passes 4 levels above the leaves.  Keyframes get theirs from the operator table (voc_nodes_keyed: the device kernel, from the
+ *     resident descriptors); frames on the TrackReferenceKeyFrame path (Frame::ComputeBoW, src/Tracking.cc:841) are rare and use the host descent,
+ *     as does every ComputeBoW over a table without voc_nodes_keyed.  The driver keeps node ids only: a keypoint whose word has weight 0 stays in
+ *     its FeatureVector (DBoW2 drops it; trained idf weights are positive), and no BowVector is built (its consumers, KeyFrameDatabase and the loop
+ *     closer, are out of scope).  Without a vocabulary ComputeBoW uses a substitute (k = 10, two levels of seeded random 256-bit words, nearest
+ *     child by Hamming distance) that yields the same FeatureVector structure, with 100 nodes;
  *   - out of scope: Relocalization (a sequence lost with more than 5 keyframes stays LOST; with <= 5 the
  *     system resets like src/Tracking.cc:553-561 and re-initialises on the next frame), loop closing, the object layer
  *     (ObjectMatcher, Object3D outlier rejection, ObjectMapRegularization), the viewer.
@@ -371,13 +376,27 @@ typedef struct oslam_slam_ops {
     int (*frame_descriptors)(void* ctx, int n, const int32_t* slots, const int32_t* counts, uint8_t* const* out);
     int (*mp_update_keyed_async)(void* ctx, oslam_job_mp_update_t* job, const int32_t* obs_key);
     int (*mp_update_collect)(void* ctx);
+    /* optional, with register_keyframes: the sibling of bow_nodes_keyed for a loaded vocabulary (oslam_slam_set_vocabulary) — the node id, `levelsup` levels
+     * above the leaves, of every descriptor of the registered keyframes (slots[i], kf_ids[i]), read from the resident copy: counts[i] descriptors ->
+     * out[i][0 .. counts[i]).  NULL (tables without a device): the driver descends on the host (oslam_voc_transform_host). */
+    int (*voc_nodes_keyed)(void* ctx, const oslam_voc_t* voc, int levelsup, int n, const int32_t* slots, const int32_t* kf_ids, const int32_t* counts,
+                           uint32_t* const* out);
 } oslam_slam_ops_t;
 
-/* System::System for S sequences of one camera model (src/System.cc:33-120, minus vocabulary / viewer / loop closer). */
+/* System::System for S sequences of one camera model (src/System.cc:33-120, minus viewer / loop closer; the vocabulary: oslam_slam_set_vocabulary). */
 int oslam_slam_create(oslam_slam_t** out, const oslam_slam_config_t* cfg);
 /* Same driver over a caller-supplied operator table (ownership of ops->ctx passes to the handle). Test seam. */
 int oslam_slam_create_with_ops(oslam_slam_t** out, const oslam_slam_config_t* cfg, const oslam_slam_ops_t* ops);
 void oslam_slam_destroy(oslam_slam_t* h);
+/* The ORB vocabulary of the system (mpVocabulary, src/System.cc:64-76), shared by all sequences of the handle.  Allowed only before the first frame
+ * (OSLAM_E_INVALID afterwards).  The vocabulary is borrowed: it must outlive the handle.  NULL, or never calling this, keeps the substitute vocabulary
+ * described above, with results bit for bit those of a handle that never heard of vocabularies. */
+int oslam_slam_set_vocabulary(oslam_slam_t* h, const oslam_voc_t* voc);
+/* KeyFrame::ComputeBoW of the new keyframes through the operator table (bow_nodes_keyed / voc_nodes_keyed) since creation: out[0] = wall seconds of
+ * those calls (upload of the pointer table, kernel, download, copy-out), out[1] = keyframes, out[2] = descriptors.  Zeros over a table without either. */
+int oslam_slam_bow_seconds(oslam_slam_t* h, double out[3]);
+/* Test hook: the FeatureVector node of every keypoint of keyframe `kf` of sequence `seq` as ComputeBoW left it (*n_out = 0: not computed yet). */
+int oslam_slam_debug_bow_nodes(oslam_slam_t* h, int seq, int kf, int cap, uint32_t* out, int32_t* n_out);
 
 /* System::TrackRGBD (include/System.h:75) for every sequence: gray[s] / depth[s] = next frame of sequence s (depth in metres,
  * i.e. after the DepthMapFactor scaling of src/Tracking.cc:262).  Tcw_out [S][16] = mCurrentFrame.mTcw (zeros while the sequence has no

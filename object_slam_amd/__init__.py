@@ -9,3 +9,4 @@ from .matcher import BowMatcher, ORBmatcher, QUERY_DTYPE, StereoMatcher, feature
 from .frame import FrameOps  # noqa: F401
 from .mappoint import MapPointBatch  # noqa: F401
 from .optimizer import LocalBundleAdjuster, PoseOptimizer  # noqa: F401
+from .vocabulary import Vocabulary  # noqa: F401

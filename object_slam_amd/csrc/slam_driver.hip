@@ -211,6 +211,9 @@ struct Ctx {
     int maxFrames, minFrames;
     bool stereo = false;
     Vocab voc;
+    const oslam_voc_t* realVoc = nullptr;   // oslam_slam_set_vocabulary: the loaded DBoW2 vocabulary (borrowed); NULL = the substitute above
+    bool started = false;                   // a frame was tracked: the vocabulary can no longer change
+    double bowSec = 0; long long bowKFs = 0, bowDesc = 0;   // KeyFrame::ComputeBoW through the operator table: wall seconds, keyframes, descriptors (oslam_slam_bow_seconds)
     std::vector<std::unique_ptr<Seq>> seq;
     std::unique_ptr<Pool> pool;
     double sec[16] = {0};
@@ -254,6 +257,10 @@ namespace oslam_drv {
 static void compute_bow(const Ctx& c, int N, const uint8_t* desc, std::vector<uint32_t>& out) {
     if (!out.empty()) return;   // Frame::ComputeBoW / KeyFrame::ComputeBoW: only once
     out.resize(N);
+    if (c.realVoc) {   // mpORBvocabulary->transform(mDescriptors, mBowVec, mFeatVec, 4): the node 4 levels above the leaves, host descent
+        (void)oslam_voc_transform_host(c.realVoc, desc, N, 4, nullptr, out.data(), nullptr);
+        return;
+    }
     for (int i = 0; i < N; i++) out[i] = c.voc.node(desc + (size_t)i * 32);
 }
 
@@ -2172,6 +2179,7 @@ static int track_step(Ctx& c, const uint8_t* const* gray, const uint8_t* const* 
                       int on_device, const double* stamps, const oslam_slam_objects_t* objs, int mask_stride, float* Tcw_out, int32_t* state_out,
                       const uint16_t* const* depth16 = nullptr, float depth_factor = 1.f) {
     const int S = c.S;
+    c.started = true;
     oslam_drv::ShardScope shard_scope(c.shard);   // library code below the operator table (local-BA preparation, BoW views) uses this handle's worker set
     AccountScope acct_scope(&c.acct);   // the workers bill the tasks of this thread's batches (driver and operator table) to this handle; unbound again on every return
     c.acct.worker_ns.store(0, std::memory_order_relaxed);
@@ -2419,7 +2427,21 @@ static int track_step(Ctx& c, const uint8_t* const* gray, const uint8_t* const* 
                 if ((rc = c.ops.keyframe_descriptors(c.ops.ctx, (int)rs.size(), rs.data(), cnt.data(), outd.data()))) return rc;
             }
         }
-        if (!rs.empty() && c.ops.bow_nodes_keyed) {   // KeyFrame::ComputeBoW of the new keyframes from their resident descriptors (ProcessNewKeyFrame finds it done)
+        const auto bow_t0 = std::chrono::steady_clock::now();
+        bool bow_op = false;
+        if (!rs.empty() && c.realVoc) {   // KeyFrame::ComputeBoW with the loaded vocabulary; a table without voc_nodes_keyed leaves it to compute_bow (host descent)
+            if (c.ops.voc_nodes_keyed) {
+                std::vector<int32_t> cnt(rs.size());
+                std::vector<uint32_t*> outp(rs.size());
+                for (size_t q = 0; q < rs.size(); q++) {
+                    KeyFrm& k = c.seq[rs[q]]->map.kfs[rk[q]];
+                    k.bowNode.resize(k.N);
+                    cnt[q] = k.N; outp[q] = k.bowNode.data();
+                }
+                if ((rc = c.ops.voc_nodes_keyed(c.ops.ctx, c.realVoc, 4, (int)rs.size(), rs.data(), rk.data(), cnt.data(), outp.data()))) return rc;
+                bow_op = true;
+            }
+        } else if (!rs.empty() && c.ops.bow_nodes_keyed) {   // KeyFrame::ComputeBoW of the new keyframes from their resident descriptors (ProcessNewKeyFrame finds it done)
             std::vector<int32_t> cnt(rs.size());
             std::vector<uint32_t*> outp(rs.size());
             for (size_t q = 0; q < rs.size(); q++) {
@@ -2428,6 +2450,12 @@ static int track_step(Ctx& c, const uint8_t* const* gray, const uint8_t* const* 
                 cnt[q] = k.N; outp[q] = k.bowNode.data();
             }
             if ((rc = c.ops.bow_nodes_keyed(c.ops.ctx, (int)rs.size(), rs.data(), rk.data(), &c.voc.top[0][0], &c.voc.sub[0][0][0], cnt.data(), outp.data()))) return rc;
+            bow_op = true;
+        }
+        if (bow_op) {
+            c.bowSec += std::chrono::duration<double>(std::chrono::steady_clock::now() - bow_t0).count();
+            c.bowKFs += (long long)rs.size();
+            for (size_t q = 0; q < rs.size(); q++) c.bowDesc += c.seq[rs[q]]->map.kfs[rk[q]].N;
         }
     }
     if ((rc = upd.run(c, true, true))) return rc;   // descriptors / normals of the points created this step
@@ -2573,6 +2601,28 @@ int oslam_slam_track_rgbd_raw16(oslam_slam_t* h, const uint8_t* const* gray, int
     if (objs && mask_stride != 0 && mask_stride < h->c.cfg.width) { oslam::set_error("oslam_slam_track_rgbd_raw16: mask_stride must be 0 (bitmaps) or >= width"); return OSLAM_E_INVALID; }
     if (objs && mask_stride == 0 && !on_device) { oslam::set_error("oslam_slam_track_rgbd_raw16: one-bit masks must be device-accessible (on_device != 0)"); return OSLAM_E_INVALID; }
     return track_step(h->c, gray, nullptr, gray_stride, nullptr, depth_pitch, on_device, timestamps, objs, mask_stride, Tcw_out, state_out, depth16, depth_factor);
+}
+
+int oslam_slam_set_vocabulary(oslam_slam_t* h, const oslam_voc_t* voc) {
+    if (!h) { oslam::set_error("oslam_slam_set_vocabulary: NULL handle"); return OSLAM_E_INVALID; }
+    if (h->c.started) { oslam::set_error("oslam_slam_set_vocabulary: only before the first frame"); return OSLAM_E_INVALID; }
+    h->c.realVoc = voc;
+    return OSLAM_OK;
+}
+
+int oslam_slam_bow_seconds(oslam_slam_t* h, double out[3]) {
+    if (!h || !out) { oslam::set_error("oslam_slam_bow_seconds: bad argument"); return OSLAM_E_INVALID; }
+    out[0] = h->c.bowSec; out[1] = (double)h->c.bowKFs; out[2] = (double)h->c.bowDesc;
+    return OSLAM_OK;
+}
+
+int oslam_slam_debug_bow_nodes(oslam_slam_t* h, int seq, int kf, int cap, uint32_t* out, int32_t* n_out) {
+    if (!h || seq < 0 || seq >= h->c.S || !n_out || kf < 0 || kf >= (int)h->c.seq[seq]->map.kfs.size()) { oslam::set_error("oslam_slam_debug_bow_nodes: bad argument"); return OSLAM_E_INVALID; }
+    const std::vector<uint32_t>& b = h->c.seq[seq]->map.kfs[kf].bowNode;
+    *n_out = (int32_t)b.size();
+    if ((int)b.size() > cap) { oslam::set_error("oslam_slam_debug_bow_nodes: cap too small"); return OSLAM_E_CAPACITY; }
+    if (!b.empty() && out) memcpy(out, b.data(), 4 * b.size());
+    return OSLAM_OK;
 }
 
 int oslam_slam_finish(oslam_slam_t* h) {

@@ -2058,6 +2058,37 @@ int h_bow_nodes_keyed(void* p, int n, const int32_t* slots, const int32_t* kf_id
     return OSLAM_OK;
 }
 
+// The same for a loaded vocabulary (oslam_slam_ops_t::voc_nodes_keyed): oslam_voc_transform_device over the resident descriptors, node ids only
+int h_voc_nodes_keyed(void* p, const oslam_voc_t* voc, int levelsup, int n, const int32_t* slots, const int32_t* kf_ids, const int32_t* counts, uint32_t* const* out) {
+    HipOps* o = (HipOps*)p;
+    OSLAM_HIP_CHECK(hipSetDevice(o->cfg.device));
+    if (n == 0) return OSLAM_OK;
+    const size_t cap = o->cap;
+    Layout L;
+    const size_t oPtr = L.take(8 * (size_t)n), oCnt = L.take(4 * (size_t)n);
+    const size_t in_bytes = L.off;
+    const size_t oOut = L.take(4 * cap * (size_t)n);
+    OPS_CHECK(o->ensure_up(L.off));
+    OPS_CHECK(o->ensure_dn(4 * cap * (size_t)n));
+    uint8_t* U = o->up_h;
+    for (int i = 0; i < n; i++) {
+        const int r = o->rec_lookup(slots[i], kf_ids[i]);
+        if (r < 0 || counts[i] < 0 || counts[i] > (int)cap) { oslam::set_error("voc_nodes: keyframe not resident / bad count"); return OSLAM_E_INVALID; }
+        ((const uint8_t**)(U + oPtr))[i] = o->rec_desc(r);
+        ((int32_t*)(U + oCnt))[i] = counts[i];
+    }
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up_d, U, in_bytes, hipMemcpyHostToDevice, o->strm));
+    uint8_t* Dv = o->up_d;
+    o->t_begin();
+    OPS_CHECK(oslam_voc_transform_device(voc, (const uint8_t* const*)(Dv + oPtr), (const int32_t*)(Dv + oCnt), n, (int)cap, levelsup, nullptr, (uint32_t*)(Dv + oOut), nullptr, o->strm));
+    o->t_end();
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h, Dv + oOut, 4 * cap * (size_t)n, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
+    o->t_collect(7, 1, 0);
+    o->pool->parallel_for(n, [&](int i) { memcpy(out[i], o->dn_h + 4 * cap * (size_t)i, 4 * (size_t)counts[i]); });
+    return OSLAM_OK;
+}
+
 int h_bow_keyed(void* p, int n, oslam_job_bow_t* jobs, const oslam_kf_key_t* keys) {
     HipOps* o = (HipOps*)p;
     OSLAM_HIP_CHECK(hipSetDevice(o->cfg.device));
@@ -2413,7 +2444,7 @@ int oslam_slam_make_hip_ops(const oslam_slam_config_t* cfg, oslam_slam_ops_t* op
     if (!getenv("OSLAM_SLAM_NO_WINDOW_UPDATES")) ops->mp_update_windows = h_mp_update_windows;   // (A/B: the MapPoint updates after a local BA through mp_update as before)
     if (!getenv("OSLAM_SLAM_NO_RESIDENT_KF") && !getenv("OSLAM_SLAM_NO_MIRROR")) { ops->map_journal = h_map_journal; ops->kf_culling_counts = h_kf_culling_counts; ops->kf_culling_collect = h_kf_culling_collect; if (o->mp_tab_on && !getenv("OSLAM_SLAM_FUSECUR_HOST")) ops->fuse_into_current = h_fuse_into_current; ops->local_points_list = h_local_points_list; }
     if (!getenv("OSLAM_SLAM_NO_RESIDENT_KF")) { ops->register_keyframes = h_register_keyframes; if (!getenv("OSLAM_SLAM_KEEP_CULLED_RECORDS")) ops->release_keyframes = h_release_keyframes; ops->bow_keyed = h_bow_keyed; ops->fuse_keyed = h_fuse_keyed; ops->mp_update_keyed = h_mp_update_keyed; if (!getenv("OSLAM_SLAM_EAGER_KEYS")) { o->lazy_keys = true; ops->keyframe_raw_keys = h_keyframe_raw_keys; if (!getenv("OSLAM_SLAM_EAGER_DESC")) { o->lazy_desc = true; ops->keyframe_descriptors = h_keyframe_descriptors; ops->frame_descriptors = h_frame_descriptors; } } ops->mp_update_keyed_async = h_mp_update_keyed_async; ops->mp_update_collect = h_mp_update_collect;
-        if (!getenv("OSLAM_SLAM_HOST_BOW_NODES")) ops->bow_nodes_keyed = h_bow_nodes_keyed;
+        if (!getenv("OSLAM_SLAM_HOST_BOW_NODES")) { ops->bow_nodes_keyed = h_bow_nodes_keyed; ops->voc_nodes_keyed = h_voc_nodes_keyed; }
         if (o->mp_tab_on && !getenv("OSLAM_SLAM_HOST_FUSE_QUERIES")) ops->fuse_points_keyed = h_fuse_points_keyed; }
     return OSLAM_OK;
 }

@@ -25,7 +25,9 @@ class SlamOps(C.Structure):
         "triangulate", "destroy", "frames_stereo", "object_kps", "pose_opt2", "register_keyframes", "bow_keyed", "fuse_keyed", "mp_update_keyed", "kernel_times", "bow_nodes_keyed", "resident_points", "fuse_points_keyed", "point_record", "frames_rgbd_raw16", "release_keyframes", "lba_submit", "lba_wait", "mp_update_windows",
         # round 5 (include/oslam_slam.h): the mirror of the observation graph, arrays on demand, deferred descriptor updates
         "map_journal", "kf_culling_counts", "kf_culling_collect", "fuse_into_current", "local_points_list", "keyframe_raw_keys", "keyframe_descriptors", "frame_descriptors",
-        "mp_update_keyed_async", "mp_update_collect")]
+        "mp_update_keyed_async", "mp_update_collect",
+        # the loaded DBoW2 vocabulary (oslam_slam_set_vocabulary)
+        "voc_nodes_keyed")]
 
 
 def _check_struct_sizes(L):
@@ -73,7 +75,8 @@ def make_config(width, height, n_sequences, cam=TUM2, dist=None, nFeatures=1000,
 
 
 class System:
-    def __init__(self, cfg, ops=None):
+    def __init__(self, cfg, ops=None, vocabulary=None):
+        """vocabulary: an object_slam_amd.vocabulary.Vocabulary (the reference's ORBvoc.txt, System.cc:64-76) or None = the substitute vocabulary."""
         self.L = lib()
         _check_struct_sizes(self.L)
         self.cfg = cfg
@@ -83,6 +86,9 @@ class System:
             check(self.L.oslam_slam_create(C.byref(self.h), C.byref(cfg)))
         else:
             check(self.L.oslam_slam_create_with_ops(C.byref(self.h), C.byref(cfg), C.byref(ops)))
+        self.vocabulary = vocabulary   # borrowed by the handle: kept alive here
+        if vocabulary is not None:
+            check(self.L.oslam_slam_set_vocabulary(self.h, vocabulary.h))
         self._gp = (C.c_void_p * self.S)()
         self._dp = (C.c_void_p * self.S)()
         self.Tcw = np.zeros((self.S, 4, 4), np.float32)
@@ -325,6 +331,23 @@ class System:
         a, b, bad = np.zeros(64, np.uint8), np.zeros(64, np.uint8), C.c_int32(0)
         check(self.L.oslam_slam_debug_point(self.h, seq, pid, ptr(a), ptr(b), C.byref(bad)))
         return a, b, bool(bad.value)
+
+    def set_vocabulary(self, vocabulary):
+        """oslam_slam_set_vocabulary: only before the first frame."""
+        check(self.L.oslam_slam_set_vocabulary(self.h, vocabulary.h if vocabulary is not None else None))
+        self.vocabulary = vocabulary
+
+    def bow_seconds(self):
+        """(wall seconds, keyframes, descriptors) of KeyFrame::ComputeBoW through the operator table since creation (include/oslam_slam.h)."""
+        out = np.zeros(3, np.float64)
+        check(self.L.oslam_slam_bow_seconds(self.h, ptr(out)))
+        return float(out[0]), int(out[1]), int(out[2])
+
+    def debug_bow_nodes(self, seq, kf, cap=4096):
+        """Test hook: FeatureVector node per keypoint of keyframe `kf` (empty: ComputeBoW has not run for it)."""
+        out, n = np.zeros(cap, np.uint32), C.c_int32(0)
+        check(self.L.oslam_slam_debug_bow_nodes(self.h, C.c_int(seq), C.c_int(kf), C.c_int(cap), ptr(out), C.byref(n)))
+        return out[:n.value].copy()
 
     def bad_keyframe_observations(self):
         """Observations in culled keyframes that ComputeDistinctiveDescriptors left out (include/oslam_slam.h)."""
