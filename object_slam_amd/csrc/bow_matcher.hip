@@ -198,27 +198,18 @@ using namespace oslam;
 struct oslam_bow {
     int device = 0, max_kps = 0;
     size_t lds = 0;
-    struct Buf { void* p = nullptr; size_t cap = 0; };
-    Buf q_idx1, q_node, keys1, desc1, ur1, flag1, keys2, desc2, ur2, mp2, nodes, start, items, out, qbest, nm;
-    uint8_t* st_h = nullptr; uint8_t* st_d = nullptr; size_t st_cap = 0;   // batch staging: pinned block mirrored on the device
+    DeviceBuffer q_idx1, q_node, keys1, desc1, ur1, flag1, keys2, desc2, ur2, mp2, nodes, start, items, out, qbest, nm;
+    StagePair st;   // batch staging: pinned block mirrored on the device
     hipStream_t strm = nullptr;   // the batch form runs on the handle's own non-blocking stream (created on first use) or on the stream given by bow_use_stream
     bool owns_strm = true;
     // device time of the batch kernel (bench.py's kernel-time groups): HIP events on `strm`
     int timing = 0; hipEvent_t ev0 = nullptr, ev1 = nullptr; double kern_ms = 0; long long kern_n = 0;
 };
 
-static int bow_ensure(oslam_bow::Buf& b, size_t bytes) {
-    if (b.p && bytes <= b.cap) return OSLAM_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = bytes + bytes / 2 + 256;
-    OSLAM_HIP_CHECK(hipMalloc(&b.p, b.cap));
-    return OSLAM_OK;
-}
-static int bow_up(oslam_bow::Buf& b, const void* src, size_t bytes) {
-    int rc = bow_ensure(b, bytes ? bytes : 4);
+static int bow_up(DeviceBuffer& b, const void* src, size_t bytes) {
+    int rc = b.grow(bytes ? bytes : 4, 256);
     if (rc) return rc;
-    if (bytes && src) OSLAM_HIP_CHECK(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
+    if (bytes && src) OSLAM_HIP_CHECK(hipMemcpy(b.ptr(), src, bytes, hipMemcpyHostToDevice));
     return OSLAM_OK;
 }
 
@@ -238,12 +229,6 @@ void oslam_bow_destroy(oslam_bow_t* h) {
     if (!h) return;
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
-    oslam_bow::Buf* bs[] = {&h->q_idx1, &h->q_node, &h->keys1, &h->desc1, &h->ur1, &h->flag1, &h->keys2, &h->desc2, &h->ur2, &h->mp2,
-                            &h->nodes, &h->start, &h->items, &h->out, &h->qbest, &h->nm};
-    for (auto* b : bs)
-        if (b->p) (void)hipFree(b->p);
-    if (h->st_h) (void)hipHostFree(h->st_h);
-    if (h->st_d) (void)hipFree(h->st_d);
     if (h->strm && h->owns_strm) (void)hipStreamDestroy(h->strm);
     delete h;
 }
@@ -296,15 +281,15 @@ static int bow_run(oslam_bow_t* h, int mode, const oslam_bow_side1_t* s1, const 
         (rc = bow_up(h->keys2, s2->keys, (size_t)s2->N * sizeof(oslam_keypoint_t))) || (rc = bow_up(h->desc2, s2->desc, (size_t)s2->N * 32)) ||
         (rc = bow_up(h->ur2, s2->uRight ? s2->uRight : negs.data(), (size_t)s2->N * 4)) || (rc = bow_up(h->mp2, s2->has_mp ? s2->has_mp : zeros.data(), (size_t)s2->N)) ||
         (rc = bow_up(h->nodes, s2->nodes, (size_t)s2->nNodes * 4)) || (rc = bow_up(h->start, s2->start, (size_t)(s2->nNodes + 1) * 4)) ||
-        (rc = bow_up(h->items, s2->items, (size_t)nitems * 4)) || (rc = bow_ensure(h->out, (size_t)std::max(std::max(s1->N, s2->N), 1) * 4)) ||
-        (rc = bow_ensure(h->qbest, (size_t)std::max(s1->nq, 1) * 4)) || (rc = bow_ensure(h->nm, 4)))
+        (rc = bow_up(h->items, s2->items, (size_t)nitems * 4)) || (rc = h->out.grow((size_t)std::max(std::max(s1->N, s2->N), 1) * 4, 256)) ||
+        (rc = h->qbest.grow((size_t)std::max(s1->nq, 1) * 4, 256)) || (rc = h->nm.grow(4, 256)))
         return rc;
     BowCtx c;
     memset(&c, 0, sizeof(c));
-    c.mode = mode; c.nq = s1->nq; c.q_idx1 = (const int*)h->q_idx1.p; c.q_node = (const uint32_t*)h->q_node.p;
-    c.N1 = s1->N; c.keys1 = (const oslam_keypoint_t*)h->keys1.p; c.desc1 = (const uint8_t*)h->desc1.p; c.uRight1 = (const float*)h->ur1.p; c.flag1 = (const uint8_t*)h->flag1.p;
-    c.N2 = s2->N; c.keys2 = (const oslam_keypoint_t*)h->keys2.p; c.desc2 = (const uint8_t*)h->desc2.p; c.uRight2 = (const float*)h->ur2.p; c.has_mp2 = (const uint8_t*)h->mp2.p;
-    c.nNodes = s2->nNodes; c.nodes = (const uint32_t*)h->nodes.p; c.start = (const int*)h->start.p; c.items = (const int*)h->items.p;
+    c.mode = mode; c.nq = s1->nq; c.q_idx1 = (const int*)h->q_idx1.ptr(); c.q_node = (const uint32_t*)h->q_node.ptr();
+    c.N1 = s1->N; c.keys1 = (const oslam_keypoint_t*)h->keys1.ptr(); c.desc1 = (const uint8_t*)h->desc1.ptr(); c.uRight1 = (const float*)h->ur1.ptr(); c.flag1 = (const uint8_t*)h->flag1.ptr();
+    c.N2 = s2->N; c.keys2 = (const oslam_keypoint_t*)h->keys2.ptr(); c.desc2 = (const uint8_t*)h->desc2.ptr(); c.uRight2 = (const float*)h->ur2.ptr(); c.has_mp2 = (const uint8_t*)h->mp2.ptr();
+    c.nNodes = s2->nNodes; c.nodes = (const uint32_t*)h->nodes.ptr(); c.start = (const int*)h->start.ptr(); c.items = (const int*)h->items.ptr();
     c.nnratio = nnratio; c.checkOri = checkOri; c.bOnlyStereo = bOnlyStereo;
     if (F12) for (int i = 0; i < 9; i++) c.F12[i] = F12[i];
     c.ex = ex; c.ey = ey;
@@ -312,14 +297,14 @@ static int bow_run(oslam_bow_t* h, int mode, const oslam_bow_side1_t* s1, const 
         c.scale[i] = (scaleFactors && i < nlevels) ? scaleFactors[i] : 0.f;
         c.sigma2[i] = (levelSigma2 && i < nlevels) ? levelSigma2[i] : 0.f;
     }
-    c.out = (int*)h->out.p; c.nmatches = (int*)h->nm.p; c.q_best = (int*)h->qbest.p;
+    c.out = (int*)h->out.ptr(); c.nmatches = (int*)h->nm.ptr(); c.q_best = (int*)h->qbest.ptr();
     hipLaunchKernelGGL(k_search_bow, dim3(1), dim3(kBowThreads), h->lds, nullptr, c, h->max_kps);
     OSLAM_HIP_CHECK(hipGetLastError());
     OSLAM_HIP_CHECK(hipDeviceSynchronize());
-    OSLAM_HIP_CHECK(hipMemcpy(nmatches, h->nm.p, 4, hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(nmatches, h->nm.ptr(), 4, hipMemcpyDeviceToHost));
     if (*nmatches < 0) { set_error("BoW matcher kernel rejected the pair (capacity)"); return OSLAM_E_CAPACITY; }
     const int nout = mode == 0 ? s2->N : s1->N;
-    if (nout > 0) OSLAM_HIP_CHECK(hipMemcpy(out, h->out.p, (size_t)nout * 4, hipMemcpyDeviceToHost));
+    if (nout > 0) OSLAM_HIP_CHECK(hipMemcpy(out, h->out.ptr(), (size_t)nout * 4, hipMemcpyDeviceToHost));
     return OSLAM_OK;
 }
 
@@ -391,18 +376,10 @@ static int bow_batch(oslam_bow_t* h, int n, oslam_bow_job_t* jobs, const oslam_b
     const size_t io_bytes = at;
     for (int i = 0; i < n; i++) off[i].qbest = take((size_t)std::max(jobs[i].s1.nq, 1) * 4);
     OSLAM_HIP_CHECK(hipSetDevice(h->device));
-    if (at > h->st_cap) {
-        OSLAM_HIP_CHECK(hipDeviceSynchronize());
-        if (h->st_h) (void)hipHostFree(h->st_h);
-        if (h->st_d) (void)hipFree(h->st_d);
-        h->st_h = nullptr; h->st_d = nullptr; h->st_cap = 0;
-        const size_t ncap = at + at / 2;
-        OSLAM_HIP_CHECK(hipHostMalloc((void**)&h->st_h, ncap, 0));
-        OSLAM_HIP_CHECK(hipMalloc((void**)&h->st_d, ncap));
-        h->st_cap = ncap;
-    }
-    uint8_t* H = h->st_h;
-    uint8_t* D = h->st_d;
+    if (at > h->st.cap()) OSLAM_HIP_CHECK(hipDeviceSynchronize());
+    OSLAM_CHECK(h->st.grow(at, 0));
+    uint8_t* H = h->st.h.bytes();
+    uint8_t* D = h->st.d.bytes();
     BowCtx* cs = (BowCtx*)H;
     oslam_drv::shared_parallel_for(n, [&](int i) {   // ~140 KB of keypoints / descriptors per job
         const oslam_bow_job_t& j = jobs[i];

@@ -145,28 +145,14 @@ using namespace oslam;
 
 struct oslam_frame {
     int device = 0;
-    struct Buf { void* p = nullptr; size_t cap = 0; };
-    Buf keys, keysUn, depth, ur, dp, status;
+    DeviceBuffer keys, keysUn, depth, ur, dp, status;
     PinStage pin;
 };
-
-static int fr_ensure(oslam_frame::Buf& b, size_t bytes) {
-    if (b.p && bytes <= b.cap) return OSLAM_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = bytes + bytes / 2 + 256;
-    OSLAM_HIP_CHECK(hipMalloc(&b.p, b.cap));
-    return OSLAM_OK;
-}
 
 extern "C" {
 
 void oslam_frame_destroy(oslam_frame_t* h) {
     if (!h) return;
-    oslam_frame::Buf* bs[] = {&h->keys, &h->keysUn, &h->depth, &h->ur, &h->dp, &h->status};
-    for (auto* b : bs)
-        if (b->p) (void)hipFree(b->p);
-    h->pin.release();
     delete h;
 }
 
@@ -281,12 +267,12 @@ int oslam_frame_undistort_keypoints(oslam_frame_t* h, int n, const oslam_keypoin
     OSLAM_HIP_CHECK(hipSetDevice(h->device));
     const size_t bytes = (size_t)n * sizeof(oslam_keypoint_t);
     int rc;
-    if ((rc = fr_ensure(h->keys, bytes)) || (rc = fr_ensure(h->keysUn, bytes)) || (rc = h->pin.reserve_total(2 * bytes + 4096))) return rc;
+    if ((rc = h->keys.grow(bytes, 256)) || (rc = h->keysUn.grow(bytes, 256)) || (rc = h->pin.reserve_total(2 * bytes + 4096))) return rc;
     h->pin.reset();
-    if ((rc = h->pin.upload(h->keys.p, keys, bytes))) return rc;
-    if ((rc = oslam_frame_undistort_batch_device((const oslam_keypoint_t*)h->keys.p, (oslam_keypoint_t*)h->keysUn.p, nullptr, n, n, 1, K4, dist, ndist, nullptr))) return rc;
+    if ((rc = h->pin.upload(h->keys.ptr(), keys, bytes))) return rc;
+    if ((rc = oslam_frame_undistort_batch_device((const oslam_keypoint_t*)h->keys.ptr(), (oslam_keypoint_t*)h->keysUn.ptr(), nullptr, n, n, 1, K4, dist, ndist, nullptr))) return rc;
     uint8_t* at = nullptr;
-    if ((rc = h->pin.download(h->keysUn.p, bytes, &at))) return rc;
+    if ((rc = h->pin.download(h->keysUn.ptr(), bytes, &at))) return rc;
     OSLAM_HIP_CHECK(hipStreamSynchronize(nullptr));
     memcpy(keysUn, at, bytes);
     return OSLAM_OK;
@@ -314,18 +300,18 @@ int oslam_frame_stereo_from_rgbd(oslam_frame_t* h, int n, const oslam_keypoint_t
     OSLAM_HIP_CHECK(hipSetDevice(h->device));
     const size_t kb = (size_t)n * sizeof(oslam_keypoint_t), db = (size_t)rows * pitch * 4;
     int rc;
-    if ((rc = fr_ensure(h->keys, kb)) || (rc = fr_ensure(h->keysUn, kb)) || (rc = fr_ensure(h->depth, db)) || (rc = fr_ensure(h->ur, (size_t)n * 4)) ||
-        (rc = fr_ensure(h->dp, (size_t)n * 4)) || (rc = fr_ensure(h->status, 4)) || (rc = h->pin.reserve_total(2 * kb + db + (size_t)n * 8 + 8192)))
+    if ((rc = h->keys.grow(kb, 256)) || (rc = h->keysUn.grow(kb, 256)) || (rc = h->depth.grow(db, 256)) || (rc = h->ur.grow((size_t)n * 4, 256)) ||
+        (rc = h->dp.grow((size_t)n * 4, 256)) || (rc = h->status.grow(4, 256)) || (rc = h->pin.reserve_total(2 * kb + db + (size_t)n * 8 + 8192)))
         return rc;
     h->pin.reset();
-    OSLAM_HIP_CHECK(hipMemsetAsync(h->status.p, 0, 4, nullptr));
-    if ((rc = h->pin.upload(h->keys.p, keys, kb)) || (rc = h->pin.upload(h->keysUn.p, keysUn, kb)) || (rc = h->pin.upload(h->depth.p, depth, db))) return rc;
-    if ((rc = oslam_frame_stereo_from_rgbd_batch_device((const oslam_keypoint_t*)h->keys.p, (const oslam_keypoint_t*)h->keysUn.p, nullptr, n, n, 1,
-                                                        (const float*)h->depth.p, rows, cols, pitch, 0, mbf, (float*)h->ur.p, (float*)h->dp.p,
-                                                        (int32_t*)h->status.p, nullptr)))
+    OSLAM_HIP_CHECK(hipMemsetAsync(h->status.ptr(), 0, 4, nullptr));
+    if ((rc = h->pin.upload(h->keys.ptr(), keys, kb)) || (rc = h->pin.upload(h->keysUn.ptr(), keysUn, kb)) || (rc = h->pin.upload(h->depth.ptr(), depth, db))) return rc;
+    if ((rc = oslam_frame_stereo_from_rgbd_batch_device((const oslam_keypoint_t*)h->keys.ptr(), (const oslam_keypoint_t*)h->keysUn.ptr(), nullptr, n, n, 1,
+                                                        (const float*)h->depth.ptr(), rows, cols, pitch, 0, mbf, (float*)h->ur.ptr(), (float*)h->dp.ptr(),
+                                                        (int32_t*)h->status.ptr(), nullptr)))
         return rc;
     uint8_t *a_u = nullptr, *a_d = nullptr, *a_s = nullptr;
-    if ((rc = h->pin.download(h->ur.p, (size_t)n * 4, &a_u)) || (rc = h->pin.download(h->dp.p, (size_t)n * 4, &a_d)) || (rc = h->pin.download(h->status.p, 4, &a_s))) return rc;
+    if ((rc = h->pin.download(h->ur.ptr(), (size_t)n * 4, &a_u)) || (rc = h->pin.download(h->dp.ptr(), (size_t)n * 4, &a_d)) || (rc = h->pin.download(h->status.ptr(), 4, &a_s))) return rc;
     OSLAM_HIP_CHECK(hipStreamSynchronize(nullptr));
     int st;
     memcpy(&st, a_s, 4);

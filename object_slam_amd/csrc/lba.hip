@@ -2302,11 +2302,10 @@ struct oslam_lba {
     //   in   : LbaProblem[n], LbaWide[n], Schur pair lists, and every window's input arrays — filled in the pinned mirror, ONE upload per launch
     //   work : solver state of every window (never copied)
     //   out  : poses_out / points_out / erase / stats of every window — ONE download per launch
-    struct Pool { void* p = nullptr; size_t cap = 0; };
-    Pool in_d, work_d, out_d;
-    uint8_t* in_h = nullptr; size_t in_h_cap = 0, in_off = 0;
-    uint8_t* out_h = nullptr; size_t out_h_cap = 0;
-    LbaCtrl* h_ctrl = nullptr; size_t h_ctrl_cap = 0;          // pinned copy of the control blocks (the host polls `done`)
+    DeviceBuffer in_d, work_d, out_d;
+    PinnedBuffer in_h; size_t in_off = 0;
+    PinnedBuffer out_h;
+    PinnedBuffer h_ctrl;          // LbaCtrl[]: pinned copy of the control blocks (the host polls `done`)
     hipStream_t strm = nullptr;   // every copy and launch of this handle (non-blocking: handles driven by different host threads overlap on the GPU)
     bool owns_strm = true;        // false: the stream of the driver handle this solver belongs to (lba_use_stream)
     std::mutex* launch_gate = nullptr;   // held from the upload to the download of a call when set (lba_use_gate): solvers sharing a gate take turns on the device
@@ -2340,7 +2339,7 @@ struct oslam_lba {
     };
     std::vector<Prep> prep;
     int n_prep = 0;               // windows of the current call (prep keeps its capacity)
-    int* h_stop = nullptr;        // pinned, device-visible stop flag
+    PinnedBuffer h_stop;          // int: pinned, device-visible stop flag
     int* d_stop = nullptr;
     size_t lds = 0;
     // kernel timing (bench.py's roofline): HIP events on this handle's stream around the solve kernels
@@ -2358,28 +2357,20 @@ static void lba_time_collect(oslam_lba* h, long long launches) {   // after the 
     if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) { h->kern_ms += ms; h->kern_launches += launches; }
 }
 
-static int pool_ensure(oslam_lba::Pool& q, size_t bytes) {
-    if (bytes <= q.cap) return OSLAM_OK;
-    OSLAM_HIP_CHECK(hipDeviceSynchronize());
-    if (q.p) (void)hipFree(q.p);
-    q.p = nullptr; q.cap = 0;
-    const size_t cap = bytes + bytes / 2 + (1u << 20);
-    hipError_t e = hipMalloc(&q.p, cap);
-    if (e != hipSuccess) { set_error("local BA: hipMalloc(%zu) failed: %s", cap, hipGetErrorString(e)); return OSLAM_E_HIP; }
-    q.cap = cap;
-    return OSLAM_OK;
+static int arena_reserve(DeviceBuffer& q, size_t bytes) {
+    if (bytes > q.cap()) OSLAM_HIP_CHECK(hipDeviceSynchronize());
+    return q.grow(bytes, 1u << 20);
 }
 
 // reserves `bytes` (256-aligned) in the pinned mirror of the `in` arena and returns the offset; the mirror grows by copy
 static int in_take(oslam_lba* h, size_t bytes, size_t* off) {
     const size_t need = h->in_off + ((bytes + 255) & ~(size_t)255);
-    if (need > h->in_h_cap) {
-        const size_t cap = need + need / 2 + (1u << 20);
-        uint8_t* nb = nullptr;
+    if (need > h->in_h.cap()) {
+        PinnedBuffer nb;
         OSLAM_HIP_CHECK(hipStreamSynchronize(h->strm));   // an earlier launch's upload may still read the old block
-        OSLAM_HIP_CHECK(hipHostMalloc((void**)&nb, cap, 0));
-        if (h->in_h) { memcpy(nb, h->in_h, h->in_off); (void)hipHostFree(h->in_h); }
-        h->in_h = nb; h->in_h_cap = cap;
+        OSLAM_CHECK(nb.alloc(need + need / 2 + (1u << 20)));
+        if (h->in_h.ptr()) memcpy(nb.ptr(), h->in_h.ptr(), h->in_off);
+        h->in_h = std::move(nb);
     }
     *off = h->in_off;
     h->in_off = need;
@@ -2388,7 +2379,7 @@ static int in_take(oslam_lba* h, size_t bytes, size_t* off) {
 static int in_put(oslam_lba* h, const void* src, size_t bytes, size_t* off) {
     const int rc = in_take(h, bytes, off);
     if (rc) return rc;
-    if (bytes) memcpy(h->in_h + *off, src, bytes);
+    if (bytes) memcpy(h->in_h.bytes() + *off, src, bytes);
     return OSLAM_OK;
 }
 
@@ -2444,12 +2435,6 @@ void oslam_lba_destroy(oslam_lba_t* h) {
     (void)hipSetDevice(h->device);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
-    for (oslam_lba::Pool* q : {&h->in_d, &h->work_d, &h->out_d})
-        if (q->p) (void)hipFree(q->p);
-    if (h->in_h) (void)hipHostFree(h->in_h);
-    if (h->out_h) (void)hipHostFree(h->out_h);
-    if (h->h_ctrl) (void)hipHostFree(h->h_ctrl);
-    if (h->h_stop) (void)hipHostFree(h->h_stop);
     if (h->strm && h->owns_strm) (void)hipStreamDestroy(h->strm);
     delete h;
 }
@@ -2487,9 +2472,9 @@ int oslam_lba_create(oslam_lba_t** out, int max_batch, int max_keyframes, int ma
     if (const char* e = getenv("OSLAM_LBA_SCHUR_VINV")) h->schur_vinv = atoi(e) != 0;
     if (const char* e = getenv("OSLAM_LBA_REC")) h->edge_rec = atoi(e) != 0;
     if (const char* e = getenv("OSLAM_LBA_SCHUR_TILES")) h->schur_tiles = atoi(e);   // 0 = always the pair gather, 1 = always tiles, 2 = per call (default)
-    if (hipHostMalloc((void**)&h->h_stop, sizeof(int), hipHostMallocMapped) != hipSuccess) { set_error("LBA stop flag allocation failed"); oslam_lba_destroy(h); return OSLAM_E_HIP; }
-    *h->h_stop = 0;
-    if (hipHostGetDevicePointer((void**)&h->d_stop, h->h_stop, 0) != hipSuccess) { set_error("hipHostGetDevicePointer failed"); oslam_lba_destroy(h); return OSLAM_E_HIP; }
+    if (const int rc = h->h_stop.alloc_mapped(sizeof(int))) { oslam_lba_destroy(h); return rc; }
+    *h->h_stop.as<int>() = 0;
+    if (hipHostGetDevicePointer((void**)&h->d_stop, h->h_stop.ptr(), 0) != hipSuccess) { set_error("hipHostGetDevicePointer failed"); oslam_lba_destroy(h); return OSLAM_E_HIP; }
     h->lds = kRowBufBytes + 64;
     h->win_lds_max = kWinLdsMax;
     if (hipFuncSetAttribute((const void*)k_lba, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess ||
@@ -2506,8 +2491,8 @@ int oslam_lba_create(oslam_lba_t** out, int max_batch, int max_keyframes, int ma
 }
 
 int oslam_lba_debug_stats(oslam_lba_t* h, int32_t out[16]) {
-    if (!h || h->n_prep < 1 || !h->out_h) return OSLAM_E_INVALID;
-    memcpy(out, h->out_h + h->prep[0].o_out_stats, 64);   // stats of window 0 of the last call
+    if (!h || h->n_prep < 1 || !h->out_h.ptr()) return OSLAM_E_INVALID;
+    memcpy(out, h->out_h.bytes() + h->prep[0].o_out_stats, 64);   // stats of window 0 of the last call
     return OSLAM_OK;
 }
 
@@ -2530,7 +2515,7 @@ int oslam_lba_set_solver(oslam_lba_t* h, int mode) {
     return OSLAM_OK;
 }
 
-volatile int32_t* oslam_lba_stop_flag(oslam_lba_t* h) { return h ? (volatile int32_t*)h->h_stop : nullptr; }
+volatile int32_t* oslam_lba_stop_flag(oslam_lba_t* h) { return h ? h->h_stop.as<volatile int32_t>() : nullptr; }
 
 }  // extern "C"
 
@@ -2922,25 +2907,15 @@ static int lba_launch(oslam_lba_t* h) {
             if (q.layout == 0 && q.dev_pairs) wo[i].pairM = takeW(std::max<size_t>((size_t)q.pr.P * q.nfree, 1) * 2);
         }
     const size_t pairM_bytes = work - pairM_base;
-    if ((rc = pool_ensure(h->in_d, h->in_off)) || (rc = pool_ensure(h->work_d, work)) || (rc = pool_ensure(h->out_d, outb))) return rc;
-    if (outb > h->out_h_cap) {
-        if (h->out_h) (void)hipHostFree(h->out_h);
-        h->out_h = nullptr; h->out_h_cap = 0;
-        OSLAM_HIP_CHECK(hipHostMalloc((void**)&h->out_h, outb + outb / 2, 0));
-        h->out_h_cap = outb + outb / 2;
-    }
-    if (wide && n0 > 0 && sizeof(LbaCtrl) * n0 > h->h_ctrl_cap) {
-        if (h->h_ctrl) (void)hipHostFree(h->h_ctrl);
-        h->h_ctrl = nullptr; h->h_ctrl_cap = 0;
-        OSLAM_HIP_CHECK(hipHostMalloc((void**)&h->h_ctrl, sizeof(LbaCtrl) * n0 * 2, 0));
-        h->h_ctrl_cap = sizeof(LbaCtrl) * n0 * 2;
-    }
-    uint8_t* I = (uint8_t*)h->in_d.p; uint8_t* Wk = (uint8_t*)h->work_d.p; uint8_t* O = (uint8_t*)h->out_d.p;
+    if ((rc = arena_reserve(h->in_d, h->in_off)) || (rc = arena_reserve(h->work_d, work)) || (rc = arena_reserve(h->out_d, outb))) return rc;
+    if ((rc = h->out_h.grow(outb, 0))) return rc;
+    if (wide && n0 > 0 && (rc = h->h_ctrl.reserve(sizeof(LbaCtrl) * n0, sizeof(LbaCtrl) * n0 * 2))) return rc;
+    uint8_t* I = h->in_d.bytes(); uint8_t* Wk = h->work_d.bytes(); uint8_t* O = h->out_d.bytes();
     // the problem records: layout-0 windows first (slots 0 .. n0-1 of probs / ws), then the layout-1 windows (slots n0 .. n-1 of probs, 0 .. n1-1 of wins)
-    LbaProblem* hp = (LbaProblem*)(h->in_h + o_probs);
-    LbaWide* hw = (LbaWide*)(h->in_h + o_ws);
-    LbaWin* hwin = (LbaWin*)(h->in_h + o_wins);
-    int* horder = (int*)(h->in_h + o_order);
+    LbaProblem* hp = (LbaProblem*)(h->in_h.bytes() + o_probs);
+    LbaWide* hw = (LbaWide*)(h->in_h.bytes() + o_ws);
+    LbaWin* hwin = (LbaWin*)(h->in_h.bytes() + o_wins);
+    int* horder = (int*)(h->in_h.bytes() + o_order);
     auto fill_problem = [&](int i) {
         const oslam_lba::Prep& q = h->prep[i];
         const WOff& o = wo[i];
@@ -3018,7 +2993,7 @@ static int lba_launch(oslam_lba_t* h) {
     static Gate* gate = [] { const char* e = getenv("OSLAM_LBA_CONCURRENCY"); const int k = e ? atoi(e) : 0; return k > 0 ? new Gate(k) : (Gate*)nullptr; }();
     struct GateScope { Gate* g; explicit GateScope(Gate* g_) : g(g_) { if (g) g->enter(); } ~GateScope() { if (g) g->leave(); } } gate_scope(gate);
     h->prof_pre_upload_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_launch0).count();
-    OSLAM_HIP_CHECK(hipMemcpyAsync(I, h->in_h, h->in_off, hipMemcpyHostToDevice, st));   // the ONE upload
+    OSLAM_HIP_CHECK(hipMemcpyAsync(I, h->in_h.bytes(), h->in_off, hipMemcpyHostToDevice, st));   // the ONE upload
     // Solvers that share a gate run their KERNELS in turns: the window preparation above and the upload (a DMA transfer on this solver's own stream: tens of
     // MB per call) proceed while the other solver has the device.
     std::unique_lock<std::mutex> handle_gate;
@@ -3115,11 +3090,11 @@ static int lba_launch(oslam_lba_t* h) {
                     if (!fold_ctrl) hipLaunchKernelGGL(k_w_ctrlB, dim3(1, n0), dim3(256), 0, st, d_probs, d_ws);
                 }
             }
-            OSLAM_HIP_CHECK(copy_to_host_async(h->h_ctrl, Wk + ctrl_base, sizeof(LbaCtrl) * n0, st));   // (a copy kernel, not the SDMA ring: common.h)
+            OSLAM_HIP_CHECK(copy_to_host_async(h->h_ctrl.as<LbaCtrl>(), Wk + ctrl_base, sizeof(LbaCtrl) * n0, st));   // (a copy kernel, not the SDMA ring: common.h)
             OSLAM_HIP_CHECK(stream_wait(st));
             bool all_done = true;
             int n_active = 0;
-            for (int i = 0; i < n0; i++) { all_done = all_done && h->h_ctrl[i].done != 0; n_active += h->h_ctrl[i].done == 0; }
+            for (int i = 0; i < n0; i++) { all_done = all_done && h->h_ctrl.as<LbaCtrl>()[i].done != 0; n_active += h->h_ctrl.as<LbaCtrl>()[i].done == 0; }
             if (call_stats) fprintf(stderr, "[lba call] %d windows, %d slots done, %d active\n", n0, slots_done, n_active);
             if (all_done) break;
             // The tail of a call — the few windows whose LM rejects steps (after the first 15 slots ~16 % of the windows of a steady-state call are still active,
@@ -3137,7 +3112,7 @@ static int lba_launch(oslam_lba_t* h) {
     }
     lba_time_end(h);
     OSLAM_HIP_CHECK(hipGetLastError());
-    OSLAM_HIP_CHECK(copy_to_host_async(h->out_h, O, outb, st));   // the ONE download
+    OSLAM_HIP_CHECK(copy_to_host_async(h->out_h.bytes(), O, outb, st));   // the ONE download
     OSLAM_HIP_CHECK(stream_wait(st));
     lba_time_collect(h, launches);
     return OSLAM_OK;
@@ -3146,11 +3121,11 @@ static int lba_launch(oslam_lba_t* h) {
 // scatter of window i's outputs (erase flags back in the caller's edge order)
 static void lba_fetch(oslam_lba_t* h, int i, float* poses_out, float* points_out, uint8_t* erase, int32_t* stats) {
     const oslam_lba::Prep& q = h->prep[i];
-    memcpy(poses_out, h->out_h + q.o_out_poses, (size_t)q.pr.K * 64);
-    if (q.pr.P > 0) memcpy(points_out, h->out_h + q.o_out_points, (size_t)q.pr.P * 12);
-    const uint8_t* er = h->out_h + q.o_out_erase;
+    memcpy(poses_out, h->out_h.bytes() + q.o_out_poses, (size_t)q.pr.K * 64);
+    if (q.pr.P > 0) memcpy(points_out, h->out_h.bytes() + q.o_out_points, (size_t)q.pr.P * 12);
+    const uint8_t* er = h->out_h.bytes() + q.o_out_erase;
     for (int e = 0; e < q.pr.E; e++) erase[q.order[e]] = er[e];
-    if (stats) { const int* st = (const int*)(h->out_h + q.o_out_stats); for (int k = 0; k < 4; k++) stats[k] = st[k]; }
+    if (stats) { const int* st = (const int*)(h->out_h.bytes() + q.o_out_stats); for (int k = 0; k < 4; k++) stats[k] = st[k]; }
 }
 
 extern "C" {

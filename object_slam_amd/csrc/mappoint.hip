@@ -198,27 +198,18 @@ using namespace oslam;
 
 struct oslam_mappoint {
     int device = 0;
-    struct Buf { void* p = nullptr; size_t cap = 0; };
-    Buf a, b, c, d, e, e2, f, g, g2, o1, o2;
+    DeviceBuffer a, b, c, d, e, e2, f, g, g2, o1, o2;   // scratch of the single-call forms, each grown by half plus 256 bytes
     // batch form (oslam_mp_triangulate_pairs): one pinned block mirrored on the device, one stream — ONE upload, one launch, ONE download per call
-    uint8_t* st_h = nullptr; uint8_t* st_d = nullptr; size_t st_cap = 0;
+    StagePair st;
     hipStream_t strm = nullptr;
     bool owns_strm = true;
     int timing = 0; hipEvent_t ev0 = nullptr, ev1 = nullptr; double kern_ms = 0; long long kern_n = 0;   // device time of the batched triangulation kernel
 };
 
-static int mp_ensure(oslam_mappoint::Buf& b, size_t bytes) {
-    if (b.p && bytes <= b.cap) return OSLAM_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = bytes + bytes / 2 + 256;
-    OSLAM_HIP_CHECK(hipMalloc(&b.p, b.cap));
-    return OSLAM_OK;
-}
-static int mp_up(oslam_mappoint::Buf& b, const void* src, size_t bytes) {
-    int rc = mp_ensure(b, bytes ? bytes : 4);
+static int mp_up(DeviceBuffer& b, const void* src, size_t bytes) {
+    int rc = b.grow(bytes ? bytes : 4, 256);
     if (rc) return rc;
-    if (bytes && src) OSLAM_HIP_CHECK(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
+    if (bytes && src) OSLAM_HIP_CHECK(hipMemcpy(b.ptr(), src, bytes, hipMemcpyHostToDevice));
     return OSLAM_OK;
 }
 
@@ -238,11 +229,6 @@ void oslam_mappoint_destroy(oslam_mappoint_t* h) {
     if (!h) return;
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
-    oslam_mappoint::Buf* bs[] = {&h->a, &h->b, &h->c, &h->d, &h->e, &h->e2, &h->f, &h->g, &h->g2, &h->o1, &h->o2};
-    for (auto* b : bs)
-        if (b->p) (void)hipFree(b->p);
-    if (h->st_h) (void)hipHostFree(h->st_h);
-    if (h->st_d) (void)hipFree(h->st_d);
     if (h->strm && h->owns_strm) (void)hipStreamDestroy(h->strm);
     delete h;
 }
@@ -278,14 +264,14 @@ int oslam_mp_distinctive_descriptors(oslam_mappoint_t* h, int P, const int32_t* 
     for (int p = 0; p < P; p++) if (obs_start[p + 1] < obs_start[p]) { set_error("obs_start not monotone"); return OSLAM_E_INVALID; }
     OSLAM_HIP_CHECK(hipSetDevice(h->device));
     int rc;
-    if ((rc = mp_up(h->a, obs_start, (size_t)(P + 1) * 4)) || (rc = mp_up(h->b, obs_desc, (size_t)total * 32)) || (rc = mp_ensure(h->o1, (size_t)P * 4)) ||
-        (rc = mp_ensure(h->o2, (size_t)P * 32)))
+    if ((rc = mp_up(h->a, obs_start, (size_t)(P + 1) * 4)) || (rc = mp_up(h->b, obs_desc, (size_t)total * 32)) || (rc = h->o1.grow((size_t)P * 4, 256)) ||
+        (rc = h->o2.grow((size_t)P * 32, 256)))
         return rc;
-    OSLAM_HIP_CHECK(hipMemset(h->o2.p, 0, (size_t)P * 32));
-    hipLaunchKernelGGL(k_distinctive, dim3(div_up(P, 4)), dim3(256), 0, nullptr, P, (const int*)h->a.p, (const uint8_t*)h->b.p, (int*)h->o1.p, (uint8_t*)h->o2.p);
+    OSLAM_HIP_CHECK(hipMemset(h->o2.ptr(), 0, (size_t)P * 32));
+    hipLaunchKernelGGL(k_distinctive, dim3(div_up(P, 4)), dim3(256), 0, nullptr, P, (const int*)h->a.ptr(), (const uint8_t*)h->b.ptr(), (int*)h->o1.ptr(), (uint8_t*)h->o2.ptr());
     OSLAM_HIP_CHECK(hipGetLastError());
-    OSLAM_HIP_CHECK(hipMemcpy(best_idx, h->o1.p, (size_t)P * 4, hipMemcpyDeviceToHost));
-    OSLAM_HIP_CHECK(hipMemcpy(out_desc, h->o2.p, (size_t)P * 32, hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(best_idx, h->o1.ptr(), (size_t)P * 4, hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(out_desc, h->o2.ptr(), (size_t)P * 32, hipMemcpyDeviceToHost));
     return OSLAM_OK;
 }
 
@@ -832,12 +818,12 @@ int oslam_mp_update_normal_depth(oslam_mappoint_t* h, int P, const float* Pos, c
     OSLAM_HIP_CHECK(hipSetDevice(h->device));
     int rc;
     if ((rc = mp_up(h->a, obs_start, (size_t)(P + 1) * 4)) || (rc = mp_up(h->b, obs_Ow, (size_t)total * 12)) || (rc = mp_up(h->c, Pos, (size_t)P * 12)) ||
-        (rc = mp_up(h->d, OwRef, (size_t)P * 12)) || (rc = mp_up(h->e, levelScaleFactor, (size_t)P * 4)) || (rc = mp_ensure(h->o1, (size_t)P * 20)))
+        (rc = mp_up(h->d, OwRef, (size_t)P * 12)) || (rc = mp_up(h->e, levelScaleFactor, (size_t)P * 4)) || (rc = h->o1.grow((size_t)P * 20, 256)))
         return rc;
-    hipLaunchKernelGGL(k_update_normal_depth, dim3(div_up(P, 256)), dim3(256), 0, nullptr, P, (const float*)h->c.p, (const int*)h->a.p, (const float*)h->b.p,
-                       (const float*)h->d.p, (const float*)h->e.p, lastScaleFactor, (float*)h->o1.p);
+    hipLaunchKernelGGL(k_update_normal_depth, dim3(div_up(P, 256)), dim3(256), 0, nullptr, P, (const float*)h->c.ptr(), (const int*)h->a.ptr(), (const float*)h->b.ptr(),
+                       (const float*)h->d.ptr(), (const float*)h->e.ptr(), lastScaleFactor, (float*)h->o1.ptr());
     OSLAM_HIP_CHECK(hipGetLastError());
-    OSLAM_HIP_CHECK(hipMemcpy(out, h->o1.p, (size_t)P * 20, hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(out, h->o1.ptr(), (size_t)P * 20, hipMemcpyDeviceToHost));
     return OSLAM_OK;
 }
 
@@ -905,13 +891,13 @@ int oslam_frame_is_in_frustum(oslam_mappoint_t* h, int M, const float* Pw, const
     int rc;
     if ((rc = mp_up(h->a, Pw, (size_t)M * 12)) || (rc = mp_up(h->b, Pn, (size_t)M * 12)) || (rc = mp_up(h->c, maxDist, (size_t)M * 4)) ||
         (rc = mp_up(h->d, minDist, (size_t)M * 4)) || (rc = mp_up(h->e, obs_gt0, (size_t)M)) || (rc = mp_up(h->f, mp_desc, (size_t)M * 32)) ||
-        (rc = mp_ensure(h->o1, (size_t)M * sizeof(oslam_proj_query_t))))
+        (rc = h->o1.grow((size_t)M * sizeof(oslam_proj_query_t), 256)))
         return rc;
-    rc = oslam_frame_is_in_frustum_device(M, (const float*)h->a.p, (const float*)h->b.p, (const float*)h->c.p, (const float*)h->d.p, (const uint8_t*)h->e.p,
-                                          (const uint8_t*)h->f.p, Tcw, K5, bounds, viewingCosLimit, logScaleFactor, scaleFactors, nLevels, th,
-                                          (oslam_proj_query_t*)h->o1.p, nullptr);
+    rc = oslam_frame_is_in_frustum_device(M, (const float*)h->a.ptr(), (const float*)h->b.ptr(), (const float*)h->c.ptr(), (const float*)h->d.ptr(), (const uint8_t*)h->e.ptr(),
+                                          (const uint8_t*)h->f.ptr(), Tcw, K5, bounds, viewingCosLimit, logScaleFactor, scaleFactors, nLevels, th,
+                                          (oslam_proj_query_t*)h->o1.ptr(), nullptr);
     if (rc) return rc;
-    OSLAM_HIP_CHECK(hipMemcpy(out, h->o1.p, (size_t)M * sizeof(oslam_proj_query_t), hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(out, h->o1.ptr(), (size_t)M * sizeof(oslam_proj_query_t), hipMemcpyDeviceToHost));
     return OSLAM_OK;
 }
 
@@ -1188,21 +1174,21 @@ extern "C" int oslam_mp_triangulate(oslam_mappoint_t* h, const oslam_tri_kf_t* k
     if ((rc = mp_up(h->a, kun.data(), total * sizeof(oslam_keypoint_t))) || (rc = mp_up(h->b, kraw.data(), total * sizeof(oslam_keypoint_t))) ||
         (rc = mp_up(h->c, ur.data(), total * 4)) || (rc = mp_up(h->d, dep.data(), total * 4)) || (rc = mp_up(h->e, dev2.data(), dev2.size() * sizeof(TriKfDev))) ||
         (rc = mp_up(h->f, pair_of.data(), (size_t)M * 4)) || (rc = mp_up(h->g, idx1, (size_t)M * 4)) || (rc = mp_up(h->g2, idx2, (size_t)M * 4)) ||
-        (rc = mp_ensure(h->o1, (size_t)M)) || (rc = mp_ensure(h->o2, (size_t)M * 12)))
+        (rc = h->o1.grow((size_t)M, 256)) || (rc = h->o2.grow((size_t)M * 12, 256)))
         return rc;
     TriCtx c;
     c.M = M; c.nLevels = nLevels;
     fill(c.kf1, *kf1, 0);
     c.kf1s = nullptr;
-    c.kf2 = (const TriKfDev*)h->e.p; c.pair_of = (const int*)h->f.p; c.idx1 = (const int*)h->g.p; c.idx2 = (const int*)h->g2.p;
-    c.keysUn = (const oslam_keypoint_t*)h->a.p; c.keys = (const oslam_keypoint_t*)h->b.p; c.uRight = (const float*)h->c.p; c.depth = (const float*)h->d.p;
+    c.kf2 = (const TriKfDev*)h->e.ptr(); c.pair_of = (const int*)h->f.ptr(); c.idx1 = (const int*)h->g.ptr(); c.idx2 = (const int*)h->g2.ptr();
+    c.keysUn = (const oslam_keypoint_t*)h->a.ptr(); c.keys = (const oslam_keypoint_t*)h->b.ptr(); c.uRight = (const float*)h->c.ptr(); c.depth = (const float*)h->d.ptr();
     for (int i = 0; i < OSLAM_MAX_LEVELS; i++) { c.scale[i] = i < nLevels ? scaleFactors[i] : 1.f; c.sigma2[i] = i < nLevels ? levelSigma2[i] : 1.f; }
     c.ratioFactor = ratioFactor;
-    c.ok = (uint8_t*)h->o1.p; c.x3D = (float*)h->o2.p;
+    c.ok = (uint8_t*)h->o1.ptr(); c.x3D = (float*)h->o2.ptr();
     hipLaunchKernelGGL(k_triangulate, dim3(div_up(M, 128)), dim3(128), 0, nullptr, c);
     OSLAM_HIP_CHECK(hipGetLastError());
-    OSLAM_HIP_CHECK(hipMemcpy(ok, h->o1.p, (size_t)M, hipMemcpyDeviceToHost));
-    OSLAM_HIP_CHECK(hipMemcpy(x3D, h->o2.p, (size_t)M * 12, hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(ok, h->o1.ptr(), (size_t)M, hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(x3D, h->o2.ptr(), (size_t)M * 12, hipMemcpyDeviceToHost));
     if (nnew) { int n = 0; for (int m = 0; m < M; m++) n += ok[m]; *nnew = n; }
     return OSLAM_OK;
 }
@@ -1229,19 +1215,11 @@ extern "C" int oslam_mp_triangulate_pairs(oslam_mappoint_t* h, int nPairs, const
                  o_d2 = take((size_t)M * 4);
     const size_t in_bytes = at;
     const size_t o_ok = take((size_t)M), o_x3 = take((size_t)M * 12);
-    if (at > h->st_cap) {
-        OSLAM_HIP_CHECK(hipDeviceSynchronize());
-        if (h->st_h) (void)hipHostFree(h->st_h);
-        if (h->st_d) (void)hipFree(h->st_d);
-        h->st_h = nullptr; h->st_d = nullptr; h->st_cap = 0;
-        const size_t ncap = at + at / 2 + 4096;
-        OSLAM_HIP_CHECK(hipHostMalloc((void**)&h->st_h, ncap, 0));
-        OSLAM_HIP_CHECK(hipMalloc((void**)&h->st_d, ncap));
-        h->st_cap = ncap;
-    }
+    if (at > h->st.cap()) OSLAM_HIP_CHECK(hipDeviceSynchronize());
+    OSLAM_CHECK(h->st.grow(at, 4096));
     if (!h->strm) OSLAM_HIP_CHECK(hipStreamCreateWithFlags(&h->strm, hipStreamNonBlocking));
-    uint8_t* H = h->st_h;
-    uint8_t* D = h->st_d;
+    uint8_t* H = h->st.h.bytes();
+    uint8_t* D = h->st.d.bytes();
     int* pair_of = (int*)(H + o_pair); int* d1 = (int*)(H + o_d1); int* d2 = (int*)(H + o_d2);
     TriKfDev* dev1 = (TriKfDev*)(H + o_dev1); TriKfDev* dev2 = (TriKfDev*)(H + o_dev2);
     oslam_keypoint_t* kun = (oslam_keypoint_t*)(H + o_kun); oslam_keypoint_t* kraw = (oslam_keypoint_t*)(H + o_kraw);

@@ -478,14 +478,14 @@ struct oslam_matcher {
     int device = 0, max_batch = 0, max_kps = 0, max_q = 0;
     size_t lds = 0;
     // device-owned
-    int* d_q_match = nullptr; int* d_q_dist = nullptr; int* d_kp_match = nullptr; int* d_nm = nullptr; int* d_iters = nullptr; int* d_pairs = nullptr;
-    uint32_t* d_cache = nullptr; int* d_ccount = nullptr;
-    oslam_proj_query_t* d_queries = nullptr;   // internal query buffer (project_last / host API)
-    long long* d_dbg = nullptr;
-    int* d_nq = nullptr;
+    DeviceBuffer d_q_match, d_q_dist, d_kp_match, d_nm, d_iters, d_pairs;   // int
+    DeviceBuffer d_cache, d_ccount;                                         // uint32_t, int
+    DeviceBuffer d_queries;   // oslam_proj_query_t: internal query buffer (project_last / host API)
+    DeviceBuffer d_dbg;       // long long
+    DeviceBuffer d_nq;        // int
     // staging for the host API (batch 1)
-    oslam_keypoint_t* d_kps = nullptr; float* d_ur = nullptr; uint8_t* d_desc = nullptr; uint8_t* d_blocked = nullptr;
-    float* d_Xw = nullptr; uint8_t* d_has = nullptr; oslam_keypoint_t* d_lkeys = nullptr; uint8_t* d_ldesc = nullptr; float* d_T = nullptr;
+    DeviceBuffer d_kps, d_ur, d_desc, d_blocked;        // oslam_keypoint_t, float, uint8_t, uint8_t
+    DeviceBuffer d_Xw, d_has, d_lkeys, d_ldesc, d_T;    // float, uint8_t, oslam_keypoint_t, uint8_t, float
     PinStage pin;   // host-pointer entry points
 };
 
@@ -493,11 +493,6 @@ extern "C" {
 
 void oslam_matcher_destroy(oslam_matcher_t* h) {
     if (!h) return;
-    void* ptrs[] = {h->d_dbg, h->d_cache, h->d_ccount, h->d_q_match, h->d_q_dist, h->d_kp_match, h->d_nm, h->d_iters, h->d_pairs, h->d_queries, h->d_nq, h->d_kps, h->d_ur,
-                    h->d_desc, h->d_blocked, h->d_Xw, h->d_has, h->d_lkeys, h->d_ldesc, h->d_T};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    h->pin.release();
     delete h;
 }
 
@@ -517,21 +512,16 @@ int oslam_matcher_create(oslam_matcher_t** out, int max_batch, int max_keypoints
     h->device = device; h->max_batch = max_batch; h->max_kps = max_keypoints; h->max_q = max_queries;
     h->lds = match_lds_bytes(max_keypoints);
     const size_t B = max_batch, NK = max_keypoints, NQ = max_queries;
-#define ALLOC(ptr, bytes)                                                         \
-    do {                                                                          \
-        hipError_t e_ = hipMalloc((void**)&(ptr), (bytes));                       \
-        if (e_ != hipSuccess) {                                                   \
-            set_error("hipMalloc(%zu) failed: %s", (size_t)(bytes), hipGetErrorString(e_)); \
-            oslam_matcher_destroy(h);                                             \
-            return OSLAM_E_HIP;                                                   \
-        }                                                                         \
-    } while (0)
-    ALLOC(h->d_q_match, B * NQ * 4); ALLOC(h->d_q_dist, B * NQ * 4); ALLOC(h->d_kp_match, B * NK * 4);
-    ALLOC(h->d_cache, B * NQ * kCacheCap * 4); ALLOC(h->d_ccount, B * NQ * 4);
-    ALLOC(h->d_nm, B * 4); ALLOC(h->d_iters, B * 4); ALLOC(h->d_pairs, B * 4); ALLOC(h->d_dbg, 64); ALLOC(h->d_queries, B * NQ * sizeof(oslam_proj_query_t)); ALLOC(h->d_nq, B * 4);
-    ALLOC(h->d_kps, NK * sizeof(oslam_keypoint_t)); ALLOC(h->d_ur, NK * 4); ALLOC(h->d_desc, NK * 32); ALLOC(h->d_blocked, NK);
-    ALLOC(h->d_Xw, NQ * 12); ALLOC(h->d_has, NQ); ALLOC(h->d_lkeys, NQ * sizeof(oslam_keypoint_t)); ALLOC(h->d_ldesc, NQ * 32); ALLOC(h->d_T, 32 * 4);
-#undef ALLOC
+    int rc;
+    if ((rc = h->d_q_match.alloc(B * NQ * 4)) || (rc = h->d_q_dist.alloc(B * NQ * 4)) || (rc = h->d_kp_match.alloc(B * NK * 4)) ||
+        (rc = h->d_cache.alloc(B * NQ * kCacheCap * 4)) || (rc = h->d_ccount.alloc(B * NQ * 4)) || (rc = h->d_nm.alloc(B * 4)) || (rc = h->d_iters.alloc(B * 4)) ||
+        (rc = h->d_pairs.alloc(B * 4)) || (rc = h->d_dbg.alloc(64)) || (rc = h->d_queries.alloc(B * NQ * sizeof(oslam_proj_query_t))) ||
+        (rc = h->d_nq.alloc(B * 4)) || (rc = h->d_kps.alloc(NK * sizeof(oslam_keypoint_t))) || (rc = h->d_ur.alloc(NK * 4)) || (rc = h->d_desc.alloc(NK * 32)) ||
+        (rc = h->d_blocked.alloc(NK)) || (rc = h->d_Xw.alloc(NQ * 12)) || (rc = h->d_has.alloc(NQ)) || (rc = h->d_lkeys.alloc(NQ * sizeof(oslam_keypoint_t))) ||
+        (rc = h->d_ldesc.alloc(NQ * 32)) || (rc = h->d_T.alloc(32 * 4))) {
+        delete h;
+        return rc;
+    }
     OSLAM_HIP_CHECK(hipFuncSetAttribute((const void*)k_search_window, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds));
     *out = h;
     return OSLAM_OK;
@@ -569,7 +559,7 @@ static int search_impl(oslam_matcher_t* h, const oslam_match_frames_t* f, const 
                        int th_high, const float* invLevelSigma2, int nlevels, void* stream) {
     int rc = check_frames(h, f, batch);
     if (rc) return rc;
-    if (!d_queries) d_queries = h->d_queries;
+    if (!d_queries) d_queries = h->d_queries.as<oslam_proj_query_t>();
     if (q_stride < 1 || q_stride > h->max_q) { set_error("q_stride %d outside [1,%d]", q_stride, h->max_q); return OSLAM_E_INVALID; }
     if (!d_n_queries && (n_queries_const < 0 || n_queries_const > q_stride)) { set_error("n_queries exceeds q_stride"); return OSLAM_E_CAPACITY; }
     OSLAM_HIP_CHECK(hipSetDevice(h->device));
@@ -583,8 +573,8 @@ static int search_impl(oslam_matcher_t* h, const oslam_match_frames_t* f, const 
     c.nnratio = nnratio; c.use_ratio = use_ratio; c.check_ori = check_ori; c.th_high = th_high;
     c.fuse = invLevelSigma2 ? 1 : 0;
     for (int i = 0; i < OSLAM_MAX_LEVELS; i++) c.invSigma2[i] = (invLevelSigma2 && i < nlevels) ? invLevelSigma2[i] : 0.f;
-    c.q_match = h->d_q_match; c.q_dist = h->d_q_dist; c.kp_match = h->d_kp_match; c.nmatches = h->d_nm; c.iters = h->d_iters; c.pairs = h->d_pairs; c.dbg = h->d_dbg;
-    c.cache = h->d_cache; c.ccount = h->d_ccount;
+    c.q_match = h->d_q_match.as<int>(); c.q_dist = h->d_q_dist.as<int>(); c.kp_match = h->d_kp_match.as<int>(); c.nmatches = h->d_nm.as<int>(); c.iters = h->d_iters.as<int>(); c.pairs = h->d_pairs.as<int>(); c.dbg = h->d_dbg.as<long long>();
+    c.cache = h->d_cache.as<uint32_t>(); c.ccount = h->d_ccount.as<int>();
     // per-frame output strides equal the input strides; outputs were sized for max_q / max_kps
     if ((size_t)f->kp_stride > (size_t)h->max_kps) { set_error("kp_stride %d > max_keypoints %d", f->kp_stride, h->max_kps); return OSLAM_E_CAPACITY; }
     hipLaunchKernelGGL(k_search_window, dim3(batch), dim3(kMatchThreads), h->lds, (hipStream_t)stream, c, h->max_kps);
@@ -608,7 +598,7 @@ int oslam_match_project_last_batch_device(oslam_matcher_t* h, const oslam_match_
     c.minX = cur->minX; c.minY = cur->minY; c.maxX = cur->maxX; c.maxY = cur->maxY;
     for (int i = 0; i < OSLAM_MAX_LEVELS; i++) c.scale[i] = i < nlevels ? scaleFactors[i] : 0.f;
     c.th = th; c.bMono = bMono;
-    c.out = h->d_queries; c.q_stride = last->kp_stride; c.n_q = h->d_nq;
+    c.out = h->d_queries.as<oslam_proj_query_t>(); c.q_stride = last->kp_stride; c.n_q = h->d_nq.as<int>();
     hipLaunchKernelGGL(k_project_last, dim3(div_up(last->kp_stride, 256), batch), dim3(256), 0, (hipStream_t)stream, c);
     OSLAM_HIP_CHECK(hipGetLastError());
     return OSLAM_OK;
@@ -617,12 +607,12 @@ int oslam_match_project_last_batch_device(oslam_matcher_t* h, const oslam_match_
 int oslam_match_results_device(const oslam_matcher_t* h, const int32_t** q_match, const int32_t** q_dist, const int32_t** kp_match,
                                const int32_t** nmatches, const oslam_proj_query_t** queries, const int32_t** n_queries) {
     if (!h) { set_error("NULL handle"); return OSLAM_E_INVALID; }
-    if (q_match) *q_match = h->d_q_match;
-    if (q_dist) *q_dist = h->d_q_dist;
-    if (kp_match) *kp_match = h->d_kp_match;
-    if (nmatches) *nmatches = h->d_nm;
-    if (queries) *queries = h->d_queries;
-    if (n_queries) *n_queries = h->d_nq;
+    if (q_match) *q_match = h->d_q_match.as<int>();
+    if (q_dist) *q_dist = h->d_q_dist.as<int>();
+    if (kp_match) *kp_match = h->d_kp_match.as<int>();
+    if (nmatches) *nmatches = h->d_nm.as<int>();
+    if (queries) *queries = h->d_queries.as<oslam_proj_query_t>();
+    if (n_queries) *n_queries = h->d_nq.as<int>();
     return OSLAM_OK;
 }
 
@@ -631,7 +621,7 @@ int oslam_match_hamming_pairs(oslam_matcher_t* h, int batch, int64_t* total) {
     OSLAM_HIP_CHECK(hipSetDevice(h->device));
     std::vector<int> v(batch);
     OSLAM_HIP_CHECK(hipDeviceSynchronize());
-    OSLAM_HIP_CHECK(hipMemcpy(v.data(), h->d_pairs, (size_t)batch * 4, hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(v.data(), h->d_pairs.as<int>(), (size_t)batch * 4, hipMemcpyDeviceToHost));
     int64_t t = 0;
     for (int x : v) t += x;
     *total = t;
@@ -640,8 +630,8 @@ int oslam_match_hamming_pairs(oslam_matcher_t* h, int batch, int64_t* total) {
 
 int oslam_match_debug_counters(oslam_matcher_t* h, long long out[8], int reset) {
     if (!h || !out) { set_error("bad argument"); return OSLAM_E_INVALID; }
-    OSLAM_HIP_CHECK(hipMemcpy(out, h->d_dbg, 64, hipMemcpyDeviceToHost));
-    if (reset) OSLAM_HIP_CHECK(hipMemset(h->d_dbg, 0, 64));
+    OSLAM_HIP_CHECK(hipMemcpy(out, h->d_dbg.as<long long>(), 64, hipMemcpyDeviceToHost));
+    if (reset) OSLAM_HIP_CHECK(hipMemset(h->d_dbg.as<long long>(), 0, 64));
     return OSLAM_OK;
 }
 
@@ -651,13 +641,13 @@ int oslam_match_fetch(oslam_matcher_t* h, int b, int q_stride, int n_q, int kp_s
     OSLAM_HIP_CHECK(hipSetDevice(h->device));
     OSLAM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     int nm = 0;
-    OSLAM_HIP_CHECK(hipMemcpy(&nm, h->d_nm + b, 4, hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(&nm, h->d_nm.as<int>() + b, 4, hipMemcpyDeviceToHost));
     if (nm < 0) { set_error("matcher kernel rejected frame %d (keypoints or queries exceed the handle capacity)", b); return OSLAM_E_CAPACITY; }
     if (nmatches) *nmatches = nm;
-    if (iterations) OSLAM_HIP_CHECK(hipMemcpy(iterations, h->d_iters + b, 4, hipMemcpyDeviceToHost));
-    if (q_match && n_q > 0) OSLAM_HIP_CHECK(hipMemcpy(q_match, h->d_q_match + (size_t)b * q_stride, (size_t)n_q * 4, hipMemcpyDeviceToHost));
-    if (q_dist && n_q > 0) OSLAM_HIP_CHECK(hipMemcpy(q_dist, h->d_q_dist + (size_t)b * q_stride, (size_t)n_q * 4, hipMemcpyDeviceToHost));
-    if (kp_match && n_kps > 0) OSLAM_HIP_CHECK(hipMemcpy(kp_match, h->d_kp_match + (size_t)b * kp_stride, (size_t)n_kps * 4, hipMemcpyDeviceToHost));
+    if (iterations) OSLAM_HIP_CHECK(hipMemcpy(iterations, h->d_iters.as<int>() + b, 4, hipMemcpyDeviceToHost));
+    if (q_match && n_q > 0) OSLAM_HIP_CHECK(hipMemcpy(q_match, h->d_q_match.as<int>() + (size_t)b * q_stride, (size_t)n_q * 4, hipMemcpyDeviceToHost));
+    if (q_dist && n_q > 0) OSLAM_HIP_CHECK(hipMemcpy(q_dist, h->d_q_dist.as<int>() + (size_t)b * q_stride, (size_t)n_q * 4, hipMemcpyDeviceToHost));
+    if (kp_match && n_kps > 0) OSLAM_HIP_CHECK(hipMemcpy(kp_match, h->d_kp_match.as<int>() + (size_t)b * kp_stride, (size_t)n_kps * 4, hipMemcpyDeviceToHost));
     return OSLAM_OK;
 }
 
@@ -665,10 +655,10 @@ int oslam_match_fetch(oslam_matcher_t* h, int b, int q_stride, int n_q, int kp_s
 static int fetch_host(oslam_matcher* h, int n_q, int n_kps, int32_t* q_match, int32_t* q_dist, int32_t* kp_match, int32_t* nmatches) {
     uint8_t *a_nm = nullptr, *a_qm = nullptr, *a_qd = nullptr, *a_km = nullptr;
     int rc;
-    if ((rc = h->pin.download(h->d_nm, 4, &a_nm))) return rc;
-    if (q_match && n_q > 0 && (rc = h->pin.download(h->d_q_match, (size_t)n_q * 4, &a_qm))) return rc;
-    if (q_dist && n_q > 0 && (rc = h->pin.download(h->d_q_dist, (size_t)n_q * 4, &a_qd))) return rc;
-    if (kp_match && n_kps > 0 && (rc = h->pin.download(h->d_kp_match, (size_t)n_kps * 4, &a_km))) return rc;
+    if ((rc = h->pin.download(h->d_nm.as<int>(), 4, &a_nm))) return rc;
+    if (q_match && n_q > 0 && (rc = h->pin.download(h->d_q_match.as<int>(), (size_t)n_q * 4, &a_qm))) return rc;
+    if (q_dist && n_q > 0 && (rc = h->pin.download(h->d_q_dist.as<int>(), (size_t)n_q * 4, &a_qd))) return rc;
+    if (kp_match && n_kps > 0 && (rc = h->pin.download(h->d_kp_match.as<int>(), (size_t)n_kps * 4, &a_km))) return rc;
     OSLAM_HIP_CHECK(hipStreamSynchronize(nullptr));
     int nm;
     memcpy(&nm, a_nm, 4);
@@ -689,12 +679,12 @@ static int stage_frame(oslam_matcher* h, int N, const oslam_keypoint_t* keysUn, 
     if (rc) return rc;
     h->pin.reset();
     if (N > 0) {
-        if ((rc = h->pin.upload(h->d_kps, keysUn, (size_t)N * sizeof(oslam_keypoint_t))) || (rc = h->pin.upload(h->d_desc, desc, (size_t)N * 32))) return rc;
-        if (uRight && (rc = h->pin.upload(h->d_ur, uRight, (size_t)N * 4))) return rc;
-        if (blocked && (rc = h->pin.upload(h->d_blocked, blocked, (size_t)N))) return rc;
+        if ((rc = h->pin.upload(h->d_kps.as<oslam_keypoint_t>(), keysUn, (size_t)N * sizeof(oslam_keypoint_t))) || (rc = h->pin.upload(h->d_desc.bytes(), desc, (size_t)N * 32))) return rc;
+        if (uRight && (rc = h->pin.upload(h->d_ur.as<float>(), uRight, (size_t)N * 4))) return rc;
+        if (blocked && (rc = h->pin.upload(h->d_blocked.bytes(), blocked, (size_t)N))) return rc;
     }
-    f->keysUn = h->d_kps; f->kp_stride = h->max_kps; f->uRight = uRight ? h->d_ur : nullptr; f->desc = h->d_desc;
-    f->blocked = blocked ? h->d_blocked : nullptr; f->n_kps = nullptr; f->n_kps_const = N;
+    f->keysUn = h->d_kps.as<oslam_keypoint_t>(); f->kp_stride = h->max_kps; f->uRight = uRight ? h->d_ur.as<float>() : nullptr; f->desc = h->d_desc.bytes();
+    f->blocked = blocked ? h->d_blocked.bytes() : nullptr; f->n_kps = nullptr; f->n_kps_const = N;
     f->minX = bounds[0]; f->minY = bounds[1]; f->maxX = bounds[2]; f->maxY = bounds[3];
     return OSLAM_OK;
 }
@@ -709,8 +699,8 @@ int oslam_match_search_by_projection(oslam_matcher_t* h, int N, const oslam_keyp
     oslam_match_frames_t f;
     int rc = stage_frame(h, N, keysUn, uRight, desc, blocked, bounds, &f);
     if (rc) return rc;
-    if (M > 0 && (rc = h->pin.upload(h->d_queries, queries, (size_t)M * sizeof(oslam_proj_query_t)))) return rc;
-    rc = oslam_match_search_batch_device(h, &f, h->d_queries, h->max_q, nullptr, M, 1, nnratio, use_ratio, check_ori, 100, nullptr);
+    if (M > 0 && (rc = h->pin.upload(h->d_queries.as<oslam_proj_query_t>(), queries, (size_t)M * sizeof(oslam_proj_query_t)))) return rc;
+    rc = oslam_match_search_batch_device(h, &f, h->d_queries.as<oslam_proj_query_t>(), h->max_q, nullptr, M, 1, nnratio, use_ratio, check_ori, 100, nullptr);
     if (rc) return rc;
     return fetch_host(h, M, N, q_match, q_dist, kp_match, nmatches);
 }
@@ -727,15 +717,15 @@ int oslam_match_project_last_frame(oslam_matcher_t* h, int N, const oslam_keypoi
     int rc = stage_frame(h, N, keysUn, uRight, desc, blocked, bounds, &f);
     if (rc) return rc;
     if (Nlast > 0) {
-        if ((rc = h->pin.upload(h->d_Xw, Xw, (size_t)Nlast * 12)) || (rc = h->pin.upload(h->d_has, has_mp, (size_t)Nlast)) ||
-            (rc = h->pin.upload(h->d_lkeys, last_keys, (size_t)Nlast * sizeof(oslam_keypoint_t))) || (rc = h->pin.upload(h->d_ldesc, mp_desc, (size_t)Nlast * 32)))
+        if ((rc = h->pin.upload(h->d_Xw.as<float>(), Xw, (size_t)Nlast * 12)) || (rc = h->pin.upload(h->d_has.bytes(), has_mp, (size_t)Nlast)) ||
+            (rc = h->pin.upload(h->d_lkeys.as<oslam_keypoint_t>(), last_keys, (size_t)Nlast * sizeof(oslam_keypoint_t))) || (rc = h->pin.upload(h->d_ldesc.bytes(), mp_desc, (size_t)Nlast * 32)))
             return rc;
     }
-    if ((rc = h->pin.upload(h->d_T, Tcw, 64)) || (rc = h->pin.upload(h->d_T + 16, Tlw, 64))) return rc;
+    if ((rc = h->pin.upload(h->d_T.as<float>(), Tcw, 64)) || (rc = h->pin.upload(h->d_T.as<float>() + 16, Tlw, 64))) return rc;
     oslam_match_last_t last;
-    last.Xw = h->d_Xw; last.has_mp = h->d_has; last.keys = h->d_lkeys; last.mp_desc = h->d_ldesc;
+    last.Xw = h->d_Xw.as<float>(); last.has_mp = h->d_has.bytes(); last.keys = h->d_lkeys.as<oslam_keypoint_t>(); last.mp_desc = h->d_ldesc.bytes();
     last.kp_stride = h->max_q; last.n_kps = nullptr; last.n_kps_const = Nlast;
-    rc = oslam_match_project_last_batch_device(h, &last, h->d_T, h->d_T + 16, cam, &f, scaleFactors, nlevels, th, bMono, 1, nullptr);
+    rc = oslam_match_project_last_batch_device(h, &last, h->d_T.as<float>(), h->d_T.as<float>() + 16, cam, &f, scaleFactors, nlevels, th, bMono, 1, nullptr);
     if (rc) return rc;
     rc = oslam_match_search_batch_device(h, &f, nullptr, h->max_q, nullptr, Nlast, 1, 0.f, 0, check_ori, 100, nullptr);
     if (rc) return rc;
@@ -751,8 +741,8 @@ int oslam_match_fuse_search(oslam_matcher_t* h, int N, const oslam_keypoint_t* k
     oslam_match_frames_t f;
     int rc = stage_frame(h, N, keysUn, uRight, desc, nullptr, bounds, &f);
     if (rc) return rc;
-    if (M > 0 && (rc = h->pin.upload(h->d_queries, queries, (size_t)M * sizeof(oslam_proj_query_t)))) return rc;
-    rc = oslam_match_fuse_batch_device(h, &f, h->d_queries, h->max_q, nullptr, M, 1, invLevelSigma2, nlevels, nullptr);
+    if (M > 0 && (rc = h->pin.upload(h->d_queries.as<oslam_proj_query_t>(), queries, (size_t)M * sizeof(oslam_proj_query_t)))) return rc;
+    rc = oslam_match_fuse_batch_device(h, &f, h->d_queries.as<oslam_proj_query_t>(), h->max_q, nullptr, M, 1, invLevelSigma2, nlevels, nullptr);
     if (rc) return rc;
     return fetch_host(h, M, 0, q_match, q_dist, nullptr, n_fused);
 }
@@ -761,7 +751,7 @@ int oslam_match_debug_get_queries(oslam_matcher_t* h, int b, int q_stride, int n
     if (!h || !out) { set_error("NULL argument"); return OSLAM_E_INVALID; }
     OSLAM_HIP_CHECK(hipSetDevice(h->device));
     OSLAM_HIP_CHECK(hipDeviceSynchronize());
-    if (n > 0) OSLAM_HIP_CHECK(hipMemcpy(out, h->d_queries + (size_t)b * q_stride, (size_t)n * sizeof(oslam_proj_query_t), hipMemcpyDeviceToHost));
+    if (n > 0) OSLAM_HIP_CHECK(hipMemcpy(out, h->d_queries.as<oslam_proj_query_t>() + (size_t)b * q_stride, (size_t)n * sizeof(oslam_proj_query_t), hipMemcpyDeviceToHost));
     return OSLAM_OK;
 }
 

@@ -102,32 +102,32 @@ struct oslam_orb {
     std::vector<int> quota;
 
     // device
-    OrbParams* dP = nullptr;
-    int2* d_rtab = nullptr;
-    int* d_qbase = nullptr; uint4* d_qpx = nullptr;
-    uint8_t* d_root_of_x = nullptr;
-    short* d_root_x = nullptr;
-    uint8_t* d_stage = nullptr;   // [B][H][pitch0] staging for host images
+    DeviceBuffer dP;   // OrbParams
+    DeviceBuffer d_rtab;   // int2
+    DeviceBuffer d_qbase; DeviceBuffer d_qpx;   // int, uint4
+    DeviceBuffer d_root_of_x;   // uint8_t
+    DeviceBuffer d_root_x;   // short
+    DeviceBuffer d_stage;   // uint8_t: [B][H][pitch0] staging for host images
     int stage_pitch = 0;
-    uint8_t* d_pyr = nullptr;
+    DeviceBuffer d_pyr;   // uint8_t
     long long pyr_stride = 0;
-    uint8_t* d_blur = nullptr;
+    DeviceBuffer d_blur;   // uint8_t
     long long blur_stride = 0;
-    int* d_cell_count = nullptr;
-    uint32_t* d_cand = nullptr;
-    FastCellRec* d_fast_cells = nullptr;   // per-cell geometry of k_fast_cells_wave
-    int* d_ovf_count = nullptr;   // FAST cells that took k_fast_cells_wave's every-pixel path since creation (diagnostics)
-    uint32_t* d_ent_g = nullptr;
-    uint16_t* d_knode_g = nullptr;
-    uint32_t* d_sel = nullptr;
-    int* d_sel_count = nullptr;
-    oslam_keypoint_t* d_out_kp = nullptr;
-    uint8_t* d_out_desc = nullptr;
-    int* d_out_count = nullptr;
-    int* d_status = nullptr;
-    unsigned long long* d_dbg = nullptr;
+    DeviceBuffer d_cell_count;   // int
+    DeviceBuffer d_cand;   // uint32_t
+    DeviceBuffer d_fast_cells;   // FastCellRec: per-cell geometry of k_fast_cells_wave
+    DeviceBuffer d_ovf_count;   // int: FAST cells that took k_fast_cells_wave's every-pixel path since creation (diagnostics)
+    DeviceBuffer d_ent_g;   // uint32_t
+    DeviceBuffer d_knode_g;   // uint16_t
+    DeviceBuffer d_sel;   // uint32_t
+    DeviceBuffer d_sel_count;   // int
+    DeviceBuffer d_out_kp;   // oslam_keypoint_t
+    DeviceBuffer d_out_desc;   // uint8_t
+    DeviceBuffer d_out_count;   // int
+    DeviceBuffer d_status;   // int
+    DeviceBuffer d_dbg;   // unsigned long long
     size_t oct_lds = 0;
-    int* d_oct_nodes = nullptr; long long oct_nodes_stride = 0;   // quad-tree node tables in HBM when they exceed the LDS
+    DeviceBuffer d_oct_nodes; long long oct_nodes_stride = 0;   // int: quad-tree node tables in HBM when they exceed the LDS
     hipStream_t side_stream = nullptr;             // blur runs here, concurrently with FAST + quad-tree
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipStream_t fast0_stream = nullptr;            // FAST of level 0 (needs only the caller's image) runs here, beside the pyramid kernels
@@ -182,11 +182,6 @@ int oslam_device_count(void) {
 
 void oslam_orb_destroy(oslam_orb_t* h) {
     if (!h) return;
-    void* ptrs[] = {h->d_qbase, h->d_qpx, h->dP, h->d_rtab, h->d_root_of_x, h->d_root_x, h->d_stage, h->d_pyr, h->d_blur,
-                    h->d_cell_count, h->d_cand, h->d_oct_nodes, h->d_fast_cells, h->d_ovf_count, h->d_ent_g, h->d_knode_g, h->d_sel, h->d_sel_count, h->d_out_kp, h->d_out_desc,
-                    h->d_out_count, h->d_status, h->d_dbg};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -426,42 +421,24 @@ int oslam_orb_create(oslam_orb_t** out, int nfeatures, float scaleFactor_, int n
     }
 
     const size_t B = max_batch;
-#define ALLOC(ptr, bytes)                                                         \
-    do {                                                                          \
-        hipError_t e_ = hipMalloc((void**)&(ptr), (bytes));                       \
-        if (e_ != hipSuccess) {                                                   \
-            set_error("hipMalloc(%zu) failed: %s", (size_t)(bytes), hipGetErrorString(e_)); \
-            oslam_orb_destroy(h);                                                 \
-            return OSLAM_E_HIP;                                                   \
-        }                                                                         \
-    } while (0)
-    ALLOC(h->dP, sizeof(OrbParams));
-    ALLOC(h->d_rtab, std::max<size_t>(rtab.size(), 1) * sizeof(int2));
-    ALLOC(h->d_qbase, std::max<size_t>(qbase.size(), 1) * sizeof(int));
-    ALLOC(h->d_qpx, std::max<size_t>(qpx.size(), 1) * sizeof(uint4));
-    ALLOC(h->d_root_of_x, root_of_x.size());
-    ALLOC(h->d_root_x, root_x.size() * sizeof(short));
     h->stage_pitch = (int)align_up(width, 64);
-    ALLOC(h->d_stage, B * (size_t)h->stage_pitch * height);
-    ALLOC(h->d_pyr, B * (size_t)h->pyr_stride);
-    ALLOC(h->d_blur, B * (size_t)h->blur_stride);
-    ALLOC(h->d_cell_count, B * (size_t)P.total_cells * sizeof(int));
-    ALLOC(h->d_cand, B * (size_t)P.cand_per_image * sizeof(uint32_t));
-    ALLOC(h->d_ovf_count, 64);
-    if (h->oct_nodes_stride) ALLOC(h->d_oct_nodes, B * (size_t)nlevels * h->oct_nodes_stride * sizeof(int));
-    ORB_CREATE_CHECK(hipMemset(h->d_ovf_count, 0, 64));
-    ALLOC(h->d_ent_g, B * (size_t)P.cand_per_image * sizeof(uint32_t));
-    ALLOC(h->d_knode_g, B * (size_t)P.cand_per_image * sizeof(uint16_t));
-    ALLOC(h->d_sel, B * (size_t)P.sel_per_image * sizeof(uint32_t));
-    ALLOC(h->d_sel_count, B * (size_t)nlevels * sizeof(int));
-    ALLOC(h->d_out_kp, B * (size_t)P.out_cap * sizeof(oslam_keypoint_t));
-    ALLOC(h->d_out_desc, B * (size_t)P.out_cap * 32);
-    ALLOC(h->d_out_count, B * sizeof(int));
-    ALLOC(h->d_status, sizeof(int));
-    ALLOC(h->d_dbg, 16 * sizeof(unsigned long long));
-    ORB_CREATE_CHECK(hipMemset(h->d_dbg, 0, 16 * sizeof(unsigned long long)));
-#undef ALLOC
-    ORB_CREATE_CHECK(hipMemcpy(h->dP, &P, sizeof(P), hipMemcpyHostToDevice));
+    int rc;
+    if ((rc = h->dP.alloc(sizeof(OrbParams))) || (rc = h->d_rtab.alloc(std::max<size_t>(rtab.size(), 1) * sizeof(int2))) ||
+        (rc = h->d_qbase.alloc(std::max<size_t>(qbase.size(), 1) * sizeof(int))) || (rc = h->d_qpx.alloc(std::max<size_t>(qpx.size(), 1) * sizeof(uint4))) ||
+        (rc = h->d_root_of_x.alloc(root_of_x.size())) || (rc = h->d_root_x.alloc(root_x.size() * sizeof(short))) ||
+        (rc = h->d_stage.alloc(B * (size_t)h->stage_pitch * height)) || (rc = h->d_pyr.alloc(B * (size_t)h->pyr_stride)) ||
+        (rc = h->d_blur.alloc(B * (size_t)h->blur_stride)) || (rc = h->d_cell_count.alloc(B * (size_t)P.total_cells * sizeof(int))) ||
+        (rc = h->d_cand.alloc(B * (size_t)P.cand_per_image * sizeof(uint32_t))) || (rc = h->d_ovf_count.alloc(64)) || (h->oct_nodes_stride && (rc = h->d_oct_nodes.alloc(B * (size_t)nlevels * h->oct_nodes_stride * sizeof(int)))) ||
+        (rc = h->d_ent_g.alloc(B * (size_t)P.cand_per_image * sizeof(uint32_t))) || (rc = h->d_knode_g.alloc(B * (size_t)P.cand_per_image * sizeof(uint16_t))) ||
+        (rc = h->d_sel.alloc(B * (size_t)P.sel_per_image * sizeof(uint32_t))) || (rc = h->d_sel_count.alloc(B * (size_t)nlevels * sizeof(int))) ||
+        (rc = h->d_out_kp.alloc(B * (size_t)P.out_cap * sizeof(oslam_keypoint_t))) || (rc = h->d_out_desc.alloc(B * (size_t)P.out_cap * 32)) ||
+        (rc = h->d_out_count.alloc(B * sizeof(int))) || (rc = h->d_status.alloc(sizeof(int))) || (rc = h->d_dbg.alloc(16 * sizeof(unsigned long long)))) {
+        oslam_orb_destroy(h);
+        return rc;
+    }
+    ORB_CREATE_CHECK(hipMemset(h->d_ovf_count.as<int>(), 0, 64));
+    ORB_CREATE_CHECK(hipMemset(h->d_dbg.as<unsigned long long>(), 0, 16 * sizeof(unsigned long long)));
+    ORB_CREATE_CHECK(hipMemcpy(h->dP.as<OrbParams>(), &P, sizeof(P), hipMemcpyHostToDevice));
     {   // FAST cell records (the cell grid of reference src/ORBextractor.cc:784-808, one record per cell of every level)
         std::vector<FastCellRec> cells((size_t)P.total_cells);
         for (int l = 0; l < nlevels; l++) {
@@ -490,18 +467,18 @@ int oslam_orb_create(oslam_orb_t** out, int nfeatures, float scaleFactor_, int n
                 cells[(size_t)g.cell_base + cell] = r;
             }
         }
-        if (hipMalloc((void**)&h->d_fast_cells, cells.size() * sizeof(FastCellRec)) != hipSuccess) { set_error("hipMalloc of the FAST cell records failed"); oslam_orb_destroy(h); return OSLAM_E_HIP; }
-        ORB_CREATE_CHECK(hipMemcpy(h->d_fast_cells, cells.data(), cells.size() * sizeof(FastCellRec), hipMemcpyHostToDevice));
+        if ((rc = h->d_fast_cells.alloc(cells.size() * sizeof(FastCellRec)))) { oslam_orb_destroy(h); return rc; }
+        ORB_CREATE_CHECK(hipMemcpy(h->d_fast_cells.as<FastCellRec>(), cells.data(), cells.size() * sizeof(FastCellRec), hipMemcpyHostToDevice));
     }
-    if (!rtab.empty()) ORB_CREATE_CHECK(hipMemcpy(h->d_rtab, rtab.data(), rtab.size() * sizeof(int2), hipMemcpyHostToDevice));
+    if (!rtab.empty()) ORB_CREATE_CHECK(hipMemcpy(h->d_rtab.as<int2>(), rtab.data(), rtab.size() * sizeof(int2), hipMemcpyHostToDevice));
     if (!qbase.empty()) {
-        ORB_CREATE_CHECK(hipMemcpy(h->d_qbase, qbase.data(), qbase.size() * sizeof(int), hipMemcpyHostToDevice));
-        ORB_CREATE_CHECK(hipMemcpy(h->d_qpx, qpx.data(), qpx.size() * sizeof(uint4), hipMemcpyHostToDevice));
+        ORB_CREATE_CHECK(hipMemcpy(h->d_qbase.as<int>(), qbase.data(), qbase.size() * sizeof(int), hipMemcpyHostToDevice));
+        ORB_CREATE_CHECK(hipMemcpy(h->d_qpx.as<uint4>(), qpx.data(), qpx.size() * sizeof(uint4), hipMemcpyHostToDevice));
     }
-    ORB_CREATE_CHECK(hipMemcpy(h->d_root_of_x, root_of_x.data(), root_of_x.size(), hipMemcpyHostToDevice));
-    ORB_CREATE_CHECK(hipMemcpy(h->d_root_x, root_x.data(), root_x.size() * sizeof(short), hipMemcpyHostToDevice));
-    ORB_CREATE_CHECK(hipMemset(h->d_status, 0, sizeof(int)));
-    ORB_CREATE_CHECK(hipMemset(h->d_out_count, 0, B * sizeof(int)));
+    ORB_CREATE_CHECK(hipMemcpy(h->d_root_of_x.bytes(), root_of_x.data(), root_of_x.size(), hipMemcpyHostToDevice));
+    ORB_CREATE_CHECK(hipMemcpy(h->d_root_x.as<short>(), root_x.data(), root_x.size() * sizeof(short), hipMemcpyHostToDevice));
+    ORB_CREATE_CHECK(hipMemset(h->d_status.as<int>(), 0, sizeof(int)));
+    ORB_CREATE_CHECK(hipMemset(h->d_out_count.as<int>(), 0, B * sizeof(int)));
     ORB_CREATE_CHECK(hipFuncSetAttribute((const void*)k_octree, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->oct_lds));
     ORB_CREATE_CHECK(hipFuncSetAttribute((const void*)k_octree_spill, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->oct_lds));
     ORB_CREATE_CHECK(hipFuncSetAttribute((const void*)k_octree_hbm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->oct_lds));
@@ -585,13 +562,13 @@ static int collect_profile(oslam_orb* h) {
 static int launch_batch(oslam_orb* h, const uint8_t* d_gray, int batch, int stride, size_t image_stride, hipStream_t st) {
     const OrbParams& P = h->P;
     OrbCtx c;
-    c.P = h->dP;
+    c.P = h->dP.as<OrbParams>();
     c.img0 = d_gray; c.img0_pitch = stride; c.img0_stride = (long long)image_stride;
-    c.pyr = h->d_pyr; c.pyr_stride = h->pyr_stride;
-    c.blur = h->d_blur; c.blur_stride = h->blur_stride;
-    c.rtab = h->d_rtab; c.qbase = h->d_qbase; c.qpx = h->d_qpx; c.root_of_x = h->d_root_of_x; c.root_x = h->d_root_x;
-    c.cell_count = h->d_cell_count; c.cand = h->d_cand; c.fast_cells = h->d_fast_cells; c.oct_nodes = h->d_oct_nodes; c.oct_nodes_stride = h->oct_nodes_stride; c.ovf_count = h->d_ovf_count; c.ent_g = h->d_ent_g; c.knode_g = h->d_knode_g; c.sel = h->d_sel; c.sel_count = h->d_sel_count;
-    c.out_kp = h->d_out_kp; c.out_desc = h->d_out_desc; c.out_count = h->d_out_count; c.status = h->d_status; c.dbg = h->d_dbg;
+    c.pyr = h->d_pyr.bytes(); c.pyr_stride = h->pyr_stride;
+    c.blur = h->d_blur.bytes(); c.blur_stride = h->blur_stride;
+    c.rtab = h->d_rtab.as<int2>(); c.qbase = h->d_qbase.as<int>(); c.qpx = h->d_qpx.as<uint4>(); c.root_of_x = h->d_root_of_x.bytes(); c.root_x = h->d_root_x.as<short>();
+    c.cell_count = h->d_cell_count.as<int>(); c.cand = h->d_cand.as<uint32_t>(); c.fast_cells = h->d_fast_cells.as<FastCellRec>(); c.oct_nodes = h->d_oct_nodes.as<int>(); c.oct_nodes_stride = h->oct_nodes_stride; c.ovf_count = h->d_ovf_count.as<int>(); c.ent_g = h->d_ent_g.as<uint32_t>(); c.knode_g = h->d_knode_g.as<uint16_t>(); c.sel = h->d_sel.as<uint32_t>(); c.sel_count = h->d_sel_count.as<int>();
+    c.out_kp = h->d_out_kp.as<oslam_keypoint_t>(); c.out_desc = h->d_out_desc.bytes(); c.out_count = h->d_out_count.as<int>(); c.status = h->d_status.as<int>(); c.dbg = h->d_dbg.as<unsigned long long>();
     const bool prof = h->profiling != 0;
     if (prof) {
         int rc = collect_profile(h);   // previous batch, if not collected yet
@@ -705,18 +682,18 @@ int oslam_orb_extract_batch_device(oslam_orb_t* h, const uint8_t* d_gray, int ba
 int oslam_orb_results_device(const oslam_orb_t* h, const oslam_keypoint_t** kp, const uint8_t** desc, const int32_t** counts,
                              const int32_t** status) {
     if (!h) { set_error("NULL handle"); return OSLAM_E_INVALID; }
-    if (kp) *kp = h->d_out_kp;
-    if (desc) *desc = h->d_out_desc;
-    if (counts) *counts = h->d_out_count;
-    if (status) *status = h->d_status;
+    if (kp) *kp = h->d_out_kp.as<oslam_keypoint_t>();
+    if (desc) *desc = h->d_out_desc.bytes();
+    if (counts) *counts = h->d_out_count.as<int>();
+    if (status) *status = h->d_status.as<int>();
     return OSLAM_OK;
 }
 
 static int check_status(oslam_orb* h) {
     int st = 0;
-    OSLAM_HIP_CHECK(hipMemcpy(&st, h->d_status, sizeof(int), hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(&st, h->d_status.as<int>(), sizeof(int), hipMemcpyDeviceToHost));
     if (st) {
-        OSLAM_HIP_CHECK(hipMemset(h->d_status, 0, sizeof(int)));
+        OSLAM_HIP_CHECK(hipMemset(h->d_status.as<int>(), 0, sizeof(int)));
         set_error("extractor arena overflow, status bits 0x%x (1 cell, 2 candidates per level, 4/8 quad-tree nodes, 16 outputs)", st);
         return OSLAM_E_CAPACITY;
     }
@@ -731,13 +708,13 @@ int oslam_orb_fetch(oslam_orb_t* h, int b, oslam_keypoint_t* kps, uint8_t* desc,
     int rc = check_status(h);
     if (rc) return rc;
     int n = 0;
-    OSLAM_HIP_CHECK(hipMemcpy(&n, h->d_out_count + b, sizeof(int), hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(&n, h->d_out_count.as<int>() + b, sizeof(int), hipMemcpyDeviceToHost));
     *n_out = n;
     if (n > cap) { set_error("caller capacity %d < %d keypoints", cap, n); return OSLAM_E_CAPACITY; }
     if (n > 0) {
         if (!kps || !desc) { set_error("NULL output"); return OSLAM_E_INVALID; }
-        OSLAM_HIP_CHECK(hipMemcpy(kps, h->d_out_kp + (size_t)b * h->P.out_cap, (size_t)n * sizeof(oslam_keypoint_t), hipMemcpyDeviceToHost));
-        OSLAM_HIP_CHECK(hipMemcpy(desc, h->d_out_desc + (size_t)b * h->P.out_cap * 32, (size_t)n * 32, hipMemcpyDeviceToHost));
+        OSLAM_HIP_CHECK(hipMemcpy(kps, h->d_out_kp.as<oslam_keypoint_t>() + (size_t)b * h->P.out_cap, (size_t)n * sizeof(oslam_keypoint_t), hipMemcpyDeviceToHost));
+        OSLAM_HIP_CHECK(hipMemcpy(desc, h->d_out_desc.bytes() + (size_t)b * h->P.out_cap * 32, (size_t)n * 32, hipMemcpyDeviceToHost));
     }
     return OSLAM_OK;
 }
@@ -752,8 +729,8 @@ int oslam_orb_extract(oslam_orb_t* h, const uint8_t* gray, int width, int height
         return OSLAM_E_INVALID;
     }
     OSLAM_HIP_CHECK(hipSetDevice(h->device));
-    OSLAM_HIP_CHECK(hipMemcpy2D(h->d_stage, h->stage_pitch, gray, stride, width, height, hipMemcpyHostToDevice));
-    int rc = launch_batch(h, h->d_stage, 1, h->stage_pitch, (size_t)h->stage_pitch * height, nullptr);
+    OSLAM_HIP_CHECK(hipMemcpy2D(h->d_stage.bytes(), h->stage_pitch, gray, stride, width, height, hipMemcpyHostToDevice));
+    int rc = launch_batch(h, h->d_stage.bytes(), 1, h->stage_pitch, (size_t)h->stage_pitch * height, nullptr);
     if (rc) return rc;
     return oslam_orb_fetch(h, 0, kps, desc, cap, n_out);
 }
@@ -782,8 +759,8 @@ int oslam_orb_get_profile(oslam_orb_t* h, double ms[5], long long* batches, long
 int oslam_orb_debug_counters(oslam_orb_t* h, unsigned long long out[16], int reset) {
     if (!h) return OSLAM_E_INVALID;
     OSLAM_HIP_CHECK(hipDeviceSynchronize());
-    OSLAM_HIP_CHECK(hipMemcpy(out, h->d_dbg, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    if (reset) OSLAM_HIP_CHECK(hipMemset(h->d_dbg, 0, 16 * sizeof(unsigned long long)));
+    OSLAM_HIP_CHECK(hipMemcpy(out, h->d_dbg.as<unsigned long long>(), 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (reset) OSLAM_HIP_CHECK(hipMemset(h->d_dbg.as<unsigned long long>(), 0, 16 * sizeof(unsigned long long)));
     return OSLAM_OK;
 }
 
@@ -800,7 +777,7 @@ int oslam_orb_pyramid_level_device(const oslam_orb_t* h, int b, int level, const
         *d_ptr = h->ctx.img0 + (long long)b * h->ctx.img0_stride;
         *pitch = h->ctx.img0_pitch;
     } else {
-        *d_ptr = h->d_pyr + (long long)b * h->pyr_stride + h->P.lv[level].img_off;
+        *d_ptr = h->d_pyr.bytes() + (long long)b * h->pyr_stride + h->P.lv[level].img_off;
         *pitch = h->P.lv[level].pitch;
     }
     return OSLAM_OK;
@@ -820,7 +797,7 @@ int oslam_orb_debug_get_blurred(oslam_orb_t* h, int b, int level, uint8_t* out) 
     if (!h || level < 0 || level >= h->nlevels || b < 0 || b >= h->last_batch) { set_error("bad level/image"); return OSLAM_E_INVALID; }
     OSLAM_HIP_CHECK(hipStreamSynchronize(h->last_stream));
     const LevelGeom& g = h->P.lv[level];
-    OSLAM_HIP_CHECK(hipMemcpy2D(out, g.w, h->d_blur + (long long)b * h->blur_stride + g.img_off, g.pitch, g.w, g.h, hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy2D(out, g.w, h->d_blur.bytes() + (long long)b * h->blur_stride + g.img_off, g.pitch, g.w, g.h, hipMemcpyDeviceToHost));
     return OSLAM_OK;
 }
 
@@ -831,8 +808,8 @@ int oslam_orb_debug_get_candidates(oslam_orb_t* h, int b, int level, int32_t* ou
     const int ncells = g.nCols * g.nRows;
     std::vector<int> cnt(ncells);
     std::vector<uint32_t> ent((size_t)ncells * g.cell_cap);
-    OSLAM_HIP_CHECK(hipMemcpy(cnt.data(), h->d_cell_count + (size_t)b * h->P.total_cells + g.cell_base, ncells * sizeof(int), hipMemcpyDeviceToHost));
-    OSLAM_HIP_CHECK(hipMemcpy(ent.data(), h->d_cand + (size_t)b * h->P.cand_per_image + g.cand_base, ent.size() * 4, hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(cnt.data(), h->d_cell_count.as<int>() + (size_t)b * h->P.total_cells + g.cell_base, ncells * sizeof(int), hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(ent.data(), h->d_cand.as<uint32_t>() + (size_t)b * h->P.cand_per_image + g.cand_base, ent.size() * 4, hipMemcpyDeviceToHost));
     int n = 0;
     for (int ce = 0; ce < ncells; ce++)
         for (int i = 0; i < cnt[ce]; i++, n++)
@@ -850,11 +827,11 @@ int oslam_orb_debug_get_level_keys(oslam_orb_t* h, int b, int level, int32_t* ou
     OSLAM_HIP_CHECK(hipStreamSynchronize(h->last_stream));
     const LevelGeom& g = h->P.lv[level];
     int n = 0;
-    OSLAM_HIP_CHECK(hipMemcpy(&n, h->d_sel_count + (size_t)b * h->nlevels + level, sizeof(int), hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(&n, h->d_sel_count.as<int>() + (size_t)b * h->nlevels + level, sizeof(int), hipMemcpyDeviceToHost));
     *n_out = n;
     if (n > cap) { set_error("capacity"); return OSLAM_E_CAPACITY; }
     std::vector<uint32_t> ent(std::max(n, 1));
-    OSLAM_HIP_CHECK(hipMemcpy(ent.data(), h->d_sel + (size_t)b * h->P.sel_per_image + g.sel_base, (size_t)n * 4, hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(ent.data(), h->d_sel.as<uint32_t>() + (size_t)b * h->P.sel_per_image + g.sel_base, (size_t)n * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) { out[3 * i] = ent_x(ent[i]); out[3 * i + 1] = ent_y(ent[i]); out[3 * i + 2] = ent_s(ent[i]); }
     return OSLAM_OK;
 }

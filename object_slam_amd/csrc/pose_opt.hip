@@ -890,37 +890,20 @@ constexpr size_t kPoseLdsBudget = OSLAM_POSE_LDS_BUDGET;   // FOUR workgroups of
 struct oslam_poseopt {
     int device = 0, max_batch = 0, max_points = 0;
     bool stage = false;   // edge data staged in LDS (fits for max_points <= 2700)
-    float* d_Tout = nullptr; uint8_t* d_outlier = nullptr; int* d_ninl = nullptr; int* d_stats = nullptr;
+    DeviceBuffer d_Tout, d_outlier, d_ninl, d_stats;   // float [B][16], uint8_t [B][NP], int [B], int [B][2]
     // staging for the host API
-    float* d_T = nullptr; float* d_Xw = nullptr; float* d_obs = nullptr; float* d_inv = nullptr; uint8_t* d_has = nullptr;
-    uint8_t* h_pin = nullptr; size_t pin_cap = 0;   // pinned staging of the single-frame host API (inputs, then results)
-    double* d_trace = nullptr; int trace_cap = 0;   // LM trace of frame 0 (oslam_poseopt_trace), off by default
+    DeviceBuffer d_T, d_Xw, d_obs, d_inv, d_has;   // float, float, float, float, uint8_t
+    PinnedBuffer h_pin;   // pinned staging of the single-frame host API (inputs, then results)
+    DeviceBuffer d_trace; int trace_cap = 0;   // LM trace of frame 0 (oslam_poseopt_trace), off by default
     const unsigned long long* bits = nullptr; const int* bits_index = nullptr;   // one-bit-per-pixel masks for the NEXT batch call (oslam_poseopt_use_mask_bits)
     // semantic variant: grow-only device buffers
-    struct Buf { void* p = nullptr; size_t cap = 0; };
-    Buf masks, rowcnt, objcnt, area, area_start, objmp_Xw, objmp_obj, joint_kp, joint_obj, kp_uv, eXw, eobs, elevel, echi2, eobj, eout, etmp, nsem;
+    DeviceBuffer masks, rowcnt, objcnt, area, area_start, objmp_Xw, objmp_obj, joint_kp, joint_obj, kp_uv, eXw, eobs, elevel, echi2, eobj, eout, etmp, nsem;
 };
-
-static int ensure(oslam_poseopt::Buf& b, size_t bytes) {
-    if (b.p && bytes <= b.cap) return OSLAM_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = bytes + bytes / 2 + 256;
-    OSLAM_HIP_CHECK(hipMalloc(&b.p, b.cap));
-    return OSLAM_OK;
-}
 
 extern "C" {
 
 void oslam_poseopt_destroy(oslam_poseopt_t* h) {
     if (!h) return;
-    void* ptrs[] = {h->d_Tout, h->d_outlier, h->d_ninl, h->d_stats, h->d_T, h->d_Xw, h->d_obs, h->d_inv, h->d_has,
-                    h->masks.p, h->rowcnt.p, h->objcnt.p, h->area.p, h->area_start.p, h->objmp_Xw.p, h->objmp_obj.p, h->joint_kp.p, h->joint_obj.p, h->kp_uv.p,
-                    h->eXw.p, h->eobs.p, h->elevel.p, h->echi2.p, h->eobj.p, h->eout.p, h->etmp.p, h->nsem.p};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (h->h_pin) (void)hipHostFree(h->h_pin);
-    if (h->d_trace) (void)hipFree(h->d_trace);
     delete h;
 }
 
@@ -935,18 +918,12 @@ int oslam_poseopt_create(oslam_poseopt_t** out, int max_batch, int max_points, i
     oslam_poseopt* h = new oslam_poseopt();
     h->device = device; h->max_batch = max_batch; h->max_points = max_points;
     const size_t B = max_batch, NP = max_points;
-#define ALLOC(ptr, bytes)                                                         \
-    do {                                                                          \
-        hipError_t e_ = hipMalloc((void**)&(ptr), (bytes));                       \
-        if (e_ != hipSuccess) {                                                   \
-            set_error("hipMalloc(%zu) failed: %s", (size_t)(bytes), hipGetErrorString(e_)); \
-            oslam_poseopt_destroy(h);                                             \
-            return OSLAM_E_HIP;                                                   \
-        }                                                                         \
-    } while (0)
-    ALLOC(h->d_Tout, B * 64); ALLOC(h->d_outlier, B * NP); ALLOC(h->d_ninl, B * 4); ALLOC(h->d_stats, B * 8);
-    ALLOC(h->d_T, 64); ALLOC(h->d_Xw, NP * 12); ALLOC(h->d_obs, NP * 12); ALLOC(h->d_inv, NP * 4); ALLOC(h->d_has, NP);
-#undef ALLOC
+    int rc;
+    if ((rc = h->d_Tout.alloc(B * 64)) || (rc = h->d_outlier.alloc(B * NP)) || (rc = h->d_ninl.alloc(B * 4)) || (rc = h->d_stats.alloc(B * 8)) ||
+        (rc = h->d_T.alloc(64)) || (rc = h->d_Xw.alloc(NP * 12)) || (rc = h->d_obs.alloc(NP * 12)) || (rc = h->d_inv.alloc(NP * 4)) || (rc = h->d_has.alloc(NP))) {
+        delete h;
+        return rc;
+    }
     h->stage = pose_lds_bytes(NP, true) <= kPoseLdsBudget;
     OSLAM_HIP_CHECK(hipFuncSetAttribute((const void*)k_pose_optimize<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pose_lds_bytes(NP, false)));
     OSLAM_HIP_CHECK(hipFuncSetAttribute((const void*)k_pose_optimize<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pose_lds_bytes(NP, false)));
@@ -971,11 +948,10 @@ int oslam_poseopt_trace(oslam_poseopt_t* h, int cap) {
     if (!h || cap < 0) { set_error("oslam_poseopt_trace: bad argument"); return OSLAM_E_INVALID; }
     OSLAM_HIP_CHECK(hipSetDevice(h->device));
     OSLAM_HIP_CHECK(hipDeviceSynchronize());
-    if (h->d_trace) (void)hipFree(h->d_trace);
-    h->d_trace = nullptr; h->trace_cap = 0;
+    h->d_trace.release(); h->trace_cap = 0;
     if (cap == 0) return OSLAM_OK;
-    OSLAM_HIP_CHECK(hipMalloc((void**)&h->d_trace, sizeof(double) * (1 + 6 * (size_t)cap)));
-    OSLAM_HIP_CHECK(hipMemset(h->d_trace, 0, sizeof(double) * (1 + 6 * (size_t)cap)));
+    OSLAM_CHECK(h->d_trace.alloc(sizeof(double) * (1 + 6 * (size_t)cap)));
+    OSLAM_HIP_CHECK(hipMemset(h->d_trace.as<double>(), 0, sizeof(double) * (1 + 6 * (size_t)cap)));
     h->trace_cap = cap;
     return OSLAM_OK;
 }
@@ -983,13 +959,13 @@ int oslam_poseopt_trace(oslam_poseopt_t* h, int cap) {
 // Copies the trace out ([cap][6] doubles: F before the trial, F of the trial, rho, lambda of the trial, accepted, first trial of a round), returns the number of trials seen
 // since the last read in *n (it can exceed cap: only the first cap are kept) and clears the trace.
 int oslam_poseopt_trace_read(oslam_poseopt_t* h, double* out, int32_t* n) {
-    if (!h || !out || !n || !h->d_trace) { set_error("oslam_poseopt_trace_read: no trace"); return OSLAM_E_INVALID; }
+    if (!h || !out || !n || !h->d_trace.ptr()) { set_error("oslam_poseopt_trace_read: no trace"); return OSLAM_E_INVALID; }
     OSLAM_HIP_CHECK(hipSetDevice(h->device));
     OSLAM_HIP_CHECK(hipDeviceSynchronize());
     double cnt = 0;
-    OSLAM_HIP_CHECK(hipMemcpy(&cnt, h->d_trace, sizeof(double), hipMemcpyDeviceToHost));
-    OSLAM_HIP_CHECK(hipMemcpy(out, h->d_trace + 1, sizeof(double) * 6 * (size_t)h->trace_cap, hipMemcpyDeviceToHost));
-    OSLAM_HIP_CHECK(hipMemset(h->d_trace, 0, sizeof(double)));
+    OSLAM_HIP_CHECK(hipMemcpy(&cnt, h->d_trace.as<double>(), sizeof(double), hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(out, h->d_trace.as<double>() + 1, sizeof(double) * 6 * (size_t)h->trace_cap, hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemset(h->d_trace.as<double>(), 0, sizeof(double)));
     *n = (int32_t)cnt;
     return OSLAM_OK;
 }
@@ -1005,7 +981,7 @@ int oslam_pose_optimize_batch_device(oslam_poseopt_t* h, int batch, int stride, 
     c.Tcw = d_Tcw; c.Xw = d_Xw; c.obs = d_obs; c.invSigma2 = d_invSigma2; c.has_mp = d_has_mp;
     c.n = d_n; c.n_const = n_const; c.stride = stride;
     c.fx = K5[0]; c.fy = K5[1]; c.cx = K5[2]; c.cy = K5[3]; c.bf = K5[4];
-    c.Tcw_out = h->d_Tout; c.outlier = h->d_outlier; c.n_inliers = h->d_ninl; c.stats = h->d_stats; c.trace = h->d_trace; c.trace_cap = h->trace_cap;
+    c.Tcw_out = h->d_Tout.as<float>(); c.outlier = h->d_outlier.bytes(); c.n_inliers = h->d_ninl.as<int>(); c.stats = h->d_stats.as<int>(); c.trace = h->d_trace.as<double>(); c.trace_cap = h->trace_cap;
     memset(&c.sem, 0, sizeof(c.sem));
     if (h->stage) hipLaunchKernelGGL((k_pose_optimize<false, true>), dim3(batch), dim3(kPoseThreads), pose_lds_bytes(stride, true), (hipStream_t)stream, c);
     else hipLaunchKernelGGL((k_pose_optimize<false, false>), dim3(batch), dim3(kPoseThreads), pose_lds_bytes(stride, false), (hipStream_t)stream, c);
@@ -1016,10 +992,10 @@ int oslam_pose_optimize_batch_device(oslam_poseopt_t* h, int batch, int stride, 
 int oslam_poseopt_results_device(const oslam_poseopt_t* h, const float** d_Tcw_out, const uint8_t** d_outlier, const int32_t** d_n_inliers,
                                  const int32_t** d_stats) {
     if (!h) { set_error("NULL handle"); return OSLAM_E_INVALID; }
-    if (d_Tcw_out) *d_Tcw_out = h->d_Tout;
-    if (d_outlier) *d_outlier = h->d_outlier;
-    if (d_n_inliers) *d_n_inliers = h->d_ninl;
-    if (d_stats) *d_stats = h->d_stats;
+    if (d_Tcw_out) *d_Tcw_out = h->d_Tout.as<float>();
+    if (d_outlier) *d_outlier = h->d_outlier.bytes();
+    if (d_n_inliers) *d_n_inliers = h->d_ninl.as<int>();
+    if (d_stats) *d_stats = h->d_stats.as<int>();
     return OSLAM_OK;
 }
 
@@ -1034,29 +1010,24 @@ int oslam_pose_optimize(oslam_poseopt_t* h, int N, const float Tcw_in[16], const
     const size_t a256 = 255;
     const size_t o_T = 0, o_X = 256, o_o = o_X + (((size_t)N * 12 + a256) & ~a256), o_i = o_o + (((size_t)N * 12 + a256) & ~a256),
                  o_h = o_i + (((size_t)N * 4 + a256) & ~a256), o_out = o_h + (((size_t)N + a256) & ~a256), total = o_out + 512 + (((size_t)N + a256) & ~a256);
-    if (total > h->pin_cap) {
-        if (h->h_pin) (void)hipHostFree(h->h_pin);
-        h->h_pin = nullptr; h->pin_cap = 0;
-        OSLAM_HIP_CHECK(hipHostMalloc((void**)&h->h_pin, total + total / 2, 0));
-        h->pin_cap = total + total / 2;
-    }
-    uint8_t* pin = h->h_pin;
+    OSLAM_CHECK(h->h_pin.grow(total, 0));
+    uint8_t* pin = h->h_pin.bytes();
     memcpy(pin + o_T, Tcw_in, 64);
-    OSLAM_HIP_CHECK(hipMemcpyAsync(h->d_T, pin + o_T, 64, hipMemcpyHostToDevice, nullptr));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(h->d_T.as<float>(), pin + o_T, 64, hipMemcpyHostToDevice, nullptr));
     if (N > 0) {
         memcpy(pin + o_X, Xw, (size_t)N * 12); memcpy(pin + o_o, obs, (size_t)N * 12); memcpy(pin + o_i, invSigma2, (size_t)N * 4); memcpy(pin + o_h, has_mp, (size_t)N);
-        OSLAM_HIP_CHECK(hipMemcpyAsync(h->d_Xw, pin + o_X, (size_t)N * 12, hipMemcpyHostToDevice, nullptr));
-        OSLAM_HIP_CHECK(hipMemcpyAsync(h->d_obs, pin + o_o, (size_t)N * 12, hipMemcpyHostToDevice, nullptr));
-        OSLAM_HIP_CHECK(hipMemcpyAsync(h->d_inv, pin + o_i, (size_t)N * 4, hipMemcpyHostToDevice, nullptr));
-        OSLAM_HIP_CHECK(hipMemcpyAsync(h->d_has, pin + o_h, (size_t)N, hipMemcpyHostToDevice, nullptr));
+        OSLAM_HIP_CHECK(hipMemcpyAsync(h->d_Xw.as<float>(), pin + o_X, (size_t)N * 12, hipMemcpyHostToDevice, nullptr));
+        OSLAM_HIP_CHECK(hipMemcpyAsync(h->d_obs.as<float>(), pin + o_o, (size_t)N * 12, hipMemcpyHostToDevice, nullptr));
+        OSLAM_HIP_CHECK(hipMemcpyAsync(h->d_inv.as<float>(), pin + o_i, (size_t)N * 4, hipMemcpyHostToDevice, nullptr));
+        OSLAM_HIP_CHECK(hipMemcpyAsync(h->d_has.bytes(), pin + o_h, (size_t)N, hipMemcpyHostToDevice, nullptr));
     }
-    int rc = oslam_pose_optimize_batch_device(h, 1, h->max_points, nullptr, N, h->d_T, h->d_Xw, h->d_obs, h->d_inv, h->d_has, K5, nullptr);
+    int rc = oslam_pose_optimize_batch_device(h, 1, h->max_points, nullptr, N, h->d_T.as<float>(), h->d_Xw.as<float>(), h->d_obs.as<float>(), h->d_inv.as<float>(), h->d_has.bytes(), K5, nullptr);
     if (rc) return rc;
     uint8_t* po = pin + o_out;   // [0,64) pose, [64,68) inliers, [128,136) stats, [512, 512+N) outlier flags
-    OSLAM_HIP_CHECK(hipMemcpyAsync(po, h->d_Tout, 64, hipMemcpyDeviceToHost, nullptr));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(po + 64, h->d_ninl, 4, hipMemcpyDeviceToHost, nullptr));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(po + 128, h->d_stats, 8, hipMemcpyDeviceToHost, nullptr));
-    if (N > 0) OSLAM_HIP_CHECK(hipMemcpyAsync(po + 512, h->d_outlier, (size_t)N, hipMemcpyDeviceToHost, nullptr));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(po, h->d_Tout.as<float>(), 64, hipMemcpyDeviceToHost, nullptr));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(po + 64, h->d_ninl.as<int>(), 4, hipMemcpyDeviceToHost, nullptr));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(po + 128, h->d_stats.as<int>(), 8, hipMemcpyDeviceToHost, nullptr));
+    if (N > 0) OSLAM_HIP_CHECK(hipMemcpyAsync(po + 512, h->d_outlier.bytes(), (size_t)N, hipMemcpyDeviceToHost, nullptr));
     OSLAM_HIP_CHECK(hipStreamSynchronize(nullptr));
     memcpy(Tcw_out, po, 64);
     memcpy(n_inliers, po + 64, 4);
@@ -1080,64 +1051,64 @@ int oslam_pose_optimize2(oslam_poseopt_t* h, int N, const float Tcw_in[16], cons
     const size_t nrows = (size_t)sem->nObj * sem->H;
     const size_t nsemcap = (size_t)sem->nJoint + sem->nObjMp;
     int rc;
-    if ((rc = ensure(h->masks, npx + 1)) || (rc = ensure(h->area, (npx + 1) * sizeof(short2))) || (rc = ensure(h->rowcnt, (nrows + 1) * 4)) ||
-        (rc = ensure(h->objcnt, ((size_t)sem->nObj + 1) * 4)) ||
-        (rc = ensure(h->area_start, ((size_t)sem->nObj + 2) * 4)) || (rc = ensure(h->objmp_Xw, (size_t)sem->nObjMp * 12 + 12)) ||
-        (rc = ensure(h->objmp_obj, (size_t)sem->nObjMp * 4 + 4)) || (rc = ensure(h->joint_kp, (size_t)sem->nJoint * 4 + 4)) ||
-        (rc = ensure(h->joint_obj, (size_t)sem->nJoint * 4 + 4)) || (rc = ensure(h->kp_uv, (size_t)N * 8 + 8)) ||
-        (rc = ensure(h->eXw, nsemcap * 12 + 12)) || (rc = ensure(h->eobs, nsemcap * 8 + 8)) || (rc = ensure(h->elevel, nsemcap + 1)) ||
-        (rc = ensure(h->echi2, nsemcap * 8 + 8)) || (rc = ensure(h->eobj, nsemcap * 4 + 4)) || (rc = ensure(h->eout, nsemcap + 1)) ||
-        (rc = ensure(h->etmp, nsemcap * 4 + 4)) || (rc = ensure(h->nsem, 4)))
+    if ((rc = h->masks.grow(npx + 1, 256)) || (rc = h->area.grow((npx + 1) * sizeof(short2), 256)) || (rc = h->rowcnt.grow((nrows + 1) * 4, 256)) ||
+        (rc = h->objcnt.grow(((size_t)sem->nObj + 1) * 4, 256)) ||
+        (rc = h->area_start.grow(((size_t)sem->nObj + 2) * 4, 256)) || (rc = h->objmp_Xw.grow((size_t)sem->nObjMp * 12 + 12, 256)) ||
+        (rc = h->objmp_obj.grow((size_t)sem->nObjMp * 4 + 4, 256)) || (rc = h->joint_kp.grow((size_t)sem->nJoint * 4 + 4, 256)) ||
+        (rc = h->joint_obj.grow((size_t)sem->nJoint * 4 + 4, 256)) || (rc = h->kp_uv.grow((size_t)N * 8 + 8, 256)) ||
+        (rc = h->eXw.grow(nsemcap * 12 + 12, 256)) || (rc = h->eobs.grow(nsemcap * 8 + 8, 256)) || (rc = h->elevel.grow(nsemcap + 1, 256)) ||
+        (rc = h->echi2.grow(nsemcap * 8 + 8, 256)) || (rc = h->eobj.grow(nsemcap * 4 + 4, 256)) || (rc = h->eout.grow(nsemcap + 1, 256)) ||
+        (rc = h->etmp.grow(nsemcap * 4 + 4, 256)) || (rc = h->nsem.grow(4, 256)))
         return rc;
 
-    OSLAM_HIP_CHECK(hipMemcpy(h->d_T, Tcw_in, 64, hipMemcpyHostToDevice));
+    OSLAM_HIP_CHECK(hipMemcpy(h->d_T.as<float>(), Tcw_in, 64, hipMemcpyHostToDevice));
     if (N > 0) {
-        OSLAM_HIP_CHECK(hipMemcpy(h->d_Xw, Xw, (size_t)N * 12, hipMemcpyHostToDevice));
-        OSLAM_HIP_CHECK(hipMemcpy(h->d_obs, obs, (size_t)N * 12, hipMemcpyHostToDevice));
-        OSLAM_HIP_CHECK(hipMemcpy(h->d_inv, invSigma2, (size_t)N * 4, hipMemcpyHostToDevice));
-        OSLAM_HIP_CHECK(hipMemcpy(h->d_has, has_mp, (size_t)N, hipMemcpyHostToDevice));
-        if (sem->kp_uv) OSLAM_HIP_CHECK(hipMemcpy((float*)h->kp_uv.p, sem->kp_uv, (size_t)N * 8, hipMemcpyHostToDevice));
+        OSLAM_HIP_CHECK(hipMemcpy(h->d_Xw.as<float>(), Xw, (size_t)N * 12, hipMemcpyHostToDevice));
+        OSLAM_HIP_CHECK(hipMemcpy(h->d_obs.as<float>(), obs, (size_t)N * 12, hipMemcpyHostToDevice));
+        OSLAM_HIP_CHECK(hipMemcpy(h->d_inv.as<float>(), invSigma2, (size_t)N * 4, hipMemcpyHostToDevice));
+        OSLAM_HIP_CHECK(hipMemcpy(h->d_has.bytes(), has_mp, (size_t)N, hipMemcpyHostToDevice));
+        if (sem->kp_uv) OSLAM_HIP_CHECK(hipMemcpy((float*)h->kp_uv.ptr(), sem->kp_uv, (size_t)N * 8, hipMemcpyHostToDevice));
     }
-    if (npx) OSLAM_HIP_CHECK(hipMemcpy((uint8_t*)h->masks.p, sem->masks, npx, hipMemcpyHostToDevice));
+    if (npx) OSLAM_HIP_CHECK(hipMemcpy((uint8_t*)h->masks.ptr(), sem->masks, npx, hipMemcpyHostToDevice));
     if (sem->nObjMp) {
-        OSLAM_HIP_CHECK(hipMemcpy((float*)h->objmp_Xw.p, sem->objmp_Xw, (size_t)sem->nObjMp * 12, hipMemcpyHostToDevice));
-        OSLAM_HIP_CHECK(hipMemcpy((int*)h->objmp_obj.p, sem->objmp_obj, (size_t)sem->nObjMp * 4, hipMemcpyHostToDevice));
+        OSLAM_HIP_CHECK(hipMemcpy((float*)h->objmp_Xw.ptr(), sem->objmp_Xw, (size_t)sem->nObjMp * 12, hipMemcpyHostToDevice));
+        OSLAM_HIP_CHECK(hipMemcpy((int*)h->objmp_obj.ptr(), sem->objmp_obj, (size_t)sem->nObjMp * 4, hipMemcpyHostToDevice));
     }
     if (sem->nJoint) {
-        OSLAM_HIP_CHECK(hipMemcpy((int*)h->joint_kp.p, sem->joint_kp, (size_t)sem->nJoint * 4, hipMemcpyHostToDevice));
-        OSLAM_HIP_CHECK(hipMemcpy((int*)h->joint_obj.p, sem->joint_obj, (size_t)sem->nJoint * 4, hipMemcpyHostToDevice));
+        OSLAM_HIP_CHECK(hipMemcpy((int*)h->joint_kp.ptr(), sem->joint_kp, (size_t)sem->nJoint * 4, hipMemcpyHostToDevice));
+        OSLAM_HIP_CHECK(hipMemcpy((int*)h->joint_obj.ptr(), sem->joint_obj, (size_t)sem->nJoint * 4, hipMemcpyHostToDevice));
     }
     if (sem->nObj > 0 && sem->H > 0 && sem->W > 0) {
-        hipLaunchKernelGGL(k_mask_rowcount, dim3(sem->H, sem->nObj), dim3(64), 0, nullptr, (uint8_t*)h->masks.p, nullptr, sem->H, sem->W, sem->W, (int*)h->rowcnt.p);
-        hipLaunchKernelGGL(k_mask_rowscan, dim3(sem->nObj), dim3(64), 0, nullptr, sem->H, (int*)h->rowcnt.p, (int*)h->objcnt.p);
-        hipLaunchKernelGGL(k_mask_objscan, dim3(1), dim3(64), 0, nullptr, sem->nObj, (int*)h->objcnt.p, (int*)h->area_start.p);
-        hipLaunchKernelGGL(k_mask_fill, dim3(sem->H, sem->nObj), dim3(64), 0, nullptr, (uint8_t*)h->masks.p, nullptr, sem->H, sem->W, sem->W, (int*)h->rowcnt.p, (int*)h->area_start.p, (short2*)h->area.p);
+        hipLaunchKernelGGL(k_mask_rowcount, dim3(sem->H, sem->nObj), dim3(64), 0, nullptr, (uint8_t*)h->masks.ptr(), nullptr, sem->H, sem->W, sem->W, (int*)h->rowcnt.ptr());
+        hipLaunchKernelGGL(k_mask_rowscan, dim3(sem->nObj), dim3(64), 0, nullptr, sem->H, (int*)h->rowcnt.ptr(), (int*)h->objcnt.ptr());
+        hipLaunchKernelGGL(k_mask_objscan, dim3(1), dim3(64), 0, nullptr, sem->nObj, (int*)h->objcnt.ptr(), (int*)h->area_start.ptr());
+        hipLaunchKernelGGL(k_mask_fill, dim3(sem->H, sem->nObj), dim3(64), 0, nullptr, (uint8_t*)h->masks.ptr(), nullptr, sem->H, sem->W, sem->W, (int*)h->rowcnt.ptr(), (int*)h->area_start.ptr(), (short2*)h->area.ptr());
     } else {
-        OSLAM_HIP_CHECK(hipMemset((int*)h->area_start.p, 0, 2 * sizeof(int)));
+        OSLAM_HIP_CHECK(hipMemset((int*)h->area_start.ptr(), 0, 2 * sizeof(int)));
     }
     PoseCtx c;
-    c.Tcw = h->d_T; c.Xw = h->d_Xw; c.obs = h->d_obs; c.invSigma2 = h->d_inv; c.has_mp = h->d_has;
+    c.Tcw = h->d_T.as<float>(); c.Xw = h->d_Xw.as<float>(); c.obs = h->d_obs.as<float>(); c.invSigma2 = h->d_inv.as<float>(); c.has_mp = h->d_has.bytes();
     c.n = nullptr; c.n_const = N; c.stride = h->max_points;
     c.fx = K5[0]; c.fy = K5[1]; c.cx = K5[2]; c.cy = K5[3]; c.bf = K5[4];
-    c.Tcw_out = h->d_Tout; c.outlier = h->d_outlier; c.n_inliers = h->d_ninl; c.stats = h->d_stats; c.trace = h->d_trace; c.trace_cap = h->trace_cap;
+    c.Tcw_out = h->d_Tout.as<float>(); c.outlier = h->d_outlier.bytes(); c.n_inliers = h->d_ninl.as<int>(); c.stats = h->d_stats.as<int>(); c.trace = h->d_trace.as<double>(); c.trace_cap = h->trace_cap;
     SemCtx& sm = c.sem;
     memset(&sm, 0, sizeof(sm));   // every optional pointer (bitmaps, frame table, pointer table) off unless set below
-    sm.nObj = sem->nObj; sm.area = (short2*)h->area.p; sm.area_start = (int*)h->area_start.p; sm.row_start = (int*)h->rowcnt.p;
-    sm.masks = (const uint8_t*)h->masks.p; sm.mask_ptrs = nullptr; sm.H = sem->H; sm.W = sem->W; sm.pitch = sem->W;
-    sm.nObjMp = sem->nObjMp; sm.objmp_Xw = (float*)h->objmp_Xw.p; sm.objmp_obj = (int*)h->objmp_obj.p;
-    sm.nJoint = sem->nJoint; sm.joint_kp = (int*)h->joint_kp.p; sm.joint_obj = (int*)h->joint_obj.p; sm.kp_uv = (float*)h->kp_uv.p;
+    sm.nObj = sem->nObj; sm.area = (short2*)h->area.ptr(); sm.area_start = (int*)h->area_start.ptr(); sm.row_start = (int*)h->rowcnt.ptr();
+    sm.masks = (const uint8_t*)h->masks.ptr(); sm.mask_ptrs = nullptr; sm.H = sem->H; sm.W = sem->W; sm.pitch = sem->W;
+    sm.nObjMp = sem->nObjMp; sm.objmp_Xw = (float*)h->objmp_Xw.ptr(); sm.objmp_obj = (int*)h->objmp_obj.ptr();
+    sm.nJoint = sem->nJoint; sm.joint_kp = (int*)h->joint_kp.ptr(); sm.joint_obj = (int*)h->joint_obj.ptr(); sm.kp_uv = (float*)h->kp_uv.ptr();
     sm.minX = sem->bounds[0]; sm.minY = sem->bounds[1]; sm.maxX = sem->bounds[2]; sm.maxY = sem->bounds[3]; sm.invSigma2_0 = sem->invSigma2_0;
-    sm.e_Xw = (float*)h->eXw.p; sm.e_obs = (float*)h->eobs.p; sm.e_level = (uint8_t*)h->elevel.p; sm.e_chi2 = (double*)h->echi2.p; sm.e_obj = (int*)h->eobj.p; sm.e_out = (uint8_t*)h->eout.p; sm.e_tmp = (int*)h->etmp.p;
-    sm.nSem = (int*)h->nsem.p;
+    sm.e_Xw = (float*)h->eXw.ptr(); sm.e_obs = (float*)h->eobs.ptr(); sm.e_level = (uint8_t*)h->elevel.ptr(); sm.e_chi2 = (double*)h->echi2.ptr(); sm.e_obj = (int*)h->eobj.ptr(); sm.e_out = (uint8_t*)h->eout.ptr(); sm.e_tmp = (int*)h->etmp.ptr();
+    sm.nSem = (int*)h->nsem.ptr();
     sm.frames = nullptr;
     if (h->stage) hipLaunchKernelGGL((k_pose_optimize<true, true>), dim3(1), dim3(kPoseThreads), pose_lds_bytes(h->max_points, true), nullptr, c);
     else hipLaunchKernelGGL((k_pose_optimize<true, false>), dim3(1), dim3(kPoseThreads), pose_lds_bytes(h->max_points, false), nullptr, c);
     OSLAM_HIP_CHECK(hipGetLastError());
     OSLAM_HIP_CHECK(hipDeviceSynchronize());
-    OSLAM_HIP_CHECK(hipMemcpy(Tcw_out, h->d_Tout, 64, hipMemcpyDeviceToHost));
-    OSLAM_HIP_CHECK(hipMemcpy(n_inliers, h->d_ninl, 4, hipMemcpyDeviceToHost));
-    OSLAM_HIP_CHECK(hipMemcpy(n_semantic, (int*)h->nsem.p, 4, hipMemcpyDeviceToHost));
-    if (N > 0) OSLAM_HIP_CHECK(hipMemcpy(outlier, h->d_outlier, (size_t)N, hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(Tcw_out, h->d_Tout.as<float>(), 64, hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(n_inliers, h->d_ninl.as<int>(), 4, hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(n_semantic, (int*)h->nsem.ptr(), 4, hipMemcpyDeviceToHost));
+    if (N > 0) OSLAM_HIP_CHECK(hipMemcpy(outlier, h->d_outlier.bytes(), (size_t)N, hipMemcpyDeviceToHost));
     return OSLAM_OK;
 }
 
@@ -1163,40 +1134,40 @@ int oslam_pose_optimize2_batch_device(oslam_poseopt_t* h, int batch, int stride,
     hipStream_t st = (hipStream_t)stream;
     const size_t npx = (size_t)total_obj * H * W, nrows = (size_t)total_obj * H, nsemcap = (size_t)total_joint + total_objmp;
     int rc;
-    if ((rc = ensure(h->area, (npx + 1) * sizeof(short2))) || (rc = ensure(h->rowcnt, (nrows + 1) * 4)) || (rc = ensure(h->objcnt, ((size_t)total_obj + 1) * 4)) ||
-        (rc = ensure(h->area_start, ((size_t)total_obj + 2) * 4)) || (rc = ensure(h->eXw, nsemcap * 12 + 12)) || (rc = ensure(h->eobs, nsemcap * 8 + 8)) ||
-        (rc = ensure(h->elevel, nsemcap + 1)) || (rc = ensure(h->echi2, nsemcap * 8 + 8)) || (rc = ensure(h->eobj, nsemcap * 4 + 4)) || (rc = ensure(h->eout, nsemcap + 1)) ||
-        (rc = ensure(h->etmp, nsemcap * 4 + 4)) || (rc = ensure(h->nsem, (size_t)h->max_batch * 4)))
+    if ((rc = h->area.grow((npx + 1) * sizeof(short2), 256)) || (rc = h->rowcnt.grow((nrows + 1) * 4, 256)) || (rc = h->objcnt.grow(((size_t)total_obj + 1) * 4, 256)) ||
+        (rc = h->area_start.grow(((size_t)total_obj + 2) * 4, 256)) || (rc = h->eXw.grow(nsemcap * 12 + 12, 256)) || (rc = h->eobs.grow(nsemcap * 8 + 8, 256)) ||
+        (rc = h->elevel.grow(nsemcap + 1, 256)) || (rc = h->echi2.grow(nsemcap * 8 + 8, 256)) || (rc = h->eobj.grow(nsemcap * 4 + 4, 256)) || (rc = h->eout.grow(nsemcap + 1, 256)) ||
+        (rc = h->etmp.grow(nsemcap * 4 + 4, 256)) || (rc = h->nsem.grow((size_t)h->max_batch * 4, 256)))
         return rc;
     if (total_obj > 0 && use_bits && use_index) {   // boundary lists from the one-bit-per-pixel masks (oslam_poseopt_use_mask_bits)
         const int WB = (W + 63) / 64;
-        hipLaunchKernelGGL(k_mask_rowcount_bits, dim3(div_up(H, 256), total_obj), dim3(256), 0, st, use_bits, use_index, H, WB, (int*)h->rowcnt.p);
-        hipLaunchKernelGGL(k_mask_rowscan, dim3(total_obj), dim3(64), 0, st, H, (int*)h->rowcnt.p, (int*)h->objcnt.p);
-        hipLaunchKernelGGL(k_mask_objscan, dim3(1), dim3(64), 0, st, total_obj, (int*)h->objcnt.p, (int*)h->area_start.p);
-        hipLaunchKernelGGL(k_mask_fill_bits, dim3(div_up(H, 256), total_obj), dim3(256), 0, st, use_bits, use_index, H, WB, (int*)h->rowcnt.p, (int*)h->area_start.p,
-                           (short2*)h->area.p);
+        hipLaunchKernelGGL(k_mask_rowcount_bits, dim3(div_up(H, 256), total_obj), dim3(256), 0, st, use_bits, use_index, H, WB, (int*)h->rowcnt.ptr());
+        hipLaunchKernelGGL(k_mask_rowscan, dim3(total_obj), dim3(64), 0, st, H, (int*)h->rowcnt.ptr(), (int*)h->objcnt.ptr());
+        hipLaunchKernelGGL(k_mask_objscan, dim3(1), dim3(64), 0, st, total_obj, (int*)h->objcnt.ptr(), (int*)h->area_start.ptr());
+        hipLaunchKernelGGL(k_mask_fill_bits, dim3(div_up(H, 256), total_obj), dim3(256), 0, st, use_bits, use_index, H, WB, (int*)h->rowcnt.ptr(), (int*)h->area_start.ptr(),
+                           (short2*)h->area.ptr());
     } else if (total_obj > 0) {
-        hipLaunchKernelGGL(k_mask_rowcount, dim3(H, total_obj), dim3(64), 0, st, nullptr, d_mask_ptrs, H, W, mask_pitch, (int*)h->rowcnt.p);
-        hipLaunchKernelGGL(k_mask_rowscan, dim3(total_obj), dim3(64), 0, st, H, (int*)h->rowcnt.p, (int*)h->objcnt.p);
-        hipLaunchKernelGGL(k_mask_objscan, dim3(1), dim3(64), 0, st, total_obj, (int*)h->objcnt.p, (int*)h->area_start.p);
-        hipLaunchKernelGGL(k_mask_fill, dim3(H, total_obj), dim3(64), 0, st, nullptr, d_mask_ptrs, H, W, mask_pitch, (int*)h->rowcnt.p, (int*)h->area_start.p, (short2*)h->area.p);
+        hipLaunchKernelGGL(k_mask_rowcount, dim3(H, total_obj), dim3(64), 0, st, nullptr, d_mask_ptrs, H, W, mask_pitch, (int*)h->rowcnt.ptr());
+        hipLaunchKernelGGL(k_mask_rowscan, dim3(total_obj), dim3(64), 0, st, H, (int*)h->rowcnt.ptr(), (int*)h->objcnt.ptr());
+        hipLaunchKernelGGL(k_mask_objscan, dim3(1), dim3(64), 0, st, total_obj, (int*)h->objcnt.ptr(), (int*)h->area_start.ptr());
+        hipLaunchKernelGGL(k_mask_fill, dim3(H, total_obj), dim3(64), 0, st, nullptr, d_mask_ptrs, H, W, mask_pitch, (int*)h->rowcnt.ptr(), (int*)h->area_start.ptr(), (short2*)h->area.ptr());
     } else {
-        OSLAM_HIP_CHECK(hipMemsetAsync((int*)h->area_start.p, 0, 2 * sizeof(int), st));
+        OSLAM_HIP_CHECK(hipMemsetAsync((int*)h->area_start.ptr(), 0, 2 * sizeof(int), st));
     }
     PoseCtx c;
     c.Tcw = d_Tcw; c.Xw = d_Xw; c.obs = d_obs; c.invSigma2 = d_invSigma2; c.has_mp = d_has_mp;
     c.n = d_n; c.n_const = 0; c.stride = stride;
     c.fx = K5[0]; c.fy = K5[1]; c.cx = K5[2]; c.cy = K5[3]; c.bf = K5[4];
-    c.Tcw_out = h->d_Tout; c.outlier = h->d_outlier; c.n_inliers = h->d_ninl; c.stats = h->d_stats; c.trace = h->d_trace; c.trace_cap = h->trace_cap;
+    c.Tcw_out = h->d_Tout.as<float>(); c.outlier = h->d_outlier.bytes(); c.n_inliers = h->d_ninl.as<int>(); c.stats = h->d_stats.as<int>(); c.trace = h->d_trace.as<double>(); c.trace_cap = h->trace_cap;
     SemCtx& sm = c.sem;
     memset(&sm, 0, sizeof(sm));
-    sm.area = (short2*)h->area.p; sm.area_start = (int*)h->area_start.p; sm.row_start = (int*)h->rowcnt.p;
+    sm.area = (short2*)h->area.ptr(); sm.area_start = (int*)h->area_start.ptr(); sm.row_start = (int*)h->rowcnt.ptr();
     sm.masks = nullptr; sm.mask_ptrs = d_mask_ptrs; sm.H = H; sm.W = W; sm.pitch = mask_pitch;
     if (total_obj > 0 && use_bits && use_index) { sm.bits = use_bits; sm.bits_index = use_index; sm.WB = (W + 63) / 64; }
     sm.objmp_Xw = d_objmp_Xw; sm.objmp_obj = d_objmp_obj; sm.joint_kp = d_joint_kp; sm.joint_obj = d_joint_obj; sm.kp_uv = nullptr;
     sm.minX = bounds[0]; sm.minY = bounds[1]; sm.maxX = bounds[2]; sm.maxY = bounds[3]; sm.invSigma2_0 = invSigma2_0;
-    sm.e_Xw = (float*)h->eXw.p; sm.e_obs = (float*)h->eobs.p; sm.e_level = (uint8_t*)h->elevel.p; sm.e_chi2 = (double*)h->echi2.p; sm.e_obj = (int*)h->eobj.p;
-    sm.e_out = (uint8_t*)h->eout.p; sm.e_tmp = (int*)h->etmp.p; sm.nSem = (int*)h->nsem.p; sm.frames = d_frames;
+    sm.e_Xw = (float*)h->eXw.ptr(); sm.e_obs = (float*)h->eobs.ptr(); sm.e_level = (uint8_t*)h->elevel.ptr(); sm.e_chi2 = (double*)h->echi2.ptr(); sm.e_obj = (int*)h->eobj.ptr();
+    sm.e_out = (uint8_t*)h->eout.ptr(); sm.e_tmp = (int*)h->etmp.ptr(); sm.nSem = (int*)h->nsem.ptr(); sm.frames = d_frames;
     if (h->stage) hipLaunchKernelGGL((k_pose_optimize<true, true>), dim3(batch), dim3(kPoseThreads), pose_lds_bytes(stride, true), st, c);
     else hipLaunchKernelGGL((k_pose_optimize<true, false>), dim3(batch), dim3(kPoseThreads), pose_lds_bytes(stride, false), st, c);
     OSLAM_HIP_CHECK(hipGetLastError());
@@ -1205,7 +1176,7 @@ int oslam_pose_optimize2_batch_device(oslam_poseopt_t* h, int batch, int stride,
 
 int oslam_poseopt_semantic_results_device(const oslam_poseopt_t* h, const int32_t** d_n_semantic) {
     if (!h || !d_n_semantic) { set_error("NULL argument"); return OSLAM_E_INVALID; }
-    *d_n_semantic = (const int32_t*)h->nsem.p;
+    *d_n_semantic = (const int32_t*)h->nsem.ptr();
     return OSLAM_OK;
 }
 

@@ -20,6 +20,8 @@
 
 namespace {
 
+#define OPS_CHECK(x) OSLAM_CHECK(x)
+
 struct LbaService;
 struct LbaJob {   // one handle's submission to the local-BA service (below)
     int n = 0; const oslam_lba_problem_t* probs = nullptr; float K5[5] = {0, 0, 0, 0, 0};
@@ -35,7 +37,7 @@ struct HipOps {
     oslam_orb_t* orb = nullptr;
     oslam_orb_t* orbR = nullptr;          // STEREO: right image extractor (src/Tracking.cc:145)
     oslam_stereo_t* stereo = nullptr;
-    uint8_t* d_grayR = nullptr;
+    oslam::DeviceBuffer d_grayR;          // uint8_t
     const float* cur_uRight = nullptr;    // mvuRight of the current batch on the device (RGB-D: d_uRight, STEREO: the stereo matcher's output)
     oslam_matcher_t* m_last = nullptr;
     oslam_matcher_t* m_map = nullptr;
@@ -51,61 +53,59 @@ struct HipOps {
     float logScale;
     int max_local = 0;
     // device-resident batch state of the current step
-    uint8_t* d_gray = nullptr; float* d_depth = nullptr; size_t gray_pitch = 0;
-    oslam_keypoint_t* d_keysUn_prev = nullptr;   // mvKeysUn of the PREVIOUS step's frames (the buffers swap at every Frame::Frame stage): the last frames of search_last
-    oslam_keypoint_t* d_keysUn = nullptr; float* d_uRight = nullptr; float* d_mvDepth = nullptr; int32_t* d_status = nullptr;
+    oslam::DeviceBuffer d_gray, d_depth; size_t gray_pitch = 0;   // uint8_t, float
+    oslam::DeviceBuffer d_keysUn_prev;           // oslam_keypoint_t: mvKeysUn of the PREVIOUS step's frames (the buffers swap at every Frame::Frame stage): the last frames of search_last
+    oslam::DeviceBuffer d_keysUn, d_uRight, d_mvDepth, d_status;   // oslam_keypoint_t, float, float, int32_t
     const oslam_keypoint_t* d_kp = nullptr; const uint8_t* d_desc = nullptr; const int32_t* d_cnt = nullptr;
     std::vector<oslam_proj_query_t> q;
     std::vector<int32_t> qm, qd;
     // staging: one pinned upload block mirrored on the device, one pinned download block; a stage of the lockstep step is
     // fill (parallel memcpy) -> ONE host-to-device copy -> batch kernels -> result copies -> ONE synchronisation -> scatter
-    uint8_t* up_h = nullptr; uint8_t* up_d = nullptr; size_t up_cap = 0;
-    uint8_t* dn_h = nullptr; size_t dn_cap = 0;
+    oslam::StagePair up;
+    oslam::PinnedBuffer dn;
     // second staging set + event pair for the ONE deferred MapPoint update (mp_update_keyed_async): its job block is read in place by the kernel and its results
     // land in the pinned block while the next operator already uses the first set
-    uint8_t* upB_h = nullptr; uint8_t* upB_d = nullptr; size_t upB_cap = 0;
-    uint8_t* dnB_h = nullptr; size_t dnB_cap = 0;
+    oslam::StagePair upB;
+    oslam::PinnedBuffer dnB;
     hipEvent_t tevB0 = nullptr, tevB1 = nullptr;
     bool lazy_desc = false;                          // the same for mDescriptors (keyframe_descriptors / frame_descriptors)
     bool lazy_keys = false;                          // frames do not send mvKeys back; register_keyframes stages the new keyframes' rows for keyframe_raw_keys
-    uint8_t* kfk_h = nullptr; size_t kfk_cap = 0; std::vector<int32_t> kfk_slots;
+    oslam::PinnedBuffer kfk; std::vector<int32_t> kfk_slots;
     static constexpr int kFuseCurStride = 16384, kFuseCurPairs = 2048;   // candidates / matches per job of fuse_into_current (beyond: overflow, the driver's own path)
-    uint8_t* fc_d = nullptr; size_t fc_cap = 0; uint32_t fc_stamp = 0;
+    oslam::DeviceBuffer fc; uint32_t fc_stamp = 0;   // scratch of fuse_into_current / local_points_list
     struct MpuPending { bool on = false; oslam_job_mp_update_t* j = nullptr; size_t P = 0, rBest = 0, rOut = 0, rOut5 = 0; double dtotal = 0; std::function<int()> launch; } mpu_pend;
     int mpu_launch_pending() { if (mpu_pend.on && mpu_pend.launch) { std::function<int()> f; f.swap(mpu_pend.launch); return f(); } return OSLAM_OK; }
-    void swap_staging() { std::swap(up_h, upB_h); std::swap(up_d, upB_d); std::swap(up_cap, upB_cap); std::swap(dn_h, dnB_h); std::swap(dn_cap, dnB_cap); std::swap(tev0, tevB0); std::swap(tev1, tevB1); }
-    oslam_proj_query_t* d_lq = nullptr; uint8_t* d_inview = nullptr; size_t lq_cap = 0;
-    uint8_t* d_objbits = nullptr;                        // [S][cap] keypoint test bits (object_kps)
+    void swap_staging() { std::swap(up, upB); std::swap(dn, dnB); std::swap(tev0, tevB0); std::swap(tev1, tevB1); }
+    oslam::DeviceBuffer d_lq, d_inview;                  // oslam_proj_query_t, uint8_t: one entry per local query
+    oslam::DeviceBuffer d_objbits;                       // uint8_t [S][cap] keypoint test bits (object_kps)
     // Resident local maps: the packed SearchLocalPoints arrays of every slot stay on the device ([S][loc_st] each); a job whose content id equals the
     // slot's is not uploaded again (the driver repacks only when the sequence's local keyframe list or map changed)
-    uint8_t* d_loc = nullptr; size_t loc_st = 0;
+    oslam::DeviceBuffer d_loc; size_t loc_st = 0;
     std::vector<long long> loc_id;
-    float* loc_Pw() const { return (float*)d_loc; }
-    float* loc_Pn() const { return (float*)(d_loc + 12 * loc_st * S); }
-    float* loc_Max() const { return (float*)(d_loc + 24 * loc_st * S); }
-    float* loc_Min() const { return (float*)(d_loc + 28 * loc_st * S); }
-    uint8_t* loc_Obs() const { return d_loc + 32 * loc_st * S; }
-    uint8_t* loc_Desc() const { return d_loc + 33 * loc_st * S; }
+    float* loc_Pw() const { return d_loc.as<float>(); }
+    float* loc_Pn() const { return (float*)(d_loc.bytes() + 12 * loc_st * S); }
+    float* loc_Max() const { return (float*)(d_loc.bytes() + 24 * loc_st * S); }
+    float* loc_Min() const { return (float*)(d_loc.bytes() + 28 * loc_st * S); }
+    uint8_t* loc_Obs() const { return d_loc.bytes() + 32 * loc_st * S; }
+    uint8_t* loc_Desc() const { return d_loc.bytes() + 33 * loc_st * S; }
     int ensure_loc() {   // follows max_local
         const size_t want = oslam::align_up((size_t)std::max(max_local, 1), 64);
-        if (d_loc && loc_st == want) return OSLAM_OK;
+        if (d_loc.ptr() && loc_st == want) return OSLAM_OK;
         OSLAM_HIP_CHECK(hipStreamSynchronize(strm));
-        if (d_loc) (void)hipFree(d_loc);
-        d_loc = nullptr;
         loc_st = want;
-        OSLAM_HIP_CHECK(hipMalloc((void**)&d_loc, 65 * loc_st * S));
+        OPS_CHECK(d_loc.alloc(65 * loc_st * S));
         loc_id.assign(S, 0);
         return OSLAM_OK;
     }
     // Resident keyframe store: one record per keyframe = device copies of mvKeysUn | mDescriptors | mvuRight (cap entries each), in chunks of kRecChunk records
     static constexpr int kRecChunk = 256;
-    std::vector<uint8_t*> rec_chunks;
+    oslam::DeviceBlocks rec_chunks;
     std::vector<std::vector<int>> rec_of_kf;              // [slot][kf id] -> record index or -1
     long long n_released = 0;                             // records returned by release_keyframes (culled keyframes)
     std::vector<int32_t> mpu_rec;                         // scratch of mp_update_impl: (record, keypoint) of every observation
     std::vector<int> free_recs;                           // records of maps that were reset, reused before the store grows
     int n_rec = 0;
-    uint8_t** d_rec_desc = nullptr; size_t rec_desc_cap = 0; int rec_desc_n = 0;   // device table: descriptor array of every record (for k_gather_desc)
+    oslam::DeviceBuffer d_rec_desc; int rec_desc_n = 0;   // device table: descriptor array of every record (for k_gather_desc)
     std::vector<uint8_t*> h_rec_desc;
     // a record = mvKeysUn, descriptors, mvuRight and — built once at registration (oslam_kf_grid_build_device) — the feature grid: cell ends + candidates sorted by cell
     // (+ the mirror of the observation graph, round 5: the keyframe's point list, "which point observes keypoint i" and the usable-depth bits: oslam_slam_ops_t::map_journal)
@@ -116,56 +116,47 @@ struct HipOps {
     size_t rec_bytes() const { return rec_core_bytes() + oslam::align_up((size_t)cap * 4, 256) + oslam::align_up((size_t)cap * 8, 256) + oslam::align_up(((size_t)cap + 31) / 32 * 4, 256); }
     std::vector<uint32_t> okf_seq;                        // [S] event counter of the mirror's okf cells (a cell keeps the event with the largest number)
     size_t mir_used = 0;                                  // bytes of the mirror's upload block in use by the flush / count request in flight
-    uint8_t* cull_h = nullptr; size_t cull_cap = 0;       // pinned result block of kf_culling_counts
+    oslam::PinnedBuffer cull;                             // pinned result block of kf_culling_counts
     struct CullPending { int32_t* out; int n; };
     std::vector<CullPending> cull_pending;
-    uint8_t* mir_h = nullptr; uint8_t* mir_d = nullptr; size_t mir_cap = 0;   // the mirror's own upload block (map_journal returns without waiting: the consumer that follows on the stream does)
+    oslam::StagePair mir;   // the mirror's own upload block (map_journal returns without waiting: the consumer that follows on the stream does)
     int ensure_mir(size_t bytes) {
-        if (bytes <= mir_cap) return OSLAM_OK;
-        OSLAM_HIP_CHECK(hipStreamSynchronize(strm));
-        if (mir_h) (void)hipHostFree(mir_h);
-        if (mir_d) (void)hipFree(mir_d);
-        mir_h = nullptr; mir_d = nullptr; mir_cap = 0;
-        const size_t want = bytes + bytes / 2 + (1 << 20);
-        OSLAM_HIP_CHECK(hipHostMalloc((void**)&mir_h, want, 0));
-        OSLAM_HIP_CHECK(hipMalloc((void**)&mir_d, want));
-        mir_cap = want;
-        return OSLAM_OK;
+        if (bytes > mir.cap()) OSLAM_HIP_CHECK(hipStreamSynchronize(strm));
+        return mir.grow(bytes, 1 << 20);
     }
     int32_t* rec_mp(int r) const { return (int32_t*)(rec_ptr(r) + rec_core_bytes()); }
     // per-point scalars of the mirror: 32-byte records per slot, grown like the map-point table: (Observations(), isBad(), octave histogram) in the first 16 bytes,
     // then the transient marks of SearchInNeighbors' second direction (k_fusecur_*: 64-bit first-occurrence key, stamp of the current keyframe's points)
     static constexpr size_t kPtAuxBytes = 32;
-    std::vector<uint8_t*> pt_aux; std::vector<size_t> pt_aux_cap;
-    uint8_t** d_pt_aux = nullptr; uint8_t** d_rec_chunk = nullptr; size_t rec_chunk_cap = 0, rec_chunk_n = 0;
+    oslam::DeviceBlocks pt_aux; std::vector<size_t> pt_aux_cap;
+    oslam::DeviceBuffer d_pt_aux, d_rec_chunk; size_t rec_chunk_n = 0;   // uint8_t* [S], uint8_t* [chunks]: device copies of the two pointer tables
     bool pt_aux_dirty = true;
+    void size_pt_aux() { if ((int)pt_aux.size() < S) { pt_aux.resize(S); pt_aux_cap.resize(S, 0); pt_aux_dirty = true; } }
     int ensure_pt_aux(int slot, size_t need) {
-        if ((int)pt_aux.size() < S) { pt_aux.resize(S, nullptr); pt_aux_cap.resize(S, 0); }
+        size_pt_aux();
         if (need <= pt_aux_cap[slot]) return OSLAM_OK;
         const size_t ncap = std::max<size_t>(need * 2, 16384);
-        uint8_t* nb = nullptr;
-        OSLAM_HIP_CHECK(hipMalloc((void**)&nb, ncap * kPtAuxBytes));
-        OSLAM_HIP_CHECK(hipMemsetAsync(nb, 0, ncap * kPtAuxBytes, strm));
+        oslam::DeviceBuffer nb;
+        OPS_CHECK(nb.alloc(ncap * kPtAuxBytes));
+        OSLAM_HIP_CHECK(hipMemsetAsync(nb.ptr(), 0, ncap * kPtAuxBytes, strm));
         if (pt_aux[slot]) {
-            OSLAM_HIP_CHECK(hipMemcpyAsync(nb, pt_aux[slot], pt_aux_cap[slot] * kPtAuxBytes, hipMemcpyDeviceToDevice, strm));
+            OSLAM_HIP_CHECK(hipMemcpyAsync(nb.ptr(), pt_aux[slot], pt_aux_cap[slot] * kPtAuxBytes, hipMemcpyDeviceToDevice, strm));
             OSLAM_HIP_CHECK(hipStreamSynchronize(strm));
-            (void)hipFree(pt_aux[slot]);
         }
-        pt_aux[slot] = nb; pt_aux_cap[slot] = ncap; pt_aux_dirty = true;
+        pt_aux.put(slot, std::move(nb)); pt_aux_cap[slot] = ncap; pt_aux_dirty = true;
         return OSLAM_OK;
     }
     int sync_mirror_tables() {   // device copies of the per-slot aux pointers and of the record chunk pointers
-        if ((int)pt_aux.size() < S) { pt_aux.resize(S, nullptr); pt_aux_cap.resize(S, 0); pt_aux_dirty = true; }
-        if (!d_pt_aux) { OSLAM_HIP_CHECK(hipMalloc((void**)&d_pt_aux, sizeof(uint8_t*) * S)); pt_aux_dirty = true; }
-        if (pt_aux_dirty) { OSLAM_HIP_CHECK(hipMemcpyAsync(d_pt_aux, pt_aux.data(), sizeof(uint8_t*) * S, hipMemcpyHostToDevice, strm)); OSLAM_HIP_CHECK(hipStreamSynchronize(strm)); pt_aux_dirty = false; }
-        if (rec_chunks.size() > rec_chunk_cap) {
+        size_pt_aux();
+        if (!d_pt_aux.ptr()) { OPS_CHECK(d_pt_aux.alloc(sizeof(uint8_t*) * S)); pt_aux_dirty = true; }
+        if (pt_aux_dirty) { OSLAM_HIP_CHECK(hipMemcpyAsync(d_pt_aux.ptr(), pt_aux.data(), sizeof(uint8_t*) * S, hipMemcpyHostToDevice, strm)); OSLAM_HIP_CHECK(hipStreamSynchronize(strm)); pt_aux_dirty = false; }
+        if (sizeof(uint8_t*) * rec_chunks.size() > d_rec_chunk.cap()) {
             OSLAM_HIP_CHECK(hipStreamSynchronize(strm));
-            if (d_rec_chunk) (void)hipFree(d_rec_chunk);
-            rec_chunk_cap = rec_chunks.size() * 2 + 64; rec_chunk_n = 0;
-            OSLAM_HIP_CHECK(hipMalloc((void**)&d_rec_chunk, sizeof(uint8_t*) * rec_chunk_cap));
+            rec_chunk_n = 0;
+            OPS_CHECK(d_rec_chunk.alloc(sizeof(uint8_t*) * (rec_chunks.size() * 2 + 64)));
         }
         if (rec_chunk_n < rec_chunks.size()) {
-            OSLAM_HIP_CHECK(hipMemcpyAsync(d_rec_chunk + rec_chunk_n, rec_chunks.data() + rec_chunk_n, sizeof(uint8_t*) * (rec_chunks.size() - rec_chunk_n), hipMemcpyHostToDevice, strm));
+            OSLAM_HIP_CHECK(hipMemcpyAsync(d_rec_chunk.as<uint8_t*>() + rec_chunk_n, rec_chunks.data() + rec_chunk_n, sizeof(uint8_t*) * (rec_chunks.size() - rec_chunk_n), hipMemcpyHostToDevice, strm));
             OSLAM_HIP_CHECK(hipStreamSynchronize(strm));
             rec_chunk_n = rec_chunks.size();
         }
@@ -179,58 +170,46 @@ struct HipOps {
     float* rec_cand(int r) const { return (float*)((uint8_t*)rec_cell_end(r) + oslam::align_up((size_t)3072 * 2, 256)); }
     int rec_lookup(int slot, int kf) const { return (slot >= 0 && slot < (int)rec_of_kf.size() && kf >= 0 && kf < (int)rec_of_kf[slot].size()) ? rec_of_kf[slot][kf] : -1; }
     // Resident map points: one growing array of 64-byte records per slot (position, normal, distances, descriptor), written by every MapPoint update
-    std::vector<uint8_t*> mp_tab; std::vector<size_t> mp_cap;   // [S] device arrays and their capacity in records
-    uint8_t** d_mp_tab = nullptr;                               // [S] device copy of the pointers
+    oslam::DeviceBlocks mp_tab; std::vector<size_t> mp_cap;     // [S] device arrays and their capacity in records
+    oslam::DeviceBuffer d_mp_tab;                               // uint8_t* [S]: device copy of the pointers
     bool mp_tab_on = true, mp_tab_dirty = true;
     int ensure_mp_records(int slot, size_t need) {
-        if ((int)mp_tab.size() < S) { mp_tab.resize(S, nullptr); mp_cap.resize(S, 0); }
+        if ((int)mp_tab.size() < S) { mp_tab.resize(S); mp_cap.resize(S, 0); }
         if (need <= mp_cap[slot]) return OSLAM_OK;
         // 16 K records (1 MB) per sequence to start with, doubling: a growth costs an allocation, a device copy, a stream synchronisation and a free (measured:
         // 0.9 ms each, 22 s of the 64 s the MapPoint-update operator took in a 225-step run of 8 x 1024 sequences when the tables started at 4 K records x 1.5)
         const size_t ncap = std::max<size_t>(need * 2, 16384);
-        uint8_t* nb = nullptr;
-        OSLAM_HIP_CHECK(hipMalloc((void**)&nb, ncap * 64));
+        oslam::DeviceBuffer nb;
+        OPS_CHECK(nb.alloc(ncap * 64));
         if (mp_tab[slot]) {
-            OSLAM_HIP_CHECK(hipMemcpyAsync(nb, mp_tab[slot], mp_cap[slot] * 64, hipMemcpyDeviceToDevice, strm));
+            OSLAM_HIP_CHECK(hipMemcpyAsync(nb.ptr(), mp_tab[slot], mp_cap[slot] * 64, hipMemcpyDeviceToDevice, strm));
             OSLAM_HIP_CHECK(hipStreamSynchronize(strm));
-            (void)hipFree(mp_tab[slot]);
         }
-        mp_tab[slot] = nb; mp_cap[slot] = ncap; mp_tab_dirty = true;
+        mp_tab.put(slot, std::move(nb)); mp_cap[slot] = ncap; mp_tab_dirty = true;
         return OSLAM_OK;
     }
     int sync_mp_table() {   // the device pointer table follows the host's
-        if ((int)mp_tab.size() < S) { mp_tab.resize(S, nullptr); mp_cap.resize(S, 0); mp_tab_dirty = true; }
+        if ((int)mp_tab.size() < S) { mp_tab.resize(S); mp_cap.resize(S, 0); mp_tab_dirty = true; }
         if (!mp_tab_dirty) return OSLAM_OK;
-        if (!d_mp_tab) OSLAM_HIP_CHECK(hipMalloc((void**)&d_mp_tab, sizeof(uint8_t*) * (size_t)S));
-        OSLAM_HIP_CHECK(hipMemcpyAsync(d_mp_tab, mp_tab.data(), sizeof(uint8_t*) * (size_t)S, hipMemcpyHostToDevice, strm));
+        if (!d_mp_tab.ptr()) OPS_CHECK(d_mp_tab.alloc(sizeof(uint8_t*) * (size_t)S));
+        OSLAM_HIP_CHECK(hipMemcpyAsync(d_mp_tab.ptr(), mp_tab.data(), sizeof(uint8_t*) * (size_t)S, hipMemcpyHostToDevice, strm));
         OSLAM_HIP_CHECK(hipStreamSynchronize(strm));   // (mp_tab is pageable host memory: the copy must have read it before it can change again)
         mp_tab_dirty = false;
         return OSLAM_OK;
     }
-    uint8_t* d_maskstage = nullptr; size_t mask_cap = 0;  // host masks of a stage, packed H x W
+    oslam::DeviceBuffer d_maskstage;                      // uint8_t: host masks of a stage, packed H x W
     // One-bit-per-pixel form of the step's masks (oslam_mask_bits_device), built by object_kps and reused by pose_opt2 of the SAME step: keyed by the
     // caller's mask pointer, valid while step_epoch (advanced by every Frame::Frame stage) equals bits_epoch
-    uint64_t* d_maskbits = nullptr; size_t maskbits_cap = 0;
+    oslam::DeviceBuffer d_maskbits;   // uint64_t
     std::unordered_map<const uint8_t*, int> bits_of_ptr;
     long long step_epoch = 0, bits_epoch = -1;
     int ensure_maskbits(size_t words) {
-        if (words <= maskbits_cap) return OSLAM_OK;
-        OSLAM_HIP_CHECK(hipStreamSynchronize(strm));
-        if (d_maskbits) (void)hipFree(d_maskbits);
-        d_maskbits = nullptr; maskbits_cap = 0;
-        OSLAM_HIP_CHECK(hipMalloc((void**)&d_maskbits, (words + words / 4) * 8));
-        maskbits_cap = words + words / 4;
-        return OSLAM_OK;
+        if (words * 8 > d_maskbits.cap()) OSLAM_HIP_CHECK(hipStreamSynchronize(strm));
+        return d_maskbits.reserve(words * 8, (words + words / 4) * 8);
     }
     int ensure_masks(size_t bytes) {
-        if (bytes <= mask_cap) return OSLAM_OK;
-        OSLAM_HIP_CHECK(hipDeviceSynchronize());
-        if (d_maskstage) (void)hipFree(d_maskstage);
-        d_maskstage = nullptr; mask_cap = 0;
-        const size_t ncap = bytes + bytes / 2 + 4096;
-        OSLAM_HIP_CHECK(hipMalloc((void**)&d_maskstage, ncap));
-        mask_cap = ncap;
-        return OSLAM_OK;
+        if (bytes > d_maskstage.cap()) OSLAM_HIP_CHECK(hipDeviceSynchronize());
+        return d_maskstage.grow(bytes, 4096);
     }
     oslam_drv::Pool* pool = nullptr;
     hipStream_t strm = nullptr;   // this handle's stream (non-blocking): several handles on one GPU, each driven by its own host thread, overlap
@@ -245,39 +224,22 @@ struct HipOps {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, tev0, tev1) == hipSuccess) { kt[3 * g] += ms; kt[3 * g + 1] += launches; kt[3 * g + 2] += work; }
     }
+    // the staging blocks and the query buffers grow with everything on the device drained
     int ensure_up(size_t bytes) {
-        if (bytes <= up_cap) return OSLAM_OK;
-        OSLAM_HIP_CHECK(hipDeviceSynchronize());
-        if (up_h) (void)hipHostFree(up_h);
-        if (up_d) (void)hipFree(up_d);
-        up_h = nullptr; up_d = nullptr; up_cap = 0;
-        const size_t ncap = bytes + bytes / 2 + 4096;
-        OSLAM_HIP_CHECK(hipHostMalloc((void**)&up_h, ncap, 0));
-        OSLAM_HIP_CHECK(hipMalloc((void**)&up_d, ncap));
-        up_cap = ncap;
-        return OSLAM_OK;
+        if (bytes > up.cap()) OSLAM_HIP_CHECK(hipDeviceSynchronize());
+        return up.grow(bytes, 4096);
     }
     int ensure_dn(size_t bytes) {
-        if (bytes <= dn_cap) return OSLAM_OK;
-        OSLAM_HIP_CHECK(hipDeviceSynchronize());
-        if (dn_h) (void)hipHostFree(dn_h);
-        dn_h = nullptr; dn_cap = 0;
-        const size_t ncap = bytes + bytes / 2 + 4096;
-        OSLAM_HIP_CHECK(hipHostMalloc((void**)&dn_h, ncap, 0));
-        dn_cap = ncap;
-        return OSLAM_OK;
+        if (bytes > dn.cap()) OSLAM_HIP_CHECK(hipDeviceSynchronize());
+        return dn.grow(bytes, 4096);
     }
     int ensure_lq(size_t entries) {
-        if (entries <= lq_cap) return OSLAM_OK;
+        if (entries <= d_inview.cap()) return OSLAM_OK;   // (one byte per entry)
         OSLAM_HIP_CHECK(hipDeviceSynchronize());
-        if (d_lq) (void)hipFree(d_lq);
-        if (d_inview) (void)hipFree(d_inview);
-        d_lq = nullptr; d_inview = nullptr; lq_cap = 0;
+        d_lq.release(); d_inview.release();
         const size_t ncap = entries + entries / 2 + 1024;
-        OSLAM_HIP_CHECK(hipMalloc((void**)&d_lq, ncap * sizeof(oslam_proj_query_t)));
-        OSLAM_HIP_CHECK(hipMalloc((void**)&d_inview, ncap));
-        lq_cap = ncap;
-        return OSLAM_OK;
+        OPS_CHECK(d_lq.alloc(ncap * sizeof(oslam_proj_query_t)));
+        return d_inview.alloc(ncap);
     }
 };
 
@@ -286,8 +248,6 @@ struct Layout {
     size_t off = 0;
     size_t take(size_t bytes) { const size_t at = off; off += oslam::align_up(bytes ? bytes : 1, 256); return at; }
 };
-
-#define OPS_CHECK(x) do { const int rc_ = (x); if (rc_) return rc_; } while (0)
 
 int h_max_keypoints(void* p) { return ((HipOps*)p)->cap; }
 int h_scale_tables(void* p, float* a, float* b, float* c, float* d) {
@@ -307,12 +267,12 @@ static int download_frames(HipOps* o, int n, const oslam_keypoint_t* d_kp, const
     const size_t oCnt = L.take(4 * (size_t)n), oSt = L.take(8), oKeys = L.take(sizeof(oslam_keypoint_t) * cap * n), oKeysUn = L.take(sizeof(oslam_keypoint_t) * cap * n),
                  oDesc = L.take(32 * cap * n), oUr = L.take(4 * cap * n), oDp = L.take(4 * cap * n);
     OPS_CHECK(o->ensure_dn(L.off));
-    uint8_t* D = o->dn_h;
+    uint8_t* D = o->dn.bytes();
     OSLAM_HIP_CHECK(hipMemcpyAsync(D + oCnt, d_cnt, 4 * (size_t)n, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(hipMemcpyAsync(D + oSt, d_st, 4, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(D + oSt + 4, o->d_status, 4, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(D + oSt + 4, o->d_status.as<int32_t>(), 4, hipMemcpyDeviceToHost, o->strm));
     if (!o->lazy_keys) OSLAM_HIP_CHECK(hipMemcpyAsync(D + oKeys, d_kp, sizeof(oslam_keypoint_t) * cap * n, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(D + oKeysUn, o->d_keysUn, sizeof(oslam_keypoint_t) * cap * n, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(D + oKeysUn, o->d_keysUn.as<oslam_keypoint_t>(), sizeof(oslam_keypoint_t) * cap * n, hipMemcpyDeviceToHost, o->strm));
     if (!o->lazy_desc) OSLAM_HIP_CHECK(hipMemcpyAsync(D + oDesc, d_desc, 32 * cap * n, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(hipMemcpyAsync(D + oUr, d_uR, 4 * cap * n, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(hipMemcpyAsync(D + oDp, d_dp, 4 * cap * n, hipMemcpyDeviceToHost, o->strm));
@@ -349,16 +309,16 @@ static int frames_impl(HipOps* o, int n, const uint8_t* const* gray, int gray_st
     if (on_device) {   // two pointer tables up, ONE gather launch for the gray images (instead of 2n two-dimensional copies).  "Device" pointers only have to be
         // device-accessible: with pinned host images the gather and the depth lookup read them over PCIe where they are.
         OPS_CHECK(o->ensure_up(16 * (size_t)n + 512));
-        memcpy(o->up_h, gray, 8 * (size_t)n); memcpy(o->up_h + 8 * (size_t)n + 256 - (8 * (size_t)n) % 256, dsrc, 8 * (size_t)n);
+        memcpy(o->up.h.bytes(), gray, 8 * (size_t)n); memcpy(o->up.h.bytes() + 8 * (size_t)n + 256 - (8 * (size_t)n) % 256, dsrc, 8 * (size_t)n);
         const size_t oD = 8 * (size_t)n + 256 - (8 * (size_t)n) % 256;
-        OSLAM_HIP_CHECK(hipMemcpyAsync(o->up_d, o->up_h, oD + 8 * (size_t)n, hipMemcpyHostToDevice, o->strm));
-        OPS_CHECK(oslam_frame_gather_images_device((const void* const*)o->up_d, n, gray_stride, W, H, o->d_gray, gimg, (int)o->gray_pitch, o->strm));
-        depth_table = (const void* const*)(o->up_d + oD);   // the depth images are read where they are: only the values at the keypoints are needed
+        OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), o->up.h.bytes(), oD + 8 * (size_t)n, hipMemcpyHostToDevice, o->strm));
+        OPS_CHECK(oslam_frame_gather_images_device((const void* const*)o->up.d.bytes(), n, gray_stride, W, H, o->d_gray.bytes(), gimg, (int)o->gray_pitch, o->strm));
+        depth_table = (const void* const*)(o->up.d.bytes() + oD);   // the depth images are read where they are: only the values at the keypoints are needed
     } else {
         // host images: rows packed into the pinned block in the device layout (parallel), then ONE copy per plane (a pageable 2-D copy is row-by-row);
         // raw 16-bit depth is scaled here the way convertTo scales it (one float multiplication per pixel)
         OPS_CHECK(o->ensure_up((gimg + dimg * 4) * n));
-        uint8_t* U = o->up_h;
+        uint8_t* U = o->up.h.bytes();
         o->pool->parallel_for(n, [&](int i) {
             for (int r = 0; r < H; r++) {
                 memcpy(U + gimg * i + o->gray_pitch * r, gray[i] + (size_t)gray_stride * r, W);
@@ -367,22 +327,22 @@ static int frames_impl(HipOps* o, int n, const uint8_t* const* gray, int gray_st
                 else memcpy(drow, depth[i] + (size_t)depth_pitch * r, (size_t)W * 4);
             }
         });
-        OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_gray, U, gimg * n, hipMemcpyHostToDevice, o->strm));
-        OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_depth, U + gimg * n, dimg * 4 * n, hipMemcpyHostToDevice, o->strm));
+        OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_gray.bytes(), U, gimg * n, hipMemcpyHostToDevice, o->strm));
+        OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_depth.as<float>(), U + gimg * n, dimg * 4 * n, hipMemcpyHostToDevice, o->strm));
     }
     o->t_begin();
-    OPS_CHECK(oslam_orb_extract_batch_device(o->orb, o->d_gray, n, (int)o->gray_pitch, gimg, o->strm));
+    OPS_CHECK(oslam_orb_extract_batch_device(o->orb, o->d_gray.bytes(), n, (int)o->gray_pitch, gimg, o->strm));
     const oslam_keypoint_t* d_kp; const uint8_t* d_desc; const int32_t* d_cnt; const int32_t* d_st;
     OPS_CHECK(oslam_orb_results_device(o->orb, &d_kp, &d_desc, &d_cnt, &d_st));
-    OPS_CHECK(oslam_frame_undistort_batch_device(d_kp, o->d_keysUn, d_cnt, 0, o->cap, n, o->K4, o->cfg.dist, o->cfg.ndist, o->strm));
-    if (depth_table && depth16) OPS_CHECK(oslam_frame_stereo_from_rgbd_batch_ptrs_u16_device(d_kp, o->d_keysUn, d_cnt, 0, o->cap, n, (const uint16_t* const*)depth_table, H, W, depth_pitch,
-                                                                                              depth_factor, o->cfg.bf, o->d_uRight, o->d_mvDepth, o->d_status, o->strm));
-    else if (depth_table) OPS_CHECK(oslam_frame_stereo_from_rgbd_batch_ptrs_device(d_kp, o->d_keysUn, d_cnt, 0, o->cap, n, (const float* const*)depth_table, H, W, depth_pitch, o->cfg.bf,
-                                                                                   o->d_uRight, o->d_mvDepth, o->d_status, o->strm));
-    else OPS_CHECK(oslam_frame_stereo_from_rgbd_batch_device(d_kp, o->d_keysUn, d_cnt, 0, o->cap, n, o->d_depth, H, W, W, dimg, o->cfg.bf, o->d_uRight,
-                                                             o->d_mvDepth, o->d_status, o->strm));
+    OPS_CHECK(oslam_frame_undistort_batch_device(d_kp, o->d_keysUn.as<oslam_keypoint_t>(), d_cnt, 0, o->cap, n, o->K4, o->cfg.dist, o->cfg.ndist, o->strm));
+    if (depth_table && depth16) OPS_CHECK(oslam_frame_stereo_from_rgbd_batch_ptrs_u16_device(d_kp, o->d_keysUn.as<oslam_keypoint_t>(), d_cnt, 0, o->cap, n, (const uint16_t* const*)depth_table, H, W, depth_pitch,
+                                                                                              depth_factor, o->cfg.bf, o->d_uRight.as<float>(), o->d_mvDepth.as<float>(), o->d_status.as<int32_t>(), o->strm));
+    else if (depth_table) OPS_CHECK(oslam_frame_stereo_from_rgbd_batch_ptrs_device(d_kp, o->d_keysUn.as<oslam_keypoint_t>(), d_cnt, 0, o->cap, n, (const float* const*)depth_table, H, W, depth_pitch, o->cfg.bf,
+                                                                                   o->d_uRight.as<float>(), o->d_mvDepth.as<float>(), o->d_status.as<int32_t>(), o->strm));
+    else OPS_CHECK(oslam_frame_stereo_from_rgbd_batch_device(d_kp, o->d_keysUn.as<oslam_keypoint_t>(), d_cnt, 0, o->cap, n, o->d_depth.as<float>(), H, W, W, dimg, o->cfg.bf, o->d_uRight.as<float>(),
+                                                             o->d_mvDepth.as<float>(), o->d_status.as<int32_t>(), o->strm));
     o->t_end();
-    OPS_CHECK(download_frames(o, n, d_kp, d_desc, d_cnt, d_st, o->d_uRight, o->d_mvDepth, out));
+    OPS_CHECK(download_frames(o, n, d_kp, d_desc, d_cnt, d_st, o->d_uRight.as<float>(), o->d_mvDepth.as<float>(), out));
     if (o->timing) { double bytes = 0; for (int i = 0; i < n; i++) bytes += (double)oslam_orb_algorithmic_bytes(o->orb, out[i]->N); o->t_collect(0, 14, bytes); }
     return OSLAM_OK;
 }
@@ -415,36 +375,36 @@ int h_frames_stereo(void* p, int n, const int32_t* slots, const uint8_t* const* 
     if (on_device) {
         OPS_CHECK(o->ensure_up(16 * (size_t)n + 512));
         const size_t oD = 8 * (size_t)n + 256 - (8 * (size_t)n) % 256;
-        memcpy(o->up_h, left, 8 * (size_t)n); memcpy(o->up_h + oD, right, 8 * (size_t)n);
-        OSLAM_HIP_CHECK(hipMemcpyAsync(o->up_d, o->up_h, oD + 8 * (size_t)n, hipMemcpyHostToDevice, o->strm));
-        OPS_CHECK(oslam_frame_gather_images_device((const void* const*)o->up_d, n, gray_stride, W, H, o->d_gray, gimg, (int)o->gray_pitch, o->strm));
-        OPS_CHECK(oslam_frame_gather_images_device((const void* const*)(o->up_d + oD), n, gray_stride, W, H, o->d_grayR, gimg, (int)o->gray_pitch, o->strm));
+        memcpy(o->up.h.bytes(), left, 8 * (size_t)n); memcpy(o->up.h.bytes() + oD, right, 8 * (size_t)n);
+        OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), o->up.h.bytes(), oD + 8 * (size_t)n, hipMemcpyHostToDevice, o->strm));
+        OPS_CHECK(oslam_frame_gather_images_device((const void* const*)o->up.d.bytes(), n, gray_stride, W, H, o->d_gray.bytes(), gimg, (int)o->gray_pitch, o->strm));
+        OPS_CHECK(oslam_frame_gather_images_device((const void* const*)(o->up.d.bytes() + oD), n, gray_stride, W, H, o->d_grayR.bytes(), gimg, (int)o->gray_pitch, o->strm));
     } else {
         OPS_CHECK(o->ensure_up(2 * gimg * n));
-        uint8_t* U = o->up_h;
+        uint8_t* U = o->up.h.bytes();
         o->pool->parallel_for(n, [&](int i) {
             for (int r = 0; r < H; r++) {
                 memcpy(U + gimg * i + o->gray_pitch * r, left[i] + (size_t)gray_stride * r, W);
                 memcpy(U + gimg * (n + i) + o->gray_pitch * r, right[i] + (size_t)gray_stride * r, W);
             }
         });
-        OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_gray, U, gimg * n, hipMemcpyHostToDevice, o->strm));
-        OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_grayR, U + gimg * n, gimg * n, hipMemcpyHostToDevice, o->strm));
+        OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_gray.bytes(), U, gimg * n, hipMemcpyHostToDevice, o->strm));
+        OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_grayR.bytes(), U + gimg * n, gimg * n, hipMemcpyHostToDevice, o->strm));
     }
     o->t_begin();
-    OPS_CHECK(oslam_orb_extract_batch_device(o->orb, o->d_gray, n, (int)o->gray_pitch, gimg, o->strm));
-    OPS_CHECK(oslam_orb_extract_batch_device(o->orbR, o->d_grayR, n, (int)o->gray_pitch, gimg, o->strm));
+    OPS_CHECK(oslam_orb_extract_batch_device(o->orb, o->d_gray.bytes(), n, (int)o->gray_pitch, gimg, o->strm));
+    OPS_CHECK(oslam_orb_extract_batch_device(o->orbR, o->d_grayR.bytes(), n, (int)o->gray_pitch, gimg, o->strm));
     const oslam_keypoint_t* d_kp; const uint8_t* d_desc; const int32_t* d_cnt; const int32_t* d_st;
     const oslam_keypoint_t* d_kpR; const uint8_t* d_descR; const int32_t* d_cntR; const int32_t* d_stR;
     OPS_CHECK(oslam_orb_results_device(o->orb, &d_kp, &d_desc, &d_cnt, &d_st));
     OPS_CHECK(oslam_orb_results_device(o->orbR, &d_kpR, &d_descR, &d_cntR, &d_stR));
-    OPS_CHECK(oslam_frame_undistort_batch_device(d_kp, o->d_keysUn, d_cnt, 0, o->cap, n, o->K4, o->cfg.dist, o->cfg.ndist, o->strm));
+    OPS_CHECK(oslam_frame_undistort_batch_device(d_kp, o->d_keysUn.as<oslam_keypoint_t>(), d_cnt, 0, o->cap, n, o->K4, o->cfg.dist, o->cfg.ndist, o->strm));
     OPS_CHECK(oslam_stereo_match_batch_device(o->stereo, o->orb, o->orbR, n, o->cap, d_kp, d_desc, d_cnt, 0, d_kpR, d_descR, d_cntR, 0, o->cfg.nLevels, o->cfg.bf,
                                               o->cfg.bf / o->cfg.fx, o->strm));
     const float* d_uR; const float* d_dp;
     OPS_CHECK(oslam_stereo_results_device(o->stereo, &d_uR, &d_dp, nullptr));
     o->t_end();
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_status, d_stR, 4, hipMemcpyDeviceToDevice, o->strm));   // right extractor's overflow flag rides in the second status word
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_status.as<int32_t>(), d_stR, 4, hipMemcpyDeviceToDevice, o->strm));   // right extractor's overflow flag rides in the second status word
     (void)slots;
     OPS_CHECK(download_frames(o, n, d_kp, d_desc, d_cnt, d_st, d_uR, d_dp, out));
     if (o->timing) { double bytes = 0; for (int i = 0; i < n; i++) bytes += 2.0 * (double)oslam_orb_algorithmic_bytes(o->orb, out[i]->N); o->t_collect(0, 28, bytes); }
@@ -452,7 +412,7 @@ int h_frames_stereo(void* p, int n, const int32_t* slots, const uint8_t* const* 
 }
 
 static void frames_view(HipOps* o, oslam_match_frames_t& fr, const uint8_t* d_blocked) {
-    fr.keysUn = o->d_keysUn; fr.kp_stride = o->cap; fr.uRight = o->cur_uRight; fr.desc = o->d_desc; fr.blocked = d_blocked;
+    fr.keysUn = o->d_keysUn.as<oslam_keypoint_t>(); fr.kp_stride = o->cap; fr.uRight = o->cur_uRight; fr.desc = o->d_desc; fr.blocked = d_blocked;
     fr.n_kps = o->d_cnt; fr.n_kps_const = 0;
     fr.minX = o->bounds[0]; fr.minY = o->bounds[1]; fr.maxX = o->bounds[2]; fr.maxY = o->bounds[3];
 }
@@ -477,7 +437,7 @@ int h_search_last(void* p, int n, oslam_job_search_last_t* jobs) {
     const size_t head = L.off;
     const size_t oXw = L.take(12 * cap * S), oKeys = L.take(by_id ? 0 : sizeof(oslam_keypoint_t) * cap * S), oDesc = L.take(32 * cap * S);
     OPS_CHECK(o->ensure_up(L.off));
-    uint8_t* U = o->up_h;
+    uint8_t* U = o->up.h.bytes();
     memset(U + oN, 0, 4 * S);
     o->pool->parallel_for(n, [&](int i) {
         const oslam_job_search_last_t& j = jobs[i];
@@ -490,13 +450,13 @@ int h_search_last(void* p, int n, oslam_job_search_last_t* jobs) {
         memcpy(U + oKeys + sizeof(oslam_keypoint_t) * cap * b, j.last_keysUn, sizeof(oslam_keypoint_t) * N);
         memcpy(U + oDesc + 32 * cap * b, j.mp_desc, 32 * N);
     });
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up_d, U, by_id ? head : L.off, hipMemcpyHostToDevice, o->strm));
-    uint8_t* Dv = o->up_d;
-    if (by_id) OPS_CHECK(oslam_mp_table_gather_device((int)S, (int)cap, (const int32_t*)(Dv + oN), (const int32_t*)(Dv + oIds), o->d_mp_tab, (float*)(Dv + oXw), Dv + oDesc, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), U, by_id ? head : L.off, hipMemcpyHostToDevice, o->strm));
+    uint8_t* Dv = o->up.d.bytes();
+    if (by_id) OPS_CHECK(oslam_mp_table_gather_device((int)S, (int)cap, (const int32_t*)(Dv + oN), (const int32_t*)(Dv + oIds), o->d_mp_tab.as<uint8_t*>(), (float*)(Dv + oXw), Dv + oDesc, o->strm));
     oslam_match_frames_t fr;
     frames_view(o, fr, nullptr);
     oslam_match_last_t la;
-    la.Xw = (const float*)(Dv + oXw); la.has_mp = Dv + oHas; la.keys = by_id ? o->d_keysUn_prev : (const oslam_keypoint_t*)(Dv + oKeys); la.mp_desc = Dv + oDesc;
+    la.Xw = (const float*)(Dv + oXw); la.has_mp = Dv + oHas; la.keys = by_id ? o->d_keysUn_prev.as<oslam_keypoint_t>() : (const oslam_keypoint_t*)(Dv + oKeys); la.mp_desc = Dv + oDesc;
     la.kp_stride = (int)cap; la.n_kps = (const int32_t*)(Dv + oN); la.n_kps_const = 0;
     o->t_begin();
     OPS_CHECK(oslam_match_project_last_batch_device(o->m_last, &la, (const float*)(Dv + oTc), (const float*)(Dv + oTl), &o->cam, &fr, o->scale, o->cfg.nLevels,
@@ -508,14 +468,14 @@ int h_search_last(void* p, int n, oslam_job_search_last_t* jobs) {
     Layout R;
     const size_t rKm = R.take(4 * cap * S), rNm = R.take(4 * S);
     OPS_CHECK(o->ensure_dn(R.off));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h + rKm, d_km, 4 * cap * S, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h + rNm, d_nm, 4 * S, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rKm, d_km, 4 * cap * S, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rNm, d_nm, 4 * S, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(3, 2, 0);
     o->pool->parallel_for(n, [&](int i) {
         oslam_job_search_last_t& j = jobs[i];
-        memcpy(j.kp_match, o->dn_h + rKm + 4 * cap * j.slot, 4 * (size_t)j.cur->N);
-        j.nmatches = ((const int32_t*)(o->dn_h + rNm))[j.slot];
+        memcpy(j.kp_match, o->dn.bytes() + rKm + 4 * cap * j.slot, 4 * (size_t)j.cur->N);
+        j.nmatches = ((const int32_t*)(o->dn.bytes() + rNm))[j.slot];
     });
     return OSLAM_OK;
 }
@@ -571,8 +531,8 @@ int h_search_local(void* p, int n, oslam_job_search_local_t* jobs) {
     const size_t oF = L.take(fbytes);
     OPS_CHECK(o->ensure_up(L.off));
     OPS_CHECK(o->ensure_lq(st * S));
-    uint8_t* U = o->up_h;
-    uint8_t* Dv = o->up_d;
+    uint8_t* U = o->up.h.bytes();
+    uint8_t* Dv = o->up.d.bytes();
     memset(U + oM, 0, 4 * S);
     memset(U + oTh, 0, 4 * S);
     o->pool->parallel_for(n, [&](int i) {
@@ -613,31 +573,31 @@ int h_search_local(void* p, int n, oslam_job_search_local_t* jobs) {
     OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, fresh.empty() ? small_bytes : L.off, hipMemcpyHostToDevice, o->strm));
     o->t_begin();   // (the gather of repacked local maps counts with the searches it feeds)
     if (!fresh.empty() && by_id)
-        OPS_CHECK(oslam_mp_table_local_gather_device((int)fresh.size(), freshMaxM, (const oslam_local_gather_t*)(Dv + oSeg), Dv + oF, o->d_mp_tab, (int)lst, o->loc_Pw(), o->loc_Pn(),
+        OPS_CHECK(oslam_mp_table_local_gather_device((int)fresh.size(), freshMaxM, (const oslam_local_gather_t*)(Dv + oSeg), Dv + oF, o->d_mp_tab.as<uint8_t*>(), (int)lst, o->loc_Pw(), o->loc_Pn(),
                                                      o->loc_Max(), o->loc_Min(), o->loc_Obs(), o->loc_Desc(), o->strm));
     else if (!fresh.empty()) OPS_CHECK(oslam_copy_segments_device(Dv + oSeg, 6 * (int)fresh.size(), o->strm));   // (a zero-byte segment's workgroup returns at once)
     OPS_CHECK(oslam_frame_is_in_frustum_batch_resident_device((int)S, (int)lst, (int)st, (const int32_t*)(Dv + oM), o->loc_Pw(), o->loc_Pn(), o->loc_Max(), o->loc_Min(),
                                                               o->loc_Obs(), o->loc_Desc(), Dv + oSk, (const float*)(Dv + oTc), (const float*)(Dv + oTh), o->K5,
-                                                              o->bounds, 0.5f, o->logScale, o->scale, o->cfg.nLevels, o->d_lq, o->d_inview, o->strm));
+                                                              o->bounds, 0.5f, o->logScale, o->scale, o->cfg.nLevels, o->d_lq.as<oslam_proj_query_t>(), o->d_inview.bytes(), o->strm));
     oslam_match_frames_t fr;
     frames_view(o, fr, Dv + oBl);
-    OPS_CHECK(oslam_match_search_batch_device(o->m_map, &fr, o->d_lq, (int)st, (const int32_t*)(Dv + oM), 0, (int)S, 0.8f, 1, 0, 100, o->strm));
+    OPS_CHECK(oslam_match_search_batch_device(o->m_map, &fr, o->d_lq.as<oslam_proj_query_t>(), (int)st, (const int32_t*)(Dv + oM), 0, (int)S, 0.8f, 1, 0, 100, o->strm));
     o->t_end();
     const int32_t* d_km; const int32_t* d_nm;
     OPS_CHECK(oslam_match_results_device(o->m_map, nullptr, nullptr, &d_km, &d_nm, nullptr, nullptr));
     Layout R;
     const size_t rKm = R.take(4 * cap * S), rNm = R.take(4 * S), rIn = R.take(st * S);
     OPS_CHECK(o->ensure_dn(R.off));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h + rKm, d_km, 4 * cap * S, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h + rNm, d_nm, 4 * S, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h + rIn, o->d_inview, st * S, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rKm, d_km, 4 * cap * S, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rNm, d_nm, 4 * S, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rIn, o->d_inview.bytes(), st * S, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(3, 2, 0);
     o->pool->parallel_for(n, [&](int i) {
         oslam_job_search_local_t& j = jobs[i];
-        memcpy(j.kp_match, o->dn_h + rKm + 4 * cap * j.slot, 4 * (size_t)j.cur->N);
-        memcpy(j.in_view, o->dn_h + rIn + st * j.slot, (size_t)j.M);
-        j.nmatches = ((const int32_t*)(o->dn_h + rNm))[j.slot];
+        memcpy(j.kp_match, o->dn.bytes() + rKm + 4 * cap * j.slot, 4 * (size_t)j.cur->N);
+        memcpy(j.in_view, o->dn.bytes() + rIn + st * j.slot, (size_t)j.M);
+        j.nmatches = ((const int32_t*)(o->dn.bytes() + rNm))[j.slot];
     });
     return OSLAM_OK;
 }
@@ -660,7 +620,7 @@ int h_pose_opt(void* p, int n, oslam_job_pose_t* jobs) {
     const size_t head = L.off;
     const size_t oXw = L.take(12 * cap * B), oObs = L.take(12 * cap * B), oInv = L.take(4 * cap * B), oHas = L.take(cap * B);
     OPS_CHECK(o->ensure_up(L.off));
-    uint8_t* U = o->up_h;
+    uint8_t* U = o->up.h.bytes();
     o->pool->parallel_for(n, [&](int i) {
         const oslam_job_pose_t& j = jobs[i];
         const size_t N = j.N;
@@ -670,10 +630,10 @@ int h_pose_opt(void* p, int n, oslam_job_pose_t* jobs) {
         memcpy(U + oXw + 12 * cap * i, j.Xw, 12 * N); memcpy(U + oObs + 12 * cap * i, j.obs, 12 * N);
         memcpy(U + oInv + 4 * cap * i, j.invSigma2, 4 * N); memcpy(U + oHas + cap * i, j.has_mp, N);
     });
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up_d, U, by_id ? head : L.off, hipMemcpyHostToDevice, o->strm));
-    uint8_t* Dv = o->up_d;
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), U, by_id ? head : L.off, hipMemcpyHostToDevice, o->strm));
+    uint8_t* Dv = o->up.d.bytes();
     if (by_id)
-        OPS_CHECK(oslam_pose_inputs_gather_device(n, (int)cap, (const int32_t*)(Dv + oSl), (const int32_t*)(Dv + oN), (const int32_t*)(Dv + oIds), o->d_mp_tab, o->d_keysUn,
+        OPS_CHECK(oslam_pose_inputs_gather_device(n, (int)cap, (const int32_t*)(Dv + oSl), (const int32_t*)(Dv + oN), (const int32_t*)(Dv + oIds), o->d_mp_tab.as<uint8_t*>(), o->d_keysUn.as<oslam_keypoint_t>(),
                                                   o->cur_uRight, (int)cap, o->invSigma2, o->cfg.nLevels, (float*)(Dv + oXw), (float*)(Dv + oObs), (float*)(Dv + oInv), Dv + oHas, o->strm));
     o->t_begin();
     OPS_CHECK(oslam_pose_optimize_batch_device(o->po, n, (int)cap, (const int32_t*)(Dv + oN), 0, (const float*)(Dv + oT), (const float*)(Dv + oXw),
@@ -684,14 +644,14 @@ int h_pose_opt(void* p, int n, oslam_job_pose_t* jobs) {
     Layout R;
     const size_t rT = R.take(64 * B), rO = R.take(cap * B), rN = R.take(4 * B), rS = R.take(8 * B);
     OPS_CHECK(o->ensure_dn(R.off));
-    if (o->timing) OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h + rS, d_stats, 8 * B, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h + rT, d_T, 64 * B, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h + rO, d_out, cap * B, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h + rN, d_ni, 4 * B, hipMemcpyDeviceToHost, o->strm));
+    if (o->timing) OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rS, d_stats, 8 * B, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rT, d_T, 64 * B, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rO, d_out, cap * B, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rN, d_ni, 4 * B, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     if (o->timing) {   // 700 flop per edge and linearisation, 90 per edge and trial evaluation
         double flop = 0;
-        const int32_t* stt = (const int32_t*)(o->dn_h + rS);
+        const int32_t* stt = (const int32_t*)(o->dn.bytes() + rS);
         for (int i = 0; i < n; i++) {
             int ne = 0;
             for (int k = 0; k < jobs[i].N; k++) ne += by_id ? jobs[i].mp_ids[k] >= 0 : jobs[i].has_mp[k] != 0;
@@ -701,9 +661,9 @@ int h_pose_opt(void* p, int n, oslam_job_pose_t* jobs) {
     }
     o->pool->parallel_for(n, [&](int i) {
         oslam_job_pose_t& j = jobs[i];
-        memcpy(j.Tcw_out, o->dn_h + rT + 64 * i, 64);
-        memcpy(j.outlier, o->dn_h + rO + cap * i, (size_t)j.N);
-        j.n_inliers = ((const int32_t*)(o->dn_h + rN))[i];
+        memcpy(j.Tcw_out, o->dn.bytes() + rT + 64 * i, 64);
+        memcpy(j.outlier, o->dn.bytes() + rO + cap * i, (size_t)j.N);
+        j.n_inliers = ((const int32_t*)(o->dn.bytes() + rN))[i];
     });
     return OSLAM_OK;
 }
@@ -716,8 +676,8 @@ static int stage_masks(HipOps* o, int total, const std::vector<const uint8_t*>& 
     pitch = (int)W;
     OPS_CHECK(o->ensure_masks(W * H * (size_t)total));
     for (int m = 0; m < total; m++) {
-        OSLAM_HIP_CHECK(hipMemcpy2DAsync(o->d_maskstage + W * H * m, W, src[m], mask_stride, W, H, hipMemcpyHostToDevice, o->strm));
-        ptrs[m] = o->d_maskstage + W * H * m;
+        OSLAM_HIP_CHECK(hipMemcpy2DAsync(o->d_maskstage.bytes() + W * H * m, W, src[m], mask_stride, W, H, hipMemcpyHostToDevice, o->strm));
+        ptrs[m] = o->d_maskstage.bytes() + W * H * m;
     }
     return OSLAM_OK;
 }
@@ -748,36 +708,36 @@ int h_object_kps(void* p, int n, oslam_job_object_kps_t* jobs) {
     Layout L;
     const size_t oPtr = L.take(8 * (size_t)total), oM0 = L.take(4 * S), oNm = L.take(4 * S), oSeg = L.take(caller_bits ? sizeof(CopySegH) * (size_t)total : 0);
     OPS_CHECK(o->ensure_up(L.off));
-    uint8_t* U = o->up_h;
+    uint8_t* U = o->up.h.bytes();
     const size_t bits_bytes = (size_t)o->cfg.height * ((o->cfg.width + 63) / 64) * 8;
     if (caller_bits) {
         OPS_CHECK(o->ensure_maskbits((size_t)total * o->cfg.height * ((o->cfg.width + 63) / 64)));
         CopySegH* sg = (CopySegH*)(U + oSeg);
-        for (int m = 0; m < total; m++) { sg[m].src = src[m]; sg[m].dst = (uint8_t*)o->d_maskbits + bits_bytes * m; sg[m].bytes = (uint32_t)bits_bytes; sg[m].pad = 0; }
+        for (int m = 0; m < total; m++) { sg[m].src = src[m]; sg[m].dst = o->d_maskbits.bytes() + bits_bytes * m; sg[m].bytes = (uint32_t)bits_bytes; sg[m].pad = 0; }
     } else memcpy(U + oPtr, ptrs.data(), 8 * (size_t)total);
     memcpy(U + oM0, mask0.data(), 4 * S); memcpy(U + oNm, nmask.data(), 4 * S);
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up_d, U, L.off, hipMemcpyHostToDevice, o->strm));
-    uint8_t* Dv = o->up_d;
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), U, L.off, hipMemcpyHostToDevice, o->strm));
+    uint8_t* Dv = o->up.d.bytes();
     o->t_begin();
     if (caller_bits || !getenv("OSLAM_SLAM_NO_MASK_BITS")) {   // one pass over the mask bytes; the test (and pose_opt2's boundary lists later in this step) read bitmaps
         const int H = o->cfg.height, W = o->cfg.width;
         OPS_CHECK(o->ensure_maskbits((size_t)total * H * ((W + 63) / 64)));
         if (caller_bits) OPS_CHECK(oslam_copy_segments_device(Dv + oSeg, total, o->strm));   // the caller's bitmaps (pinned host memory: read over PCIe) into the step's bitmap array
-        else OPS_CHECK(oslam_mask_bits_device((const uint8_t* const*)(Dv + oPtr), total, H, W, pitch, o->d_maskbits, o->strm));
-        OPS_CHECK(oslam_frame_object_kp_test_bits_batch_device(o->d_keysUn, (int)cap, o->d_cnt, (int)S, o->d_maskbits, (const int32_t*)(Dv + oM0), (const int32_t*)(Dv + oNm), H, W,
-                                                               o->d_objbits, o->strm));
+        else OPS_CHECK(oslam_mask_bits_device((const uint8_t* const*)(Dv + oPtr), total, H, W, pitch, o->d_maskbits.as<uint64_t>(), o->strm));
+        OPS_CHECK(oslam_frame_object_kp_test_bits_batch_device(o->d_keysUn.as<oslam_keypoint_t>(), (int)cap, o->d_cnt, (int)S, o->d_maskbits.as<uint64_t>(), (const int32_t*)(Dv + oM0), (const int32_t*)(Dv + oNm), H, W,
+                                                               o->d_objbits.bytes(), o->strm));
         o->bits_of_ptr.clear();
         for (int m = 0; m < total; m++) o->bits_of_ptr[src[m]] = m;
         o->bits_epoch = o->step_epoch;
     } else
-    OPS_CHECK(oslam_frame_object_kp_test_batch_device(o->d_keysUn, (int)cap, o->d_cnt, (int)S, (const uint8_t* const*)(Dv + oPtr), (const int32_t*)(Dv + oM0),
-                                                      (const int32_t*)(Dv + oNm), o->cfg.height, o->cfg.width, pitch, o->d_objbits, o->strm));
+    OPS_CHECK(oslam_frame_object_kp_test_batch_device(o->d_keysUn.as<oslam_keypoint_t>(), (int)cap, o->d_cnt, (int)S, (const uint8_t* const*)(Dv + oPtr), (const int32_t*)(Dv + oM0),
+                                                      (const int32_t*)(Dv + oNm), o->cfg.height, o->cfg.width, pitch, o->d_objbits.bytes(), o->strm));
     o->t_end();
     OPS_CHECK(o->ensure_dn(cap * S));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h, o->d_objbits, cap * S, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes(), o->d_objbits.bytes(), cap * S, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(7, 2, 0);
-    for (int i = 0; i < n; i++) memcpy(jobs[i].in_mask, o->dn_h + cap * jobs[i].slot, (size_t)jobs[i].cur->N);
+    for (int i = 0; i < n; i++) memcpy(jobs[i].in_mask, o->dn.bytes() + cap * jobs[i].slot, (size_t)jobs[i].cur->N);
     return OSLAM_OK;
 }
 
@@ -803,7 +763,7 @@ int h_pose_opt2(void* p, int n, oslam_job_pose2_t* jobs) {
     std::vector<const uint8_t*> ptrs;
     int pitch = o->cfg.width;
     // with this step's bitmaps (object_kps) the kernel reads no mask byte: nothing to stage
-    bool use_bits = tObj > 0 && o->bits_epoch == o->step_epoch && o->d_maskbits;
+    bool use_bits = tObj > 0 && o->bits_epoch == o->step_epoch && o->d_maskbits.ptr();
     std::vector<int32_t> bidx(tObj);
     for (int m = 0; m < tObj && use_bits; m++) {
         const auto it = o->bits_of_ptr.find(src[m]);
@@ -826,7 +786,7 @@ int h_pose_opt2(void* p, int n, oslam_job_pose2_t* jobs) {
     const size_t oMxDev = by_id ? L.take(12 * (size_t)tMp) : oMx;   // object map-point positions: uploaded, or gathered from the records
     const size_t oXw = L.take(12 * cap * B), oObs = L.take(12 * cap * B), oInv = L.take(4 * cap * B), oHas = L.take(cap * B);
     OPS_CHECK(o->ensure_up(L.off));
-    uint8_t* U = o->up_h;
+    uint8_t* U = o->up.h.bytes();
     memcpy(U + oFr, fr.data(), sizeof(oslam_sem_frame_t) * B);
     if (use_bits) memcpy(U + oBi, bidx.data(), 4 * (size_t)tObj);
     if (tObj && !use_bits) memcpy(U + oPtr, ptrs.data(), 8 * (size_t)tObj);
@@ -851,15 +811,15 @@ int h_pose_opt2(void* p, int n, oslam_job_pose2_t* jobs) {
         }
         if (j2.nJoint) { memcpy(U + oJk + 4 * (size_t)fr[i].joint0, j2.joint_kp, 4 * (size_t)j2.nJoint); memcpy(U + oJo + 4 * (size_t)fr[i].joint0, j2.joint_obj, 4 * (size_t)j2.nJoint); }
     });
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up_d, U, by_id ? head : L.off, hipMemcpyHostToDevice, o->strm));
-    uint8_t* Dv = o->up_d;
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), U, by_id ? head : L.off, hipMemcpyHostToDevice, o->strm));
+    uint8_t* Dv = o->up.d.bytes();
     if (by_id) {
-        OPS_CHECK(oslam_pose_inputs_gather_device(n, (int)cap, (const int32_t*)(Dv + oSl), (const int32_t*)(Dv + oN), (const int32_t*)(Dv + oIds), o->d_mp_tab, o->d_keysUn,
+        OPS_CHECK(oslam_pose_inputs_gather_device(n, (int)cap, (const int32_t*)(Dv + oSl), (const int32_t*)(Dv + oN), (const int32_t*)(Dv + oIds), o->d_mp_tab.as<uint8_t*>(), o->d_keysUn.as<oslam_keypoint_t>(),
                                                   o->cur_uRight, (int)cap, o->invSigma2, o->cfg.nLevels, (float*)(Dv + oXw), (float*)(Dv + oObs), (float*)(Dv + oInv), Dv + oHas, o->strm));
-        OPS_CHECK(oslam_mp_table_positions_device(tMp, (const int32_t*)(Dv + oMs), (const int32_t*)(Dv + oMi), o->d_mp_tab, (float*)(Dv + oMxDev), o->strm));
+        OPS_CHECK(oslam_mp_table_positions_device(tMp, (const int32_t*)(Dv + oMs), (const int32_t*)(Dv + oMi), o->d_mp_tab.as<uint8_t*>(), (float*)(Dv + oMxDev), o->strm));
     }
     o->t_begin();
-    if (use_bits) OPS_CHECK(oslam_poseopt_use_mask_bits(o->po, o->d_maskbits, (const int32_t*)(Dv + oBi)));
+    if (use_bits) OPS_CHECK(oslam_poseopt_use_mask_bits(o->po, o->d_maskbits.as<uint64_t>(), (const int32_t*)(Dv + oBi)));
     OPS_CHECK(oslam_pose_optimize2_batch_device(o->po, n, (int)cap, (const int32_t*)(Dv + oN), (const float*)(Dv + oT), (const float*)(Dv + oXw), (const float*)(Dv + oObs),
                                                 (const float*)(Dv + oInv), Dv + oHas, o->K5, (const oslam_sem_frame_t*)(Dv + oFr), tObj, use_bits ? nullptr : (const uint8_t* const*)(Dv + oPtr),
                                                 o->cfg.height, o->cfg.width, pitch, tMp, (const float*)(Dv + oMxDev), (const int32_t*)(Dv + oMo), tJ, (const int32_t*)(Dv + oJk),
@@ -871,15 +831,15 @@ int h_pose_opt2(void* p, int n, oslam_job_pose2_t* jobs) {
     Layout R;
     const size_t rT = R.take(64 * B), rO = R.take(cap * B), rN = R.take(4 * B), rS = R.take(8 * B), rNs = R.take(4 * B);
     OPS_CHECK(o->ensure_dn(R.off));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h + rT, d_T, 64 * B, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h + rO, d_out, cap * B, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h + rN, d_ni, 4 * B, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h + rS, d_stats, 8 * B, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h + rNs, d_ns, 4 * B, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rT, d_T, 64 * B, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rO, d_out, cap * B, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rN, d_ni, 4 * B, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rS, d_stats, 8 * B, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rNs, d_ns, 4 * B, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     if (o->timing) {
         double flop = 0;
-        const int32_t* stt = (const int32_t*)(o->dn_h + rS);
+        const int32_t* stt = (const int32_t*)(o->dn.bytes() + rS);
         for (int i = 0; i < n; i++) {
             int ne = jobs[i].nObjMp + jobs[i].nJoint;   // upper bound of the semantic edges
             for (int k = 0; k < jobs[i].base.N; k++) ne += by_id ? jobs[i].base.mp_ids[k] >= 0 : jobs[i].base.has_mp[k] != 0;
@@ -889,10 +849,10 @@ int h_pose_opt2(void* p, int n, oslam_job_pose2_t* jobs) {
     }
     o->pool->parallel_for(n, [&](int i) {
         oslam_job_pose_t& j = jobs[i].base;
-        memcpy(j.Tcw_out, o->dn_h + rT + 64 * i, 64);
-        memcpy(j.outlier, o->dn_h + rO + cap * i, (size_t)j.N);
-        j.n_inliers = ((const int32_t*)(o->dn_h + rN))[i];
-        jobs[i].n_semantic = ((const int32_t*)(o->dn_h + rNs))[i];
+        memcpy(j.Tcw_out, o->dn.bytes() + rT + 64 * i, 64);
+        memcpy(j.outlier, o->dn.bytes() + rO + cap * i, (size_t)j.N);
+        j.n_inliers = ((const int32_t*)(o->dn.bytes() + rN))[i];
+        jobs[i].n_semantic = ((const int32_t*)(o->dn.bytes() + rNs))[i];
     });
     return OSLAM_OK;
 }
@@ -910,7 +870,7 @@ int h_keyframe_raw_keys(void* p, int n, const int32_t* slots, const int32_t* cou
     const size_t cap = o->cap;
     for (int i = 0; i < n; i++) {
         if (slots[i] != o->kfk_slots[i] || counts[i] < 0 || (size_t)counts[i] > cap) { oslam::set_error("keyframe_raw_keys: not the keyframes of the last register_keyframes call"); return OSLAM_E_INVALID; }
-        memcpy(out[i], o->kfk_h + (size_t)i * cap * sizeof(oslam_keypoint_t), (size_t)counts[i] * sizeof(oslam_keypoint_t));
+        memcpy(out[i], o->kfk.bytes() + (size_t)i * cap * sizeof(oslam_keypoint_t), (size_t)counts[i] * sizeof(oslam_keypoint_t));
     }
     return OSLAM_OK;
 }
@@ -918,7 +878,7 @@ int h_keyframe_descriptors(void* p, int n, const int32_t* slots, const int32_t* 
     HipOps* o = (HipOps*)p;
     if (!o->lazy_desc || n != (int)o->kfk_slots.size()) { oslam::set_error("keyframe_descriptors: not the keyframes of the last register_keyframes call"); return OSLAM_E_INVALID; }
     const size_t cap = o->cap;
-    const uint8_t* base = o->kfk_h + (size_t)n * cap * sizeof(oslam_keypoint_t);
+    const uint8_t* base = o->kfk.bytes() + (size_t)n * cap * sizeof(oslam_keypoint_t);
     for (int i = 0; i < n; i++) {
         if (slots[i] != o->kfk_slots[i] || counts[i] < 0 || (size_t)counts[i] > cap) { oslam::set_error("keyframe_descriptors: not the keyframes of the last register_keyframes call"); return OSLAM_E_INVALID; }
         memcpy(out[i], base + (size_t)i * cap * 32, (size_t)counts[i] * 32);
@@ -936,14 +896,14 @@ int h_frame_descriptors(void* p, int n, const int32_t* slots, const int32_t* cou
     std::vector<CopySegH> segs(n);
     for (int i = 0; i < n; i++) {
         if (slots[i] < 0 || slots[i] >= o->S || counts[i] < 0 || (size_t)counts[i] > cap) { oslam::set_error("frame_descriptors: bad slot / count"); return OSLAM_E_INVALID; }
-        segs[i] = {o->d_desc + 32 * cap * slots[i], o->dn_h + (size_t)i * cap * 32, (uint32_t)(cap * 32), 0};
+        segs[i] = {o->d_desc + 32 * cap * slots[i], o->dn.bytes() + (size_t)i * cap * 32, (uint32_t)(cap * 32), 0};
     }
     OPS_CHECK(o->ensure_up(segs.size() * sizeof(CopySegH)));
-    memcpy(o->up_h, segs.data(), segs.size() * sizeof(CopySegH));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up_d, o->up_h, segs.size() * sizeof(CopySegH), hipMemcpyHostToDevice, o->strm));
-    OPS_CHECK(oslam_copy_segments_device(o->up_d, (int)segs.size(), o->strm));
+    memcpy(o->up.h.bytes(), segs.data(), segs.size() * sizeof(CopySegH));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), o->up.h.bytes(), segs.size() * sizeof(CopySegH), hipMemcpyHostToDevice, o->strm));
+    OPS_CHECK(oslam_copy_segments_device(o->up.d.bytes(), (int)segs.size(), o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
-    for (int i = 0; i < n; i++) memcpy(out[i], o->dn_h + (size_t)i * cap * 32, (size_t)counts[i] * 32);
+    for (int i = 0; i < n; i++) memcpy(out[i], o->dn.bytes() + (size_t)i * cap * 32, (size_t)counts[i] * 32);
     return OSLAM_OK;
 }
 // The deferred form: only the one-launch path (k_mp_update_fused) is deferred — it needs no staging beyond the job block and writes its results into a pinned
@@ -967,8 +927,8 @@ int h_mp_update_collect(void* p) {
     q.on = false;
     o->swap_staging();   // (the deferred job's event pair and result block)
     o->t_collect(6, 1, q.dtotal);
-    if (q.j->do_desc) { memcpy(q.j->best_idx, o->dn_h + q.rBest, 4 * q.P); memcpy(q.j->out_desc, o->dn_h + q.rOut, 32 * q.P); }
-    if (q.j->do_normal) memcpy(q.j->out5, o->dn_h + q.rOut5, 20 * q.P);
+    if (q.j->do_desc) { memcpy(q.j->best_idx, o->dn.bytes() + q.rBest, 4 * q.P); memcpy(q.j->out_desc, o->dn.bytes() + q.rOut, 32 * q.P); }
+    if (q.j->do_normal) memcpy(q.j->out5, o->dn.bytes() + q.rOut5, 20 * q.P);
     o->swap_staging();
     return OSLAM_OK;
 }
@@ -1037,8 +997,8 @@ static int mp_update_impl(HipOps* o, oslam_job_mp_update_t* j, const int32_t* ob
     const size_t oDesc = keyed ? L.take(32 * dtotal) : oDescUp;
     const size_t oBest = L.take(4 * P), oOut = L.take(32 * P), oOut5 = L.take(20 * P);
     OPS_CHECK(o->ensure_up(L.off));
-    uint8_t* U = o->up_h;
-    uint8_t* Dv = o->up_d;
+    uint8_t* U = o->up.h.bytes();
+    uint8_t* Dv = o->up.d.bytes();
     memcpy(U + oStart, j->obs_start, 4 * (P + 1));
     if (table) memcpy(U + oItems, j->items, 8 * P);
     if (j->desc_start) memcpy(U + oDStart, j->desc_start, 4 * (P + 1));
@@ -1068,14 +1028,14 @@ static int mp_update_impl(HipOps* o, oslam_job_mp_update_t* j, const int32_t* ob
         // (the deferred form does not even enqueue the kernel here: it is launched right in front of the next operator's own kernel — the next Fuse round's search —
         // or by mp_update_collect, so that ONE wait covers both and nothing runs on the card while the driver does the round's bookkeeping)
         const bool do_desc = j->do_desc != 0, do_normal = j->do_normal != 0, has_ds = j->desc_start != nullptr;
-        uint8_t* const dn = o->dn_h;
+        uint8_t* const dn = o->dn.bytes();
         hipEvent_t e0 = o->tev0, e1 = o->tev1;
         std::function<int()> launch = [=]() -> int {
             if (o->timing) (void)hipEventRecord(e0, o->strm);
             const int rcl = oslam_mp_update_fused_device((int)P, do_desc, do_normal, (const int32_t*)(In + oStart), (const int32_t*)(In + (has_ds ? oDStart : oStart)),
-                                                         keyed ? (const int32_t*)(In + oRec) : nullptr, (const uint8_t* const*)o->d_rec_desc, (const float*)(In + oOw), (const float*)(In + oPos),
+                                                         keyed ? (const int32_t*)(In + oRec) : nullptr, o->d_rec_desc.as<uint8_t*>(), (const float*)(In + oOw), (const float*)(In + oPos),
                                                          (const float*)(In + oRef), (const float*)(In + oLsf), o->scale[o->cfg.nLevels - 1], table ? (const int32_t*)(In + oItems) : nullptr,
-                                                         table ? o->d_mp_tab : nullptr, (int32_t*)(dn + rBest), dn + rOut, (float*)(dn + rOut5), o->strm);
+                                                         table ? o->d_mp_tab.as<uint8_t*>() : nullptr, (int32_t*)(dn + rBest), dn + rOut, (float*)(dn + rOut5), o->strm);
             if (o->timing) (void)hipEventRecord(e1, o->strm);
             return rcl;
         };
@@ -1089,34 +1049,34 @@ static int mp_update_impl(HipOps* o, oslam_job_mp_update_t* j, const int32_t* ob
         OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
         lap_(4);
         o->t_collect(6, 1, (double)dtotal);
-        if (j->do_desc) { memcpy(j->best_idx, o->dn_h + rBest, 4 * P); memcpy(j->out_desc, o->dn_h + rOut, 32 * P); }
-        if (j->do_normal) memcpy(j->out5, o->dn_h + rOut5, 20 * P);
+        if (j->do_desc) { memcpy(j->best_idx, o->dn.bytes() + rBest, 4 * P); memcpy(j->out_desc, o->dn.bytes() + rOut, 32 * P); }
+        if (j->do_normal) memcpy(j->out5, o->dn.bytes() + rOut5, 20 * P);
         lap_(5);
         return OSLAM_OK;
     }
     o->t_begin();
-    if (keyed) OPS_CHECK(oslam_gather_descriptors_device((const uint8_t* const*)o->d_rec_desc, (const int32_t*)(In + oRec), (int)dtotal, Dv + oDesc, o->strm));
+    if (keyed) OPS_CHECK(oslam_gather_descriptors_device(o->d_rec_desc.as<uint8_t*>(), (const int32_t*)(In + oRec), (int)dtotal, Dv + oDesc, o->strm));
     if (j->do_desc) {
         OSLAM_HIP_CHECK(hipMemsetAsync(Dv + oOut, 0, 32 * P, o->strm));
         OPS_CHECK(oslam_mp_distinctive_descriptors_device((int)P, (const int32_t*)(In + (j->desc_start ? oDStart : oStart)), Dv + oDesc, (int32_t*)(Dv + oBest), Dv + oOut, o->strm));
-        OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn_h + rBest, Dv + oBest, 4 * P, o->strm));
-        OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn_h + rOut, Dv + oOut, 32 * P, o->strm));
+        OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn.bytes() + rBest, Dv + oBest, 4 * P, o->strm));
+        OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn.bytes() + rOut, Dv + oOut, 32 * P, o->strm));
     }
     if (j->do_normal) {
         OPS_CHECK(oslam_mp_update_normal_depth_device((int)P, (const float*)(In + oPos), (const int32_t*)(In + oStart), (const float*)(In + oOw), (const float*)(In + oRef),
                                                       (const float*)(In + oLsf), o->scale[o->cfg.nLevels - 1], (float*)(Dv + oOut5), o->strm));
-        OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn_h + rOut5, Dv + oOut5, 20 * P, o->strm));
+        OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn.bytes() + rOut5, Dv + oOut5, 20 * P, o->strm));
     }
     if (table)
-        OPS_CHECK(oslam_mp_table_write_device((int)P, (const int32_t*)(In + oItems), o->d_mp_tab, (const int32_t*)(In + oStart), (const int32_t*)(In + (j->desc_start ? oDStart : oStart)),
+        OPS_CHECK(oslam_mp_table_write_device((int)P, (const int32_t*)(In + oItems), o->d_mp_tab.as<uint8_t*>(), (const int32_t*)(In + oStart), (const int32_t*)(In + (j->desc_start ? oDStart : oStart)),
                                               (const float*)(In + oPos), (const float*)(Dv + oOut5), Dv + oOut, j->do_desc, j->do_normal, o->strm));
     o->t_end();
     lap_(3);
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     lap_(4);
     o->t_collect(6, (keyed ? 1 : 0) + (j->do_desc ? 2 : 0) + (j->do_normal ? 1 : 0) + (table ? 1 : 0), (double)dtotal);
-    if (j->do_desc) { memcpy(j->best_idx, o->dn_h + rBest, 4 * P); memcpy(j->out_desc, o->dn_h + rOut, 32 * P); }
-    if (j->do_normal) memcpy(j->out5, o->dn_h + rOut5, 20 * P);
+    if (j->do_desc) { memcpy(j->best_idx, o->dn.bytes() + rBest, 4 * P); memcpy(j->out_desc, o->dn.bytes() + rOut, 32 * P); }
+    if (j->do_normal) memcpy(j->out5, o->dn.bytes() + rOut5, 20 * P);
     lap_(5);
     return OSLAM_OK;
 }
@@ -1150,8 +1110,8 @@ int h_mp_update_windows(void* p, int n, oslam_job_mp_window_t* wins) {
     const size_t in_bytes = L.off;
     const size_t oOut = L.take(20 * P);
     OPS_CHECK(o->ensure_up(L.off));
-    uint8_t* U = o->up_h;
-    uint8_t* Dv = o->up_d;
+    uint8_t* U = o->up.h.bytes();
+    uint8_t* Dv = o->up.d.bytes();
     std::vector<size_t> pb(n + 1, 0), eb(n + 1, 0), kb(n + 1, 0);
     for (int i = 0; i < n; i++) { pb[i + 1] = pb[i] + wins[i].nP; eb[i + 1] = eb[i] + wins[i].nE; kb[i + 1] = kb[i] + wins[i].nK; }
     o->pool->parallel_for(n, [&](int i) {
@@ -1174,15 +1134,15 @@ int h_mp_update_windows(void* p, int n, oslam_job_mp_window_t* wins) {
     });
     OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, in_bytes, hipMemcpyHostToDevice, o->strm));
     o->t_begin();
-    OPS_CHECK(oslam_mp_update_windows_device((int)P, (const int32_t*)(Dv + oItems), table ? o->d_mp_tab : nullptr, (const int32_t*)(Dv + oE0), (const int32_t*)(Dv + oNe),
+    OPS_CHECK(oslam_mp_update_windows_device((int)P, (const int32_t*)(Dv + oItems), table ? o->d_mp_tab.as<uint8_t*>() : nullptr, (const int32_t*)(Dv + oE0), (const int32_t*)(Dv + oNe),
                                              (const int32_t*)(Dv + oKb), (const int32_t*)(Dv + oRef), (const float*)(Dv + oLsf), Dv + oSkip, (const float*)(Dv + oPos),
                                              (const int32_t*)(Dv + oEkf), Dv + oEr, (const float*)(Dv + oOw), o->scale[o->cfg.nLevels - 1], (float*)(Dv + oOut), o->strm));
     o->t_end();
     OPS_CHECK(o->ensure_dn(20 * P));
-    OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn_h, Dv + oOut, 20 * P, o->strm));
+    OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn.bytes(), Dv + oOut, 20 * P, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(6, 1, (double)E);
-    o->pool->parallel_for(n, [&](int i) { memcpy(wins[i].out5, o->dn_h + 20 * pb[i], 20 * (size_t)wins[i].nP); });
+    o->pool->parallel_for(n, [&](int i) { memcpy(wins[i].out5, o->dn.bytes() + 20 * pb[i], 20 * (size_t)wins[i].nP); });
     return OSLAM_OK;
 }
 
@@ -1472,66 +1432,58 @@ int h_register_keyframes(void* p, int n, const int32_t* slots, const int32_t* kf
         else {
             r = o->n_rec++;
             if (r / HipOps::kRecChunk >= (int)o->rec_chunks.size()) {
-                uint8_t* c = nullptr;
-                OSLAM_HIP_CHECK(hipMalloc((void**)&c, rb * HipOps::kRecChunk));
-                o->rec_chunks.push_back(c);
+                oslam::DeviceBuffer c;
+                OPS_CHECK(c.alloc(rb * HipOps::kRecChunk));
+                o->rec_chunks.push_back(std::move(c));
             }
             o->h_rec_desc.push_back((uint8_t*)o->rec_desc(r));
         }
         o->rec_of_kf[slot][kf] = r;
         // the frame built for `slot` in this step is still in the batch arrays
-        segs.push_back({(const uint8_t*)(o->d_keysUn + cap * slot), (uint8_t*)o->rec_keys(r), (uint32_t)(cap * sizeof(oslam_keypoint_t)), 0});
+        segs.push_back({(const uint8_t*)(o->d_keysUn.as<oslam_keypoint_t>() + cap * slot), (uint8_t*)o->rec_keys(r), (uint32_t)(cap * sizeof(oslam_keypoint_t)), 0});
         segs.push_back({o->d_desc + 32 * cap * slot, (uint8_t*)o->rec_desc(r), (uint32_t)(cap * 32), 0});
         segs.push_back({(const uint8_t*)(o->cur_uRight + cap * slot), (uint8_t*)o->rec_ur(r), (uint32_t)(cap * 4), 0});
     }
     if (o->lazy_keys && (!o->d_kp || !o->d_desc)) { oslam::set_error("register_keyframes: no frame has been built yet"); return OSLAM_E_INVALID; }
     if (o->lazy_keys) {   // mvKeys of the new keyframes: written by the same launch into a pinned block the device can address (keyframe_raw_keys hands them out)
         const size_t need = (size_t)n * cap * (sizeof(oslam_keypoint_t) + (o->lazy_desc ? 32 : 0));
-        if (need > o->kfk_cap) {
-            OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
-            if (o->kfk_h) (void)hipHostFree(o->kfk_h);
-    if (o->fc_d) (void)hipFree(o->fc_d);
-            o->kfk_h = nullptr; o->kfk_cap = 0;
-            OSLAM_HIP_CHECK(hipHostMalloc((void**)&o->kfk_h, need + need / 2 + 4096, 0));
-            o->kfk_cap = need + need / 2 + 4096;
-        }
+        if (need > o->kfk.cap()) OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
+        OPS_CHECK(o->kfk.grow(need, 4096));
         o->kfk_slots.assign(slots, slots + n);
         for (int i = 0; i < n; i++)
-            segs.push_back({(const uint8_t*)(o->d_kp + cap * slots[i]), o->kfk_h + (size_t)i * cap * sizeof(oslam_keypoint_t), (uint32_t)(cap * sizeof(oslam_keypoint_t)), 0});
+            segs.push_back({(const uint8_t*)(o->d_kp + cap * slots[i]), o->kfk.bytes() + (size_t)i * cap * sizeof(oslam_keypoint_t), (uint32_t)(cap * sizeof(oslam_keypoint_t)), 0});
         if (o->lazy_desc)
             for (int i = 0; i < n; i++)
-                segs.push_back({o->d_desc + 32 * cap * slots[i], o->kfk_h + (size_t)n * cap * sizeof(oslam_keypoint_t) + (size_t)i * cap * 32, (uint32_t)(cap * 32), 0});
+                segs.push_back({o->d_desc + 32 * cap * slots[i], o->kfk.bytes() + (size_t)n * cap * sizeof(oslam_keypoint_t) + (size_t)i * cap * 32, (uint32_t)(cap * 32), 0});
     }
     const size_t oJobs = oslam::align_up(segs.size() * sizeof(CopySegH), 256), up_bytes = oJobs + (size_t)n * sizeof(oslam_kf_grid_job_t);
     OPS_CHECK(o->ensure_up(up_bytes));
-    memcpy(o->up_h, segs.data(), segs.size() * sizeof(CopySegH));
-    oslam_kf_grid_job_t* gj = (oslam_kf_grid_job_t*)(o->up_h + oJobs);
+    memcpy(o->up.h.bytes(), segs.data(), segs.size() * sizeof(CopySegH));
+    oslam_kf_grid_job_t* gj = (oslam_kf_grid_job_t*)(o->up.h.bytes() + oJobs);
     for (int i = 0; i < n; i++) {
         const int r = o->rec_of_kf[slots[i]][kf_ids[i]];
         gj[i].keys = o->rec_keys(r); gj[i].uRight = o->rec_ur(r); gj[i].cell_end = o->rec_cell_end(r); gj[i].cand = o->rec_cand(r); gj[i].slot = slots[i]; gj[i].pad_ = 0;
     }
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up_d, o->up_h, up_bytes, hipMemcpyHostToDevice, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), o->up.h.bytes(), up_bytes, hipMemcpyHostToDevice, o->strm));
     o->t_begin();
-    OPS_CHECK(oslam_copy_segments_device(o->up_d, (int)segs.size(), o->strm));
+    OPS_CHECK(oslam_copy_segments_device(o->up.d.bytes(), (int)segs.size(), o->strm));
     // KeyFrame::mGrid of the new keyframes (fixed from here on): sorted once, read by every later Fuse against them
-    OPS_CHECK(oslam_kf_grid_build_device(n, (const oslam_kf_grid_job_t*)(o->up_d + oJobs), o->d_cnt, o->bounds, (int)cap, o->d_status + 8, o->strm));
+    OPS_CHECK(oslam_kf_grid_build_device(n, (const oslam_kf_grid_job_t*)(o->up.d.bytes() + oJobs), o->d_cnt, o->bounds, (int)cap, o->d_status.as<int32_t>() + 8, o->strm));
     o->t_end();
     // descriptor-array table for the observation gathers
-    if ((size_t)o->n_rec > o->rec_desc_cap) {
+    if ((size_t)o->n_rec * sizeof(uint8_t*) > o->d_rec_desc.cap()) {
         OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
-        if (o->d_rec_desc) (void)hipFree(o->d_rec_desc);
-        o->rec_desc_cap = (size_t)o->n_rec * 2 + 1024;
-        OSLAM_HIP_CHECK(hipMalloc((void**)&o->d_rec_desc, o->rec_desc_cap * sizeof(uint8_t*)));
+        OPS_CHECK(o->d_rec_desc.alloc(((size_t)o->n_rec * 2 + 1024) * sizeof(uint8_t*)));
         o->rec_desc_n = 0;
     }
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_rec_desc + o->rec_desc_n, o->h_rec_desc.data() + o->rec_desc_n, (size_t)(o->n_rec - o->rec_desc_n) * sizeof(uint8_t*),
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_rec_desc.as<uint8_t*>() + o->rec_desc_n, o->h_rec_desc.data() + o->rec_desc_n, (size_t)(o->n_rec - o->rec_desc_n) * sizeof(uint8_t*),
                                    hipMemcpyHostToDevice, o->strm));
     o->rec_desc_n = o->n_rec;
     OPS_CHECK(o->ensure_dn(4));
-    OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn_h, o->d_status + 8, 4, o->strm));
+    OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn.bytes(), o->d_status.as<int32_t>() + 8, 4, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));   // the records are complete when this returns
     o->t_collect(7, 2, 0);
-    if (*(const int32_t*)o->dn_h != 0) { oslam::set_error("register_keyframes: a keyframe has more keypoints than the extractor's capacity"); return OSLAM_E_CAPACITY; }
+    if (*(const int32_t*)o->dn.bytes() != 0) { oslam::set_error("register_keyframes: a keyframe has more keypoints than the extractor's capacity"); return OSLAM_E_CAPACITY; }
     return OSLAM_OK;
 }
 
@@ -1642,7 +1594,7 @@ int h_map_journal(void* p, int n, const oslam_map_changes_t* ch) {
     HipOps* o = (HipOps*)p;
     OSLAM_HIP_CHECK(hipSetDevice(o->cfg.device));
     if (n <= 0) return OSLAM_OK;
-    if ((int)o->pt_aux.size() < o->S) { o->pt_aux.resize(o->S, nullptr); o->pt_aux_cap.resize(o->S, 0); }
+    o->size_pt_aux();
     if ((int)o->okf_seq.size() < o->S) o->okf_seq.resize(o->S, 0u);
     if (o->mir_used) { OSLAM_HIP_CHECK(oslam::stream_wait(o->strm)); o->mir_used = 0; }   // (a flush without a collected count request before it: its block must have landed)
     size_t nbulk = 0, ncell = 0, nokf = 0, npt = 0, bw = 0;
@@ -1672,7 +1624,7 @@ int h_map_journal(void* p, int n, const oslam_map_changes_t* ch) {
     // event numbers: the new keyframes of a flush take the slot's counter, its observation events counter + 1 + position
     std::vector<uint32_t> seq0(n);
     for (int i = 0; i < n; i++) { seq0[i] = o->okf_seq[ch[i].slot]; o->okf_seq[ch[i].slot] += 1u + (uint32_t)ch[i].n_events; }
-    uint8_t* U = o->mir_h;
+    uint8_t* U = o->mir.h.bytes();
     // keyframe id -> record index (a keyframe whose record was released — culled — or never registered: -1, skipped on the device)
     o->pool->parallel_for(n, [&](int i) {
         const oslam_map_changes_t& c = ch[i];
@@ -1701,13 +1653,13 @@ int h_map_journal(void* p, int n, const oslam_map_changes_t* ch) {
             Pp[2 * q + 1] = make_uint4(c.points[5 * q + 3], c.points[5 * q + 4], 0u, 0u);
         }
     });
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->mir_d, o->mir_h, L.off, hipMemcpyHostToDevice, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->mir.d.bytes(), o->mir.h.bytes(), L.off, hipMemcpyHostToDevice, o->strm));
     o->mir_used = L.off;
     const MirrorGeom g = mirror_geom(o);
-    if (nbulk) hipLaunchKernelGGL(k_mirror_bulk, dim3((unsigned)nbulk), dim3(256), 0, o->strm, (const MirrorBulk*)(o->mir_d + aB), (const uint32_t*)(o->mir_d + aW), (uint8_t* const*)o->d_rec_chunk, g);
+    if (nbulk) hipLaunchKernelGGL(k_mirror_bulk, dim3((unsigned)nbulk), dim3(256), 0, o->strm, (const MirrorBulk*)(o->mir.d.bytes() + aB), (const uint32_t*)(o->mir.d.bytes() + aW), o->d_rec_chunk.as<uint8_t*>(), g);
     const size_t nops = ncell + nokf + npt;
-    if (nops) hipLaunchKernelGGL(k_mirror_ops, dim3((unsigned)((nops + 255) / 256)), dim3(256), 0, o->strm, (const int4*)(o->mir_d + aC), (int)ncell, (const uint4*)(o->mir_d + aO), (int)nokf,
-                                 (const uint4*)(o->mir_d + aP), (int)npt, (uint8_t* const*)o->d_rec_chunk, (uint8_t* const*)o->d_pt_aux, g);
+    if (nops) hipLaunchKernelGGL(k_mirror_ops, dim3((unsigned)((nops + 255) / 256)), dim3(256), 0, o->strm, (const int4*)(o->mir.d.bytes() + aC), (int)ncell, (const uint4*)(o->mir.d.bytes() + aO), (int)nokf,
+                                 (const uint4*)(o->mir.d.bytes() + aP), (int)npt, o->d_rec_chunk.as<uint8_t*>(), o->d_pt_aux.as<uint8_t*>(), g);
     OSLAM_HIP_CHECK(hipGetLastError());
     // (no wait: the consumer that follows on this stream — kf_culling_counts — synchronises; the mirror's upload block is not touched before the next flush, and
     // every operator of the step after this one waits for the stream before it returns)
@@ -1724,33 +1676,28 @@ int h_kf_culling_counts(void* p, int n, const oslam_job_cull_t* jobs, float thDe
     if (total == 0) return OSLAM_OK;
     // the request goes behind the flush in the mirror's upload block (both may be in flight together)
     const size_t base = oslam::align_up(o->mir_used, 256), oC = base, oOut = oslam::align_up(oC + sizeof(CullCand) * total, 256), end = oOut + 16 * total;
-    if (end > o->mir_cap) {   // (rare: the block is grown with nothing in flight; the flush, if any, has completed by then)
+    if (end > o->mir.cap()) {   // (rare: the block is grown with nothing in flight; the flush, if any, has completed by then)
         OSLAM_HIP_CHECK(hipStreamSynchronize(o->strm));
         o->mir_used = 0;
         OPS_CHECK(o->ensure_mir(sizeof(CullCand) * total + 16 * total + 1024));
         return h_kf_culling_counts(p, n, jobs, thDepth);
     }
-    if (16 * total > o->cull_cap) {
-        OSLAM_HIP_CHECK(hipStreamSynchronize(o->strm));
-        if (o->cull_h) (void)hipHostFree(o->cull_h);
-        o->cull_h = nullptr; o->cull_cap = 0;
-        OSLAM_HIP_CHECK(hipHostMalloc((void**)&o->cull_h, 32 * total + 4096, 0));
-        o->cull_cap = 32 * total + 4096;
-    }
-    CullCand* cc = (CullCand*)(o->mir_h + oC);
+    if (16 * total > o->cull.cap()) OSLAM_HIP_CHECK(hipStreamSynchronize(o->strm));
+    OPS_CHECK(o->cull.reserve(16 * total, 32 * total + 4096));
+    CullCand* cc = (CullCand*)(o->mir.h.bytes() + oC);
     size_t at = 0;
-    if ((int)o->pt_aux.size() < o->S) { o->pt_aux.resize(o->S, nullptr); o->pt_aux_cap.resize(o->S, 0); }
+    o->size_pt_aux();
     for (int i = 0; i < n; i++) {
         if (!o->pt_aux[jobs[i].slot]) OPS_CHECK(o->ensure_pt_aux(jobs[i].slot, 1));
         for (int q = 0; q < jobs[i].n; q++, at++) { cc[at].rec = o->rec_lookup(jobs[i].slot, jobs[i].kf_ids[q]); cc[at].slot = jobs[i].slot; }
         o->cull_pending.push_back({jobs[i].out, jobs[i].n});
     }
     OPS_CHECK(o->sync_mirror_tables());
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->mir_d + oC, o->mir_h + oC, sizeof(CullCand) * total, hipMemcpyHostToDevice, o->strm));
-    hipLaunchKernelGGL(k_cull_counts, dim3((unsigned)total), dim3(64), 0, o->strm, (const CullCand*)(o->mir_d + oC), (uint8_t* const*)o->d_rec_chunk, (uint8_t* const*)o->d_pt_aux,
-                       mirror_geom(o), (int32_t*)(o->mir_d + oOut));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->mir.d.bytes() + oC, o->mir.h.bytes() + oC, sizeof(CullCand) * total, hipMemcpyHostToDevice, o->strm));
+    hipLaunchKernelGGL(k_cull_counts, dim3((unsigned)total), dim3(64), 0, o->strm, (const CullCand*)(o->mir.d.bytes() + oC), o->d_rec_chunk.as<uint8_t*>(), o->d_pt_aux.as<uint8_t*>(),
+                       mirror_geom(o), (int32_t*)(o->mir.d.bytes() + oOut));
     OSLAM_HIP_CHECK(hipGetLastError());
-    OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->cull_h, o->mir_d + oOut, 16 * total, o->strm));
+    OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->cull.bytes(), o->mir.d.bytes() + oOut, 16 * total, o->strm));
     o->mir_used = end;
     return OSLAM_OK;   // (results: h_kf_culling_collect)
 }
@@ -1761,7 +1708,7 @@ int h_kf_culling_collect(void* p) {
     if (o->cull_pending.empty()) { o->mir_used = 0; return OSLAM_OK; }
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));   // (usually already drained: the MapPoint-update operator between request and collection synchronises the same stream)
     size_t at = 0;
-    for (const HipOps::CullPending& c : o->cull_pending) { memcpy(c.out, o->cull_h + 16 * at, 16 * (size_t)c.n); at += (size_t)c.n; }
+    for (const HipOps::CullPending& c : o->cull_pending) { memcpy(c.out, o->cull.bytes() + 16 * at, 16 * (size_t)c.n); at += (size_t)c.n; }
     o->cull_pending.clear();
     o->mir_used = 0;
     return OSLAM_OK;
@@ -1875,7 +1822,7 @@ int h_fuse_into_current(void* p, int n, oslam_job_fuse_cur_t* jobs) {
     }
     if (o->cap > 0xFFFF) { oslam::set_error("fuse_into_current: more than 65535 keypoints per keyframe"); return OSLAM_E_CAPACITY; }
     OPS_CHECK(o->sync_mp_table());
-    if ((int)o->pt_aux.size() < o->S) { o->pt_aux.resize(o->S, nullptr); o->pt_aux_cap.resize(o->S, 0); }
+    o->size_pt_aux();
     for (int i = 0; i < n; i++) if (!o->pt_aux[jobs[i].slot]) OPS_CHECK(o->ensure_pt_aux(jobs[i].slot, 1));
     OPS_CHECK(o->sync_mirror_tables());
     // job block (pinned, read in place) | device scratch: candidate ids, flags, match table, counts
@@ -1885,20 +1832,15 @@ int h_fuse_into_current(void* p, int n, oslam_job_fuse_cur_t* jobs) {
     OPS_CHECK(o->ensure_up(L.off));
     const size_t sIds = 0, sEx = oslam::align_up(sIds + 4 * (size_t)stride * B, 256), sQm = oslam::align_up(sEx + (size_t)stride * B, 256), sM = oslam::align_up(sQm + 4 * (size_t)stride * B, 256),
                  sM1 = oslam::align_up(sM + 8 * B, 256), sEnd = sM1 + 4 * B;
-    if (sEnd > o->fc_cap) {
-        OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
-        if (o->fc_d) (void)hipFree(o->fc_d);
-        o->fc_d = nullptr; o->fc_cap = 0;
-        OSLAM_HIP_CHECK(hipMalloc((void**)&o->fc_d, sEnd + sEnd / 2));
-        o->fc_cap = sEnd + sEnd / 2;
-    }
+    if (sEnd > o->fc.cap()) OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
+    OPS_CHECK(o->fc.grow(sEnd, 0));
     Layout R;
     const size_t rCnt = R.take(12 * B), rPairs = R.take(8 * (size_t)maxPairs * B);
     bool dbg = false;
     for (int i = 0; i < n; i++) dbg = dbg || (jobs[i].dbg_cap > 0 && jobs[i].dbg_ids && jobs[i].dbg_excl);
     const size_t rIds = R.take(dbg ? 4 * (size_t)stride * B : 0), rEx = R.take(dbg ? (size_t)stride * B : 0);
     OPS_CHECK(o->ensure_dn(R.off));
-    uint8_t* U = o->up_h;
+    uint8_t* U = o->up.h.bytes();
     FuseCurJob* fj = (FuseCurJob*)(U + oJ);
     int32_t* recs = (int32_t*)(U + oR);
     size_t at = 0;
@@ -1915,37 +1857,37 @@ int h_fuse_into_current(void* p, int n, oslam_job_fuse_cur_t* jobs) {
     }
     const uint32_t stamp = ++o->fc_stamp;
     const MirrorGeom g = mirror_geom(o);
-    uint8_t* D = o->fc_d;
+    uint8_t* D = o->fc.bytes();
     o->t_begin();
     hipLaunchKernelGGL(k_fusecur_mark, dim3((unsigned)((g.cap + 255) / 256), (unsigned)(maxT + 1), (unsigned)n), dim3(256), 0, o->strm, (const FuseCurJob*)(U + oJ), (const int32_t*)(U + oR),
-                       (uint8_t* const*)o->d_rec_chunk, (uint8_t* const*)o->d_pt_aux, g, stamp);
-    hipLaunchKernelGGL(k_fusecur_list, dim3((unsigned)n), dim3(1024), 0, o->strm, (const FuseCurJob*)(U + oJ), (const int32_t*)(U + oR), (uint8_t* const*)o->d_rec_chunk,
-                       (uint8_t* const*)o->d_pt_aux, g, stamp, stride, (int32_t*)(D + sIds), D + sEx, (int32_t*)(D + sM));
+                       o->d_rec_chunk.as<uint8_t*>(), o->d_pt_aux.as<uint8_t*>(), g, stamp);
+    hipLaunchKernelGGL(k_fusecur_list, dim3((unsigned)n), dim3(1024), 0, o->strm, (const FuseCurJob*)(U + oJ), (const int32_t*)(U + oR), o->d_rec_chunk.as<uint8_t*>(),
+                       o->d_pt_aux.as<uint8_t*>(), g, stamp, stride, (int32_t*)(D + sIds), D + sEx, (int32_t*)(D + sM));
     OSLAM_HIP_CHECK(hipGetLastError());
     // (k_fuse_search reads M at d_M[b]; the list kernel's table holds [M, overflow] pairs: the search gets a compacted copy)
     hipLaunchKernelGGL(k_fusecur_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o->strm, (const int32_t*)(D + sM), n, (int32_t*)(D + sM1));
     OPS_CHECK(oslam_fuse_search_device(n, stride, (const oslam_kf_grid_ref_t*)(U + oRef), (const int32_t*)(U + oSl), (const int32_t*)(D + sM1), (const int32_t*)(D + sIds), D + sEx,
-                                       o->d_mp_tab, (const float*)(U + oT), (const float*)(U + oOw), o->K5, o->bounds, jobs[0].th, o->logScale, o->scale, o->invSigma2, o->cfg.nLevels,
+                                       o->d_mp_tab.as<uint8_t*>(), (const float*)(U + oT), (const float*)(U + oOw), o->K5, o->bounds, jobs[0].th, o->logScale, o->scale, o->invSigma2, o->cfg.nLevels,
                                        (int32_t*)(D + sQm), o->strm));
     hipLaunchKernelGGL(k_fusecur_pairs, dim3((unsigned)n), dim3(1024), 0, o->strm, (const int32_t*)(D + sM), (const int32_t*)(D + sIds), (const int32_t*)(D + sQm), stride, maxPairs,
-                       (int32_t*)(o->dn_h + rPairs), (int32_t*)(o->dn_h + rCnt));
+                       (int32_t*)(o->dn.bytes() + rPairs), (int32_t*)(o->dn.bytes() + rCnt));
     OSLAM_HIP_CHECK(hipGetLastError());
     if (dbg) {
-        OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn_h + rIds, D + sIds, 4 * (size_t)stride * B, o->strm));
-        OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn_h + rEx, D + sEx, (size_t)stride * B, o->strm));
+        OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn.bytes() + rIds, D + sIds, 4 * (size_t)stride * B, o->strm));
+        OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn.bytes() + rEx, D + sEx, (size_t)stride * B, o->strm));
     }
     o->t_end();
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(4, 4, 0);
-    const int32_t* cnt = (const int32_t*)(o->dn_h + rCnt);
+    const int32_t* cnt = (const int32_t*)(o->dn.bytes() + rCnt);
     for (int i = 0; i < n; i++) {
         oslam_job_fuse_cur_t& j = jobs[i];
         j.n_pairs = cnt[3 * i]; j.n_candidates = cnt[3 * i + 1]; j.overflow = (cnt[3 * i + 2] != 0 || j.n_pairs > maxPairs || j.n_pairs > j.max_pairs) ? 1 : 0;
-        if (!j.overflow) memcpy(j.pairs, o->dn_h + rPairs + 8 * (size_t)maxPairs * i, 8 * (size_t)j.n_pairs);
+        if (!j.overflow) memcpy(j.pairs, o->dn.bytes() + rPairs + 8 * (size_t)maxPairs * i, 8 * (size_t)j.n_pairs);
         if (j.dbg_cap > 0 && j.dbg_ids && j.dbg_excl) {
             const int m = std::min(j.n_candidates, j.dbg_cap);
-            memcpy(j.dbg_ids, o->dn_h + rIds + 4 * (size_t)stride * i, 4 * (size_t)m);
-            memcpy(j.dbg_excl, o->dn_h + rEx + (size_t)stride * i, (size_t)m);
+            memcpy(j.dbg_ids, o->dn.bytes() + rIds + 4 * (size_t)stride * i, 4 * (size_t)m);
+            memcpy(j.dbg_excl, o->dn.bytes() + rEx + (size_t)stride * i, (size_t)m);
         }
     }
     return OSLAM_OK;
@@ -1967,7 +1909,7 @@ int h_local_points_list(void* p, int n, oslam_job_local_list_t* jobs) {
         nrec += (size_t)j.n_kfs; maxT = std::max(maxT, j.n_kfs);
     }
     if (o->cap > 0xFFFF) { oslam::set_error("local_points_list: more than 65535 keypoints per keyframe"); return OSLAM_E_CAPACITY; }
-    if ((int)o->pt_aux.size() < o->S) { o->pt_aux.resize(o->S, nullptr); o->pt_aux_cap.resize(o->S, 0); }
+    o->size_pt_aux();
     for (int i = 0; i < n; i++) if (!o->pt_aux[jobs[i].slot]) OPS_CHECK(o->ensure_pt_aux(jobs[i].slot, 1));
     OPS_CHECK(o->sync_mirror_tables());
     const size_t B = n;
@@ -1975,17 +1917,12 @@ int h_local_points_list(void* p, int n, oslam_job_local_list_t* jobs) {
     const size_t oJ = L.take(sizeof(FuseCurJob) * B), oR = L.take(4 * std::max<size_t>(nrec, 1));
     OPS_CHECK(o->ensure_up(L.off));
     const size_t sEx = 0, sEnd = (size_t)stride * B;
-    if (sEnd > o->fc_cap) {
-        OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
-        if (o->fc_d) (void)hipFree(o->fc_d);
-        o->fc_d = nullptr; o->fc_cap = 0;
-        OSLAM_HIP_CHECK(hipMalloc((void**)&o->fc_d, sEnd + sEnd / 2));
-        o->fc_cap = sEnd + sEnd / 2;
-    }
+    if (sEnd > o->fc.cap()) OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
+    OPS_CHECK(o->fc.grow(sEnd, 0));
     Layout R;
     const size_t rM = R.take(8 * B), rIds = R.take(4 * (size_t)stride * B);
     OPS_CHECK(o->ensure_dn(R.off));
-    uint8_t* U = o->up_h;
+    uint8_t* U = o->up.h.bytes();
     FuseCurJob* fj = (FuseCurJob*)(U + oJ);
     int32_t* recs = (int32_t*)(U + oR);
     size_t at = 0;
@@ -1998,18 +1935,18 @@ int h_local_points_list(void* p, int n, oslam_job_local_list_t* jobs) {
     const MirrorGeom g = mirror_geom(o);
     o->t_begin();
     hipLaunchKernelGGL(k_fusecur_mark, dim3((unsigned)((g.cap + 255) / 256), (unsigned)(maxT + 1), (unsigned)n), dim3(256), 0, o->strm, (const FuseCurJob*)(U + oJ), (const int32_t*)(U + oR),
-                       (uint8_t* const*)o->d_rec_chunk, (uint8_t* const*)o->d_pt_aux, g, stamp);
-    hipLaunchKernelGGL(k_fusecur_list, dim3((unsigned)n), dim3(1024), 0, o->strm, (const FuseCurJob*)(U + oJ), (const int32_t*)(U + oR), (uint8_t* const*)o->d_rec_chunk,
-                       (uint8_t* const*)o->d_pt_aux, g, stamp, stride, (int32_t*)(o->dn_h + rIds), o->fc_d + sEx, (int32_t*)(o->dn_h + rM));
+                       o->d_rec_chunk.as<uint8_t*>(), o->d_pt_aux.as<uint8_t*>(), g, stamp);
+    hipLaunchKernelGGL(k_fusecur_list, dim3((unsigned)n), dim3(1024), 0, o->strm, (const FuseCurJob*)(U + oJ), (const int32_t*)(U + oR), o->d_rec_chunk.as<uint8_t*>(),
+                       o->d_pt_aux.as<uint8_t*>(), g, stamp, stride, (int32_t*)(o->dn.bytes() + rIds), o->fc.bytes() + sEx, (int32_t*)(o->dn.bytes() + rM));
     OSLAM_HIP_CHECK(hipGetLastError());
     o->t_end();
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(3, 2, 0);
-    const int32_t* Mn = (const int32_t*)(o->dn_h + rM);
+    const int32_t* Mn = (const int32_t*)(o->dn.bytes() + rM);
     for (int i = 0; i < n; i++) {
         oslam_job_local_list_t& j = jobs[i];
         j.n_ids = Mn[2 * i]; j.overflow = (Mn[2 * i + 1] != 0 || j.n_ids > j.cap) ? 1 : 0;
-        if (!j.overflow) memcpy(j.ids, o->dn_h + rIds + 4 * (size_t)stride * i, 4 * (size_t)j.n_ids);
+        if (!j.overflow) memcpy(j.ids, o->dn.bytes() + rIds + 4 * (size_t)stride * i, 4 * (size_t)j.n_ids);
     }
     return OSLAM_OK;
 }
@@ -2037,7 +1974,7 @@ int h_bow_nodes_keyed(void* p, int n, const int32_t* slots, const int32_t* kf_id
     const size_t oOut = L.take(4 * cap * (size_t)n);
     OPS_CHECK(o->ensure_up(L.off));
     OPS_CHECK(o->ensure_dn(4 * cap * (size_t)n));
-    uint8_t* U = o->up_h;
+    uint8_t* U = o->up.h.bytes();
     for (int i = 0; i < n; i++) {
         const int r = o->rec_lookup(slots[i], kf_ids[i]);
         if (r < 0 || counts[i] < 0 || counts[i] > (int)cap) { oslam::set_error("bow_nodes: keyframe not resident / bad count"); return OSLAM_E_INVALID; }
@@ -2045,16 +1982,16 @@ int h_bow_nodes_keyed(void* p, int n, const int32_t* slots, const int32_t* kf_id
         ((int32_t*)(U + oCnt))[i] = counts[i];
     }
     memcpy(U + oTop, top, 320); memcpy(U + oSub, sub, 3200);
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up_d, U, in_bytes, hipMemcpyHostToDevice, o->strm));
-    uint8_t* Dv = o->up_d;
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), U, in_bytes, hipMemcpyHostToDevice, o->strm));
+    uint8_t* Dv = o->up.d.bytes();
     o->t_begin();
     OPS_CHECK(oslam_bow_nodes_device((const uint8_t* const*)(Dv + oPtr), (const int32_t*)(Dv + oCnt), n, (int)cap, (const uint64_t*)(Dv + oTop), (const uint64_t*)(Dv + oSub),
                                      (uint32_t*)(Dv + oOut), o->strm));
     o->t_end();
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h, Dv + oOut, 4 * cap * (size_t)n, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes(), Dv + oOut, 4 * cap * (size_t)n, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(7, 1, 0);
-    o->pool->parallel_for(n, [&](int i) { memcpy(out[i], o->dn_h + 4 * cap * (size_t)i, 4 * (size_t)counts[i]); });
+    o->pool->parallel_for(n, [&](int i) { memcpy(out[i], o->dn.bytes() + 4 * cap * (size_t)i, 4 * (size_t)counts[i]); });
     return OSLAM_OK;
 }
 
@@ -2070,22 +2007,22 @@ int h_voc_nodes_keyed(void* p, const oslam_voc_t* voc, int levelsup, int n, cons
     const size_t oOut = L.take(4 * cap * (size_t)n);
     OPS_CHECK(o->ensure_up(L.off));
     OPS_CHECK(o->ensure_dn(4 * cap * (size_t)n));
-    uint8_t* U = o->up_h;
+    uint8_t* U = o->up.h.bytes();
     for (int i = 0; i < n; i++) {
         const int r = o->rec_lookup(slots[i], kf_ids[i]);
         if (r < 0 || counts[i] < 0 || counts[i] > (int)cap) { oslam::set_error("voc_nodes: keyframe not resident / bad count"); return OSLAM_E_INVALID; }
         ((const uint8_t**)(U + oPtr))[i] = o->rec_desc(r);
         ((int32_t*)(U + oCnt))[i] = counts[i];
     }
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up_d, U, in_bytes, hipMemcpyHostToDevice, o->strm));
-    uint8_t* Dv = o->up_d;
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), U, in_bytes, hipMemcpyHostToDevice, o->strm));
+    uint8_t* Dv = o->up.d.bytes();
     o->t_begin();
     OPS_CHECK(oslam_voc_transform_device(voc, (const uint8_t* const*)(Dv + oPtr), (const int32_t*)(Dv + oCnt), n, (int)cap, levelsup, nullptr, (uint32_t*)(Dv + oOut), nullptr, o->strm));
     o->t_end();
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h, Dv + oOut, 4 * cap * (size_t)n, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes(), Dv + oOut, 4 * cap * (size_t)n, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(7, 1, 0);
-    o->pool->parallel_for(n, [&](int i) { memcpy(out[i], o->dn_h + 4 * cap * (size_t)i, 4 * (size_t)counts[i]); });
+    o->pool->parallel_for(n, [&](int i) { memcpy(out[i], o->dn.bytes() + 4 * cap * (size_t)i, 4 * (size_t)counts[i]); });
     return OSLAM_OK;
 }
 
@@ -2099,7 +2036,7 @@ int h_bow_keyed(void* p, int n, oslam_job_bow_t* jobs, const oslam_kf_key_t* key
         const int r1 = o->rec_lookup(keys[i].slot, keys[i].kf1);
         if (r1 >= 0) { res[i].d_keys1 = o->rec_keys(r1); res[i].d_desc1 = o->rec_desc(r1); res[i].d_uRight1 = o->rec_ur(r1); }
         if (keys[i].kf2 == -2 && keys[i].slot >= 0 && keys[i].slot < o->S) {   // side 2 = the current frame of the slot
-            res[i].d_keys2 = o->d_keysUn + cap * keys[i].slot; res[i].d_desc2 = o->d_desc + 32 * cap * keys[i].slot; res[i].d_uRight2 = o->cur_uRight + cap * keys[i].slot;
+            res[i].d_keys2 = o->d_keysUn.as<oslam_keypoint_t>() + cap * keys[i].slot; res[i].d_desc2 = o->d_desc + 32 * cap * keys[i].slot; res[i].d_uRight2 = o->cur_uRight + cap * keys[i].slot;
         } else {
             const int r2 = o->rec_lookup(keys[i].slot, keys[i].kf2);
             if (r2 >= 0) { res[i].d_keys2 = o->rec_keys(r2); res[i].d_desc2 = o->rec_desc(r2); res[i].d_uRight2 = o->rec_ur(r2); }
@@ -2157,8 +2094,8 @@ static int fuse_impl(HipOps* o, int n, oslam_job_fuse_t* jobs, const oslam_kf_ke
     const size_t small_bytes = L.off;
     const size_t oKeys = L.take(sizeof(oslam_keypoint_t) * cap * B), oUr = L.take(4 * cap * B), oDesc = L.take(32 * cap * B);
     OPS_CHECK(o->ensure_up(L.off));
-    uint8_t* U = o->up_h;
-    uint8_t* Dv = o->up_d;
+    uint8_t* U = o->up.h.bytes();
+    uint8_t* Dv = o->up.d.bytes();
     std::vector<int> rec(n, -1);
     int nres = 0;
     if (keys) for (int i = 0; i < n; i++) { rec[i] = o->rec_lookup(keys[i].slot, keys[i].kf1); nres += rec[i] >= 0; }
@@ -2192,10 +2129,10 @@ static int fuse_impl(HipOps* o, int n, oslam_job_fuse_t* jobs, const oslam_kf_ke
     const int32_t* d_qm;
     OPS_CHECK(oslam_match_results_device(o->m_map, &d_qm, nullptr, nullptr, nullptr, nullptr, nullptr));
     OPS_CHECK(o->ensure_dn(4 * st * B));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h, d_qm, 4 * st * B, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes(), d_qm, 4 * st * B, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(4, 2, 0);
-    o->pool->parallel_for(n, [&](int i) { memcpy(jobs[i].q_match, o->dn_h + 4 * st * i, 4 * (size_t)jobs[i].M); });
+    o->pool->parallel_for(n, [&](int i) { memcpy(jobs[i].q_match, o->dn.bytes() + 4 * st * i, 4 * (size_t)jobs[i].M); });
     return OSLAM_OK;
 }
 
@@ -2226,8 +2163,8 @@ int h_fuse_points_keyed(void* p, int n, oslam_job_fuse_pts_t* jobs) {
         const size_t head = L.off;
         OPS_CHECK(o->ensure_up(L.off));
         OPS_CHECK(o->ensure_dn(4 * st * B));   // the match table: written by the kernel itself
-        uint8_t* U = o->up_h;
-        uint8_t* Dv = o->up_d;
+        uint8_t* U = o->up.h.bytes();
+        uint8_t* Dv = o->up.d.bytes();
         o->pool->parallel_for(n, [&](int i) {
             const oslam_job_fuse_pts_t& j = jobs[i];
             const size_t M = j.M;
@@ -2244,12 +2181,12 @@ int h_fuse_points_keyed(void* p, int n, oslam_job_fuse_pts_t* jobs) {
         if (upload) OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, head, hipMemcpyHostToDevice, o->strm));
         o->t_begin();
         OPS_CHECK(oslam_fuse_search_device(n, (int)st, (const oslam_kf_grid_ref_t*)(In + oRef), (const int32_t*)(In + oSl), (const int32_t*)(In + oM), (const int32_t*)(In + oIds),
-                                           In + oEx, o->d_mp_tab, (const float*)(In + oT), (const float*)(In + oOw), o->K5, o->bounds, jobs[0].th, o->logScale, o->scale,
-                                           o->invSigma2, o->cfg.nLevels, (int32_t*)o->dn_h, o->strm));   // (every query writes its one result: straight into the pinned result block, no copy kernel behind it)
+                                           In + oEx, o->d_mp_tab.as<uint8_t*>(), (const float*)(In + oT), (const float*)(In + oOw), o->K5, o->bounds, jobs[0].th, o->logScale, o->scale,
+                                           o->invSigma2, o->cfg.nLevels, (int32_t*)o->dn.bytes(), o->strm));   // (every query writes its one result: straight into the pinned result block, no copy kernel behind it)
         o->t_end();
         OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
         o->t_collect(4, 1, 0);
-        o->pool->parallel_for(n, [&](int i) { memcpy(jobs[i].q_match, o->dn_h + 4 * st * i, 4 * (size_t)jobs[i].M); });
+        o->pool->parallel_for(n, [&](int i) { memcpy(jobs[i].q_match, o->dn.bytes() + 4 * st * i, 4 * (size_t)jobs[i].M); });
         return OSLAM_OK;
     }
     if (maxM > o->max_local) {
@@ -2267,8 +2204,8 @@ int h_fuse_points_keyed(void* p, int n, oslam_job_fuse_pts_t* jobs) {
     const size_t head = L.off;
     const size_t oQ = L.take(sizeof(oslam_proj_query_t) * st * B), oKeys = L.take(sizeof(oslam_keypoint_t) * cap * B), oUr = L.take(4 * cap * B), oDesc = L.take(32 * cap * B);
     OPS_CHECK(o->ensure_up(L.off));
-    uint8_t* U = o->up_h;
-    uint8_t* Dv = o->up_d;
+    uint8_t* U = o->up.h.bytes();
+    uint8_t* Dv = o->up.d.bytes();
     CopySegH* segs = (CopySegH*)(U + oSeg);
     o->pool->parallel_for(n, [&](int i) {
         const oslam_job_fuse_pts_t& j = jobs[i];
@@ -2283,7 +2220,7 @@ int h_fuse_points_keyed(void* p, int n, oslam_job_fuse_pts_t* jobs) {
     OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, head, hipMemcpyHostToDevice, o->strm));
     o->t_begin();
     OPS_CHECK(oslam_copy_segments_device(Dv + oSeg, 3 * n, o->strm));
-    OPS_CHECK(oslam_fuse_queries_device(n, (int)st, (const int32_t*)(Dv + oSl), (const int32_t*)(Dv + oM), (const int32_t*)(Dv + oIds), Dv + oEx, o->d_mp_tab,
+    OPS_CHECK(oslam_fuse_queries_device(n, (int)st, (const int32_t*)(Dv + oSl), (const int32_t*)(Dv + oM), (const int32_t*)(Dv + oIds), Dv + oEx, o->d_mp_tab.as<uint8_t*>(),
                                         (const float*)(Dv + oT), (const float*)(Dv + oOw), o->K5, o->bounds, jobs[0].th, o->logScale, o->scale, o->cfg.nLevels,
                                         (oslam_proj_query_t*)(Dv + oQ), o->strm));
     oslam_match_frames_t fr;
@@ -2295,10 +2232,10 @@ int h_fuse_points_keyed(void* p, int n, oslam_job_fuse_pts_t* jobs) {
     const int32_t* d_qm;
     OPS_CHECK(oslam_match_results_device(o->m_map, &d_qm, nullptr, nullptr, nullptr, nullptr, nullptr));
     OPS_CHECK(o->ensure_dn(4 * st * B));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn_h, d_qm, 4 * st * B, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes(), d_qm, 4 * st * B, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(4, 3, 0);
-    o->pool->parallel_for(n, [&](int i) { memcpy(jobs[i].q_match, o->dn_h + 4 * st * i, 4 * (size_t)jobs[i].M); });
+    o->pool->parallel_for(n, [&](int i) { memcpy(jobs[i].q_match, o->dn.bytes() + 4 * st * i, 4 * (size_t)jobs[i].M); });
     return OSLAM_OK;
 }
 
@@ -2337,33 +2274,15 @@ void h_destroy(void* p) {
     (void)hipSetDevice(o->cfg.device);
     if (o->job_active) (void)h_lba_wait(o);   // (the submitted windows' arrays belong to the driver handle being destroyed)
     lba_service_release(o->svc);
-    oslam_orb_destroy(o->orb); oslam_orb_destroy(o->orbR); oslam_stereo_destroy(o->stereo); (void)hipFree(o->d_grayR); oslam_matcher_destroy(o->m_last); oslam_matcher_destroy(o->m_map); oslam_poseopt_destroy(o->po);
+    oslam_orb_destroy(o->orb); oslam_orb_destroy(o->orbR); oslam_stereo_destroy(o->stereo); oslam_matcher_destroy(o->m_last); oslam_matcher_destroy(o->m_map); oslam_poseopt_destroy(o->po);
     oslam_lba_destroy(o->ba); oslam_lba_destroy(o->ba1); oslam_mappoint_destroy(o->mp); oslam_frame_destroy(o->fr); oslam_bow_destroy(o->bow);
-    if (o->up_h) (void)hipHostFree(o->up_h);
-    if (o->dn_h) (void)hipHostFree(o->dn_h);
-    for (uint8_t* c : o->rec_chunks) (void)hipFree(c);
-    if (o->d_rec_desc) (void)hipFree(o->d_rec_desc);
-    for (uint8_t* q : o->mp_tab) if (q) (void)hipFree(q);
-    (void)hipFree(o->d_mp_tab);
-    for (uint8_t* q : o->pt_aux) if (q) (void)hipFree(q);
-    if (o->d_pt_aux) (void)hipFree(o->d_pt_aux);
-    if (o->d_rec_chunk) (void)hipFree(o->d_rec_chunk);
-    if (o->cull_h) (void)hipHostFree(o->cull_h);
-    if (o->mir_h) (void)hipHostFree(o->mir_h);
-    if (o->mir_d) (void)hipFree(o->mir_d);
-    (void)hipFree(o->up_d); (void)hipFree(o->d_maskbits); (void)hipFree(o->d_loc); (void)hipFree(o->d_lq); (void)hipFree(o->d_inview); (void)hipFree(o->d_objbits); (void)hipFree(o->d_maskstage);
     delete o->pool;
     if (o->tev0) (void)hipEventDestroy(o->tev0);
     if (o->tevB0) (void)hipEventDestroy(o->tevB0);
     if (o->tevB1) (void)hipEventDestroy(o->tevB1);
-    if (o->upB_h) (void)hipHostFree(o->upB_h);
-    if (o->kfk_h) (void)hipHostFree(o->kfk_h);
-    if (o->upB_d) (void)hipFree(o->upB_d);
-    if (o->dnB_h) (void)hipHostFree(o->dnB_h);
     if (o->tev1) (void)hipEventDestroy(o->tev1);
     if (o->strm) (void)hipStreamDestroy(o->strm);
-    (void)hipFree(o->d_gray); (void)hipFree(o->d_depth); (void)hipFree(o->d_keysUn); (void)hipFree(o->d_keysUn_prev); (void)hipFree(o->d_uRight); (void)hipFree(o->d_mvDepth); (void)hipFree(o->d_status);
-    delete o;
+    delete o;   // (with every block of device and pinned memory it holds)
 }
 
 }  // namespace
@@ -2414,17 +2333,16 @@ int oslam_slam_make_hip_ops(const oslam_slam_config_t* cfg, oslam_slam_ops_t* op
     if (!rc) {
         o->gray_pitch = oslam::align_up((size_t)cfg->width, 64);
         const size_t S = o->S;
-        hipError_t e = hipMalloc((void**)&o->d_gray, o->gray_pitch * cfg->height * S);
-        if (e == hipSuccess && cfg->sensor == 1) e = hipMalloc((void**)&o->d_grayR, o->gray_pitch * cfg->height * S);
-        if (e == hipSuccess) e = hipMalloc((void**)&o->d_depth, (size_t)cfg->width * cfg->height * 4 * S);
-        if (e == hipSuccess) e = hipMalloc((void**)&o->d_keysUn, sizeof(oslam_keypoint_t) * o->cap * S);
-        if (e == hipSuccess) e = hipMalloc((void**)&o->d_keysUn_prev, sizeof(oslam_keypoint_t) * o->cap * S);
-        if (e == hipSuccess) e = hipMalloc((void**)&o->d_uRight, 4 * (size_t)o->cap * S);
-        if (e == hipSuccess) e = hipMalloc((void**)&o->d_mvDepth, 4 * (size_t)o->cap * S);
-        if (e == hipSuccess) e = hipMalloc((void**)&o->d_objbits, (size_t)o->cap * S);
-        if (e == hipSuccess) e = hipMalloc((void**)&o->d_status, 64);
-        if (e == hipSuccess) e = hipMemset(o->d_status, 0, 64);
-        if (e != hipSuccess) { oslam::set_error("slam ops: hipMalloc failed: %s", hipGetErrorString(e)); rc = OSLAM_E_HIP; }
+        rc = o->d_gray.alloc(o->gray_pitch * cfg->height * S);
+        if (!rc && cfg->sensor == 1) rc = o->d_grayR.alloc(o->gray_pitch * cfg->height * S);
+        if (!rc) rc = o->d_depth.alloc((size_t)cfg->width * cfg->height * 4 * S);
+        if (!rc) rc = o->d_keysUn.alloc(sizeof(oslam_keypoint_t) * o->cap * S);
+        if (!rc) rc = o->d_keysUn_prev.alloc(sizeof(oslam_keypoint_t) * o->cap * S);
+        if (!rc) rc = o->d_uRight.alloc(4 * (size_t)o->cap * S);
+        if (!rc) rc = o->d_mvDepth.alloc(4 * (size_t)o->cap * S);
+        if (!rc) rc = o->d_objbits.alloc((size_t)o->cap * S);
+        if (!rc) rc = o->d_status.alloc(64);
+        if (!rc && hipMemset(o->d_status.ptr(), 0, 64) != hipSuccess) { oslam::set_error("slam ops: hipMemset failed"); rc = OSLAM_E_HIP; }
     }
     if (!rc && hipDeviceSynchronize() != hipSuccess) { oslam::set_error("slam ops: device synchronisation failed"); rc = OSLAM_E_HIP; }   // creation-time fills ran on the null stream
     if (rc) { h_destroy(o); return rc; }

@@ -327,18 +327,15 @@ using namespace oslam;
 struct oslam_stereo {
     int device = 0, max_batch = 0, max_kps = 0;
     size_t lds = 0;
-    float* d_uRight = nullptr; float* d_depth = nullptr; int* d_sad = nullptr; int* d_nm = nullptr;
-    short* d_best = nullptr; unsigned short* d_items = nullptr;
-    oslam_keypoint_t* d_kpL = nullptr; oslam_keypoint_t* d_kpR = nullptr; uint8_t* d_descL = nullptr; uint8_t* d_descR = nullptr;
+    DeviceBuffer d_uRight, d_depth, d_sad, d_nm;    // float, float, int, int
+    DeviceBuffer d_best, d_items;                   // short, unsigned short
+    DeviceBuffer d_kpL, d_kpR, d_descL, d_descR;    // oslam_keypoint_t, oslam_keypoint_t, uint8_t, uint8_t
 };
 
 extern "C" {
 
 void oslam_stereo_destroy(oslam_stereo_t* h) {
     if (!h) return;
-    void* ptrs[] = {h->d_uRight, h->d_depth, h->d_sad, h->d_nm, h->d_best, h->d_items, h->d_kpL, h->d_kpR, h->d_descL, h->d_descR};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
     delete h;
 }
 
@@ -354,19 +351,14 @@ int oslam_stereo_create(oslam_stereo_t** out, int max_batch, int max_keypoints, 
     h->device = device; h->max_batch = max_batch; h->max_kps = max_keypoints;
     h->lds = (size_t)max_keypoints * (32 + 4 + 2 + 2 + 1) + (kStereoMaxRows + 1) * 4 + 64;   // k_stereo_scan: descriptors, u, row band, octave + row starts
     const size_t B = max_batch, NK = max_keypoints;
-#define ALLOC(ptr, bytes)                                                         \
-    do {                                                                          \
-        hipError_t e_ = hipMalloc((void**)&(ptr), (bytes));                       \
-        if (e_ != hipSuccess) {                                                   \
-            set_error("hipMalloc(%zu) failed: %s", (size_t)(bytes), hipGetErrorString(e_)); \
-            oslam_stereo_destroy(h);                                              \
-            return OSLAM_E_HIP;                                                   \
-        }                                                                         \
-    } while (0)
-    ALLOC(h->d_uRight, B * NK * 4); ALLOC(h->d_depth, B * NK * 4); ALLOC(h->d_sad, B * NK * 4); ALLOC(h->d_nm, B * 4);
-    ALLOC(h->d_best, B * NK * sizeof(short)); ALLOC(h->d_items, B * NK * kRowItemsPerKp * sizeof(unsigned short));
-    ALLOC(h->d_kpL, NK * sizeof(oslam_keypoint_t)); ALLOC(h->d_kpR, NK * sizeof(oslam_keypoint_t)); ALLOC(h->d_descL, NK * 32); ALLOC(h->d_descR, NK * 32);
-#undef ALLOC
+    int rc;
+    if ((rc = h->d_uRight.alloc(B * NK * 4)) || (rc = h->d_depth.alloc(B * NK * 4)) || (rc = h->d_sad.alloc(B * NK * 4)) || (rc = h->d_nm.alloc(B * 4)) ||
+        (rc = h->d_best.alloc(B * NK * sizeof(short))) || (rc = h->d_items.alloc(B * NK * kRowItemsPerKp * sizeof(unsigned short))) ||
+        (rc = h->d_kpL.alloc(NK * sizeof(oslam_keypoint_t))) || (rc = h->d_kpR.alloc(NK * sizeof(oslam_keypoint_t))) || (rc = h->d_descL.alloc(NK * 32)) ||
+        (rc = h->d_descR.alloc(NK * 32))) {
+        delete h;
+        return rc;
+    }
     OSLAM_HIP_CHECK(hipFuncSetAttribute((const void*)k_stereo_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds));
     *out = h;
     return OSLAM_OK;
@@ -411,7 +403,7 @@ int oslam_stereo_match_batch_device(oslam_stereo_t* h, oslam_orb_t* orbL, oslam_
     c.kpL = d_kpL; c.descL = d_descL; c.nL = d_nL; c.nL_const = nL_const;
     c.kpR = d_kpR; c.descR = d_descR; c.nR = d_nR; c.nR_const = nR_const;
     c.kp_stride = kp_stride; c.bf = bf; c.b = b;
-    c.uRight = h->d_uRight; c.depth = h->d_depth; c.sad = h->d_sad; c.n_matched = h->d_nm; c.best = h->d_best; c.row_items = h->d_items;
+    c.uRight = h->d_uRight.as<float>(); c.depth = h->d_depth.as<float>(); c.sad = h->d_sad.as<int>(); c.n_matched = h->d_nm.as<int>(); c.best = h->d_best.as<short>(); c.row_items = h->d_items.as<unsigned short>();
     if (c.L.h[0] > kStereoMaxRows) { set_error("image height %d above the stereo row table (%d)", c.L.h[0], kStereoMaxRows); return OSLAM_E_CAPACITY; }
     hipLaunchKernelGGL(k_stereo_scan, dim3(batch), dim3(kStereoThreads), h->lds, (hipStream_t)stream, c, h->max_kps);
     hipLaunchKernelGGL(k_stereo_sad, dim3((kp_stride + 3) / 4, batch), dim3(256), 0, (hipStream_t)stream, c, h->max_kps);
@@ -422,9 +414,9 @@ int oslam_stereo_match_batch_device(oslam_stereo_t* h, oslam_orb_t* orbL, oslam_
 
 int oslam_stereo_results_device(const oslam_stereo_t* h, const float** d_uRight, const float** d_depth, const int32_t** d_n_matched) {
     if (!h) { set_error("NULL handle"); return OSLAM_E_INVALID; }
-    if (d_uRight) *d_uRight = h->d_uRight;
-    if (d_depth) *d_depth = h->d_depth;
-    if (d_n_matched) *d_n_matched = h->d_nm;
+    if (d_uRight) *d_uRight = h->d_uRight.as<float>();
+    if (d_depth) *d_depth = h->d_depth.as<float>();
+    if (d_n_matched) *d_n_matched = h->d_nm.as<int>();
     return OSLAM_OK;
 }
 
@@ -435,23 +427,23 @@ int oslam_stereo_match(oslam_stereo_t* h, oslam_orb_t* orbL, oslam_orb_t* orbR, 
     if (N < 0 || Nr < 0 || N > h->max_kps || Nr > h->max_kps) { set_error("keypoint count exceeds capacity %d", h->max_kps); return OSLAM_E_CAPACITY; }
     OSLAM_HIP_CHECK(hipSetDevice(h->device));
     if (N > 0) {
-        OSLAM_HIP_CHECK(hipMemcpy(h->d_kpL, keysL, (size_t)N * sizeof(oslam_keypoint_t), hipMemcpyHostToDevice));
-        OSLAM_HIP_CHECK(hipMemcpy(h->d_descL, descL, (size_t)N * 32, hipMemcpyHostToDevice));
+        OSLAM_HIP_CHECK(hipMemcpy(h->d_kpL.as<oslam_keypoint_t>(), keysL, (size_t)N * sizeof(oslam_keypoint_t), hipMemcpyHostToDevice));
+        OSLAM_HIP_CHECK(hipMemcpy(h->d_descL.bytes(), descL, (size_t)N * 32, hipMemcpyHostToDevice));
     }
     if (Nr > 0) {
-        OSLAM_HIP_CHECK(hipMemcpy(h->d_kpR, keysR, (size_t)Nr * sizeof(oslam_keypoint_t), hipMemcpyHostToDevice));
-        OSLAM_HIP_CHECK(hipMemcpy(h->d_descR, descR, (size_t)Nr * 32, hipMemcpyHostToDevice));
+        OSLAM_HIP_CHECK(hipMemcpy(h->d_kpR.as<oslam_keypoint_t>(), keysR, (size_t)Nr * sizeof(oslam_keypoint_t), hipMemcpyHostToDevice));
+        OSLAM_HIP_CHECK(hipMemcpy(h->d_descR.bytes(), descR, (size_t)Nr * 32, hipMemcpyHostToDevice));
     }
-    int rc = oslam_stereo_match_batch_device(h, orbL, orbR, 1, h->max_kps, h->d_kpL, h->d_descL, nullptr, N, h->d_kpR, h->d_descR, nullptr, Nr,
+    int rc = oslam_stereo_match_batch_device(h, orbL, orbR, 1, h->max_kps, h->d_kpL.as<oslam_keypoint_t>(), h->d_descL.bytes(), nullptr, N, h->d_kpR.as<oslam_keypoint_t>(), h->d_descR.bytes(), nullptr, Nr,
                                              nlevels, bf, b, nullptr);
     if (rc) return rc;
     OSLAM_HIP_CHECK(hipDeviceSynchronize());
     int nm = 0;
-    OSLAM_HIP_CHECK(hipMemcpy(&nm, h->d_nm, 4, hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(&nm, h->d_nm.as<int>(), 4, hipMemcpyDeviceToHost));
     if (nm < 0) { set_error("stereo kernel rejected the frame (capacity)"); return OSLAM_E_CAPACITY; }
     if (N > 0) {
-        OSLAM_HIP_CHECK(hipMemcpy(uRight, h->d_uRight, (size_t)N * 4, hipMemcpyDeviceToHost));
-        OSLAM_HIP_CHECK(hipMemcpy(depth, h->d_depth, (size_t)N * 4, hipMemcpyDeviceToHost));
+        OSLAM_HIP_CHECK(hipMemcpy(uRight, h->d_uRight.as<float>(), (size_t)N * 4, hipMemcpyDeviceToHost));
+        OSLAM_HIP_CHECK(hipMemcpy(depth, h->d_depth.as<float>(), (size_t)N * 4, hipMemcpyDeviceToHost));
     }
     return OSLAM_OK;
 }

@@ -28,11 +28,14 @@ struct oslam_voc {
     std::vector<uint2> p_ids;         // (file node id, word id or 0xffffffff)
     std::vector<double> p_weight;
     // device images, one per device that asked
-    struct Image { uint8_t* desc = nullptr; uint2* link = nullptr; uint2* ids = nullptr; double* weight = nullptr; };
-    struct Scratch { uint8_t* p = nullptr; size_t cap = 0; };   // staging of the host-pointer entry point (oslam_voc_transform), one per device
+    struct Image { uint8_t* desc = nullptr; uint2* link = nullptr; uint2* ids = nullptr; double* weight = nullptr; };   // what voc_image hands out, by value
+    struct ImageMem {   // the arrays behind an Image: they live as long as the vocabulary
+        oslam::DeviceBuffer desc, link, ids, weight;
+        Image view() const { return {desc.bytes(), link.as<uint2>(), ids.as<uint2>(), weight.as<double>()}; }
+    };
     mutable std::mutex mu, mu_scratch;
-    mutable std::map<int, Scratch> scratch;
-    mutable std::map<int, Image> images;
+    mutable std::map<int, oslam::DeviceBuffer> scratch;   // staging of the host-pointer entry point (oslam_voc_transform), one per device
+    mutable std::map<int, ImageMem> images;
 };
 
 namespace {
@@ -201,32 +204,25 @@ inline int host_dist(const uint8_t* a, const uint64_t* q) {
 int voc_image(const oslam_voc* v, int device, oslam_voc::Image* out) {
     std::lock_guard<std::mutex> lock(v->mu);
     auto it = v->images.find(device);
-    if (it != v->images.end()) { *out = it->second; return OSLAM_OK; }
+    if (it != v->images.end()) { *out = it->second.view(); return OSLAM_OK; }
     int prev = 0;
     OSLAM_HIP_CHECK(hipGetDevice(&prev));
     OSLAM_HIP_CHECK(hipSetDevice(device));
     const size_t m = (size_t)v->n + 1;
-    oslam_voc::Image im;
-    hipError_t e = hipMalloc((void**)&im.desc, m * 32);
-    if (e == hipSuccess) e = hipMalloc((void**)&im.link, m * sizeof(uint2));
-    if (e == hipSuccess) e = hipMalloc((void**)&im.ids, m * sizeof(uint2));
-    if (e == hipSuccess) e = hipMalloc((void**)&im.weight, m * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(im.desc, v->p_desc.data(), m * 32, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(im.link, v->p_link.data(), m * sizeof(uint2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(im.ids, v->p_ids.data(), m * sizeof(uint2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(im.weight, v->p_weight.data(), m * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (im.desc) (void)hipFree(im.desc);
-        if (im.link) (void)hipFree(im.link);
-        if (im.ids) (void)hipFree(im.ids);
-        if (im.weight) (void)hipFree(im.weight);
+    oslam_voc::ImageMem im;
+    int rc;
+    if ((rc = im.desc.alloc(m * 32)) || (rc = im.link.alloc(m * sizeof(uint2))) || (rc = im.ids.alloc(m * sizeof(uint2))) || (rc = im.weight.alloc(m * sizeof(double)))) {
         (void)hipSetDevice(prev);
-        set_error("vocabulary upload failed: %s", hipGetErrorString(e));
-        return OSLAM_E_HIP;
+        return rc;
     }
+    hipError_t e = hipMemcpy(im.desc.ptr(), v->p_desc.data(), m * 32, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(im.link.ptr(), v->p_link.data(), m * sizeof(uint2), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(im.ids.ptr(), v->p_ids.data(), m * sizeof(uint2), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(im.weight.ptr(), v->p_weight.data(), m * sizeof(double), hipMemcpyHostToDevice);
     (void)hipSetDevice(prev);
-    v->images[device] = im;
-    *out = im;
+    if (e != hipSuccess) { set_error("vocabulary upload failed: %s", hipGetErrorString(e)); return OSLAM_E_HIP; }
+    *out = im.view();
+    v->images[device] = std::move(im);
     return OSLAM_OK;
 }
 
@@ -274,11 +270,6 @@ extern "C" {
 
 void oslam_voc_destroy(oslam_voc_t* v) {
     if (!v) return;
-    for (auto& kv : v->images) {
-        (void)hipFree(kv.second.desc); (void)hipFree(kv.second.link); (void)hipFree(kv.second.ids); (void)hipFree(kv.second.weight);
-    }
-    for (auto& kv : v->scratch)
-        if (kv.second.p) (void)hipFree(kv.second.p);
     delete v;
 }
 
@@ -456,25 +447,21 @@ int oslam_voc_transform(const oslam_voc_t* v, const uint8_t* desc, int n, int le
     int device = 0;
     OSLAM_HIP_CHECK(hipGetDevice(&device));
     std::lock_guard<std::mutex> lock(v->mu_scratch);   // (host-pointer calls on one vocabulary run one at a time)
-    oslam_voc::Scratch& sc = v->scratch[device];
+    oslam::DeviceBuffer& scratch = v->scratch[device];
     const size_t N = (size_t)n, oDesc = 256, oWord = oDesc + oslam::align_up(32 * N, 256), oNode = oWord + oslam::align_up(4 * N, 256), oWt = oNode + oslam::align_up(4 * N, 256),
                  total = oWt + 8 * N;
-    if (total > sc.cap) {
-        if (sc.p) (void)hipFree(sc.p);
-        sc.p = nullptr; sc.cap = 0;
-        OSLAM_HIP_CHECK(hipMalloc((void**)&sc.p, total + total / 2));
-        sc.cap = total + total / 2;
-    }
-    struct { const uint8_t* ptr; int32_t count; } head = {sc.p + oDesc, n};   // the one-array batch: pointer table at offset 0, count at offset 8
-    OSLAM_HIP_CHECK(hipMemcpy(sc.p, &head, sizeof(head), hipMemcpyHostToDevice));
-    OSLAM_HIP_CHECK(hipMemcpy(sc.p + oDesc, desc, 32 * N, hipMemcpyHostToDevice));
-    const int rc = oslam_voc_transform_device(v, (const uint8_t* const*)sc.p, (const int32_t*)(sc.p + 8), 1, n, levelsup, (uint32_t*)(sc.p + oWord), (uint32_t*)(sc.p + oNode),
-                                              (double*)(sc.p + oWt), nullptr);
+    OSLAM_CHECK(scratch.grow(total, 0));
+    uint8_t* const sc = scratch.bytes();
+    struct { const uint8_t* ptr; int32_t count; } head = {sc + oDesc, n};   // the one-array batch: pointer table at offset 0, count at offset 8
+    OSLAM_HIP_CHECK(hipMemcpy(sc, &head, sizeof(head), hipMemcpyHostToDevice));
+    OSLAM_HIP_CHECK(hipMemcpy(sc + oDesc, desc, 32 * N, hipMemcpyHostToDevice));
+    const int rc = oslam_voc_transform_device(v, (const uint8_t* const*)sc, (const int32_t*)(sc + 8), 1, n, levelsup, (uint32_t*)(sc + oWord), (uint32_t*)(sc + oNode),
+                                              (double*)(sc + oWt), nullptr);
     if (rc) return rc;
     OSLAM_HIP_CHECK(hipStreamSynchronize(nullptr));
-    if (word) OSLAM_HIP_CHECK(hipMemcpy(word, sc.p + oWord, 4 * N, hipMemcpyDeviceToHost));
-    if (node) OSLAM_HIP_CHECK(hipMemcpy(node, sc.p + oNode, 4 * N, hipMemcpyDeviceToHost));
-    if (weight) OSLAM_HIP_CHECK(hipMemcpy(weight, sc.p + oWt, 8 * N, hipMemcpyDeviceToHost));
+    if (word) OSLAM_HIP_CHECK(hipMemcpy(word, sc + oWord, 4 * N, hipMemcpyDeviceToHost));
+    if (node) OSLAM_HIP_CHECK(hipMemcpy(node, sc + oNode, 4 * N, hipMemcpyDeviceToHost));
+    if (weight) OSLAM_HIP_CHECK(hipMemcpy(weight, sc + oWt, 8 * N, hipMemcpyDeviceToHost));
     return OSLAM_OK;
 }
 

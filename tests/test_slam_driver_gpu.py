@@ -321,6 +321,49 @@ def test_lost_and_reset_on_one_slot_matches_oracle_driver(oracle):
     assert len(hip.trajectory(0)[0]) == n - 9           # the trajectory of the new map only
 
 
+def test_sequences_that_initialise_late_match_the_oracle_driver(oracle):
+    """Sequences 1 and 2 see textureless frames until sequence 0 has run its first local BA — SearchInNeighbors has then allocated the scratch block of
+    fuse_into_current — and initialise together on the step after: that register_keyframes call is the first to carry more than one keyframe, so its
+    pinned key block grows while the scratch block exists.  (The growth once freed the scratch block and left its pointer in place.)  The schedule is
+    decided by the HIP run and replayed on the oracle table: same states, statistics and poses."""
+    from object_slam_amd import scene
+    S, cap, tail = 3, 20, 8
+    # the streams of make_scene_streams(3, cap + 1 + tail, speed=2.0); of the late sequences only the frames that can be reached are rendered
+    seqs = [scene.make_rgbd_sequence(s, cap + 1 + tail, speed=2.0, count=None if s == 0 else tail + 1) for s in range(S)]
+    blank = np.full((H, W), 90, np.uint8)
+    flat = np.full((H, W), 2.0, np.float32)
+
+    def run(system, switch=None):
+        """switch = None: the late sequences start when sequence 0 has a local BA behind it (at step `cap` at the latest); otherwise at step `switch`"""
+        poses, states, t, start = [], [], 0, switch
+        while start is None or t <= start + tail:
+            if start is None and (system.stats(0)["local_bas"] > 0 or t == cap):
+                start = t
+            late = start is not None and t >= start
+            gray = [seqs[0]["gray"][t]] + [seqs[s]["gray"][t - start] if late else blank for s in (1, 2)]
+            depth = [seqs[0]["depth"][t]] + [seqs[s]["depth"][t - start] if late else flat for s in (1, 2)]
+            T, st = system.TrackRGBD(gray, depth, [t / 30.0] * S)
+            poses.append(T.copy()); states.append(st.copy())
+            t += 1
+        return np.array(poses), np.array(states), start
+
+    hip = slam.System(slam.make_config(W, H, S))
+    ph, sh, start = run(hip)
+    assert 0 < start < cap, start          # the first local BA of sequence 0 came within the cap: the case was reached
+    cfg_o = slam.make_config(W, H, S)
+    ora = slam.System(cfg_o, oracle_ops(cfg_o))
+    po, so, _ = run(ora, start)
+    assert len(sh) == start + 1 + tail
+    assert np.array_equal(sh, so), (sh.T, so.T)
+    assert (sh[:start, 1:] == slam.NOT_INITIALIZED).all() and (sh[start + 1:, 1:] == slam.OK).all(), sh.T
+    assert (sh[:, 0] == slam.OK).all()
+    for s in range(S):
+        a, b = hip.stats(s), ora.stats(s)
+        assert a["map_violations"] == 0
+        assert a == b, (s, a, b)
+    assert np.abs(ph - po).max() < 4e-4, np.abs(ph - po).max()
+
+
 def test_resident_map_point_records_equal_the_host_map():
     """The HIP table keeps a 64-byte record per map point (position, normal, distances, descriptor) that every MapPoint update writes.  After a run with
     keyframe insertions, triangulation, fusions, local BA and cullings the record of EVERY point that is alive must equal the driver's host copy bit for bit."""
