@@ -137,7 +137,7 @@ typedef struct oslam_proj_query {
 /* Frame side of a search, batch of frames in HBM (device pointers), fixed per-frame stride. */
 typedef struct oslam_match_frames {
     const oslam_keypoint_t* keysUn; /* mvKeysUn [batch][kp_stride] */
-    int kp_stride;
+    int kp_stride;                  /* 1 <= kp_stride <= max_keypoints of the handle (OSLAM_E_CAPACITY above it, nothing is launched) */
     const float* uRight;            /* mvuRight [batch][kp_stride], NULL = monocular (-1) */
     const uint8_t* desc;            /* mDescriptors [batch][kp_stride][32] */
     const uint8_t* blocked;         /* [batch][kp_stride]: mvpMapPoints[i] && Observations()>0 before the call; NULL = none */
@@ -180,8 +180,12 @@ int oslam_match_project_last_batch_device(oslam_matcher_t* h, const oslam_match_
                                           const oslam_match_frames_t* cur, const float* scaleFactors, int nlevels,
                                           float th, int bMono, int batch, void* stream);
 /* Device results of the last search: q_match/q_dist [batch][q_stride] (keypoint index or -1, Hamming
- * distance), kp_match [batch][max_keypoints] (query index now held in mvpMapPoints[k]; -1 untouched;
- * -2 set to NULL by the rotation check), nmatches [batch] (return value of the reference call). */
+ * distance), kp_match [batch][kp_stride] (the strides of that search's arguments, frames->kp_stride <=
+ * max_keypoints; query index now held in mvpMapPoints[k]; -1 untouched; -2 set to NULL by the rotation
+ * check), nmatches [batch] (return value of the reference call).  Entries beyond a frame's counts are
+ * unspecified.  queries / n_queries: the internal query buffer [batch][last->kp_stride] and counts [batch]
+ * that oslam_match_project_last_batch_device filled (pass n_queries as d_n_queries of the search that
+ * follows it with d_queries NULL). */
 int oslam_match_results_device(const oslam_matcher_t* h, const int32_t** q_match, const int32_t** q_dist,
                                const int32_t** kp_match, const int32_t** nmatches,
                                const oslam_proj_query_t** queries, const int32_t** n_queries);
@@ -292,6 +296,9 @@ int oslam_stereo_match_batch_device(oslam_stereo_t* h, oslam_orb_t* orbL, oslam_
                                     const oslam_keypoint_t* d_kpL, const uint8_t* d_descL, const int32_t* d_nL,
                                     int nL_const, const oslam_keypoint_t* d_kpR, const uint8_t* d_descR,
                                     const int32_t* d_nR, int nR_const, int nlevels, float bf, float b, void* stream);
+/* Device results of the last batch: d_uRight / d_depth [batch][kp_stride] (the stride of that call; entries beyond a pair's left count are
+ * unspecified), d_n_matched [batch] = left keypoints that had a match BEFORE the median-SAD cut (the size of vDistIdx, src/Frame.cc:866; the cut then
+ * resets some of them to -1), or -1 when the kernel rejected the pair (a count above the handle's capacity). */
 int oslam_stereo_results_device(const oslam_stereo_t* h, const float** d_uRight, const float** d_depth,
                                 const int32_t** d_n_matched);
 
@@ -522,7 +529,8 @@ int oslam_mp_table_local_gather_device(int n, int maxM, const oslam_local_gather
 /* Positions of n map points named by (d_slots[i], d_ids[i]) into d_Xw[n][3] (the object map points of ObjectOptimizer::PoseOptimization2). */
 int oslam_mp_table_positions_device(int n, const int32_t* d_slots, const int32_t* d_ids, uint8_t* const* d_tab, float* d_Xw, void* stream);
 int oslam_mp_table_gather_device(int batch, int stride, const int32_t* d_n, const int32_t* d_ids, uint8_t* const* d_tab, float* d_Xw, uint8_t* d_desc, void* stream);
-/* device-pointer forms (asynchronous on `stream`); d_out_desc rows of points without observations are left untouched (zero-fill them first) */
+/* device-pointer forms (asynchronous on `stream`); d_out_desc rows of points without observations are left untouched (zero-fill them first), their
+ * d_best_idx is -1 and their d_out row is five zeros.  Nothing outside d_best_idx [P], d_out_desc [P][32] and d_out [P][5] is written. */
 int oslam_mp_distinctive_descriptors_device(int P, const int32_t* d_obs_start, const uint8_t* d_obs_desc, int32_t* d_best_idx, uint8_t* d_out_desc, void* stream);
 int oslam_mp_update_normal_depth_device(int P, const float* d_Pos, const int32_t* d_obs_start, const float* d_obs_Ow, const float* d_OwRef,
                                         const float* d_levelScaleFactor, float lastScaleFactor, float* d_out, void* stream);
@@ -544,7 +552,8 @@ int oslam_frame_is_in_frustum_device(int M, const float* d_Pw, const float* d_Pn
 
 /* batch of frames (Tracking::SearchLocalPoints for several sequences): per-point arrays [batch][stride], d_M[b] points of frame b are
  * tested against pose d_Tcw[b] (16 floats) with radius factor d_th[b]; d_out [batch][stride] feeds oslam_match_search_batch_device
- * (q_stride = stride); d_in_view [batch][stride] = mbTrackInView (may be NULL). */
+ * (q_stride = stride); d_in_view [batch][stride] = mbTrackInView (may be NULL).  Entries i >= d_M[b] of d_out and d_in_view are left untouched
+ * (pass d_M as d_n_queries of the search: it never reads them). */
 int oslam_frame_is_in_frustum_batch_device(int batch, int stride, const int32_t* d_M, const float* d_Pw, const float* d_Pn, const float* d_maxDist,
                                            const float* d_minDist, const uint8_t* d_obs_gt0, const uint8_t* d_mp_desc, const float* d_Tcw, const float* d_th,
                                            const float K5[5], const float bounds[4], float viewingCosLimit, float logScaleFactor, const float* scaleFactors,
@@ -579,7 +588,8 @@ int oslam_mp_triangulate(oslam_mappoint_t* h, const oslam_tri_kf_t* kf1, int nPa
                          const int32_t* idx1, const int32_t* idx2, const float* scaleFactors, const float* levelSigma2, int nLevels,
                          float ratioFactor /* 1.5f*mfScaleFactor */, uint8_t* ok /*[M]*/, float* x3D /*[M][3]*/, int32_t* nnew);
 
-/* Same numeric core for nPairs independent (current keyframe, neighbour) pairs, e.g. one pair per sequence of a batch: pair p = (kf1[p], kf2[p]). */
+/* Same numeric core for nPairs independent (current keyframe, neighbour) pairs, e.g. one pair per sequence of a batch: pair p = (kf1[p], kf2[p]).  Host
+ * pointers, synchronous (the handle's own stream).  ok [M] and x3D [M][3] with M = pair_start[nPairs] are written, x3D = 0 where ok = 0; a pair may be empty. */
 int oslam_mp_triangulate_pairs(oslam_mappoint_t* h, int nPairs, const oslam_tri_kf_t* kf1, const oslam_tri_kf_t* kf2, const int32_t* pair_start,
                                const int32_t* idx1, const int32_t* idx2, const float* scaleFactors, const float* levelSigma2, int nLevels,
                                float ratioFactor, uint8_t* ok /*[M]*/, float* x3D /*[M][3]*/);
@@ -589,7 +599,10 @@ int oslam_mp_triangulate_pairs(oslam_mappoint_t* h, int nPairs, const oslam_tri_
  * cvUndistortPoints: fp64, 5 fixed-point iterations), Frame::ComputeImageBounds (:677-704) and Frame::ComputeStereoFromRGBD
  * (:883-904).  K4 = fx, fy, cx, cy (mK, CV_32F); dist = mDistCoef (k1, k2, p1, p2[, k3]; ndist 0 or dist[0] == 0 -> mvKeysUn = mvKeys,
  * bounds = the image rectangle).  The *_batch_device forms work on the extractor's device arrays ([batch][stride] keypoints,
- * counts per frame or n_const) and are asynchronous on `stream`; `image_stride` of the depth batch is in floats. */
+ * counts per frame or n_const) and are asynchronous on `stream`; `image_stride` of the depth batch is in floats.
+ * oslam_frame_undistort_batch_device leaves the slots i >= count of a row untouched; the oslam_frame_stereo_from_rgbd_batch* forms write the whole
+ * [batch][stride] block of d_uRight / d_mvDepth, -1 in the slots i >= count.  *d_status is OR-ed with 1 when a keypoint lies outside the depth image
+ * (the caller zeroes it first; 0 afterwards = every keypoint was inside). */
 typedef struct oslam_frame oslam_frame_t;
 int oslam_frame_create(oslam_frame_t** out, int device);
 void oslam_frame_destroy(oslam_frame_t* h);
@@ -605,11 +618,12 @@ int oslam_frame_image_bounds(oslam_frame_t* h, int cols, int rows, const float K
 int oslam_frame_stereo_from_rgbd(oslam_frame_t* h, int n, const oslam_keypoint_t* keys, const oslam_keypoint_t* keysUn, const float* depth, int rows,
                                  int cols, int pitch, float mbf, float* uRight, float* mvDepth);
 /* n images given by a table of device pointers (rows src_pitch bytes apart) gathered into one contiguous batch [n][rows][dst_pitch]: the extractor's input
- * layout, in one launch. */
+ * layout, in one launch.  Only the first row_bytes bytes of a destination row are written (the padding up to dst_pitch and between images is left as it was). */
 int oslam_frame_gather_images_device(const void* const* d_src_ptrs, int n, int src_pitch, int row_bytes, int rows, void* d_dst, size_t dst_image_stride, int dst_pitch,
                                      void* stream);
 /* Device-to-device helpers of the driver's resident keyframe store: n segments {const void* src; void* dst; uint32 bytes; uint32 pad} copied in one launch;
- * d_out[i] = the 32-byte descriptor number d_rec[i][1] of the array d_desc_base[d_rec[i][0]]. */
+ * d_out[i] = the 32-byte descriptor number d_rec[i][1] of the array d_desc_base[d_rec[i][0]] (d_rec is int32 [n][2]; d_out and the descriptor arrays 4-byte
+ * aligned).  Segments may have any byte count (0 included) and any alignment; exactly `bytes` bytes are written per segment. */
 int oslam_copy_segments_device(const void* d_segs, int n, void* stream);
 int oslam_gather_descriptors_device(const uint8_t* const* d_desc_base, const int32_t* d_rec, int n, uint8_t* d_out, void* stream);
 int oslam_frame_stereo_from_rgbd_batch_device(const oslam_keypoint_t* d_keys, const oslam_keypoint_t* d_keysUn, const int32_t* d_counts, int n_const,

@@ -531,7 +531,9 @@ static int check_frames(const oslam_matcher* h, const oslam_match_frames_t* f, i
     if (!h || !f) { set_error("NULL argument"); return OSLAM_E_INVALID; }
     if (batch < 1 || batch > h->max_batch) { set_error("batch %d outside [1,%d]", batch, h->max_batch); return OSLAM_E_INVALID; }
     if (!f->keysUn || !f->desc) { set_error("keysUn/desc NULL"); return OSLAM_E_INVALID; }
-    if (f->kp_stride < 1 || f->kp_stride > h->max_kps * 64) { set_error("bad kp_stride"); return OSLAM_E_INVALID; }
+    if (f->kp_stride < 1) { set_error("bad kp_stride %d", f->kp_stride); return OSLAM_E_INVALID; }
+    // the per-frame stride of kp_match equals the input stride, and kp_match was sized for max_kps per frame
+    if (f->kp_stride > h->max_kps) { set_error("kp_stride %d > max_keypoints %d", f->kp_stride, h->max_kps); return OSLAM_E_CAPACITY; }
     if (!f->n_kps && (f->n_kps_const < 0 || f->n_kps_const > h->max_kps || f->n_kps_const > f->kp_stride)) { set_error("n_kps %d exceeds capacity %d", f->n_kps_const, h->max_kps); return OSLAM_E_CAPACITY; }
     if (!(f->maxX > f->minX) || !(f->maxY > f->minY)) { set_error("empty image bounds"); return OSLAM_E_INVALID; }
     return OSLAM_OK;
@@ -575,8 +577,7 @@ static int search_impl(oslam_matcher_t* h, const oslam_match_frames_t* f, const 
     for (int i = 0; i < OSLAM_MAX_LEVELS; i++) c.invSigma2[i] = (invLevelSigma2 && i < nlevels) ? invLevelSigma2[i] : 0.f;
     c.q_match = h->d_q_match.as<int>(); c.q_dist = h->d_q_dist.as<int>(); c.kp_match = h->d_kp_match.as<int>(); c.nmatches = h->d_nm.as<int>(); c.iters = h->d_iters.as<int>(); c.pairs = h->d_pairs.as<int>(); c.dbg = h->d_dbg.as<long long>();
     c.cache = h->d_cache.as<uint32_t>(); c.ccount = h->d_ccount.as<int>();
-    // per-frame output strides equal the input strides; outputs were sized for max_q / max_kps
-    if ((size_t)f->kp_stride > (size_t)h->max_kps) { set_error("kp_stride %d > max_keypoints %d", f->kp_stride, h->max_kps); return OSLAM_E_CAPACITY; }
+    // per-frame output strides equal the input strides; outputs were sized for max_q / max_kps (check_frames, q_stride above)
     hipLaunchKernelGGL(k_search_window, dim3(batch), dim3(kMatchThreads), h->lds, (hipStream_t)stream, c, h->max_kps);
     OSLAM_HIP_CHECK(hipGetLastError());
     return OSLAM_OK;

@@ -171,6 +171,18 @@ class BowSide2(C.Structure):
                 ("nNodes", C.c_int32), ("nodes", C.c_void_p), ("start", C.c_void_p), ("items", C.c_void_p)]
 
 
+class BowJob(C.Structure):
+    """oslam_bow_job_t"""
+    _fields_ = [("s1", BowSide1), ("s2", BowSide2), ("triangulation", C.c_int32), ("nnratio", C.c_float), ("checkOri", C.c_int32),
+                ("F12", C.c_float * 9), ("ex", C.c_float), ("ey", C.c_float), ("match", C.c_void_p), ("nmatches", C.c_int32)]
+
+
+class BowResident(C.Structure):
+    """oslam_bow_resident_t"""
+    _fields_ = [("d_keys1", C.c_void_p), ("d_desc1", C.c_void_p), ("d_uRight1", C.c_void_p),
+                ("d_keys2", C.c_void_p), ("d_desc2", C.c_void_p), ("d_uRight2", C.c_void_p)]
+
+
 def feature_vector(node_of_kp):
     """node id per keypoint -> (flat (idx, node) list in std::map order, CSR (nodes, start, items))."""
     node_of_kp = np.asarray(node_of_kp, np.uint32)

@@ -235,7 +235,8 @@ namespace oracle {
 void ComputeStereoMatches(int N, const KeyPoint* keysL, const uint8_t* descL, int Nr, const KeyPoint* keysR,
                           const uint8_t* descR, const std::vector<Image>& pyrL, const std::vector<Image>& pyrR,
                           const float* mvScaleFactors, const float* mvInvScaleFactors, float mbf, float mb, float* mvuRight,
-                          float* mvDepth) {
+                          float* mvDepth, int* nBeforeCut) {
+    if (nBeforeCut) *nBeforeCut = 0;
     for (int i = 0; i < N; i++) { mvuRight[i] = -1.0f; mvDepth[i] = -1.0f; }
     const int thOrbDist = (TH_HIGH + TH_LOW) / 2;
     const int nRows = pyrL[0].h;
@@ -331,6 +332,7 @@ void ComputeStereoMatches(int N, const KeyPoint* keysL, const uint8_t* descL, in
             }
         }
     }
+    if (nBeforeCut) *nBeforeCut = (int)vDistIdx.size();
     if (vDistIdx.empty()) return;
     std::sort(vDistIdx.begin(), vDistIdx.end());
     const float median = vDistIdx[vDistIdx.size() / 2].first;

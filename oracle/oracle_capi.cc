@@ -192,6 +192,14 @@ void oo_stereo_matches(void* orbL, void* orbR, int N, const KeyPoint* keysL, con
     ComputeStereoMatches(N, keysL, descL, Nr, keysR, descR, L->mvImagePyramid, R->mvImagePyramid, L->mvScaleFactor.data(),
                          L->mvInvScaleFactor.data(), bf, b, uRight, depth);
 }
+// the same, and the number of matches before the median-SAD cut
+void oo_stereo_matches_n(void* orbL, void* orbR, int N, const KeyPoint* keysL, const uint8_t* descL, int Nr,
+                         const KeyPoint* keysR, const uint8_t* descR, float bf, float b, float* uRight, float* depth, int* nBeforeCut) {
+    OrbExtractor* L = (OrbExtractor*)orbL;
+    OrbExtractor* R = (OrbExtractor*)orbR;
+    ComputeStereoMatches(N, keysL, descL, Nr, keysR, descR, L->mvImagePyramid, R->mvImagePyramid, L->mvScaleFactor.data(),
+                         L->mvInvScaleFactor.data(), bf, b, uRight, depth, nBeforeCut);
+}
 }
 
 extern "C" {

@@ -3,25 +3,12 @@
 import numpy as np
 import pytest
 
+from batch_common import TUM1_D, TUM1_K, frame_keys as _keys
+
 pytestmark = pytest.mark.gpu
 
-TUM1_K = (517.306408, 516.469215, 318.643040, 255.313989)                      # reference Examples/RGB-D/TUM1.yaml:8-11
-TUM1_D = (0.262383, -0.953104, -0.005358, 0.002628, 1.163314)                  # k1, k2, p1, p2, k3 (:13-17)
 TUM2_K = (520.908620, 521.007327, 325.141442, 249.701764)
 TUM2_D = (0.231222, -0.784899, -0.003257, -0.000105, 0.917205)
-
-
-def _keys(rng, n, w, h):
-    from object_slam_amd import KP_DTYPE
-    k = np.zeros(n, KP_DTYPE)
-    k["x"] = rng.uniform(0, w - 1, n).astype(np.float32)
-    k["y"] = rng.uniform(0, h - 1, n).astype(np.float32)
-    k["octave"] = rng.integers(0, 8, n)
-    k["angle"] = rng.uniform(0, 360, n)
-    k["size"] = 31
-    k["response"] = rng.integers(7, 200, n)
-    k["class_id"] = -1
-    return k
 
 
 @pytest.mark.parametrize("K,D", [(TUM1_K, TUM1_D), (TUM2_K, TUM2_D), (TUM2_K, TUM2_D[:4]), (TUM2_K, (0.0, 0.1, 0, 0)), (TUM2_K, ())])

@@ -4,19 +4,9 @@ bit-exact too (same operation order, -ffp-contract=off)."""
 import numpy as np
 import pytest
 
+from batch_common import desc_lists as _lists
+
 pytestmark = pytest.mark.gpu
-
-
-def _lists(rng, P, nmax):
-    base = rng.integers(0, 256, (P, 32), dtype=np.uint8)
-    out = []
-    for p in range(P):
-        n = int(rng.integers(0, nmax + 1)) if p % 7 else (0 if p % 14 == 0 else nmax)
-        d = np.repeat(base[p][None], n, 0)
-        flips = rng.random((n, 256)) < 0.08          # noisy views of one descriptor: many ties in the medians
-        d = np.bitwise_xor(d, np.packbits(flips, axis=1))
-        out.append(d)
-    return out
 
 
 @pytest.mark.parametrize("nmax", [1, 2, 9, 40, 128, 200])

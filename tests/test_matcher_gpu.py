@@ -3,51 +3,10 @@ sequential claim order, rotation histogram) vs the CPU oracle.  Bit-exact indice
 import numpy as np
 import pytest
 
-from object_slam_amd import KP_DTYPE, QUERY_DTYPE, ORBextractor, ORBmatcher, synth
+from object_slam_amd import KP_DTYPE, ORBextractor, ORBmatcher, synth
+from batch_common import SCALE, bow_pair as _bow_pair, rand_frame as _rand_frame, rand_queries as _rand_queries
 
 pytestmark = pytest.mark.gpu
-
-SCALE = np.array([1.2 ** i for i in range(8)], np.float32)
-
-
-def _rand_frame(rng, N, w=640, h=480, clustered=False):
-    k = np.zeros(N, KP_DTYPE)
-    if clustered:   # few distinct positions: many queries compete for the same keypoints
-        cx = rng.uniform(50, w - 50, 12)
-        cy = rng.uniform(50, h - 50, 12)
-        sel = rng.integers(0, 12, N)
-        k["x"] = (cx[sel] + rng.normal(0, 4, N)).astype(np.float32)
-        k["y"] = (cy[sel] + rng.normal(0, 4, N)).astype(np.float32)
-    else:
-        k["x"] = rng.uniform(-5, w + 5, N).astype(np.float32)   # a few outside the grid on purpose
-        k["y"] = rng.uniform(-5, h + 5, N).astype(np.float32)
-    k["octave"] = rng.integers(0, 8, N)
-    k["angle"] = rng.uniform(0, 360, N).astype(np.float32)
-    desc = rng.integers(0, 256, (N, 32)).astype(np.uint8)
-    uR = np.where(rng.random(N) < 0.7, k["x"] - rng.uniform(1, 40, N), -1).astype(np.float32)
-    return k, uR, desc
-
-
-def _rand_queries(rng, k, uR, desc, M, noise_bits, p_block=0.8, few_desc=False):
-    q = np.zeros(M, QUERY_DTYPE)
-    src = rng.integers(0, len(k), M)
-    q["u"] = k["x"][src] + rng.normal(0, 3, M)
-    q["v"] = k["y"][src] + rng.normal(0, 3, M)
-    q["ur"] = q["u"] - (k["x"][src] - uR[src]) + rng.normal(0, 2, M)
-    lvl = np.clip(k["octave"][src] + rng.integers(-1, 2, M), 0, 7)
-    q["radius"] = (rng.choice([2.5, 4.0], M) * rng.choice([1, 3, 7], M) * SCALE[lvl]).astype(np.float32)
-    q["minLevel"] = lvl - 1
-    q["maxLevel"] = lvl
-    q["flags"] = (rng.random(M) < 0.95).astype(np.int32) | ((rng.random(M) < p_block).astype(np.int32) << 1)
-    q["angle"] = (k["angle"][src] + rng.normal(0, 20, M)) % 360
-    d = desc[src].copy()
-    if few_desc:   # force Hamming ties: only a handful of distinct descriptors
-        d = desc[src % 5].copy()
-    flip = rng.random((M, 256)) < noise_bits
-    d ^= np.packbits(flip, axis=1, bitorder="little")
-    q["desc"] = d
-    return q
-
 
 def _check(oracle, m, k, uR, desc, blocked, q, use_ratio, check_ori):
     bounds = (0.0, 0.0, 640.0, 480.0)
@@ -152,24 +111,6 @@ def test_fuse_search(oracle, seed):
     np.testing.assert_array_equal(qd, oqd)
     assert nf == onf and (nf > 10 or N < 300)
     m.close()
-
-
-def _bow_pair(rng, N1, N2, n_nodes):
-    k1, uR1, d1 = _rand_frame(rng, N1)
-    src = rng.integers(0, N1, N2)
-    k2 = np.zeros(N2, KP_DTYPE)
-    k2["x"] = k1["x"][src] - rng.uniform(2, 30, N2)
-    k2["y"] = k1["y"][src] + rng.normal(0, 1.0, N2)
-    k2["octave"] = np.clip(k1["octave"][src] + rng.integers(-1, 2, N2), 0, 7)
-    k2["angle"] = (k1["angle"][src] + rng.normal(0, 8, N2)) % 360
-    d2 = d1[src].copy()
-    d2 ^= np.packbits(rng.random((N2, 256)) < 0.06, axis=1, bitorder="little")
-    node1 = rng.integers(0, n_nodes, N1).astype(np.uint32)
-    node2 = node1[src].copy()
-    wrong = rng.random(N2) < 0.15
-    node2[wrong] = rng.integers(0, n_nodes, wrong.sum())
-    uR2 = np.where(rng.random(N2) < 0.6, k2["x"] - rng.uniform(1, 30, N2), -1).astype(np.float32)
-    return k1, uR1, d1, node1, k2, uR2, d2, node2
 
 
 @pytest.mark.parametrize("seed", range(4))

@@ -4,47 +4,9 @@ Jacobi rotations and the stereo-parallax threshold)."""
 import numpy as np
 import pytest
 
+from batch_common import LS2, SF, tri_make_kf as _make_kf, tri_pose as _pose
+
 pytestmark = pytest.mark.gpu
-
-SF = (np.float32(1.2) ** np.arange(8)).astype(np.float32)
-LS2 = (SF * SF).astype(np.float32)
-
-
-def _pose(rng, t_scale):
-    a = rng.normal(0, 0.08, 3)
-    th = np.linalg.norm(a)
-    k = a / th
-    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
-    R = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
-    Tcw = np.eye(4, dtype=np.float32)
-    Tcw[:3, :3] = R
-    Tcw[:3, 3] = rng.normal(0, t_scale, 3)
-    Twc = np.eye(4, dtype=np.float32)
-    Twc[:3, :3] = Tcw[:3, :3].T
-    Twc[:3, 3] = -(Tcw[:3, :3].T @ Tcw[:3, 3])
-    return Tcw, Twc
-
-
-def _make_kf(rng, X, Tcw, cam, stereo_frac, noise):
-    from object_slam_amd import KP_DTYPE
-    fx, fy, cx, cy, bf = cam
-    Pc = X @ Tcw[:3, :3].T.astype(np.float64) + Tcw[:3, 3]
-    z = Pc[:, 2]
-    N = len(X)
-    k = np.zeros(N, KP_DTYPE)
-    octv = rng.integers(0, 8, N)
-    sig = np.sqrt(LS2[octv])
-    k["x"] = fx * Pc[:, 0] / z + cx + rng.normal(0, noise, N) * sig
-    k["y"] = fy * Pc[:, 1] / z + cy + rng.normal(0, noise, N) * sig
-    k["octave"] = octv
-    k["size"] = 31 * SF[octv]
-    st = (rng.random(N) < stereo_frac) & (z > 0.1)
-    depth = np.where(st, z * (1 + rng.normal(0, 0.01, N)), -1).astype(np.float32)
-    ur = np.where(st, k["x"] - bf / np.maximum(depth, 1e-3), -1).astype(np.float32)
-    raw = k.copy()
-    raw["x"] += 0.3   # mvKeys differs from mvKeysUn (distortion); only UnprojectStereo reads it
-    return k, raw, ur, depth
-
 
 @pytest.mark.parametrize("seed,stereo_frac,baseline", [(0, 0.0, 0.5), (1, 0.6, 0.5), (2, 0.6, 0.02), (3, 1.0, 1.5)])
 def test_triangulate_matches(seed, stereo_frac, baseline):
