@@ -404,7 +404,7 @@ volatile int32_t* oslam_lba_stop_flag(oslam_lba_t* h);
  *    driver; a window whose reduced system and poses exceed the CU's LDS — roughly 30 free keyframes — runs in mode 1 beside the others);
  * 0: the round-1 one-workgroup-per-problem kernel (reduced system in global memory), kept as an A/B layout.  Same arithmetic in all three. */
 int oslam_lba_set_mode(oslam_lba_t* h, int wide);
-/* Schur complement of mode 1: 0 = gather of the (W_a, B_b) pairs from memory (one wavefront per 6x6 block), 1 = on chip by tiles of points staged in LDS (one
+/* Schur complement of mode 1: 0 = gather, per pair of a 6x6 block, of the two 32-byte edge records plus the landmark's 48-byte inverse (one wavefront per block), 1 = on chip by tiles of points staged in LDS (one
  * coalesced read of the per-edge blocks per trial), 2 = chosen per call from the mean window size.  Same results to rounding.  The pair lists of mode 0 (the
  * default) are built on the device once per call (k_w_pair_*); 3 = mode 0 with the lists built by the host (the round-2 path): bit-identical results. */
 int oslam_lba_set_schur(oslam_lba_t* h, int mode);

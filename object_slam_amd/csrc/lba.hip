@@ -20,7 +20,6 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <mutex>
 #include <array>
 #include <vector>
@@ -635,7 +634,6 @@ struct LbaCtrl {
     int stage, iter, qmax, need_lin, gate, done, ok2, cur, robust, ok, early;
     int its[2], trials[2];
     int nfree, n;
-    int ticket[2];   // blocks finished in k_w_lin / k_w_eval: the last one runs the LM control step
     double lambda, ni, currentChi, rho;
     double lambdaA, FA;   // LM control after a linearisation, pair-gather path: written by block 0 of k_w_edgeW, committed by the next k_w_ctrlB (see w_ctrlA_values)
 };
@@ -653,10 +651,10 @@ struct LbaWide {
     const int2* pairs;        // (edge in pose a, edge in pose b) of every point both poses see, grouped by Schur block, point order
     const int* pair_start;    // [nfree*(nfree+1)/2 + 1]
     uint16_t* pairM; int2* pairs_w; int* pair_start_w;   // pair lists built on the device (k_w_pair_*): then pairs / pair_start point at pairs_w / pair_start_w
-    double* W;                // [E][18]: Hpl_e * (Hll_p + lambda I)^-1, written by k_w_edgeW for the current trial
+    double* W;                // [P][6]: (Hll_p + lambda I)^-1 of every landmark (symmetric: 6 doubles), written by k_w_edgeW for the current trial; null on the tiles route
     float4* eoi;              // [E] (u, v, u_R, invSigma2) of every edge in one 16-byte record (k_w_init_arrays packs e_obs / e_info once per call), or null
     double* rec;              // [E][4] compact edge records of the current linearisation (x, y, 1/z of the point in the camera frame, weight x information with the
-                              // sign bit = monocular), or null: the per-edge blocks B_e are then materialised in pr.Hpl (see k_w_schur_rec)
+                              // sign bit = monocular: see k_w_schur_rec), or null on the tiles route: the per-edge blocks B_e are then materialised in pr.Hpl
     // Schur complement by tiles (k_w_schur_tiles / k_w_schur_sum, lba_win.inc): the structures of LbaWin on the point-major edge numbering
     const int* tile_p0; const int* tile_s0; const int* stg_edge; const int* thr_own; const int* blk_thr; const int* blk_slots;
     double* parts;            // [nwg][ngroup * kWinThreads][42] per-workgroup, per-slot block sums
@@ -664,6 +662,7 @@ struct LbaWide {
 };
 
 constexpr int kWPt = 128;   // threads per block of the per-point kernels
+constexpr int kUpdLanes = 2;   // lanes per landmark in k_w_update: 1 / 2 / 4 measured, one lane waits on its ~8 edges and four repeat the per-landmark part
 
 
 __device__ __forceinline__ double* w_X(const LbaProblem& pr, int which) { return which ? pr.Xb : pr.Xa; }
@@ -681,7 +680,6 @@ __global__ __launch_bounds__(256) void k_w_init(const LbaProblem* probs, const L
         }
         ct->stage = 0; ct->iter = 0; ct->qmax = 0; ct->need_lin = 1; ct->gate = 0; ct->done = 0; ct->ok2 = 1; ct->cur = 0; ct->robust = pr.robust0; ct->ok = 1;
         ct->its[0] = ct->its[1] = ct->trials[0] = ct->trials[1] = 0;
-        ct->ticket[0] = ct->ticket[1] = 0;
         ct->nfree = nb; ct->n = 6 * nb;
         ct->lambda = 0; ct->ni = 2; ct->currentChi = 0; ct->rho = 0; ct->lambdaA = 0; ct->FA = 0;
         ct->early = pr.stop ? (*pr.stop != 0) : 0;   // reference :655-657
@@ -705,7 +703,7 @@ __global__ __launch_bounds__(256) void k_w_init_arrays(const LbaProblem* probs, 
 }
 
 // Between the two optimisation stages (reference src/Optimizer.cc:668-689): edges with chi2 above the gate or behind the
-// camera leave the problem (level 1).  Runs once per LBA, inside the last block of the k_w_eval launch that ended stage 0.
+// camera leave the problem (level 1).  Runs once per LBA, in the k_w_ctrlB launch that ended stage 0.
 __device__ void w_gate_block(const LbaProblem& pr, const LbaWide& w) {
     const LbaCtrl* ct = w.ct;
     const double* X = w_X(pr, ct->cur);
@@ -730,9 +728,7 @@ constexpr int kLinKfLds = 128;          // keyframes of a window whose rotation 
 __device__ void w_ctrlA(const LbaProblem& pr, const LbaWide& w);
 __device__ void w_ctrlB(const LbaProblem& pr, const LbaWide& w, int win);
 
-#ifndef OSLAM_LIN_MIN_WAVES
-#define OSLAM_LIN_MIN_WAVES 4   // 128 VGPRs (96 B of scratch per lane) so that two 512-thread workgroups share a CU; 1 = the compiler's 166 VGPRs, one workgroup per CU
-#endif
+constexpr int kLinMinWaves = 4;   // 128 VGPRs (96 B of scratch per lane) so that two 512-thread workgroups share a CU; 1 = the compiler's 166 VGPRs, one workgroup per CU
 // Workgroups are dispatched to the 8 XCDs round robin in linear block order, and every XCD has its own 4 MB L2.  The per-window kernels below map
 // (window, item) so that ALL workgroups of a window run on ONE XCD (window w -> XCD w mod 8; the windows of an XCD one after the other): the window's per-edge
 // blocks (B_e, W_e: 288 B per edge, read once per pair they take part in) then come out of that XCD's L2 instead of being pulled into all eight.
@@ -749,7 +745,7 @@ __device__ __forceinline__ bool xcd_window_item(int nwin, int& win, int& item) {
 }
 
 template <bool REC>
-__global__ __launch_bounds__(kLinThreads, OSLAM_LIN_MIN_WAVES) void k_w_lin(const LbaProblem* probs, const LbaWide* ws, int nwin) {
+__global__ __launch_bounds__(kLinThreads, kLinMinWaves) void k_w_lin(const LbaProblem* probs, const LbaWide* ws, int nwin) {
     int win_, item_;
     if (!xcd_window_item(nwin, win_, item_)) return;
     const LbaProblem& pr = probs[win_];
@@ -968,19 +964,10 @@ __device__ void w_ctrlA(const LbaProblem& pr, const LbaWide& w) {
     ct->qmax = 0;
 }
 
-// W_e = B_e (Hll_p + lambda I)^-1 for every active edge of a free keyframe: one inversion per edge instead of one per
-// (block, edge) pair inside the Schur kernel
-// (Writing W_e inside k_w_lin for the iterations whose lambda is known beforehand — the four lanes of a point hold its complete Hll — was measured: k_w_lin
-// 107 -> 160 us, this kernel 73 -> 14 us per trial of 40 steady-state windows, bit-identical results: no gain, not kept.)
-// The 144-byte block of an edge is computed by one lane, but a lane-per-block store (nine 16-byte pieces at a stride of 144 bytes across the lanes) reached
-// the memory side as 2.5x the bytes (rocprofv3 WRITE_SIZE 185 MB per launch of 40 windows against 75 MB of blocks: profiles/r03_pmc_lba_traffic.json): the blocks
-// of the workgroup's 256 consecutive edges are contiguous, so they go through LDS and out as 16 bytes per lane, consecutive lanes consecutive addresses.
-// (Inactive edges — outliers, fixed keyframes — get zeros: nothing reads their W.)
-// VINV (round 4, default): the kernel only inverts — (Hll_p + lambda I)^-1 of every landmark as 6 doubles (the cofactor inverse of a symmetric matrix is
-// symmetric bit for bit) at w.W + 6 p — and k_w_schur forms W_e = B_e V^-1 for the operand it needs from the B block it fetched: the 144-byte W blocks (1.9 MB
-// per steady-state window and trial written here, re-read ~8.5 times by the pair gather) no longer exist, both operands of a pair come from ONE array, and
-// this launch shrinks from 145 to ~10 us per 128 windows.  Same products in the same order: the reduced system does not change by a bit.
-template <bool VINV>
+// (Hll_p + lambda I)^-1 of every landmark for the current trial, as 6 doubles (the cofactor inverse of a symmetric matrix is symmetric bit for bit) at
+// w.W + 6 p: one inversion per landmark and trial instead of one per pair inside the Schur kernel.  k_w_schur_rec forms (w_a Jx_a) V^-1 from it for every pair,
+// k_w_update takes the landmark's step from it.  The kernel also carries the LM control values of the first trial after a linearisation (below).
+// (Rounds 1-4 materialised W_e = B_e V^-1, then B_e alone, as 144-byte blocks per edge; measured against the compact records and removed: DESIGN.md §6.)
 __global__ __launch_bounds__(256) void k_w_edgeW(const LbaProblem* probs, const LbaWide* ws, int nwin) {
     int win_, item_;
     if (!xcd_window_item(nwin, win_, item_)) return;
@@ -989,8 +976,7 @@ __global__ __launch_bounds__(256) void k_w_edgeW(const LbaProblem* probs, const 
     const LbaCtrl* ct = w.ct;
     if (ct->done) return;
     const int e0 = item_ * 256;
-    if (e0 >= (VINV ? max(pr.P, 1) : pr.E)) return;   // (VINV: 256 landmarks per workgroup; workgroup 0 always runs — it publishes the control values)
-    __shared__ double sW[VINV ? 1 : 256 * 19];   // 19: one double of padding per block (18 would put the lanes of a wavefront on 16 of the 64 banks)
+    if (e0 >= max(pr.P, 1)) return;   // (256 landmarks per workgroup; workgroup 0 always runs — it publishes the control values)
     __shared__ double s_lambda;
     // LM control after a linearisation (w_ctrlA's values, see w_lambda_eff): lambda of the first trial of a stage = 1e-5 x the largest diagonal entry of the
     // linearised system (computeLambdaInit), from the landmark blocks' partial maxima and the free keyframes' Hpp — by wavefront 0 of every workgroup;
@@ -1014,57 +1000,22 @@ __global__ __launch_bounds__(256) void k_w_edgeW(const LbaProblem* probs, const 
         if (lane == 0) s_lambda = lam;
     }
     __syncthreads();
-    if (VINV) {
-        const int p = e0 + threadIdx.x;
-        if (p >= pr.P) return;
-        const double lambda = s_lambda;
-        double D[9], Di[9];
-        const double* H = pr.Hll + (long long)p * 9;
+    const int p = e0 + threadIdx.x;
+    if (p >= pr.P) return;
+    const double lambda = s_lambda;
+    double D[9], Di[9];
+    const double* H = pr.Hll + (long long)p * 9;
 #pragma unroll
-        for (int i = 0; i < 9; i++) D[i] = H[i];
-        D[0] += lambda; D[4] += lambda; D[8] += lambda;
-        inv3(D, Di);
-        double2* out = (double2*)(w.W + (long long)p * 6);
-        out[0] = make_double2(Di[0], Di[1]); out[1] = make_double2(Di[2], Di[4]); out[2] = make_double2(Di[5], Di[8]);
-        return;
-    }
-    const int e = e0 + threadIdx.x;
-    if (e < pr.E && pr.level[e] == 0 && w.blk[pr.e_kf[e]] >= 0) {
-        const double lambda = s_lambda;
-        const int p = pr.e_pt[e];
-        double D[9], Di[9];
-        const double* H = pr.Hll + (long long)p * 9;
-#pragma unroll
-        for (int i = 0; i < 9; i++) D[i] = H[i];
-        D[0] += lambda; D[4] += lambda; D[8] += lambda;
-        inv3(D, Di);
-        const double* Ba = pr.Hpl + (long long)e * 18;
-        double* We = sW + threadIdx.x * 19;
-#pragma unroll
-        for (int i = 0; i < 6; i++) {
-            const double b0 = Ba[i * 3], b1 = Ba[i * 3 + 1], b2v = Ba[i * 3 + 2];
-            We[i * 3] = b0 * Di[0] + b1 * Di[3] + b2v * Di[6];
-            We[i * 3 + 1] = b0 * Di[1] + b1 * Di[4] + b2v * Di[7];
-            We[i * 3 + 2] = b0 * Di[2] + b1 * Di[5] + b2v * Di[8];
-        }
-    } else {   // inactive edge (outlier, fixed keyframe): nothing reads its W, but it is written below — zeros, not whatever the LDS held
-        double* We = sW + threadIdx.x * 19;
-#pragma unroll
-        for (int i = 0; i < 18; i++) We[i] = 0.0;
-    }
-    __syncthreads();
-    const int nE = min(256, pr.E - e0);
-    double2* out = (double2*)(w.W + (long long)e0 * 18);   // (e0 * 144 bytes: 16-byte aligned)
-    for (int k = threadIdx.x; k < nE * 9; k += 256) {
-        const int blk = k / 9, part = k - blk * 9;
-        const double* src = sW + blk * 19 + part * 2;
-        out[k] = make_double2(src[0], src[1]);
-    }
+    for (int i = 0; i < 9; i++) D[i] = H[i];
+    D[0] += lambda; D[4] += lambda; D[8] += lambda;
+    inv3(D, Di);
+    double2* out = (double2*)(w.W + (long long)p * 6);
+    out[0] = make_double2(Di[0], Di[1]); out[1] = make_double2(Di[2], Di[4]); out[2] = make_double2(Di[5], Di[8]);
 }
 
 // ---- Schur pair lists built on the device (once per call; the host used to spend ~430 us per steady-state window on them and upload 8 bytes per pair) ----
 // Block t = (a, b), a <= b, of the reduced system lists the points both free keyframes see, ascending, as (edge in a, edge in b): exactly the order of the host
-// builder in lba_build (a point has one observation per keyframe), so the sums of k_w_schur do not change by a bit.
+// builder in lba_build (a point has one observation per keyframe), so the sums of the Schur kernel do not depend on who built the lists.
 //   k_w_pair_matrix : M[a][p] = 1 + position of the edge of point p in free keyframe a inside the point's edge range (0 = not seen); M is zeroed by the caller
 //   k_w_pair_blocks : one wavefront per block walks the points 64 at a time — FILL = false counts, FILL = true writes the pairs at pair_start[t] + rank
 //   k_w_pair_scan   : one wavefront per window, exclusive scan of the counts into pair_start[0 .. nblk]
@@ -1139,163 +1090,25 @@ __device__ __forceinline__ double dpp_quad_f64(double v) {
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
-// One wavefront per 6x6 block (a, b) of the reduced system walks the block's pair list, 64 pairs per round, one pair per lane.
-// Operand fetch (round 4): a pair's operands are two 144-byte blocks, W_a of edge pe.x and B_b of edge pe.y.  Fetched by the lane that owns the pair (nine
-// 16-byte loads per block at a 144-byte stride ACROSS the lanes) every load instruction touched 64 different cache lines: rocprofv3 --pmc showed the texture
-// addresser busy 70-77 % of the launch (TA_BUSY_avr 176 k of 256 k cycles, 46 cache accesses per load instruction) with the vector ALU at 22 %.  Now the
-// wavefront fetches the 128 blocks of a round COOPERATIVELY — 16-byte piece g of the round's 18 KB goes to lane g mod 64, so nine consecutive lanes read one
-// block and a load instruction touches ~21 lines — and hands them to their owners through LDS (half a round at a time: 9.2 KB per wavefront).
-template <bool VINV>
-__global__ __launch_bounds__(64) void k_w_schur(const LbaProblem* probs, const LbaWide* ws, int nwin) {
-    int win, t;
-    if (!xcd_window_item(nwin, win, t)) return;
-    const LbaProblem& pr = probs[win];
-    const LbaWide& w = ws[win];
-    const LbaCtrl* ct = w.ct;
-    if (ct->done) return;
-    const int nfree = ct->nfree, n = ct->n, ld = n + 1;
-    const int lane = threadIdx.x;
-    if (t >= nfree * (nfree + 1) / 2) return;
-    const double lambda = w_lambda_eff(ct);
-    int ba = 0, rem = t;
-    while (rem >= nfree - ba) { rem -= nfree - ba; ba++; }
-    const int bb = ba + rem;
-    const int a = w.free_pose[ba];
-    const bool diag = ba == bb;
-    double acc[36];
-#pragma unroll
-    for (int i = 0; i < 36; i++) acc[i] = 0;
-    double bsv[6] = {0, 0, 0, 0, 0, 0};
-    __shared__ __align__(16) double s_stage[64 * 18];   // 64 blocks of half a round; after the loop: the [42][17] reduction array
-    __shared__ int s_idx[128];                          // edge of block b of the round (b = 2 x pair lane + operand), -1 = none
-    const int q_end = w.pair_start[t + 1];
-    int2 pe_next = make_int2(0, 0);
-    if (w.pair_start[t] + lane < q_end) pe_next = w.pairs[w.pair_start[t] + lane];
-    const double2* Wg = (const double2*)w.W;
-    const double2* Bg = (const double2*)pr.Hpl;
-    for (int q = w.pair_start[t] + lane; q - lane < q_end; q += 64) {   // (wave-uniform trip count: every lane takes part in the cooperative fetch)
-        const bool mine = q < q_end;
-        const int2 pe = pe_next;
-        if (q + 64 < q_end) pe_next = w.pairs[q + 64];   // the next round's list entry travels while this round's operands do
-        uint8_t la = 1, lb = 1;
-        int pt = 0;
-        if (mine) { la = pr.level[pe.x]; lb = pr.level[pe.y]; if (VINV) pt = pr.e_pt[pe.x]; }
-        double2 vi0 = make_double2(0.0, 0.0), vi1 = vi0, vi2 = vi0;
-        if (VINV && mine) { const double2* vp = (const double2*)(w.W + (long long)pt * 6); vi0 = vp[0]; vi1 = vp[1]; vi2 = vp[2]; }   // V^-1 of the pair's landmark (k_w_edgeW<true>)
-        s_idx[2 * lane] = mine ? pe.x : -1;
-        s_idx[2 * lane + 1] = mine ? pe.y : -1;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        double BD[18], B2[18];
-#pragma unroll
-        for (int half = 0; half < 2; half++) {
-            double2 v[9];
-#pragma unroll
-            for (int i = 0; i < 9; i++) {
-                const int g = 64 * i + lane, b = g / 9, piece = g - 9 * b;   // piece `piece` of block b of this half
-                const int e = s_idx[64 * half + b];
-                const double2* src = (VINV || (b & 1)) ? Bg : Wg;
-                v[i] = e >= 0 ? src[(long long)e * 9 + piece] : make_double2(0.0, 0.0);
-            }
-            if (half == 1) {   // (the first half's blocks have been read by their owners)
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
-#pragma unroll
-            for (int i = 0; i < 9; i++) ((double2*)s_stage)[64 * i + lane] = v[i];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            if ((lane >> 5) == half) {
-                const double2* mb = (const double2*)s_stage + (lane & 31) * 18;   // blocks 2 (lane & 31) and + 1: W_a then B_b
-#pragma unroll
-                for (int i = 0; i < 9; i++) { const double2 x = mb[i]; BD[2 * i] = x.x; BD[2 * i + 1] = x.y; }
-#pragma unroll
-                for (int i = 0; i < 9; i++) { const double2 x = mb[9 + i]; B2[2 * i] = x.x; B2[2 * i + 1] = x.y; }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();   // (the next round's fetch overwrites the staging area and the index table)
-        if (la != 0 || lb != 0) continue;
-        if (VINV) {   // W_a = B_a V^-1: k_w_edgeW's products, in its order
-            const double d0 = vi0.x, d1 = vi0.y, d2 = vi1.x, d4 = vi1.y, d5 = vi2.x, d8 = vi2.y;   // Di[0], [1] = [3], [2] = [6], [4], [5] = [7], [8]
-#pragma unroll
-            for (int i = 0; i < 6; i++) {
-                const double b0 = BD[i * 3], b1 = BD[i * 3 + 1], b2v = BD[i * 3 + 2];
-                BD[i * 3] = b0 * d0 + b1 * d1 + b2v * d2;
-                BD[i * 3 + 1] = b0 * d1 + b1 * d4 + b2v * d5;
-                BD[i * 3 + 2] = b0 * d2 + b1 * d5 + b2v * d8;
-            }
-        }
-        if (diag) {
-            const double* bl = pr.bl + (long long)(VINV ? pt : pr.e_pt[pe.x]) * 3;
-            const double l0 = bl[0], l1 = bl[1], l2 = bl[2];
-#pragma unroll
-            for (int i = 0; i < 6; i++) bsv[i] += BD[i * 3] * l0 + BD[i * 3 + 1] * l1 + BD[i * 3 + 2] * l2;
-        }
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-#pragma unroll
-            for (int j = 0; j < 6; j++)
-                acc[i * 6 + j] += BD[i * 3] * B2[j * 3] + BD[i * 3 + 1] * B2[j * 3 + 1] + BD[i * 3 + 2] * B2[j * 3 + 2];
-    }
-    // Sum of the 64 lanes' partial blocks: first inside every quad of lanes by two DPP quad-permute steps (full-rate cross-lane moves, no LDS), then the 16
-    // quad sums of each of the 36 (+6) entries through a [42][17] LDS array (rows skewed by one double: conflict-free row reads), added in lane order by
-    // lane i < 42 (the array lives in the staging area: the fetch loop is over).
-    double* red = s_stage;
-    static_assert(42 * 17 <= 64 * 18, "reduction array fits the staging area");
-    auto quad_sum = [](double v) {
-        v += dpp_quad_f64<0xB1>(v);   // quad_perm [1,0,3,2]: lane ^ 1
-        v += dpp_quad_f64<0x4E>(v);   // quad_perm [2,3,0,1]: lane ^ 2
-        return v;
-    };
-#pragma unroll
-    for (int i = 0; i < 36; i++) { const double q4 = quad_sum(acc[i]); if ((lane & 3) == 0) red[i * 17 + (lane >> 2)] = q4; }
-    if (diag) {
-#pragma unroll
-        for (int i = 0; i < 6; i++) { const double q4 = quad_sum(bsv[i]); if ((lane & 3) == 0) red[(36 + i) * 17 + (lane >> 2)] = q4; }
-    }
-    __syncthreads();
-    double mine = 0;
-    if (lane < (diag ? 42 : 36)) {
-        const double* row = red + lane * 17;
-        double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-#pragma unroll
-        for (int k = 0; k < 16; k += 4) { s0 += row[k]; s1 += row[k + 1]; s2 += row[k + 2]; s3 += row[k + 3]; }
-        mine = (s0 + s1) + (s2 + s3);
-    }
-    if (lane < 36) {   // lanes 0..35 write one entry each
-        const int i = lane / 6, j = lane - i * 6;
-        double v = -mine;
-        if (diag) v += pr.Hpp[a * 36 + lane] + (i == j ? lambda : 0.0);
-        pr.Hs[(size_t)(6 * ba + i) * ld + 6 * bb + j] = v;
-    } else if (diag && lane < 42) {
-        const int i = lane - 36;
-        pr.Hs[(size_t)(6 * ba + i) * ld + n] = pr.bp[a * 6 + i] - mine;
-    }
-}
-
-// The Schur complement from COMPACT EDGE RECORDS (round 5, the default of the pair-gather path).  The 144-byte block of an edge, B_e = Jp^T (w info) Jx, is a
+// The Schur complement of the pair-gather path, from COMPACT EDGE RECORDS: one wavefront per 6x6 block (a, b) of the reduced system walks the block's pair
+// list, 64 pairs per round, one pair per lane.  The 144-byte block of an edge, B_e = Jp^T (w info) Jx, is a
 // function of four doubles — the point in the edge's camera frame as (x, y, 1/z) and the edge's weight — and of the keyframe's rotation, which is the same
 // for every pair of a 6x6 block (a, b).  So k_w_lin<true> stores 32 bytes per edge instead of 144, and the product of a pair is formed from the records:
 //     W_a B_b^T = Jp_a^T [ (w_a Jx_a) V^-1 (w_b Jx_b)^T ] Jp_b = Jp_a^T M Jp_b,       M 3x3,
 // (Jx = -d proj / d p_c * R: point_jac_rows; Jp: pose_jac_rows — the formulas k_w_lin used for B_e).  Per pair a lane fetches 64 + 48 bytes (two records and
-// the landmark's V^-1) instead of two 144-byte blocks, straight into registers: the cooperative fetch through LDS of k_w_schur (two dependent hand-overs per
-// round, the kernel's bound after round 4: profiles/r04_pmc_lba_wait_ta.json) is gone, and so are k_w_lin's 144-byte-per-lane stores (128 MB written per launch
+// the landmark's V^-1) instead of two 144-byte blocks, straight into registers: the cooperative fetch through LDS of the round-4 kernel (two dependent hand-overs
+// per round, its bound: profiles/r04_pmc_lba_wait_ta.json) is gone, and so are k_w_lin's 144-byte-per-lane stores (128 MB written per launch
 // of 40 windows for 75 MB of blocks).  ~300 fused multiply-adds per pair instead of ~180: the vector ALU was at 16-22 % of the wave cycles.  An edge that has
-// left the problem (level 1) carries weight 0 and adds exact zeros.  Same summation order over the pairs as k_w_schur (lane l takes pairs l, l + 64, ...; quad
+// left the problem (level 1) carries weight 0 and adds exact zeros.  Fixed summation order over the pairs (lane l takes pairs l, l + 64, ...; quad
 // sums, then 16 partial sums in lane order), so a window's result does not depend on the batch it is solved in.
-#ifndef OSLAM_SCHUR_REC_WAVES
-#define OSLAM_SCHUR_REC_WAVES 2
-#endif
+// Two waves per SIMD (256 VGPRs): three (168 VGPRs) spill and were slower, DESIGN.md §6.
 __device__ __forceinline__ double uniform_f64(double v) {   // a wave-uniform value into scalar registers
     const long long b = __double_as_longlong(v);
     const int lo = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffll)), hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
-#ifndef OSLAM_SCHUR_PRE
-#define OSLAM_SCHUR_PRE 2   // rounds of a Schur block whose pair entries and point indices are requested together
-#endif
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OSLAM_SCHUR_REC_WAVES, OSLAM_SCHUR_REC_WAVES))) void k_w_schur_rec(const LbaProblem* probs, const LbaWide* ws, int nwin) {
+constexpr int kSchurPre = 2;   // rounds of a Schur block whose pair entries and point indices are requested together (1 / 2 / 3 / 4 measured: DESIGN.md §6.1)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_w_schur_rec(const LbaProblem* probs, const LbaWide* ws, int nwin) {
 #pragma clang fp contract(fast)
     int win, t;
     if (!xcd_window_item(nwin, win, t)) return;
@@ -1412,7 +1225,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OSLAM_SCHUR_
         Ops oa, ob;
         oa.a0 = ob.a0 = oa.b0 = ob.b0 = make_double2(0.0, 0.0); oa.a1 = ob.a1 = oa.b1 = ob.b1 = make_double2(1.0, 0.0);
         oa.v0 = oa.v1 = oa.v2 = ob.v0 = ob.v1 = ob.v2 = make_double2(0.0, 0.0); oa.pt = ob.pt = 0;
-        constexpr int kSchurPre = OSLAM_SCHUR_PRE;
         for (int q = q0 + lane; q < q_end; q += 64 * kSchurPre) {   // (per lane; a lane past its last pair idles)
             int2 pe[kSchurPre]; int pt[kSchurPre];
 #pragma unroll
@@ -1952,40 +1764,11 @@ __global__ __launch_bounds__(kMfmaThreads) void k_w_chol_mfma(const LbaProblem* 
 // Blocks [0, nblk_pt): 128 landmarks each — x_l, the trial position, then the errors of the landmark's edges at the TRIAL state.  The trial poses of the free
 // keyframes are what the pose block (item == nblk_pt) writes to w.T / w.R for the later launches; a landmark block cannot wait for another block, so it
 // recomputes them itself into LDS (se3_exp + se3_mul per free keyframe: the same two calls on the same inputs, hence the same bits).
-__device__ void w_gate_block(const LbaProblem& pr, const LbaWide& w);
-// FOLD: the LM control step of the trial (k_w_ctrlB of rounds 1-4) runs in the LAST workgroup of the window to finish — every workgroup publishes its partial sums,
-// then takes a ticket; the one that draws the last ticket sees all of them (release / acquire fences at device scope around the ticket) — one launch less per trial,
-// and slower than the launch it replaces (see fold_ctrl at the launch site): an A/B knob, off by default.
-__device__ __forceinline__ void w_update_tail(const LbaProblem& pr, const LbaWide& w, int win) {
-    __shared__ int s_last, s_gate;
-    __threadfence();        // every lane's chi2 / trial-state stores are out before the ticket is taken
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        LbaCtrl* ct = w.ct;
-        const int t = atomicAdd(&ct->ticket[1], 1);
-        s_last = t == w.nblk_pt;
-        s_gate = 0;
-        if (s_last) {
-            ct->ticket[1] = 0;
-            __threadfence();
-            w_ctrlB(pr, w, win);
-            s_gate = ct->gate && !ct->done;
-        }
-    }
-    __syncthreads();
-    if (s_last && s_gate) {
-        __threadfence();
-        w_gate_block(pr, w);
-        __syncthreads();
-        if (threadIdx.x == 0) w.ct->gate = 0;
-    }
-}
-
-// (round 5: kUpdLanes = 1, 2 or 4 lanes per landmark split its edge list — stride kUpdLanes, partial sums combined by a fixed xor-shuffle tree — like k_w_lin's landmark
-// role: the one-lane form walked ~8 edges twice in one dependent chain and the kernel spent its time waiting)
-template <bool REC, bool FOLD, int kUpdLanes>
+// (kUpdLanes lanes per landmark split its edge list — stride kUpdLanes, partial sums combined by a fixed xor-shuffle tree — like k_w_lin's landmark role)
+template <bool REC>
 __global__ __launch_bounds__(kWPt * kUpdLanes) void k_w_update(const LbaProblem* probs, const LbaWide* ws, int nwin) {
     constexpr int kUpdThreads = kWPt * kUpdLanes;   // the workgroup still owns kWPt landmarks
+    static_assert(kUpdLanes == 2, "the partial sums of a landmark are combined by one lane_xor1");
     int win_, item_;
     if (!xcd_window_item(nwin, win_, item_)) return;
     const LbaProblem& pr = probs[win_];
@@ -2022,7 +1805,6 @@ __global__ __launch_bounds__(kWPt * kUpdLanes) void k_w_update(const LbaProblem*
             for (int i = 1; i < kUpdThreads / 64; i++) a += sS[i];
             w.partS[item_] = a;
         }
-        if (FOLD) w_update_tail(pr, w, win_);
         return;
     }
     // ---- landmark block ----
@@ -2079,8 +1861,7 @@ __global__ __launch_bounds__(kWPt * kUpdLanes) void k_w_update(const LbaProblem*
             }
 #pragma unroll
             for (int j = 0; j < 3; j++) {
-#pragma unroll
-                for (int d = 1; d < kUpdLanes; d <<= 1) dl[j] += d == 1 ? lane_xor1(dl[j]) : (d == 2 ? lane_xor2(dl[j]) : __shfl_xor(dl[j], d, 64));
+                dl[j] += lane_xor1(dl[j]);   // (kUpdLanes == 2: the landmark's other lane)
                 cl[j] -= dl[j];
             }
         } else if (ok2) {
@@ -2105,12 +1886,11 @@ __global__ __launch_bounds__(kWPt * kUpdLanes) void k_w_update(const LbaProblem*
             }
 #pragma unroll
             for (int j = 0; j < 3; j++) {
-#pragma unroll
-                for (int d = 1; d < kUpdLanes; d <<= 1) dl[j] += d == 1 ? lane_xor1(dl[j]) : (d == 2 ? lane_xor2(dl[j]) : __shfl_xor(dl[j], d, 64));
+                dl[j] += lane_xor1(dl[j]);   // (kUpdLanes == 2: the landmark's other lane)
                 cl[j] -= dl[j];
             }
         }
-        if (ok2 && REC) {   // (Hll_p + lambda I)^-1 as k_w_edgeW<true> left it for this trial
+        if (ok2 && REC) {   // (Hll_p + lambda I)^-1 as k_w_edgeW left it for this trial
             const double2* vp = (const double2*)(w.W + (long long)p * 6);
             const double2 v0 = vp[0], v1 = vp[1], v2 = vp[2];
             xo[0] = v0.x * cl[0] + v0.y * cl[1] + v1.x * cl[2];
@@ -2167,12 +1947,11 @@ __global__ __launch_bounds__(kWPt * kUpdLanes) void k_w_update(const LbaProblem*
         w.partS[item_] = a;
         w.partF[item_] = b;
     }
-    if (FOLD) w_update_tail(pr, w, win_);
 }
 
 // Levenberg-Marquardt decision + schedule transitions (g2o OptimizationAlgorithmLevenberg::solve tail,
 // SparseOptimizer::optimize loop, and the stage logic of reference src/Optimizer.cc:660-707)
-// LM control after the trial evaluation (one thread: the last block of k_w_eval): gain ratio, accept / reject, lambda
+// LM control after the trial evaluation (one thread of k_w_ctrlB): gain ratio, accept / reject, lambda
 // update, iteration / stage bookkeeping of g2o's OptimizationAlgorithmLevenberg + SparseOptimizer::optimize
 // Test hook (oslam_lba_trace): LM trials of window 0 of the wide layout. [0] = records seen, then [cap][6] = (F before, F of the trial, rho, lambda,
 // accepted, first trial of a stage).
@@ -2314,10 +2093,8 @@ struct oslam_lba {
     int wide = 1;                 // 1: every LM trial of all windows as whole-GPU launches, 0: one workgroup per window in one launch (k_lba, the round-1 kernel),
                                   // 2: one workgroup per window, LDS-resident reduced system (k_lba_win); windows that do not fit its LDS go through layout 1
     size_t win_lds_max = 0;       // dynamic LDS a k_lba_win workgroup may use
-    int edge_rec = 1;             // pair gather with per-landmark inverses: compact 32-byte edge records instead of the 144-byte B_e blocks (k_w_schur_rec; round 5 default), 0 = materialised B_e (OSLAM_LBA_REC)
-    int schur_vinv = 1;           // pair gather: W_e = B_e V^-1 formed inside k_w_schur from per-landmark inverses (1, default) or materialised per edge by k_w_edgeW (0: rounds 1-3)
     int schur_tiles = 0;          // wide layout, Schur complement (default 0: in the bench the gather is as fast or faster at every window size, see below): 1 = by LDS tiles (k_w_schur_tiles: one coalesced read of Hpl per trial), 0 = by the pair gather
-                                  // (k_w_edgeW + k_w_schur: 288 bytes per pair from memory), 2 = per call: tiles when the windows average >= kSchurTilesMinEdges edges.
+                                  // (k_w_edgeW + k_w_schur_rec: two 32-byte edge records and the landmark's 48-byte inverse per pair), 2 = per call: tiles when the windows average >= kSchurTilesMinEdges edges.
                                   // Measured (tools/lba_win_prof.py, kernels of one call): 50 windows of 10 keyframes / 4.4 k edges: gather 3.2 ms, tiles 5.7 ms; 40 windows
                                   // of 27 keyframes / 13 k edges: gather 8.7 ms, tiles 9.2 ms alone, but in the bench (8 handles, ~330 such windows in flight: the W / B
                                   // blocks no longer fit the 256 MB cache) the local-BA group takes 5.9 s with tiles against 6.9 s with the gather
@@ -2469,8 +2246,6 @@ int oslam_lba_create(oslam_lba_t** out, int max_batch, int max_keyframes, int ma
     if (const char* e = getenv("OSLAM_LBA_CHOL_MFMA")) h->chol_mode = atoi(e) ? 1 : 2;   // kernel experiments: 1 = matrix cores for every size, 0 = never
     if (const char* e = getenv("OSLAM_LBA_SOLVER")) { const int v = atoi(e); if (v >= 0 && v <= 4) h->chol_mode = v; }   // A/B knob: oslam_lba_set_solver for every handle of the process
     if (getenv("OSLAM_LBA_HOST_PAIRS")) h->device_pairs = false;
-    if (const char* e = getenv("OSLAM_LBA_SCHUR_VINV")) h->schur_vinv = atoi(e) != 0;
-    if (const char* e = getenv("OSLAM_LBA_REC")) h->edge_rec = atoi(e) != 0;
     if (const char* e = getenv("OSLAM_LBA_SCHUR_TILES")) h->schur_tiles = atoi(e);   // 0 = always the pair gather, 1 = always tiles, 2 = per call (default)
     if (const int rc = h->h_stop.alloc_mapped(sizeof(int))) { oslam_lba_destroy(h); return rc; }
     *h->h_stop.as<int>() = 0;
@@ -2827,7 +2602,7 @@ static int lba_prepare_all(oslam_lba_t* h, int n, const LbaArgs* a, const float 
 
 // Runs the prepared windows and brings their outputs into the pinned `out` mirror (the stream is drained on return).
 // Layout-1 windows: ONE launch of k_lba_win, one workgroup per window (largest first).  Layout-0 windows: compact mode = one launch of k_lba; wide mode =
-// every LM trial as eight launches whose grids cover all of them (blockIdx.y = window, blockIdx.x sized for the largest one; finished windows return at once).
+// every LM trial as six launches (seven on the tiles route) whose grids cover all of them (blockIdx.y = window, blockIdx.x sized for the largest one; finished windows return at once).
 static int lba_launch(oslam_lba_t* h) {
     const auto t_launch0 = std::chrono::steady_clock::now();
     const int n = h->n_prep;
@@ -2849,7 +2624,7 @@ static int lba_launch(oslam_lba_t* h) {
     struct WOff { size_t Xa, Xb, chi2, level, Hpl, Hll, Dinv, bl, xl, Hpp, bp, Hs, xp, ctrl, T, R, blk, free_pose, partF, partS, partM, W, rec, eoi, chunkC, pairPart, parts, pairM, pairsW, pstartW; };
     bool tiles = wide && n0 > 0;     // wide layout: Schur complement by tiles when every layout-0 window carries the structures
     for (int i : idx0) tiles = tiles && !h->prep[i].tile_p0.empty();
-    const bool use_rec = wide && !tiles && h->schur_vinv && h->edge_rec;   // compact edge records (k_w_schur_rec): no B_e blocks at all
+    const bool use_rec = wide && !tiles;   // compact edge records (k_w_schur_rec): no B_e blocks at all
     const int nwg_call = std::max(1, std::min(16, (2 * 256 + std::max(n0, 1) - 1) / std::max(n0, 1)));   // workgroups per window: ~2 per CU over the call
     size_t tiles_lds = 0, packed_lds = 0, ldsm_lds = 0;
     int maxWg = 1, maxSum = 1, min_n6_big = 1 << 30;   // (min_n6_big: the smallest reduced system of the call)
@@ -2882,7 +2657,7 @@ static int lba_launch(oslam_lba_t* h) {
                     maxWg = std::max(maxWg, nwg); maxSum = std::max(maxSum, div_up(q.nblk * 42, 256));
                 } else {
                     // (per-landmark inverses: 48 bytes per point, whatever the edge count — a window may hold points without edges)
-                    o.W = takeW(use_rec ? P * 48 : std::max(E * 144, h->schur_vinv ? P * 48 : (size_t)0));
+                    o.W = takeW(P * 48);
                     o.rec = use_rec ? takeW(E * 32) : 0;
                     o.eoi = use_rec ? takeW(E * 16) : 0;
                     if (q.dev_pairs) { o.pairsW = takeW(std::max<size_t>(q.npairs, 1) * 8); o.pstartW = takeW(((size_t)q.nblk + 1) * 4); any_dev_pairs = true; }   // (pairM: one block for the call, below)
@@ -2982,16 +2757,6 @@ static int lba_launch(oslam_lba_t* h) {
     }
     std::sort(cost.begin(), cost.end());   // the most expensive windows are dispatched first
     for (int j = 0; j < n1; j++) horder[j] = cost[j].second;
-    // OSLAM_LBA_CONCURRENCY=k: at most k local-BA calls of this process have device work in flight at a time (A/B knob: two overlapping calls both take about
-    // twice as long, one after the other the first is back after half of that)
-    struct Gate {
-        std::mutex m; std::condition_variable cv; int free_slots;
-        explicit Gate(int k) : free_slots(k) {}
-        void enter() { std::unique_lock<std::mutex> lk(m); cv.wait(lk, [&] { return free_slots > 0; }); free_slots--; }
-        void leave() { { std::lock_guard<std::mutex> lk(m); free_slots++; } cv.notify_one(); }
-    };
-    static Gate* gate = [] { const char* e = getenv("OSLAM_LBA_CONCURRENCY"); const int k = e ? atoi(e) : 0; return k > 0 ? new Gate(k) : (Gate*)nullptr; }();
-    struct GateScope { Gate* g; explicit GateScope(Gate* g_) : g(g_) { if (g) g->enter(); } ~GateScope() { if (g) g->leave(); } } gate_scope(gate);
     h->prof_pre_upload_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_launch0).count();
     OSLAM_HIP_CHECK(hipMemcpyAsync(I, h->in_h.bytes(), h->in_off, hipMemcpyHostToDevice, st));   // the ONE upload
     // Solvers that share a gate run their KERNELS in turns: the window preparation above and the upload (a DMA transfer on this solver's own stream: tens of
@@ -3040,17 +2805,7 @@ static int lba_launch(oslam_lba_t* h) {
         // worst case 15 iterations x 10 trials; slots past `done` return at once.  First group = the minimum number of LM trials (one per
         // iteration), so the common case needs a single host round trip; rejected steps add groups of 4.
         const int ny_xcd = n0 >= 8 ? (n0 + 7) / 8 * 8 : n0;   // grid rows of the kernels that map a window to one XCD (xcd_window_item)
-        static const double gate_release_frac = [] { const char* e = getenv("OSLAM_LBA_GATE_RELEASE"); return e ? atof(e) : 0.0; }();
         static const bool call_stats = getenv("OSLAM_LBA_CALL_STATS") != nullptr;   // per host poll: windows of the call, trial slots enqueued so far, windows not done
-        // LM control step in the last workgroup of k_w_update instead of its own launch (5 launches per trial instead of 6).  Default OFF, measured: the device-scope release
-        // fence every workgroup needs before it takes its ticket (an L2 write-back on gfx950: the window's workgroups may sit on different XCDs) costs more than the
-        // launch it saves — 314 against 294 us per trial at 40 windows, 750 against 640 us at 128 (same box, alternating runs; tests/test_lba_gpu.py green both ways).
-        static const bool fold_ctrl = [] { const char* e = getenv("OSLAM_LBA_FOLD_CTRL"); return e && atoi(e) != 0; }();
-        // lanes per landmark in k_w_update (OSLAM_LBA_UPD_LANES = 1 / 2 / 4 overrides).  us per LM trial of a call, 1 / 2 / 4 lanes, same box, two sweeps: 40 windows
-        // 293 / 279 / 283, 96 windows 494 / 485 / 498, 128 windows 639 / 616 / 641, 256 windows 1223 / 1180 / 1232: the one-lane form waits (~8 edges walked twice in one
-        // dependent chain), four lanes repeat the per-landmark part (inverse, step, stores) four times
-        static const int upd_lanes_env = getenv("OSLAM_LBA_UPD_LANES") ? atoi(getenv("OSLAM_LBA_UPD_LANES")) : 0;
-        const int upd_lanes = upd_lanes_env ? upd_lanes_env : 2;
         int slots_done = 0, group = min_group;
         while (slots_done < max_slots) {
             for (int sl = 0; sl < group; sl++, slots_done++) {
@@ -3061,16 +2816,8 @@ static int lba_launch(oslam_lba_t* h) {
                     hipLaunchKernelGGL(k_w_schur_tiles, dim3(maxWg, n0), dim3(kWinThreads), tiles_lds, st, d_probs, d_ws);
                     hipLaunchKernelGGL(k_w_schur_sum, dim3(maxSum, n0), dim3(256), 0, st, d_probs, d_ws);
                 } else {
-                    if (use_rec) {
-                        hipLaunchKernelGGL(k_w_edgeW<true>, dim3(div_up(maxNbPt * kWPt, 256), ny_xcd), dim3(256), 0, st, d_probs, d_ws, n0);
-                        hipLaunchKernelGGL(k_w_schur_rec, dim3(maxBlk, ny_xcd), dim3(64), 0, st, d_probs, d_ws, n0);
-                    } else if (h->schur_vinv) {
-                        hipLaunchKernelGGL(k_w_edgeW<true>, dim3(div_up(maxNbPt * kWPt, 256), ny_xcd), dim3(256), 0, st, d_probs, d_ws, n0);
-                        hipLaunchKernelGGL(k_w_schur<true>, dim3(maxBlk, ny_xcd), dim3(64), 0, st, d_probs, d_ws, n0);
-                    } else {
-                        hipLaunchKernelGGL(k_w_edgeW<false>, dim3(div_up(maxE, 256), ny_xcd), dim3(256), 0, st, d_probs, d_ws, n0);
-                        hipLaunchKernelGGL(k_w_schur<false>, dim3(maxBlk, ny_xcd), dim3(64), 0, st, d_probs, d_ws, n0);
-                    }
+                    hipLaunchKernelGGL(k_w_edgeW, dim3(div_up(maxNbPt * kWPt, 256), ny_xcd), dim3(256), 0, st, d_probs, d_ws, n0);
+                    hipLaunchKernelGGL(k_w_schur_rec, dim3(maxBlk, ny_xcd), dim3(64), 0, st, d_probs, d_ws, n0);
                 }
                 if (chol_ldsm) hipLaunchKernelGGL(k_w_chol_lds_mfma, dim3(1, n0), dim3(kWinThreads), ldsm_lds, st, d_probs, d_ws, 0);
                 if (chol_packed) hipLaunchKernelGGL(k_w_chol_packed, dim3(1, n0), dim3(kWinThreads), packed_lds, st, d_probs, d_ws);
@@ -3078,17 +2825,9 @@ static int lba_launch(oslam_lba_t* h) {
                 if (chol_ldsm || chol_packed || chol_mfma) { }
                 else if (chol_lds) hipLaunchKernelGGL(k_w_chol<true>, dim3(1, n0), dim3(1024), chol_lds, st, d_probs, d_ws);
                 else hipLaunchKernelGGL(k_w_chol<false>, dim3(1, n0), dim3(1024), 0, st, d_probs, d_ws);
-                // (+ the trial's chi2: k_w_eval of rounds 1-3; OSLAM_LBA_FOLD_CTRL=1: + the LM control step in the window's last workgroup)
-                {
-                    const dim3 ug(maxNbPt + 1, ny_xcd);
-#define OSLAM_UPD_LAUNCH(R, F, L) hipLaunchKernelGGL((k_w_update<R, F, L>), ug, dim3(kWPt * L), 0, st, d_probs, d_ws, n0)
-#define OSLAM_UPD_LANES(R, F) do { if (upd_lanes == 4) OSLAM_UPD_LAUNCH(R, F, 4); else if (upd_lanes == 2) OSLAM_UPD_LAUNCH(R, F, 2); else OSLAM_UPD_LAUNCH(R, F, 1); } while (0)
-                    if (fold_ctrl) { if (use_rec) OSLAM_UPD_LANES(true, true); else OSLAM_UPD_LANES(false, true); }
-                    else { if (use_rec) OSLAM_UPD_LANES(true, false); else OSLAM_UPD_LANES(false, false); }
-#undef OSLAM_UPD_LANES
-#undef OSLAM_UPD_LAUNCH
-                    if (!fold_ctrl) hipLaunchKernelGGL(k_w_ctrlB, dim3(1, n0), dim3(256), 0, st, d_probs, d_ws);
-                }
+                if (use_rec) hipLaunchKernelGGL(k_w_update<true>, dim3(maxNbPt + 1, ny_xcd), dim3(kWPt * kUpdLanes), 0, st, d_probs, d_ws, n0);
+                else hipLaunchKernelGGL(k_w_update<false>, dim3(maxNbPt + 1, ny_xcd), dim3(kWPt * kUpdLanes), 0, st, d_probs, d_ws, n0);
+                hipLaunchKernelGGL(k_w_ctrlB, dim3(1, n0), dim3(256), 0, st, d_probs, d_ws);
             }
             OSLAM_HIP_CHECK(copy_to_host_async(h->h_ctrl.as<LbaCtrl>(), Wk + ctrl_base, sizeof(LbaCtrl) * n0, st));   // (a copy kernel, not the SDMA ring: common.h)
             OSLAM_HIP_CHECK(stream_wait(st));
@@ -3097,18 +2836,12 @@ static int lba_launch(oslam_lba_t* h) {
             for (int i = 0; i < n0; i++) { all_done = all_done && h->h_ctrl.as<LbaCtrl>()[i].done != 0; n_active += h->h_ctrl.as<LbaCtrl>()[i].done == 0; }
             if (call_stats) fprintf(stderr, "[lba call] %d windows, %d slots done, %d active\n", n0, slots_done, n_active);
             if (all_done) break;
-            // The tail of a call — the few windows whose LM rejects steps (after the first 15 slots ~16 % of the windows of a steady-state call are still active,
-            // after 19 slots ~6 %) — is a chain of latency-bound launches that leaves the card almost idle: the solver that shares the gate may start its call
-            // beside it when OSLAM_LBA_GATE_RELEASE=f is set (release once <= f x windows are active).  Default off: same-box A/B of the headline with f = 0.25,
-            // alternating runs: 35.2 / 38.7 k frames/s against 37.7 / 38.5 k without — the overlapping call stretches this call's kernels (local-BA device time
-            // 3.6 -> 3.9-4.4 s per 20 steps) by what the tail used to idle.
-            if (handle_gate.owns_lock() && gate_release_frac > 0 && (double)n_active <= gate_release_frac * n0) handle_gate.unlock();
             group = 4;
         }
         hipLaunchKernelGGL(k_w_final, dim3(div_up(maxFin, 256), n0), dim3(256), 0, st, d_probs, d_ws);
         // launches per trial slot: linearisation, (control step +) Schur complement, the solver kernels this call mixes, update, control
         const int n_chol = (chol_ldsm ? 1 : 0) + (chol_packed ? 1 : 0) + (chol_mfma ? 1 : 0);
-        launches += 3 + (1 + (tiles ? 3 : 2) + std::max(n_chol, 1) + (fold_ctrl ? 1 : 2)) * (long long)slots_done;
+        launches += 3 + (1 + (tiles ? 3 : 2) + std::max(n_chol, 1) + 2) * (long long)slots_done;
     }
     lba_time_end(h);
     OSLAM_HIP_CHECK(hipGetLastError());

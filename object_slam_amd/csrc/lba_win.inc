@@ -781,7 +781,7 @@ __global__ __launch_bounds__(kWinThreads) void k_lba_win(const LbaProblem* probs
 // ==========================================================================================================================================================
 // The same on-chip Schur complement for the WIDE layout (every LM trial of all windows as whole-GPU launches): `nwg` workgroups per window share its tiles
 // (workgroup g takes tiles g, g + nwg, ...), stage B_e from the stored Hpl blocks (one coalesced read per trial instead of the 288 bytes per PAIR the
-// pair-gather kernel k_w_schur pulled from HBM: 4-6 pairs per edge in the driver's windows) and leave per-workgroup block sums; k_w_schur_sum adds them in
+// pair-gather kernel of rounds 1-4 pulled from HBM: 4-6 pairs per edge in the driver's windows) and leave per-workgroup block sums; k_w_schur_sum adds them in
 // workgroup / slot order into the reduced system.  Short kernels: the windows of a call spread over the whole GPU and the other handles' kernels interleave.
 // ==========================================================================================================================================================
 __global__ __launch_bounds__(kWinThreads) void k_w_schur_tiles(const LbaProblem* probs, const LbaWide* ws) {
