@@ -2,7 +2,7 @@
 // ORB_SLAM2::ORBextractor (include/ORBextractor.h:45-110), ORB_SLAM2::ORBmatcher (include/ORBmatcher.h:41-83: both projection searches,
 // SearchByBoW, SearchForTriangulation, Fuse, DescriptorDistance), Frame::ComputeStereoMatches (src/Frame.cc:706), ORB_SLAM2::Optimizer
 // (include/Optimizer.h:38-46: PoseOptimization, LocalBundleAdjustment, BundleAdjustment) and ObjectOptimizer::PoseOptimization2
-// (include/ObjectOptimizer.h:23), and ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: loadFromTextFile, transform, score).  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
+// (include/ObjectOptimizer.h:23), ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: loadFromTextFile, transform, score) and ORB_SLAM2::PnPsolver (include/PnPsolver.h: SetRansacParameters, iterate, find).  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
 // "view" of exactly the members it reads and writes (the gather loops are in INTEGRATION.md).  tests/adapter_program.cc uses nothing but
 // these classes; tests/test_adapter_gpu.py builds it, runs it and compares its outputs with the ctypes path.
 //
@@ -449,6 +449,96 @@ public:
         if (nSemNum) *nSemNum = ns;
         return n;
     }
+};
+
+// Flat views of what PnPsolver::PnPsolver(const Frame&, const vector<MapPoint*>&) reads (src/PnPsolver.cc:67-110)
+struct PnPFrameView {
+    int N;                                // mvKeysUn.size()
+    const oslam::KeyPoint* mvKeysUn;
+    const float* mvLevelSigma2; int nLevels;
+    float fx, fy, cx, cy;
+};
+struct PnPMatchView {                     // vpMapPointMatches, one entry per keypoint
+    const uint8_t* has_mp;                // vpMapPointMatches[i] != NULL
+    const uint8_t* bad;                   // pMP->isBad() (may be NULL: none is bad)
+    const float* Xw;                      // [N][3] pMP->GetWorldPos()
+};
+
+// ORB_SLAM2::PnPsolver (include/PnPsolver.h:62-72).  The reference returns the pose as a cv::Mat that is empty when there is none; here iterate / find
+// return whether there is one and write it to Tcw (4 x 4 row-major float).  A solver is one shot (oslam_hip.h, "PnP solver"): the first iterate() runs the
+// reference's whole interleaved loop, whatever nIterations says; later calls have nothing left to do and return no pose with bNoMore.
+// `seed` stands for the clock-seeded DUtils::Random of the reference.
+class PnPsolver {
+public:
+    PnPsolver(const PnPFrameView& F, const PnPMatchView& M, uint32_t seed = 0) : nKeys_(F.N), seed_(seed) {
+        K_[0] = F.fx; K_[1] = F.fy; K_[2] = F.cx; K_[3] = F.cy;
+        for (int i = 0; i < F.N; i++) {   // :78-101
+            if (!M.has_mp[i] || (M.bad && M.bad[i])) continue;
+            const oslam::KeyPoint& kp = F.mvKeysUn[i];
+#ifdef OSLAM_ADAPTER_USE_OPENCV
+            mvP2D.push_back(kp.pt.x); mvP2D.push_back(kp.pt.y);
+#else
+            mvP2D.push_back(kp.x); mvP2D.push_back(kp.y);
+#endif
+            if (kp.octave < 0 || kp.octave >= F.nLevels) throw std::runtime_error("PnPsolver: keypoint octave outside mvLevelSigma2");
+            mvSigma2.push_back(F.mvLevelSigma2[kp.octave]);
+            mvP3Dw.push_back(M.Xw[3 * (size_t)i]); mvP3Dw.push_back(M.Xw[3 * (size_t)i + 1]); mvP3Dw.push_back(M.Xw[3 * (size_t)i + 2]);
+            mvKeyPointIndices.push_back(i);
+        }
+        SetRansacParameters();
+    }
+    ~PnPsolver() { oslam_pnp_destroy(h_); }
+    PnPsolver(const PnPsolver&) = delete;
+    PnPsolver& operator=(const PnPsolver&) = delete;
+
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4, float epsilon = 0.4f, float th2 = 5.991f) {
+        prm_.probability = probability; prm_.min_inliers = minInliers; prm_.max_iterations = maxIterations; prm_.min_set = minSet; prm_.epsilon = epsilon; prm_.th2 = th2;
+        prm_.reserved = 0;
+    }
+    // mRansacMinInliers, mRansacEpsilon, mRansacMaxIts as SetRansacParameters leaves them (:134-152)
+    oslam_pnp_ransac_t Adjusted() const {
+        oslam_pnp_ransac_t r;
+        oslam::throw_on(oslam_pnp_ransac_params((int)mvSigma2.size(), prm_.probability, prm_.min_inliers, prm_.max_iterations, prm_.min_set, prm_.epsilon, &r));
+        return r;
+    }
+    bool find(std::vector<bool>& vbInliers, int& nInliers, float Tcw[16]) {
+        bool bFlag;
+        return iterate(prm_.max_iterations, bFlag, vbInliers, nInliers, Tcw);
+    }
+    // vbInliers is indexed by keypoint (:229-234) and empty when there is no pose
+    bool iterate(int /*nIterations*/, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, float Tcw[16]) {
+        bNoMore = false;
+        vbInliers.clear();
+        nInliers = 0;
+        const int N = (int)mvSigma2.size();
+        if (done_ || N == 0) { bNoMore = true; done_ = true; return false; }
+        done_ = true;
+        if (!h_) oslam::throw_on(oslam_pnp_create(&h_, 1, N, prm_.max_iterations));
+        oslam_pnp_problem_t pr;
+        pr.count = N; pr.offset = 0; pr.fx = K_[0]; pr.fy = K_[1]; pr.cx = K_[2]; pr.cy = K_[3]; pr.seed = seed_; pr.reserved = 0;
+        std::vector<uint8_t> flags(N, 0);
+        int32_t st[4] = {0, 0, 0, -1};
+        oslam::throw_on(oslam_pnp_ransac_batch(h_, 1, &pr, N, mvP3Dw.data(), mvP2D.data(), mvSigma2.data(), &prm_, nullptr, Tcw, flags.data(), st, nullptr));
+        mnIterations = st[2];
+        if (st[0] != 1) bNoMore = true;   // :241-243
+        if (st[0] <= 0) return false;
+        nInliers = st[1];
+        vbInliers.assign(nKeys_, false);
+        for (int i = 0; i < N; i++)
+            if (flags[i]) vbInliers[mvKeyPointIndices[i]] = true;
+        return true;
+    }
+    int mnIterations = 0;                       // iterations run by the last iterate()
+    std::vector<float> mvP2D, mvSigma2, mvP3Dw;   // the filtered correspondences (:87-93), packed
+    std::vector<size_t> mvKeyPointIndices;
+
+private:
+    int nKeys_;
+    uint32_t seed_;
+    float K_[4];
+    oslam_pnp_params_t prm_;
+    oslam_pnp_t* h_ = nullptr;
+    bool done_ = false;
 };
 
 }  // namespace ORB_SLAM2

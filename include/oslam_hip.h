@@ -696,6 +696,87 @@ int oslam_voc_vectors(const oslam_voc_t* voc, int n, const uint32_t* word, const
  * The other five scorings are not implemented: *rc = OSLAM_E_INVALID with a message (rc may be NULL), return value 0. */
 double oslam_voc_score(const oslam_voc_t* voc, int na, const uint32_t* ids_a, const double* vals_a, int nb, const uint32_t* ids_b, const double* vals_b, int* rc);
 
+/* ------------------------------------------------------------------------------------------
+ * PnP solver — ORB_SLAM2::PnPsolver (include/PnPsolver.h, src/PnPsolver.cc: EPnP inside RANSAC), the numerical operator of
+ * Tracking::Relocalization (src/Tracking.cc:1650-1676), for batches of independent problems (one per lost frame and candidate keyframe).
+ * The tracking driver does not call it: a sequence that is LOST stays LOST (oslam_slam.h).
+ *
+ * A problem is `count` correspondences (P3Dw, P2D = mvKeysUn[i].pt, sigma2 = mvLevelSigma2[octave], all float: :87-93) at `offset` of the packed
+ * arrays, the intrinsics and a seed.  Problems of one call must not share correspondences.
+ * SetRansacParameters (:121-157) is restated with its mixed arithmetic (oslam_pnp_ransac_params).  iterate (:165-258): its loop condition
+ * `mnIterations < mRansacMaxIts || nCurrentIterations < nIterations` makes the first call run to mRansacMaxIts, so a solver is one shot and one call
+ * per problem reproduces the reference's interleaved loop.  Per iteration: four indices by the swap-with-back rule (:188-201), compute_pose
+ * (:477-525, fp64), CheckInliers (:308-339: Xc, Yc, invZc, distX, distY, error2 float, ue, ve double, strict comparison with sigma2 * th2); a count
+ * >= minInliers that is strictly above every earlier one becomes the best (:209-224), then Refine (:260-305: EPnP over the best set, CheckInliers,
+ * success when the count is strictly above minInliers) and a success returns at once.  Refine depends on the best set alone, so the result is the first
+ * RECORD iteration (count >= minInliers and above every earlier count) whose Refine succeeds — status kind 1 — otherwise the last record, unrefined
+ * (:241-255, bNoMore) — kind 2 — otherwise none — kind 0.  Tcw is converted from fp64 where the reference calls convertTo(CV_32F) (:219-223, :296-300).
+ *
+ * Normalisations:
+ *  1. DUtils::Random is not in the reference tree and is seeded from the clock.  Here the four indices of an iteration either are the caller's
+ *     (`samples`: four distinct correspondence indices of the problem; anything else makes that hypothesis count zero) or come from a counter-based
+ *     generator: mix(x) = { x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16 } on uint32,
+ *     hash(seed, iteration, draw) = mix(mix(seed + 0x9E3779B9 * (iteration + 1)) ^ (0x85EBCA6B * (draw + 1))), and draw k = 0..3 takes
+ *     randi = (hash * (N - k)) >> 32 (64-bit product) from the list of remaining indices, whose entry randi is then replaced by its last entry.
+ *     oslam_pnp_draw evaluates it on the host.
+ *  2. For the minimal set of four points MtM has rank 8: the hypothesis depends on the null-space basis the eigen-solver returns (cvSVD in the
+ *     reference, cyclic Jacobi here), so single hypotheses are not comparable with any CPU restatement; what is determined (the refined pose, the
+ *     inlier set, the control flow) is.  For n >= 6 points compute_pose agrees with a CPU restatement to rounding.
+ *  3. min_set other than 4 is refused with OSLAM_E_INVALID.
+ *  4. cvSolve(CV_SVD) of the beta initialisations is the least-squares solution by the Householder QR of qr_solve; cvInvert(CV_SVD) of the control-point
+ *     matrix uses its known factors (orthonormal PCA axes times their scales); a singular qr_solve leaves its step at zero (the reference leaves it unset).
+ *     A hypothesis whose pose is not finite counts zero inliers.  pow and log of the iteration count are the device's in the kernels and the host's in
+ *     oslam_pnp_ransac_params.
+ *  5. Input validation: a problem with a coordinate, observation, sigma2 or intrinsic that is not finite gets kind 0 with 0 iterations run.
+ *  6. The sign of a PCA axis of choose_control_points is cvSVD's choice in the reference; with noisy observations it moves compute_pose's result at
+ *     the 1e-3 level (the control points, and with them the algebraic error EPnP minimises, change).  Here the component of largest magnitude of each
+ *     axis (the first of equals) is positive.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct oslam_pnp oslam_pnp_t;
+typedef struct oslam_pnp_params {   /* the arguments of SetRansacParameters (:121); the reference's call is (0.99, 10, 300, 4, 0.5, 5.991) */
+    double probability;
+    int32_t min_inliers, max_iterations, min_set;
+    float epsilon, th2;
+    int32_t reserved;
+} oslam_pnp_params_t;
+typedef struct oslam_pnp_problem {
+    int32_t count, offset;   /* correspondences offset .. offset + count - 1 of the packed arrays */
+    float fx, fy, cx, cy;
+    uint32_t seed;
+    int32_t reserved;
+} oslam_pnp_problem_t;
+typedef struct oslam_pnp_ransac {   /* what SetRansacParameters leaves in mRansacMinInliers, mRansacEpsilon, mRansacMaxIts */
+    int32_t min_inliers;
+    float epsilon;
+    int32_t iterations;   /* 0 when no_more */
+    int32_t no_more;      /* N < min_inliers: iterate() returns no pose and bNoMore at once (:173-177) */
+} oslam_pnp_ransac_t;
+/* Host only, needs no device. */
+int oslam_pnp_ransac_params(int N, double probability, int min_inliers, int max_iterations, int min_set, float epsilon, oslam_pnp_ransac_t* out);
+/* The four indices iteration `iteration` of a problem with N >= 4 correspondences draws from `seed` (normalisation 1).  Host only. */
+int oslam_pnp_draw(uint32_t seed, int iteration, int N, int32_t idx[4]);
+/* max_iterations bounds params.max_iterations of the calls (the work arena holds one pose per problem and iteration).  OSLAM_E_HIP without a device. */
+int oslam_pnp_create(oslam_pnp_t** out, int max_problems, int max_correspondences_total, int max_iterations);
+void oslam_pnp_destroy(oslam_pnp_t* h);
+/* Host pointers; one upload, two launches, one download, synchronous.  P3Dw [n_corr][3], P2D [n_corr][2], sigma2 [n_corr];
+ * samples NULL or [n_problems][params.max_iterations][4] int32.  Outputs: Tcw [n_problems][16] float (row-major 4 x 4), inliers [n_corr] bytes (by
+ * correspondence), status [n_problems][4] int32 = kind (0 none, 1 refined, 2 best unrefined), nInliers, iterations run, the iteration whose set gave
+ * the result or -1; iter_inliers NULL or [n_problems][params.max_iterations] int32 = the CheckInliers count of every hypothesis of the problem's
+ * iteration count (also of those after an early success), -1 beyond it.  A problem with kind 0 (count 0 or below minInliers included) keeps the caller's Tcw and inlier bytes; nothing is written
+ * beyond a problem's count.  More problems, correspondences or iterations than the handle was created for: OSLAM_E_CAPACITY before anything is launched. */
+int oslam_pnp_ransac_batch(oslam_pnp_t* h, int n_problems, const oslam_pnp_problem_t* problems, int n_corr, const float* P3Dw, const float* P2D, const float* sigma2,
+                           const oslam_pnp_params_t* params, const int32_t* samples, float* Tcw, uint8_t* inliers, int32_t* status, int32_t* iter_inliers);
+/* The same over device arrays (the problem records with their counts included; `params` is a host pointer), asynchronous on `stream`, no host
+ * synchronisation.  d_iter_inliers entries beyond a problem's iteration count are left as they were.  A problem record that does not lie inside the
+ * n_corr correspondences gets kind -1 and nothing else. */
+int oslam_pnp_ransac_batch_device(oslam_pnp_t* h, int n_problems, const oslam_pnp_problem_t* d_problems, int n_corr, const float* d_P3Dw, const float* d_P2D,
+                                  const float* d_sigma2, const oslam_pnp_params_t* params, const int32_t* d_samples, float* d_Tcw, uint8_t* d_inliers,
+                                  int32_t* d_status, int32_t* d_iter_inliers, void* stream);
+/* compute_pose (:477-525) alone — the device code Refine runs — for n_sets sets of counts[s] >= 4 correspondences at offsets[s]; K4 = fx, fy, cx, cy.
+ * R [n_sets][9], t [n_sets][3] and err [n_sets] (the mean reprojection error compute_pose returns) are fp64.  Host pointers, synchronous. */
+int oslam_pnp_epnp(oslam_pnp_t* h, int n_sets, const int32_t* counts, const int32_t* offsets, int n_corr, const float* P3Dw, const float* P2D, const float K4[4], double* R,
+                   double* t, double* err);
+
 #ifdef __cplusplus
 }
 #endif

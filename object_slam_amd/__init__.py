@@ -10,3 +10,5 @@ from .frame import FrameOps  # noqa: F401
 from .mappoint import MapPointBatch  # noqa: F401
 from .optimizer import LocalBundleAdjuster, PoseOptimizer  # noqa: F401
 from .vocabulary import Vocabulary  # noqa: F401
+from .pnp import PnPsolver  # noqa: F401
+from . import pnp  # noqa: F401
