@@ -98,6 +98,32 @@ int oslam_orb_debug_get_candidates(oslam_orb_t* h, int b, int level, int32_t* ou
 /* Quad-tree survivors of a level in reference order (level coords): src/ORBextractor.cc:834-847. */
 int oslam_orb_debug_get_level_keys(oslam_orb_t* h, int b, int level, int32_t* out, int cap, int* n_out);
 
+/* Which kernel variants the last batch launched.  Every field is written where the library takes the
+ * decision, from the value that selects the kernel (nothing is derived a second time), so a parity
+ * test can assert that the variant it is meant to pin really ran.  big_cell and skipped_cells are fixed
+ * when the handle is created (they go into the FAST cell records); everything else is per launch, and
+ * per issued half when the batch is cut in two (n_halves 1 or 2). */
+#define OSLAM_ORB_RESIZE_NONE 0    /* level 0, or nothing launched yet */
+#define OSLAM_ORB_RESIZE_PLAIN 1   /* k_resize: byte loads */
+#define OSLAM_ORB_RESIZE_WORDS 2   /* k_resize_words: quad tables, 4-byte aligned source rows */
+#define OSLAM_ORB_RESIZE_LDS 3     /* k_resize_lds: quad tables, source tile staged in LDS, 16-byte aligned source rows */
+typedef struct oslam_orb_plan {
+    int32_t nlevels;
+    int32_t batch;
+    int32_t n_halves;
+    int32_t half_nb[2];                               /* images of the half */
+    int32_t half_kpw[2];                              /* keypoints per wavefront of its k_orient_describe */
+    int32_t half_src_aligned4[2];                     /* level-0 rows of the half taken as 4-byte aligned (level-1 resize; FAST, blur and
+                                                         k_orient_describe test the same pitch and pointer bits per image); -1 with one level */
+    int32_t half_src_aligned16[2];                    /* ... as 16-byte aligned; -1 with one level */
+    int32_t half_oct_nodes_hbm[2];                    /* 1: k_octree_hbm (node tables in HBM), 0: k_octree + k_octree_spill */
+    int32_t half_big_cell_kernel[2];                  /* 1: k_fast_cells was launched beside k_fast_cells_wave */
+    int32_t half_resize[2][OSLAM_MAX_LEVELS];         /* OSLAM_ORB_RESIZE_* per level */
+    int32_t big_cell[OSLAM_MAX_LEVELS];               /* 1: the level's cells exceed the per-wavefront kernel and are left to k_fast_cells */
+    int32_t skipped_cells[OSLAM_MAX_LEVELS];          /* cells of the level recorded as empty (valid == 2) */
+} oslam_orb_plan_t;
+int oslam_orb_debug_get_plan(const oslam_orb_t* h, oslam_orb_plan_t* out);
+
 /* Kernel-group timing with HIP events recorded on the launch stream (bench.py's roofline leg).
  * Groups: 0 pyramid (K1 x (nlevels-1)), 1 FAST cells (K2/K3), 2 blur (K6 x nlevels), 3 quad-tree (K4),
  * 4 orientation + descriptors (K5/K7).  get_profile returns accumulated milliseconds since

@@ -149,6 +149,7 @@ struct oslam_orb {
     // last batch
     OrbCtx ctx;
     int last_batch = 0;
+    oslam_orb_plan_t plan = {};   // what the last launch_batch() chose (oslam_orb_debug_get_plan); big_cell / skipped_cells: what create chose
     hipStream_t last_stream = nullptr;
 };
 
@@ -455,8 +456,8 @@ int oslam_orb_create(oslam_orb_t** out, int nfeatures, float scaleFactor_, int n
                 if (maxX > maxBX) maxX = maxBX;
                 const int cw = maxX - iniX - 6, ch = maxY - iniY - 6;
                 int valid = 1;
-                if (g.wCell > kWCell || g.hCell > kWCell) valid = 0;          // k_fast_cells handles the level
-                else if (skip || cw <= 0 || ch <= 0) valid = 2;
+                if (g.wCell > kWCell || g.hCell > kWCell) { valid = 0; h->plan.big_cell[l] = 1; }   // k_fast_cells handles the level
+                else if (skip || cw <= 0 || ch <= 0) { valid = 2; h->plan.skipped_cells[l]++; }
                 if (iniX > 0xFFFF || iniY > 0xFFFF || g.img_off > 0xFFFFFFFFll) { set_error("oslam_orb_create: image too large for the FAST cell records"); oslam_orb_destroy(h); return OSLAM_E_INVALID; }
                 r.xy = (uint32_t)iniX | ((uint32_t)iniY << 16);
                 r.dims = (uint32_t)(valid == 1 ? cw : 0) | ((uint32_t)(valid == 1 ? ch : 0) << 8) | ((uint32_t)l << 16) | ((uint32_t)valid << 24);
@@ -575,6 +576,13 @@ static int launch_batch(oslam_orb* h, const uint8_t* d_gray, int batch, int stri
         if (rc) return rc;
     }
     h->ctx = c; h->last_batch = batch; h->last_stream = st;
+    oslam_orb_plan_t& plan = h->plan;   // the per-launch part of the record starts empty; issue() fills one half per call
+    plan.nlevels = P.nlevels; plan.batch = batch; plan.n_halves = 0;
+    for (int i = 0; i < 2; i++) {
+        plan.half_nb[i] = plan.half_kpw[i] = plan.half_oct_nodes_hbm[i] = plan.half_big_cell_kernel[i] = 0;
+        plan.half_src_aligned4[i] = plan.half_src_aligned16[i] = -1;
+        for (int l = 0; l < OSLAM_MAX_LEVELS; l++) plan.half_resize[i][l] = OSLAM_ORB_RESIZE_NONE;
+    }
     // One sub-batch = the whole kernel sequence for images [b0, b0 + nb) on a (main, blur) stream pair.  The blur needs only the pyramid and
     // so do FAST + quad-tree: the blur goes to the pair's second stream and overlaps the (VALU-bound) FAST kernel and the
     // (barrier-latency-bound) quad-tree kernel.  Large batches are cut in two halves on two stream pairs so that the kernels of one half
@@ -582,6 +590,8 @@ static int launch_batch(oslam_orb* h, const uint8_t* d_gray, int batch, int stri
     auto issue = [&](const OrbCtx& cs, int nb, hipStream_t sm, hipStream_t sb, hipStream_t f0, hipEvent_t fork, hipEvent_t join, bool pr) -> int {
 #define PROF_MARK(i) do { if (pr) OSLAM_HIP_CHECK(hipEventRecord(h->ev[i], sm)); } while (0)
         if (pr) h->prof_fast0 = false;
+        const int hi = plan.n_halves++;   // this call's slot of the plan record
+        plan.half_nb[hi] = nb;
         PROF_MARK(0);
         // level 0's FAST cells need only the caller's image: they run on their own stream beside the (HBM / latency bound) pyramid kernels
         const int cells0 = (f0 && P.nlevels > 1) ? P.lv[1].cell_base : 0;
@@ -601,10 +611,17 @@ static int launch_batch(oslam_orb* h, const uint8_t* d_gray, int batch, int stri
             const bool src_aligned = l > 1 || (((stride & 3) == 0) && ((((uintptr_t)cs.img0) & 3) == 0) && ((image_stride & 3) == 0));
             // source rows 16-byte aligned (LDS-staged variant)?
             const bool src_aligned16 = l > 1 || (((stride & 15) == 0) && ((((uintptr_t)cs.img0) & 15) == 0) && ((image_stride & 15) == 0));
-            if (g.qtab_off >= 0 && g.lds_tile_ok && src_aligned16 && !h->no_lds_resize)
+            if (l == 1) { plan.half_src_aligned4[hi] = src_aligned; plan.half_src_aligned16[hi] = src_aligned16; }
+            if (g.qtab_off >= 0 && g.lds_tile_ok && src_aligned16 && !h->no_lds_resize) {
+                plan.half_resize[hi][l] = OSLAM_ORB_RESIZE_LDS;
                 hipLaunchKernelGGL(k_resize_lds, dim3(div_up(g.w, kRzTW), div_up(g.h, kRzTH), nb), dim3(256), 0, sm, cs, l);
-            else if (g.qtab_off >= 0 && src_aligned) hipLaunchKernelGGL(k_resize_words, gridw, dim3(256), 0, sm, cs, l);
-            else hipLaunchKernelGGL(k_resize, grid, dim3(256), 0, sm, cs, l);
+            } else if (g.qtab_off >= 0 && src_aligned) {
+                plan.half_resize[hi][l] = OSLAM_ORB_RESIZE_WORDS;
+                hipLaunchKernelGGL(k_resize_words, gridw, dim3(256), 0, sm, cs, l);
+            } else {
+                plan.half_resize[hi][l] = OSLAM_ORB_RESIZE_PLAIN;
+                hipLaunchKernelGGL(k_resize, grid, dim3(256), 0, sm, cs, l);
+            }
         }
         PROF_MARK(1);
         const bool overlap = sb != sm;
@@ -615,14 +632,19 @@ static int launch_batch(oslam_orb* h, const uint8_t* d_gray, int batch, int stri
         hipLaunchKernelGGL(k_fast_cells_wave, dim3(div_up(P.total_cells - cells0, 4 * kFastCellsPerWave), nb), dim3(256), 0, sm, cs, cells0, P.total_cells);
         if (cells0 > 0) OSLAM_HIP_CHECK(hipStreamWaitEvent(sm, h->ev_join0, 0));
         if (getenv("OSLAM_ORB_DEBUG_OVF")) { int n = 0; (void)hipStreamSynchronize(sm); (void)hipMemcpy(&n, cs.ovf_count, 4, hipMemcpyDeviceToHost); fprintf(stderr, "fast overflow cells since creation: %d (this batch has %d cells)\n", n, P.total_cells * nb); }
-        if (P.any_big_cell) hipLaunchKernelGGL(k_fast_cells, dim3(P.total_cells, nb), dim3(256), 0, sm, cs);
+        if (P.any_big_cell) {
+            plan.half_big_cell_kernel[hi] = 1;
+            hipLaunchKernelGGL(k_fast_cells, dim3(P.total_cells, nb), dim3(256), 0, sm, cs);
+        }
         PROF_MARK(2);
         if (pr) OSLAM_HIP_CHECK(hipEventRecord(h->ev[6], sb));
         hipLaunchKernelGGL(k_blur_strip<false>, dim3(P.blur_block_base[P.nlevels], nb), dim3(256), 0, sb, cs, h->blur_sse2);
         hipLaunchKernelGGL(k_blur_strip<true>, dim3(P.blurb_block_base[P.nlevels], nb), dim3(256), 0, sb, cs, h->blur_sse2);
         if (pr) OSLAM_HIP_CHECK(hipEventRecord(h->ev[7], sb));
-        if (cs.oct_nodes) hipLaunchKernelGGL(k_octree_hbm, dim3(P.nlevels, nb), dim3(kOctThreads), h->oct_lds, sm, cs);
-        else {
+        if (cs.oct_nodes) {
+            plan.half_oct_nodes_hbm[hi] = 1;
+            hipLaunchKernelGGL(k_octree_hbm, dim3(P.nlevels, nb), dim3(kOctThreads), h->oct_lds, sm, cs);
+        } else {
             hipLaunchKernelGGL(k_octree, dim3(P.nlevels, nb), dim3(kOctThreads), h->oct_lds, sm, cs);
             hipLaunchKernelGGL(k_octree_spill, dim3(P.nlevels, nb), dim3(kOctThreads), h->oct_lds, sm, cs);
         }
@@ -634,6 +656,7 @@ static int launch_batch(oslam_orb* h, const uint8_t* d_gray, int batch, int stri
         PROF_MARK(4);
         {
             const int kpw = nb >= 32 ? 16 : (nb >= 8 ? 4 : 1);
+            plan.half_kpw[hi] = kpw;
             hipLaunchKernelGGL(k_orient_describe, dim3(div_up(P.out_cap, 4 * kpw), nb), dim3(256), 0, sm, cs, kpw);
         }
         PROF_MARK(5);
@@ -833,6 +856,12 @@ int oslam_orb_debug_get_level_keys(oslam_orb_t* h, int b, int level, int32_t* ou
     std::vector<uint32_t> ent(std::max(n, 1));
     OSLAM_HIP_CHECK(hipMemcpy(ent.data(), h->d_sel.as<uint32_t>() + (size_t)b * h->P.sel_per_image + g.sel_base, (size_t)n * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) { out[3 * i] = ent_x(ent[i]); out[3 * i + 1] = ent_y(ent[i]); out[3 * i + 2] = ent_s(ent[i]); }
+    return OSLAM_OK;
+}
+
+int oslam_orb_debug_get_plan(const oslam_orb_t* h, oslam_orb_plan_t* out) {
+    if (!h || !out) { set_error("NULL argument"); return OSLAM_E_INVALID; }
+    *out = h->plan;
     return OSLAM_OK;
 }
 

@@ -8,6 +8,18 @@ from . import _lib
 from ._lib import KP_DTYPE, check, ptr
 
 
+MAX_LEVELS = 16   # OSLAM_MAX_LEVELS
+RESIZE_NONE, RESIZE_PLAIN, RESIZE_WORDS, RESIZE_LDS = 0, 1, 2, 3   # OSLAM_ORB_RESIZE_*
+
+
+class OrbPlan(C.Structure):
+    """oslam_orb_plan_t (include/oslam_hip.h): the kernel variants the last batch launched."""
+    _fields_ = [("nlevels", C.c_int32), ("batch", C.c_int32), ("n_halves", C.c_int32), ("half_nb", C.c_int32 * 2), ("half_kpw", C.c_int32 * 2),
+                ("half_src_aligned4", C.c_int32 * 2), ("half_src_aligned16", C.c_int32 * 2), ("half_oct_nodes_hbm", C.c_int32 * 2),
+                ("half_big_cell_kernel", C.c_int32 * 2), ("half_resize", (C.c_int32 * MAX_LEVELS) * 2), ("big_cell", C.c_int32 * MAX_LEVELS),
+                ("skipped_cells", C.c_int32 * MAX_LEVELS)]
+
+
 class ORBextractor:
     def __init__(self, nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height,
                  max_batch=1, device=0):
@@ -118,6 +130,19 @@ class ORBextractor:
         n = C.c_int(0)
         check(self.L.oslam_orb_debug_get_level_keys(self.h, b, level, ptr(out), cap, C.byref(n)))
         return out[:n.value].copy()
+
+    def debug_plan(self):
+        """What the last batch launched, as plain Python values: per issued half (one, or two when the batch was cut) the images `nb`, `kpw` of
+        k_orient_describe, the level-0 alignment flags (None with a single level), `oct_nodes_hbm`, `big_cell_kernel` and `resize` (RESIZE_* per
+        level, level 0 = RESIZE_NONE); per level `big_cell` and `skipped_cells`."""
+        p = OrbPlan()
+        check(self.L.oslam_orb_debug_get_plan(self.h, C.byref(p)))
+        n = p.nlevels if p.n_halves else self.nlevels
+        al = lambda v: None if v < 0 else bool(v)
+        halves = [dict(nb=p.half_nb[i], kpw=p.half_kpw[i], src_aligned4=al(p.half_src_aligned4[i]), src_aligned16=al(p.half_src_aligned16[i]),
+                       oct_nodes_hbm=bool(p.half_oct_nodes_hbm[i]), big_cell_kernel=bool(p.half_big_cell_kernel[i]),
+                       resize=list(p.half_resize[i][:n])) for i in range(p.n_halves)]
+        return dict(batch=p.batch, halves=halves, big_cell=[bool(v) for v in p.big_cell[:n]], skipped_cells=list(p.skipped_cells[:n]))
 
     def algorithmic_bytes(self, n_keypoints):
         return int(self.L.oslam_orb_algorithmic_bytes(self.h, n_keypoints))

@@ -56,13 +56,13 @@ def test_ctypes_mirrors_have_the_sizes_of_the_headers(tmp_path):
     buffer: the suite crashed or not depending on the order of its tests).  gcc prints the sizes of the headers; the library reports its own (oslam_slam_struct_sizes)."""
     import ctypes as C
     import subprocess
-    from object_slam_amd import mappoint, matcher, optimizer, slam
+    from object_slam_amd import extractor, mappoint, matcher, optimizer, slam
     from object_slam_amd._lib import lib
     pairs = [("oslam_slam_config_t", slam.SlamConfig), ("oslam_slam_ops_t", slam.SlamOps), ("oslam_slam_objects_t", slam.SlamObjects),
              ("oslam_tri_kf_t", mappoint.TriKF), ("oslam_camera_t", matcher.Camera), ("oslam_match_frames_t", matcher.MatchFrames),
              ("oslam_match_last_t", matcher.MatchLast), ("oslam_bow_side1_t", matcher.BowSide1), ("oslam_bow_side2_t", matcher.BowSide2),
              ("oslam_bow_job_t", matcher.BowJob), ("oslam_bow_resident_t", matcher.BowResident),
-             ("oslam_semantic_t", optimizer.Semantic), ("oslam_lba_problem_t", optimizer.LbaProblem)]
+             ("oslam_semantic_t", optimizer.Semantic), ("oslam_lba_problem_t", optimizer.LbaProblem), ("oslam_orb_plan_t", extractor.OrbPlan)]
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     src = tmp_path / "sizes.c"
     src.write_text('#include <stdio.h>\n#include "oslam_hip.h"\n#include "oslam_slam.h"\nint main(void) {\n'

@@ -4,43 +4,13 @@ survivors (order), keypoints (all 7 fields) and descriptors."""
 import numpy as np
 import pytest
 
+from extractor_common import _stages
 from object_slam_amd import ORBextractor, synth
 
 pytestmark = pytest.mark.gpu
 
 TUM = dict(nfeatures=1000, scaleFactor=1.2, nlevels=8, iniThFAST=20, minThFAST=7)
 KITTI = dict(nfeatures=2000, scaleFactor=1.2, nlevels=8, iniThFAST=20, minThFAST=7)
-
-
-def _stages(oracle, cfg, img):
-    h, w = img.shape
-    ex = ORBextractor(width=w, height=h, **cfg)
-    oe = oracle.OrbExtractor(cfg["nfeatures"], cfg["scaleFactor"], cfg["nlevels"], cfg["iniThFAST"], cfg["minThFAST"])
-    kps, desc = ex(img)
-    okps, odesc = oe.extract(img)
-    for l in range(cfg["nlevels"]):
-        assert ex.level_size(l) == oe.level_size(l)
-        np.testing.assert_array_equal(ex.pyramid_level(l), oe.level(l), err_msg="pyramid level %d" % l)
-        cand = ex.debug_candidates(l)
-        oc = oe.candidates(l)
-        assert len(cand) == len(oc), "level %d: %d vs %d candidates" % (l, len(cand), len(oc))
-        np.testing.assert_array_equal(cand[:, 0], oc["x"].astype(np.int32))
-        np.testing.assert_array_equal(cand[:, 1], oc["y"].astype(np.int32))
-        np.testing.assert_array_equal(cand[:, 2], oc["response"].astype(np.int32))
-        keys = ex.debug_level_keys(l)
-        ok = oe.level_keys(l)
-        assert len(keys) == len(ok), "level %d: %d vs %d survivors" % (l, len(keys), len(ok))
-        np.testing.assert_array_equal(keys[:, 0], ok["x"].astype(np.int32))
-        np.testing.assert_array_equal(keys[:, 1], ok["y"].astype(np.int32))
-        ob = oe.blurred(l)
-        if ob is not None:
-            np.testing.assert_array_equal(ex.debug_blurred(l), ob, err_msg="blur level %d" % l)
-    assert len(kps) == len(okps)
-    for f in ("x", "y", "size", "angle", "response", "octave", "class_id"):
-        np.testing.assert_array_equal(kps[f], okps[f], err_msg=f)
-    np.testing.assert_array_equal(desc, odesc)
-    ex.close()
-    return len(kps)
 
 
 def test_tum_shape_stage_parity(oracle):
