@@ -2,7 +2,7 @@
 // ORB_SLAM2::ORBextractor (include/ORBextractor.h:45-110), ORB_SLAM2::ORBmatcher (include/ORBmatcher.h:41-83: both projection searches,
 // SearchByBoW, SearchForTriangulation, Fuse, DescriptorDistance), Frame::ComputeStereoMatches (src/Frame.cc:706), ORB_SLAM2::Optimizer
 // (include/Optimizer.h:38-46: PoseOptimization, LocalBundleAdjustment, BundleAdjustment) and ObjectOptimizer::PoseOptimization2
-// (include/ObjectOptimizer.h:23), ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: loadFromTextFile, transform, score) and ORB_SLAM2::PnPsolver (include/PnPsolver.h: SetRansacParameters, iterate, find).  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
+// (include/ObjectOptimizer.h:23), ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: loadFromTextFile, transform, score) ORB_SLAM2::PnPsolver (include/PnPsolver.h: SetRansacParameters, iterate, find) and ORB_SLAM2::Sim3Solver (include/Sim3Solver.h: SetRansacParameters, iterate, find, GetEstimatedRotation / Translation / Scale).  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
 // "view" of exactly the members it reads and writes (the gather loops are in INTEGRATION.md).  tests/adapter_program.cc uses nothing but
 // these classes; tests/test_adapter_gpu.py builds it, runs it and compares its outputs with the ctypes path.
 //
@@ -539,6 +539,113 @@ private:
     oslam_pnp_params_t prm_;
     oslam_pnp_t* h_ = nullptr;
     bool done_ = false;
+};
+
+// Flat views of what Sim3Solver::Sim3Solver(KeyFrame*, KeyFrame*, const vector<MapPoint*>&, bool) reads (src/Sim3Solver.cc:37-112)
+struct Sim3KeyFrameView {
+    int N;                                // mvKeysUn.size()
+    const oslam::KeyPoint* mvKeysUn;
+    const float* mvLevelSigma2; int nLevels;
+    float fx, fy, cx, cy;                 // mK
+    float Rcw[9], tcw[3];                 // GetRotation() (row-major), GetTranslation()
+};
+struct Sim3MatchView {                    // one entry per keypoint of KF1 (mN1 = vpMatched12.size())
+    int N1;
+    const uint8_t* matched;               // vpMatched12[i1] != NULL
+    const uint8_t* has_mp1;               // pKF1->GetMapPointMatches()[i1] != NULL (may be NULL: every keypoint has one)
+    const uint8_t* bad1; const uint8_t* bad2;   // pMP1->isBad(), pMP2->isBad() (may be NULL: none is bad)
+    const int32_t* indexKF1; const int32_t* indexKF2;   // pMP1->GetIndexInKeyFrame(pKF1), pMP2->GetIndexInKeyFrame(pKF2)
+    const float* Xw1; const float* Xw2;   // [N1][3] GetWorldPos() of both points
+};
+
+// ORB_SLAM2::Sim3Solver (include/Sim3Solver.h:38-62).  The reference returns the transform as a cv::Mat that is empty when there is none; here iterate /
+// find return whether there is one and write it to T12 (4 x 4 row-major float).  The class keeps the state record of the operator (oslam_hip.h, "Sim3
+// solver"), so repeated calls resume as the reference's do.  `seed` stands for the clock-seeded DUtils::Random of the reference.
+class Sim3Solver {
+public:
+    Sim3Solver(const Sim3KeyFrameView& KF1, const Sim3KeyFrameView& KF2, const Sim3MatchView& M, bool bFixScale = true, uint32_t seed = 0) : mN1(M.N1), seed_(seed), fix_(bFixScale) {
+        K_[0] = KF1.fx; K_[1] = KF1.fy; K_[2] = KF1.cx; K_[3] = KF1.cy; K_[4] = KF2.fx; K_[5] = KF2.fy; K_[6] = KF2.cx; K_[7] = KF2.cy;
+        for (int i1 = 0; i1 < mN1; i1++) {   // :62-103
+            if (!M.matched[i1]) continue;
+            if (M.has_mp1 && !M.has_mp1[i1]) continue;
+            if ((M.bad1 && M.bad1[i1]) || (M.bad2 && M.bad2[i1])) continue;
+            const int indexKF1 = M.indexKF1[i1], indexKF2 = M.indexKF2[i1];
+            if (indexKF1 < 0 || indexKF2 < 0) continue;
+            if (indexKF1 >= KF1.N || indexKF2 >= KF2.N) throw std::runtime_error("Sim3Solver: keypoint index outside mvKeysUn");
+            const int o1 = KF1.mvKeysUn[indexKF1].octave, o2 = KF2.mvKeysUn[indexKF2].octave;
+            if (o1 < 0 || o1 >= KF1.nLevels || o2 < 0 || o2 >= KF2.nLevels) throw std::runtime_error("Sim3Solver: keypoint octave outside mvLevelSigma2");
+            mvSigma2_1.push_back(KF1.mvLevelSigma2[o1]);
+            mvSigma2_2.push_back(KF2.mvLevelSigma2[o2]);
+            mvnIndices1.push_back((size_t)i1);
+            to_camera(KF1, M.Xw1 + 3 * (size_t)i1, mvX3Dc1);   // Rcw1 * X3D1w + tcw1 (:94-98)
+            to_camera(KF2, M.Xw2 + 3 * (size_t)i1, mvX3Dc2);
+        }
+        SetRansacParameters();
+        reset_state();
+    }
+    ~Sim3Solver() { oslam_sim3_destroy(h_); }
+    Sim3Solver(const Sim3Solver&) = delete;
+    Sim3Solver& operator=(const Sim3Solver&) = delete;
+
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+        if (h_ && maxIterations > prm_.max_iterations) { oslam_sim3_destroy(h_); h_ = nullptr; }   // (the handle's arena is sized by maxIterations)
+        prm_.probability = probability; prm_.min_inliers = minInliers; prm_.max_iterations = maxIterations;
+        st_.iterations_done = 0;   // mnIterations = 0 (:137); mnBestInliers and the best transform stay
+    }
+    // mRansacMaxIts as SetRansacParameters leaves it (:135), and whether iterate() gives up at once
+    oslam_sim3_ransac_t Adjusted() const {
+        oslam_sim3_ransac_t r;
+        oslam::throw_on(oslam_sim3_ransac_params((int)mvSigma2_1.size(), prm_.probability, prm_.min_inliers, prm_.max_iterations, &r));
+        return r;
+    }
+    bool find(std::vector<bool>& vbInliers12, int& nInliers, float T12[16]) {
+        bool bFlag;
+        return iterate(Adjusted().iterations, bFlag, vbInliers12, nInliers, T12);
+    }
+    // vbInliers has mN1 entries and is indexed by keypoint of KF1 (:143, :195-197)
+    bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, float T12[16]) {
+        bNoMore = false;
+        vbInliers.assign((size_t)mN1, false);
+        nInliers = 0;
+        const int N = (int)mvSigma2_1.size();
+        if (N == 0) { bNoMore = true; return false; }   // (N < mRansacMinInliers, or nothing to draw from)
+        if (!h_) oslam::throw_on(oslam_sim3_create(&h_, 1, N, prm_.max_iterations));
+        oslam_sim3_problem_t pr;
+        pr.count = N; pr.offset = 0; pr.fx1 = K_[0]; pr.fy1 = K_[1]; pr.cx1 = K_[2]; pr.cy1 = K_[3]; pr.fx2 = K_[4]; pr.fy2 = K_[5]; pr.cx2 = K_[6]; pr.cy2 = K_[7];
+        pr.seed = seed_; pr.fix_scale = fix_ ? 1 : 0;
+        std::vector<uint8_t> flags((size_t)N, 0);
+        int32_t st[4] = {0, 0, 0, 0};
+        oslam::throw_on(oslam_sim3_iterate_batch(h_, 1, &pr, &st_, N, mvX3Dc1.data(), mvX3Dc2.data(), mvSigma2_1.data(), mvSigma2_2.data(), &prm_, nIterations < 0 ? 0 : nIterations,
+                                                 nullptr, T12, flags.data(), st, nullptr, nullptr));
+        bNoMore = st[3] != 0;
+        if (st[0] != 1) return false;
+        nInliers = st[1];
+        for (int i = 0; i < N; i++)
+            if (flags[i]) vbInliers[mvnIndices1[i]] = true;
+        return true;
+    }
+    // GetEstimatedRotation (3 x 3 row-major) / Translation / Scale of the best hypothesis so far (:367-380)
+    void GetEstimatedRotation(float R[9]) const { memcpy(R, st_.R, sizeof(st_.R)); }
+    void GetEstimatedTranslation(float t[3]) const { memcpy(t, st_.t, sizeof(st_.t)); }
+    float GetEstimatedScale() const { return st_.s; }
+    int mnIterations() const { return st_.iterations_done; }
+    int mnBestInliers() const { return st_.best_inliers; }
+
+    int mN1;
+    std::vector<float> mvX3Dc1, mvX3Dc2, mvSigma2_1, mvSigma2_2;   // the filtered correspondences (:84-98), packed
+    std::vector<size_t> mvnIndices1;
+
+private:
+    static void to_camera(const Sim3KeyFrameView& KF, const float* Xw, std::vector<float>& out) {   // float, sums from left to right
+        for (int i = 0; i < 3; i++) out.push_back(((KF.Rcw[3 * i] * Xw[0] + KF.Rcw[3 * i + 1] * Xw[1]) + KF.Rcw[3 * i + 2] * Xw[2]) + KF.tcw[i]);
+    }
+    void reset_state() { memset(&st_, 0, sizeof(st_)); st_.best_iteration = -1; }
+    uint32_t seed_;
+    bool fix_;
+    float K_[8];
+    oslam_sim3_params_t prm_;
+    oslam_sim3_state_t st_;
+    oslam_sim3_t* h_ = nullptr;
 };
 
 }  // namespace ORB_SLAM2

@@ -803,6 +803,90 @@ int oslam_pnp_ransac_batch_device(oslam_pnp_t* h, int n_problems, const oslam_pn
 int oslam_pnp_epnp(oslam_pnp_t* h, int n_sets, const int32_t* counts, const int32_t* offsets, int n_corr, const float* P3Dw, const float* P2D, const float K4[4], double* R,
                    double* t, double* err);
 
+/* ------------------------------------------------------------------------------------------
+ * Sim3 solver — ORB_SLAM2::Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc: Horn's closed form inside RANSAC), the numerical operator of
+ * LoopClosing::ComputeSim3 (src/LoopClosing.cc:232-343), for batches of independent problems (one per loop candidate of every sequence): one round of
+ * ComputeSim3's while loop — iterate(5) of every live solver — is one call.  The driver does not close loops and does not call it.  Out of scope:
+ * ORBmatcher::SearchBySim3, and Optimizer::OptimizeSim3 (its g2o Sim3 vertex and edge types are not in the reference tree).
+ *
+ * A problem is `count` correspondences at `offset` of the packed arrays — X3Dc1, X3Dc2 (the two map points in the frames of their own cameras,
+ * :94-98) and sigma2_1, sigma2_2 (mvLevelSigma2[octave] of the two keypoints, :84-85), all float — the intrinsics of both cameras (mK1, mK2), a seed
+ * and bFixScale.  Problems of one call must not share correspondences.  The operator derives mvP1im1 / mvP2im2 (FromCameraToImage, :405-423) and the
+ * thresholds itself: mvnMaxError1/2 are std::vector<size_t> (Sim3Solver.h:78-79), so the double product 9.210 * sigmaSquare is TRUNCATED when pushed
+ * (:87-88: 9 for sigma2 = 1, 13 for 1.44) and CheckInliers compares the float error with that integer converted to float, strictly, on both sides
+ * (:356).  A sigma2 <= 0 gives the threshold 0.
+ * SetRansacParameters (:114-138): epsilon = (float)minInliers / N, nIterations = ceil(log(1 - p) / log(1 - pow(epsilon, 3))) in double, 1 when
+ * minInliers == N, clamped to [1, maxIterations] (oslam_sim3_ransac_params).  The constructor's call is (0.99, 6, 300), LoopClosing's (0.99, 20, 300).
+ * iterate(nIterations) (:140-207) is incremental — its loop condition is `mnIterations < mRansacMaxIts && nCurrentIterations < nIterations` — and the
+ * solver keeps mnIterations, mnBestInliers and the best transform between calls: that is the state record, input and output of every call.  N <
+ * minInliers gives bNoMore at once.  Per iteration: three indices by the swap-with-back rule (:163-177), ComputeSim3 (:226-337: centroids, M = Pr2
+ * Pr1^T, the 4 x 4 matrix N, the eigenvector of its largest eigenvalue as a quaternion, angle-axis, Rodrigues, the scale Pr1 . P3 / sum P3^2 or 1
+ * with bFixScale, t = O1 - s R O2, T12 = [sR | t], T21 = [(1 / s) R^T | -(1 / s) R^T t], everything stored as CV_32F), CheckInliers / Project
+ * (:340-403, all float: invz = 1 / z, fx * x + cx).  A count >= mnBestInliers (not strict) becomes the best; if it is also > mRansacMinInliers
+ * (strict) the call returns mBestT12 at once with the inlier flags, and bNoMore stays false even on the last iteration.  After the loop bNoMore =
+ * mnIterations >= mRansacMaxIts.  A later call resumes where the last one stopped.
+ *
+ * Normalisations:
+ *  1. The generator: as normalisation 1 of the PnP solver, with three draws (`samples`: three distinct correspondence indices of the problem; anything
+ *     else makes that hypothesis count zero and never the best).  oslam_sim3_draw evaluates it on the host.
+ *  2. cv::eigen on the float matrix N is a cyclic Jacobi in fp64 here.  Horn is computed in fp64 from the float inputs; R, then s (from the rounded R),
+ *     then t (from the rounded R and s) are rounded to float where the reference stores CV_32F, and T12, T21 and the projections are formed in
+ *     float, one rounding per operator, sums from left to right.  The sign of the eigenvector does not matter: q and -q give the same rotation through
+ *     the atan2 / Rodrigues route.  A hypothesis is undetermined when the two largest eigenvalues of N coincide (a collinear or coincident sample).
+ *  3. A hypothesis whose R, t or s is not finite counts zero inliers and never becomes the best (in the reference a zero count can become the best
+ *     while mnBestInliers is 0; a finite hypothesis with a zero count still can).
+ *  4. Input validation: a problem with a coordinate, sigma2 or intrinsic that is not finite gets no_more with 0 iterations; so does N < 3, where the
+ *     reference would draw from an empty list.
+ *  5. log and pow of the iteration count are the device's in the kernels and the host's in oslam_sim3_ransac_params.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct oslam_sim3 oslam_sim3_t;
+typedef struct oslam_sim3_params {   /* the arguments of SetRansacParameters (:114) */
+    double probability;
+    int32_t min_inliers, max_iterations;
+} oslam_sim3_params_t;
+typedef struct oslam_sim3_problem {
+    int32_t count, offset;   /* correspondences offset .. offset + count - 1 of the packed arrays */
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;   /* mK1, mK2 */
+    uint32_t seed;
+    int32_t fix_scale;       /* bFixScale */
+} oslam_sim3_problem_t;
+typedef struct oslam_sim3_state {   /* what a solver keeps between iterate() calls; zeroed with best_iteration = -1 = a fresh solver */
+    int32_t iterations_done;        /* mnIterations */
+    int32_t best_inliers;           /* mnBestInliers */
+    int32_t best_iteration;         /* the iteration that gave the best, or -1 */
+    float R[9], t[3], s;            /* GetEstimatedRotation (row-major) / Translation / Scale */
+} oslam_sim3_state_t;
+typedef struct oslam_sim3_ransac {
+    int32_t iterations;   /* mRansacMaxIts as SetRansacParameters leaves it; 0 when no_more */
+    int32_t no_more;      /* N < min_inliers (:146-150) or N < 3 (normalisation 4) */
+} oslam_sim3_ransac_t;
+/* Host only, needs no device. */
+int oslam_sim3_ransac_params(int N, double probability, int min_inliers, int max_iterations, oslam_sim3_ransac_t* out);
+/* The three indices iteration `iteration` of a problem with N >= 3 correspondences draws from `seed` (normalisation 1).  Host only. */
+int oslam_sim3_draw(uint32_t seed, int iteration, int N, int32_t idx[3]);
+/* max_iterations bounds params.max_iterations of the calls (the work arena holds one hypothesis per problem and iteration).  OSLAM_E_HIP without a device. */
+int oslam_sim3_create(oslam_sim3_t** out, int max_problems, int max_correspondences_total, int max_iterations);
+void oslam_sim3_destroy(oslam_sim3_t* h);
+/* iterate(n_iterations) of every problem.  Host pointers; one upload, two launches, one download, synchronous.  X3Dc1, X3Dc2 [n_corr][3], sigma2_1,
+ * sigma2_2 [n_corr]; states [n_problems], read and always written; samples NULL or [n_problems][params.max_iterations][3] int32, indexed by absolute
+ * iteration.  Iterations iterations_done .. min(iterations_done + n_iterations, iterations) - 1 are evaluated and iterate()'s control flow is applied
+ * in order.  status [n_problems][4] int32 = returned (1: there is a Sim3), nInliers, iterations run in this call, no_more.  On a return T12
+ * [n_problems][16] float (row-major 4 x 4) and the problem's bytes of inliers [n_corr] (by correspondence) are written; otherwise the caller's bytes
+ * are left as they are.  iter_inliers NULL or [n_problems][params.max_iterations] int32: the CheckInliers counts of the iterations run in this call
+ * (up to a returning one), untouched elsewhere; hypotheses NULL or [n_problems][params.max_iterations][13] float: R (row-major), t, s of those
+ * iterations.  OSLAM_E_CAPACITY, before anything is launched, for more problems, correspondences or iterations (params.max_iterations) than the
+ * handle was created for; OSLAM_E_INVALID for min_inliers < 0 or n_iterations < 0. */
+int oslam_sim3_iterate_batch(oslam_sim3_t* h, int n_problems, const oslam_sim3_problem_t* problems, oslam_sim3_state_t* states, int n_corr, const float* X3Dc1,
+                             const float* X3Dc2, const float* sigma2_1, const float* sigma2_2, const oslam_sim3_params_t* params, int n_iterations, const int32_t* samples,
+                             float* T12, uint8_t* inliers, int32_t* status, int32_t* iter_inliers, float* hypotheses);
+/* The same over device arrays (problem and state records included; `params` is a host pointer), asynchronous on `stream`, no host synchronisation.
+ * A problem record that does not lie inside the n_corr correspondences, or a state record with iterations_done < 0, gets returned = -1 and nothing
+ * else is written for it. */
+int oslam_sim3_iterate_batch_device(oslam_sim3_t* h, int n_problems, const oslam_sim3_problem_t* d_problems, oslam_sim3_state_t* d_states, int n_corr, const float* d_X3Dc1,
+                                    const float* d_X3Dc2, const float* d_sigma2_1, const float* d_sigma2_2, const oslam_sim3_params_t* params, int n_iterations,
+                                    const int32_t* d_samples, float* d_T12, uint8_t* d_inliers, int32_t* d_status, int32_t* d_iter_inliers, float* d_hypotheses,
+                                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

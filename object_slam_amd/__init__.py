@@ -12,3 +12,5 @@ from .optimizer import LocalBundleAdjuster, PoseOptimizer  # noqa: F401
 from .vocabulary import Vocabulary  # noqa: F401
 from .pnp import PnPsolver  # noqa: F401
 from . import pnp  # noqa: F401
+from .sim3 import Sim3Solver  # noqa: F401
+from . import sim3  # noqa: F401

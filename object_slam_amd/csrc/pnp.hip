@@ -10,6 +10,7 @@
 
 #include "common.h"
 #include "lane_ops.h"
+#include "ransac_draw.h"   // the counter-based generator and the draw rule, shared with sim3.hip
 
 using oslam::set_error;
 
@@ -49,29 +50,6 @@ __host__ __device__ inline RansacAdj ransac_adjust(int N, double probability, in
     if (nIterations > maxIterations) nIterations = maxIterations;
     r.iterations = nIterations < 1 ? 1 : nIterations;
     return r;
-}
-
-// The counter-based generator of include/oslam_hip.h: a 32-bit hash of (seed, iteration, draw).
-__host__ __device__ inline uint32_t pnp_mix(uint32_t x) {
-    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-    return x;
-}
-__host__ __device__ inline uint32_t pnp_hash(uint32_t seed, int iteration, int draw) {
-    return pnp_mix(pnp_mix(seed + 0x9E3779B9u * (uint32_t)(iteration + 1)) ^ (0x85EBCA6Bu * (uint32_t)(draw + 1)));
-}
-// Four indices without replacement by the swap-with-back rule of :188-201, without the list: position p of the list holds p unless an earlier draw moved
-// the back element there.
-__host__ __device__ inline void pnp_draw4(uint32_t seed, int iteration, int N, int idx[4]) {
-    int pos[4], val[4];
-    for (int k = 0; k < 4; k++) {
-        const int size = N - k;
-        const int randi = (int)(((uint64_t)pnp_hash(seed, iteration, k) * (uint64_t)size) >> 32);
-        int at = randi, back = size - 1;
-        for (int j = k - 1; j >= 0; j--) if (pos[j] == randi) { at = val[j]; break; }
-        for (int j = k - 1; j >= 0; j--) if (pos[j] == size - 1) { back = val[j]; break; }
-        idx[k] = at;
-        pos[k] = randi; val[k] = back;
-    }
 }
 
 struct PnpPts {
@@ -614,7 +592,7 @@ __global__ __launch_bounds__(kG* kHypPerBlock) void k_pnp_hypotheses(PnpArgs a) 
         for (int k = 0; k < 4; k++) { idx[k] = s[k]; ok = ok && idx[k] >= 0 && idx[k] < pr.count; }
         ok = ok && idx[0] != idx[1] && idx[0] != idx[2] && idx[0] != idx[3] && idx[1] != idx[2] && idx[1] != idx[3] && idx[2] != idx[3];
     } else {
-        pnp_draw4(pr.seed, it, pr.count, idx);
+        oslam::ransac_draw<4>(pr.seed, it, pr.count, idx);
     }
     if (c < 4) s_sel[g][c] = ok ? idx[c] : c;   // (count >= min_inliers >= min_set = 4)
     __syncthreads();
@@ -745,7 +723,7 @@ int oslam_pnp_ransac_params(int N, double probability, int min_inliers, int max_
 int oslam_pnp_draw(uint32_t seed, int iteration, int N, int32_t idx[4]) {
     if (!idx || N < 4 || iteration < 0) { set_error("oslam_pnp_draw: bad argument"); return OSLAM_E_INVALID; }
     int v[4];
-    pnp_draw4(seed, iteration, N, v);
+    oslam::ransac_draw<4>(seed, iteration, N, v);
     for (int k = 0; k < 4; k++) idx[k] = v[k];
     return OSLAM_OK;
 }
