@@ -1,6 +1,6 @@
 // orb_slam2_adapter.hpp — header-only C++ adapter that re-exposes the reference's class API on top of the C ABI in oslam_hip.h:
 // ORB_SLAM2::ORBextractor (include/ORBextractor.h:45-110), ORB_SLAM2::ORBmatcher (include/ORBmatcher.h:41-83: both projection searches,
-// SearchByBoW, SearchForTriangulation, Fuse, DescriptorDistance), Frame::ComputeStereoMatches (src/Frame.cc:706), ORB_SLAM2::Optimizer
+// SearchByBoW, SearchForTriangulation, Fuse, SearchBySim3, DescriptorDistance), Frame::ComputeStereoMatches (src/Frame.cc:706), ORB_SLAM2::Optimizer
 // (include/Optimizer.h:38-46: PoseOptimization, LocalBundleAdjustment, BundleAdjustment) and ObjectOptimizer::PoseOptimization2
 // (include/ObjectOptimizer.h:23), ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: loadFromTextFile, transform, score) ORB_SLAM2::PnPsolver (include/PnPsolver.h: SetRansacParameters, iterate, find) and ORB_SLAM2::Sim3Solver (include/Sim3Solver.h: SetRansacParameters, iterate, find, GetEstimatedRotation / Translation / Scale).  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
 // "view" of exactly the members it reads and writes (the gather loops are in INTEGRATION.md).  tests/adapter_program.cc uses nothing but
@@ -128,6 +128,21 @@ struct FrameView {
     float mnMinX, mnMinY, mnMaxX, mnMaxY;
 };
 
+// Flat view of what ORBmatcher::SearchBySim3 reads of a KeyFrame and of its map points (src/ORBmatcher.cc:1102-1326); one entry per keypoint
+struct Sim3MatchKeyFrameView {
+    int N;                                // mvKeysUn.size() = GetMapPointMatches().size()
+    const oslam::KeyPoint* mvKeysUn;
+    const uint8_t* mDescriptors;          // N x 32
+    const uint8_t* has_mp;                // pMP && !pMP->isBad()
+    const float* Xw;                      // [N][3] pMP->GetWorldPos()
+    const uint8_t* mpDescriptors;         // N x 32 pMP->GetDescriptor()
+    const float* mfMaxDistance; const float* mfMinDistance;   // the members (GetMaxDistanceInvariance() / 1.2f, GetMinDistanceInvariance() / 0.8f is NOT the same float)
+    float Tcw[16];                        // GetPose(), row-major
+    float fx, fy, cx, cy;                 // read of KF1 only (:1105-1108)
+    float mnMinX, mnMinY, mnMaxX, mnMaxY; // the same for both keyframes (one camera)
+    const float* mvScaleFactors; int mnScaleLevels; float mfLogScaleFactor;
+};
+
 class ORBmatcher {
 public:
     static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 30;   // src/ORBmatcher.cc:37-39
@@ -135,7 +150,7 @@ public:
         : mfNNratio(nnratio), mbCheckOrientation(checkOri) {
         oslam::throw_on(oslam_matcher_create(&h_, 1, max_keypoints, max_queries, device));
     }
-    ~ORBmatcher() { oslam_matcher_destroy(h_); oslam_bow_destroy(bow_); }
+    ~ORBmatcher() { oslam_matcher_destroy(h_); oslam_bow_destroy(bow_); oslam_sim3_match_destroy(sim3m_); }
     ORBmatcher(const ORBmatcher&) = delete;
 
     // int SearchByProjection(Frame &F, const vector<MapPoint*> &vpMapPoints, const float th):
@@ -239,6 +254,44 @@ public:
         return nm;
     }
 
+    // int SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12, const float& s12, const cv::Mat& R12, const cv::Mat& t12, const float th)
+    // (:1102-1326).  vpMatches12 [KF1.N]: -1 = NULL, otherwise pMP->GetIndexInKeyFrame(pKF2) of the matched point (-2: matched, not in KF2); where the
+    // reference sets vpMatches12[i1] = vpMapPoints2[idx2] the entry becomes idx2.  R12 3 x 3 row-major.  Returns nFound.
+    int SearchBySim3(const Sim3MatchKeyFrameView& KF1, const Sim3MatchKeyFrameView& KF2, std::vector<int32_t>& vpMatches12, float s12, const float R12[9], const float t12[3],
+                     float th) {
+        if ((int)vpMatches12.size() != KF1.N) throw std::runtime_error("SearchBySim3: vpMatches12 must have one entry per keypoint of KF1");
+        if (!sim3m_) oslam::throw_on(oslam_sim3_match_create(&sim3m_, 1, 2400, 0));
+        const Sim3MatchKeyFrameView* kf[2] = {&KF1, &KF2};
+        const size_t n = (size_t)KF1.N + (size_t)KF2.N;
+        std::vector<oslam_keypoint_t> keys(n);
+        std::vector<uint8_t> desc(n * 32), has(n), mpd(n * 32);
+        std::vector<float> Xw(n * 3), maxD(n), minD(n);
+        size_t at = 0;
+        for (int k = 0; k < 2; k++) {   // rows 0 .. N1 - 1 are KF1's, the rest KF2's
+            const size_t m = (size_t)kf[k]->N;
+            if (m) {
+                memcpy(keys.data() + at, kf[k]->mvKeysUn, m * sizeof(oslam_keypoint_t)); memcpy(desc.data() + at * 32, kf[k]->mDescriptors, m * 32);
+                memcpy(has.data() + at, kf[k]->has_mp, m); memcpy(Xw.data() + at * 3, kf[k]->Xw, m * 12); memcpy(mpd.data() + at * 32, kf[k]->mpDescriptors, m * 32);
+                memcpy(maxD.data() + at, kf[k]->mfMaxDistance, m * 4); memcpy(minD.data() + at, kf[k]->mfMinDistance, m * 4);
+            }
+            at += m;
+        }
+        oslam_sim3_pair_t pr;
+        pr.n1 = KF1.N; pr.off1 = 0; pr.n2 = KF2.N; pr.off2 = KF1.N; pr.out_off = 0; pr.s12 = s12; pr.th = th;
+        memcpy(pr.R12, R12, sizeof(pr.R12)); memcpy(pr.t12, t12, sizeof(pr.t12)); memcpy(pr.T1w, KF1.Tcw, sizeof(pr.T1w)); memcpy(pr.T2w, KF2.Tcw, sizeof(pr.T2w));
+        const oslam_sim3_match_rows_t rows = {(int32_t)n, keys.data(), desc.data(), has.data(), Xw.data(), mpd.data(), maxD.data(), minD.data()};
+        const oslam_camera_t cam = {KF1.fx, KF1.fy, KF1.cx, KF1.cy, 0.f, 0.f};
+        const float bounds[4] = {KF1.mnMinX, KF1.mnMinY, KF1.mnMaxX, KF1.mnMaxY};
+        std::vector<int32_t> match12((size_t)KF1.N + 1, -1);
+        int32_t nFound = 0;
+        oslam::throw_on(oslam_match_search_by_sim3_batch(sim3m_, 1, &pr, &rows, KF1.N, vpMatches12.data(), &cam, bounds, KF1.mvScaleFactors, KF1.mnScaleLevels, KF1.mfLogScaleFactor,
+                                                         match12.data(), &nFound));
+        if (nFound < 0) return 0;   // (a Sim3 or pose that is not finite: nothing matches)
+        for (int i1 = 0; i1 < KF1.N; i1++)
+            if (match12[i1] >= 0) vpMatches12[i1] = match12[i1];
+        return nFound;
+    }
+
     float mfNNratio;
     bool mbCheckOrientation;
 
@@ -246,6 +299,7 @@ private:
     void ensure_bow() { if (!bow_) oslam::throw_on(oslam_bow_create(&bow_, 2400, 0)); }
     oslam_matcher_t* h_ = nullptr;
     oslam_bow_t* bow_ = nullptr;
+    oslam_sim3_match_t* sim3m_ = nullptr;
 };
 
 }  // namespace ORB_SLAM2

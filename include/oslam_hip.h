@@ -806,8 +806,9 @@ int oslam_pnp_epnp(oslam_pnp_t* h, int n_sets, const int32_t* counts, const int3
 /* ------------------------------------------------------------------------------------------
  * Sim3 solver — ORB_SLAM2::Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc: Horn's closed form inside RANSAC), the numerical operator of
  * LoopClosing::ComputeSim3 (src/LoopClosing.cc:232-343), for batches of independent problems (one per loop candidate of every sequence): one round of
- * ComputeSim3's while loop — iterate(5) of every live solver — is one call.  The driver does not close loops and does not call it.  Out of scope:
- * ORBmatcher::SearchBySim3, and Optimizer::OptimizeSim3 (its g2o Sim3 vertex and edge types are not in the reference tree).
+ * ComputeSim3's while loop — iterate(5) of every live solver — is one call.  The driver does not close loops and does not call it.  What follows a
+ * returned Sim3 there: ORBmatcher::SearchBySim3 is the next section; Optimizer::OptimizeSim3 is out of scope (its g2o Sim3 vertex and edge types are
+ * not in the reference tree).
  *
  * A problem is `count` correspondences at `offset` of the packed arrays — X3Dc1, X3Dc2 (the two map points in the frames of their own cameras,
  * :94-98) and sigma2_1, sigma2_2 (mvLevelSigma2[octave] of the two keypoints, :84-85), all float — the intrinsics of both cameras (mK1, mK2), a seed
@@ -886,6 +887,83 @@ int oslam_sim3_iterate_batch_device(oslam_sim3_t* h, int n_problems, const oslam
                                     const float* d_X3Dc2, const float* d_sigma2_1, const float* d_sigma2_2, const oslam_sim3_params_t* params, int n_iterations,
                                     const int32_t* d_samples, float* d_T12, uint8_t* d_inliers, int32_t* d_status, int32_t* d_iter_inliers, float* d_hypotheses,
                                     void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * SearchBySim3 — ORBmatcher::SearchBySim3 (include/ORBmatcher.h:72, src/ORBmatcher.cc:1102-1326), called by LoopClosing::ComputeSim3 on every Sim3 a
+ * solver returns (src/LoopClosing.cc:324, th = 7.5), for batches of independent keyframe pairs (KF1 = the current keyframe, KF2 = a loop candidate):
+ * one call is that step of every candidate of every sequence.  An operator: the driver does not close loops and does not call it.
+ *
+ * Keyframes are rows of flat per-keypoint arrays (oslam_sim3_match_rows_t); a pair names n1 rows at off1 and n2 rows at off2, so several pairs may
+ * share the rows of the current keyframe.  Per row: mvKeysUn, mDescriptors, whether the keypoint's map point exists and is not bad (:1150-1156), and of
+ * that map point GetWorldPos, GetDescriptor, mfMaxDistance and mfMinDistance (the raw members, not the 1.2f / 0.8f getters).  One camera (the
+ * reference projects both directions with KF1's fx, fy, cx, cy, :1105-1108), one bounds[4] = mnMinX, mnMinY, mnMaxX, mnMaxY, mvScaleFactors,
+ * mnScaleLevels and mfLogScaleFactor per call.  The pair carries the Sim3 (s12, R12 row-major, t12), both poses (T1w, T2w: row-major 4 x 4 float,
+ * rows 0-2 read) and th.
+ * matched_in (vpMatches12 on entry), at out_off .. out_off + n1 - 1: -1 = NULL; anything else = a map point, the value being its GetIndexInKeyFrame(pKF2)
+ * (:1138), which sets vbAlreadyMatched2 only when 0 <= value < n2 (:1139); -2 stands for "matched, not in KF2".  NULL = nothing matched.
+ * match12, at the same rows: the keypoint index of KF2 where the reference writes vpMatches12[i1] = vpMapPoints2[idx2] (:1319), -1 elsewhere (also
+ * where matched_in had a match: -1 means "no new match").  n_found [n_pairs] is the reference's return value.
+ *
+ * Direction 1 -> 2 (:1148-1225), every keypoint of KF1 with a map point that is not already matched: p3Dc1 = R1w Xw + t1w, p3Dc2 = sR21 p3Dc1 + t21;
+ * skipped on z < 0.0 (z == +0 gives inf / NaN projections, which IsInImage rejects; there is no special case); invz = 1.0 / z; u = fx x invz + cx;
+ * KeyFrame::IsInImage (src/KeyFrame.cc:610: >= on the minimum, < on the maximum, false for NaN); dist3D = cv::norm(p3Dc2) kept when 0.8f mfMinDistance
+ * <= dist3D <= 1.2f mfMaxDistance (src/MapPoint.cc:476-486); level = MapPoint::PredictScale (src/MapPoint.cc:488-503: ceil(log(mfMaxDistance /
+ * dist3D) / mfLogScaleFactor) clamped to [0, nlevels - 1]); radius = th * mvScaleFactors[level]; KeyFrame::GetFeaturesInArea
+ * (src/KeyFrame.cc:569-608: floor / ceil cell bounds, strict fabs(d) < r; the grid is assigned by round, src/Frame.cc:455-470, :623-632); octave in
+ * [level - 1, level]; DescriptorDistance of the map point's descriptor against mDescriptors; the first strictly smaller distance wins in the order
+ * cell column ix, cell row iy, keypoint index inside a cell; accepted when bestDist <= TH_HIGH = 100.  Direction 2 -> 1 (:1228-1305) is the mirror with
+ * sR12, t12 and KF1's grid.  Agreement (:1308-1323): match12[i1] = idx2 iff vnMatch1[i1] == idx2 and vnMatch2[idx2] == i1.
+ *
+ * Roundings (float = IEEE binary32, one rounding per operator unless stated; no contraction, no fast-math):
+ *  - sR12 = s12 * R12 and sR21 = (1.0 / s12) * R12^T (:1119-1120): each element is the double product (1.0 / s12 in double) rounded once to float
+ *    (for sR12 that is the float product; an implementation of the scaled copy that narrows the factor 1.0 / s12 to float first differs from
+ *    this by at most one unit in the last place of an element of sR21);
+ *    t21 = -sR21 * t12 (:1121): the three float products summed in float from left to right, negated (a gemm with alpha = -1).
+ *  - a 3 x 3 * 3 x 1 + 3 x 1 cv::Mat expression: the three float products summed in float from left to right, then `+ c` in double, rounded once
+ *    (gemm_row of csrc/matcher.hip).
+ *  - invz = 1.0 / z in double, rounded to float; x = X invz, u = fx x + cx in float.
+ *  - cv::norm: the squares accumulated in double from left to right, an fp64 square root, rounded to float.
+ *  - 1.2f * mfMaxDistance, 0.8f * mfMinDistance, mfMaxDistance / dist3D, the division by mfLogScaleFactor and th * scale in float; log is the fp64
+ *    log of the float ratio rounded to float (the convention of csrc/mappoint.hip:172-173); a quotient whose ceil is NaN or does not fit an int gives
+ *    level 0 (what the x86 conversion of the reference build gives, INT_MIN, clamps to).
+ *  - (u - mnMinX - r) * mfGridElementWidthInv in float, mfGridElementWidthInv = 64.f / (mnMaxX - mnMinX) (src/Frame.cc:160-161).
+ * Refusals: more pairs than the handle's max_pairs, a pair with more keypoints than max_keypoints, or a negative count: OSLAM_E_CAPACITY, nothing is
+ * launched (rows outside the arrays: OSLAM_E_INVALID).  The device entry point cannot read the pair records: there such a record gets n_found = -2 and
+ * nothing else of it is written.  A pair whose s12, R12, t12, T1w or T2w is not finite, or whose s12 <= 0, gets n_found = -1 and its match12 rows all
+ * -1; the other pairs of the call are not affected.  Point data that is not finite falls out through the reference's own comparisons.  Pairs of one
+ * call must not share output rows.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct oslam_sim3_match oslam_sim3_match_t;
+typedef struct oslam_sim3_pair {
+    int32_t n1, off1, n2, off2;   /* KF1 = rows off1 .. off1 + n1 - 1, KF2 = rows off2 .. off2 + n2 - 1 */
+    int32_t out_off;              /* matched_in and match12 rows out_off .. out_off + n1 - 1 */
+    float s12, R12[9], t12[3];
+    float T1w[16], T2w[16];
+    float th;
+} oslam_sim3_pair_t;
+typedef struct oslam_sim3_match_rows {   /* n_rows entries each; the device entry point takes device pointers, desc and mp_desc 16-byte aligned */
+    int32_t n_rows;
+    const oslam_keypoint_t* keysUn;
+    const uint8_t* desc;          /* [n_rows][32] mDescriptors */
+    const uint8_t* has_mp;        /* pMP && !pMP->isBad() */
+    const float* Xw;              /* [n_rows][3] */
+    const uint8_t* mp_desc;       /* [n_rows][32] pMP->GetDescriptor() */
+    const float* maxDistance;     /* mfMaxDistance */
+    const float* minDistance;     /* mfMinDistance */
+} oslam_sim3_match_rows_t;
+/* max_keypoints <= 2400 (one keyframe is staged in LDS).  OSLAM_E_HIP without a device: there is no CPU fallback. */
+int oslam_sim3_match_create(oslam_sim3_match_t** out, int max_pairs, int max_keypoints, int device);
+void oslam_sim3_match_destroy(oslam_sim3_match_t* h);
+/* Host pointers, staged through one pinned / device block pair: one upload, one launch, one download, synchronous.  matched_in may be NULL; match12
+ * [n_out] and n_found [n_pairs] are read and written (rows no pair owns keep what they held). */
+int oslam_match_search_by_sim3_batch(oslam_sim3_match_t* h, int n_pairs, const oslam_sim3_pair_t* pairs, const oslam_sim3_match_rows_t* rows, int n_out,
+                                     const int32_t* matched_in, const oslam_camera_t* cam, const float bounds[4], const float* scaleFactors, int nlevels,
+                                     float logScaleFactor, int32_t* match12, int32_t* n_found);
+/* The same over device arrays (`rows` is a host struct of device pointers; cam, bounds and scaleFactors are host pointers), one launch, asynchronous
+ * on `stream`, no host synchronisation. */
+int oslam_match_search_by_sim3_batch_device(oslam_sim3_match_t* h, int n_pairs, const oslam_sim3_pair_t* d_pairs, const oslam_sim3_match_rows_t* rows, int n_out,
+                                            const int32_t* d_matched_in, const oslam_camera_t* cam, const float bounds[4], const float* scaleFactors, int nlevels,
+                                            float logScaleFactor, int32_t* d_match12, int32_t* d_n_found, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,3 +14,5 @@ from .pnp import PnPsolver  # noqa: F401
 from . import pnp  # noqa: F401
 from .sim3 import Sim3Solver  # noqa: F401
 from . import sim3  # noqa: F401
+from .sim3_match import Sim3Matcher  # noqa: F401
+from . import sim3_match  # noqa: F401

@@ -1,0 +1,387 @@
+// sim3_match.hip — ORBmatcher::SearchBySim3 (reference src/ORBmatcher.cc:1102-1326) for batches of independent keyframe pairs on gfx950
+// (include/oslam_hip.h, "SearchBySim3").  One launch, one workgroup per pair: the workgroup stages KF2 in LDS (keypoint xy, octave, descriptors and
+// the 64 x 48 cell table, as k_search_window of matcher.hip does), its threads stride over KF1's map points (:1148-1225), then it stages KF1 in the
+// same LDS and strides over KF2's map points (:1228-1305); vnMatch1 and vnMatch2 stay in LDS and the agreement (:1308-1323) follows after a barrier.
+// No inter-workgroup synchronisation and no atomics on global memory: the result does not depend on the order the hardware runs anything in.
+// The roundings are those the header lists.  Product code; never includes oracle/.
+#include <climits>
+#include <cmath>
+#include <mutex>
+
+#include "common.h"
+
+using oslam::set_error;
+
+struct oslam_sim3_match {
+    int device = 0, max_pairs = 0, max_kps = 0;
+    size_t lds = 0;
+    oslam::StagePair io;   // staging of the host-pointer entry point: inputs | outputs
+    std::mutex mu;
+};
+
+namespace {
+
+constexpr int kGridCols = 64, kGridRows = 48;   // reference include/Frame.h:43-44 (KeyFrame copies the Frame's grid, src/KeyFrame.cc:33-55)
+constexpr int kGridCells = kGridCols * kGridRows;
+constexpr int kThreads = 1024;
+constexpr int kMaxKps = 2400;                   // LDS budget, see lds_bytes()
+constexpr int kThHigh = 100;                    // ORBmatcher::TH_HIGH, src/ORBmatcher.cc:36
+constexpr int kSkip = -2;                       // vbAlreadyMatched, kept in the vnMatch arrays (never equal to a keypoint index)
+
+struct Sim3MatchArgs {
+    const oslam_sim3_pair_t* pairs;
+    int n_pairs, n_rows, n_out, ncap;
+    oslam_sim3_match_rows_t rows;
+    const int32_t* matched_in;
+    int32_t* match12; int32_t* n_found;
+    float fx, fy, cx, cy;
+    float minX, minY, maxX, maxY, invW, invH;
+    float scale[OSLAM_MAX_LEVELS];
+    int nlevels; float logScale;
+};
+
+size_t lds_bytes(int ncap) {
+    // desc 32 + xy 8 + vnMatch1 4 + vnMatch2 4 + items 2 + octave 1 per keypoint, the cell table
+    return (size_t)ncap * 51 + (kGridCells + 1) * 4 + 16;
+}
+
+struct Lds {
+    uint32_t* desc;    // [ncap][8]
+    float2* xy;        // [ncap]
+    int* m1;           // [ncap] vnMatch1 (kSkip: vbAlreadyMatched1)
+    int* m2;           // [ncap] vnMatch2 (kSkip: vbAlreadyMatched2)
+    int* cell;         // [kGridCells + 1] end of every cell in items
+    uint16_t* items;   // [ncap] keypoints sorted by cell (ix major, iy minor), index order inside a cell
+    int8_t* oct;       // [ncap]
+};
+
+// cv::Mat 3x3 * 3x1 + 3x1 as matcher.hip restates it (gemm_row): the three products summed in float from left to right, the `+ c` in double, rounded once
+__device__ __forceinline__ float gemm_row(const float* a, const float* x, float cc) {
+    const float t0 = a[0] * x[0] + a[1] * x[1] + a[2] * x[2];
+    return (float)((double)t0 + (double)cc);
+}
+
+__device__ __forceinline__ bool finite_all(const float* v, int n) {
+    bool ok = true;
+    for (int i = 0; i < n; i++) ok = ok && isfinite(v[i]);
+    return ok;
+}
+
+// The target keyframe into LDS: xy, octave, descriptors, and mGrid (src/Frame.cc:455-470: cell = round((x - mnMinX) * inv), push_back in index order)
+__device__ void stage_target(const Sim3MatchArgs& a, const Lds& s, int off, int N, int* s_wtot) {
+    const int tid = threadIdx.x;
+    const oslam_keypoint_t* kps = a.rows.keysUn + off;
+    const uint32_t* gdesc = (const uint32_t*)(a.rows.desc + (size_t)off * 32);
+    __syncthreads();   // the readers of the keyframe staged before are done
+    for (int i = tid; i <= kGridCells; i += kThreads) s.cell[i] = 0;
+    __syncthreads();
+    for (int i = tid; i < N; i += kThreads) {
+        const oslam_keypoint_t kp = kps[i];
+        s.xy[i] = make_float2(kp.x, kp.y);
+        s.oct[i] = (int8_t)min(max(kp.octave, -2), 127);   // (the level gate compares with levels 0 .. 15: -2 and 127 stand for everything beyond)
+        const int px = (int)roundf((kp.x - a.minX) * a.invW);
+        const int py = (int)roundf((kp.y - a.minY) * a.invH);
+        if (px >= 0 && px < kGridCols && py >= 0 && py < kGridRows) atomicAdd(&s.cell[px * kGridRows + py], 1);
+    }
+    for (int i = tid; i < N * 8; i += kThreads) s.desc[i] = gdesc[i];
+    __syncthreads();
+    {   // exclusive scan of the cell counts, kCellsPer per thread
+        constexpr int kCellsPer = kGridCells / kThreads;
+        static_assert(kCellsPer * kThreads == kGridCells, "the cell scan gives every thread the same number of cells");
+        const int lane = tid & 63, wv = tid >> 6;
+        const int base = tid * kCellsPer;
+        int cc[kCellsPer];
+        int incl = 0;
+#pragma unroll
+        for (int k = 0; k < kCellsPer; k++) { cc[k] = s.cell[base + k]; incl += cc[k]; }
+        const int local = incl;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int t = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += t;
+        }
+        if (lane == 63) s_wtot[wv] = incl;
+        __syncthreads();
+        int start = incl - local;
+        for (int i = 0; i < wv; i++) start += s_wtot[i];
+#pragma unroll
+        for (int k = 0; k < kCellsPer; k++) { s.cell[base + k] = start; start += cc[k]; }
+    }
+    __syncthreads();
+    // scatter with the cell starts as cursors (afterwards cell[c] = end of cell c = start of c + 1), then restore index order inside every cell
+    for (int i = tid; i < N; i += kThreads) {
+        const float2 p = s.xy[i];
+        const int px = (int)roundf((p.x - a.minX) * a.invW);
+        const int py = (int)roundf((p.y - a.minY) * a.invH);
+        if (px >= 0 && px < kGridCols && py >= 0 && py < kGridRows) {
+            const int pos = atomicAdd(&s.cell[px * kGridRows + py], 1);
+            s.items[pos] = (uint16_t)i;
+        }
+    }
+    __syncthreads();
+    for (int cell = tid; cell < kGridCells; cell += kThreads) {
+        const int st = cell > 0 ? s.cell[cell - 1] : 0, en = s.cell[cell];
+        for (int q = st + 1; q < en; q++) {   // insertion sort, cells hold a handful of points
+            const uint16_t v = s.items[q];
+            int p = q - 1;
+            while (p >= st && s.items[p] > v) { s.items[p + 1] = s.items[p]; p--; }
+            s.items[p + 1] = v;
+        }
+    }
+    __syncthreads();
+}
+
+// One direction (:1148-1225 / :1228-1305): the map points of the source keyframe (rows off .. off + N - 1, pose Tsw) through (sR, t) into the staged target.
+// m_src[i] is kSkip for an already matched point and receives bestIdx.
+__device__ void search_direction(const Sim3MatchArgs& a, const Lds& s, const float* s_scale, int off, int N, const float* Tsw, const float* sR, const float* t,
+                                 float th, int* m_src) {
+    float Rs[9], ts[3];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) Rs[3 * r + k] = Tsw[4 * r + k];
+        ts[r] = Tsw[4 * r + 3];
+    }
+    for (int i = threadIdx.x; i < N; i += kThreads) {
+        const size_t o = (size_t)off + i;
+        if (!a.rows.has_mp[o] || m_src[i] == kSkip) continue;
+        const float X[3] = {a.rows.Xw[3 * o], a.rows.Xw[3 * o + 1], a.rows.Xw[3 * o + 2]};
+        const float Ps[3] = {gemm_row(Rs, X, ts[0]), gemm_row(Rs + 3, X, ts[1]), gemm_row(Rs + 6, X, ts[2])};
+        const float Pt[3] = {gemm_row(sR, Ps, t[0]), gemm_row(sR + 3, Ps, t[1]), gemm_row(sR + 6, Ps, t[2])};
+        if (Pt[2] < 0.0f) continue;
+        const float invz = (float)(1.0 / (double)Pt[2]);
+        const float x = Pt[0] * invz, y = Pt[1] * invz;
+        const float u = a.fx * x + a.cx, v = a.fy * y + a.cy;
+        if (!(u >= a.minX && u < a.maxX && v >= a.minY && v < a.maxY)) continue;   // KeyFrame::IsInImage (src/KeyFrame.cc:610)
+        const float mfMax = a.rows.maxDistance[o];
+        const float maxDistance = 1.2f * mfMax, minDistance = 0.8f * a.rows.minDistance[o];
+        const float dist3D = (float)sqrt(((double)Pt[0] * (double)Pt[0] + (double)Pt[1] * (double)Pt[1]) + (double)Pt[2] * (double)Pt[2]);   // cv::norm
+        if (dist3D < minDistance || dist3D > maxDistance) continue;
+        // MapPoint::PredictScale (src/MapPoint.cc:488-503) with the log convention of mappoint.hip
+        const float ratio = __fdiv_rn(mfMax, dist3D);
+        const float cl = ceilf(__fdiv_rn((float)log((double)ratio), a.logScale));
+        const int level = (cl >= 0.0f && cl < 2147483648.0f) ? min((int)cl, a.nlevels - 1) : 0;   // (what does not fit an int converts to INT_MIN on x86: level 0)
+        const float r = th * s_scale[level];
+        // KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:569-608)
+        const int nMinCellX = max(0, (int)floorf((u - a.minX - r) * a.invW));
+        const int nMaxCellX = min(kGridCols - 1, (int)ceilf((u - a.minX + r) * a.invW));
+        const int nMinCellY = max(0, (int)floorf((v - a.minY - r) * a.invH));
+        const int nMaxCellY = min(kGridRows - 1, (int)ceilf((v - a.minY + r) * a.invH));
+        if (nMinCellX >= kGridCols || nMaxCellX < 0 || nMinCellY >= kGridRows || nMaxCellY < 0) continue;
+        const uint4 q0 = ((const uint4*)(a.rows.mp_desc + o * 32))[0], q1 = ((const uint4*)(a.rows.mp_desc + o * 32))[1];
+        int bestDist = INT_MAX, bestIdx = -1;
+        for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
+            const int c0 = ix * kGridRows + nMinCellY;
+            const int st = c0 > 0 ? s.cell[c0 - 1] : 0, en = s.cell[ix * kGridRows + nMaxCellY];
+            for (int q = st; q < en; q++) {   // cells iy = min .. max of a column are contiguous
+                const int k = s.items[q];
+                const float2 p = s.xy[k];
+                if (!(fabsf(p.x - u) < r && fabsf(p.y - v) < r)) continue;
+                const int oct = s.oct[k];
+                if (oct < level - 1 || oct > level) continue;
+                const uint4 d0 = ((const uint4*)(s.desc + k * 8))[0], d1 = ((const uint4*)(s.desc + k * 8))[1];
+                const int dist = __popc(q0.x ^ d0.x) + __popc(q0.y ^ d0.y) + __popc(q0.z ^ d0.z) + __popc(q0.w ^ d0.w) + __popc(q1.x ^ d1.x) + __popc(q1.y ^ d1.y) +
+                                 __popc(q1.z ^ d1.z) + __popc(q1.w ^ d1.w);
+                if (dist < bestDist) { bestDist = dist; bestIdx = k; }
+            }
+        }
+        if (bestDist <= kThHigh) m_src[i] = bestIdx;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_search_by_sim3(Sim3MatchArgs a) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const oslam_sim3_pair_t& P = a.pairs[b];
+    const int n1 = P.n1, off1 = P.off1, n2 = P.n2, off2 = P.off2, out_off = P.out_off;
+    // a record that does not fit the handle or the arrays: -2, nothing else is written (the host-pointer entry point refuses the call instead)
+    if (n1 < 0 || n2 < 0 || n1 > a.ncap || n2 > a.ncap || off1 < 0 || off2 < 0 || out_off < 0 || off1 > a.n_rows - n1 || off2 > a.n_rows - n2 || out_off > a.n_out - n1) {
+        if (tid == 0) a.n_found[b] = -2;
+        return;
+    }
+    int32_t* match12 = a.match12 + out_off;
+    const float s12 = P.s12;
+    if (!(isfinite(s12) && s12 > 0.0f && finite_all(P.R12, 9) && finite_all(P.t12, 3) && finite_all(P.T1w, 16) && finite_all(P.T2w, 16))) {
+        for (int i = tid; i < n1; i += kThreads) match12[i] = -1;
+        if (tid == 0) a.n_found[b] = -1;
+        return;
+    }
+
+    extern __shared__ __align__(16) uint8_t smem[];
+    Lds s;
+    s.desc = (uint32_t*)smem;
+    s.xy = (float2*)(s.desc + (size_t)a.ncap * 8);
+    s.m1 = (int*)(s.xy + a.ncap);
+    s.m2 = s.m1 + a.ncap;
+    s.cell = s.m2 + a.ncap;
+    s.items = (uint16_t*)(s.cell + kGridCells + 1);
+    s.oct = (int8_t*)(s.items + a.ncap);
+    __shared__ int s_wtot[kThreads / 64];
+    __shared__ float s_scale[OSLAM_MAX_LEVELS];
+    __shared__ int s_nfound;
+
+    // sR12 = s12 * R12, sR21 = (1.0 / s12) * R12^T: one rounding of the double product; t21 = -sR21 * t12: a gemm with alpha = -1 (:1119-1121)
+    float sR12[9], sR21[9], t21[3];
+    const double inv = 1.0 / (double)s12;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            sR12[3 * i + j] = (float)((double)s12 * (double)P.R12[3 * i + j]);
+            sR21[3 * i + j] = (float)(inv * (double)P.R12[3 * j + i]);
+        }
+#pragma unroll
+    for (int i = 0; i < 3; i++) t21[i] = -(sR21[3 * i] * P.t12[0] + sR21[3 * i + 1] * P.t12[1] + sR21[3 * i + 2] * P.t12[2]);
+
+    // vbAlreadyMatched1 / 2 (:1129-1142), vnMatch1 / 2 (:1144-1145)
+    if (tid < OSLAM_MAX_LEVELS) s_scale[tid] = a.scale[tid];
+    if (tid == 0) s_nfound = 0;
+    for (int i = tid; i < n2; i += kThreads) s.m2[i] = -1;
+    __syncthreads();
+    for (int i = tid; i < n1; i += kThreads) {
+        const int idx2 = a.matched_in ? a.matched_in[out_off + i] : -1;
+        s.m1[i] = idx2 != -1 ? kSkip : -1;
+        if (idx2 >= 0 && idx2 < n2) s.m2[idx2] = kSkip;   // (-2, other negative values and >= n2: matched, but not a keypoint of KF2)
+    }
+    // (stage_target begins with a barrier)
+    stage_target(a, s, off2, n2, s_wtot);
+    search_direction(a, s, s_scale, off1, n1, P.T1w, sR21, t21, P.th, s.m1);
+    stage_target(a, s, off1, n1, s_wtot);
+    search_direction(a, s, s_scale, off2, n2, P.T2w, sR12, P.t12, P.th, s.m2);
+    __syncthreads();
+    // agreement (:1308-1323)
+    int found = 0;
+    for (int i1 = tid; i1 < n1; i1 += kThreads) {
+        const int idx2 = s.m1[i1];
+        const bool ok = idx2 >= 0 && s.m2[idx2] == i1;
+        match12[i1] = ok ? idx2 : -1;
+        found += ok ? 1 : 0;
+    }
+    if (found) atomicAdd(&s_nfound, found);
+    __syncthreads();
+    if (tid == 0) a.n_found[b] = s_nfound;
+}
+
+int check_call(const char* fn, const oslam_sim3_match* h, int n_pairs, const oslam_sim3_match_rows_t* rows, int n_out, const oslam_camera_t* cam, const float* bounds,
+               const float* scaleFactors, int nlevels, float logScaleFactor) {
+    if (!h || !rows || !cam || !bounds || !scaleFactors) { set_error("%s: NULL argument", fn); return OSLAM_E_INVALID; }
+    if (n_pairs < 0 || rows->n_rows < 0 || n_out < 0) { set_error("%s: %d pairs, %d rows, %d output rows: none may be negative", fn, n_pairs, rows->n_rows, n_out); return OSLAM_E_CAPACITY; }
+    if (n_pairs > h->max_pairs) { set_error("%s: %d pairs exceed the handle's %d", fn, n_pairs, h->max_pairs); return OSLAM_E_CAPACITY; }
+    if (nlevels < 1 || nlevels > OSLAM_MAX_LEVELS) { set_error("%s: nlevels = %d outside [1, %d]", fn, nlevels, OSLAM_MAX_LEVELS); return OSLAM_E_INVALID; }
+    if (!(bounds[2] > bounds[0]) || !(bounds[3] > bounds[1])) { set_error("%s: empty image bounds", fn); return OSLAM_E_INVALID; }
+    if (!(logScaleFactor > 0.0f)) { set_error("%s: logScaleFactor must be positive", fn); return OSLAM_E_INVALID; }
+    if (rows->n_rows > 0 && (!rows->keysUn || !rows->desc || !rows->has_mp || !rows->Xw || !rows->mp_desc || !rows->maxDistance || !rows->minDistance)) {
+        set_error("%s: a per-keypoint array is NULL", fn);
+        return OSLAM_E_INVALID;
+    }
+    return OSLAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void oslam_sim3_match_destroy(oslam_sim3_match_t* h) {
+    if (!h) return;
+    delete h;
+}
+
+int oslam_sim3_match_create(oslam_sim3_match_t** out, int max_pairs, int max_keypoints, int device) {
+    if (!out) { set_error("oslam_sim3_match_create: out is NULL"); return OSLAM_E_INVALID; }
+    *out = nullptr;
+    if (max_pairs < 1 || max_keypoints < 1) { set_error("oslam_sim3_match_create: bad argument"); return OSLAM_E_INVALID; }
+    if (max_keypoints > kMaxKps) {
+        set_error("oslam_sim3_match_create: max_keypoints %d > %d (one keyframe's keypoints, descriptors and grid, and both match vectors, must fit 160 KiB of LDS)", max_keypoints, kMaxKps);
+        return OSLAM_E_INVALID;
+    }
+    const int ndev = oslam_device_count();
+    if (ndev <= 0) { set_error("no HIP device visible: oslam_sim3_match_create has no CPU fallback"); return OSLAM_E_HIP; }
+    if (device < 0 || device >= ndev) { set_error("oslam_sim3_match_create: device out of range"); return OSLAM_E_INVALID; }
+    OSLAM_HIP_CHECK(hipSetDevice(device));
+    oslam_sim3_match* h = new oslam_sim3_match;
+    h->device = device; h->max_pairs = max_pairs; h->max_kps = max_keypoints; h->lds = lds_bytes(max_keypoints);
+    const hipError_t e = hipFuncSetAttribute((const void*)k_search_by_sim3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(kMaxKps));   // (the attribute belongs to the kernel, not to the handle)
+    if (e != hipSuccess) {
+        set_error("oslam_sim3_match_create: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+        delete h;
+        return OSLAM_E_HIP;
+    }
+    *out = h;
+    return OSLAM_OK;
+}
+
+int oslam_match_search_by_sim3_batch_device(oslam_sim3_match_t* h, int n_pairs, const oslam_sim3_pair_t* d_pairs, const oslam_sim3_match_rows_t* rows, int n_out,
+                                            const int32_t* d_matched_in, const oslam_camera_t* cam, const float bounds[4], const float* scaleFactors, int nlevels,
+                                            float logScaleFactor, int32_t* d_match12, int32_t* d_n_found, void* stream) {
+    const char* fn = "oslam_match_search_by_sim3_batch_device";
+    OSLAM_CHECK(check_call(fn, h, n_pairs, rows, n_out, cam, bounds, scaleFactors, nlevels, logScaleFactor));
+    if (n_pairs == 0) return OSLAM_OK;
+    if (!d_pairs || !d_n_found || (n_out > 0 && !d_match12)) { set_error("%s: NULL argument", fn); return OSLAM_E_INVALID; }
+    OSLAM_HIP_CHECK(hipSetDevice(h->device));
+    Sim3MatchArgs a;
+    a.pairs = d_pairs; a.n_pairs = n_pairs; a.n_rows = rows->n_rows; a.n_out = n_out; a.ncap = h->max_kps;
+    a.rows = *rows; a.matched_in = d_matched_in; a.match12 = d_match12; a.n_found = d_n_found;
+    a.fx = cam->fx; a.fy = cam->fy; a.cx = cam->cx; a.cy = cam->cy;
+    a.minX = bounds[0]; a.minY = bounds[1]; a.maxX = bounds[2]; a.maxY = bounds[3];
+    a.invW = (float)kGridCols / (float)(a.maxX - a.minX);   // src/Frame.cc:160-161
+    a.invH = (float)kGridRows / (float)(a.maxY - a.minY);
+    for (int i = 0; i < OSLAM_MAX_LEVELS; i++) a.scale[i] = i < nlevels ? scaleFactors[i] : 0.f;
+    a.nlevels = nlevels; a.logScale = logScaleFactor;
+    hipLaunchKernelGGL(k_search_by_sim3, dim3(n_pairs), dim3(kThreads), h->lds, (hipStream_t)stream, a);
+    OSLAM_HIP_CHECK(hipGetLastError());
+    return OSLAM_OK;
+}
+
+int oslam_match_search_by_sim3_batch(oslam_sim3_match_t* h, int n_pairs, const oslam_sim3_pair_t* pairs, const oslam_sim3_match_rows_t* rows, int n_out,
+                                     const int32_t* matched_in, const oslam_camera_t* cam, const float bounds[4], const float* scaleFactors, int nlevels,
+                                     float logScaleFactor, int32_t* match12, int32_t* n_found) {
+    const char* fn = "oslam_match_search_by_sim3_batch";
+    OSLAM_CHECK(check_call(fn, h, n_pairs, rows, n_out, cam, bounds, scaleFactors, nlevels, logScaleFactor));
+    if (n_pairs == 0) return OSLAM_OK;
+    if (!pairs || !n_found || (n_out > 0 && !match12)) { set_error("%s: NULL argument", fn); return OSLAM_E_INVALID; }
+    const int nr = rows->n_rows;
+    for (int b = 0; b < n_pairs; b++) {
+        const oslam_sim3_pair_t& P = pairs[b];
+        if (P.n1 < 0 || P.n2 < 0 || P.n1 > h->max_kps || P.n2 > h->max_kps) {
+            set_error("%s: pair %d has %d / %d keypoints, outside [0, %d]", fn, b, P.n1, P.n2, h->max_kps);
+            return OSLAM_E_CAPACITY;
+        }
+        if (P.off1 < 0 || P.off2 < 0 || P.out_off < 0 || P.off1 > nr - P.n1 || P.off2 > nr - P.n2 || P.out_off > n_out - P.n1) {
+            set_error("%s: pair %d (off1 %d, off2 %d, out_off %d) lies outside the %d rows / %d output rows", fn, b, P.off1, P.off2, P.out_off, nr, n_out);
+            return OSLAM_E_INVALID;
+        }
+    }
+    std::lock_guard<std::mutex> lock(h->mu);
+    OSLAM_HIP_CHECK(hipSetDevice(h->device));
+    using oslam::align_up;
+    const size_t np = (size_t)n_pairs, R = (size_t)nr, NO = (size_t)n_out;
+    // one block: pairs | keysUn | desc | has_mp | Xw | mp_desc | maxDistance | minDistance | matched_in || match12 | n_found: one upload, one download
+    const size_t oPair = 0, oKeys = oPair + align_up(np * sizeof(oslam_sim3_pair_t), 256), oDesc = oKeys + align_up(R * sizeof(oslam_keypoint_t), 256),
+                 oHas = oDesc + align_up(R * 32, 256), oXw = oHas + align_up(R, 256), oMpd = oXw + align_up(R * 12, 256), oMax = oMpd + align_up(R * 32, 256),
+                 oMin = oMax + align_up(R * 4, 256), oIn = oMin + align_up(R * 4, 256), oOut = oIn + (matched_in ? align_up(NO * 4, 256) : 0),
+                 oNf = oOut + align_up(NO * 4, 256), total = oNf + align_up(np * 4, 256);
+    OSLAM_CHECK(h->io.grow(total, 4096));
+    uint8_t *ph = h->io.h.bytes(), *pd = h->io.d.bytes();
+    memcpy(ph + oPair, pairs, np * sizeof(oslam_sim3_pair_t));
+    if (R) {
+        memcpy(ph + oKeys, rows->keysUn, R * sizeof(oslam_keypoint_t)); memcpy(ph + oDesc, rows->desc, R * 32); memcpy(ph + oHas, rows->has_mp, R);
+        memcpy(ph + oXw, rows->Xw, R * 12); memcpy(ph + oMpd, rows->mp_desc, R * 32); memcpy(ph + oMax, rows->maxDistance, R * 4);
+        memcpy(ph + oMin, rows->minDistance, R * 4);
+    }
+    if (matched_in && NO) memcpy(ph + oIn, matched_in, NO * 4);
+    // the caller's output rows travel too: rows no pair owns, and those of a pair the kernel leaves alone, come back as they were
+    if (NO) memcpy(ph + oOut, match12, NO * 4);
+    memcpy(ph + oNf, n_found, np * 4);
+    OSLAM_HIP_CHECK(hipMemcpyAsync(pd, ph, total, hipMemcpyHostToDevice, nullptr));
+    oslam_sim3_match_rows_t d;
+    d.n_rows = nr; d.keysUn = (const oslam_keypoint_t*)(pd + oKeys); d.desc = pd + oDesc; d.has_mp = pd + oHas; d.Xw = (const float*)(pd + oXw); d.mp_desc = pd + oMpd;
+    d.maxDistance = (const float*)(pd + oMax); d.minDistance = (const float*)(pd + oMin);
+    OSLAM_CHECK(oslam_match_search_by_sim3_batch_device(h, n_pairs, (const oslam_sim3_pair_t*)(pd + oPair), &d, n_out, matched_in ? (const int32_t*)(pd + oIn) : nullptr, cam,
+                                                        bounds, scaleFactors, nlevels, logScaleFactor, (int32_t*)(pd + oOut), (int32_t*)(pd + oNf), nullptr));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(ph + oOut, pd + oOut, total - oOut, hipMemcpyDeviceToHost, nullptr));
+    OSLAM_HIP_CHECK(hipStreamSynchronize(nullptr));
+    if (NO) memcpy(match12, ph + oOut, NO * 4);
+    memcpy(n_found, ph + oNf, np * 4);
+    return OSLAM_OK;
+}
+
+}  // extern "C"
