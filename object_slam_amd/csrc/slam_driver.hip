@@ -108,8 +108,14 @@ struct BowViews {
 };
 
 // (local-BA windows: the solver's reduced system holds 6 x 128 unknowns, i.e. at most 128 FREE keyframes; fixed keyframes are not limited.  OSLAM_SLAM_LBA_MAX_FREE
-// lowers the bound — a test knob for the degraded-window path of run_local_mapping)
+// lowers the bound — a test knob for the degraded-window path of lm_gather_window)
 static const int kLbaMaxFreeKFs = [] { const char* e = getenv("OSLAM_SLAM_LBA_MAX_FREE"); const int v = e ? atoi(e) : 0; return (v > 0 && v < 128) ? v : 128; }();
+// the other knobs of the local-mapping pass, read once per process
+static const bool kCullDev = !getenv("OSLAM_SLAM_CULL_HOST");                         // KeyFrameCulling from the device's counts (lm_request_cull)
+static const bool kCullCheck = getenv("OSLAM_SLAM_CULL_CHECK") != nullptr;            // debugging: every device verdict is compared with the host count
+static const bool kFuseExclCheck = getenv("OSLAM_SLAM_FUSE_EXCL_CHECK") != nullptr;   // debugging: compare the cached exclusion flags of a Fuse round with the full pass
+static const bool kFusecurCheck = getenv("OSLAM_SLAM_FUSECUR_CHECK") != nullptr;      // debugging: the table's candidate list of sn_fuse_into_current against the driver's
+static const bool kMpuAsync = getenv("OSLAM_SLAM_MPU_SYNC") == nullptr;               // a Fuse round's descriptor updates are collected behind the next round's search (sn_fuse_round_by_id)
 
 enum { ST_NOT_INITIALIZED = OSLAM_SLAM_NOT_INITIALIZED, ST_OK = OSLAM_SLAM_OK, ST_LOST = OSLAM_SLAM_LOST };
 
@@ -130,7 +136,7 @@ struct Seq {
     int matchesInliers = 0;
     std::vector<int> localKFs, localMPs;
     std::vector<uint64_t> mpMark;         // mnTrackReferenceForFrame of the map points as ONE BIT per point id: set <=> the point was visited by the cached walk (update_local_map)
-    std::vector<int> baMark;              // mnBALocalForKF per map point id (dense, see the local-BA gather in run_local_mapping)
+    std::vector<int> baMark;              // mnBALocalForKF per map point id (dense, see lm_gather_window)
     std::vector<int> fuseMark;            // mnFuseCandidateForKF per map point id (dense, SearchInNeighbors' second direction)
     // UpdateLocalKeyFrames' keyframeCounter kept from frame to frame (update_local_map): vote[k] = matched points of the last voted frame that keyframe k observes,
     // votePts = those points (one entry per keypoint), valid while voteVersion == mapVersion (observation lists only change under a version bump)
@@ -221,7 +227,7 @@ struct Ctx {
     double fine[8] = {0};   // OSLAM_SLAM_SN_STATS: core-seconds inside SearchInNeighbors (target lists + masks, first-direction rounds, second-direction list, its round, updates + connections)
     CpuAccount acct;
     int shard = 0;   // worker set of this handle (slam_pool.h)
-    struct Win {   // one local-BA window (run_local_mapping)
+    struct Win {   // one local-BA window (lm_gather_window)
         int si = -1, nLocal = 0, nFree = 0;   // nFree: window indices below it are free poses (== nLocal unless the window was degraded)
         std::vector<int> kfs, pts; std::vector<float> poses, points, eobs, einv, poses_out, points_out; std::vector<uint8_t> fixed, erase;
         std::vector<int32_t> ekf, ept; std::vector<std::pair<int, int>> eref;
@@ -850,10 +856,276 @@ static void fuse_apply_pairs(Seq& s, int k, const int32_t* pairs, int n) {
     for (int q = 0; q < n; q++) fuse_apply_one(s, k, pairs[2 * q], pairs[2 * q + 1], nullptr);
 }
 
-// Second half of a local-mapping pass: Optimizer::LocalBundleAdjustment's write-back (src/Optimizer.cc:711-777) from the solved windows, the MapPoint updates of
-// their points, KeyFrameCulling (src/LocalMapping.cc:633-697) for every sequence of the pass.  Synchronous schedule: called at the end of run_local_mapping;
-// deferred schedule: by finish_local_mapping after the next step's tracking.
-static int local_mapping_back_ok(Ctx& c, const std::vector<int>& who, const std::vector<Ctx::Win*>& wins);
+// ---- one local-mapping pass: what all its steps work on ----
+static MpUpdate& map_updates(Ctx& c) { if (!c.updMap) c.updMap.reset(new MpUpdate); return *c.updMap; }
+struct LmPass {
+    Ctx& c;
+    const std::vector<int>& who;   // the sequences of the pass; w below is an index into it
+    const int nW, flags;           // flags: oslam_slam_config_t::local_mapping
+    Pool& pool;
+    MpUpdate& upd;                 // the batched MapPoint updates of the pass
+    Timer tm;
+    LmPass(Ctx& c_, const std::vector<int>& who_) : c(c_), who(who_), nW((int)who_.size()), flags(c_.cfg.local_mapping), pool(*c_.pool), upd(map_updates(c_)) {}
+    Seq& seq(int w) const { return *c.seq[who[w]]; }
+    // the points the sequences listed for an update (Seq::updList) become the items of `upd`: sequence order, then list order
+    void merge_upd() { upd.clear(); for (int si : who) { Seq& s = *c.seq[si]; for (int p : s.updList) upd.add(si, p); s.updList.clear(); } }
+    // The time since the last charge goes to a stage of oslam_slam_stage_seconds.  charge: host work of the pass, to [7] and its part [stage] (9 ProcessNewKeyFrame,
+    // 10 CreateNewMapPoints, 11 SearchInNeighbors — and its part Ctx::fine[fine] —, 12 local-BA gather + write-back, 13 KeyFrameCulling); charge_op: an operator call,
+    // to [5] mp_update, [6] lba or [8] fuse / bow / triangulate, which are not part of [7].
+    void charge(int stage, int fine = -1) {
+        const double d = tm.lap();
+        c.sec[7] += d; c.sec[stage] += d; c.cpu[7] += tm.cpu; c.cpu[stage] += tm.cpu;
+        if (fine >= 0) c.fine[fine] += tm.cpu;
+    }
+    void charge_op(int slot) { c.sec[slot] += tm.lap(); c.cpu[slot] += tm.cpu; }
+};
+
+// the change sets of the sequences' maps since the last call, to the table's mirror of the observation graph (oslam_slam_ops_t::map_journal)
+static int lm_send_journal(LmPass& L) {
+    Ctx& c = L.c;
+    std::vector<oslam_map_changes_t> chg(L.nW), chs;
+    std::vector<uint8_t> has(L.nW, 0);
+    if (c.jrScratch.size() < (size_t)c.S) c.jrScratch.resize(c.S);
+    L.pool.parallel_for(L.nW, [&](int w) { Seq& s = L.seq(w); if (s.map.jr_pending()) { s.map.journal_changes(L.who[w], c.thDepth, c.jrScratch[L.who[w]], chg[w]); has[w] = 1; } });
+    for (int w = 0; w < L.nW; w++) if (has[w]) chs.push_back(chg[w]);
+    return chs.empty() ? OSLAM_OK : c.ops.map_journal(c.ops.ctx, (int)chs.size(), chs.data());
+}
+
+// ---- second half of a pass: Optimizer::LocalBundleAdjustment's write-back (src/Optimizer.cc:711-777), the MapPoint updates, KeyFrameCulling ----
+// write-back of one solved window: erase list, poses, and what the MapPoint updates of its points need
+static void lm_write_back_window(const Ctx& c, Ctx::Win& W, bool useWin) {
+    Seq& s = *c.seq[W.si];
+    Map& m = s.map;
+    // erase list: mono edges first, then stereo edges (:711-757)
+    for (int pass = 0; pass < 2; pass++)
+        for (size_t e = 0; e < W.ekf.size(); e++) {
+            if (!W.erase[e]) continue;
+            const bool stereo = W.eobs[e * 3 + 2] >= 0;
+            if ((pass == 1) != stereo) continue;
+            const int k = W.eref[e].first, p = W.eref[e].second;
+            const int idx = m.mps[p].obs_index(k);
+            if (idx >= 0) m.set_kf_mp(k, idx, -1);
+            m.erase_observation(p, k);
+        }
+    for (int q = 0; q < W.nFree; q++) {   // (the local keyframes a degraded window held fixed keep their poses)
+        M4 T; memcpy(T.m, &W.poses_out[(size_t)q * 16], 64);
+        m.kfs[W.kfs[q]].pose.set_keyframe(T);
+    }
+    if (!useWin) {
+        for (size_t j = 0; j < W.pts.size(); j++) {
+            if (j + kPF < W.pts.size()) __builtin_prefetch(&m.mps[W.pts[j + kPF]]);
+            MapPt& mp = m.mps[W.pts[j]];
+            for (int d = 0; d < 3; d++) mp.pos[d] = W.points_out[j * 3 + d];
+            s.updList.push_back(W.pts[j]);
+        }
+        return;
+    }
+    // UpdateNormalAndDepth from the window itself (oslam_job_mp_window_t): per point only the reference keyframe's window index and level scale factor
+    // are looked up here; the positions are written together with the results (lm_update_points_from_windows).  A point with an observation the window does not
+    // carry, or whose reference keyframe's observation is not among its surviving edges, takes the general path (position now, update through mp_update).
+    const size_t nP = W.pts.size(), nK = W.kfs.size();
+    std::vector<int>& slot = s.counter;   // keyframe id -> window index + 1 (restored to 0 below)
+    for (size_t q = 0; q < nK; q++) slot[W.kfs[q]] = (int)q + 1;
+    W.uOw.resize(nK * 3);
+    for (size_t q = 0; q < nK; q++) memcpy(&W.uOw[q * 3], m.kfs[W.kfs[q]].pose.Ow, 12);
+    W.uskip.assign(nP, 0); W.uref.assign(nP, 0); W.ulsf.assign(nP, 1.f); W.uout5.resize(nP * 5 + 5);
+    for (size_t j = 0; j < nP; j++) {
+        const int p = W.pts[j];
+        if (j + kPF < nP && !m.pBad[W.pts[j + kPF]]) __builtin_prefetch(&m.mps[W.pts[j + kPF]].refKF);
+        if (m.pBad[p]) { W.uskip[j] = 1; continue; }
+        int q = -1, eRef = -1;
+        if (!W.pquirk[j]) {
+            const int rk = m.mps[p].refKF;
+            q = rk >= 0 ? slot[rk] - 1 : -1;
+            if (q >= 0)
+                for (int e = W.pstart[j]; e < W.pstart[j + 1]; e++)
+                    if (W.ekf[e] == q && !W.erase[e]) { eRef = e; break; }
+        }
+        if (eRef < 0) {   // general path
+            W.uskip[j] = 2;
+            MapPt& mp = m.mps[p];
+            for (int d = 0; d < 3; d++) mp.pos[d] = W.points_out[j * 3 + d];
+            s.updList.push_back(p);
+            continue;
+        }
+        W.uref[j] = q; W.ulsf[j] = c.scale[W.eoct[eRef]];
+    }
+    for (size_t q = 0; q < nK; q++) slot[W.kfs[q]] = 0;
+}
+
+// positions, normals and depth ranges of the windows' points: from the windows on the device (useWin), the rest through the general update
+static int lm_update_points_from_windows(LmPass& L, const std::vector<Ctx::Win*>& wins, bool useWin) {
+    typedef Ctx::Win Win;
+    Ctx& c = L.c;
+    int rc;
+    if (useWin && !wins.empty()) {
+        L.charge(12);
+        std::vector<oslam_job_mp_window_t> wj(wins.size());
+        for (size_t wi = 0; wi < wins.size(); wi++) {
+            Win& W = *wins[wi];
+            oslam_job_mp_window_t& j = wj[wi];
+            j.slot = W.si; j.nP = (int32_t)W.pts.size(); j.nE = (int32_t)W.ekf.size(); j.nK = (int32_t)W.kfs.size();
+            j.pt_ids = W.pts.data(); j.pt_start = W.pstart.data(); j.edge_kf = W.ekf.data(); j.erase = W.erase.data(); j.skip = W.uskip.data(); j.ref_kf = W.uref.data();
+            j.lsf = W.ulsf.data(); j.Ow = W.uOw.data(); j.pos = W.points_out.data(); j.out5 = W.uout5.data();
+        }
+        if ((rc = c.ops.mp_update_windows(c.ops.ctx, (int)wj.size(), wj.data()))) return rc;
+        L.charge_op(5);
+        L.pool.parallel_for((int)wins.size(), [&](int wi) {
+            Win& W = *wins[wi];
+            Map& m = c.seq[W.si]->map;
+            for (size_t j = 0; j < W.pts.size(); j++) {
+                if (j + kPF < W.pts.size() && W.uskip[j + kPF] != 2) __builtin_prefetch(&m.mps[W.pts[j + kPF]]);
+                if (W.uskip[j] == 2) continue;   // (took the general path: position already written)
+                MapPt& mp = m.mps[W.pts[j]];
+                for (int d = 0; d < 3; d++) mp.pos[d] = W.points_out[j * 3 + d];
+                if (W.uskip[j]) continue;
+                const float* o = &W.uout5[j * 5];
+                mp.normal[0] = o[0]; mp.normal[1] = o[1]; mp.normal[2] = o[2]; mp.maxD = o[3]; mp.minD = o[4];
+            }
+        });
+    }
+    L.merge_upd();
+    L.charge(12);
+    if ((rc = L.upd.run(c, false, true))) return rc;
+    L.charge_op(5);
+    return OSLAM_OK;
+}
+
+// KeyFrameCulling's counting loop runs on the device from the table's mirror of the observation graph (oslam_slam_ops_t::map_journal / kf_culling_counts): requested
+// once the observation lists of the pass are final, collected in front of the verdicts.  The jobs name the arrays of ids / out, so all of it lives until then.
+struct CullRequest {
+    bool requested = false, collected = false;
+    std::vector<std::vector<int32_t>> ids, out;   // [w]: the candidates (m.kfs[curKF].ordered without keyframe 0), 4 counts per candidate (empty: host walk)
+    std::vector<oslam_job_cull_t> jobs;
+};
+static int lm_request_cull(LmPass& L, CullRequest& cr) {
+    Ctx& c = L.c;
+    cr.requested = true;
+    if (!((L.flags & 16) && kCullDev && c.ops.map_journal && c.ops.kf_culling_counts)) { cr.collected = true; return OSLAM_OK; }
+    int rc;
+    if ((rc = lm_send_journal(L))) return rc;
+    cr.out.resize(L.nW); cr.ids.resize(L.nW);
+    for (int w = 0; w < L.nW; w++) {
+        Seq& s = L.seq(w);
+        Map& m = s.map;
+        if (m.lvlOverflow) continue;
+        for (int k : m.kfs[s.curKF].ordered) if (k != 0) cr.ids[w].push_back(k);
+        if (cr.ids[w].empty()) continue;
+        cr.out[w].assign(cr.ids[w].size() * 4, 0);
+        oslam_job_cull_t j; j.slot = L.who[w]; j.n = (int32_t)cr.ids[w].size(); j.kf_ids = cr.ids[w].data(); j.out = cr.out[w].data();
+        cr.jobs.push_back(j);
+    }
+    if (!cr.jobs.empty() && (rc = c.ops.kf_culling_counts(c.ops.ctx, (int)cr.jobs.size(), cr.jobs.data(), c.thDepth))) return rc;
+    if (!c.ops.kf_culling_collect) cr.collected = true;
+    L.charge(13);
+    return OSLAM_OK;
+}
+
+// KeyFrameCulling (src/LocalMapping.cc:633-697) of one sequence.  dev: the device's counts of its candidates (NULL: none).  The host takes the verdicts in the
+// reference's order; SetBadFlag changes the counts of the candidates behind a culled keyframe, so from the first cull of a pass on — and for a keyframe the mirror
+// flags as ambiguous, and for a map whose octave histogram overflowed — the host counts itself.
+static void lm_cull_keyframes(const Ctx& c, Seq& s, int si, const int32_t* dev) {
+    Map& m = s.map;
+    const std::vector<int> local = m.kfs[s.curKF].ordered;
+    const bool useHist = !m.lvlOverflow;
+    bool culled_any = false;
+    int qi = 0;   // index of the candidate among the non-zero ids (CullRequest::ids order)
+    for (int k : local) {
+        if (k == 0) continue;
+        const int q = qi++;
+        if (dev && !culled_any && dev[4 * q + 3] == 0) {
+            const int ub = dev[4 * q], nMPs = dev[4 * q + 1], nRed = dev[4 * q + 2];
+            const int keepAt = ub / 10 + 2;
+            const bool cull = (nMPs - nRed < keepAt) && (nRed > 0.9 * nMPs);
+            if (kCullCheck) {
+                const KeyFrm& kfc = m.kfs[k];
+                int ub2 = 0, r2 = 0, n2 = 0;
+                for (int i = 0; i < kfc.N; i++) {
+                    const int p = kfc.mp[i];
+                    const bool good = !(kfc.depth[i] > c.thDepth || kfc.depth[i] < 0);
+                    ub2 += p >= 0 && good;
+                    if (p < 0 || m.pBad[p] || !good) continue;
+                    n2++;
+                    if (m.pNObs[p] > 3) {
+                        int nn = 0;
+                        const MapPt& mq = m.mps[p];
+                        for (size_t oi = 0; oi < mq.obs.size(); oi++) if (mq.obs[oi].first != k && mq.okp[oi].octave <= kfc.oct[i] + 1) nn++;
+                        r2 += nn >= 3;
+                    }
+                }
+                if (ub2 != ub || n2 != nMPs || r2 != nRed) { fprintf(stderr, "OSLAM_SLAM_CULL_CHECK: sequence %d keyframe %d: device (%d, %d, %d), host (%d, %d, %d)\n", si, k, ub, nMPs, nRed, ub2, n2, r2); abort(); }
+            }
+            if (cull) { m.set_bad_keyframe(k); s.st[11]++; s.culledKFs.push_back(k); culled_any = true; }
+            continue;
+        }
+        const KeyFrm& kf = m.kfs[k];
+        // The verdict is nRed > 0.9 * nMPs.  nMPs is at most the number of slots that hold a point at a usable depth (counted from the keyframe's own
+        // arrays, no map access), so once the points found NOT redundant reach a tenth of that bound (+ 2: away from the rounding of 0.9 * nMPs) the keyframe
+        // stays whatever the remaining slots hold, and the walk over their observation lists is skipped.  Most keyframes leave the loop this way.
+        int ub = 0;
+        for (int i = 0; i < kf.N; i++) ub += kf.mp[i] >= 0 && !(kf.depth[i] > c.thDepth || kf.depth[i] < 0);
+        const int keepAt = ub / 10 + 2;
+        int nRed = 0, nMPs = 0;
+        for (int i = 0; i < kf.N && nMPs - nRed < keepAt; i++) {
+            if (!useHist) prefetch_okp_ahead(m.mps, kf.mp, i, kf.N);
+            const int p = kf.mp[i];
+            if (p < 0 || m.pBad[p]) continue;
+            if (kf.depth[i] > c.thDepth || kf.depth[i] < 0) continue;
+            nMPs++;
+            if (m.pNObs[p] > 3) {
+                const int lvl = kf.oct[i];
+                // "three OTHER observations at octave <= lvl + 1": the point's octave histogram counts ALL its observations there; with four or more the
+                // answer is yes and with two or fewer no, whether or not this keyframe's own observation is among them (Map::pLvl).  Exactly three: the lists.
+                const int all_le = useHist ? m.lvl_count_le(p, lvl + 1) : 3;
+                if (all_le != 3) { nRed += all_le >= 4; continue; }
+                int n = 0;
+                const MapPt& mq = m.mps[p];
+                for (size_t oi = 0; oi < mq.obs.size(); oi++) {
+                    if (mq.obs[oi].first == k) continue;
+                    if (mq.okp[oi].octave <= lvl + 1) { n++; if (n >= 3) break; }   // (the observing keypoint's octave, cached beside the observation: slam_map.h ObsKp)
+                }
+                if (n >= 3) nRed++;
+            }
+        }
+        if (nMPs - nRed < keepAt && nRed > 0.9 * nMPs) { m.set_bad_keyframe(k); s.st[11]++; s.culledKFs.push_back(k); culled_any = true; }
+    }
+}
+
+// the table may recycle the resident records of the keyframes culled in this pass
+static int lm_release_keyframes(LmPass& L) {
+    Ctx& c = L.c;
+    std::vector<int32_t> rs, rk;
+    for (int si : L.who) {
+        Seq& s = *c.seq[si];
+        if (c.ops.release_keyframes) for (int k : s.culledKFs) { rs.push_back(si); rk.push_back(k); }
+        s.culledKFs.clear();
+    }
+    return rs.empty() ? OSLAM_OK : c.ops.release_keyframes(c.ops.ctx, (int)rs.size(), rs.data(), rk.data());
+}
+
+// Second half of a local-mapping pass for every sequence of it.  Synchronous schedule: called at the end of run_local_mapping; deferred schedule: by
+// finish_local_mapping after the next step's tracking.
+static int local_mapping_back_ok(Ctx& c, const std::vector<int>& who, const std::vector<Ctx::Win*>& wins) {
+    LmPass L(c, who);
+    CullRequest cull;
+    int rc;
+    if (L.flags & 8) {
+        const bool useWin = c.ops.mp_update_windows != nullptr;
+        L.pool.parallel_for((int)wins.size(), [&](int wi) { lm_write_back_window(c, *wins[wi], useWin); });
+        L.charge(12);
+        // the observation lists are final for this pass (the MapPoint updates do not touch them): the culling counts are requested now and collected after them
+        if ((rc = lm_request_cull(L, cull))) return rc;
+        if ((rc = lm_update_points_from_windows(L, wins, useWin))) return rc;
+    }
+    if (!cull.requested && (rc = lm_request_cull(L, cull))) return rc;   // (a pass without local BA)
+    if (!cull.collected && (rc = c.ops.kf_culling_collect(c.ops.ctx))) return rc;
+    if (L.flags & 16)
+        L.pool.parallel_for(L.nW, [&](int w) { lm_cull_keyframes(c, L.seq(w), who[w], cull.out.empty() || cull.out[w].empty() ? nullptr : cull.out[w].data()); });
+    if ((rc = lm_release_keyframes(L))) return rc;
+    L.charge(13);
+    return OSLAM_OK;
+}
+
 // Per-sequence failure isolation (the reference: one System that loses track resets ITSELF, src/Tracking.cc:553-560).  A local-BA window the operator refused
 // (Win::st[0] < 0: beyond its bounds, malformed) fails its own sequence only: that sequence leaves the pass here — no write-back, no culling —, is counted
 // (oslam_slam_lba_window_stats [7]) and resets before its next frame like a system that lost track right after initialisation; the other sequences of the handle
@@ -879,238 +1151,6 @@ static int local_mapping_back(Ctx& c, const std::vector<int>& who, const std::ve
     return local_mapping_back_ok(c, who2, wins2);
 }
 
-static int local_mapping_back_ok(Ctx& c, const std::vector<int>& who, const std::vector<Ctx::Win*>& wins) {
-    typedef Ctx::Win Win;
-    Timer tm;
-    int rc;
-    if (!c.updMap) c.updMap.reset(new MpUpdate);
-    MpUpdate& upd = *c.updMap;
-    Pool& pool = *c.pool;
-    const int flags = c.cfg.local_mapping;
-    const int nW = (int)who.size();
-    auto merge_upd = [&]() { upd.clear(); for (int si : who) { Seq& s = *c.seq[si]; for (int p : s.updList) upd.add(si, p); s.updList.clear(); } };
-    const bool useWin = c.ops.mp_update_windows != nullptr;
-    std::vector<std::vector<int32_t>> cullOut;   // [w][4 per candidate] device counts (empty: host path)
-    std::vector<std::vector<int32_t>> cullIds;
-    std::vector<oslam_job_cull_t> cullJobs;
-    static const bool cull_dev = !getenv("OSLAM_SLAM_CULL_HOST");
-    static const bool cull_check = getenv("OSLAM_SLAM_CULL_CHECK") != nullptr;   // debugging: every device verdict is compared with the host count
-    struct CullStats { std::atomic<long long> dev{0}, amb{0}, after{0}; ~CullStats() { fprintf(stderr, "[cull stats] candidates decided from device counts %lld, ambiguous (host recount) %lld, after a cull of the pass (host) %lld\n", dev.load(), amb.load(), after.load()); } };
-    static CullStats* cull_stats = getenv("OSLAM_SLAM_CULL_STATS") ? new CullStats : nullptr;
-    static struct CullStatsAtExit { ~CullStatsAtExit() { delete cull_stats; } } cull_stats_at_exit;
-    bool cull_requested = false, cull_collected = false;
-    auto request_cull = [&]() -> int {
-        cull_requested = true;
-        if (!((flags & 16) && cull_dev && c.ops.map_journal && c.ops.kf_culling_counts)) { cull_collected = true; return OSLAM_OK; }
-        cullOut.resize(nW); cullIds.resize(nW);
-        std::vector<oslam_map_changes_t> chg(nW), chs;
-        std::vector<uint8_t> has(nW, 0);
-        std::vector<oslam_job_cull_t> jobs;
-        if (c.jrScratch.size() < (size_t)c.S) c.jrScratch.resize(c.S);
-        pool.parallel_for(nW, [&](int w) { Seq& s = *c.seq[who[w]]; if (s.map.jr_pending()) { s.map.journal_changes(who[w], c.thDepth, c.jrScratch[who[w]], chg[w]); has[w] = 1; } });
-        for (int w = 0; w < nW; w++) {
-            Seq& s = *c.seq[who[w]];
-            Map& m = s.map;
-            if (has[w]) chs.push_back(chg[w]);
-            if (m.lvlOverflow) continue;
-            for (int k : m.kfs[s.curKF].ordered) if (k != 0) cullIds[w].push_back(k);
-            if (cullIds[w].empty()) continue;
-            cullOut[w].assign(cullIds[w].size() * 4, 0);
-            oslam_job_cull_t j; j.slot = who[w]; j.n = (int32_t)cullIds[w].size(); j.kf_ids = cullIds[w].data(); j.out = cullOut[w].data();
-            jobs.push_back(j);
-        }
-        int rc2;
-        if (!chs.empty() && (rc2 = c.ops.map_journal(c.ops.ctx, (int)chs.size(), chs.data()))) return rc2;
-        cullJobs.swap(jobs);   // (the jobs name arrays of cullIds / cullOut: all stay alive until the collection)
-        if (!cullJobs.empty() && (rc2 = c.ops.kf_culling_counts(c.ops.ctx, (int)cullJobs.size(), cullJobs.data(), c.thDepth))) return rc2;
-        if (!c.ops.kf_culling_collect) cull_collected = true;
-        { const double d_ = tm.lap(); c.sec[7] += d_; c.sec[13] += d_; c.cpu[7] += tm.cpu; c.cpu[13] += tm.cpu; }
-        return OSLAM_OK;
-    };
-    if (flags & 8) {
-        pool.parallel_for((int)wins.size(), [&](int wi) {
-            Win& W = *wins[wi];
-            Seq& s = *c.seq[W.si];
-            Map& m = s.map;
-            // erase list: mono edges first, then stereo edges (:711-757)
-            for (int pass = 0; pass < 2; pass++)
-                for (size_t e = 0; e < W.ekf.size(); e++) {
-                    if (!W.erase[e]) continue;
-                    const bool stereo = W.eobs[e * 3 + 2] >= 0;
-                    if ((pass == 1) != stereo) continue;
-                    const int k = W.eref[e].first, p = W.eref[e].second;
-                    const int idx = m.mps[p].obs_index(k);
-                    if (idx >= 0) m.set_kf_mp(k, idx, -1);
-                    m.erase_observation(p, k);
-                }
-            for (int q = 0; q < W.nFree; q++) {   // (the local keyframes a degraded window held fixed keep their poses)
-                M4 T; memcpy(T.m, &W.poses_out[(size_t)q * 16], 64);
-                m.kfs[W.kfs[q]].pose.set_keyframe(T);
-            }
-            if (!useWin) {
-                for (size_t j = 0; j < W.pts.size(); j++) {
-                    if (j + kPF < W.pts.size()) __builtin_prefetch(&m.mps[W.pts[j + kPF]]);
-                    MapPt& mp = m.mps[W.pts[j]];
-                    for (int d = 0; d < 3; d++) mp.pos[d] = W.points_out[j * 3 + d];
-                    s.updList.push_back(W.pts[j]);
-                }
-                return;
-            }
-            // UpdateNormalAndDepth from the window itself (oslam_job_mp_window_t): per point only the reference keyframe's window index and level scale factor
-            // are looked up here; the positions are written together with the results below.  A point with an observation the window does not carry, or
-            // whose reference keyframe's observation is not among its surviving edges, takes the general path (position now, update through mp_update).
-            const size_t nP = W.pts.size(), nK = W.kfs.size();
-            std::vector<int>& slot = s.counter;   // keyframe id -> window index + 1 (restored to 0 below)
-            for (size_t q = 0; q < nK; q++) slot[W.kfs[q]] = (int)q + 1;
-            W.uOw.resize(nK * 3);
-            for (size_t q = 0; q < nK; q++) memcpy(&W.uOw[q * 3], m.kfs[W.kfs[q]].pose.Ow, 12);
-            W.uskip.assign(nP, 0); W.uref.assign(nP, 0); W.ulsf.assign(nP, 1.f); W.uout5.resize(nP * 5 + 5);
-            for (size_t j = 0; j < nP; j++) {
-                const int p = W.pts[j];
-                if (j + kPF < nP && !m.pBad[W.pts[j + kPF]]) __builtin_prefetch(&m.mps[W.pts[j + kPF]].refKF);
-                if (m.pBad[p]) { W.uskip[j] = 1; continue; }
-                int q = -1, eRef = -1;
-                if (!W.pquirk[j]) {
-                    const int rk = m.mps[p].refKF;
-                    q = rk >= 0 ? slot[rk] - 1 : -1;
-                    if (q >= 0)
-                        for (int e = W.pstart[j]; e < W.pstart[j + 1]; e++)
-                            if (W.ekf[e] == q && !W.erase[e]) { eRef = e; break; }
-                }
-                if (eRef < 0) {   // general path
-                    W.uskip[j] = 2;
-                    MapPt& mp = m.mps[p];
-                    for (int d = 0; d < 3; d++) mp.pos[d] = W.points_out[j * 3 + d];
-                    s.updList.push_back(p);
-                    continue;
-                }
-                W.uref[j] = q; W.ulsf[j] = c.scale[W.eoct[eRef]];
-            }
-            for (size_t q = 0; q < nK; q++) slot[W.kfs[q]] = 0;
-        });
-        // the observation lists are final for this pass (the MapPoint updates below do not touch them): the culling counts are requested now and collected after them
-        { const double d_ = tm.lap(); c.sec[7] += d_; c.sec[12] += d_; c.cpu[7] += tm.cpu; c.cpu[12] += tm.cpu; }
-        if ((rc = request_cull())) return rc;
-        if (useWin && !wins.empty()) {
-            { const double d_ = tm.lap(); c.sec[7] += d_; c.sec[12] += d_; c.cpu[7] += tm.cpu; c.cpu[12] += tm.cpu; }
-            std::vector<oslam_job_mp_window_t> wj(wins.size());
-            for (size_t wi = 0; wi < wins.size(); wi++) {
-                Win& W = *wins[wi];
-                oslam_job_mp_window_t& j = wj[wi];
-                j.slot = W.si; j.nP = (int32_t)W.pts.size(); j.nE = (int32_t)W.ekf.size(); j.nK = (int32_t)W.kfs.size();
-                j.pt_ids = W.pts.data(); j.pt_start = W.pstart.data(); j.edge_kf = W.ekf.data(); j.erase = W.erase.data(); j.skip = W.uskip.data(); j.ref_kf = W.uref.data();
-                j.lsf = W.ulsf.data(); j.Ow = W.uOw.data(); j.pos = W.points_out.data(); j.out5 = W.uout5.data();
-            }
-            if ((rc = c.ops.mp_update_windows(c.ops.ctx, (int)wj.size(), wj.data()))) return rc;
-            { c.sec[5] += tm.lap(); c.cpu[5] += tm.cpu; }
-            pool.parallel_for((int)wins.size(), [&](int wi) {
-                Win& W = *wins[wi];
-                Map& m = c.seq[W.si]->map;
-                for (size_t j = 0; j < W.pts.size(); j++) {
-                    if (j + kPF < W.pts.size() && W.uskip[j + kPF] != 2) __builtin_prefetch(&m.mps[W.pts[j + kPF]]);
-                    if (W.uskip[j] == 2) continue;   // (took the general path: position already written)
-                    MapPt& mp = m.mps[W.pts[j]];
-                    for (int d = 0; d < 3; d++) mp.pos[d] = W.points_out[j * 3 + d];
-                    if (W.uskip[j]) continue;
-                    const float* o = &W.uout5[j * 5];
-                    mp.normal[0] = o[0]; mp.normal[1] = o[1]; mp.normal[2] = o[2]; mp.maxD = o[3]; mp.minD = o[4];
-                }
-            });
-        }
-        merge_upd();
-        { const double d_ = tm.lap(); c.sec[7] += d_; c.sec[12] += d_; c.cpu[7] += tm.cpu; c.cpu[12] += tm.cpu; }
-        if ((rc = upd.run(c, false, true))) return rc;
-        { c.sec[5] += tm.lap(); c.cpu[5] += tm.cpu; }
-    }
-    // --- KeyFrameCulling (:633-697) ---
-    // Round 5: the counting loop of the candidates runs on the device from the table's mirror of the observation graph (oslam_slam_ops_t::map_journal /
-    // kf_culling_counts); the host takes the verdicts in the reference's order.  SetBadFlag changes the counts of the candidates behind a culled keyframe, so from
-    // the first cull of a pass on — and for a keyframe the mirror flags as ambiguous, and for a map whose octave histogram overflowed — the host counts itself.
-    if (!cull_requested && (rc = request_cull())) return rc;   // (a pass without local BA)
-    if (!cull_collected) { if ((rc = c.ops.kf_culling_collect(c.ops.ctx))) return rc; cull_collected = true; }
-    if (flags & 16)
-        pool.parallel_for(nW, [&](int w) {
-            Seq& s = *c.seq[who[w]];
-            Map& m = s.map;
-            const std::vector<int> local = m.kfs[s.curKF].ordered;
-            const bool useHist = !m.lvlOverflow;
-            const int32_t* dev = (!cullOut.empty() && !cullOut[w].empty()) ? cullOut[w].data() : nullptr;
-            bool culled_any = false;
-            long long n_dev = 0, n_amb = 0, n_after = 0;
-            int qi = 0;   // index of the candidate among the non-zero ids (cullIds order)
-            for (int k : local) {
-                if (k == 0) continue;
-                const int q = qi++;
-                if (dev) { if (culled_any) n_after++; else if (dev[4 * q + 3] != 0) n_amb++; else n_dev++; }
-                if (dev && !culled_any && dev[4 * q + 3] == 0) {
-                    const int ub = dev[4 * q], nMPs = dev[4 * q + 1], nRed = dev[4 * q + 2];
-                    const int keepAt = ub / 10 + 2;
-                    const bool cull = (nMPs - nRed < keepAt) && (nRed > 0.9 * nMPs);
-                    if (cull_check) {
-                        const KeyFrm& kfc = m.kfs[k];
-                        int ub2 = 0, r2 = 0, n2 = 0;
-                        for (int i = 0; i < kfc.N; i++) {
-                            const int p = kfc.mp[i];
-                            const bool good = !(kfc.depth[i] > c.thDepth || kfc.depth[i] < 0);
-                            ub2 += p >= 0 && good;
-                            if (p < 0 || m.pBad[p] || !good) continue;
-                            n2++;
-                            if (m.pNObs[p] > 3) {
-                                int nn = 0;
-                                const MapPt& mq = m.mps[p];
-                                for (size_t oi = 0; oi < mq.obs.size(); oi++) if (mq.obs[oi].first != k && mq.okp[oi].octave <= kfc.oct[i] + 1) nn++;
-                                r2 += nn >= 3;
-                            }
-                        }
-                        if (ub2 != ub || n2 != nMPs || r2 != nRed) { fprintf(stderr, "OSLAM_SLAM_CULL_CHECK: sequence %d keyframe %d: device (%d, %d, %d), host (%d, %d, %d)\n", who[w], k, ub, nMPs, nRed, ub2, n2, r2); abort(); }
-                    }
-                    if (cull) { m.set_bad_keyframe(k); s.st[11]++; s.culledKFs.push_back(k); culled_any = true; }
-                    continue;
-                }
-                const KeyFrm& kf = m.kfs[k];
-                // The verdict is nRed > 0.9 * nMPs.  nMPs is at most the number of slots that hold a point at a usable depth (counted from the keyframe's own
-                // arrays, no map access), so once the points found NOT redundant reach a tenth of that bound (+ 2: away from the rounding of 0.9 * nMPs) the keyframe
-                // stays whatever the remaining slots hold, and the walk over their observation lists is skipped.  Most keyframes leave the loop this way.
-                int ub = 0;
-                for (int i = 0; i < kf.N; i++) ub += kf.mp[i] >= 0 && !(kf.depth[i] > c.thDepth || kf.depth[i] < 0);
-                const int keepAt = ub / 10 + 2;
-                int nRed = 0, nMPs = 0;
-                for (int i = 0; i < kf.N && nMPs - nRed < keepAt; i++) {
-                    if (!useHist) prefetch_okp_ahead(m.mps, kf.mp, i, kf.N);
-                    const int p = kf.mp[i];
-                    if (p < 0 || m.pBad[p]) continue;
-                    if (kf.depth[i] > c.thDepth || kf.depth[i] < 0) continue;
-                    nMPs++;
-                    if (m.pNObs[p] > 3) {
-                        const int lvl = kf.oct[i];
-                        // "three OTHER observations at octave <= lvl + 1": the point's octave histogram counts ALL its observations there; with four or more the
-                        // answer is yes and with two or fewer no, whether or not this keyframe's own observation is among them (Map::pLvl).  Exactly three: the lists.
-                        const int all_le = useHist ? m.lvl_count_le(p, lvl + 1) : 3;
-                        if (all_le != 3) { nRed += all_le >= 4; continue; }
-                        int n = 0;
-                        const MapPt& mq = m.mps[p];
-                        for (size_t oi = 0; oi < mq.obs.size(); oi++) {
-                            if (mq.obs[oi].first == k) continue;
-                            if (mq.okp[oi].octave <= lvl + 1) { n++; if (n >= 3) break; }   // (the observing keypoint's octave, cached beside the observation: slam_map.h ObsKp)
-                        }
-                        if (n >= 3) nRed++;
-                    }
-                }
-                if (nMPs - nRed < keepAt && nRed > 0.9 * nMPs) { m.set_bad_keyframe(k); s.st[11]++; s.culledKFs.push_back(k); culled_any = true; }
-            }
-            if (cull_stats) { cull_stats->dev += n_dev; cull_stats->amb += n_amb; cull_stats->after += n_after; }
-        });
-    if (c.ops.release_keyframes) {   // the table may recycle the resident records of the keyframes culled above
-        std::vector<int32_t> rs, rk;
-        for (int si : who) { Seq& s = *c.seq[si]; for (int k : s.culledKFs) { rs.push_back(si); rk.push_back(k); } s.culledKFs.clear(); }
-        if (!rs.empty() && (rc = c.ops.release_keyframes(c.ops.ctx, (int)rs.size(), rs.data(), rk.data()))) return rc;
-    } else
-        for (int si : who) c.seq[si]->culledKFs.clear();
-    { const double d_ = tm.lap(); c.sec[7] += d_; c.sec[13] += d_; c.cpu[7] += tm.cpu; c.cpu[13] += tm.cpu; }
-    return OSLAM_OK;
-}
-
-
 // Deferred schedule: what is left of the previous step's local-mapping pass.  Waits for the local BA in flight (or runs it now when the table has no
 // asynchronous form), then write-back, MapPoint updates and KeyFrameCulling.
 static int finish_local_mapping(Ctx& c) {
@@ -1130,22 +1170,13 @@ static int finish_local_mapping(Ctx& c) {
     return local_mapping_back(c, pd.who, pd.wins);
 }
 
-static int run_local_mapping(Ctx& c, const std::vector<int>& who) {
-    if (who.empty()) return OSLAM_OK;
-    Timer tm;
+// ---- first half of a pass: the steps of LocalMapping::Run up to the local-BA solve ----
+// ProcessNewKeyFrame (:129-169), then UpdateConnections and MapPointCulling (:171-206)
+static int lm_process_new_keyframe(LmPass& L) {
+    Ctx& c = L.c;
     int rc;
-    if (!c.updMap) c.updMap.reset(new MpUpdate);
-    MpUpdate& upd = *c.updMap;
-    upd.clear();
-    const int flags = c.cfg.local_mapping;
-    // --- ProcessNewKeyFrame (:129-169) ---
-    Pool& pool = *c.pool;
-    const int nW = (int)who.size();
-    for (int si : who) c.seq[si]->mapVersion++;   // the map of these sequences changes below: their cached local maps are stale
-    c.mapStep++;
-    auto merge_upd = [&]() { upd.clear(); for (int si : who) { Seq& s = *c.seq[si]; for (int p : s.updList) upd.add(si, p); s.updList.clear(); } };
-    pool.parallel_for(nW, [&](int w) {
-        Seq& s = *c.seq[who[w]];
+    L.pool.parallel_for(L.nW, [&](int w) {
+        Seq& s = L.seq(w);
         Map& m = s.map;
         s.updList.clear();
         s.curKF = s.newKFs.front();
@@ -1160,666 +1191,617 @@ static int run_local_mapping(Ctx& c, const std::vector<int>& who) {
             else s.recentAdded.push_back(p);
         }
     });
-    merge_upd();
-    { const double d_ = tm.lap(); c.sec[7] += d_; c.sec[9] += d_; c.cpu[7] += tm.cpu; c.cpu[9] += tm.cpu; }
-    if ((rc = upd.run(c, true, true))) return rc;
-    { c.sec[5] += tm.lap(); c.cpu[5] += tm.cpu; }
-    pool.parallel_for(nW, [&](int w) {
-        Seq& s = *c.seq[who[w]];
+    L.merge_upd();
+    L.charge(9);
+    if ((rc = L.upd.run(c, true, true))) return rc;
+    L.charge_op(5);
+    L.pool.parallel_for(L.nW, [&](int w) {
+        Seq& s = L.seq(w);
         s.map.update_connections(s.curKF, s.counter);
         s.map.nKFsInMap++;
-        if (flags & 1) map_point_culling(s);
+        if (L.flags & 1) map_point_culling(s);
     });
-    { const double d_ = tm.lap(); c.sec[7] += d_; c.sec[9] += d_; c.cpu[7] += tm.cpu; c.cpu[9] += tm.cpu; }
+    L.charge(9);
+    return OSLAM_OK;
+}
 
-    // --- CreateNewMapPoints (:208-453) ---
-    // The reference handles the neighbours one after the other, and neighbour i sees the points created from neighbours < i in exactly one way: a keypoint of the
-    // current keyframe that has received a point is skipped (`if(pMP1) continue`, src/ORBmatcher.cc:711-716).  Everything else a neighbour's search and
-    // triangulation read is fixed during the pass: the poses, the neighbour's own map points (a neighbour occurs once, and new points only touch the current
-    // keyframe and THEIR neighbour), and — SearchForTriangulation never sets vbMatched2 — every keypoint of the current keyframe picks its partner independently
-    // of the others.  So ALL neighbours of all sequences are searched and triangulated in ONE batch each from the state before the pass, and the results are
-    // applied in neighbour order with the skip test at application time: the same points in the same order as the reference's loop, with 3 operator calls instead
-    // of 3 per neighbour round.  OSLAM_SLAM_CNMP_ROUNDS=1 keeps the lockstep rounds (A/B: bit-identical runs, tests/test_slam_driver_gpu.py).
-    const bool cnmp_rounds = getenv("OSLAM_SLAM_CNMP_ROUNDS") != nullptr;
-    if ((flags & 2) && !cnmp_rounds) {
-        struct Pair { int w, ni, k2; };
-        std::vector<std::vector<int>> neigh(who.size());
-        std::vector<Pair> pairs;
-        for (size_t w = 0; w < who.size(); w++) {
-            Seq& s = *c.seq[who[w]];
-            const Map::IntSpan bc = s.map.best_covisibles(s.curKF, 10);
-            neigh[w].assign(bc.begin(), bc.end());
-            for (size_t ni = 0; ni < neigh[w].size(); ni++) pairs.push_back({(int)w, (int)ni, neigh[w][ni]});
-        }
-        const int nPairs = (int)pairs.size();
-        std::vector<std::vector<uint8_t>> flag1(who.size());
-        pool.parallel_for(nW, [&](int w) {
-            Seq& s = *c.seq[who[w]];
-            const KeyFrm& k1 = s.map.kfs[s.curKF];
-            flag1[w].resize(k1.N);
-            for (int i = 0; i < k1.N; i++) flag1[w][i] = k1.mp[i] >= 0;
-            (void)s.bow_views(c, s.curKF);   // (built once per keyframe: not from several pair jobs at a time)
-            for (int k2 : neigh[w]) (void)s.bow_views(c, k2);
-        });
-        std::vector<std::vector<uint8_t>> has2(nPairs);
-        std::vector<std::vector<int32_t>> match(nPairs);
-        std::vector<oslam_job_bow_t> cand(nPairs);
-        std::vector<uint8_t> have(nPairs, 0);
-        pool.parallel_for(nPairs, [&](int q) {
-            const Pair& pq = pairs[q];
-            Seq& s = *c.seq[who[pq.w]];
-            Map& m = s.map;
-            const KeyFrm& k1 = m.kfs[s.curKF];
-            KeyFrm& k2 = m.kfs[pq.k2];
-            const float vb[3] = {k2.pose.Ow[0] - k1.pose.Ow[0], k2.pose.Ow[1] - k1.pose.Ow[1], k2.pose.Ow[2] - k1.pose.Ow[2]};
-            if (norm3(vb) < c.mb) return;   // :251-254
-            oslam_job_bow_t& j = cand[q];
-            memset(&j, 0, sizeof(j));
-            compute_F12(c, k1, k2, j.F12);
-            // epipole of camera 1 in image 2 (src/ORBmatcher.cc:663-670)
-            float C2[3];
-            for (int r = 0; r < 3; r++) {
-                float sacc = k2.pose.Tcw.m[r * 4] * k1.pose.Ow[0];
-                sacc += k2.pose.Tcw.m[r * 4 + 1] * k1.pose.Ow[1];
-                sacc += k2.pose.Tcw.m[r * 4 + 2] * k1.pose.Ow[2];
-                C2[r] = (float)((double)sacc + (double)k2.pose.Tcw.m[r * 4 + 3]);
-            }
-            const float invz = 1.0f / C2[2];
-            j.ex = c.cfg.fx * C2[0] * invz + c.cfg.cx; j.ey = c.cfg.fy * C2[1] * invz + c.cfg.cy;
-            const BowViews& v1 = s.bow_views(c, s.curKF);
-            const BowViews& v2 = s.bow_views(c, pq.k2);
-            has2[q].resize(k2.N);
-            for (int i = 0; i < k2.N; i++) has2[q][i] = k2.mp[i] >= 0;
-            match[q].assign(k1.N, -1);
-            j.s1.N = k1.N; j.s1.keys = k1.keysUn.data(); j.s1.desc = k1.desc.data(); j.s1.uRight = k1.uRight.data(); j.s1.flag = flag1[pq.w].data();
-            j.s1.nq = k1.N; j.s1.q_idx = v1.q_idx.data(); j.s1.q_node = v1.q_node.data();
-            j.s2.N = k2.N; j.s2.keys = k2.keysUn.data(); j.s2.desc = k2.desc.data(); j.s2.uRight = k2.uRight.data(); j.s2.has_mp = has2[q].data();
-            j.s2.nNodes = (int)v2.nodes.size(); j.s2.nodes = v2.nodes.data(); j.s2.start = v2.start.data(); j.s2.items = v2.items.data();
-            j.triangulation = 1; j.nnratio = 0.6f; j.checkOri = 0; j.match = match[q].data();
-            have[q] = 1;
-        });
-        std::vector<oslam_job_bow_t> bj;
-        std::vector<int> bjq;
-        std::vector<oslam_kf_key_t> bkey;
-        for (int q = 0; q < nPairs; q++)
-            if (have[q]) { bj.push_back(cand[q]); bjq.push_back(q); bkey.push_back({who[pairs[q].w], c.seq[who[pairs[q].w]]->curKF, pairs[q].k2}); }
-        { const double d_ = tm.lap(); c.sec[7] += d_; c.sec[10] += d_; c.cpu[7] += tm.cpu; c.cpu[10] += tm.cpu; }
-        if (!bj.empty()) {
-            if ((rc = c.ops.bow_keyed ? c.ops.bow_keyed(c.ops.ctx, (int)bj.size(), bj.data(), bkey.data()) : c.ops.bow(c.ops.ctx, (int)bj.size(), bj.data()))) return rc;
-            const int nJ = (int)bj.size();
-            std::vector<oslam_job_triangulate_t> tj(nJ);
-            std::vector<std::vector<int32_t>> i1(nJ), i2(nJ);
-            std::vector<std::vector<uint8_t>> okv(nJ);
-            std::vector<std::vector<float>> x3(nJ);
-            pool.parallel_for(nJ, [&](int jq) {
-                const int q = bjq[jq];
-                Seq& s = *c.seq[who[pairs[q].w]];
-                const KeyFrm& k1 = s.map.kfs[s.curKF];
-                // vMatchedIndices order (:815-820): ascending index of keyframe 1
-                for (int i = 0; i < k1.N; i++) if (match[q][i] >= 0) { i1[jq].push_back(i); i2[jq].push_back(match[q][i]); }
-                oslam_job_triangulate_t& t = tj[jq];
-                fill_tri_kf(c, k1, t.kf1); fill_tri_kf(c, s.map.kfs[pairs[q].k2], t.kf2);
-                t.M = (int)i1[jq].size(); t.idx1 = i1[jq].data(); t.idx2 = i2[jq].data();
-                okv[jq].assign(t.M + 1, 0); x3[jq].assign((size_t)t.M * 3 + 3, 0.f);
-                t.ok = okv[jq].data(); t.x3D = x3[jq].data();
-            });
-            if ((rc = c.ops.triangulate(c.ops.ctx, nJ, tj.data()))) return rc;
-            { c.sec[8] += tm.lap(); c.cpu[8] += tm.cpu; }
-            // application in neighbour order per sequence (the jobs of a sequence are consecutive and in neighbour order)
-            std::vector<int> first(who.size() + 1, 0);
-            for (int jq = 0; jq < nJ; jq++) first[pairs[bjq[jq]].w + 1]++;
-            for (size_t w = 0; w < who.size(); w++) first[w + 1] += first[w];
-            pool.parallel_for(nW, [&](int w) {
-                Seq& s = *c.seq[who[w]];
-                Map& m = s.map;
-                for (int jq = first[w]; jq < first[w + 1]; jq++) {
-                    const int k2 = pairs[bjq[jq]].k2;
-                    for (int e = 0; e < tj[jq].M; e++) {
-                        if (!okv[jq][e]) continue;
-                        if (m.kfs[s.curKF].mp[i1[jq][e]] >= 0) continue;   // the keypoint received a point from an earlier neighbour: the reference's search skipped it
-                        const int p = m.new_point(&x3[jq][(size_t)e * 3], s.curKF, m.kfs[s.curKF].frameId);   // :408-430
-                        m.add_observation(p, s.curKF, i1[jq][e]);
-                        m.add_observation(p, k2, i2[jq][e]);
-                        m.set_kf_mp(s.curKF, i1[jq][e], p);
-                        m.set_kf_mp(k2, i2[jq][e], p);
-                        m.nMPsInMap++; s.st[3]++; s.st[10]++;
-                        s.recentAdded.push_back(p);
-                        s.updList.push_back(p);
-                    }
-                }
-            });
-            merge_upd();
-            { const double d_ = tm.lap(); c.sec[7] += d_; c.sec[10] += d_; c.cpu[7] += tm.cpu; c.cpu[10] += tm.cpu; }
-            if ((rc = upd.run(c, true, true))) return rc;
-            { c.sec[5] += tm.lap(); c.cpu[5] += tm.cpu; }
-        }
-    }
-    // the same in lockstep rounds (round i = neighbour i of every sequence; the matches of neighbour i see the points created from neighbour i-1): A/B form
-    if ((flags & 2) && cnmp_rounds) {
-        std::vector<std::vector<int>> neigh(who.size());
-        size_t maxn = 0;
-        for (size_t w = 0; w < who.size(); w++) {
-            Seq& s = *c.seq[who[w]];
-            const Map::IntSpan bc = s.map.best_covisibles(s.curKF, 10);
-            neigh[w].assign(bc.begin(), bc.end());
-            maxn = std::max(maxn, neigh[w].size());
-        }
-        std::vector<std::vector<uint8_t>> flag1(who.size()), has2(who.size());
-        std::vector<std::vector<int32_t>> match(who.size());
-        std::vector<oslam_job_bow_t> bj;
-        std::vector<int> bjw;
-        for (size_t ni = 0; ni < maxn; ni++) {
-            bj.clear(); bjw.clear();
-            std::vector<oslam_job_bow_t> cand(who.size());
-            std::vector<uint8_t> have(who.size(), 0);
-            pool.parallel_for(nW, [&](int w) {
-                if (ni >= neigh[w].size()) return;
-                Seq& s = *c.seq[who[w]];
-                Map& m = s.map;
-                const KeyFrm& k1 = m.kfs[s.curKF];
-                KeyFrm& k2 = m.kfs[neigh[w][ni]];
-                const float vb[3] = {k2.pose.Ow[0] - k1.pose.Ow[0], k2.pose.Ow[1] - k1.pose.Ow[1], k2.pose.Ow[2] - k1.pose.Ow[2]};
-                if (norm3(vb) < c.mb) return;   // :251-254
-                oslam_job_bow_t& j = cand[w];
-                memset(&j, 0, sizeof(j));
-                compute_F12(c, k1, k2, j.F12);
-                // epipole of camera 1 in image 2 (src/ORBmatcher.cc:663-670)
-                float C2[3];
-                for (int r = 0; r < 3; r++) {
-                    float sacc = k2.pose.Tcw.m[r * 4] * k1.pose.Ow[0];
-                    sacc += k2.pose.Tcw.m[r * 4 + 1] * k1.pose.Ow[1];
-                    sacc += k2.pose.Tcw.m[r * 4 + 2] * k1.pose.Ow[2];
-                    C2[r] = (float)((double)sacc + (double)k2.pose.Tcw.m[r * 4 + 3]);
-                }
-                const float invz = 1.0f / C2[2];
-                j.ex = c.cfg.fx * C2[0] * invz + c.cfg.cx; j.ey = c.cfg.fy * C2[1] * invz + c.cfg.cy;
-                const BowViews& v1 = s.bow_views(c, s.curKF);
-                const BowViews& v2 = s.bow_views(c, neigh[w][ni]);
-                flag1[w].resize(k1.N); has2[w].resize(k2.N);
-                for (int i = 0; i < k1.N; i++) flag1[w][i] = k1.mp[i] >= 0;
-                for (int i = 0; i < k2.N; i++) has2[w][i] = k2.mp[i] >= 0;
-                match[w].assign(k1.N, -1);
-                j.s1.N = k1.N; j.s1.keys = k1.keysUn.data(); j.s1.desc = k1.desc.data(); j.s1.uRight = k1.uRight.data(); j.s1.flag = flag1[w].data();
-                j.s1.nq = k1.N; j.s1.q_idx = v1.q_idx.data(); j.s1.q_node = v1.q_node.data();
-                j.s2.N = k2.N; j.s2.keys = k2.keysUn.data(); j.s2.desc = k2.desc.data(); j.s2.uRight = k2.uRight.data(); j.s2.has_mp = has2[w].data();
-                j.s2.nNodes = (int)v2.nodes.size(); j.s2.nodes = v2.nodes.data(); j.s2.start = v2.start.data(); j.s2.items = v2.items.data();
-                j.triangulation = 1; j.nnratio = 0.6f; j.checkOri = 0; j.match = match[w].data();
-                have[w] = 1;
-            });
-            std::vector<oslam_kf_key_t> bkey;
-            for (size_t w = 0; w < who.size(); w++)
-                if (have[w]) { bj.push_back(cand[w]); bjw.push_back((int)w); bkey.push_back({who[w], c.seq[who[w]]->curKF, neigh[w][ni]}); }
-            if (bj.empty()) continue;
-            { const double d_ = tm.lap(); c.sec[7] += d_; c.sec[10] += d_; c.cpu[7] += tm.cpu; c.cpu[10] += tm.cpu; }
-            if ((rc = c.ops.bow_keyed ? c.ops.bow_keyed(c.ops.ctx, (int)bj.size(), bj.data(), bkey.data()) : c.ops.bow(c.ops.ctx, (int)bj.size(), bj.data()))) return rc;
-            std::vector<oslam_job_triangulate_t> tj(bj.size());
-            std::vector<std::vector<int32_t>> i1(bj.size()), i2(bj.size());
-            std::vector<std::vector<uint8_t>> okv(bj.size());
-            std::vector<std::vector<float>> x3(bj.size());
-            pool.parallel_for((int)bj.size(), [&](int q) {
-                const size_t w = bjw[q];
-                Seq& s = *c.seq[who[w]];
-                const KeyFrm& k1 = s.map.kfs[s.curKF];
-                // vMatchedIndices order (:815-820): ascending index of keyframe 1
-                for (int i = 0; i < k1.N; i++) if (match[w][i] >= 0) { i1[q].push_back(i); i2[q].push_back(match[w][i]); }
-                oslam_job_triangulate_t& t = tj[q];
-                fill_tri_kf(c, k1, t.kf1); fill_tri_kf(c, s.map.kfs[neigh[w][ni]], t.kf2);
-                t.M = (int)i1[q].size(); t.idx1 = i1[q].data(); t.idx2 = i2[q].data();
-                okv[q].assign(t.M + 1, 0); x3[q].assign((size_t)t.M * 3 + 3, 0.f);
-                t.ok = okv[q].data(); t.x3D = x3[q].data();
-            });
-            if ((rc = c.ops.triangulate(c.ops.ctx, (int)tj.size(), tj.data()))) return rc;
-            { c.sec[8] += tm.lap(); c.cpu[8] += tm.cpu; }
-            pool.parallel_for((int)bj.size(), [&](int q) {   // one job per sequence: independent maps
-                const size_t w = bjw[q];
-                Seq& s = *c.seq[who[w]];
-                Map& m = s.map;
-                const int k2 = neigh[w][ni];
-                for (int e = 0; e < tj[q].M; e++) {
-                    if (!okv[q][e]) continue;
-                    const int p = m.new_point(&x3[q][(size_t)e * 3], s.curKF, m.kfs[s.curKF].frameId);   // :408-430
-                    m.add_observation(p, s.curKF, i1[q][e]);
-                    m.add_observation(p, k2, i2[q][e]);
-                    m.set_kf_mp(s.curKF, i1[q][e], p);
-                    m.set_kf_mp(k2, i2[q][e], p);
-                    m.nMPsInMap++; s.st[3]++; s.st[10]++;
-                    s.recentAdded.push_back(p);
-                    s.updList.push_back(p);
-                }
-            });
-            merge_upd();
-            { const double d_ = tm.lap(); c.sec[7] += d_; c.sec[10] += d_; c.cpu[7] += tm.cpu; c.cpu[10] += tm.cpu; }
-            if ((rc = upd.run(c, true, true))) return rc;
-            { c.sec[5] += tm.lap(); c.cpu[5] += tm.cpu; }
-        }
-    }
+// --- CreateNewMapPoints (:208-453) ---
+// The reference handles the neighbours one after the other, and neighbour i sees the points created from neighbours < i in exactly one way: a keypoint of the
+// current keyframe that has received a point is skipped (`if(pMP1) continue`, src/ORBmatcher.cc:711-716).  Everything else a neighbour's search and
+// triangulation read is fixed during the pass: the poses, the neighbour's own map points (a neighbour occurs once, and new points only touch the current
+// keyframe and THEIR neighbour), and — SearchForTriangulation never sets vbMatched2 — every keypoint of the current keyframe picks its partner independently
+// of the others.  So ALL neighbours of all sequences are searched and triangulated in ONE batch each from the state before the pass, and the results are
+// applied in neighbour order with the skip test at application time: the same points in the same order as the reference's loop, with 3 operator calls instead
+// of 3 per neighbour round.  OSLAM_SLAM_CNMP_ROUNDS=1 keeps the lockstep rounds (A/B: bit-identical runs, tests/test_slam_driver_gpu.py, test_slam_driver_cpu.py).
+struct CnmpPair { int w, k2; };   // the current keyframe of sequence who[w] against its neighbour k2
+struct CnmpTri { std::vector<int32_t> i1, i2; std::vector<uint8_t> ok; std::vector<float> x3; };   // the arrays of one triangulation job
 
-    // --- SearchInNeighbors (:455-535) ---
-    // The target keyframes of one sequence are fused one after the other like the reference's loop (a fusion changes descriptors and
-    // observations the next target sees); round t handles target t of every sequence in one batch.
-    if (flags & 4) {
-        // badf / mask / dup / slotOf / touched: what only the host knows of ORBmatcher::Fuse's gates (:849: the point is bad, or already observed in the target) for
-        // the points of the current keyframe against ALL targets, computed once before the rounds (bit t of mask[i] = point i is observed in the keyframe with
-        // slot t) and refreshed after every round for the points that round changed — instead of a pass over all ~1000 point records and their observation
-        // lists per round and sequence.
-        struct FuseSeq {
-            std::vector<int> targets; std::vector<int> pts; std::vector<oslam_proj_query_t> q; std::vector<int> qpt; std::vector<int32_t> qm; std::vector<uint8_t> excl; int kf;
-            std::vector<uint8_t> badf, slotOf; std::vector<uint64_t> mask; std::vector<int> dup, touched; bool cached = false;
-        };
-        static const bool excl_check = getenv("OSLAM_SLAM_FUSE_EXCL_CHECK") != nullptr;   // debugging: compare the cached flags with the full pass every round
-        static const bool excl_cache = !getenv("OSLAM_SLAM_FUSE_EXCL_FULL");               // A/B knob: the full pass every round
-        const bool fuse_by_id = c.residentPts && c.ops.fuse_points_keyed != nullptr;   // the table runs the projection gates itself from its map-point records
-        // A round's descriptor updates (MapPoint::Replace -> ComputeDistinctiveDescriptors) are handed to the table WITHOUT a wait (mp_update_keyed_async): the table launches
-        // them right in front of the NEXT round's search, so one wait covers both — one device round trip per round instead of two.  Same-box A/B, alternating,
-        // identical results: 39.7 / 40.9 k against 38.6 / 40.6 k frames/s.  (The first form enqueued the update kernel at once and let it run beside the round's host
-        // bookkeeping: 33.4 / 35.4 k against 36.1 / 37.8 k — slower; OSLAM_SLAM_MPU_SYNC=1 restores the wait per update.)
-        static const bool mpu_async = getenv("OSLAM_SLAM_MPU_SYNC") == nullptr;
-        std::vector<oslam_job_fuse_pts_t> pjobs;
-        std::vector<FuseSeq> fs(who.size());
-        std::vector<oslam_job_fuse_t> jobs;
-        std::vector<int> jw;
-        std::vector<oslam_kf_key_t> fkey;
-        size_t maxt = 0;
-        pool.parallel_for(nW, [&](int w) {
-            Seq& s = *c.seq[who[w]];
-            Map& m = s.map;
-            const int cur = s.curKF;
-            for (int k : m.best_covisibles(cur, 10)) {
-                if (m.kfs[k].bad || m.kfs[k].fuseTargetForKF == cur) continue;
-                fs[w].targets.push_back(k);
-                m.kfs[k].fuseTargetForKF = cur;
-                for (int k2 : m.best_covisibles(k, 5)) {
-                    if (m.kfs[k2].bad || m.kfs[k2].fuseTargetForKF == cur || k2 == cur) continue;
-                    fs[w].targets.push_back(k2);
-                }
-            }
-            fs[w].pts.assign(m.kfs[cur].mp.begin(), m.kfs[cur].mp.end());   // vpMapPointMatches snapshot (:484)
-            FuseSeq& f = fs[w];
-            f.cached = false;
-            if (!fuse_by_id || !excl_cache) return;
-            f.slotOf.assign(m.kfs.size(), 255);
-            int nslot = 0;
-            for (int k : f.targets) if (f.slotOf[k] == 255) f.slotOf[k] = (uint8_t)nslot++;   // (the target list may name a keyframe twice, like the reference's)
-            if (nslot > 64) return;   // (cannot happen with 10 + 10 x 5 targets; the full pass serves it)
-            const size_t n = f.pts.size();
-            f.badf.assign(n, 1); f.mask.assign(n, 0); f.dup.assign(n, -1); f.touched.clear();
-            const int stamp = cur + 1;
-            for (size_t pi = 0; pi < n; pi++) {
-                prefetch_obs_ahead(m.mps, f.pts, pi, n);
-                const int p = f.pts[pi];
-                if (p < 0) continue;
-                MapPt& mp = m.mps[p];
-                if (mp.fuseListStamp == stamp) f.dup[pi] = mp.fuseListIdx;   // the same point at two keypoints of the keyframe: a chain through its positions
-                mp.fuseListStamp = stamp; mp.fuseListIdx = (int)pi;
-                f.badf[pi] = m.pBad[p] ? 1 : 0;
-                uint64_t mk = 0;
-                for (auto& e : mp.obs) { const uint8_t sl = f.slotOf[e.first]; if (sl != 255) mk |= 1ull << sl; }
-                f.mask[pi] = mk;
-            }
-            f.cached = true;
-        });
-        auto fine = [&](int i) { const double d_ = tm.lap(); c.sec[7] += d_; c.sec[11] += d_; c.cpu[7] += tm.cpu; c.cpu[11] += tm.cpu; c.fine[i] += tm.cpu; };
-        fine(0);
-        auto refresh_touched = [&](Seq& s, FuseSeq& f) {   // after a round: the points it changed, if they are in the list
-            const Map& m = s.map;
-            const int stamp = s.curKF + 1;
-            for (int x : f.touched) {
-                const MapPt& mp = m.mps[x];
-                if (mp.fuseListStamp != stamp) continue;
-                uint64_t mk = 0;
-                for (auto& e : mp.obs) { const uint8_t sl = (size_t)e.first < f.slotOf.size() ? f.slotOf[e.first] : 255; if (sl != 255) mk |= 1ull << sl; }
-                for (int pi = mp.fuseListIdx; pi >= 0; pi = f.dup[pi]) { f.badf[pi] = m.pBad[x] ? 1 : 0; f.mask[pi] = mk; }
-            }
-            f.touched.clear();
-        };
-        for (size_t w = 0; w < who.size(); w++) maxt = std::max(maxt, fs[w].targets.size());
-        auto fuse_round_by_id = [&](bool into_current, size_t t) -> int {
-            jw.clear(); pjobs.clear();
-            pool.parallel_for(nW, [&](int w) {
-                Seq& s = *c.seq[who[w]];
-                fs[w].kf = -1;
-                if (!into_current && t >= fs[w].targets.size()) return;
-                if (into_current && fs[w].targets.empty()) return;
-                const int k = into_current ? s.curKF : fs[w].targets[t];
-                fs[w].kf = k;
-                const Map& m = s.map;
-                const std::vector<int>& pts = fs[w].pts;
-                fs[w].excl.assign(pts.size() + 1, 1);
-                bool any = false;
-                const bool cached = !into_current && fs[w].cached;
-                if (cached) {
-                    const FuseSeq& f = fs[w];
-                    const int sl = f.slotOf[k];
-                    for (size_t pi = 0; pi < pts.size(); pi++) {
-                        const uint8_t ex = f.badf[pi] | (uint8_t)((f.mask[pi] >> sl) & 1);
-                        fs[w].excl[pi] = ex; any = any || !ex;
-                    }
-                }
-                if (!cached || excl_check)
-                    for (size_t pi = 0; pi < pts.size(); pi++) {   // what only the host knows of ORBmatcher::Fuse's gates (:849): bad, or already in the keyframe
-                        prefetch_obs_ahead(m.mps, pts, pi, pts.size());
-                        const int p = pts[pi];
-                        uint8_t ex = 1;
-                        if (p >= 0) { const MapPt& mp = m.mps[p]; ex = (m.pBad[p] || mp.obs_index(k) >= 0) ? 1 : 0; }
-                        if (cached) { if (ex != fs[w].excl[pi]) { fprintf(stderr, "[fuse excl check] mismatch: sequence %d keyframe %d point %d (list index %zu): cached %d, full %d\n", who[w], k, p, pi, fs[w].excl[pi], ex); abort(); } }
-                        else { fs[w].excl[pi] = ex; any = any || !ex; }
-                    }
-                if (!any) fs[w].kf = -1;
-                fs[w].qm.assign(pts.size() + 1, -1);
-            });
-            for (size_t w = 0; w < who.size(); w++) {
-                if (fs[w].kf < 0) continue;
-                const KeyFrm& kf = c.seq[who[w]]->map.kfs[fs[w].kf];
-                oslam_job_fuse_pts_t j;
-                j.slot = who[w]; j.kf = fs[w].kf; j.N = kf.N; j.M = (int)fs[w].pts.size(); j.ids = fs[w].pts.data(); j.excl = fs[w].excl.data();
-                memcpy(j.Tcw, kf.pose.Tcw.m, 64); memcpy(j.Ow, kf.pose.Ow, 12); j.th = 3.0f; j.q_match = fs[w].qm.data();
-                pjobs.push_back(j); jw.push_back((int)w);
-            }
-            fine(into_current ? 3 : 1);
-            int rc2 = OSLAM_OK;
-            if (pjobs.empty()) {
-                if ((rc2 = upd.finish(c))) return rc2;
-                { c.sec[5] += tm.lap(); c.cpu[5] += tm.cpu; }
-                return OSLAM_OK;
-            }
-            // (the descriptor updates of the previous round may still be in flight: this search is queued behind them and reads their results from the resident
-            // records; their host copies are scattered right after it)
-            rc2 = c.ops.fuse_points_keyed(c.ops.ctx, (int)pjobs.size(), pjobs.data());
-            if (rc2) return rc2;
-            { c.sec[8] += tm.lap(); c.cpu[8] += tm.cpu; }
-            if ((rc2 = upd.finish(c))) return rc2;
-            { c.sec[5] += tm.lap(); c.cpu[5] += tm.cpu; }
-            pool.parallel_for((int)jw.size(), [&](int q) {
-                const int w = jw[q];
-                const bool cached = !into_current && fs[w].cached;
-                fuse_apply(*c.seq[who[w]], fs[w].kf, fs[w].pts, fs[w].qm.data(), cached ? &fs[w].touched : nullptr);
-                if (cached) refresh_touched(*c.seq[who[w]], fs[w]);
-            });
-            merge_upd();
-            fine(into_current ? 3 : 1);
-            rc2 = upd.submit(c, true, false, mpu_async);   // Replace -> ComputeDistinctiveDescriptors (src/MapPoint.cc:314); collected behind the next round's search
-            { c.sec[5] += tm.lap(); c.cpu[5] += tm.cpu; }
-            return rc2;
-        };
-        auto fuse_round = [&](bool into_current, size_t t) -> int {
-            if (fuse_by_id) return fuse_round_by_id(into_current, t);
-            jobs.clear(); jw.clear(); fkey.clear();
-            pool.parallel_for(nW, [&](int w) {
-                Seq& s = *c.seq[who[w]];
-                fs[w].q.clear(); fs[w].qpt.clear();
-                if (!into_current && t >= fs[w].targets.size()) return;
-                if (into_current && fs[w].targets.empty()) return;
-                const int k = into_current ? s.curKF : fs[w].targets[t];
-                fs[w].kf = k;
-                fuse_queries(c, s.map, k, fs[w].pts, 3.0f, fs[w].q, fs[w].qpt);
-                fs[w].qm.assign(fs[w].q.size() + 1, -1);
-            });
-            for (size_t w = 0; w < who.size(); w++) {
-                Seq& s = *c.seq[who[w]];
-                Map& m = s.map;
-                if (fs[w].q.empty()) continue;
-                const int k = fs[w].kf;
-                const KeyFrm& kf = m.kfs[k];
-                oslam_job_fuse_t j;
-                j.N = kf.N; j.keysUn = kf.keysUn.data(); j.uRight = kf.uRight.data(); j.desc = kf.desc.data();
-                j.M = (int)fs[w].q.size(); j.queries = fs[w].q.data(); j.q_match = fs[w].qm.data();
-                jobs.push_back(j); jw.push_back((int)w); fkey.push_back({who[w], k, -1});
-            }
-            fine(into_current ? 3 : 1);
-            if (jobs.empty()) return OSLAM_OK;
-            int rc2 = c.ops.fuse_keyed ? c.ops.fuse_keyed(c.ops.ctx, (int)jobs.size(), jobs.data(), fkey.data()) : c.ops.fuse(c.ops.ctx, (int)jobs.size(), jobs.data());
-            if (rc2) return rc2;
-            { c.sec[8] += tm.lap(); c.cpu[8] += tm.cpu; }
-            pool.parallel_for((int)jw.size(), [&](int q) { const int w = jw[q]; fuse_apply(*c.seq[who[w]], fs[w].kf, fs[w].qpt, fs[w].qm.data()); });
-            merge_upd();
-            fine(into_current ? 3 : 1);
-            rc2 = upd.run(c, true, false);   // Replace -> ComputeDistinctiveDescriptors (src/MapPoint.cc:314)
-            { c.sec[5] += tm.lap(); c.cpu[5] += tm.cpu; }
-            return rc2;
-        };
-        for (size_t t = 0; t < maxt; t++)
-            if ((rc = fuse_round(false, t))) return rc;
-        if ((rc = upd.finish(c))) return rc;
-        { c.sec[5] += tm.lap(); c.cpu[5] += tm.cpu; }
-        // the targets' points into the current keyframe (:492-515)
-        auto build_lists = [&]() {
-            pool.parallel_for(nW, [&](int w) {
-                Seq& s = *c.seq[who[w]];
-                Map& m = s.map;
-                const int cur = s.curKF;
-                fs[w].pts.clear();
-                // (mnFuseCandidateForKF as a dense per-sequence array, like baMark: up to 60 targets x 1000 slots per keyframe, most of them already marked)
-                if (s.fuseMark.size() < m.mps.size()) s.fuseMark.resize(m.mps.size() + m.mps.size() / 2 + 64, 0);
-                int* fm = s.fuseMark.data();
-                for (int k : fs[w].targets) {
-                    const int* kmp = m.kfs[k].mp.data();
-                    for (size_t i = 0, n = m.kfs[k].mp.size(); i < n; i++) {
-                        const int p = kmp[i];
-                        if (p < 0 || m.pBad[p] || fm[p] == cur) continue;
-                        fm[p] = cur;
-                        fs[w].pts.push_back(p);
-                    }
-                }
-            });
-        };
-        // With a table that mirrors the observation graph the candidate list is the TABLE's: it walks the targets' point lists where they are resident, runs Fuse's gates
-        // and search and returns the matches (oslam_slam_ops_t::fuse_into_current) — no 60 x 1000-slot walk, no observation-list lookups, no candidate upload.  The change
-        // sets of this pass so far (new keyframe, triangulated points, the first direction's fusions) go to the table first.  OSLAM_SLAM_FUSECUR_CHECK=1: the list and
-        // its flags are also built here and compared entry by entry.
-        static const bool fusecur_check = getenv("OSLAM_SLAM_FUSECUR_CHECK") != nullptr;
-        bool cur_done = false;
-        if (fuse_by_id && c.ops.fuse_into_current && c.ops.map_journal) {
-            bool all_on = true;
-            for (int w = 0; w < nW; w++) all_on = all_on && c.seq[who[w]]->map.jrOn;
-            if (all_on) {
-                std::vector<oslam_map_changes_t> chg(nW), chs;
-                std::vector<uint8_t> has(nW, 0);
-                if (c.jrScratch.size() < (size_t)c.S) c.jrScratch.resize(c.S);
-                pool.parallel_for(nW, [&](int w) { Seq& s = *c.seq[who[w]]; if (s.map.jr_pending()) { s.map.journal_changes(who[w], c.thDepth, c.jrScratch[who[w]], chg[w]); has[w] = 1; } });
-                for (int w = 0; w < nW; w++) if (has[w]) chs.push_back(chg[w]);
-                if (!chs.empty() && (rc = c.ops.map_journal(c.ops.ctx, (int)chs.size(), chs.data()))) return rc;
-                std::vector<oslam_job_fuse_cur_t> cj;
-                std::vector<int> cw;
-                std::vector<std::vector<int32_t>> cpairs(nW), dIds(nW);
-                std::vector<std::vector<uint8_t>> dEx(nW);
-                for (int w = 0; w < nW; w++) {
-                    if (fs[w].targets.empty()) continue;
-                    Seq& s = *c.seq[who[w]];
-                    const KeyFrm& kf = s.map.kfs[s.curKF];
-                    oslam_job_fuse_cur_t j;
-                    memset(&j, 0, sizeof(j));
-                    j.slot = who[w]; j.kf = s.curKF; j.n_targets = (int32_t)fs[w].targets.size(); j.targets = fs[w].targets.data();
-                    memcpy(j.Tcw, kf.pose.Tcw.m, 64); memcpy(j.Ow, kf.pose.Ow, 12); j.th = 3.0f;
-                    cpairs[w].resize(2 * 2048); j.max_pairs = 2048; j.pairs = cpairs[w].data();
-                    if (fusecur_check) { dIds[w].resize(16384); dEx[w].resize(16384); j.dbg_cap = 16384; j.dbg_ids = dIds[w].data(); j.dbg_excl = dEx[w].data(); }
-                    cj.push_back(j); cw.push_back(w);
-                }
-                fine(2);
-                if (!cj.empty() && (rc = c.ops.fuse_into_current(c.ops.ctx, (int)cj.size(), cj.data()))) return rc;
-                { c.sec[8] += tm.lap(); c.cpu[8] += tm.cpu; }
-                bool overflow = false;
-                for (auto& j : cj) overflow = overflow || j.overflow != 0;
-                if (!overflow) {
-                    if (fusecur_check) {
-                        build_lists();
-                        for (size_t q = 0; q < cj.size(); q++) {
-                            const int w = cw[q];
-                            const Seq& s = *c.seq[who[w]];
-                            const std::vector<int>& pts = fs[w].pts;
-                            bool same = (size_t)cj[q].n_candidates == pts.size();
-                            for (size_t pi = 0; same && pi < pts.size(); pi++) {
-                                const int pp = pts[pi];
-                                const uint8_t ex = (s.map.pBad[pp] || s.map.mps[pp].obs_index(s.curKF) >= 0) ? 1 : 0;
-                                same = dIds[w][pi] == pp && dEx[w][pi] == ex;
-                                if (!same) fprintf(stderr, "OSLAM_SLAM_FUSECUR_CHECK: sequence %d keyframe %d candidate %zu: table (%d, %d), driver (%d, %d)\n", who[w], s.curKF, pi, dIds[w][pi], dEx[w][pi], pp, ex);
-                            }
-                            if (!same) { fprintf(stderr, "OSLAM_SLAM_FUSECUR_CHECK: the table's candidate list differs from the driver's (sequence %d keyframe %d: %d against %zu candidates)\n", who[w], s.curKF, cj[q].n_candidates, pts.size()); abort(); }
-                        }
-                    }
-                    pool.parallel_for((int)cj.size(), [&](int q) { Seq& s = *c.seq[who[cw[q]]]; fuse_apply_pairs(s, s.curKF, cj[q].pairs, cj[q].n_pairs); });
-                    merge_upd();
-                    fine(3);
-                    if ((rc = upd.run(c, true, false))) return rc;   // Replace -> ComputeDistinctiveDescriptors (src/MapPoint.cc:314)
-                    { c.sec[5] += tm.lap(); c.cpu[5] += tm.cpu; }
-                    cur_done = true;
-                }
+// SearchForTriangulation job of the current keyframe against neighbour k2; false: the baseline is too short (:251-254).  flag1: the current keyframe's keypoints that have a point
+static bool cnmp_pair_job(const Ctx& c, Seq& s, int k2id, const std::vector<uint8_t>& flag1, std::vector<uint8_t>& has2, std::vector<int32_t>& match, oslam_job_bow_t& j) {
+    const KeyFrm& k1 = s.map.kfs[s.curKF];
+    const KeyFrm& k2 = s.map.kfs[k2id];
+    const float vb[3] = {k2.pose.Ow[0] - k1.pose.Ow[0], k2.pose.Ow[1] - k1.pose.Ow[1], k2.pose.Ow[2] - k1.pose.Ow[2]};
+    if (norm3(vb) < c.mb) return false;
+    memset(&j, 0, sizeof(j));
+    compute_F12(c, k1, k2, j.F12);
+    // epipole of camera 1 in image 2 (src/ORBmatcher.cc:663-670)
+    float C2[3];
+    for (int r = 0; r < 3; r++) {
+        float sacc = k2.pose.Tcw.m[r * 4] * k1.pose.Ow[0];
+        sacc += k2.pose.Tcw.m[r * 4 + 1] * k1.pose.Ow[1];
+        sacc += k2.pose.Tcw.m[r * 4 + 2] * k1.pose.Ow[2];
+        C2[r] = (float)((double)sacc + (double)k2.pose.Tcw.m[r * 4 + 3]);
+    }
+    const float invz = 1.0f / C2[2];
+    j.ex = c.cfg.fx * C2[0] * invz + c.cfg.cx; j.ey = c.cfg.fy * C2[1] * invz + c.cfg.cy;
+    const BowViews& v1 = s.bow_views(c, s.curKF);
+    const BowViews& v2 = s.bow_views(c, k2id);
+    has2.resize(k2.N);
+    for (int i = 0; i < k2.N; i++) has2[i] = k2.mp[i] >= 0;
+    match.assign(k1.N, -1);
+    j.s1.N = k1.N; j.s1.keys = k1.keysUn.data(); j.s1.desc = k1.desc.data(); j.s1.uRight = k1.uRight.data(); j.s1.flag = flag1.data();
+    j.s1.nq = k1.N; j.s1.q_idx = v1.q_idx.data(); j.s1.q_node = v1.q_node.data();
+    j.s2.N = k2.N; j.s2.keys = k2.keysUn.data(); j.s2.desc = k2.desc.data(); j.s2.uRight = k2.uRight.data(); j.s2.has_mp = has2.data();
+    j.s2.nNodes = (int)v2.nodes.size(); j.s2.nodes = v2.nodes.data(); j.s2.start = v2.start.data(); j.s2.items = v2.items.data();
+    j.triangulation = 1; j.nnratio = 0.6f; j.checkOri = 0; j.match = match.data();
+    return true;
+}
+
+static void cnmp_triangulate_job(const Ctx& c, const Seq& s, int k2, const std::vector<int32_t>& match, CnmpTri& b, oslam_job_triangulate_t& t) {
+    const KeyFrm& k1 = s.map.kfs[s.curKF];
+    // vMatchedIndices order (:815-820): ascending index of keyframe 1
+    for (int i = 0; i < k1.N; i++) if (match[i] >= 0) { b.i1.push_back(i); b.i2.push_back(match[i]); }
+    fill_tri_kf(c, k1, t.kf1); fill_tri_kf(c, s.map.kfs[k2], t.kf2);
+    t.M = (int)b.i1.size(); t.idx1 = b.i1.data(); t.idx2 = b.i2.data();
+    b.ok.assign(t.M + 1, 0); b.x3.assign((size_t)t.M * 3 + 3, 0.f);
+    t.ok = b.ok.data(); t.x3D = b.x3.data();
+}
+
+// the new points of one triangulation job (:408-430).  skip_taken: a keypoint that received a point from an earlier neighbour is left out, as the reference's search would have
+static void cnmp_apply(Seq& s, int k2, const CnmpTri& b, bool skip_taken) {
+    Map& m = s.map;
+    for (size_t e = 0; e < b.i1.size(); e++) {
+        if (!b.ok[e]) continue;
+        if (skip_taken && m.kfs[s.curKF].mp[b.i1[e]] >= 0) continue;
+        const int p = m.new_point(&b.x3[e * 3], s.curKF, m.kfs[s.curKF].frameId);
+        m.add_observation(p, s.curKF, b.i1[e]);
+        m.add_observation(p, k2, b.i2[e]);
+        m.set_kf_mp(s.curKF, b.i1[e], p);
+        m.set_kf_mp(k2, b.i2[e], p);
+        m.nMPsInMap++; s.st[3]++; s.st[10]++;
+        s.recentAdded.push_back(p);
+        s.updList.push_back(p);
+    }
+}
+
+// search, triangulation and new points of `pairs` (grouped by sequence, neighbour order within a sequence) from the maps as they are: one call of each operator
+static int cnmp_run_pairs(LmPass& L, const std::vector<CnmpPair>& pairs, bool skip_taken) {
+    Ctx& c = L.c;
+    int rc;
+    const int nPairs = (int)pairs.size();
+    std::vector<int> first(L.nW + 1, 0);   // pairs of sequence w: [first[w], first[w + 1])
+    for (const CnmpPair& pq : pairs) first[pq.w + 1]++;
+    for (int w = 0; w < L.nW; w++) first[w + 1] += first[w];
+    std::vector<std::vector<uint8_t>> flag1(L.nW), has2(nPairs);
+    L.pool.parallel_for(L.nW, [&](int w) {
+        Seq& s = L.seq(w);
+        const KeyFrm& k1 = s.map.kfs[s.curKF];
+        flag1[w].resize(k1.N);
+        for (int i = 0; i < k1.N; i++) flag1[w][i] = k1.mp[i] >= 0;
+        (void)s.bow_views(c, s.curKF);   // (built once per keyframe: not from several pair jobs at a time)
+        for (int q = first[w]; q < first[w + 1]; q++) (void)s.bow_views(c, pairs[q].k2);
+    });
+    std::vector<std::vector<int32_t>> match(nPairs);
+    std::vector<oslam_job_bow_t> cand(nPairs);
+    std::vector<uint8_t> have(nPairs, 0);
+    L.pool.parallel_for(nPairs, [&](int q) { have[q] = cnmp_pair_job(c, L.seq(pairs[q].w), pairs[q].k2, flag1[pairs[q].w], has2[q], match[q], cand[q]); });
+    std::vector<oslam_job_bow_t> bj;
+    std::vector<int> bjq, jobOf(nPairs, -1);   // job -> pair, pair -> job (-1: baseline too short)
+    std::vector<oslam_kf_key_t> bkey;
+    for (int q = 0; q < nPairs; q++)
+        if (have[q]) { jobOf[q] = (int)bj.size(); bj.push_back(cand[q]); bjq.push_back(q); bkey.push_back({L.who[pairs[q].w], L.seq(pairs[q].w).curKF, pairs[q].k2}); }
+    L.charge(10);
+    if (bj.empty()) return OSLAM_OK;
+    const int nJ = (int)bj.size();
+    if ((rc = c.ops.bow_keyed ? c.ops.bow_keyed(c.ops.ctx, nJ, bj.data(), bkey.data()) : c.ops.bow(c.ops.ctx, nJ, bj.data()))) return rc;
+    std::vector<oslam_job_triangulate_t> tj(nJ);
+    std::vector<CnmpTri> tb(nJ);
+    L.pool.parallel_for(nJ, [&](int jq) { const int q = bjq[jq]; cnmp_triangulate_job(c, L.seq(pairs[q].w), pairs[q].k2, match[q], tb[jq], tj[jq]); });
+    if ((rc = c.ops.triangulate(c.ops.ctx, nJ, tj.data()))) return rc;
+    L.charge_op(8);
+    L.pool.parallel_for(L.nW, [&](int w) {   // per sequence (independent maps), its jobs in neighbour order
+        for (int q = first[w]; q < first[w + 1]; q++)
+            if (jobOf[q] >= 0) cnmp_apply(L.seq(w), pairs[q].k2, tb[jobOf[q]], skip_taken);
+    });
+    L.merge_upd();
+    L.charge(10);
+    if ((rc = L.upd.run(c, true, true))) return rc;
+    L.charge_op(5);
+    return OSLAM_OK;
+}
+
+static std::vector<std::vector<int>> cnmp_neighbours(const LmPass& L) {   // vpNeighKFs (:218): the 10 best covisible keyframes of every sequence's current keyframe
+    std::vector<std::vector<int>> neigh(L.nW);
+    for (int w = 0; w < L.nW; w++) {
+        Seq& s = L.seq(w);
+        const Map::IntSpan bc = s.map.best_covisibles(s.curKF, 10);
+        neigh[w].assign(bc.begin(), bc.end());
+    }
+    return neigh;
+}
+static int lm_create_new_map_points(LmPass& L) {
+    const std::vector<std::vector<int>> neigh = cnmp_neighbours(L);
+    std::vector<CnmpPair> pairs;
+    for (int w = 0; w < L.nW; w++)
+        for (int k2 : neigh[w]) pairs.push_back({w, k2});
+    return cnmp_run_pairs(L, pairs, true);
+}
+// the same in lockstep rounds (round i = neighbour i of every sequence; the matches of neighbour i see the points created from neighbour i-1): A/B form
+static int lm_create_new_map_points_rounds(LmPass& L) {
+    const std::vector<std::vector<int>> neigh = cnmp_neighbours(L);
+    size_t maxn = 0;
+    for (auto& v : neigh) maxn = std::max(maxn, v.size());
+    std::vector<CnmpPair> pairs;
+    for (size_t ni = 0; ni < maxn; ni++) {
+        pairs.clear();
+        for (int w = 0; w < L.nW; w++) if (ni < neigh[w].size()) pairs.push_back({w, neigh[w][ni]});
+        const int rc = cnmp_run_pairs(L, pairs, false);
+        if (rc) return rc;
+    }
+    return OSLAM_OK;
+}
+
+// --- SearchInNeighbors (:455-535) ---
+// The target keyframes of one sequence are fused one after the other like the reference's loop (a fusion changes descriptors and
+// observations the next target sees); round t handles target t of every sequence in one batch.
+// badf / mask / dup / slotOf / touched: what only the host knows of ORBmatcher::Fuse's gates (:849: the point is bad, or already observed in the target) for
+// the points of the current keyframe against ALL targets, computed once before the rounds (bit t of mask[i] = point i is observed in the keyframe with
+// slot t) and refreshed after every round for the points that round changed — instead of a pass over all ~1000 point records and their observation
+// lists per round and sequence.
+struct FuseSeq {
+    std::vector<int> targets; std::vector<int> pts; std::vector<oslam_proj_query_t> q; std::vector<int> qpt; std::vector<int32_t> qm; std::vector<uint8_t> excl; int kf;
+    std::vector<uint8_t> badf, slotOf; std::vector<uint64_t> mask; std::vector<int> dup, touched; bool cached = false;
+};
+static bool fuse_by_id(const Ctx& c) { return c.residentPts && c.ops.fuse_points_keyed != nullptr; }   // the table runs the projection gates itself from its map-point records
+
+// vpTargetKFs (:458-478), the snapshot of the current keyframe's points and, for the rounds by id, the exclusion cache
+static void sn_target_lists(LmPass& L, std::vector<FuseSeq>& fs) {
+    const bool by_id = fuse_by_id(L.c);
+    L.pool.parallel_for(L.nW, [&](int w) {
+        Seq& s = L.seq(w);
+        Map& m = s.map;
+        FuseSeq& f = fs[w];
+        const int cur = s.curKF;
+        for (int k : m.best_covisibles(cur, 10)) {
+            if (m.kfs[k].bad || m.kfs[k].fuseTargetForKF == cur) continue;
+            f.targets.push_back(k);
+            m.kfs[k].fuseTargetForKF = cur;
+            for (int k2 : m.best_covisibles(k, 5)) {
+                if (m.kfs[k2].bad || m.kfs[k2].fuseTargetForKF == cur || k2 == cur) continue;
+                f.targets.push_back(k2);
             }
         }
-        if (!cur_done) {
-            build_lists();
-            fine(2);
-            if ((rc = fuse_round(true, 0))) return rc;
-            if ((rc = upd.finish(c))) return rc;
-            { c.sec[5] += tm.lap(); c.cpu[5] += tm.cpu; }
+        f.pts.assign(m.kfs[cur].mp.begin(), m.kfs[cur].mp.end());   // vpMapPointMatches snapshot (:484)
+        f.cached = false;
+        if (!by_id) return;
+        f.slotOf.assign(m.kfs.size(), 255);
+        int nslot = 0;
+        for (int k : f.targets) if (f.slotOf[k] == 255) f.slotOf[k] = (uint8_t)nslot++;   // (the target list may name a keyframe twice, like the reference's)
+        if (nslot > 64) return;   // (cannot happen with 10 + 10 x 5 targets; the full pass serves it)
+        const size_t n = f.pts.size();
+        f.badf.assign(n, 1); f.mask.assign(n, 0); f.dup.assign(n, -1); f.touched.clear();
+        const int stamp = cur + 1;
+        for (size_t pi = 0; pi < n; pi++) {
+            prefetch_obs_ahead(m.mps, f.pts, pi, n);
+            const int p = f.pts[pi];
+            if (p < 0) continue;
+            MapPt& mp = m.mps[p];
+            if (mp.fuseListStamp == stamp) f.dup[pi] = mp.fuseListIdx;   // the same point at two keypoints of the keyframe: a chain through its positions
+            mp.fuseListStamp = stamp; mp.fuseListIdx = (int)pi;
+            f.badf[pi] = m.pBad[p] ? 1 : 0;
+            uint64_t mk = 0;
+            for (auto& e : mp.obs) { const uint8_t sl = f.slotOf[e.first]; if (sl != 255) mk |= 1ull << sl; }
+            f.mask[pi] = mk;
         }
-        // update points of the current keyframe (:517-531) and its connections
-        pool.parallel_for(nW, [&](int w) {
-            Seq& s = *c.seq[who[w]];
-            // The reference recomputes descriptor and normal of every point of the keyframe here.  A point that went through a full update earlier in THIS
-            // pass (ProcessNewKeyFrame, triangulation) and whose observation list has not changed since would get the same result: its position, the poses and
-            // the bad flags of the observing keyframes only change later in the pass (local BA, culling).
-            s.updList.clear();
-            const std::vector<int>& kmp = s.map.kfs[s.curKF].mp;
-            for (size_t i = 0; i < kmp.size(); i++) {
-                prefetch_ahead(s.map.mps, kmp, i, kmp.size());
+        f.cached = true;
+    });
+    L.charge(11, 0);
+}
+
+// after a round: the exclusion flags of the points it changed, if they are in the list
+static void sn_refresh_touched(const Seq& s, FuseSeq& f) {
+    const Map& m = s.map;
+    const int stamp = s.curKF + 1;
+    for (int x : f.touched) {
+        const MapPt& mp = m.mps[x];
+        if (mp.fuseListStamp != stamp) continue;
+        uint64_t mk = 0;
+        for (auto& e : mp.obs) { const uint8_t sl = (size_t)e.first < f.slotOf.size() ? f.slotOf[e.first] : 255; if (sl != 255) mk |= 1ull << sl; }
+        for (int pi = mp.fuseListIdx; pi >= 0; pi = f.dup[pi]) { f.badf[pi] = m.pBad[x] ? 1 : 0; f.mask[pi] = mk; }
+    }
+    f.touched.clear();
+}
+
+// One Fuse round by map-point id (oslam_slam_ops_t::fuse_points_keyed): the lists `pts` into target t of every sequence, or into the current keyframes.
+// A round's descriptor updates (MapPoint::Replace -> ComputeDistinctiveDescriptors) are handed to the table WITHOUT a wait (mp_update_keyed_async): the table launches
+// them right in front of the NEXT round's search, so one wait covers both — one device round trip per round instead of two.  Same-box A/B, alternating,
+// identical results: 39.7 / 40.9 k against 38.6 / 40.6 k frames/s.  (The first form enqueued the update kernel at once and let it run beside the round's host
+// bookkeeping: 33.4 / 35.4 k against 36.1 / 37.8 k — slower; OSLAM_SLAM_MPU_SYNC=1 restores the wait per update.)
+static int sn_fuse_round_by_id(LmPass& L, std::vector<FuseSeq>& fs, bool into_current, size_t t) {
+    Ctx& c = L.c;
+    const int fine = into_current ? 3 : 1;
+    int rc;
+    L.pool.parallel_for(L.nW, [&](int w) {
+        Seq& s = L.seq(w);
+        FuseSeq& f = fs[w];
+        f.kf = -1;
+        if (into_current ? f.targets.empty() : t >= f.targets.size()) return;
+        const int k = into_current ? s.curKF : f.targets[t];
+        f.kf = k;
+        const Map& m = s.map;
+        const std::vector<int>& pts = f.pts;
+        f.excl.assign(pts.size() + 1, 1);
+        bool any = false;
+        const bool cached = !into_current && f.cached;
+        if (cached) {
+            const int sl = f.slotOf[k];
+            for (size_t pi = 0; pi < pts.size(); pi++) {
+                const uint8_t ex = f.badf[pi] | (uint8_t)((f.mask[pi] >> sl) & 1);
+                f.excl[pi] = ex; any = any || !ex;
+            }
+        }
+        if (!cached || kFuseExclCheck)
+            for (size_t pi = 0; pi < pts.size(); pi++) {   // what only the host knows of ORBmatcher::Fuse's gates (:849): bad, or already in the keyframe
+                prefetch_obs_ahead(m.mps, pts, pi, pts.size());
+                const int p = pts[pi];
+                uint8_t ex = 1;
+                if (p >= 0) { const MapPt& mp = m.mps[p]; ex = (m.pBad[p] || mp.obs_index(k) >= 0) ? 1 : 0; }
+                if (cached) { if (ex != f.excl[pi]) { fprintf(stderr, "[fuse excl check] mismatch: sequence %d keyframe %d point %d (list index %zu): cached %d, full %d\n", L.who[w], k, p, pi, f.excl[pi], ex); abort(); } }
+                else { f.excl[pi] = ex; any = any || !ex; }
+            }
+        if (!any) f.kf = -1;
+        f.qm.assign(pts.size() + 1, -1);
+    });
+    std::vector<oslam_job_fuse_pts_t> pjobs;
+    std::vector<int> jw;
+    for (int w = 0; w < L.nW; w++) {
+        if (fs[w].kf < 0) continue;
+        const KeyFrm& kf = L.seq(w).map.kfs[fs[w].kf];
+        oslam_job_fuse_pts_t j;
+        j.slot = L.who[w]; j.kf = fs[w].kf; j.N = kf.N; j.M = (int)fs[w].pts.size(); j.ids = fs[w].pts.data(); j.excl = fs[w].excl.data();
+        memcpy(j.Tcw, kf.pose.Tcw.m, 64); memcpy(j.Ow, kf.pose.Ow, 12); j.th = 3.0f; j.q_match = fs[w].qm.data();
+        pjobs.push_back(j); jw.push_back(w);
+    }
+    L.charge(11, fine);
+    // (the descriptor updates of the previous round may still be in flight: this search is queued behind them and reads their results from the resident
+    // records; their host copies are scattered right after it)
+    if (!pjobs.empty()) {
+        if ((rc = c.ops.fuse_points_keyed(c.ops.ctx, (int)pjobs.size(), pjobs.data()))) return rc;
+        L.charge_op(8);
+    }
+    if ((rc = L.upd.finish(c))) return rc;
+    L.charge_op(5);
+    if (pjobs.empty()) return OSLAM_OK;
+    L.pool.parallel_for((int)jw.size(), [&](int q) {
+        const int w = jw[q];
+        const bool cached = !into_current && fs[w].cached;
+        fuse_apply(L.seq(w), fs[w].kf, fs[w].pts, fs[w].qm.data(), cached ? &fs[w].touched : nullptr);
+        if (cached) sn_refresh_touched(L.seq(w), fs[w]);
+    });
+    L.merge_upd();
+    L.charge(11, fine);
+    rc = L.upd.submit(c, true, false, kMpuAsync);   // Replace -> ComputeDistinctiveDescriptors (src/MapPoint.cc:314); collected behind the next round's search
+    L.charge_op(5);
+    return rc;
+}
+
+// one Fuse round: by id where the table can, else with the projection gates run here (fuse_queries) and the queries handed over
+static int sn_fuse_round(LmPass& L, std::vector<FuseSeq>& fs, bool into_current, size_t t) {
+    Ctx& c = L.c;
+    if (fuse_by_id(c)) return sn_fuse_round_by_id(L, fs, into_current, t);
+    const int fine = into_current ? 3 : 1;
+    L.pool.parallel_for(L.nW, [&](int w) {
+        Seq& s = L.seq(w);
+        FuseSeq& f = fs[w];
+        f.q.clear(); f.qpt.clear();
+        if (into_current ? f.targets.empty() : t >= f.targets.size()) return;
+        f.kf = into_current ? s.curKF : f.targets[t];
+        fuse_queries(c, s.map, f.kf, f.pts, 3.0f, f.q, f.qpt);
+        f.qm.assign(f.q.size() + 1, -1);
+    });
+    std::vector<oslam_job_fuse_t> jobs;
+    std::vector<int> jw;
+    std::vector<oslam_kf_key_t> fkey;
+    for (int w = 0; w < L.nW; w++) {
+        if (fs[w].q.empty()) continue;
+        const KeyFrm& kf = L.seq(w).map.kfs[fs[w].kf];
+        oslam_job_fuse_t j;
+        j.N = kf.N; j.keysUn = kf.keysUn.data(); j.uRight = kf.uRight.data(); j.desc = kf.desc.data();
+        j.M = (int)fs[w].q.size(); j.queries = fs[w].q.data(); j.q_match = fs[w].qm.data();
+        jobs.push_back(j); jw.push_back(w); fkey.push_back({L.who[w], fs[w].kf, -1});
+    }
+    L.charge(11, fine);
+    if (jobs.empty()) return OSLAM_OK;
+    int rc = c.ops.fuse_keyed ? c.ops.fuse_keyed(c.ops.ctx, (int)jobs.size(), jobs.data(), fkey.data()) : c.ops.fuse(c.ops.ctx, (int)jobs.size(), jobs.data());
+    if (rc) return rc;
+    L.charge_op(8);
+    L.pool.parallel_for((int)jw.size(), [&](int q) { const int w = jw[q]; fuse_apply(L.seq(w), fs[w].kf, fs[w].qpt, fs[w].qm.data()); });
+    L.merge_upd();
+    L.charge(11, fine);
+    rc = L.upd.run(c, true, false);   // Replace -> ComputeDistinctiveDescriptors (src/MapPoint.cc:314)
+    L.charge_op(5);
+    return rc;
+}
+
+// vpFuseCandidates (:492-508): the targets' points, each once, as the list `pts` of the second direction
+static void sn_build_lists(LmPass& L, std::vector<FuseSeq>& fs) {
+    L.pool.parallel_for(L.nW, [&](int w) {
+        Seq& s = L.seq(w);
+        Map& m = s.map;
+        const int cur = s.curKF;
+        fs[w].pts.clear();
+        // (mnFuseCandidateForKF as a dense per-sequence array, like baMark: up to 60 targets x 1000 slots per keyframe, most of them already marked)
+        if (s.fuseMark.size() < m.mps.size()) s.fuseMark.resize(m.mps.size() + m.mps.size() / 2 + 64, 0);
+        int* fm = s.fuseMark.data();
+        for (int k : fs[w].targets) {
+            const int* kmp = m.kfs[k].mp.data();
+            for (size_t i = 0, n = m.kfs[k].mp.size(); i < n; i++) {
                 const int p = kmp[i];
-                if (p < 0) continue;
-                const MapPt& mp = s.map.mps[p];
-                if (s.map.pBad[p] || (mp.updStep == c.mapStep && mp.updVer == mp.obsVer)) continue;
-                s.updList.push_back(p);
+                if (p < 0 || m.pBad[p] || fm[p] == cur) continue;
+                fm[p] = cur;
+                fs[w].pts.push_back(p);
             }
-        });
-        merge_upd();   // (sequence order, then keypoint order: the order of the serial loop this replaces)
-        fine(4);
-        if ((rc = upd.run(c, true, true))) return rc;
-        { c.sec[5] += tm.lap(); c.cpu[5] += tm.cpu; }
-        pool.parallel_for(nW, [&](int w) { Seq& s = *c.seq[who[w]]; s.map.update_connections(s.curKF, s.counter); });
-        fine(4);
-    }
-
-    // --- Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778), all windows in one batch ---
-    if (flags & 8) {
-        typedef Ctx::Win Win;
-        std::vector<Win>& pool_w = c.winPool;   // the windows' arrays keep their capacity from step to step
-        if (pool_w.size() < who.size()) pool_w.resize(who.size());
-        pool.parallel_for(nW, [&](int w) {
-            const int si = who[w];
-            Seq& s = *c.seq[si];
-            Map& m = s.map;
-            Win& W = pool_w[w];
-            W.reset();
-            W.si = -1;
-            if (m.nKFsInMap <= 2) return;   // src/LocalMapping.cc:81
-            const int cur = s.curKF;
-            W.si = si;
-            W.kfs.push_back(cur);
-            for (int k : m.kfs[cur].ordered)
-                if (!m.kfs[k].bad) W.kfs.push_back(k);
-            W.nLocal = (int)W.kfs.size();
-            // lLocalMapPoints (src/Optimizer.cc:470-487).  mnBALocalForKF of the points is a dense per-sequence array (as mpMark in update_local_map): the loop visits
-            // ~1000 slots per local keyframe and most of them hold a point that is already in the list, so it should touch 4 bytes per slot, not a MapPt record.
-            if (s.baMark.size() < m.mps.size()) s.baMark.resize(m.mps.size() + m.mps.size() / 2 + 64, 0);
-            int* bam = s.baMark.data();
-            size_t edgeCap = 0;
-            for (int q = 0; q < W.nLocal; q++) {
-                const std::vector<int>& kmp = m.kfs[W.kfs[q]].mp;
-                const int* kp_ = kmp.data();
-                for (size_t i = 0, n = kmp.size(); i < n; i++) {
-                    if (i + kPF < n) { const int pq = kp_[i + kPF]; if (pq >= 0 && bam[pq] != cur) __builtin_prefetch(&m.mps[pq].obs); }
-                    const int p = kp_[i];
-                    if (p < 0 || bam[p] == cur) continue;
-                    bam[p] = cur;
-
-                    if (!m.pBad[p]) { W.pts.push_back(p); edgeCap += m.mps[p].obs.size(); }
-                }
-            }
-            // Fixed keyframes (:489-504: every observer outside the local set, no bound) and the edges (:560-650) in ONE walk over the observation lists: a fixed
-            // keyframe takes the next window index the first time an observation names it, which is the order the reference's lFixedCameras list is built in.
-            std::vector<int>& slot = s.counter;   // keyframe id -> window index + 1 (restored to 0 below)
-            for (int q = 0; q < W.nLocal; q++) slot[W.kfs[q]] = q + 1;
-            W.points.resize(W.pts.size() * 3);
-            W.ekf.resize(edgeCap); W.ept.resize(edgeCap); W.eobs.resize(edgeCap * 3); W.einv.resize(edgeCap); W.eref.resize(edgeCap); W.eoct.resize(edgeCap);
-            W.pstart.resize(W.pts.size() + 1); W.pquirk.assign(W.pts.size(), 0);
-            size_t ne = 0;
-            for (size_t j = 0; j < W.pts.size(); j++) {
-                prefetch_okp_ahead(m.mps, W.pts, j, W.pts.size());
-                const int p = W.pts[j];
-                const MapPt& mp = m.mps[p];
-                W.pstart[j] = (int32_t)ne;
-                for (int d = 0; d < 3; d++) W.points[j * 3 + d] = mp.pos[d];
-                for (size_t oi = 0; oi < mp.obs.size(); oi++) {
-                    const int kid = mp.obs[oi].first;
-                    int q = slot[kid];
-                    if (q == 0) {
-                        if (m.kfs[kid].bad) { W.pquirk[j] = 1; continue; }   // (an observation the window does not carry: this point's update takes the general path)
-                        W.kfs.push_back(kid);
-                        slot[kid] = q = (int)W.kfs.size();
-                    }
-                    const ObsKp& kp = mp.okp[oi];   // mvKeysUn[idx].pt, mvuRight[idx], octave of the observing keypoint (cached beside the observation)
-                    W.ekf[ne] = q - 1; W.ept[ne] = (int)j;
-                    W.eobs[ne * 3] = kp.x; W.eobs[ne * 3 + 1] = kp.y; W.eobs[ne * 3 + 2] = kp.ur;
-                    W.einv[ne] = c.invSigma2[kp.octave];
-                    W.eoct[ne] = (uint8_t)kp.octave;
-                    W.eref[ne] = std::make_pair(kid, p);
-                    ne++;
-                }
-            }
-            W.pstart[W.pts.size()] = (int32_t)ne;
-            W.ekf.resize(ne); W.ept.resize(ne); W.eobs.resize(ne * 3); W.einv.resize(ne); W.eref.resize(ne); W.eoct.resize(ne);
-            // A window with more than 128 FREE keyframes (768 unknowns) is beyond the local-BA operator (OSLAM_E_CAPACITY).  The reference has no such bound.  The
-            // window is kept, DEGRADED: m.kfs[cur].ordered is weight-descending, so the current keyframe and its strongest covisible keyframes stay free up to the
-            // bound and the remaining local keyframes enter as fixed cameras (fixed = 1): their points and edges are still in the window, points and the strongest
-            // poses are still refined and outlier observations still erased.  Counted (oslam_slam_lba_window_stats [5]: degraded windows).
-            int nFreeCap = W.nLocal;   // window indices >= nFreeCap are fixed cameras
-            {
-                int nFreeKF = 0;
-                for (int q = 0; q < W.nLocal; q++) {
-                    nFreeKF += W.kfs[q] != 0;
-                    if (nFreeKF > kLbaMaxFreeKFs) { nFreeCap = q; break; }
-                }
-                if (nFreeCap < W.nLocal) s.lbaWindowsDegraded++;
-            }
-            W.nFree = nFreeCap;
-            W.poses.resize(W.kfs.size() * 16); W.fixed.resize(W.kfs.size());
-            for (size_t q = 0; q < W.kfs.size(); q++) {
-                memcpy(&W.poses[q * 16], m.kfs[W.kfs[q]].pose.Tcw.m, 64);
-                W.fixed[q] = (int)q >= nFreeCap ? 1 : (W.kfs[q] == 0 ? 2 : 0);
-            }
-            for (size_t q = 0; q < W.kfs.size(); q++) slot[W.kfs[q]] = 0;
-            W.poses_out.resize(W.poses.size()); W.points_out.resize(W.points.size() + 3); W.erase.assign(W.ekf.size() + 1, 0);
-            s.st[5]++; s.st[14] += (int64_t)W.ekf.size();
-            s.lbaWin[0] += W.nLocal; s.lbaWin[1] += (int64_t)W.kfs.size() - W.nLocal; s.lbaWin[2] += (int64_t)W.pts.size(); s.lbaWin[3] += (int64_t)W.ekf.size();
-        });
-        std::vector<Win*> wins;
-        for (int w = 0; w < nW; w++) if (pool_w[w].si >= 0) wins.push_back(&pool_w[w]);
-        std::vector<oslam_lba_problem_t> probs(wins.size());
-        for (size_t i = 0; i < wins.size(); i++) {
-            Win& W = *wins[i];
-            oslam_lba_problem_t& p = probs[i];
-            p.nKF = (int)W.kfs.size(); p.poses = W.poses.data(); p.fixed = W.fixed.data(); p.nP = (int)W.pts.size(); p.points = W.points.data();
-            p.nE = (int)W.ekf.size(); p.edge_kf = W.ekf.data(); p.edge_pt = W.ept.data(); p.edge_obs = W.eobs.data(); p.edge_invSigma2 = W.einv.data();
-            p.poses_out = W.poses_out.data(); p.points_out = W.points_out.data(); p.erase = W.erase.data();
-            W.st[0] = W.st[1] = W.st[2] = W.st[3] = 0;
-            p.stats = W.st;
-            if (c.injectLbaFailure >= 0 && W.si == c.injectLbaFailure && !W.ekf.empty()) { W.ekf[0] = (int32_t)W.kfs.size(); c.injectLbaFailure = -1; }   // test hook (oslam_slam_inject_failure): an edge that names a keyframe outside the window — the operator refuses the window (OSLAM_E_INVALID)
         }
-        { const double d_ = tm.lap(); c.sec[7] += d_; c.sec[12] += d_; c.cpu[7] += tm.cpu; c.cpu[12] += tm.cpu; }
-        if (flags & OSLAM_SLAM_LM_DEFERRED) {
-            // deferred schedule: the solve runs while the next frame is tracked; write-back, MapPoint updates and KeyFrameCulling follow in finish_local_mapping
-            Ctx::PendingLM& pd = c.pend;
-            pd.active = true; pd.who = who; pd.wins = wins; pd.probs.swap(probs); pd.submitted = false;
-            if (!pd.probs.empty() && c.ops.lba_submit) {
-                if ((rc = c.ops.lba_submit(c.ops.ctx, (int)pd.probs.size(), pd.probs.data()))) return rc;
-                pd.submitted = true;
-            }
-            { c.sec[6] += tm.lap(); c.cpu[6] += tm.cpu; }
-            return OSLAM_OK;
-        }
-        if (!probs.empty() && (rc = c.ops.lba(c.ops.ctx, (int)probs.size(), probs.data()))) return rc;
-        { c.sec[6] += tm.lap(); c.cpu[6] += tm.cpu; }
-        return local_mapping_back(c, who, wins);
+    });
+}
+
+// The second direction from the table's mirror of the observation graph: the candidate list is the TABLE's.  It walks the targets' point lists where they are resident,
+// runs Fuse's gates and search and returns the matches (oslam_slam_ops_t::fuse_into_current) — no 60 x 1000-slot walk, no observation-list lookups, no candidate upload.
+// The change sets of this pass so far (new keyframe, triangulated points, the first direction's fusions) go to the table first.  OSLAM_SLAM_FUSECUR_CHECK=1: the list
+// and its flags are also built here and compared entry by entry.  done = false: not served this way (no mirror, or a list beyond the job's bounds); the rounds do it.
+static int sn_fuse_into_current(LmPass& L, std::vector<FuseSeq>& fs, bool& done) {
+    Ctx& c = L.c;
+    const int nW = L.nW;
+    int rc;
+    done = false;
+    if (!(fuse_by_id(c) && c.ops.fuse_into_current && c.ops.map_journal)) return OSLAM_OK;
+    for (int w = 0; w < nW; w++) if (!L.seq(w).map.jrOn) return OSLAM_OK;
+    if ((rc = lm_send_journal(L))) return rc;
+    std::vector<oslam_job_fuse_cur_t> cj;
+    std::vector<int> cw;
+    std::vector<std::vector<int32_t>> cpairs(nW), dIds(nW);
+    std::vector<std::vector<uint8_t>> dEx(nW);
+    for (int w = 0; w < nW; w++) {
+        if (fs[w].targets.empty()) continue;
+        Seq& s = L.seq(w);
+        const KeyFrm& kf = s.map.kfs[s.curKF];
+        oslam_job_fuse_cur_t j;
+        memset(&j, 0, sizeof(j));
+        j.slot = L.who[w]; j.kf = s.curKF; j.n_targets = (int32_t)fs[w].targets.size(); j.targets = fs[w].targets.data();
+        memcpy(j.Tcw, kf.pose.Tcw.m, 64); memcpy(j.Ow, kf.pose.Ow, 12); j.th = 3.0f;
+        cpairs[w].resize(2 * 2048); j.max_pairs = 2048; j.pairs = cpairs[w].data();
+        if (kFusecurCheck) { dIds[w].resize(16384); dEx[w].resize(16384); j.dbg_cap = 16384; j.dbg_ids = dIds[w].data(); j.dbg_excl = dEx[w].data(); }
+        cj.push_back(j); cw.push_back(w);
     }
-    if (flags & OSLAM_SLAM_LM_DEFERRED) {   // (no local BA in this configuration: only the culling is deferred)
+    L.charge(11, 2);
+    if (!cj.empty() && (rc = c.ops.fuse_into_current(c.ops.ctx, (int)cj.size(), cj.data()))) return rc;
+    L.charge_op(8);
+    for (auto& j : cj) if (j.overflow != 0) return OSLAM_OK;
+    if (kFusecurCheck) {
+        sn_build_lists(L, fs);
+        for (size_t q = 0; q < cj.size(); q++) {
+            const int w = cw[q];
+            const Seq& s = L.seq(w);
+            const std::vector<int>& pts = fs[w].pts;
+            bool same = (size_t)cj[q].n_candidates == pts.size();
+            for (size_t pi = 0; same && pi < pts.size(); pi++) {
+                const int pp = pts[pi];
+                const uint8_t ex = (s.map.pBad[pp] || s.map.mps[pp].obs_index(s.curKF) >= 0) ? 1 : 0;
+                same = dIds[w][pi] == pp && dEx[w][pi] == ex;
+                if (!same) fprintf(stderr, "OSLAM_SLAM_FUSECUR_CHECK: sequence %d keyframe %d candidate %zu: table (%d, %d), driver (%d, %d)\n", L.who[w], s.curKF, pi, dIds[w][pi], dEx[w][pi], pp, ex);
+            }
+            if (!same) { fprintf(stderr, "OSLAM_SLAM_FUSECUR_CHECK: the table's candidate list differs from the driver's (sequence %d keyframe %d: %d against %zu candidates)\n", L.who[w], s.curKF, cj[q].n_candidates, pts.size()); abort(); }
+        }
+    }
+    L.pool.parallel_for((int)cj.size(), [&](int q) { Seq& s = L.seq(cw[q]); fuse_apply_pairs(s, s.curKF, cj[q].pairs, cj[q].n_pairs); });
+    L.merge_upd();
+    L.charge(11, 3);
+    if ((rc = L.upd.run(c, true, false))) return rc;   // Replace -> ComputeDistinctiveDescriptors (src/MapPoint.cc:314)
+    L.charge_op(5);
+    done = true;
+    return OSLAM_OK;
+}
+
+// update points of the current keyframe (:517-531) and its connections
+static int sn_update_current_keyframe(LmPass& L) {
+    Ctx& c = L.c;
+    L.pool.parallel_for(L.nW, [&](int w) {
+        Seq& s = L.seq(w);
+        // The reference recomputes descriptor and normal of every point of the keyframe here.  A point that went through a full update earlier in THIS
+        // pass (ProcessNewKeyFrame, triangulation) and whose observation list has not changed since would get the same result: its position, the poses and
+        // the bad flags of the observing keyframes only change later in the pass (local BA, culling).
+        s.updList.clear();
+        const std::vector<int>& kmp = s.map.kfs[s.curKF].mp;
+        for (size_t i = 0; i < kmp.size(); i++) {
+            prefetch_ahead(s.map.mps, kmp, i, kmp.size());
+            const int p = kmp[i];
+            if (p < 0) continue;
+            const MapPt& mp = s.map.mps[p];
+            if (s.map.pBad[p] || (mp.updStep == c.mapStep && mp.updVer == mp.obsVer)) continue;
+            s.updList.push_back(p);
+        }
+    });
+    L.merge_upd();   // (sequence order, then keypoint order: the order of the serial loop this replaces)
+    L.charge(11, 4);
+    const int rc = L.upd.run(c, true, true);
+    if (rc) return rc;
+    L.charge_op(5);
+    L.pool.parallel_for(L.nW, [&](int w) { Seq& s = L.seq(w); s.map.update_connections(s.curKF, s.counter); });
+    L.charge(11, 4);
+    return OSLAM_OK;
+}
+
+static int lm_search_in_neighbors(LmPass& L) {
+    Ctx& c = L.c;
+    int rc;
+    std::vector<FuseSeq> fs(L.nW);
+    sn_target_lists(L, fs);
+    size_t maxt = 0;
+    for (const FuseSeq& f : fs) maxt = std::max(maxt, f.targets.size());
+    for (size_t t = 0; t < maxt; t++)   // the current keyframe's points into the targets (:480-490)
+        if ((rc = sn_fuse_round(L, fs, false, t))) return rc;
+    if ((rc = L.upd.finish(c))) return rc;
+    L.charge_op(5);
+    bool cur_done = false;   // the targets' points into the current keyframe (:492-515)
+    if ((rc = sn_fuse_into_current(L, fs, cur_done))) return rc;
+    if (!cur_done) {
+        sn_build_lists(L, fs);
+        L.charge(11, 2);
+        if ((rc = sn_fuse_round(L, fs, true, 0))) return rc;
+        if ((rc = L.upd.finish(c))) return rc;
+        L.charge_op(5);
+    }
+    return sn_update_current_keyframe(L);
+}
+
+// --- Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778), all windows in one batch ---
+// the window of sequence si around its current keyframe (:453-650); W.si stays -1 when the map is too young for a local BA
+static void lm_gather_window(const Ctx& c, Seq& s, int si, Ctx::Win& W) {
+    Map& m = s.map;
+    W.reset();
+    W.si = -1;
+    if (m.nKFsInMap <= 2) return;   // src/LocalMapping.cc:81
+    const int cur = s.curKF;
+    W.si = si;
+    W.kfs.push_back(cur);
+    for (int k : m.kfs[cur].ordered)
+        if (!m.kfs[k].bad) W.kfs.push_back(k);
+    W.nLocal = (int)W.kfs.size();
+    // lLocalMapPoints (src/Optimizer.cc:470-487).  mnBALocalForKF of the points is a dense per-sequence array (as mpMark in update_local_map): the loop visits
+    // ~1000 slots per local keyframe and most of them hold a point that is already in the list, so it should touch 4 bytes per slot, not a MapPt record.
+    if (s.baMark.size() < m.mps.size()) s.baMark.resize(m.mps.size() + m.mps.size() / 2 + 64, 0);
+    int* bam = s.baMark.data();
+    size_t edgeCap = 0;
+    for (int q = 0; q < W.nLocal; q++) {
+        const std::vector<int>& kmp = m.kfs[W.kfs[q]].mp;
+        const int* kp_ = kmp.data();
+        for (size_t i = 0, n = kmp.size(); i < n; i++) {
+            if (i + kPF < n) { const int pq = kp_[i + kPF]; if (pq >= 0 && bam[pq] != cur) __builtin_prefetch(&m.mps[pq].obs); }
+            const int p = kp_[i];
+            if (p < 0 || bam[p] == cur) continue;
+            bam[p] = cur;
+            if (!m.pBad[p]) { W.pts.push_back(p); edgeCap += m.mps[p].obs.size(); }
+        }
+    }
+    // Fixed keyframes (:489-504: every observer outside the local set, no bound) and the edges (:560-650) in ONE walk over the observation lists: a fixed
+    // keyframe takes the next window index the first time an observation names it, which is the order the reference's lFixedCameras list is built in.
+    std::vector<int>& slot = s.counter;   // keyframe id -> window index + 1 (restored to 0 below)
+    for (int q = 0; q < W.nLocal; q++) slot[W.kfs[q]] = q + 1;
+    W.points.resize(W.pts.size() * 3);
+    W.ekf.resize(edgeCap); W.ept.resize(edgeCap); W.eobs.resize(edgeCap * 3); W.einv.resize(edgeCap); W.eref.resize(edgeCap); W.eoct.resize(edgeCap);
+    W.pstart.resize(W.pts.size() + 1); W.pquirk.assign(W.pts.size(), 0);
+    size_t ne = 0;
+    for (size_t j = 0; j < W.pts.size(); j++) {
+        prefetch_okp_ahead(m.mps, W.pts, j, W.pts.size());
+        const int p = W.pts[j];
+        const MapPt& mp = m.mps[p];
+        W.pstart[j] = (int32_t)ne;
+        for (int d = 0; d < 3; d++) W.points[j * 3 + d] = mp.pos[d];
+        for (size_t oi = 0; oi < mp.obs.size(); oi++) {
+            const int kid = mp.obs[oi].first;
+            int q = slot[kid];
+            if (q == 0) {
+                if (m.kfs[kid].bad) { W.pquirk[j] = 1; continue; }   // (an observation the window does not carry: this point's update takes the general path)
+                W.kfs.push_back(kid);
+                slot[kid] = q = (int)W.kfs.size();
+            }
+            const ObsKp& kp = mp.okp[oi];   // mvKeysUn[idx].pt, mvuRight[idx], octave of the observing keypoint (cached beside the observation)
+            W.ekf[ne] = q - 1; W.ept[ne] = (int)j;
+            W.eobs[ne * 3] = kp.x; W.eobs[ne * 3 + 1] = kp.y; W.eobs[ne * 3 + 2] = kp.ur;
+            W.einv[ne] = c.invSigma2[kp.octave];
+            W.eoct[ne] = (uint8_t)kp.octave;
+            W.eref[ne] = std::make_pair(kid, p);
+            ne++;
+        }
+    }
+    W.pstart[W.pts.size()] = (int32_t)ne;
+    W.ekf.resize(ne); W.ept.resize(ne); W.eobs.resize(ne * 3); W.einv.resize(ne); W.eref.resize(ne); W.eoct.resize(ne);
+    // A window with more than 128 FREE keyframes (768 unknowns) is beyond the local-BA operator (OSLAM_E_CAPACITY).  The reference has no such bound.  The
+    // window is kept, DEGRADED: m.kfs[cur].ordered is weight-descending, so the current keyframe and its strongest covisible keyframes stay free up to the
+    // bound and the remaining local keyframes enter as fixed cameras (fixed = 1): their points and edges are still in the window, points and the strongest
+    // poses are still refined and outlier observations still erased.  Counted (oslam_slam_lba_window_stats [5]: degraded windows).
+    int nFreeCap = W.nLocal;   // window indices >= nFreeCap are fixed cameras
+    {
+        int nFreeKF = 0;
+        for (int q = 0; q < W.nLocal; q++) {
+            nFreeKF += W.kfs[q] != 0;
+            if (nFreeKF > kLbaMaxFreeKFs) { nFreeCap = q; break; }
+        }
+        if (nFreeCap < W.nLocal) s.lbaWindowsDegraded++;
+    }
+    W.nFree = nFreeCap;
+    W.poses.resize(W.kfs.size() * 16); W.fixed.resize(W.kfs.size());
+    for (size_t q = 0; q < W.kfs.size(); q++) {
+        memcpy(&W.poses[q * 16], m.kfs[W.kfs[q]].pose.Tcw.m, 64);
+        W.fixed[q] = (int)q >= nFreeCap ? 1 : (W.kfs[q] == 0 ? 2 : 0);
+    }
+    for (size_t q = 0; q < W.kfs.size(); q++) slot[W.kfs[q]] = 0;
+    W.poses_out.resize(W.poses.size()); W.points_out.resize(W.points.size() + 3); W.erase.assign(W.ekf.size() + 1, 0);
+    s.st[5]++; s.st[14] += (int64_t)W.ekf.size();
+    s.lbaWin[0] += W.nLocal; s.lbaWin[1] += (int64_t)W.kfs.size() - W.nLocal; s.lbaWin[2] += (int64_t)W.pts.size(); s.lbaWin[3] += (int64_t)W.ekf.size();
+}
+
+// the windows of the pass as local-BA problems; the solve now and the second half behind it (synchronous schedule), or handed to finish_local_mapping (deferred)
+static int lm_local_ba(LmPass& L) {
+    typedef Ctx::Win Win;
+    Ctx& c = L.c;
+    int rc;
+    std::vector<Win>& pool_w = c.winPool;   // the windows' arrays keep their capacity from step to step
+    if (pool_w.size() < L.who.size()) pool_w.resize(L.who.size());
+    L.pool.parallel_for(L.nW, [&](int w) { lm_gather_window(c, L.seq(w), L.who[w], pool_w[w]); });
+    std::vector<Win*> wins;
+    for (int w = 0; w < L.nW; w++) if (pool_w[w].si >= 0) wins.push_back(&pool_w[w]);
+    std::vector<oslam_lba_problem_t> probs(wins.size());
+    for (size_t i = 0; i < wins.size(); i++) {
+        Win& W = *wins[i];
+        oslam_lba_problem_t& p = probs[i];
+        p.nKF = (int)W.kfs.size(); p.poses = W.poses.data(); p.fixed = W.fixed.data(); p.nP = (int)W.pts.size(); p.points = W.points.data();
+        p.nE = (int)W.ekf.size(); p.edge_kf = W.ekf.data(); p.edge_pt = W.ept.data(); p.edge_obs = W.eobs.data(); p.edge_invSigma2 = W.einv.data();
+        p.poses_out = W.poses_out.data(); p.points_out = W.points_out.data(); p.erase = W.erase.data();
+        W.st[0] = W.st[1] = W.st[2] = W.st[3] = 0;
+        p.stats = W.st;
+        if (c.injectLbaFailure >= 0 && W.si == c.injectLbaFailure && !W.ekf.empty()) { W.ekf[0] = (int32_t)W.kfs.size(); c.injectLbaFailure = -1; }   // test hook (oslam_slam_inject_failure): an edge that names a keyframe outside the window — the operator refuses the window (OSLAM_E_INVALID)
+    }
+    L.charge(12);
+    if (L.flags & OSLAM_SLAM_LM_DEFERRED) {
+        // deferred schedule: the solve runs while the next frame is tracked; write-back, MapPoint updates and KeyFrameCulling follow in finish_local_mapping
+        Ctx::PendingLM& pd = c.pend;
+        pd.active = true; pd.who = L.who; pd.wins = wins; pd.probs.swap(probs); pd.submitted = false;
+        if (!pd.probs.empty() && c.ops.lba_submit) {
+            if ((rc = c.ops.lba_submit(c.ops.ctx, (int)pd.probs.size(), pd.probs.data()))) return rc;
+            pd.submitted = true;
+        }
+        L.charge_op(6);
+        return OSLAM_OK;
+    }
+    if (!probs.empty() && (rc = c.ops.lba(c.ops.ctx, (int)probs.size(), probs.data()))) return rc;
+    L.charge_op(6);
+    return local_mapping_back(c, L.who, wins);
+}
+
+// LocalMapping::Run (src/LocalMapping.cc:48-113) for the sequences that inserted a keyframe this step
+static int run_local_mapping(Ctx& c, const std::vector<int>& who) {
+    if (who.empty()) return OSLAM_OK;
+    LmPass L(c, who);
+    int rc;
+    L.upd.clear();
+    for (int si : who) c.seq[si]->mapVersion++;   // the map of these sequences changes below: their cached local maps are stale
+    c.mapStep++;
+    if ((rc = lm_process_new_keyframe(L))) return rc;
+    if ((L.flags & 2) && (rc = getenv("OSLAM_SLAM_CNMP_ROUNDS") ? lm_create_new_map_points_rounds(L) : lm_create_new_map_points(L))) return rc;
+    if ((L.flags & 4) && (rc = lm_search_in_neighbors(L))) return rc;
+    if (L.flags & 8) return lm_local_ba(L);
+    if (L.flags & OSLAM_SLAM_LM_DEFERRED) {   // (no local BA in this configuration: only the culling is deferred)
         c.pend.active = true; c.pend.who = who; c.pend.wins.clear(); c.pend.probs.clear(); c.pend.submitted = false;
         return OSLAM_OK;
     }

@@ -365,3 +365,23 @@ def test_golden_driver_fixture_equals_the_cpp_driver_over_the_oracle_table(oracl
     sysm.finish()
     _, Twc = sysm.trajectory(0)
     assert np.array_equal(Twc, g["trajectory"])
+
+
+def test_create_new_map_points_in_one_batch_equals_the_neighbour_rounds(oracle, monkeypatch):
+    """CPU twin of the test of the same name in tests/test_slam_driver_gpu.py, over the oracle's operator table: CreateNewMapPoints as one batch over all neighbours
+    (skip test at application time) and as one lockstep round per neighbour (OSLAM_SLAM_CNMP_ROUNDS=1, read per pass) build their jobs and apply their points through
+    the same code and must give the same points in the same order.  9 frames is the shortest make_scene_streams length at which both sequences have triangulated
+    (4 and 12 points; at 8 frames sequence 0 has none)."""
+    from slam_common import make_scene_streams, run_scene
+    n, S = 9, 2
+    seqs = make_scene_streams(S, n)
+    cfg = slam.make_config(W, H, S)
+    a = slam.System(cfg, oracle_ops(cfg))
+    pa, sa = run_scene(a, seqs, n)
+    monkeypatch.setenv("OSLAM_SLAM_CNMP_ROUNDS", "1")
+    b = slam.System(cfg, oracle_ops(cfg))
+    pb, sb = run_scene(b, seqs, n)
+    assert np.array_equal(sa, sb) and np.array_equal(pa, pb)
+    for q in range(S):
+        st = a.stats(q)
+        assert st == b.stats(q) and st["points_triangulated"] > 0, st
