@@ -48,8 +48,8 @@ static inline int div_up(int a, int b) { return (a + b - 1) / b; }
 // Device -> pinned-host transfer as a KERNEL on the caller's stream (the pinned block of hipHostMalloc is mapped into the device's address space: the stores go
 // over PCIe), used for the small downloads that end an operator (local-BA results and control blocks, Fuse matches, status words): the copy stays in the stream's
 // own queue instead of going through the runtime's copy path, which all streams of the process share.  Same-box A/B in the steady-state bench: 17.3 k frames/s
-// against 17.0 k with hipMemcpyAsync (OSLAM_D2H_SDMA=1) — within the spread; kept because it removes a dependency on that shared path.  `dst` must be
-// device-accessible host memory.
+// against 17.0 k with hipMemcpyAsync — within the spread; kept because it removes a dependency on that shared path.  `dst` must be device-accessible host
+// memory.
 hipError_t copy_to_host_async(void* dst_pinned, const void* src_dev, size_t bytes, hipStream_t s);   // (defined once, in orb_extractor.hip, next to stream_wait)
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 

@@ -1498,7 +1498,7 @@ __global__ __launch_bounds__(1024) void k_w_chol(const LbaProblem* probs, const 
 // apply the rank-16 trailing update A22 -= U12^T U12 tile by tile with v_mfma_f64_16x16x4_f64: four MFMAs per 16x16 tile, the A operand
 // (lane l: U12[4s + (l>>4)][i0 + (l&15)]) and the B operand (U12[4s + (l>>4)][k0 + (l&15)]) straight from the LDS row panel, C/D
 // (col = l&15, row = (l>>4) + 4 reg) read-modify-written in place.  The right-hand side rides along as column n.  Then a blocked back
-// substitution.  Used for systems that do not fit the LDS-resident kernel (6 nfree > kCholLdsN); OSLAM_LBA_CHOL_MFMA=1 forces it for all sizes.
+// substitution.  Used for systems that do not fit the LDS-resident kernel (6 nfree > kCholLdsN); oslam_lba_set_solver 1 forces it for all sizes.
 constexpr int kMB = 16;                       // panel width = MFMA tile edge
 constexpr int kMfmaMaxN = 6 * kLbaMaxKF;      // 768
 typedef double v4f64 __attribute__((ext_vector_type(4)));
@@ -2088,7 +2088,7 @@ struct oslam_lba {
     hipStream_t strm = nullptr;   // every copy and launch of this handle (non-blocking: handles driven by different host threads overlap on the GPU)
     bool owns_strm = true;        // false: the stream of the driver handle this solver belongs to (lba_use_stream)
     std::mutex* launch_gate = nullptr;   // held from the upload to the download of a call when set (lba_use_gate): solvers sharing a gate take turns on the device
-    bool device_pairs = true;     // pair lists of the gather Schur built by k_w_pair_* (OSLAM_LBA_HOST_PAIRS=1: by lba_build on the host, the round-2 path)
+    bool device_pairs = true;     // pair lists of the gather Schur built by k_w_pair_* (oslam_lba_set_schur 3: by lba_build on the host, the round-2 path)
     long long prof_pre_upload_ns = 0;   // host time of the last lba_launch before its upload (OSLAM_LBA_HOSTPROF)
     int wide = 1;                 // 1: every LM trial of all windows as whole-GPU launches, 0: one workgroup per window in one launch (k_lba, the round-1 kernel),
                                   // 2: one workgroup per window, LDS-resident reduced system (k_lba_win); windows that do not fit its LDS go through layout 1
@@ -2243,10 +2243,6 @@ int oslam_lba_create(oslam_lba_t** out, int max_batch, int max_keyframes, int ma
     oslam_lba* h = new oslam_lba();
     if (hipStreamCreateWithFlags(&h->strm, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); delete h; return OSLAM_E_HIP; }
     h->device = device; h->max_batch = max_batch; h->max_kf = max_keyframes;
-    if (const char* e = getenv("OSLAM_LBA_CHOL_MFMA")) h->chol_mode = atoi(e) ? 1 : 2;   // kernel experiments: 1 = matrix cores for every size, 0 = never
-    if (const char* e = getenv("OSLAM_LBA_SOLVER")) { const int v = atoi(e); if (v >= 0 && v <= 4) h->chol_mode = v; }   // A/B knob: oslam_lba_set_solver for every handle of the process
-    if (getenv("OSLAM_LBA_HOST_PAIRS")) h->device_pairs = false;
-    if (const char* e = getenv("OSLAM_LBA_SCHUR_TILES")) h->schur_tiles = atoi(e);   // 0 = always the pair gather, 1 = always tiles, 2 = per call (default)
     if (const int rc = h->h_stop.alloc_mapped(sizeof(int))) { oslam_lba_destroy(h); return rc; }
     *h->h_stop.as<int>() = 0;
     if (hipHostGetDevicePointer((void**)&h->d_stop, h->h_stop.ptr(), 0) != hipSuccess) { set_error("hipHostGetDevicePointer failed"); oslam_lba_destroy(h); return OSLAM_E_HIP; }
@@ -2280,7 +2276,7 @@ int oslam_lba_set_mode(oslam_lba_t* h, int wide) {
 int oslam_lba_set_schur(oslam_lba_t* h, int mode) {
     if (!h || mode < 0 || mode > 3) { set_error("oslam_lba_set_schur: mode must be 0 (pair gather), 1 (LDS tiles), 2 (per call) or 3 (pair gather, host-built lists)"); return OSLAM_E_INVALID; }
     h->schur_tiles = mode == 3 ? 0 : mode;
-    h->device_pairs = mode != 3 && !getenv("OSLAM_LBA_HOST_PAIRS");
+    h->device_pairs = mode != 3;
     return OSLAM_OK;
 }
 

@@ -71,8 +71,6 @@ __global__ void k_copy_to_host(uint8_t* __restrict__ dst, const uint8_t* __restr
 }
 hipError_t copy_to_host_async(void* dst_pinned, const void* src_dev, size_t bytes, hipStream_t s) {
     if (!bytes) return hipSuccess;
-    static const bool sdma = getenv("OSLAM_D2H_SDMA") != nullptr;   // A/B knob: the runtime's copy path
-    if (sdma) return hipMemcpyAsync(dst_pinned, src_dev, bytes, hipMemcpyDeviceToHost, s);
     const bool aligned = ((((uintptr_t)dst_pinned) | ((uintptr_t)src_dev)) & 15) == 0;
     const size_t n16 = aligned ? bytes / 16 : 0, units = n16 + (bytes - n16 * 16);
     const int blocks = (int)((units + 255) / 256 < 1024 ? (units + 255) / 256 : 1024);
@@ -487,16 +485,9 @@ int oslam_orb_create(oslam_orb_t** out, int nfeatures, float scaleFactor_, int n
         // caller's stream dispatched first).  In the batch-of-sequences driver that starves it: with eight handles on the card there is almost always ordinary-priority
         // work of another handle to dispatch, the blur — and with it the frame's descriptor kernel and the whole Frame::Frame stage — waits for gaps, and the stereo
         // workload (two extractions per frame) fell into phases of 10-30x its Frame::Frame time in 6 of 9 runs on fresh boxes (2.3-4.0 k instead of 22-24 k frames/s;
-        // tools/gpu/r5b_stereo_queues.sh).  Ordinary priority: 3 of 3 stereo runs at 22.4-23.3 k, the RGB-D headline 41.2-41.9 k against 41.0 k (same box).
-        // OSLAM_ORB_SIDE_PRIORITY=low restores the lowest priority (A/B knob).
-        int least = 0, greatest = 0;
-        const char* spe = getenv("OSLAM_ORB_SIDE_PRIORITY");
-        const bool low = spe && !strcmp(spe, "low");
-        if (!low || hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || hipStreamCreateWithPriority(&h->side_stream, hipStreamNonBlocking, least) != hipSuccess) {
-            (void)hipGetLastError();
-            h->side_stream = nullptr;
-            ORB_CREATE_CHECK(hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
-        }
+        // DESIGN.md section 8, "A starved side stream").  Ordinary priority: 3 of 3 stereo runs at 22.4-23.3 k, the RGB-D headline 41.2-41.9 k against 41.0 k
+        // (same box).
+        ORB_CREATE_CHECK(hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
     }
     ORB_CREATE_CHECK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
     if (getenv("OSLAM_ORB_FAST0_STREAM")) {   // kernel experiments (off: measured no gain at B = 512, the pyramid kernels slow down by what FAST gains: 2.60 ms per batch either way)

@@ -30,7 +30,7 @@ struct LbaJob {   // one handle's submission to the local-BA service (below)
 };
 
 struct HipOps {
-    LbaService* svc = nullptr;            // deferred schedule: the process-wide local-BA service of this device
+    LbaService* svc = nullptr;            // the process-wide local-BA service of this device (both schedules)
     LbaJob job; bool job_active = false;
     oslam_slam_config_t cfg;
     int S = 0, cap = 0;
@@ -42,8 +42,7 @@ struct HipOps {
     oslam_matcher_t* m_last = nullptr;
     oslam_matcher_t* m_map = nullptr;
     oslam_poseopt_t* po = nullptr;
-    oslam_lba_t* ba = nullptr;
-    oslam_lba_t* ba1 = nullptr;
+    oslam_lba_t* ba1 = nullptr;           // one window per call (n == 1); larger calls go to the local-BA service
     oslam_mappoint_t* mp = nullptr;
     oslam_frame_t* fr = nullptr;
     oslam_bow_t* bow = nullptr;
@@ -68,8 +67,9 @@ struct HipOps {
     oslam::StagePair upB;
     oslam::PinnedBuffer dnB;
     hipEvent_t tevB0 = nullptr, tevB1 = nullptr;
-    bool lazy_desc = false;                          // the same for mDescriptors (keyframe_descriptors / frame_descriptors)
-    bool lazy_keys = false;                          // frames do not send mvKeys back; register_keyframes stages the new keyframes' rows for keyframe_raw_keys
+    // true with the resident keyframe store: frames send neither mvKeys nor mDescriptors back; register_keyframes stages the new keyframes' rows for
+    // keyframe_raw_keys / keyframe_descriptors, frame_descriptors reads the current frames' rows from the extractor's batch arrays
+    bool lazy_rows = false;
     oslam::PinnedBuffer kfk; std::vector<int32_t> kfk_slots;
     static constexpr int kFuseCurStride = 16384, kFuseCurPairs = 2048;   // candidates / matches per job of fuse_into_current (beyond: overflow, the driver's own path)
     oslam::DeviceBuffer fc; uint32_t fc_stamp = 0;   // scratch of fuse_into_current / local_points_list
@@ -271,9 +271,9 @@ static int download_frames(HipOps* o, int n, const oslam_keypoint_t* d_kp, const
     OSLAM_HIP_CHECK(hipMemcpyAsync(D + oCnt, d_cnt, 4 * (size_t)n, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(hipMemcpyAsync(D + oSt, d_st, 4, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(hipMemcpyAsync(D + oSt + 4, o->d_status.as<int32_t>(), 4, hipMemcpyDeviceToHost, o->strm));
-    if (!o->lazy_keys) OSLAM_HIP_CHECK(hipMemcpyAsync(D + oKeys, d_kp, sizeof(oslam_keypoint_t) * cap * n, hipMemcpyDeviceToHost, o->strm));
+    if (!o->lazy_rows) OSLAM_HIP_CHECK(hipMemcpyAsync(D + oKeys, d_kp, sizeof(oslam_keypoint_t) * cap * n, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(hipMemcpyAsync(D + oKeysUn, o->d_keysUn.as<oslam_keypoint_t>(), sizeof(oslam_keypoint_t) * cap * n, hipMemcpyDeviceToHost, o->strm));
-    if (!o->lazy_desc) OSLAM_HIP_CHECK(hipMemcpyAsync(D + oDesc, d_desc, 32 * cap * n, hipMemcpyDeviceToHost, o->strm));
+    if (!o->lazy_rows) OSLAM_HIP_CHECK(hipMemcpyAsync(D + oDesc, d_desc, 32 * cap * n, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(hipMemcpyAsync(D + oUr, d_uR, 4 * cap * n, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(hipMemcpyAsync(D + oDp, d_dp, 4 * cap * n, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
@@ -285,9 +285,9 @@ static int download_frames(HipOps* o, int n, const oslam_keypoint_t* d_kp, const
         oslam_slam_frame_t* f = out[i];
         const size_t N = cnt[i], at = (size_t)i * cap;
         f->N = (int)N;
-        if (!o->lazy_keys) memcpy(f->keys, D + oKeys + at * sizeof(oslam_keypoint_t), N * sizeof(oslam_keypoint_t));
+        if (!o->lazy_rows) memcpy(f->keys, D + oKeys + at * sizeof(oslam_keypoint_t), N * sizeof(oslam_keypoint_t));
         memcpy(f->keysUn, D + oKeysUn + at * sizeof(oslam_keypoint_t), N * sizeof(oslam_keypoint_t));
-        if (!o->lazy_desc) memcpy(f->desc, D + oDesc + at * 32, N * 32);
+        if (!o->lazy_rows) memcpy(f->desc, D + oDesc + at * 32, N * 32);
         memcpy(f->uRight, D + oUr + at * 4, N * 4);
         memcpy(f->depth, D + oDp + at * 4, N * 4);
     });
@@ -865,7 +865,7 @@ int h_mp_update_keyed(void* p, oslam_job_mp_update_t* j, const int32_t* obs_key)
 // mvKeys of the keyframes registered by the LAST register_keyframes call (include/oslam_slam.h): staged by that call's copy launch, handed out here
 int h_keyframe_raw_keys(void* p, int n, const int32_t* slots, const int32_t* counts, oslam_keypoint_t* const* out) {
     HipOps* o = (HipOps*)p;
-    if (!o->lazy_keys) { oslam::set_error("keyframe_raw_keys: the table sends mvKeys with every frame"); return OSLAM_E_INVALID; }
+    if (!o->lazy_rows) { oslam::set_error("keyframe_raw_keys: the table sends mvKeys with every frame"); return OSLAM_E_INVALID; }
     if (n != (int)o->kfk_slots.size()) { oslam::set_error("keyframe_raw_keys: not the keyframes of the last register_keyframes call"); return OSLAM_E_INVALID; }
     const size_t cap = o->cap;
     for (int i = 0; i < n; i++) {
@@ -876,7 +876,10 @@ int h_keyframe_raw_keys(void* p, int n, const int32_t* slots, const int32_t* cou
 }
 int h_keyframe_descriptors(void* p, int n, const int32_t* slots, const int32_t* counts, uint8_t* const* out) {
     HipOps* o = (HipOps*)p;
-    if (!o->lazy_desc || n != (int)o->kfk_slots.size()) { oslam::set_error("keyframe_descriptors: not the keyframes of the last register_keyframes call"); return OSLAM_E_INVALID; }
+    if (!o->lazy_rows || n != (int)o->kfk_slots.size()) {
+        oslam::set_error("keyframe_descriptors: not the keyframes of the last register_keyframes call");
+        return OSLAM_E_INVALID;
+    }
     const size_t cap = o->cap;
     const uint8_t* base = o->kfk.bytes() + (size_t)n * cap * sizeof(oslam_keypoint_t);
     for (int i = 0; i < n; i++) {
@@ -1008,11 +1011,11 @@ static int mp_update_impl(HipOps* o, oslam_job_mp_update_t* j, const int32_t* ob
     lap_(2);
     // The job block is read by the kernels where it is (pinned, mapped into the device's address space) unless it carries the observations' descriptors, which
     // k_distinctive reads many times: every array of the keyed form is read once or twice, and the copy engine hop + its dependency cost more than the PCIe
-    // reads (Fuse: +4.4 % frames/s, same box).  Results come back through the copy kernel for the same reason.  OSLAM_SLAM_MPU_UPLOAD=1: the staged path.
-    static const bool force_upload = getenv("OSLAM_SLAM_MPU_UPLOAD") != nullptr;
+    // reads.  Results come back through the copy kernel for the same reason.
     // (only the SMALL jobs — the per-round descriptor updates of SearchInNeighbors: the large ones after a local BA read 12 bytes per observation, their kernels
     // then hold the device 20 % longer and the whole bench loses 4 %)
-    const bool upload = force_upload || (j->do_desc && !keyed) || in_bytes > (size_t)(getenv("OSLAM_SLAM_MPU_ZC_BYTES") ? atol(getenv("OSLAM_SLAM_MPU_ZC_BYTES")) : 262144);
+    constexpr size_t kZeroCopyMaxBytes = 262144;
+    const bool upload = (j->do_desc && !keyed) || in_bytes > kZeroCopyMaxBytes;
     const uint8_t* In = upload ? Dv : U;
     if (upload) OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, in_bytes, hipMemcpyHostToDevice, o->strm));
     Layout R;
@@ -1020,9 +1023,8 @@ static int mp_update_impl(HipOps* o, oslam_job_mp_update_t* j, const int32_t* ob
     OPS_CHECK(o->ensure_dn(R.off));
     // The small keyed jobs (every Fuse round's descriptor updates, the new keyframe's and the new points' updates) in ONE launch: k_mp_update_fused reads the
     // observations' descriptors from the resident keyframes, writes the results straight into the (device-accessible) result block and into the resident records.
-    // OSLAM_SLAM_MPU_FUSED=0: the separate kernels.
-    static const bool fused_on = !(getenv("OSLAM_SLAM_MPU_FUSED") && atoi(getenv("OSLAM_SLAM_MPU_FUSED")) == 0);
-    bool fused = fused_on && (!j->do_desc || keyed);
+    // Large jobs and jobs that carry their descriptors take the separate kernels below.
+    bool fused = !j->do_desc || keyed;
     if (fused && j->do_desc) for (size_t i = 0; i < P && fused; i++) fused = dstart[i + 1] - dstart[i] <= 128;   // (kDdMaxObs of csrc/mappoint.hip: beyond it k_distinctive reads from memory)
     if (fused) {
         // (the deferred form does not even enqueue the kernel here: it is launched right in front of the next operator's own kernel — the next Fuse round's search —
@@ -1168,14 +1170,14 @@ static double lba_flop(const oslam_lba_problem_t& q, const int32_t st[4]) {
 struct LbaService {
     typedef LbaJob Job;
     int device = 0;
-    // OSLAM_LBA_SERVICE_THREADS workers (default 2), each with its own solver handle and stream: while one has the device the other prepares the next batch
-    // and scatters the previous one's results (window preparation, upload and result scatter are ~a third of a call's wall time).  The device part of a call
-    // (upload .. download) is taken in turns (launch_mu): two overlapping calls ran 7.1 s of stream time per 20 bench steps against 5.3 s in turns, at the
-    // same frames/s (same-box A/B: 26.6 k overlapping, 26.3-27.1 k in turns)
-    struct Worker { oslam_lba_t* ba = nullptr; hipStream_t strm = nullptr; std::thread th; };
+    // OSLAM_LBA_SERVICE_THREADS workers (default 2), each with its own solver handle (and that handle's own stream, of ordinary priority): while one has the
+    // device the other prepares the next batch and scatters the previous one's results (window preparation, upload and result scatter are ~a third of a call's
+    // wall time).  The device part of a call (upload .. download) is taken in turns (launch_mu).  Every batch goes through the multi-launch layout
+    // (oslam_lba_set_mode 1).  What was measured against each of these choices: DESIGN.md section 7.2.
+    struct Worker { oslam_lba_t* ba = nullptr; std::thread th; };
     std::vector<std::unique_ptr<Worker>> workers;
-    int max_batch = 0, mode_small = 1, mode_big = 1, big_from = 1 << 30;
-    std::mutex launch_mu;   // one call on the device at a time: the other worker prepares / scatters meanwhile (OSLAM_LBA_SERVICE_OVERLAP=1 lets the calls overlap)
+    int max_batch = 0;
+    std::mutex launch_mu;   // one call on the device at a time: the other worker prepares / scatters meanwhile
     std::mutex mu;
     std::condition_variable cv_work, cv_done;
     std::deque<Job*> queue;
@@ -1207,7 +1209,7 @@ struct LbaService {
         for (auto& wk : sv->workers) if (wk->th.joinable()) wk->th.join();
         if (getenv("OSLAM_LBA_SERVICE_STATS")) fprintf(stderr, "[lba service] %lld calls, %lld windows (%.1f per call, max %lld)\n", sv->calls, sv->windows, sv->calls ? (double)sv->windows / sv->calls : 0.0, sv->max_windows);
         (void)hipSetDevice(sv->device);
-        for (auto& wk : sv->workers) { oslam_lba_destroy(wk->ba); if (wk->strm) (void)hipStreamDestroy(wk->strm); }
+        for (auto& wk : sv->workers) oslam_lba_destroy(wk->ba);
         slot(sv->device) = nullptr;
         delete sv;
     }
@@ -1215,39 +1217,14 @@ struct LbaService {
         OSLAM_HIP_CHECK(hipSetDevice(device));
         max_batch = getenv("OSLAM_LBA_SERVICE_MAX_BATCH") ? atoi(getenv("OSLAM_LBA_SERVICE_MAX_BATCH")) : 4096;
         const int nthreads = std::max(1, getenv("OSLAM_LBA_SERVICE_THREADS") ? atoi(getenv("OSLAM_LBA_SERVICE_THREADS")) : 2);
-        // OSLAM_LBA_SERVICE_CUS=k: the service's streams may only use k of the card's CUs (the tracking kernels of the handles keep the others to themselves)
-        const int cus = getenv("OSLAM_LBA_SERVICE_CUS") ? atoi(getenv("OSLAM_LBA_SERVICE_CUS")) : 0;
         for (int t = 0; t < nthreads; t++) {
             std::unique_ptr<Worker> wk(new Worker);
-            const int rc = oslam_lba_create(&wk->ba, max_batch, 1 << 16, 4096, 32768, device);
-            if (rc) return rc;
-            if (cus > 0) {
-                hipDeviceProp_t pr;
-                OSLAM_HIP_CHECK(hipGetDeviceProperties(&pr, device));
-                const int total = pr.multiProcessorCount;
-                std::vector<uint32_t> mask((total + 31) / 32, 0u);
-                for (int i = 0; i < std::min(cus, total); i++) mask[i >> 5] |= 1u << (i & 31);
-                OSLAM_HIP_CHECK(hipExtStreamCreateWithCUMask(&wk->strm, (uint32_t)mask.size(), mask.data()));
-                oslam::lba_use_stream(wk->ba, wk->strm);
-            } else if (const char* pe = getenv("OSLAM_LBA_SERVICE_PRIORITY")) {
-                // Rounds 4-5 gave the service's streams the LOWEST priority (the handles' short tracking / mapping kernels dispatched ahead of the queued local-BA
-                // launches).  Since the end of round 5 they are ordinary streams (the solver handle's own): same frames/s (41.10 / 41.17 k against 41.13 k, same box,
-                // alternating), 6.5 % less local-BA device time (roofline.frac 0.056 against 0.052), and no stream of the rank left that the other streams' work can
-                // starve ("A starved side stream").  OSLAM_LBA_SERVICE_PRIORITY=low / high are the A/B knobs (section 7.2).
-                if (!strcmp(pe, "low") || !strcmp(pe, "high")) {
-                    int lo = 0, hi = 0;
-                    OSLAM_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));   // (lo = numerically greatest = lowest priority)
-                    OSLAM_HIP_CHECK(hipStreamCreateWithPriority(&wk->strm, hipStreamNonBlocking, !strcmp(pe, "high") ? hi : lo));
-                    oslam::lba_use_stream(wk->ba, wk->strm);
-                }
-            }
-            if (!getenv("OSLAM_LBA_SERVICE_OVERLAP")) oslam::lba_use_gate(wk->ba, &launch_mu);
+            int rc = oslam_lba_create(&wk->ba, max_batch, 1 << 16, 4096, 32768, device);
+            if (!rc) rc = oslam_lba_set_mode(wk->ba, 1);
+            if (rc) { oslam_lba_destroy(wk->ba); return rc; }
+            oslam::lba_use_gate(wk->ba, &launch_mu);
             workers.push_back(std::move(wk));
         }
-        // layout per call: batches of at least `big_from` windows go through the one-workgroup-per-window kernel (mode 2), smaller ones through the multi-launch layout
-        mode_small = getenv("OSLAM_LBA_SERVICE_MODE") ? atoi(getenv("OSLAM_LBA_SERVICE_MODE")) : 1;
-        mode_big = getenv("OSLAM_LBA_SERVICE_MODE_BIG") ? atoi(getenv("OSLAM_LBA_SERVICE_MODE_BIG")) : mode_small;
-        big_from = getenv("OSLAM_LBA_SERVICE_BIG_FROM") ? atoi(getenv("OSLAM_LBA_SERVICE_BIG_FROM")) : (1 << 30);
         for (auto& wk : workers) { Worker* w = wk.get(); w->th = std::thread([this, w] { run(*w); }); }
         return OSLAM_OK;
     }
@@ -1261,7 +1238,7 @@ struct LbaService {
     }
     void run(Worker& wk) {
         (void)hipSetDevice(device);
-        oslam::stream_wait_thread_mode(getenv("OSLAM_LBA_SERVICE_SPIN_US") ? atoi(getenv("OSLAM_LBA_SERVICE_SPIN_US")) : 0);   // sleep, do not spin: off the critical path
+        oslam::stream_wait_thread_mode(0);   // sleep, do not spin: off the critical path
         oslam_lba_t* ba = wk.ba;
         std::vector<Job*> take;
         std::vector<oslam_lba_problem_t> probs;
@@ -1291,8 +1268,7 @@ struct LbaService {
             int rc = OSLAM_OK;
             double ms = 0; long long launches = 0;
             if (n > 0) {
-                rc = oslam_lba_set_mode(ba, n >= big_from ? mode_big : mode_small);
-                if (!rc) rc = oslam_lba_kernel_time(ba, timing ? 1 : 0, nullptr, nullptr);
+                rc = oslam_lba_kernel_time(ba, timing ? 1 : 0, nullptr, nullptr);
                 for (int at = 0; !rc && at < n; at += max_batch) rc = oslam_lba_optimize_batch(ba, std::min(max_batch, n - at), probs.data() + at, take[0]->K5);
                 if (!rc && timing) rc = oslam_lba_kernel_time(ba, 0, &ms, &launches);
             }
@@ -1342,45 +1318,32 @@ int h_lba_wait(void* p);
 int h_lba(void* p, int n, const oslam_lba_problem_t* pr) {
     HipOps* o = (HipOps*)p;
     OSLAM_HIP_CHECK(hipSetDevice(o->cfg.device));   // the HIP current device is per host thread: a handle may be stepped from any thread
-    if (o->svc && n > 1) {   // Also the synchronous schedule solves through the process-wide service: the windows of the handles that are at this point together
-                             // form shared batches, one call on the device at a time, and this handle SLEEPS meanwhile.  On its own stream a handle's call ran
-                             // against the other handles' calls (6.2 s of device time per 20 steps of the headline against 4.3 s) and its thread spun through
-                             // the wait (73 against 58 busy core-seconds): 31.8 k -> 35.4-36.3 k frames/s, same box.  OSLAM_LBA_SYNC_OWN_STREAM=1: as before.
+    if (n > 1) {   // Also the synchronous schedule solves through the process-wide service: the windows of the handles that are at this point together
+                   // form shared batches, one call on the device at a time, and this handle SLEEPS meanwhile (against a call on the handle's own stream:
+                   // DESIGN.md section 7.2).
         const int rc = h_lba_submit(p, n, pr);
         return rc ? rc : h_lba_wait(p);
     }
-    std::vector<oslam_lba_problem_t> tp;
-    std::vector<int32_t> st;
-    const oslam_lba_problem_t* caller = pr;
-    if (o->timing) {
-        tp.assign(pr, pr + n); st.assign((size_t)4 * n, 0);
-        for (int i = 0; i < n; i++) tp[i].stats = &st[4 * (size_t)i];
-        pr = tp.data();
+    if (n < 1 || !pr) { oslam::set_error("lba: no window"); return OSLAM_E_INVALID; }
+    // one window: spread over the whole GPU by the handle's own solver
+    oslam_lba_problem_t q = pr[0];
+    int32_t st[4] = {0, 0, 0, 0};
+    if (o->timing) q.stats = st;
+    int rc = oslam_lba_optimize(o->ba1, q.nKF, q.poses, q.fixed, q.nP, q.points, q.nE, q.edge_kf, q.edge_pt, q.edge_obs, q.edge_invSigma2, o->K5, 0,
+                                q.poses_out, q.points_out, q.erase, q.stats);
+    // the window was refused: it fails alone, like a window of a batch (oslam_lba_optimize_batch)
+    if ((rc == OSLAM_E_CAPACITY || rc == OSLAM_E_INVALID) && pr[0].stats) {
+        if (q.poses_out && q.poses && q.nKF > 0) memcpy(q.poses_out, q.poses, (size_t)q.nKF * 64);
+        if (q.points_out && q.points && q.nP > 0) memcpy(q.points_out, q.points, (size_t)q.nP * 12);
+        if (q.erase && q.nE > 0) memset(q.erase, 0, (size_t)q.nE);
+        q.stats[0] = -1; q.stats[1] = rc; q.stats[2] = q.stats[3] = 0;
+        rc = OSLAM_OK;
     }
-    oslam_lba_t* ba = n == 1 ? o->ba1 : o->ba;
-    int rc;
-    if (n == 1) {   // one window: spread over the whole GPU
-        rc = oslam_lba_optimize(o->ba1, pr[0].nKF, pr[0].poses, pr[0].fixed, pr[0].nP, pr[0].points, pr[0].nE, pr[0].edge_kf, pr[0].edge_pt, pr[0].edge_obs,
-                                pr[0].edge_invSigma2, o->K5, 0, pr[0].poses_out, pr[0].points_out, pr[0].erase, pr[0].stats);
-        if ((rc == OSLAM_E_CAPACITY || rc == OSLAM_E_INVALID) && caller[0].stats) {   // the window was refused: it fails alone, like a window of a batch (oslam_lba_optimize_batch)
-            const oslam_lba_problem_t& q = pr[0];
-            if (q.poses_out && q.poses && q.nKF > 0) memcpy(q.poses_out, q.poses, (size_t)q.nKF * 64);
-            if (q.points_out && q.points && q.nP > 0) memcpy(q.points_out, q.points, (size_t)q.nP * 12);
-            if (q.erase && q.nE > 0) memset(q.erase, 0, (size_t)q.nE);
-            q.stats[0] = -1; q.stats[1] = rc; q.stats[2] = q.stats[3] = 0;
-            rc = OSLAM_OK;
-        }
-    } else rc = oslam_lba_optimize_batch(o->ba, n, pr, o->K5);   // one workgroup per window, one launch
-    if (!rc && pr != caller)
-        for (int i = 0; i < n; i++) if (caller[i].stats) memcpy(caller[i].stats, pr[i].stats, 16);
+    if (!rc && q.stats != pr[0].stats && pr[0].stats) memcpy(pr[0].stats, q.stats, 16);
     if (!rc && o->timing) {
         double ms = 0; long long launches = 0;
-        OPS_CHECK(oslam_lba_kernel_time(ba, 1, &ms, &launches));
-        std::vector<double> fl(n, 0.0);   // (instrumentation inside the timed region of bench.py: on the shared workers, not serially on the stepping thread)
-        o->pool->parallel_for(n, [&](int i) { fl[i] = pr[i].stats[0] >= 0 ? lba_flop(pr[i], pr[i].stats) : 0.0; });
-        double flop = 0;
-        for (int i = 0; i < n; i++) flop += fl[i];
-        o->kt[6] += ms; o->kt[7] += (double)launches; o->kt[8] += flop;
+        OPS_CHECK(oslam_lba_kernel_time(o->ba1, 1, &ms, &launches));
+        o->kt[6] += ms; o->kt[7] += (double)launches; o->kt[8] += q.stats[0] >= 0 ? lba_flop(q, q.stats) : 0.0;
     }
     return rc;
 }
@@ -1389,7 +1352,6 @@ static void lba_service_release(LbaService* s) { LbaService::release(s); }
 
 int h_lba_submit(void* p, int n, const oslam_lba_problem_t* pr) {
     HipOps* o = (HipOps*)p;
-    if (!o->svc) { oslam::set_error("lba_submit: no local-BA service"); return OSLAM_E_INVALID; }
     if (o->job_active) { oslam::set_error("lba_submit: a submission is already in flight"); return OSLAM_E_INVALID; }
     LbaService::Job& j = o->job;
     j = LbaService::Job();
@@ -1444,17 +1406,17 @@ int h_register_keyframes(void* p, int n, const int32_t* slots, const int32_t* kf
         segs.push_back({o->d_desc + 32 * cap * slot, (uint8_t*)o->rec_desc(r), (uint32_t)(cap * 32), 0});
         segs.push_back({(const uint8_t*)(o->cur_uRight + cap * slot), (uint8_t*)o->rec_ur(r), (uint32_t)(cap * 4), 0});
     }
-    if (o->lazy_keys && (!o->d_kp || !o->d_desc)) { oslam::set_error("register_keyframes: no frame has been built yet"); return OSLAM_E_INVALID; }
-    if (o->lazy_keys) {   // mvKeys of the new keyframes: written by the same launch into a pinned block the device can address (keyframe_raw_keys hands them out)
-        const size_t need = (size_t)n * cap * (sizeof(oslam_keypoint_t) + (o->lazy_desc ? 32 : 0));
+    if (o->lazy_rows && (!o->d_kp || !o->d_desc)) { oslam::set_error("register_keyframes: no frame has been built yet"); return OSLAM_E_INVALID; }
+    if (o->lazy_rows) {   // mvKeys and mDescriptors of the new keyframes: written by the same launch into a pinned block the device can address
+                          // (keyframe_raw_keys / keyframe_descriptors hand them out)
+        const size_t need = (size_t)n * cap * (sizeof(oslam_keypoint_t) + 32);
         if (need > o->kfk.cap()) OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
         OPS_CHECK(o->kfk.grow(need, 4096));
         o->kfk_slots.assign(slots, slots + n);
         for (int i = 0; i < n; i++)
             segs.push_back({(const uint8_t*)(o->d_kp + cap * slots[i]), o->kfk.bytes() + (size_t)i * cap * sizeof(oslam_keypoint_t), (uint32_t)(cap * sizeof(oslam_keypoint_t)), 0});
-        if (o->lazy_desc)
-            for (int i = 0; i < n; i++)
-                segs.push_back({o->d_desc + 32 * cap * slots[i], o->kfk.bytes() + (size_t)n * cap * sizeof(oslam_keypoint_t) + (size_t)i * cap * 32, (uint32_t)(cap * 32), 0});
+        uint8_t* const desc_rows = o->kfk.bytes() + (size_t)n * cap * sizeof(oslam_keypoint_t);
+        for (int i = 0; i < n; i++) segs.push_back({o->d_desc + 32 * cap * slots[i], desc_rows + (size_t)i * cap * 32, (uint32_t)(cap * 32), 0});
     }
     const size_t oJobs = oslam::align_up(segs.size() * sizeof(CopySegH), 256), up_bytes = oJobs + (size_t)n * sizeof(oslam_kf_grid_job_t);
     OPS_CHECK(o->ensure_up(up_bytes));
@@ -2059,7 +2021,6 @@ int h_kernel_times(void* p, int enable, double* out) {
     if (out) memcpy(out, o->kt, sizeof(o->kt));
     memset(o->kt, 0, sizeof(o->kt));
     o->timing = enable;
-    OPS_CHECK(oslam_lba_kernel_time(o->ba, enable, nullptr, nullptr));
     OPS_CHECK(oslam_lba_kernel_time(o->ba1, enable, nullptr, nullptr));
     return OSLAM_OK;
 }
@@ -2152,89 +2113,34 @@ int h_fuse_points_keyed(void* p, int n, oslam_job_fuse_pts_t* jobs) {
         maxM = std::max(maxM, jobs[i].M);
     }
     OPS_CHECK(o->mpu_launch_pending());   // (the previous round's descriptor updates, if they were deferred: in front of this search, behind one wait)
-    static const bool staged = getenv("OSLAM_SLAM_FUSE_STAGED") != nullptr;   // A/B knob: the round-2 path (copy the records into a batch, queries, LDS window search)
-    if (!staged) {
-        // gates + window search of every candidate in ONE launch, straight from the resident records and their grids (oslam_fuse_search_device)
-        OPS_CHECK(o->sync_mp_table());
-        const size_t st = oslam::align_up((size_t)maxM, 64);
-        Layout L;
-        const size_t oM = L.take(4 * B), oSl = L.take(4 * B), oT = L.take(64 * B), oOw = L.take(12 * B), oRef = L.take(sizeof(oslam_kf_grid_ref_t) * B), oIds = L.take(4 * st * B),
-                     oEx = L.take(st * B);
-        const size_t head = L.off;
-        OPS_CHECK(o->ensure_up(L.off));
-        OPS_CHECK(o->ensure_dn(4 * st * B));   // the match table: written by the kernel itself
-        uint8_t* U = o->up.h.bytes();
-        uint8_t* Dv = o->up.d.bytes();
-        o->pool->parallel_for(n, [&](int i) {
-            const oslam_job_fuse_pts_t& j = jobs[i];
-            const size_t M = j.M;
-            ((int32_t*)(U + oM))[i] = j.M; ((int32_t*)(U + oSl))[i] = j.slot;
-            memcpy(U + oT + 64 * i, j.Tcw, 64); memcpy(U + oOw + 12 * i, j.Ow, 12);
-            memcpy(U + oIds + 4 * st * i, j.ids, 4 * M); memcpy(U + oEx + st * i, j.excl, M);
-            oslam_kf_grid_ref_t& ref = ((oslam_kf_grid_ref_t*)(U + oRef))[i];
-            ref.cell_end = o->rec_cell_end(rec[i]); ref.cand = o->rec_cand(rec[i]); ref.desc = o->rec_desc(rec[i]);
-        });
-        // The job block (~5 KB per job) is read by the kernel where it is — the pinned staging block is mapped into the device's address space — instead of
-        // being copied first: one dependent copy-engine hop less per SearchInNeighbors round (OSLAM_SLAM_FUSE_UPLOAD=1 restores the copy: A/B knob).
-        static const bool upload = getenv("OSLAM_SLAM_FUSE_UPLOAD") != nullptr;
-        const uint8_t* In = upload ? Dv : U;
-        if (upload) OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, head, hipMemcpyHostToDevice, o->strm));
-        o->t_begin();
-        OPS_CHECK(oslam_fuse_search_device(n, (int)st, (const oslam_kf_grid_ref_t*)(In + oRef), (const int32_t*)(In + oSl), (const int32_t*)(In + oM), (const int32_t*)(In + oIds),
-                                           In + oEx, o->d_mp_tab.as<uint8_t*>(), (const float*)(In + oT), (const float*)(In + oOw), o->K5, o->bounds, jobs[0].th, o->logScale, o->scale,
-                                           o->invSigma2, o->cfg.nLevels, (int32_t*)o->dn.bytes(), o->strm));   // (every query writes its one result: straight into the pinned result block, no copy kernel behind it)
-        o->t_end();
-        OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
-        o->t_collect(4, 1, 0);
-        o->pool->parallel_for(n, [&](int i) { memcpy(jobs[i].q_match, o->dn.bytes() + 4 * st * i, 4 * (size_t)jobs[i].M); });
-        return OSLAM_OK;
-    }
-    if (maxM > o->max_local) {
-        OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
-        oslam_matcher_destroy(o->m_map);
-        o->m_map = nullptr;
-        o->max_local = (int)oslam::align_up((size_t)maxM + maxM / 2, 64);
-        OPS_CHECK(oslam_matcher_create(&o->m_map, o->S, o->cap, o->max_local, o->cfg.device));
-    }
+    // gates + window search of every candidate in ONE launch, straight from the resident records and their grids (oslam_fuse_search_device)
     OPS_CHECK(o->sync_mp_table());
     const size_t st = oslam::align_up((size_t)maxM, 64);
     Layout L;
-    const size_t oN = L.take(4 * B), oM = L.take(4 * B), oSl = L.take(4 * B), oT = L.take(64 * B), oOw = L.take(12 * B), oSeg = L.take(sizeof(CopySegH) * 3 * B),
+    const size_t oM = L.take(4 * B), oSl = L.take(4 * B), oT = L.take(64 * B), oOw = L.take(12 * B), oRef = L.take(sizeof(oslam_kf_grid_ref_t) * B),
                  oIds = L.take(4 * st * B), oEx = L.take(st * B);
-    const size_t head = L.off;
-    const size_t oQ = L.take(sizeof(oslam_proj_query_t) * st * B), oKeys = L.take(sizeof(oslam_keypoint_t) * cap * B), oUr = L.take(4 * cap * B), oDesc = L.take(32 * cap * B);
     OPS_CHECK(o->ensure_up(L.off));
+    OPS_CHECK(o->ensure_dn(4 * st * B));   // the match table: written by the kernel itself
+    // The job block (~5 KB per job) is read by the kernel where it is — the pinned staging block is mapped into the device's address space — instead of
+    // being copied first: one dependent copy-engine hop less per SearchInNeighbors round.
     uint8_t* U = o->up.h.bytes();
-    uint8_t* Dv = o->up.d.bytes();
-    CopySegH* segs = (CopySegH*)(U + oSeg);
     o->pool->parallel_for(n, [&](int i) {
         const oslam_job_fuse_pts_t& j = jobs[i];
-        const size_t N = j.N, M = j.M;
-        ((int32_t*)(U + oN))[i] = j.N; ((int32_t*)(U + oM))[i] = j.M; ((int32_t*)(U + oSl))[i] = j.slot;
+        const size_t M = j.M;
+        ((int32_t*)(U + oM))[i] = j.M; ((int32_t*)(U + oSl))[i] = j.slot;
         memcpy(U + oT + 64 * i, j.Tcw, 64); memcpy(U + oOw + 12 * i, j.Ow, 12);
         memcpy(U + oIds + 4 * st * i, j.ids, 4 * M); memcpy(U + oEx + st * i, j.excl, M);
-        segs[3 * i] = {(const uint8_t*)o->rec_keys(rec[i]), Dv + oKeys + sizeof(oslam_keypoint_t) * cap * i, (uint32_t)(sizeof(oslam_keypoint_t) * N), 0};
-        segs[3 * i + 1] = {(const uint8_t*)o->rec_ur(rec[i]), Dv + oUr + 4 * cap * i, (uint32_t)(4 * N), 0};
-        segs[3 * i + 2] = {o->rec_desc(rec[i]), Dv + oDesc + 32 * cap * i, (uint32_t)(32 * N), 0};
+        oslam_kf_grid_ref_t& ref = ((oslam_kf_grid_ref_t*)(U + oRef))[i];
+        ref.cell_end = o->rec_cell_end(rec[i]); ref.cand = o->rec_cand(rec[i]); ref.desc = o->rec_desc(rec[i]);
     });
-    OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, head, hipMemcpyHostToDevice, o->strm));
     o->t_begin();
-    OPS_CHECK(oslam_copy_segments_device(Dv + oSeg, 3 * n, o->strm));
-    OPS_CHECK(oslam_fuse_queries_device(n, (int)st, (const int32_t*)(Dv + oSl), (const int32_t*)(Dv + oM), (const int32_t*)(Dv + oIds), Dv + oEx, o->d_mp_tab.as<uint8_t*>(),
-                                        (const float*)(Dv + oT), (const float*)(Dv + oOw), o->K5, o->bounds, jobs[0].th, o->logScale, o->scale, o->cfg.nLevels,
-                                        (oslam_proj_query_t*)(Dv + oQ), o->strm));
-    oslam_match_frames_t fr;
-    fr.keysUn = (const oslam_keypoint_t*)(Dv + oKeys); fr.kp_stride = (int)cap; fr.uRight = (const float*)(Dv + oUr); fr.desc = Dv + oDesc; fr.blocked = nullptr;
-    fr.n_kps = (const int32_t*)(Dv + oN); fr.n_kps_const = 0;
-    fr.minX = o->bounds[0]; fr.minY = o->bounds[1]; fr.maxX = o->bounds[2]; fr.maxY = o->bounds[3];
-    OPS_CHECK(oslam_match_fuse_batch_device(o->m_map, &fr, (const oslam_proj_query_t*)(Dv + oQ), (int)st, (const int32_t*)(Dv + oM), 0, n, o->invSigma2, o->cfg.nLevels, o->strm));
+    // (every query writes its one result: straight into the pinned result block, no copy kernel behind it)
+    OPS_CHECK(oslam_fuse_search_device(n, (int)st, (const oslam_kf_grid_ref_t*)(U + oRef), (const int32_t*)(U + oSl), (const int32_t*)(U + oM),
+                                       (const int32_t*)(U + oIds), U + oEx, o->d_mp_tab.as<uint8_t*>(), (const float*)(U + oT), (const float*)(U + oOw), o->K5,
+                                       o->bounds, jobs[0].th, o->logScale, o->scale, o->invSigma2, o->cfg.nLevels, (int32_t*)o->dn.bytes(), o->strm));
     o->t_end();
-    const int32_t* d_qm;
-    OPS_CHECK(oslam_match_results_device(o->m_map, &d_qm, nullptr, nullptr, nullptr, nullptr, nullptr));
-    OPS_CHECK(o->ensure_dn(4 * st * B));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes(), d_qm, 4 * st * B, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
-    o->t_collect(4, 3, 0);
+    o->t_collect(4, 1, 0);
     o->pool->parallel_for(n, [&](int i) { memcpy(jobs[i].q_match, o->dn.bytes() + 4 * st * i, 4 * (size_t)jobs[i].M); });
     return OSLAM_OK;
 }
@@ -2275,7 +2181,7 @@ void h_destroy(void* p) {
     if (o->job_active) (void)h_lba_wait(o);   // (the submitted windows' arrays belong to the driver handle being destroyed)
     lba_service_release(o->svc);
     oslam_orb_destroy(o->orb); oslam_orb_destroy(o->orbR); oslam_stereo_destroy(o->stereo); oslam_matcher_destroy(o->m_last); oslam_matcher_destroy(o->m_map); oslam_poseopt_destroy(o->po);
-    oslam_lba_destroy(o->ba); oslam_lba_destroy(o->ba1); oslam_mappoint_destroy(o->mp); oslam_frame_destroy(o->fr); oslam_bow_destroy(o->bow);
+    oslam_lba_destroy(o->ba1); oslam_mappoint_destroy(o->mp); oslam_frame_destroy(o->fr); oslam_bow_destroy(o->bow);
     delete o->pool;
     if (o->tev0) (void)hipEventDestroy(o->tev0);
     if (o->tevB0) (void)hipEventDestroy(o->tevB0);
@@ -2308,21 +2214,18 @@ int oslam_slam_make_hip_ops(const oslam_slam_config_t* cfg, oslam_slam_ops_t* op
     if (!rc && cfg->sensor == 1) rc = oslam_orb_create(&o->orbR, cfg->nFeatures, cfg->scaleFactor, cfg->nLevels, cfg->iniThFAST, cfg->minThFAST, cfg->width, cfg->height, o->S, dev);
     if (!rc && cfg->sensor == 1) rc = oslam_stereo_create(&o->stereo, o->S, o->cap, dev);
     if (!rc) rc = oslam_poseopt_create(&o->po, o->S, o->cap, dev);
-    if (!rc) rc = oslam_lba_create(&o->ba, o->S, 1 << 16, 4096, 32768, dev);    // keyframes / points / edges per window grow on demand (include/oslam_hip.h); <= 128 FREE keyframes
+    // the handle's own solver takes the calls of ONE window; larger calls go to the local-BA service.  Keyframes / points / edges per window grow on demand
+    // (include/oslam_hip.h); <= 128 FREE keyframes
     if (!rc) rc = oslam_lba_create(&o->ba1, 1, 1 << 16, 4096, 32768, dev);
-    // batches of windows: every LM trial of ALL windows as short whole-GPU launches (mode 1: the windows of a call spread over all CUs and the kernels of the other
-    // handles interleave; the Schur complement is formed on chip by tiles).  OSLAM_LBA_BATCH_MODE = 2 (one workgroup per window, the whole schedule in one launch:
-    // the most work per CU-second, but a call of ~40 windows then holds 40 CUs for tens of milliseconds and the other handles' short kernels queue behind the
-    // windows of all handles: measured 7.6 k against 16.8 k frames/s in bench.py's steady state) or 0 (the round-1 compact kernel) are A/B knobs
-    if (!rc) rc = oslam_lba_set_mode(o->ba, getenv("OSLAM_LBA_BATCH_MODE") ? atoi(getenv("OSLAM_LBA_BATCH_MODE")) : (getenv("OSLAM_LBA_BATCH_COMPACT") ? 0 : 1));
     if (!rc) rc = oslam_mappoint_create(&o->mp, dev);
     if (!rc) rc = oslam_frame_create(&o->fr, dev);
     if (!rc) rc = oslam_bow_create(&o->bow, o->cap, dev);
-    // One stream per driver handle: the operators run one after the other on the handle's thread, so the solvers and batch matchers use o->strm instead of
-    // a stream each (OSLAM_SLAM_OWN_STREAMS=1 restores the separate streams: an A/B knob).
-    if (!rc && o->strm && !getenv("OSLAM_SLAM_OWN_STREAMS")) {
-        oslam::lba_use_stream(o->ba, o->strm); oslam::lba_use_stream(o->ba1, o->strm);
-        oslam::bow_use_stream(o->bow, o->strm); oslam::mappoint_use_stream(o->mp, o->strm);
+    // One stream per driver handle: the operators run one after the other on the handle's thread, so the solver and the batch matchers use o->strm instead of
+    // a stream each.
+    if (!rc && o->strm) {
+        oslam::lba_use_stream(o->ba1, o->strm);
+        oslam::bow_use_stream(o->bow, o->strm);
+        oslam::mappoint_use_stream(o->mp, o->strm);
     }
     if (!rc) rc = oslam_orb_get_scale_tables(o->orb, o->scale, o->invScale, o->sigma2, o->invSigma2, nullptr);
     o->K4[0] = cfg->fx; o->K4[1] = cfg->fy; o->K4[2] = cfg->cx; o->K4[3] = cfg->cy;
@@ -2351,18 +2254,48 @@ int oslam_slam_make_hip_ops(const oslam_slam_config_t* cfg, oslam_slam_ops_t* op
     ops->search_last = h_search_last; ops->search_local = h_search_local; ops->pose_opt = h_pose_opt; ops->mp_update = h_mp_update; ops->lba = h_lba;
     ops->fuse = h_fuse; ops->bow = h_bow; ops->triangulate = h_triangulate; ops->destroy = h_destroy; ops->frames_stereo = cfg->sensor == 1 ? h_frames_stereo : nullptr;
     ops->kernel_times = h_kernel_times; ops->object_kps = h_object_kps; ops->pose_opt2 = h_pose_opt2;
-    const bool deferred_cfg = (cfg->local_mapping & OSLAM_SLAM_LM_DEFERRED) != 0;
-    if (deferred_cfg ? !getenv("OSLAM_LBA_NO_SERVICE") : !getenv("OSLAM_LBA_SYNC_OWN_STREAM")) {   // (OSLAM_LBA_NO_SERVICE=1: the deferred schedule with the handle's own solver at collection time)
-        o->svc = LbaService::acquire(dev);
-        if (!o->svc) { h_destroy(o); return OSLAM_E_HIP; }
-        if (deferred_cfg) { ops->lba_submit = h_lba_submit; ops->lba_wait = h_lba_wait; }
+    // Local BA: both schedules solve calls of more than one window through the process-wide service of the device; the deferred schedule submits and collects.
+    o->svc = LbaService::acquire(dev);
+    if (!o->svc) { h_destroy(o); return OSLAM_E_HIP; }
+    if (cfg->local_mapping & OSLAM_SLAM_LM_DEFERRED) {
+        ops->lba_submit = h_lba_submit;
+        ops->lba_wait = h_lba_wait;
     }
-    o->mp_tab_on = getenv("OSLAM_SLAM_NO_RESIDENT_POINTS") == nullptr;
-    if (o->mp_tab_on) { ops->point_record = h_point_record; ops->resident_points = h_resident_points; }
-    if (!getenv("OSLAM_SLAM_NO_WINDOW_UPDATES")) ops->mp_update_windows = h_mp_update_windows;   // (A/B: the MapPoint updates after a local BA through mp_update as before)
-    if (!getenv("OSLAM_SLAM_NO_RESIDENT_KF") && !getenv("OSLAM_SLAM_NO_MIRROR")) { ops->map_journal = h_map_journal; ops->kf_culling_counts = h_kf_culling_counts; ops->kf_culling_collect = h_kf_culling_collect; if (o->mp_tab_on && !getenv("OSLAM_SLAM_FUSECUR_HOST")) ops->fuse_into_current = h_fuse_into_current; ops->local_points_list = h_local_points_list; }
-    if (!getenv("OSLAM_SLAM_NO_RESIDENT_KF")) { ops->register_keyframes = h_register_keyframes; if (!getenv("OSLAM_SLAM_KEEP_CULLED_RECORDS")) ops->release_keyframes = h_release_keyframes; ops->bow_keyed = h_bow_keyed; ops->fuse_keyed = h_fuse_keyed; ops->mp_update_keyed = h_mp_update_keyed; if (!getenv("OSLAM_SLAM_EAGER_KEYS")) { o->lazy_keys = true; ops->keyframe_raw_keys = h_keyframe_raw_keys; if (!getenv("OSLAM_SLAM_EAGER_DESC")) { o->lazy_desc = true; ops->keyframe_descriptors = h_keyframe_descriptors; ops->frame_descriptors = h_frame_descriptors; } } ops->mp_update_keyed_async = h_mp_update_keyed_async; ops->mp_update_collect = h_mp_update_collect;
-        if (!getenv("OSLAM_SLAM_HOST_BOW_NODES")) { ops->bow_nodes_keyed = h_bow_nodes_keyed; ops->voc_nodes_keyed = h_voc_nodes_keyed; }
-        if (o->mp_tab_on && !getenv("OSLAM_SLAM_HOST_FUSE_QUERIES")) ops->fuse_points_keyed = h_fuse_points_keyed; }
+    ops->mp_update_windows = h_mp_update_windows;
+
+    // Optional operators.  The driver falls back to its host path where one is NULL; which ones a table carries depends on two stores and one switch.
+    // tests/test_slam_driver_gpu.py::test_resident_local_maps_and_keyframes_leave_the_run_unchanged switches both stores off.
+    const bool resident_points = getenv("OSLAM_SLAM_NO_RESIDENT_POINTS") == nullptr;
+    const bool resident_kf = getenv("OSLAM_SLAM_NO_RESIDENT_KF") == nullptr;
+    o->mp_tab_on = resident_points;
+    if (resident_points) {   // OSLAM_SLAM_NO_RESIDENT_POINTS unset: a record per map point, jobs name points by id
+        ops->point_record = h_point_record;
+        ops->resident_points = h_resident_points;
+    }
+    if (resident_kf) {   // OSLAM_SLAM_NO_RESIDENT_KF unset: the resident keyframe store and the device mirror of the observation graph
+        o->lazy_rows = true;
+        ops->register_keyframes = h_register_keyframes;
+        ops->release_keyframes = h_release_keyframes;
+        ops->keyframe_raw_keys = h_keyframe_raw_keys;
+        ops->keyframe_descriptors = h_keyframe_descriptors;
+        ops->frame_descriptors = h_frame_descriptors;
+        ops->bow_keyed = h_bow_keyed;
+        ops->bow_nodes_keyed = h_bow_nodes_keyed;
+        ops->voc_nodes_keyed = h_voc_nodes_keyed;
+        ops->fuse_keyed = h_fuse_keyed;
+        ops->mp_update_keyed = h_mp_update_keyed;
+        ops->mp_update_keyed_async = h_mp_update_keyed_async;
+        ops->mp_update_collect = h_mp_update_collect;
+        ops->map_journal = h_map_journal;
+        ops->kf_culling_counts = h_kf_culling_counts;
+        ops->kf_culling_collect = h_kf_culling_collect;
+        ops->local_points_list = h_local_points_list;
+    }
+    if (resident_kf && resident_points) {   // operators that read both stores
+        ops->fuse_points_keyed = h_fuse_points_keyed;
+        // OSLAM_SLAM_FUSECUR_HOST: the driver's own walk of SearchInNeighbors' second direction, the "host" run of
+        // tests/test_slam_driver_gpu.py::test_device_culling_counts_equal_the_host_walk
+        if (!getenv("OSLAM_SLAM_FUSECUR_HOST")) ops->fuse_into_current = h_fuse_into_current;
+    }
     return OSLAM_OK;
 }
