@@ -1,7 +1,7 @@
 // orb_slam2_adapter.hpp — header-only C++ adapter that re-exposes the reference's class API on top of the C ABI in oslam_hip.h:
 // ORB_SLAM2::ORBextractor (include/ORBextractor.h:45-110), ORB_SLAM2::ORBmatcher (include/ORBmatcher.h:41-83: both projection searches,
 // SearchByBoW, SearchForTriangulation, Fuse, SearchBySim3, DescriptorDistance), Frame::ComputeStereoMatches (src/Frame.cc:706), ORB_SLAM2::Optimizer
-// (include/Optimizer.h:38-46: PoseOptimization, LocalBundleAdjustment, BundleAdjustment) and ObjectOptimizer::PoseOptimization2
+// (include/Optimizer.h:38-57: PoseOptimization, LocalBundleAdjustment, BundleAdjustment, OptimizeSim3) and ObjectOptimizer::PoseOptimization2
 // (include/ObjectOptimizer.h:23), ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: loadFromTextFile, transform, score) ORB_SLAM2::PnPsolver (include/PnPsolver.h: SetRansacParameters, iterate, find) and ORB_SLAM2::Sim3Solver (include/Sim3Solver.h: SetRansacParameters, iterate, find, GetEstimatedRotation / Translation / Scale).  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
 // "view" of exactly the members it reads and writes (the gather loops are in INTEGRATION.md).  tests/adapter_program.cc uses nothing but
 // these classes; tests/test_adapter_gpu.py builds it, runs it and compares its outputs with the ctypes path.
@@ -421,8 +421,82 @@ struct BAGraph {
     float fx, fy, cx, cy, mbf;
 };
 
+// Flat view of what Optimizer::OptimizeSim3 reads of a KeyFrame and of its map points (src/Optimizer.cc:1046-1178); one entry per keypoint
+struct Sim3OptKeyFrameView {
+    int N;                                // mvKeysUn.size() = GetMapPointMatches().size()
+    const oslam::KeyPoint* mvKeysUn;
+    const uint8_t* has_mp;                // pMP && !pMP->isBad() of the keypoint's map point
+    const float* Xw;                      // [N][3] pMP->GetWorldPos()
+    const float* mvInvLevelSigma2;
+    float Tcw[16];                        // GetRotation() / GetTranslation(), row-major 4 x 4
+    float fx, fy, cx, cy;                 // mK
+};
+struct Sim3 {                             // g2o::Sim3 as rotation().toRotationMatrix() (row-major), translation(), scale()
+    double R[9], t[3], s;
+};
+
 class Optimizer {
 public:
+    // int static OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2, const bool bFixScale)
+    // (include/Optimizer.h:56, src/Optimizer.cc:1046-1241).  vpMatches1 [KF1.N] as SearchBySim3 leaves it: -1 = NULL, a value in [0, KF2.N) = the map point
+    // of that keypoint of KF2 (its GetIndexInKeyFrame(pKF2)), anything else = a map point without an index in KF2 (skipped by :1114, the entry stays).
+    // Entries the reference clears become -1.  g2oS12 is read as the floats LoopClosing builds gScm from (:326) and written when the reference writes it.
+    static int OptimizeSim3(const Sim3OptKeyFrameView& KF1, const Sim3OptKeyFrameView& KF2, std::vector<int32_t>& vpMatches1, Sim3& g2oS12, float th2, bool bFixScale) {
+        if ((int)vpMatches1.size() != KF1.N) throw std::runtime_error("OptimizeSim3: vpMatches1 must have one entry per keypoint of KF1");
+        std::vector<float> X1, X2, o1, o2, i1, i2;
+        std::vector<int> row;   // vnIndexEdge
+        for (int i = 0; i < KF1.N; i++) {   // :1099-1137
+            const int k2 = vpMatches1[i];
+            if (k2 == -1) continue;
+            if (k2 < 0 || k2 >= KF2.N) continue;                  // i2 < 0
+            if (!KF1.has_mp[i] || !KF2.has_mp[k2]) continue;      // !pMP1 || pMP1->isBad() || pMP2->isBad()
+            float P[3];
+            to_camera(KF1.Tcw, KF1.Xw + (size_t)i * 3, P); X1.insert(X1.end(), P, P + 3);
+            to_camera(KF2.Tcw, KF2.Xw + (size_t)k2 * 3, P); X2.insert(X2.end(), P, P + 3);
+            o1.push_back(KF1.mvKeysUn[i].x); o1.push_back(KF1.mvKeysUn[i].y); i1.push_back(KF1.mvInvLevelSigma2[KF1.mvKeysUn[i].octave]);
+            o2.push_back(KF2.mvKeysUn[k2].x); o2.push_back(KF2.mvKeysUn[k2].y); i2.push_back(KF2.mvInvLevelSigma2[KF2.mvKeysUn[k2].octave]);
+            row.push_back(i);
+        }
+        const int n = (int)row.size();
+        oslam_sim3_opt_problem_t pr;
+        pr.count = n; pr.offset = 0;
+        pr.fx1 = KF1.fx; pr.fy1 = KF1.fy; pr.cx1 = KF1.cx; pr.cy1 = KF1.cy; pr.fx2 = KF2.fx; pr.fy2 = KF2.fy; pr.cx2 = KF2.cx; pr.cy2 = KF2.cy;
+        pr.s12 = (float)g2oS12.s;
+        for (int k = 0; k < 9; k++) pr.R12[k] = (float)g2oS12.R[k];
+        for (int k = 0; k < 3; k++) pr.t12[k] = (float)g2oS12.t[k];
+        pr.th2 = th2; pr.fix_scale = bFixScale ? 1 : 0;
+        double S[13];
+        memcpy(S, g2oS12.R, sizeof(g2oS12.R)); memcpy(S + 9, g2oS12.t, sizeof(g2oS12.t)); S[12] = g2oS12.s;
+        std::vector<uint8_t> inl((size_t)n + 1, 0);
+        int32_t status[4] = {0, 0, 0, 0};
+        oslam::throw_on(oslam_optimize_sim3_batch(sim3_opt_handle(n), 1, &pr, n, X1.data(), X2.data(), o1.data(), o2.data(), i1.data(), i2.data(), S, inl.data(), status, nullptr,
+                                                  nullptr));
+        for (int e = 0; e < n; e++)
+            if (!inl[e]) vpMatches1[row[e]] = -1;
+        if (status[0] < 0) return 0;   // (an input that is not finite: every entry is cleared, g2oS12 stays)
+        memcpy(g2oS12.R, S, sizeof(g2oS12.R)); memcpy(g2oS12.t, S + 9, sizeof(g2oS12.t)); g2oS12.s = S[12];   // (S is unchanged where the reference returns early)
+        return status[0];
+    }
+    // cv::Mat P3Dc = Rcw * P3Dw + tcw (:1118, :1126): the three float products summed in float from left to right, `+ t` in double, rounded once
+    static void to_camera(const float T[16], const float X[3], float P[3]) {
+        for (int r = 0; r < 3; r++) {
+            const float p0 = T[4 * r] * X[0], p1 = T[4 * r + 1] * X[1], p2 = T[4 * r + 2] * X[2];
+            const float s01 = p0 + p1;
+            const float s = s01 + p2;
+            P[r] = (float)((double)s + (double)T[4 * r + 3]);
+        }
+    }
+    static oslam_sim3_opt_t* sim3_opt_handle(int n) {   // one handle per thread (the reference's static methods keep no state)
+        static thread_local oslam_sim3_opt_t* h = nullptr;
+        static thread_local int cap = 0;
+        if (!h || n > cap) {
+            oslam_sim3_opt_destroy(h);
+            h = nullptr;
+            cap = n < 2400 ? 2400 : n;
+            oslam::throw_on(oslam_sim3_opt_create(&h, 1, cap, 0));
+        }
+        return h;
+    }
     // int static PoseOptimization(Frame* pFrame) (include/Optimizer.h:46)
     static int PoseOptimization(PoseFrameView& F) {
         std::vector<float> obs, inv;

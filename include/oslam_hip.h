@@ -807,8 +807,7 @@ int oslam_pnp_epnp(oslam_pnp_t* h, int n_sets, const int32_t* counts, const int3
  * Sim3 solver — ORB_SLAM2::Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc: Horn's closed form inside RANSAC), the numerical operator of
  * LoopClosing::ComputeSim3 (src/LoopClosing.cc:232-343), for batches of independent problems (one per loop candidate of every sequence): one round of
  * ComputeSim3's while loop — iterate(5) of every live solver — is one call.  The driver does not close loops and does not call it.  What follows a
- * returned Sim3 there: ORBmatcher::SearchBySim3 is the next section; Optimizer::OptimizeSim3 is out of scope (its g2o Sim3 vertex and edge types are
- * not in the reference tree).
+ * returned Sim3 there: ORBmatcher::SearchBySim3 is the next section and Optimizer::OptimizeSim3 the one after it.
  *
  * A problem is `count` correspondences at `offset` of the packed arrays — X3Dc1, X3Dc2 (the two map points in the frames of their own cameras,
  * :94-98) and sigma2_1, sigma2_2 (mvLevelSigma2[octave] of the two keypoints, :84-85), all float — the intrinsics of both cameras (mK1, mK2), a seed
@@ -964,6 +963,87 @@ int oslam_match_search_by_sim3_batch(oslam_sim3_match_t* h, int n_pairs, const o
 int oslam_match_search_by_sim3_batch_device(oslam_sim3_match_t* h, int n_pairs, const oslam_sim3_pair_t* d_pairs, const oslam_sim3_match_rows_t* rows, int n_out,
                                             const int32_t* d_matched_in, const oslam_camera_t* cam, const float bounds[4], const float* scaleFactors, int nlevels,
                                             float logScaleFactor, int32_t* d_match12, int32_t* d_n_found, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * OptimizeSim3 — Optimizer::OptimizeSim3 (include/Optimizer.h, src/Optimizer.cc:1046-1241), called by LoopClosing::ComputeSim3 with th2 = 10 on the
+ * matches SearchBySim3 has completed (src/LoopClosing.cc:327), for batches of independent problems: one call is that step of every candidate of every
+ * sequence, and its return value is what the `nInliers >= 20` decision (:330) reads.  An operator: the driver does not close loops and does not call it.
+ *
+ * A problem is `count` correspondences at `offset` of the packed arrays, one row per pair that passed :1101-1114 (both map points exist, neither is
+ * bad, the second has an index in KF2): X3Dc1 = R1w Xw1 + t1w and X3Dc2 = R2w Xw2 + t2w (:1118, :1126: the float cv::Mat expressions), obs1, obs2 (the
+ * two undistorted keypoints) and invSigma2_1, invSigma2_2 (mvInvLevelSigma2 of their octaves), all float; both cameras' fx, fy, cx, cy; the Sim3 as
+ * the floats LoopClosing builds gScm from (s12, R12 row-major, t12, :326); th2 and bFixScale.  Everything is fp64 from there on.
+ *
+ * Graph (:1068-1178): one VertexSim3Expmap (S12) and per correspondence two fixed points and two edges with a 2 x 2 information invSigma2 * I and
+ * a Huber kernel of delta = (double)sqrtf(th2):
+ *   EdgeSim3ProjectXYZ          e12 = obs1 - cam_map1(project(S12.map(X3Dc2)))
+ *   EdgeInverseSim3ProjectXYZ   e21 = obs2 - cam_map2(project(S12.inverse().map(X3Dc1)))
+ * with map(x) = s (r x) + t, inverse() = (r*, r* ((-1 / s) t), 1 / s), project(v) = v.xy / v.z, cam_map(v) = v f + c; there is no depth test.
+ * Flow (:1181-1240): optimize(5); every pair with e12.chi2() > th2 || e21.chi2() > th2 is cleared and removed (nBad); with nCorrespondences - nBad < 10
+ * the call returns 0 and g2oS12 stays as it was (the cleared entries stay cleared); otherwise optimize(nBad > 0 ? 10 : 5) on the rest, the same test
+ * again (it clears entries and counts nIn, it removes nothing), g2oS12 := the estimate, return nIn.  chi2() is error . information . error of the
+ * edge's stored _error, not robustified: after an optimize() whose last trial was rejected that is the rejected trial's error (the estimate is popped,
+ * the errors are not recomputed).
+ *
+ * The g2o pieces, restated from the published ORB_SLAM2 Thirdparty/g2o sources (types_seven_dof_expmap, sim3.h, base_binary_edge.hpp,
+ * optimization_algorithm_levenberg.cpp, linear_solver_dense.h) in the way csrc/se3_math.h restates the SE3 ones:
+ *  - both edges' linearizeOplus are commented out there, so the Jacobian is BaseBinaryEdge's numeric one: per dimension d of the Sim3 vertex push,
+ *    oplus(+delta e_d), computeError, pop, the same with -delta, delta = 1e-9; the column is scalar * (e+ - e-) with scalar = 1.0 / (2 delta) — a
+ *    product with the reciprocal, where a description from memory may say a quotient; the points are fixed and get none.
+ *  - VertexSim3Expmap::oplusImpl: update[6] = 0 with _fix_scale, estimate = Sim3(update) * estimate.
+ *  - Sim3(Vector7d) with (omega, upsilon, sigma): s = exp(sigma), eps = 1e-5, four branches on |sigma| < eps and theta < eps; R = I + Omega + Omega^2
+ *    for theta < eps, Rodrigues otherwise; t = (A Omega + B Omega^2 + C I) upsilon; r = Quaterniond(R), not normalised.  In the branch |sigma| >= eps,
+ *    theta < eps the published text has B = ((sigma^2 / 2 - sigma + 1) s) / sigma^3 (the series of that branch would subtract 1 in the numerator); it
+ *    is kept as published.
+ *  - Sim3 product r = r1 r2, t = s1 (r1 t2) + t1, s = s1 s2; Eigen's matrix-to-quaternion, quaternion product and quaternion-times-vector.
+ *  - OptimizationAlgorithmLevenberg: lambda = 1e-5 max |H_jj| and ni = 2 at iteration 0 of EVERY optimize call; per trial solve (H + lambda I) x = b,
+ *    oplus, F' = the robustified chi2 of the live edges (DBL_MAX after a failed solve, with x = 0), rho = (F - F') / (x . (lambda x + b) + 1e-3);
+ *    rho > 0 and F' finite accepts: lambda *= max(1 / 3, min(1 - (2 rho - 1)^3, 2 / 3)), ni = 2; otherwise lambda *= ni, ni *= 2 and the estimate is
+ *    popped; trials repeat while rho < 0, ten at most; the call stops on the tenth trial or rho == 0.
+ *  - BlockSolverX over LinearSolverDense with one 7 x 7 block: H = sum J^T (w Omega) J, b = -sum J^T (w Omega) e, w = Huber's rho[1].  With bFixScale
+ *    column 6 of every J is exactly zero (both perturbed estimates are the same), so row and column 6 of H hold lambda alone and x[6] = 0.
+ *
+ * Normalisations:
+ *  1. The order of the sums over edges is this implementation's own: lane l of a 64-lane wavefront adds its correspondences l, l + 64, ... in order
+ *     (e12 before e21), then the xor butterfly 32, 16, 8, 4, 2, 1.  It is fixed, does not depend on what else is in the batch and is the same from
+ *     run to run: results are bit-identical between calls, batch orders and entry points.
+ *  2. An unpivoted 7 x 7 LDL^T in fp64 stands in for Eigen's pivoted one; a pivot that is not positive and finite is a failed solve.
+ *  3. (2 rho - 1)^3 is two products, not pow (as csrc/pose_opt.hip); exp, sin and cos are the device's.
+ *  4. Invalid inputs: a problem with a point, observation, information, intrinsic, th2 or Sim3 that is not finite, or with s12 <= 0, gets status -1
+ *     and its inlier bytes are all 0; the other problems of the call are not affected.
+ *  5. count == 0 returns 0 without optimising.  1 <= count < 10 still runs the first optimize and the first chi2 pass — the cleared entries are an
+ *     output — and then returns 0.
+ *
+ * Outputs: S12 [n_problems][13] double = R (row-major, r.toRotationMatrix()), t, s, written only where the reference writes g2oS12 (otherwise the
+ * caller's bytes stay); inliers [n_corr] uint8, 1 where vpMatches1[i] survives (a problem's bytes are always written; bytes no problem owns stay);
+ * status [n_problems][4] int32 = the return value (or -1, -2), nCorrespondences, nBad of the first pass, 256 * LM iterations + LM trials of both
+ * optimize calls together.  trace / trace_n: NULL, or [n_problems][OSLAM_SIM3_OPT_TRACE_ROWS][6] double and [n_problems] int32: per trial F before,
+ * F of the trial, rho, lambda of the trial, accepted, first trial of an optimize call (the fields of oslam_poseopt_trace) and the number of trials.
+ * Refusals: more problems or correspondences than the handle was created for: OSLAM_E_CAPACITY, before anything is launched.  A record that does not
+ * lie inside the n_corr correspondences: OSLAM_E_INVALID from the host entry point; the device entry point cannot read the records, there such a
+ * record gets status[0] = -2 and nothing else of it is written.  Problems of one call must not share correspondences.
+ * ---------------------------------------------------------------------------------------- */
+#define OSLAM_SIM3_OPT_TRACE_ROWS 150   /* (5 + 10) iterations of at most 10 trials */
+typedef struct oslam_sim3_opt oslam_sim3_opt_t;
+typedef struct oslam_sim3_opt_problem {
+    int32_t count, offset;   /* correspondences offset .. offset + count - 1 of the packed arrays */
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;   /* pKF1->mK, pKF2->mK */
+    float s12, R12[9], t12[3];   /* the Sim3 on entry */
+    float th2;
+    int32_t fix_scale;       /* bFixScale */
+} oslam_sim3_opt_problem_t;
+/* OSLAM_E_HIP without a device: there is no CPU fallback. */
+int oslam_sim3_opt_create(oslam_sim3_opt_t** out, int max_problems, int max_correspondences_total, int device);
+void oslam_sim3_opt_destroy(oslam_sim3_opt_t* h);
+/* Host pointers, staged through one pinned / device block pair: one upload, one launch, one download, synchronous.  X3Dc1, X3Dc2 [n_corr][3], obs1,
+ * obs2 [n_corr][2], invSigma2_1, invSigma2_2 [n_corr]; S12, inliers and status are read and written; trace and trace_n may both be NULL. */
+int oslam_optimize_sim3_batch(oslam_sim3_opt_t* h, int n_problems, const oslam_sim3_opt_problem_t* problems, int n_corr, const float* X3Dc1, const float* X3Dc2, const float* obs1,
+                              const float* obs2, const float* invSigma2_1, const float* invSigma2_2, double* S12, uint8_t* inliers, int32_t* status, double* trace,
+                              int32_t* trace_n);
+/* The same over device arrays (the problem records included), one launch, asynchronous on `stream`, no host synchronisation. */
+int oslam_optimize_sim3_batch_device(oslam_sim3_opt_t* h, int n_problems, const oslam_sim3_opt_problem_t* d_problems, int n_corr, const float* d_X3Dc1, const float* d_X3Dc2,
+                                     const float* d_obs1, const float* d_obs2, const float* d_invSigma2_1, const float* d_invSigma2_2, double* d_S12, uint8_t* d_inliers,
+                                     int32_t* d_status, double* d_trace, int32_t* d_trace_n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,3 +16,5 @@ from .sim3 import Sim3Solver  # noqa: F401
 from . import sim3  # noqa: F401
 from .sim3_match import Sim3Matcher  # noqa: F401
 from . import sim3_match  # noqa: F401
+from .sim3_opt import Sim3Optimizer  # noqa: F401
+from . import sim3_opt  # noqa: F401

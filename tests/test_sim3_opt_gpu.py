@@ -1,0 +1,267 @@
+"""GPU: OptimizeSim3 (include/oslam_hip.h, "OptimizeSim3") against the numpy restatement of tests/sim3_opt_common.py — status, surviving entries, whether
+S12 is written and the accept / reject sequence element for element, S12 within the project's optimiser bound — against hand-built known answers and the
+truth of generated problems; independence of the problems of a batch, both entry points, untouched rows, refusals, and the adapter's caller program."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import sim3_match_common as smc
+import sim3_opt_common as soc
+from object_slam_amd import sim3_opt   # (at import: every test of this file needs the operator's module)
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIBDIR = os.path.join(ROOT, "object_slam_amd")
+FILL_S, FILL_I, FILL_ST = -7.25, 0x5A, -77   # what the outputs hold before a call
+
+
+def _pack(problems, extra_rows=0):
+    """problem records and packed arrays; extra_rows rows that no problem owns follow the last problem"""
+    arrays, counts = soc.concat_batch(problems)
+    n = len(problems)
+    pr = sim3_opt.pack_problems(counts, [p["K1"] for p in problems], [p["K2"] for p in problems], [p["s12"] for p in problems], np.stack([p["R12"] for p in problems]).reshape(n, 3, 3),
+                                np.stack([p["t12"] for p in problems]).reshape(n, 3), [p["fix_scale"] for p in problems], [p["th2"] for p in problems])
+    if extra_rows:
+        arrays = {k: np.concatenate([v, np.ones((extra_rows,) + v.shape[1:], np.float32)]) for k, v in arrays.items()}
+    return pr, arrays
+
+
+def _call(opt, pr, arrays, device=False, trace=False):
+    M = len(arrays["invSigma2_1"])
+    return opt.optimize_batch(pr, arrays["X3Dc1"], arrays["X3Dc2"], arrays["obs1"], arrays["obs2"], arrays["invSigma2_1"], arrays["invSigma2_2"],
+                              S12=np.full((len(pr), 13), FILL_S, np.float64), inliers=np.full(M, FILL_I, np.uint8), status=np.full((len(pr), 4), FILL_ST, np.int32),
+                              trace=trace, device=device)
+
+
+def _split(pr, out):
+    """per problem: (status [4], inliers [count], S12 [13])"""
+    return [(out["status"][j].copy(), out["inliers"][o:o + max(n, 0)].copy(), out["S12"][j].copy()) for j, (o, n) in enumerate(zip(pr["offset"], pr["count"]))]
+
+
+def _run(opt, problems, device=False):
+    pr, arrays = _pack(problems)
+    return _split(pr, _call(opt, pr, arrays, device))
+
+
+def _same(a, b):
+    return len(a) == len(b) and all(np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1]) and x[2].tobytes() == y[2].tobytes() for x, y in zip(a, b))
+
+
+@pytest.fixture(scope="module")
+def opt():
+    o = sim3_opt.Sim3Optimizer(64, 8192)
+    yield o
+    o.close()
+
+
+@pytest.fixture(scope="module")
+def batch():
+    """the hand-built cases and the generated problems with 0, 1, 9, 10, 11, 63, 64, 65, 129, 300, 2400 and 100 (no outliers) correspondences"""
+    problems = soc.parity_problems()
+    return dict(problems=problems, ref=soc.reference_of(problems, "parity", "wavefront"), fwd=soc.reference_of(problems, "parity", "forward"),
+                rev=soc.reference_of(problems, "parity", "reversed"))
+
+
+@pytest.fixture(scope="module")
+def first(opt, batch):
+    pr, arrays = _pack(batch["problems"], extra_rows=5)
+    out = _call(opt, pr, arrays, trace=True)
+    return dict(pr=pr, out=out, res=_split(pr, out))
+
+
+def test_parity_with_the_restatement(batch, first):
+    """Status, surviving entries, whether S12 is written and the accept / reject sequence of the Levenberg-Marquardt trials equal those of the restatement
+    (summing in the kernel's order), no exclusions; S12 within 1e-4 relative to max(1, |.|), also against the restatement
+    summing forward.  Prints the largest differences beside the difference the restatement shows between the forward and the reversed edge order."""
+    bad, worst, reorder = [], 0.0, 0.0
+    worst_fwd = 0.0
+    for j, (p, r, fw, rv, (st, inl, S)) in enumerate(zip(batch["problems"], batch["ref"], batch["fwd"], batch["rev"], first["res"])):
+        n_tr = int(first["out"]["trace_n"][j])
+        acc = first["out"]["trace"][j, :n_tr, 4].tolist()
+        first_flags = first["out"]["trace"][j, :n_tr, 5].tolist()
+        written = S.tobytes() != np.full(13, FILL_S).tobytes()
+        d = float((np.abs(S - r["S12"]) / np.maximum(1.0, np.abs(r["S12"]))).max()) if written and r["written"] else 0.0
+        df = float((np.abs(S - fw["S12"]) / np.maximum(1.0, np.abs(fw["S12"]))).max()) if written and fw["written"] else 0.0
+        dr = float((np.abs(rv["S12"] - fw["S12"]) / np.maximum(1.0, np.abs(fw["S12"]))).max()) if fw["written"] else 0.0
+        worst, worst_fwd, reorder = max(worst, d), max(worst_fwd, df), max(reorder, dr)
+        print("%-20s n %4d ret %4d (restatement %4d) nBad %3d its %2d trials %3d  |dS12| %.2e, against the forward order %.2e (forward against reversed order on the CPU %.2e)"
+              % (p["name"], r["count"], st[0], r["ret"], st[2], st[3] >> 8, st[3] & 255, d, df, dr))
+        ok = (st.tolist() == [r["ret"], r["count"], r["nBad"], 256 * r["iterations"] + r["trials"]] and np.array_equal(inl, r["inliers"]) and written == r["written"]
+              and n_tr == r["trials"] and acc == [t[4] for t in r["trace"]] and first_flags == [t[5] for t in r["trace"]] and d <= 1e-4 and df <= 1e-4)
+        if not ok:
+            bad.append((p["name"], st.tolist(), r["ret"], r["nBad"], r["iterations"], r["trials"], written, r["written"], acc, [t[4] for t in r["trace"]], d))
+    print("largest |S12 - restatement| / max(1, |.|) = %.3g in the kernel's order, %.3g against the forward order; reorder noise of the restatement = %.3g" % (worst, worst_fwd, reorder))
+    assert not bad, bad
+    counts = [r["count"] for r in batch["ref"]]
+    assert {0, 1, 9, 10, 11, 63, 64, 65, 129, 300, 2400} <= set(counts)
+    more = {r["nBad"] > 0 for r in batch["ref"] if r["written"]}
+    assert more == {False, True} and {int(p["fix_scale"]) for p, r in zip(batch["problems"], batch["ref"]) if r["written"]} == {0, 1}
+
+
+def test_trace_costs_and_damping_match_the_restatement(batch, first):
+    """F before, F of the trial and lambda of every trial with the tolerances tests/test_poseopt_gpu.py applies to its trace (lm_trace.compare_lm_traces: F to
+    1e-7 relative + 1e-9, lambda to 1e-4 relative + 1e-12), against the restatement summing in the kernel's order.  Prints the largest differences, and
+    what the restatement itself shows between the forward and the reversed edge order: a trial whose update falls into the |sigma| >= eps, theta < eps
+    branch of the published exponential map has an F that no order-independent tolerance of this size can hold (sim3_opt_common.PARITY_SPECS)."""
+    worst = dict(F=0.0, lam=0.0, F_cpu=0.0, lam_cpu=0.0)
+    bad = []
+    rel = lambda a, b: abs(a - b) / abs(b) if b != 0 else abs(a - b)
+    for j, (p, r, fw, rv) in enumerate(zip(batch["problems"], batch["ref"], batch["fwd"], batch["rev"])):
+        n_tr = min(int(first["out"]["trace_n"][j]), r["trials"])
+        for k in range(n_tr):
+            h, o, o1, o2 = first["out"]["trace"][j, k], r["trace"][k], fw["trace"][k], rv["trace"][k]
+            worst["F"] = max(worst["F"], rel(h[0], o[0]), rel(h[1], o[1]))
+            worst["lam"] = max(worst["lam"], rel(h[3], o[3]))
+            worst["F_cpu"] = max(worst["F_cpu"], rel(o2[0], o1[0]), rel(o2[1], o1[1]))
+            worst["lam_cpu"] = max(worst["lam_cpu"], rel(o2[3], o1[3]))
+            if not (abs(h[3] - o[3]) <= 1e-4 * abs(o[3]) + 1e-12 and abs(h[0] - o[0]) <= 1e-7 * abs(o[0]) + 1e-9 and abs(h[1] - o[1]) <= 1e-7 * abs(o[1]) + 1e-9):
+                bad.append((p["name"], k, h[:4].tolist(), list(o[:4])))
+    print("largest relative difference of F %.3g and of lambda %.3g (forward against reversed order on the CPU: %.3g, %.3g); %d trials outside the tolerances"
+          % (worst["F"], worst["lam"], worst["F_cpu"], worst["lam_cpu"], len(bad)))
+    assert not bad, bad[:6]
+
+
+def test_hand_built_cases_give_their_known_answers(batch, first):
+    seen = 0
+    for p, (st, inl, S) in zip(batch["problems"], first["res"]):
+        if "expect" not in p:
+            continue
+        e = p["expect"]
+        seen += 1
+        assert st[0] == e["ret"] and st[1] == len(inl) and st[2] == e["nBad"] and inl.tolist() == list(e["inliers"]), p["name"]
+        if e["written"]:
+            assert np.abs(S - e["S12"]).max() <= 1e-12, p["name"]
+        else:
+            assert (S == FILL_S).all(), p["name"]
+    assert seen == 4
+
+
+def test_kernel_recovers_the_truth(batch, first):
+    """the bounds of test_sim3_opt_cpu.py::test_restatement_recovers_the_truth_of_generated_problems, on the two largest generated problems; every generated
+    problem loses exactly its gross outliers"""
+    checked = 0
+    for p, (st, inl, S) in zip(batch["problems"], first["res"]):
+        if "gross" not in p:
+            continue
+        assert np.array_equal(inl == 0, p["gross"]), p["name"]
+        if p["name"] in ("generated_7_129", "generated_10_2400"):
+            eR, et, es = soc.sim3_error(S, p["truth"])
+            assert st[0] == len(inl) - int(p["gross"].sum()) and eR < 2e-3 and et < 1.4e-2 and es < 5e-3, (p["name"], eR, et, es)
+            checked += 1
+    assert checked == 2
+
+
+def test_problems_are_independent(opt, batch, first):
+    problems = batch["problems"]
+    res = first["res"]
+    assert _same(_run(opt, problems[::-1])[::-1], res)
+    for j in range(len(problems)):
+        if len(problems[j]["invSigma2_1"]) <= 300:
+            assert _same(_run(opt, [problems[j]]), [res[j]]), problems[j]["name"]
+    assert _same(_run(opt, problems), res)
+
+
+def test_entry_points_agree_and_untouched_rows_keep_their_bytes(opt, batch, first):
+    pr, arrays = _pack(batch["problems"], extra_rows=5)
+    dev = _call(opt, pr, arrays, device=True, trace=True)
+    host = first["out"]
+    for k in ("S12", "inliers", "status", "trace_n"):
+        assert host[k].tobytes() == dev[k].tobytes(), k
+    for j, n in enumerate(host["trace_n"]):
+        assert host["trace"][j, :n].tobytes() == dev["trace"][j, :n].tobytes()
+    # the five rows no problem owns, and the S12 records of the problems that return before the reference writes g2oS12
+    assert (host["inliers"][-5:] == FILL_I).all() and len(host["inliers"]) == int(pr["count"].sum()) + 5
+    for r, (st, inl, S) in zip(batch["ref"], first["res"]):
+        assert (S == FILL_S).all() == (not r["written"])
+    assert any(not r["written"] for r in batch["ref"]) and any(r["written"] for r in batch["ref"])
+
+
+def test_refusals(opt, batch, first):
+    from object_slam_amd._lib import OSLAM_E_CAPACITY, OSLAM_E_INVALID, OslamError
+    names = ("generated_1_11", "generated_4_63", "generated_1_100")
+    idx = [[p["name"] for p in batch["problems"]].index(n) for n in names]
+    three = [batch["problems"][j] for j in idx]
+    want = [first["res"][j] for j in idx]
+    pr, arrays = _pack(three)
+    assert _same(_split(pr, _call(opt, pr, arrays)), want)
+    small = sim3_opt.Sim3Optimizer(2, 150)
+    try:
+        for what, recs, arr in (("three problems, two allowed", pr, arrays), ("174 correspondences, 150 allowed", pr[:2], arrays)):
+            for device in (False, True):
+                M = len(arr["invSigma2_1"])
+                S, inl, st = np.full((len(recs), 13), FILL_S), np.full(M, FILL_I, np.uint8), np.full((len(recs), 4), FILL_ST, np.int32)
+                with pytest.raises(OslamError) as ei:
+                    small.optimize_batch(recs, arr["X3Dc1"], arr["X3Dc2"], arr["obs1"], arr["obs2"], arr["invSigma2_1"], arr["invSigma2_2"], S12=S, inliers=inl, status=st, device=device)
+                assert ei.value.code == OSLAM_E_CAPACITY, what
+                assert (S == FILL_S).all() and (inl == FILL_I).all() and (st == FILL_ST).all(), what
+    finally:
+        small.close()
+    # a record that does not lie inside the arrays: refused by the host entry point, -2 and nothing else from the device entry point
+    M = len(arrays["invSigma2_1"])
+    for field, value in (("count", -1), ("offset", -1), ("offset", M - 62), ("count", M + 1)):
+        recs = pr.copy()
+        recs[field][1] = value
+        with pytest.raises(OslamError) as ei:
+            _call(opt, recs, arrays)
+        assert ei.value.code == OSLAM_E_INVALID, field
+        out = _call(opt, recs, arrays, device=True)
+        o, n = pr["offset"][1], pr["count"][1]
+        assert out["status"][1].tolist() == [-2, FILL_ST, FILL_ST, FILL_ST] and (out["inliers"][o:o + n] == FILL_I).all() and (out["S12"][1] == FILL_S).all(), (field, value)
+        got = _split(pr, out)
+        assert _same([got[0], got[2]], [want[0], want[2]]), field
+
+    # a value that is not finite, or a scale that is not positive, in one problem of three
+    def poison(rec_field=None, value=None, index=None, arr_field=None):
+        recs, arr = pr.copy(), {k: v.copy() for k, v in arrays.items()}
+        if rec_field:
+            if index is None:
+                recs[rec_field][1] = value
+            else:
+                recs[rec_field][1][index] = value
+        else:
+            arr[arr_field].reshape(len(arr[arr_field]), -1)[pr["offset"][1] + 40, -1] = value
+        return recs, arr
+    cases = [("s12 NaN", poison("s12", np.nan)), ("s12 inf", poison("s12", np.inf)), ("s12 0", poison("s12", 0.0)), ("s12 < 0", poison("s12", -1.0)),
+             ("R12 NaN", poison("R12", np.nan, (1, 2))), ("t12 -inf", poison("t12", -np.inf, 0)), ("fx2 NaN", poison("fx2", np.nan)), ("cy1 inf", poison("cy1", np.inf))]
+    cases += [(k + " " + str(v), poison(arr_field=k, value=v)) for k, v in (("X3Dc1", np.nan), ("X3Dc2", np.inf), ("obs1", -np.inf), ("obs2", np.nan), ("invSigma2_1", np.inf),
+                                                                            ("invSigma2_2", np.nan))]
+    for what, (recs, arr) in cases:
+        for device in (False, True):
+            got = _split(pr, _call(opt, recs, arr, device))
+            st, inl, S = got[1]
+            assert st[0] == -1 and (inl == 0).all() and len(inl) == 63 and (S == FILL_S).all(), what
+            assert _same([got[0], got[2]], [want[0], want[2]]), what
+
+
+def test_adapter_program_matches_the_restatement(tmp_path):
+    from object_slam_amd import build
+    build.build_hip()
+    d = str(tmp_path)
+    p = smc.make_pair(102, 300, 400, 1.1)
+    ref = soc.compute_sim3_step(p, 0)
+    for tag, kf, pose in (("1", p["kf1"], p["T1w"]), ("2", p["kf2"], p["T2w"])):
+        for name, a in dict(keys=kf["keysUn"], desc=kf["desc"], has_mp=kf["has_mp"], Xw=kf["Xw"], mp_desc=kf["mp_desc"], maxD=kf["maxDistance"], minD=kf["minDistance"],
+                            pose=pose).items():
+            np.ascontiguousarray(a).tofile(os.path.join(d, name + tag + ".bin"))
+    p["matched_in"].astype(np.int32).tofile(os.path.join(d, "matched.bin"))
+    np.concatenate([[p["s12"]], p["R12"].reshape(-1), p["t12"]]).astype(np.float32).tofile(os.path.join(d, "sim3.bin"))
+    smc.SF.tofile(os.path.join(d, "scale.bin"))
+    soc.INV_SIGMA2.tofile(os.path.join(d, "invsigma.bin"))
+    with open(os.path.join(d, "meta.txt"), "w") as f:
+        for k, v in dict(fx=smc.CAM[0], fy=smc.CAM[1], cx=smc.CAM[2], cy=smc.CAM[3], minX=smc.BOUNDS[0], minY=smc.BOUNDS[1], maxX=smc.BOUNDS[2], maxY=smc.BOUNDS[3],
+                         logScaleFactor=smc.LOG_SF, fixScale=0).items():
+            f.write("%s %r\n" % (k, float(v)))
+    prog = str(tmp_path / "prog")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "adapter_sim3_opt_program.cc"), "-o", prog,
+                           "-L", LIBDIR, "-loslam_hip", "-Wl,-rpath," + LIBDIR, "-Wl,-rpath-link,/opt/rocm/lib"])
+    r = subprocess.run([prog, d], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    lines = [l for l in r.stdout.split("\n") if l]
+    assert lines[:3] == ["nFound %d" % ref["nFound"], "nInliers %d" % ref["nInliers"], "bMatch 1"] and ref["nInliers"] > 100 and ref["result"]["written"]
+    after = np.array([int(l.split()[1]) for l in lines[3:-1]], np.int32)
+    assert np.array_equal(after, ref["vpMatches"])
+    assert lines[-1].startswith("S12 ")
+    S = np.array([float(v) for v in lines[-1].split()[1:]])
+    assert len(S) == 13 and (np.abs(S - ref["S12"]) / np.maximum(1.0, np.abs(ref["S12"]))).max() <= 1e-4
