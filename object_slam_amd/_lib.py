@@ -3,6 +3,7 @@
 There is no CPU fallback: if the library is missing or no HIP device is visible the product
 entry points raise.  Nothing here imports oracle/.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -58,3 +59,53 @@ def check(rc):
 def ptr(a):
     # ndarray.ctypes builds a helper object per call (~15 us); the array interface gives the address directly
     return C.c_void_p(a.__array_interface__["data"][0])
+
+
+def optptr(a):
+    return None if a is None else ptr(a)
+
+
+class Handle:
+    """One handle of the library: self.L, self.h (a c_void_p, NULL once closed) and the name of the function that destroys it."""
+
+    def __init__(self, L, prefix, *args):
+        """h = <prefix>_create(*args); close() calls <prefix>_destroy(h)."""
+        self.L, self.h, self._destroy = L, C.c_void_p(), prefix + "_destroy"
+        check(getattr(L, prefix + "_create")(C.byref(self.h), *args))
+
+    def close(self):
+        h = getattr(self, "h", None)   # (None: the constructor failed before it had a handle)
+        if h is not None and h.value:
+            getattr(self.L, self._destroy)(h)
+            h.value = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown: module globals may already be gone
+            pass
+
+
+def upload(a):
+    """A numpy array as a byte tensor on the current device; None stays None, and an empty array gets 8 bytes so that its address is not NULL."""
+    if a is None:
+        return None
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1) if a.size else np.zeros(8, np.uint8)).to(torch.device("cuda", torch.cuda.current_device()))
+
+
+@contextlib.contextmanager
+def device_call(arrays, outputs):
+    """The device=True path of a wrapper.  Uploads `arrays` (inputs and outputs alike) and yields (addr, stream) with a side stream current: addr(a) is the
+    device address of array a (None for None), stream the side stream's handle.  Afterwards waits for the side stream and copies `outputs`, which are among
+    `arrays`, back into the caller's arrays in place."""
+    import torch
+    t = {id(a): upload(a) for a in arrays if a is not None}
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        yield (lambda a: None if a is None else t[id(a)].data_ptr()), C.c_void_p(side.cuda_stream)
+    side.synchronize()
+    for a in outputs:
+        if a is not None and a.size:
+            a.reshape(-1).view(np.uint8)[:] = t[id(a)].cpu().numpy()[:a.nbytes]

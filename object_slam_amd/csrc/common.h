@@ -43,6 +43,11 @@ void lba_use_gate(struct ::oslam_lba* h, std::mutex* gate);
 void bow_use_stream(struct ::oslam_bow* h, hipStream_t s);
 void mappoint_use_stream(struct ::oslam_mappoint* h, hipStream_t s);
 
+static inline int no_device(const char* fn) {   // what every create function answers without a device
+    set_error("no HIP device visible: %s has no CPU fallback", fn);
+    return OSLAM_E_HIP;
+}
+
 static inline int div_up(int a, int b) { return (a + b - 1) / b; }
 
 // Device -> pinned-host transfer as a KERNEL on the caller's stream (the pinned block of hipHostMalloc is mapped into the device's address space: the stores go

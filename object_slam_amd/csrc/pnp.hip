@@ -11,6 +11,7 @@
 #include "common.h"
 #include "lane_ops.h"
 #include "ransac_draw.h"   // the counter-based generator and the draw rule, shared with sim3.hip
+#include "stage_layout.h"
 
 using oslam::set_error;
 
@@ -690,11 +691,6 @@ __global__ __launch_bounds__(kG) void k_pnp_epnp(const int32_t* counts, const in
     }
 }
 
-int no_device(const char* fn) {
-    set_error("no HIP device visible: %s has no CPU fallback", fn);
-    return OSLAM_E_HIP;
-}
-
 int check_params(const char* fn, const oslam_pnp_t* h, const oslam_pnp_params_t* p) {
     if (!p) { set_error("%s: params is NULL", fn); return OSLAM_E_INVALID; }
     if (p->min_set != 4) { set_error("%s: min_set = %d: only the minimal set of 4 is implemented", fn, p->min_set); return OSLAM_E_INVALID; }
@@ -737,7 +733,7 @@ int oslam_pnp_create(oslam_pnp_t** out, int max_problems, int max_correspondence
     if (!out) { set_error("oslam_pnp_create: out is NULL"); return OSLAM_E_INVALID; }
     *out = nullptr;
     if (max_problems < 1 || max_correspondences_total < 1 || max_iterations < 1 || max_problems > 65535 * 16) { set_error("oslam_pnp_create: bad argument"); return OSLAM_E_INVALID; }
-    if (oslam_device_count() <= 0) return no_device("oslam_pnp_create");
+    if (oslam_device_count() <= 0) return oslam::no_device("oslam_pnp_create");
     oslam_pnp* h = new oslam_pnp;
     h->max_problems = max_problems; h->max_corr = max_correspondences_total; h->max_iterations = max_iterations;
     const size_t hyp = (size_t)max_problems * max_iterations;
@@ -800,32 +796,30 @@ int oslam_pnp_ransac_batch(oslam_pnp_t* h, int n_problems, const oslam_pnp_probl
     }
     if (n_problems == 0) return OSLAM_OK;
     std::lock_guard<std::mutex> lock(h->mu);
-    using oslam::align_up;
     const size_t np = (size_t)n_problems, nc = (size_t)n_corr, its = (size_t)params->max_iterations;
-    // one upload: problems | P3Dw | P2D | sigma2 | samples;  one download: status | Tcw | inliers | iter_inliers
-    const size_t uProb = 0, uP3 = uProb + align_up(np * sizeof(oslam_pnp_problem_t), 256), uP2 = uP3 + align_up(nc * 12, 256), uSig = uP2 + align_up(nc * 8, 256),
-                 uSam = uSig + align_up(nc * 4, 256), uTotal = uSam + (samples ? align_up(np * its * 16, 256) : 0);
-    const size_t dSt = 0, dT = dSt + align_up(np * 16, 256), dIn = dT + align_up(np * 64, 256), dIt = dIn + align_up(nc, 256),
-                 dTotal = dIt + (iter_inliers ? align_up(np * its * 4, 256) : 0);
-    OSLAM_CHECK(h->up.grow(uTotal, 4096));
-    OSLAM_CHECK(h->down.grow(dTotal, 4096));
+    oslam::StageLayout up, down;   // one upload, one download
+    const auto uProb = up.add<oslam_pnp_problem_t>(np);
+    const auto uP3 = up.add<float>(nc * 3), uP2 = up.add<float>(nc * 2), uSig = up.add<float>(nc);
+    const auto uSam = up.add<int32_t>(np * its * 4, samples != nullptr);
+    const auto dSt = down.add<int32_t>(np * 4);
+    const auto dT = down.add<float>(np * 16);
+    const auto dIn = down.add<uint8_t>(nc);
+    const auto dIt = down.add<int32_t>(np * its, iter_inliers != nullptr);
+    OSLAM_CHECK(h->up.grow(up.total(), 4096));
+    OSLAM_CHECK(h->down.grow(down.total(), 4096));
     uint8_t *uh = h->up.h.bytes(), *ud = h->up.d.bytes(), *dh = h->down.h.bytes(), *dd = h->down.d.bytes();
-    memcpy(uh + uProb, problems, np * sizeof(oslam_pnp_problem_t));
-    if (nc) { memcpy(uh + uP3, P3Dw, nc * 12); memcpy(uh + uP2, P2D, nc * 8); memcpy(uh + uSig, sigma2, nc * 4); }
-    if (samples) memcpy(uh + uSam, samples, np * its * 16);
-    OSLAM_HIP_CHECK(hipMemcpyAsync(ud, uh, uTotal, hipMemcpyHostToDevice, nullptr));
-    if (iter_inliers) OSLAM_HIP_CHECK(hipMemsetAsync(dd + dIt, 0xff, np * its * 4, nullptr));   // -1 = not run
-    OSLAM_CHECK(oslam_pnp_ransac_batch_device(h, n_problems, (const oslam_pnp_problem_t*)(ud + uProb), n_corr, (const float*)(ud + uP3), (const float*)(ud + uP2),
-                                              (const float*)(ud + uSig), params, samples ? (const int32_t*)(ud + uSam) : nullptr, (float*)(dd + dT), dd + dIn,
-                                              (int32_t*)(dd + dSt), iter_inliers ? (int32_t*)(dd + dIt) : nullptr, nullptr));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(dh, dd, dTotal, hipMemcpyDeviceToHost, nullptr));
+    put(uProb, uh, problems); put(uP3, uh, P3Dw); put(uP2, uh, P2D); put(uSig, uh, sigma2); put(uSam, uh, samples);
+    OSLAM_HIP_CHECK(hipMemcpyAsync(ud, uh, up.total(), hipMemcpyHostToDevice, nullptr));
+    if (iter_inliers) OSLAM_HIP_CHECK(hipMemsetAsync(at(dIt, dd), 0xff, dIt.bytes, nullptr));   // -1 = not run
+    OSLAM_CHECK(oslam_pnp_ransac_batch_device(h, n_problems, at(uProb, ud), n_corr, at(uP3, ud), at(uP2, ud), at(uSig, ud), params, at(uSam, ud), at(dT, dd), at(dIn, dd),
+                                              at(dSt, dd), at(dIt, dd), nullptr));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(dh, dd, down.total(), hipMemcpyDeviceToHost, nullptr));
     OSLAM_HIP_CHECK(hipStreamSynchronize(nullptr));
-    memcpy(status, dh + dSt, np * 16);
-    if (iter_inliers) memcpy(iter_inliers, dh + dIt, np * its * 4);
+    get(dSt, dh, status); get(dIt, dh, iter_inliers);
     for (int b = 0; b < n_problems; b++) {   // a problem without a pose keeps the caller's Tcw and inlier bytes
         if (status[4 * b] <= 0) continue;
-        memcpy(Tcw + 16 * (size_t)b, dh + dT + 64 * (size_t)b, 64);
-        memcpy(inliers + problems[b].offset, dh + dIn + problems[b].offset, (size_t)problems[b].count);
+        memcpy(Tcw + 16 * (size_t)b, at(dT, dh) + 16 * (size_t)b, 16 * sizeof(float));
+        memcpy(inliers + problems[b].offset, at(dIn, dh) + problems[b].offset, (size_t)problems[b].count);
     }
     return OSLAM_OK;
 }
@@ -847,21 +841,22 @@ int oslam_pnp_epnp(oslam_pnp_t* h, int n_sets, const int32_t* counts, const int3
         }
     if (n_sets == 0) return OSLAM_OK;
     std::lock_guard<std::mutex> lock(h->mu);
-    using oslam::align_up;
     const size_t ns = (size_t)n_sets, nc = (size_t)n_corr;
-    const size_t uCnt = 0, uOff = uCnt + align_up(ns * 4, 256), uP3 = uOff + align_up(ns * 4, 256), uP2 = uP3 + align_up(nc * 12, 256), uTotal = uP2 + align_up(nc * 8, 256);
-    const size_t dR = 0, dT = dR + align_up(ns * 72, 256), dE = dT + align_up(ns * 24, 256), dTotal = dE + align_up(ns * 8, 256);
-    OSLAM_CHECK(h->up.grow(uTotal, 4096));
-    OSLAM_CHECK(h->down.grow(dTotal, 4096));
+    oslam::StageLayout up, down;
+    const auto uCnt = up.add<int32_t>(ns), uOff = up.add<int32_t>(ns);
+    const auto uP3 = up.add<float>(nc * 3), uP2 = up.add<float>(nc * 2);
+    const auto dR = down.add<double>(ns * 9), dT = down.add<double>(ns * 3), dE = down.add<double>(ns);
+    OSLAM_CHECK(h->up.grow(up.total(), 4096));
+    OSLAM_CHECK(h->down.grow(down.total(), 4096));
     uint8_t *uh = h->up.h.bytes(), *ud = h->up.d.bytes(), *dh = h->down.h.bytes(), *dd = h->down.d.bytes();
-    memcpy(uh + uCnt, counts, ns * 4); memcpy(uh + uOff, offsets, ns * 4); memcpy(uh + uP3, P3Dw, nc * 12); memcpy(uh + uP2, P2D, nc * 8);
-    OSLAM_HIP_CHECK(hipMemcpyAsync(ud, uh, uTotal, hipMemcpyHostToDevice, nullptr));
-    hipLaunchKernelGGL(k_pnp_epnp, dim3(n_sets), dim3(kG), 0, nullptr, (const int32_t*)(ud + uCnt), (const int32_t*)(ud + uOff), (const float*)(ud + uP3), (const float*)(ud + uP2),
-                       (double)K4[0], (double)K4[1], (double)K4[2], (double)K4[3], (double*)(dd + dR), (double*)(dd + dT), (double*)(dd + dE));
+    put(uCnt, uh, counts); put(uOff, uh, offsets); put(uP3, uh, P3Dw); put(uP2, uh, P2D);
+    OSLAM_HIP_CHECK(hipMemcpyAsync(ud, uh, up.total(), hipMemcpyHostToDevice, nullptr));
+    hipLaunchKernelGGL(k_pnp_epnp, dim3(n_sets), dim3(kG), 0, nullptr, at(uCnt, ud), at(uOff, ud), at(uP3, ud), at(uP2, ud), (double)K4[0], (double)K4[1], (double)K4[2],
+                       (double)K4[3], at(dR, dd), at(dT, dd), at(dE, dd));
     OSLAM_HIP_CHECK(hipGetLastError());
-    OSLAM_HIP_CHECK(hipMemcpyAsync(dh, dd, dTotal, hipMemcpyDeviceToHost, nullptr));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(dh, dd, down.total(), hipMemcpyDeviceToHost, nullptr));
     OSLAM_HIP_CHECK(hipStreamSynchronize(nullptr));
-    memcpy(R, dh + dR, ns * 72); memcpy(t, dh + dT, ns * 24); memcpy(err, dh + dE, ns * 8);
+    get(dR, dh, R); get(dT, dh, t); get(dE, dh, err);
     return OSLAM_OK;
 }
 

@@ -11,6 +11,7 @@
 #include "common.h"
 #include "lane_ops.h"
 #include "ransac_draw.h"
+#include "stage_layout.h"
 
 using oslam::set_error;
 
@@ -373,11 +374,6 @@ __global__ __launch_bounds__(kG* kPerBlock) void k_sim3_select(Sim3Args a) {
     }
 }
 
-int no_device(const char* fn) {
-    set_error("no HIP device visible: %s has no CPU fallback", fn);
-    return OSLAM_E_HIP;
-}
-
 int check_call(const char* fn, const oslam_sim3_t* h, const oslam_sim3_params_t* p, int n_problems, int n_corr, int n_iterations) {
     if (!p) { set_error("%s: params is NULL", fn); return OSLAM_E_INVALID; }
     if (p->min_inliers < 0 || n_iterations < 0) { set_error("%s: min_inliers = %d, n_iterations = %d: neither may be negative", fn, p->min_inliers, n_iterations); return OSLAM_E_INVALID; }
@@ -424,7 +420,7 @@ int oslam_sim3_create(oslam_sim3_t** out, int max_problems, int max_corresponden
         set_error("oslam_sim3_create: bad argument");
         return OSLAM_E_INVALID;
     }
-    if (oslam_device_count() <= 0) return no_device("oslam_sim3_create");
+    if (oslam_device_count() <= 0) return oslam::no_device("oslam_sim3_create");
     oslam_sim3* h = new oslam_sim3;
     h->max_problems = max_problems; h->max_corr = max_correspondences_total; h->max_iterations = max_iterations;
     const size_t hyp = (size_t)max_problems * max_iterations;
@@ -481,37 +477,36 @@ int oslam_sim3_iterate_batch(oslam_sim3_t* h, int n_problems, const oslam_sim3_p
     }
     if (n_problems == 0) return OSLAM_OK;
     std::lock_guard<std::mutex> lock(h->mu);
-    using oslam::align_up;
     const size_t np = (size_t)n_problems, nc = (size_t)n_corr, its = (size_t)params->max_iterations;
-    // one block: problems | X3Dc1 | X3Dc2 | sigma2_1 | sigma2_2 | samples | states | status | T12 | inliers | iter_inliers | hypotheses.
-    // One upload of everything up to and including the states, one download of everything from the states on.
-    const size_t oProb = 0, oX1 = oProb + align_up(np * sizeof(oslam_sim3_problem_t), 256), oX2 = oX1 + align_up(nc * 12, 256), oS1 = oX2 + align_up(nc * 12, 256),
-                 oS2 = oS1 + align_up(nc * 4, 256), oSam = oS2 + align_up(nc * 4, 256), oState = oSam + (samples ? align_up(np * its * 12, 256) : 0),
-                 oSt = oState + align_up(np * sizeof(oslam_sim3_state_t), 256), oT = oSt + align_up(np * 16, 256), oIn = oT + align_up(np * 64, 256),
-                 oIt = oIn + align_up(nc, 256), oHy = oIt + (iter_inliers ? align_up(np * its * 4, 256) : 0), total = oHy + (hypotheses ? align_up(np * its * 52, 256) : 0);
-    OSLAM_CHECK(h->io.grow(total, 4096));
+    // one block.  One upload of everything up to and including the states, one download of everything from the states on.
+    oslam::StageLayout lay;
+    const auto fProb = lay.add<oslam_sim3_problem_t>(np);
+    const auto fX1 = lay.add<float>(nc * 3), fX2 = lay.add<float>(nc * 3), fS1 = lay.add<float>(nc), fS2 = lay.add<float>(nc);
+    const auto fSam = lay.add<int32_t>(np * its * 3, samples != nullptr);
+    const auto fState = lay.add<oslam_sim3_state_t>(np);
+    const auto fSt = lay.add<int32_t>(np * 4);
+    const auto fT = lay.add<float>(np * 16);
+    const auto fIn = lay.add<uint8_t>(nc);
+    const auto fIt = lay.add<int32_t>(np * its, iter_inliers != nullptr);
+    const auto fHy = lay.add<float>(np * its * 13, hypotheses != nullptr);
+    OSLAM_CHECK(h->io.grow(lay.total(), 4096));
     uint8_t *ph = h->io.h.bytes(), *pd = h->io.d.bytes();
-    memcpy(ph + oProb, problems, np * sizeof(oslam_sim3_problem_t));
-    if (nc) { memcpy(ph + oX1, X3Dc1, nc * 12); memcpy(ph + oX2, X3Dc2, nc * 12); memcpy(ph + oS1, sigma2_1, nc * 4); memcpy(ph + oS2, sigma2_2, nc * 4); }
-    if (samples) memcpy(ph + oSam, samples, np * its * 12);
-    memcpy(ph + oState, states, np * sizeof(oslam_sim3_state_t));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(pd, ph, oSt, hipMemcpyHostToDevice, nullptr));
-    OSLAM_CHECK(oslam_sim3_iterate_batch_device(h, n_problems, (const oslam_sim3_problem_t*)(pd + oProb), (oslam_sim3_state_t*)(pd + oState), n_corr, (const float*)(pd + oX1),
-                                                (const float*)(pd + oX2), (const float*)(pd + oS1), (const float*)(pd + oS2), params, n_iterations,
-                                                samples ? (const int32_t*)(pd + oSam) : nullptr, (float*)(pd + oT), pd + oIn, (int32_t*)(pd + oSt),
-                                                iter_inliers ? (int32_t*)(pd + oIt) : nullptr, hypotheses ? (float*)(pd + oHy) : nullptr, nullptr));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(ph + oState, pd + oState, total - oState, hipMemcpyDeviceToHost, nullptr));
+    put(fProb, ph, problems); put(fX1, ph, X3Dc1); put(fX2, ph, X3Dc2); put(fS1, ph, sigma2_1); put(fS2, ph, sigma2_2); put(fSam, ph, samples); put(fState, ph, states);
+    OSLAM_HIP_CHECK(hipMemcpyAsync(pd, ph, fSt.off, hipMemcpyHostToDevice, nullptr));
+    OSLAM_CHECK(oslam_sim3_iterate_batch_device(h, n_problems, at(fProb, pd), at(fState, pd), n_corr, at(fX1, pd), at(fX2, pd), at(fS1, pd), at(fS2, pd), params, n_iterations,
+                                                at(fSam, pd), at(fT, pd), at(fIn, pd), at(fSt, pd), at(fIt, pd), at(fHy, pd), nullptr));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(ph + fState.off, pd + fState.off, lay.total() - fState.off, hipMemcpyDeviceToHost, nullptr));
     OSLAM_HIP_CHECK(hipStreamSynchronize(nullptr));
-    memcpy(status, ph + oSt, np * 16);
+    get(fSt, ph, status);
     for (int b = 0; b < n_problems; b++) {
-        const int it0 = states[b].iterations_done, ran = status[4 * b + 2];   // (the caller's record still holds the state before the call)
-        if (iter_inliers && ran > 0) memcpy(iter_inliers + (size_t)b * its + it0, ph + oIt + ((size_t)b * its + it0) * 4, (size_t)ran * 4);
-        if (hypotheses && ran > 0) memcpy(hypotheses + ((size_t)b * its + it0) * 13, ph + oHy + ((size_t)b * its + it0) * 52, (size_t)ran * 52);
+        const size_t row = (size_t)b * its + states[b].iterations_done, ran = (size_t)std::max(status[4 * b + 2], 0);   // (the caller's record still holds the state before the call)
+        if (iter_inliers && ran) memcpy(iter_inliers + row, at(fIt, ph) + row, ran * sizeof(int32_t));
+        if (hypotheses && ran) memcpy(hypotheses + row * 13, at(fHy, ph) + row * 13, ran * 13 * sizeof(float));
         if (status[4 * b] <= 0) continue;   // a problem without a Sim3 keeps the caller's T12 and inlier bytes
-        memcpy(T12 + 16 * (size_t)b, ph + oT + 64 * (size_t)b, 64);
-        memcpy(inliers + problems[b].offset, ph + oIn + problems[b].offset, (size_t)problems[b].count);
+        memcpy(T12 + 16 * (size_t)b, at(fT, ph) + 16 * (size_t)b, 16 * sizeof(float));
+        memcpy(inliers + problems[b].offset, at(fIn, ph) + problems[b].offset, (size_t)problems[b].count);
     }
-    memcpy(states, ph + oState, np * sizeof(oslam_sim3_state_t));
+    get(fState, ph, states);
     return OSLAM_OK;
 }
 

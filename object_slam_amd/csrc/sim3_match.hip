@@ -9,6 +9,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "stage_layout.h"
 
 using oslam::set_error;
 
@@ -294,7 +295,7 @@ int oslam_sim3_match_create(oslam_sim3_match_t** out, int max_pairs, int max_key
         return OSLAM_E_INVALID;
     }
     const int ndev = oslam_device_count();
-    if (ndev <= 0) { set_error("no HIP device visible: oslam_sim3_match_create has no CPU fallback"); return OSLAM_E_HIP; }
+    if (ndev <= 0) return oslam::no_device("oslam_sim3_match_create");
     if (device < 0 || device >= ndev) { set_error("oslam_sim3_match_create: device out of range"); return OSLAM_E_INVALID; }
     OSLAM_HIP_CHECK(hipSetDevice(device));
     oslam_sim3_match* h = new oslam_sim3_match;
@@ -352,35 +353,31 @@ int oslam_match_search_by_sim3_batch(oslam_sim3_match_t* h, int n_pairs, const o
     }
     std::lock_guard<std::mutex> lock(h->mu);
     OSLAM_HIP_CHECK(hipSetDevice(h->device));
-    using oslam::align_up;
     const size_t np = (size_t)n_pairs, R = (size_t)nr, NO = (size_t)n_out;
-    // one block: pairs | keysUn | desc | has_mp | Xw | mp_desc | maxDistance | minDistance | matched_in || match12 | n_found: one upload, one download
-    const size_t oPair = 0, oKeys = oPair + align_up(np * sizeof(oslam_sim3_pair_t), 256), oDesc = oKeys + align_up(R * sizeof(oslam_keypoint_t), 256),
-                 oHas = oDesc + align_up(R * 32, 256), oXw = oHas + align_up(R, 256), oMpd = oXw + align_up(R * 12, 256), oMax = oMpd + align_up(R * 32, 256),
-                 oMin = oMax + align_up(R * 4, 256), oIn = oMin + align_up(R * 4, 256), oOut = oIn + (matched_in ? align_up(NO * 4, 256) : 0),
-                 oNf = oOut + align_up(NO * 4, 256), total = oNf + align_up(np * 4, 256);
-    OSLAM_CHECK(h->io.grow(total, 4096));
+    oslam::StageLayout lay;   // one block, inputs then outputs: one upload, one download
+    const auto fPair = lay.add<oslam_sim3_pair_t>(np);
+    const auto fKeys = lay.add<oslam_keypoint_t>(R);
+    const auto fDesc = lay.add<uint8_t>(R * 32), fHas = lay.add<uint8_t>(R);
+    const auto fXw = lay.add<float>(R * 3);
+    const auto fMpd = lay.add<uint8_t>(R * 32);
+    const auto fMax = lay.add<float>(R), fMin = lay.add<float>(R);
+    const auto fIn = lay.add<int32_t>(NO, matched_in != nullptr);
+    const auto fOut = lay.add<int32_t>(NO), fNf = lay.add<int32_t>(np);
+    OSLAM_CHECK(h->io.grow(lay.total(), 4096));
     uint8_t *ph = h->io.h.bytes(), *pd = h->io.d.bytes();
-    memcpy(ph + oPair, pairs, np * sizeof(oslam_sim3_pair_t));
-    if (R) {
-        memcpy(ph + oKeys, rows->keysUn, R * sizeof(oslam_keypoint_t)); memcpy(ph + oDesc, rows->desc, R * 32); memcpy(ph + oHas, rows->has_mp, R);
-        memcpy(ph + oXw, rows->Xw, R * 12); memcpy(ph + oMpd, rows->mp_desc, R * 32); memcpy(ph + oMax, rows->maxDistance, R * 4);
-        memcpy(ph + oMin, rows->minDistance, R * 4);
-    }
-    if (matched_in && NO) memcpy(ph + oIn, matched_in, NO * 4);
+    put(fPair, ph, pairs); put(fKeys, ph, rows->keysUn); put(fDesc, ph, rows->desc); put(fHas, ph, rows->has_mp); put(fXw, ph, rows->Xw); put(fMpd, ph, rows->mp_desc);
+    put(fMax, ph, rows->maxDistance); put(fMin, ph, rows->minDistance); put(fIn, ph, matched_in);
     // the caller's output rows travel too: rows no pair owns, and those of a pair the kernel leaves alone, come back as they were
-    if (NO) memcpy(ph + oOut, match12, NO * 4);
-    memcpy(ph + oNf, n_found, np * 4);
-    OSLAM_HIP_CHECK(hipMemcpyAsync(pd, ph, total, hipMemcpyHostToDevice, nullptr));
+    put(fOut, ph, match12); put(fNf, ph, n_found);
+    OSLAM_HIP_CHECK(hipMemcpyAsync(pd, ph, lay.total(), hipMemcpyHostToDevice, nullptr));
     oslam_sim3_match_rows_t d;
-    d.n_rows = nr; d.keysUn = (const oslam_keypoint_t*)(pd + oKeys); d.desc = pd + oDesc; d.has_mp = pd + oHas; d.Xw = (const float*)(pd + oXw); d.mp_desc = pd + oMpd;
-    d.maxDistance = (const float*)(pd + oMax); d.minDistance = (const float*)(pd + oMin);
-    OSLAM_CHECK(oslam_match_search_by_sim3_batch_device(h, n_pairs, (const oslam_sim3_pair_t*)(pd + oPair), &d, n_out, matched_in ? (const int32_t*)(pd + oIn) : nullptr, cam,
-                                                        bounds, scaleFactors, nlevels, logScaleFactor, (int32_t*)(pd + oOut), (int32_t*)(pd + oNf), nullptr));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(ph + oOut, pd + oOut, total - oOut, hipMemcpyDeviceToHost, nullptr));
+    d.n_rows = nr; d.keysUn = at(fKeys, pd); d.desc = at(fDesc, pd); d.has_mp = at(fHas, pd); d.Xw = at(fXw, pd); d.mp_desc = at(fMpd, pd);
+    d.maxDistance = at(fMax, pd); d.minDistance = at(fMin, pd);
+    OSLAM_CHECK(oslam_match_search_by_sim3_batch_device(h, n_pairs, at(fPair, pd), &d, n_out, at(fIn, pd), cam, bounds, scaleFactors, nlevels, logScaleFactor, at(fOut, pd),
+                                                        at(fNf, pd), nullptr));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(ph + fOut.off, pd + fOut.off, lay.total() - fOut.off, hipMemcpyDeviceToHost, nullptr));
     OSLAM_HIP_CHECK(hipStreamSynchronize(nullptr));
-    if (NO) memcpy(match12, ph + oOut, NO * 4);
-    memcpy(n_found, ph + oNf, np * 4);
+    get(fOut, ph, match12); get(fNf, ph, n_found);
     return OSLAM_OK;
 }
 

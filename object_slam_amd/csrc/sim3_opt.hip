@@ -12,6 +12,7 @@
 #include "common.h"
 #include "lane_ops.h"
 #include "se3_math.h"
+#include "stage_layout.h"
 
 using oslam::set_error;
 
@@ -507,7 +508,7 @@ int oslam_sim3_opt_create(oslam_sim3_opt_t** out, int max_problems, int max_corr
     *out = nullptr;
     if (max_problems < 1 || max_correspondences_total < 1) { set_error("oslam_sim3_opt_create: bad argument"); return OSLAM_E_INVALID; }
     const int ndev = oslam_device_count();
-    if (ndev <= 0) { set_error("no HIP device visible: oslam_sim3_opt_create has no CPU fallback"); return OSLAM_E_HIP; }
+    if (ndev <= 0) return oslam::no_device("oslam_sim3_opt_create");
     if (device < 0 || device >= ndev) { set_error("oslam_sim3_opt_create: device out of range"); return OSLAM_E_INVALID; }
     oslam_sim3_opt* h = new oslam_sim3_opt;
     h->device = device; h->max_problems = max_problems; h->max_corr = max_correspondences_total;
@@ -555,34 +556,27 @@ int oslam_optimize_sim3_batch(oslam_sim3_opt_t* h, int n_problems, const oslam_s
     }
     std::lock_guard<std::mutex> lock(h->mu);
     OSLAM_HIP_CHECK(hipSetDevice(h->device));
-    using oslam::align_up;
     const size_t np = (size_t)n_problems, M = (size_t)n_corr;
-    // one block: problems | X3Dc1 | X3Dc2 | obs1 | obs2 | invSigma2_1 | invSigma2_2 || S12 | inliers | status | trace_n | trace: one upload, one download
-    const size_t oPr = 0, oX1 = oPr + align_up(np * sizeof(oslam_sim3_opt_problem_t), 256), oX2 = oX1 + align_up(M * 12, 256), oO1 = oX2 + align_up(M * 12, 256),
-                 oO2 = oO1 + align_up(M * 8, 256), oI1 = oO2 + align_up(M * 8, 256), oI2 = oI1 + align_up(M * 4, 256), oS = oI2 + align_up(M * 4, 256),
-                 oIn = oS + align_up(np * 13 * 8, 256), oSt = oIn + align_up(M, 256), oTn = oSt + align_up(np * 16, 256), oTr = oTn + align_up(np * 4, 256),
-                 nTr = trace ? np * kTraceRows * 6 * 8 : 0, total = oTr + align_up(nTr, 256);
-    OSLAM_CHECK(h->io.grow(total, 4096));
+    oslam::StageLayout lay;   // one block, inputs then outputs: one upload, one download
+    const auto fPr = lay.add<oslam_sim3_opt_problem_t>(np);
+    const auto fX1 = lay.add<float>(M * 3), fX2 = lay.add<float>(M * 3), fO1 = lay.add<float>(M * 2), fO2 = lay.add<float>(M * 2), fI1 = lay.add<float>(M), fI2 = lay.add<float>(M);
+    const auto fS = lay.add<double>(np * 13);
+    const auto fIn = lay.add<uint8_t>(M);
+    const auto fSt = lay.add<int32_t>(np * 4), fTn = lay.add<int32_t>(np);   // (trace_n has its room with or without a trace)
+    const auto fTr = lay.add<double>(np * kTraceRows * 6, trace != nullptr);
+    OSLAM_CHECK(h->io.grow(lay.total(), 4096));
     uint8_t *ph = h->io.h.bytes(), *pd = h->io.d.bytes();
-    memcpy(ph + oPr, problems, np * sizeof(oslam_sim3_opt_problem_t));
-    if (M) {
-        memcpy(ph + oX1, X3Dc1, M * 12); memcpy(ph + oX2, X3Dc2, M * 12); memcpy(ph + oO1, obs1, M * 8); memcpy(ph + oO2, obs2, M * 8);
-        memcpy(ph + oI1, invSigma2_1, M * 4); memcpy(ph + oI2, invSigma2_2, M * 4);
-        memcpy(ph + oIn, inliers, M);   // the caller's output bytes travel too: what no problem owns, or the kernel leaves alone, comes back as it was
-    }
-    memcpy(ph + oS, S12, np * 13 * 8);
-    memcpy(ph + oSt, status, np * 16);
-    if (trace) { memcpy(ph + oTn, trace_n, np * 4); memcpy(ph + oTr, trace, nTr); }
-    OSLAM_HIP_CHECK(hipMemcpyAsync(pd, ph, total, hipMemcpyHostToDevice, nullptr));
-    OSLAM_CHECK(oslam_optimize_sim3_batch_device(h, n_problems, (const oslam_sim3_opt_problem_t*)(pd + oPr), n_corr, (const float*)(pd + oX1), (const float*)(pd + oX2),
-                                                 (const float*)(pd + oO1), (const float*)(pd + oO2), (const float*)(pd + oI1), (const float*)(pd + oI2), (double*)(pd + oS),
-                                                 pd + oIn, (int32_t*)(pd + oSt), trace ? (double*)(pd + oTr) : nullptr, trace ? (int32_t*)(pd + oTn) : nullptr, nullptr));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(ph + oS, pd + oS, total - oS, hipMemcpyDeviceToHost, nullptr));
+    put(fPr, ph, problems); put(fX1, ph, X3Dc1); put(fX2, ph, X3Dc2); put(fO1, ph, obs1); put(fO2, ph, obs2); put(fI1, ph, invSigma2_1); put(fI2, ph, invSigma2_2);
+    // the caller's output bytes travel too: what no problem owns, or the kernel leaves alone, comes back as it was
+    put(fS, ph, S12); put(fIn, ph, inliers); put(fSt, ph, status);
+    if (trace) { put(fTn, ph, trace_n); put(fTr, ph, trace); }
+    OSLAM_HIP_CHECK(hipMemcpyAsync(pd, ph, lay.total(), hipMemcpyHostToDevice, nullptr));
+    OSLAM_CHECK(oslam_optimize_sim3_batch_device(h, n_problems, at(fPr, pd), n_corr, at(fX1, pd), at(fX2, pd), at(fO1, pd), at(fO2, pd), at(fI1, pd), at(fI2, pd), at(fS, pd),
+                                                 at(fIn, pd), at(fSt, pd), at(fTr, pd), trace ? at(fTn, pd) : nullptr, nullptr));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(ph + fS.off, pd + fS.off, lay.total() - fS.off, hipMemcpyDeviceToHost, nullptr));
     OSLAM_HIP_CHECK(hipStreamSynchronize(nullptr));
-    memcpy(S12, ph + oS, np * 13 * 8);
-    if (M) memcpy(inliers, ph + oIn, M);
-    memcpy(status, ph + oSt, np * 16);
-    if (trace) { memcpy(trace_n, ph + oTn, np * 4); memcpy(trace, ph + oTr, nTr); }
+    get(fS, ph, S12); get(fIn, ph, inliers); get(fSt, ph, status);
+    if (trace) { get(fTn, ph, trace_n); get(fTr, ph, trace); }
     return OSLAM_OK;
 }
 

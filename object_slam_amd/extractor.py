@@ -20,23 +20,13 @@ class OrbPlan(C.Structure):
                 ("skipped_cells", C.c_int32 * MAX_LEVELS)]
 
 
-class ORBextractor:
+class ORBextractor(_lib.Handle):
     def __init__(self, nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height,
                  max_batch=1, device=0):
-        self.L = _lib.lib()
-        self.h = C.c_void_p()
-        check(self.L.oslam_orb_create(C.byref(self.h), nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST,
-                                      width, height, max_batch, device))
+        super().__init__(_lib.lib(), "oslam_orb", nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height, max_batch, device)
         self.nfeatures, self.nlevels = nfeatures, nlevels
         self.width, self.height, self.max_batch = width, height, max_batch
         self.cap = self.L.oslam_orb_max_keypoints(self.h)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.oslam_orb_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     # --- getters, reference include/ORBextractor.h:63-83 ---
     def _tables(self):

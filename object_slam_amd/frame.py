@@ -8,18 +8,9 @@ from . import _lib
 from ._lib import KP_DTYPE, check, ptr
 
 
-class FrameOps:
+class FrameOps(_lib.Handle):
     def __init__(self, device=0):
-        self.L = _lib.lib()
-        self.h = C.c_void_p()
-        check(self.L.oslam_frame_create(C.byref(self.h), device))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.oslam_frame_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+        super().__init__(_lib.lib(), "oslam_frame", device)
 
     @staticmethod
     def _kd(K4, dist):

@@ -22,18 +22,9 @@ def _csr(lists, width, dtype):
     return start, flat
 
 
-class MapPointBatch:
+class MapPointBatch(_lib.Handle):
     def __init__(self, device=0):
-        self.L = _lib.lib()
-        self.h = C.c_void_p()
-        check(self.L.oslam_mappoint_create(C.byref(self.h), device))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.oslam_mappoint_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+        super().__init__(_lib.lib(), "oslam_mappoint", device)
 
     def ComputeDistinctiveDescriptors(self, obs_desc_lists):
         """obs_desc_lists[p] = [n_p][32] descriptors of point p's observations, in the reference's map order.

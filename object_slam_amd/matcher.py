@@ -28,22 +28,13 @@ class MatchLast(C.Structure):
                 ("kp_stride", C.c_int), ("n_kps", C.c_void_p), ("n_kps_const", C.c_int)]
 
 
-class ORBmatcher:
+class ORBmatcher(_lib.Handle):
     TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30   # reference src/ORBmatcher.cc:37-39
 
     def __init__(self, nnratio=0.6, checkOri=True, max_keypoints=2400, max_queries=4096, max_batch=1, device=0):
-        self.L = _lib.lib()
-        self.h = C.c_void_p()
-        check(self.L.oslam_matcher_create(C.byref(self.h), max_batch, max_keypoints, max_queries, device))
+        super().__init__(_lib.lib(), "oslam_matcher", max_batch, max_keypoints, max_queries, device)
         self.mfNNratio, self.mbCheckOrientation = float(nnratio), bool(checkOri)
         self.max_kps, self.max_q, self.max_batch = max_keypoints, max_queries, max_batch
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.oslam_matcher_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     # SearchByProjection(Frame&, const vector<MapPoint*>&, th): src/ORBmatcher.cc:45
     # (use_ratio=True); generic windowed search otherwise.
@@ -133,20 +124,11 @@ class ORBmatcher:
         return nm.value, qm[:n_q], qd[:n_q], km[:n_kps], it.value
 
 
-class StereoMatcher:
+class StereoMatcher(_lib.Handle):
     """Frame::ComputeStereoMatches (reference src/Frame.cc:706-880) on two ORBextractor handles."""
 
     def __init__(self, max_keypoints=2400, max_batch=1, device=0):
-        self.L = _lib.lib()
-        self.h = C.c_void_p()
-        check(self.L.oslam_stereo_create(C.byref(self.h), max_batch, max_keypoints, device))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.oslam_stereo_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+        super().__init__(_lib.lib(), "oslam_stereo", max_batch, max_keypoints, device)
 
     def ComputeStereoMatches(self, orbL, orbR, keysL, descL, keysR, descR, bf, b):
         """orbL / orbR: ORBextractor objects that just extracted the pair. Returns (mvuRight, mvDepth)."""
@@ -192,21 +174,12 @@ def feature_vector(node_of_kp):
     return order, node_of_kp[order].astype(np.uint32), nodes.astype(np.uint32), start, order.copy()
 
 
-class BowMatcher:
+class BowMatcher(_lib.Handle):
     """SearchByBoW(KeyFrame*, Frame&) and SearchForTriangulation (reference src/ORBmatcher.cc:159, :657) with
     caller-supplied FeatureVectors (the DBoW2 vocabulary is not part of the reference tree)."""
 
     def __init__(self, max_keypoints=2400, device=0):
-        self.L = _lib.lib()
-        self.h = C.c_void_p()
-        check(self.L.oslam_bow_create(C.byref(self.h), max_keypoints, device))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.oslam_bow_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+        super().__init__(_lib.lib(), "oslam_bow", max_keypoints, device)
 
     @staticmethod
     def _sides(keys1, desc1, uR1, flag1, node1, keys2, desc2, uR2, mp2, node2):

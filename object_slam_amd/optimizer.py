@@ -14,21 +14,12 @@ class Semantic(C.Structure):
                 ("joint_obj", C.c_void_p), ("kp_uv", C.c_void_p), ("bounds", C.c_float * 4), ("invSigma2_0", C.c_float)]
 
 
-class PoseOptimizer:
+class PoseOptimizer(_lib.Handle):
     """Optimizer::PoseOptimization (reference src/Optimizer.cc:239-451)."""
 
     def __init__(self, max_points=4096, max_batch=1, device=0):
-        self.L = _lib.lib()
-        self.h = C.c_void_p()
-        check(self.L.oslam_poseopt_create(C.byref(self.h), max_batch, max_points, device))
+        super().__init__(_lib.lib(), "oslam_poseopt", max_batch, max_points, device)
         self.max_points, self.max_batch = max_points, max_batch
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.oslam_poseopt_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def PoseOptimization(self, Tcw, Xw, obs, invSigma2, has_mp, K5):
         """Returns (n_inliers, Tcw_out[4,4] float32, outlier uint8[N], (LM iterations, trials))."""
@@ -105,21 +96,12 @@ class LbaProblem(C.Structure):
                 ("poses_out", C.c_void_p), ("points_out", C.c_void_p), ("erase", C.c_void_p), ("stats", C.c_void_p)]
 
 
-class LocalBundleAdjuster:
+class LocalBundleAdjuster(_lib.Handle):
     """Optimizer::LocalBundleAdjustment (reference src/Optimizer.cc:453-778) on a flattened graph."""
 
     def __init__(self, max_keyframes=64, max_points=8192, max_edges=65536, max_batch=1, device=0):
-        self.L = _lib.lib()
+        super().__init__(_lib.lib(), "oslam_lba", max_batch, max_keyframes, max_points, max_edges, device)
         self.L.oslam_lba_stop_flag.restype = C.POINTER(C.c_int32)
-        self.h = C.c_void_p()
-        check(self.L.oslam_lba_create(C.byref(self.h), max_batch, max_keyframes, max_points, max_edges, device))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.oslam_lba_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def set_mode(self, wide):
         """wide=True: one problem over the whole GPU (multi-kernel LM); False: one workgroup per problem."""

@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import check, lib, ptr
+from ._lib import Handle, check, device_call, lib, optptr, ptr
 
 REFERENCE_PARAMS = dict(probability=0.99, min_inliers=10, max_iterations=300, min_set=4, epsilon=0.5, th2=5.991)   # src/Tracking.cc:1660
 
@@ -79,25 +79,11 @@ def pack_problems(counts, K4, seeds, offsets=None):
     return pr
 
 
-class PnPsolver:
+class PnPsolver(Handle):
     """A handle for up to max_problems problems with max_correspondences correspondences in all and params.max_iterations <= max_iterations."""
 
     def __init__(self, max_problems=1024, max_correspondences=1 << 17, max_iterations=300):
-        self.L = _bind(lib())
-        self.h = C.c_void_p()
-        check(self.L.oslam_pnp_create(C.byref(self.h), max_problems, max_correspondences, max_iterations))
-
-    def close(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self.L.oslam_pnp_destroy(h)
-            h.value = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # interpreter shutdown
-            pass
+        super().__init__(_bind(lib()), "oslam_pnp", max_problems, max_correspondences, max_iterations)
 
     def ransac_batch(self, problems, P3Dw, P2D, sigma2, params=None, samples=None, iter_inliers=False, Tcw=None, inliers=None, device=False):
         """problems: PROBLEM_DTYPE array (pack_problems); P3Dw [M, 3], P2D [M, 2], sigma2 [M] float32; samples None or int32 [n, max_iterations, 4].
@@ -119,30 +105,12 @@ class PnPsolver:
         assert Tcw.dtype == np.float32 and Tcw.size == 16 * n and Tcw.flags.c_contiguous and inliers.dtype == np.uint8 and inliers.size == M and inliers.flags.c_contiguous
         status = np.zeros((n, 4), np.int32)
         itc = np.full((n, its), -1, np.int32) if iter_inliers else None
+        args = lambda a: (self.h, n, a(problems), M, a(P3Dw), a(P2D), a(sigma2), C.addressof(params), a(samples), a(Tcw), a(inliers), a(status), a(itc))
         if not device:
-            check(self.L.oslam_pnp_ransac_batch(self.h, n, ptr(problems), M, ptr(P3Dw), ptr(P2D), ptr(sigma2), C.addressof(params), ptr(samples) if samples is not None else None,
-                                                ptr(Tcw), ptr(inliers), ptr(status), ptr(itc) if iter_inliers else None))
+            check(self.L.oslam_pnp_ransac_batch(*args(optptr)))
         else:
-            import torch
-            dev = torch.device("cuda", torch.cuda.current_device())
-            up = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1) if a.size else np.zeros(1, np.uint8)).to(dev)
-            d_pr, d_p3, d_p2, d_s = up(problems), up(P3Dw), up(P2D), up(sigma2)
-            d_sam = up(samples) if samples is not None else None
-            d_T, d_in, d_st = up(Tcw), up(inliers), up(status)
-            d_it = up(itc) if iter_inliers else None
-            torch.cuda.synchronize()
-            side = torch.cuda.Stream()
-            with torch.cuda.stream(side):
-                check(self.L.oslam_pnp_ransac_batch_device(self.h, n, d_pr.data_ptr(), M, d_p3.data_ptr(), d_p2.data_ptr(), d_s.data_ptr(), C.addressof(params),
-                                                           d_sam.data_ptr() if d_sam is not None else None, d_T.data_ptr(), d_in.data_ptr(), d_st.data_ptr(),
-                                                           d_it.data_ptr() if d_it is not None else None, C.c_void_p(side.cuda_stream)))
-            side.synchronize()
-            def down(t, a):
-                if a.size:
-                    a.reshape(-1).view(np.uint8)[:] = t.cpu().numpy()[:a.nbytes]
-            down(d_T, Tcw); down(d_in, inliers); down(d_st, status)
-            if iter_inliers:
-                down(d_it, itc)
+            with device_call((problems, P3Dw, P2D, sigma2, samples, Tcw, inliers, status, itc), outputs=(Tcw, inliers, status, itc)) as (addr, stream):
+                check(self.L.oslam_pnp_ransac_batch_device(*args(addr), stream))
         out = dict(Tcw=Tcw.reshape(n, 4, 4), inliers=inliers, status=status)
         if iter_inliers:
             out["iter_inliers"] = itc

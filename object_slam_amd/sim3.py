@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import check, lib, ptr
+from ._lib import Handle, check, device_call, lib, optptr, ptr
 
 REFERENCE_PARAMS = dict(probability=0.99, min_inliers=20, max_iterations=300)   # src/LoopClosing.cc:276
 
@@ -93,25 +93,11 @@ def fresh_states(n):
     return st
 
 
-class Sim3Solver:
+class Sim3Solver(Handle):
     """A handle for up to max_problems problems with max_correspondences correspondences in all and params.max_iterations <= max_iterations."""
 
     def __init__(self, max_problems=1024, max_correspondences=1 << 17, max_iterations=300):
-        self.L = _bind(lib())
-        self.h = C.c_void_p()
-        check(self.L.oslam_sim3_create(C.byref(self.h), max_problems, max_correspondences, max_iterations))
-
-    def close(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self.L.oslam_sim3_destroy(h)
-            h.value = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # interpreter shutdown
-            pass
+        super().__init__(_bind(lib()), "oslam_sim3", max_problems, max_correspondences, max_iterations)
 
     def iterate_batch(self, problems, states, X3Dc1, X3Dc2, sigma2_1, sigma2_2, n_iterations, params=None, samples=None, iter_inliers=False, hypotheses=False, T12=None,
                       inliers=None, device=False):
@@ -138,28 +124,14 @@ class Sim3Solver:
         status = np.zeros((n, 4), np.int32)
         itc = np.full((n, its), -1, np.int32) if iter_inliers else None
         hyp = np.full((n, its, 13), np.nan, np.float32) if hypotheses else None
-        opt = lambda a: ptr(a) if a is not None else None
+        args = lambda a: (self.h, n, a(problems), a(states), M, a(X3Dc1), a(X3Dc2), a(sigma2_1), a(sigma2_2), C.addressof(params), int(n_iterations), a(samples), a(T12),
+                          a(inliers), a(status), a(itc), a(hyp))
         if not device:
-            check(self.L.oslam_sim3_iterate_batch(self.h, n, ptr(problems), ptr(states), M, ptr(X3Dc1), ptr(X3Dc2), ptr(sigma2_1), ptr(sigma2_2), C.addressof(params),
-                                                  int(n_iterations), opt(samples), ptr(T12), ptr(inliers), ptr(status), opt(itc), opt(hyp)))
+            check(self.L.oslam_sim3_iterate_batch(*args(optptr)))
         else:
-            import torch
-            dev = torch.device("cuda", torch.cuda.current_device())
-            up = lambda a: None if a is None else torch.from_numpy(a.view(np.uint8).reshape(-1) if a.size else np.zeros(1, np.uint8)).to(dev)
-            dp = lambda t: t.data_ptr() if t is not None else None
-            d_pr, d_state, d_x1, d_x2, d_s1, d_s2, d_sam = up(problems), up(states), up(X3Dc1), up(X3Dc2), up(sigma2_1), up(sigma2_2), up(samples)
-            d_T, d_in, d_st, d_it, d_hy = up(T12), up(inliers), up(status), up(itc), up(hyp)
-            torch.cuda.synchronize()
-            side = torch.cuda.Stream()
-            with torch.cuda.stream(side):
-                check(self.L.oslam_sim3_iterate_batch_device(self.h, n, dp(d_pr), dp(d_state), M, dp(d_x1), dp(d_x2), dp(d_s1), dp(d_s2), C.addressof(params), int(n_iterations),
-                                                             dp(d_sam), dp(d_T), dp(d_in), dp(d_st), dp(d_it), dp(d_hy), C.c_void_p(side.cuda_stream)))
-            side.synchronize()
-
-            def down(t, a):
-                if a is not None and a.size:
-                    a.reshape(-1).view(np.uint8)[:] = t.cpu().numpy()[:a.nbytes]
-            down(d_T, T12); down(d_in, inliers); down(d_st, status); down(d_state, states); down(d_it, itc); down(d_hy, hyp)
+            with device_call((problems, states, X3Dc1, X3Dc2, sigma2_1, sigma2_2, samples, T12, inliers, status, itc, hyp),
+                             outputs=(T12, inliers, status, states, itc, hyp)) as (addr, stream):
+                check(self.L.oslam_sim3_iterate_batch_device(*args(addr), stream))
         out = dict(T12=T12.reshape(n, 4, 4), inliers=inliers, status=status, states=states)
         if iter_inliers:
             out["iter_inliers"] = itc

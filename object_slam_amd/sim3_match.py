@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import KP_DTYPE, check, lib, ptr
+from ._lib import KP_DTYPE, Handle, check, device_call, lib, optptr, ptr
 from .matcher import Camera
 
 MAX_KEYPOINTS = 2400
@@ -72,25 +72,11 @@ def pack_rows(rows):
     return out
 
 
-class Sim3Matcher:
+class Sim3Matcher(Handle):
     """A handle for up to max_pairs pairs of keyframes with up to max_keypoints (<= 2400) keypoints each."""
 
     def __init__(self, max_pairs=1024, max_keypoints=MAX_KEYPOINTS, device=0):
-        self.L = _bind(lib())
-        self.h = C.c_void_p()
-        check(self.L.oslam_sim3_match_create(C.byref(self.h), max_pairs, max_keypoints, device))
-
-    def close(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self.L.oslam_sim3_match_destroy(h)
-            h.value = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # interpreter shutdown
-            pass
+        super().__init__(_bind(lib()), "oslam_sim3_match", max_pairs, max_keypoints, device)
 
     def search_batch(self, pairs, rows, cam, bounds, scale_factors, log_scale_factor, matched_in=None, match12=None, n_found=None, n_out=None, device=False):
         """SearchBySim3 of every pair.  pairs: PAIR_DTYPE array (pack_pairs); rows: dict of the per-keypoint arrays (ROW_KEYS); cam = (fx, fy, cx, cy);
@@ -112,26 +98,12 @@ class Sim3Matcher:
         camera = Camera(c[0], c[1], c[2], c[3], 0.0, 0.0)
         bnd = np.ascontiguousarray(bounds, np.float32).reshape(4)
         sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
-        opt = lambda a: ptr(a) if a is not None else None
+        def args(a):
+            r = Rows(n_rows, *[a(rows[k]) for k in ROW_KEYS])   # (byref keeps r alive until the call has returned)
+            return (self.h, n, a(pairs), C.byref(r), n_out, a(matched_in), C.addressof(camera), ptr(bnd), ptr(sf), len(sf), float(log_scale_factor), a(match12), a(n_found))
         if not device:
-            r = Rows(n_rows, *[ptr(rows[k]) for k in ROW_KEYS])
-            check(self.L.oslam_match_search_by_sim3_batch(self.h, n, ptr(pairs), C.addressof(r), n_out, opt(matched_in), C.addressof(camera), ptr(bnd), ptr(sf), len(sf),
-                                                          float(log_scale_factor), ptr(match12), ptr(n_found)))
+            check(self.L.oslam_match_search_by_sim3_batch(*args(optptr)))
         else:
-            import torch
-            dev = torch.device("cuda", torch.cuda.current_device())
-            up = lambda a: None if a is None else torch.from_numpy(a.view(np.uint8).reshape(-1) if a.size else np.zeros(1, np.uint8)).to(dev)
-            dp = lambda t: t.data_ptr() if t is not None else None
-            d_rows = {k: up(rows[k]) for k in ROW_KEYS}
-            d_pairs, d_in, d_m, d_nf = up(pairs), up(matched_in), up(match12), up(n_found)
-            torch.cuda.synchronize()
-            r = Rows(n_rows, *[dp(d_rows[k]) for k in ROW_KEYS])
-            side = torch.cuda.Stream()
-            with torch.cuda.stream(side):
-                check(self.L.oslam_match_search_by_sim3_batch_device(self.h, n, dp(d_pairs), C.addressof(r), n_out, dp(d_in), C.addressof(camera), ptr(bnd), ptr(sf), len(sf),
-                                                                     float(log_scale_factor), dp(d_m), dp(d_nf), C.c_void_p(side.cuda_stream)))
-            side.synchronize()
-            for t, a in ((d_m, match12), (d_nf, n_found)):
-                if a.size:
-                    a.reshape(-1).view(np.uint8)[:] = t.cpu().numpy()[:a.nbytes]
+            with device_call([pairs, matched_in, match12, n_found] + [rows[k] for k in ROW_KEYS], outputs=(match12, n_found)) as (addr, stream):
+                check(self.L.oslam_match_search_by_sim3_batch_device(*args(addr), stream))
         return dict(match12=match12, n_found=n_found)

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import check, lib, ptr
+from ._lib import Handle, check, device_call, lib, optptr
 
 REFERENCE_TH2 = 10.0   # src/LoopClosing.cc:327
 TRACE_ROWS = 150       # OSLAM_SIM3_OPT_TRACE_ROWS
@@ -56,25 +56,11 @@ def pack_problems(counts, K1, K2, s12, R12, t12, fix_scale, th2=REFERENCE_TH2, o
     return pr
 
 
-class Sim3Optimizer:
+class Sim3Optimizer(Handle):
     """A handle for up to max_problems problems with max_correspondences correspondences in all."""
 
     def __init__(self, max_problems=1024, max_correspondences=1 << 17, device=0):
-        self.L = _bind(lib())
-        self.h = C.c_void_p()
-        check(self.L.oslam_sim3_opt_create(C.byref(self.h), max_problems, max_correspondences, device))
-
-    def close(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self.L.oslam_sim3_opt_destroy(h)
-            h.value = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # interpreter shutdown
-            pass
+        super().__init__(_bind(lib()), "oslam_sim3_opt", max_problems, max_correspondences, device)
 
     def optimize_batch(self, problems, X3Dc1, X3Dc2, obs1, obs2, invSigma2_1, invSigma2_2, S12=None, inliers=None, status=None, trace=False, device=False):
         """OptimizeSim3 of every problem.  problems: PROBLEM_DTYPE array (pack_problems); X3Dc1, X3Dc2 [M, 3], obs1, obs2 [M, 2], invSigma2_1, invSigma2_2 [M]
@@ -94,26 +80,12 @@ class Sim3Optimizer:
         assert status.dtype == np.int32 and status.size == 4 * n and status.flags.c_contiguous
         tr = np.zeros((n, TRACE_ROWS, 6), np.float64) if trace else None
         tn = np.zeros(n, np.int32) if trace else None
-        opt = lambda a: ptr(a) if a is not None else None
+        args = lambda a: (self.h, n, a(problems), M, a(X3Dc1), a(X3Dc2), a(obs1), a(obs2), a(invSigma2_1), a(invSigma2_2), a(S12), a(inliers), a(status), a(tr), a(tn))
         if not device:
-            check(self.L.oslam_optimize_sim3_batch(self.h, n, ptr(problems), M, ptr(X3Dc1), ptr(X3Dc2), ptr(obs1), ptr(obs2), ptr(invSigma2_1), ptr(invSigma2_2), ptr(S12),
-                                                   ptr(inliers), ptr(status), opt(tr), opt(tn)))
+            check(self.L.oslam_optimize_sim3_batch(*args(optptr)))
         else:
-            import torch
-            dev = torch.device("cuda", torch.cuda.current_device())
-            up = lambda a: None if a is None else torch.from_numpy(a.view(np.uint8).reshape(-1) if a.size else np.zeros(8, np.uint8)).to(dev)
-            dp = lambda t: t.data_ptr() if t is not None else None
-            d_pr, d_x1, d_x2, d_o1, d_o2, d_i1, d_i2 = up(problems), up(X3Dc1), up(X3Dc2), up(obs1), up(obs2), up(invSigma2_1), up(invSigma2_2)
-            d_S, d_in, d_st, d_tr, d_tn = up(S12), up(inliers), up(status), up(tr), up(tn)
-            torch.cuda.synchronize()
-            side = torch.cuda.Stream()
-            with torch.cuda.stream(side):
-                check(self.L.oslam_optimize_sim3_batch_device(self.h, n, dp(d_pr), M, dp(d_x1), dp(d_x2), dp(d_o1), dp(d_o2), dp(d_i1), dp(d_i2), dp(d_S), dp(d_in), dp(d_st),
-                                                              dp(d_tr), dp(d_tn), C.c_void_p(side.cuda_stream)))
-            side.synchronize()
-            for t, a in ((d_S, S12), (d_in, inliers), (d_st, status), (d_tr, tr), (d_tn, tn)):
-                if a is not None and a.size:
-                    a.reshape(-1).view(np.uint8)[:] = t.cpu().numpy()[:a.nbytes]
+            with device_call((problems, X3Dc1, X3Dc2, obs1, obs2, invSigma2_1, invSigma2_2, S12, inliers, status, tr, tn), outputs=(S12, inliers, status, tr, tn)) as (addr, stream):
+                check(self.L.oslam_optimize_sim3_batch_device(*args(addr), stream))
         out = dict(S12=S12.reshape(n, 13), inliers=inliers, status=status.reshape(n, 4))
         if trace:
             out["trace"], out["trace_n"] = tr, tn

@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import check, lib, ptr
+from ._lib import Handle, check, lib, ptr
 
 
 class SlamConfig(C.Structure):
@@ -74,7 +74,9 @@ def make_config(width, height, n_sequences, cam=TUM2, dist=None, nFeatures=1000,
     return c
 
 
-class System:
+class System(Handle):
+    _destroy = "oslam_slam_destroy"   # (created by one of two functions, below)
+
     def __init__(self, cfg, ops=None, vocabulary=None):
         """vocabulary: an object_slam_amd.vocabulary.Vocabulary (the reference's ORBvoc.txt, System.cc:64-76) or None = the substitute vocabulary."""
         self.L = lib()
@@ -93,18 +95,6 @@ class System:
         self._dp = (C.c_void_p * self.S)()
         self.Tcw = np.zeros((self.S, 4, 4), np.float32)
         self.state = np.zeros(self.S, np.int32)
-
-    def close(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self.L.oslam_slam_destroy(h)
-            h.value = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # interpreter shutdown: module globals may already be gone
-            pass
 
     def prepare_rgbd(self, gray, depth, timestamps=None, objects=None, on_device=False, gray_stride=None, depth_pitch=None, mask_stride=None):
         """Marshals one TrackRGBD call ahead of time (pointer tables as ctypes arrays): callers that replay recorded streams keep the Python work out of

@@ -11,7 +11,7 @@ import sys
 
 import numpy as np
 
-from ._lib import OslamError, check, lib, ptr
+from ._lib import Handle, OslamError, check, lib, ptr
 
 SCORING = ("L1_NORM", "L2_NORM", "CHI_SQUARE", "KL", "BHATTACHARYYA", "DOT_PRODUCT")
 WEIGHTING = ("TF_IDF", "TF", "IDF", "BINARY")
@@ -51,7 +51,9 @@ def save_text(path, k, L, scoring, weighting, parent, is_leaf, desc, weight):
             f.write("%d %d %s %r\n" % (int(parent[j]), 1 if is_leaf[j] else 0, " ".join(map(str, desc[j].tolist())), float(weight[j])))
 
 
-class Vocabulary:
+class Vocabulary(Handle):
+    _destroy = "oslam_voc_destroy"   # (the handle comes from one of the class methods)
+
     def __init__(self, handle):
         self.L = _bind(lib())
         self.h = handle
@@ -76,18 +78,6 @@ class Vocabulary:
         h = C.c_void_p()
         check(L.oslam_voc_create(C.byref(h), k, L_, scoring, weighting, n, ptr(parent), ptr(is_leaf), ptr(desc), ptr(weight)))
         return cls(h)
-
-    def close(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            self.L.oslam_voc_destroy(h)
-            h.value = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # interpreter shutdown
-            pass
 
     @property
     def info(self):

@@ -170,6 +170,11 @@ def test_independence_and_determinism(batch, solver):
     assert _same(solver.ransac_batch(pr, p3, p2, sg, samples=samples, iter_inliers=True, **fill()), ref)
     # the device entry point on a side stream
     assert _same(solver.ransac_batch(pr, p3, p2, sg, iter_inliers=True, device=True, **fill()), ref)
+    # one problem without a correspondence: on the device path every per-correspondence array is an empty one, which gets a placeholder address
+    pr0, p30, p20, sg0 = _pack([batch["scenes"][-1]], [1])
+    assert len(pr0) == 1 and len(sg0) == 0
+    fill0 = lambda: dict(Tcw=np.full((1, 4, 4), 7.0, np.float32), inliers=np.zeros(0, np.uint8))
+    assert _same(solver.ransac_batch(pr0, p30, p20, sg0, iter_inliers=True, device=True, **fill0()), solver.ransac_batch(pr0, p30, p20, sg0, iter_inliers=True, **fill0()))
 
 
 def test_bad_numbers_give_no_pose_and_leave_the_neighbours_alone(batch, solver):

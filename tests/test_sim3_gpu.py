@@ -253,6 +253,12 @@ def test_independence_and_determinism(solver, batch, first):
     # the device entry point on a side stream
     assert _same(_run(solver, pr, arrays, 300, device=True), first)
     assert _same(_run(solver, pr, arrays, 300, samples=samples, device=True), first)
+    # one problem without a correspondence: on the device path every per-correspondence array is an empty one, which gets a placeholder address
+    from object_slam_amd import sim3
+    s0 = batch["scenes"][0]
+    pr0 = sim3.pack_problems([0], [s0["K1"]], [s0["K2"]], [1], [0])
+    arr0 = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros(0, np.float32), np.zeros(0, np.float32))
+    assert _same(_run(solver, pr0, arr0, 300, device=True), _run(solver, pr0, arr0, 300))
 
 
 def test_bad_numbers_give_no_sim3_and_leave_the_neighbours_alone(solver, batch, first):

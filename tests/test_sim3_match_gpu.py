@@ -109,6 +109,11 @@ def test_pairs_are_independent(matcher, batch, first):
 
 def test_host_and_device_entry_points_agree(matcher, batch, first):
     assert _same(_run(matcher, batch["pairs"], device=True), first)
+    # one pair of keyframes without keypoints: no rows at all, so on the device path every per-keypoint array is an empty one, which gets a placeholder address
+    empty = [dict(batch["pairs"][1], name="no_rows", kf1=smc.empty_kf(0), kf2=smc.empty_kf(0), matched_in=None)]
+    host = _run(matcher, empty)
+    assert len(host) == 1 and len(host[0][0]) == 0 and host[0][1] == 0
+    assert _same(_run(matcher, empty, device=True), host)
 
 
 def test_refusals(matcher, batch, first):

@@ -176,6 +176,10 @@ def test_entry_points_agree_and_untouched_rows_keep_their_bytes(opt, batch, firs
     for r, (st, inl, S) in zip(batch["ref"], first["res"]):
         assert (S == FILL_S).all() == (not r["written"])
     assert any(not r["written"] for r in batch["ref"]) and any(r["written"] for r in batch["ref"])
+    # the problem without a correspondence alone: on the device path every per-correspondence array is an empty one, which gets a placeholder address
+    zero = [p for p in batch["problems"] if len(p["invSigma2_1"]) == 0][:1]
+    assert len(zero) == 1
+    assert _same(_run(opt, zero, device=True), _run(opt, zero))
 
 
 def test_refusals(opt, batch, first):

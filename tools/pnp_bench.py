@@ -31,7 +31,7 @@ def main():
         raise SystemExit("pnp_bench: no GPU (there is no CPU fallback to time)")
     import pnp_common as pc
     from object_slam_amd import pnp
-    from object_slam_amd._lib import check
+    from object_slam_amd._lib import check, upload as up
     B, N = args.problems, args.n
     base = [pc.make_scene(500 + i, N, outlier_frac=args.outliers) for i in range(min(B, 64))]   # 64 distinct scenes, repeated with other seeds
     scenes = [base[i % len(base)] for i in range(B)]
@@ -40,7 +40,6 @@ def main():
     prm = pnp.make_params()
     solver = pnp.PnPsolver(B, B * N, prm.max_iterations)
     dev = torch.device("cuda", 0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
     d_pr, d_p3, d_p2, d_sg = up(pr), up(p3), up(p2), up(sg)
     d_T = torch.zeros(B * 16, dtype=torch.float32, device=dev)
     d_in = torch.zeros(B * N, dtype=torch.uint8, device=dev)

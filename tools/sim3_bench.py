@@ -33,9 +33,8 @@ def main():
         raise SystemExit("sim3_bench: no GPU (there is no CPU fallback to time)")
     import sim3_common as sc3
     from object_slam_amd import sim3
-    from object_slam_amd._lib import check
+    from object_slam_amd._lib import check, upload as up
     dev = torch.device("cuda", 0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
     stream = torch.cuda.current_stream()
     prm = sim3.make_params()
     results = []

@@ -31,10 +31,9 @@ def main():
         raise SystemExit("sim3_match_bench: no GPU (there is no CPU fallback to time)")
     import sim3_match_common as smc
     from object_slam_amd import sim3_match
-    from object_slam_amd._lib import check, ptr
+    from object_slam_amd._lib import check, ptr, upload as up
     from object_slam_amd.matcher import Camera
     dev = torch.device("cuda", 0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
     stream = torch.cuda.current_stream()
     K = args.keypoints
     base = [smc.make_pair(900 + i, K - 40 + (i * 7) % 80, K - 40 + (i * 13) % 80, (None, 1.1, 0.9, 1.05)[i % 4]) for i in range(64)]

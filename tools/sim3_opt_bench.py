@@ -31,9 +31,8 @@ def main():
         raise SystemExit("sim3_opt_bench: no GPU (there is no CPU fallback to time)")
     import sim3_opt_common as soc
     from object_slam_amd import sim3_opt
-    from object_slam_amd._lib import check
+    from object_slam_amd._lib import check, upload as up
     dev = torch.device("cuda", 0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
     stream = torch.cuda.current_stream()
     B = args.problems
     reps = (B + 63) // 64
