@@ -143,6 +143,26 @@ struct Sim3MatchKeyFrameView {
     const float* mvScaleFactors; int mnScaleLevels; float mfLogScaleFactor;
 };
 
+// Flat views of what ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cc:290-403) and ORBmatcher::Fuse(pKF, Scw, vpPoints, th,
+// vpReplacePoint) (:977-1100) read of the keyframe and of the candidate points (LoopClosing's mvpLoopMapPoints)
+struct Sim3ProjKeyFrameView {
+    int N;                                // mvKeysUn.size()
+    const oslam::KeyPoint* mvKeysUn;
+    const uint8_t* mDescriptors;          // N x 32
+    const uint8_t* mapPointState;         // Fuse only: 0 = GetMapPoint(idx) is NULL, 1 = a point that is not bad, 2 = a bad one
+    float fx, fy, cx, cy;
+    float mnMinX, mnMinY, mnMaxX, mnMaxY;
+    const float* mvScaleFactors; int mnScaleLevels; float mfLogScaleFactor;
+};
+struct Sim3ProjPointsView {
+    int n;                                // vpPoints.size()
+    const float* Xw;                      // [n][3] GetWorldPos()
+    const float* normal;                  // [n][3] GetNormal()
+    const uint8_t* mDescriptors;          // n x 32 GetDescriptor()
+    const float* mfMaxDistance; const float* mfMinDistance;   // the members, as in Sim3MatchKeyFrameView
+    const uint8_t* skip;                  // pMP->isBad() || spAlreadyFound.count(pMP) (:317 / :1005); NULL: no point is skipped
+};
+
 class ORBmatcher {
 public:
     static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 30;   // src/ORBmatcher.cc:37-39
@@ -150,7 +170,7 @@ public:
         : mfNNratio(nnratio), mbCheckOrientation(checkOri) {
         oslam::throw_on(oslam_matcher_create(&h_, 1, max_keypoints, max_queries, device));
     }
-    ~ORBmatcher() { oslam_matcher_destroy(h_); oslam_bow_destroy(bow_); oslam_sim3_match_destroy(sim3m_); }
+    ~ORBmatcher() { oslam_matcher_destroy(h_); oslam_bow_destroy(bow_); oslam_sim3_match_destroy(sim3m_); oslam_sim3_proj_destroy(sim3p_); }
     ORBmatcher(const ORBmatcher&) = delete;
 
     // int SearchByProjection(Frame &F, const vector<MapPoint*> &vpMapPoints, const float th):
@@ -292,14 +312,83 @@ public:
         return nFound;
     }
 
+    // int SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, vector<MapPoint*>& vpMatched, int th) (:290-403).  Scw 4 x 4 row-major.
+    // vpMatched [KF.N]: -1 = NULL, any other value on entry = a matched point; where the reference sets vpMatched[bestIdx] = pMP the entry becomes the point's index
+    // in `points`.  Returns nmatches.
+    int SearchByProjection(const Sim3ProjKeyFrameView& KF, const float Scw[16], const Sim3ProjPointsView& points, std::vector<int32_t>& vpMatched, float th) {
+        if ((int)vpMatched.size() != KF.N) throw std::runtime_error("SearchByProjection: vpMatched must have one entry per keypoint of the keyframe");
+        ensure_proj(points.n);
+        std::vector<uint8_t> state((size_t)KF.N + 1);
+        for (int k = 0; k < KF.N; k++) state[k] = vpMatched[k] != -1;
+        const oslam_sim3_proj_problem_t pr = proj_problem(KF, Scw, points, th);
+        const oslam_sim3_proj_kf_rows_t kf = {KF.N, reinterpret_cast<const oslam_keypoint_t*>(KF.mvKeysUn), KF.mDescriptors, state.data()};
+        const oslam_sim3_proj_pt_rows_t pts = {points.n, points.Xw, points.normal, points.mDescriptors, points.mfMaxDistance, points.mfMinDistance};
+        const oslam_camera_t cam = {KF.fx, KF.fy, KF.cx, KF.cy, 0.f, 0.f};
+        const float bounds[4] = {KF.mnMinX, KF.mnMinY, KF.mnMaxX, KF.mnMaxY};
+        std::vector<int32_t> matched((size_t)KF.N + 1, -1);
+        int32_t nmatches = 0;
+        oslam::throw_on(oslam_match_search_by_projection_sim3_batch(sim3p_, 1, &pr, &kf, &pts, points.n, points.skip, KF.N, &cam, bounds, KF.mvScaleFactors, KF.mnScaleLevels,
+                                                                    KF.mfLogScaleFactor, matched.data(), &nmatches, nullptr));
+        if (nmatches < 0) return 0;   // (an Scw that is not finite or has no positive scale: nothing matches)
+        for (int k = 0; k < KF.N; k++)
+            if (matched[k] >= 0) vpMatched[k] = matched[k];
+        return nmatches;
+    }
+
+    // int Fuse(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, float th, vector<MapPoint*>& vpReplacePoint) (:977-1100).  The surgery is reported:
+    // vpReplacePoint [points.n] is -1 = NULL, OSLAM_FUSE_OCCUPANT = the keyframe's own point at fusedKp[i] (pKF->GetMapPoint(fusedKp[i])), or p >= 0 = points[p],
+    // which this call added at that keypoint earlier; addedKp [points.n] (may be NULL) is bestIdx where the reference calls pMP->AddObservation(pKF, bestIdx) and
+    // pKF->AddMapPoint(pMP, bestIdx), -1 elsewhere; fusedKp [points.n] (may be NULL) is bestIdx of every point that counts in nFused.  Returns nFused.
+    int Fuse(const Sim3ProjKeyFrameView& KF, const float Scw[16], const Sim3ProjPointsView& points, float th, std::vector<int32_t>& vpReplacePoint,
+             std::vector<int32_t>* addedKp = nullptr, std::vector<int32_t>* fusedKp = nullptr) {
+        if ((int)vpReplacePoint.size() != points.n) throw std::runtime_error("Fuse: vpReplacePoint must have one entry per point");
+        if (KF.N > 0 && !KF.mapPointState) throw std::runtime_error("Fuse: the keyframe view has no mapPointState");
+        ensure_proj(points.n);
+        const oslam_sim3_proj_problem_t pr = proj_problem(KF, Scw, points, th);
+        const oslam_sim3_proj_kf_rows_t kf = {KF.N, reinterpret_cast<const oslam_keypoint_t*>(KF.mvKeysUn), KF.mDescriptors, KF.mapPointState};
+        const oslam_sim3_proj_pt_rows_t pts = {points.n, points.Xw, points.normal, points.mDescriptors, points.mfMaxDistance, points.mfMinDistance};
+        const oslam_camera_t cam = {KF.fx, KF.fy, KF.cx, KF.cy, 0.f, 0.f};
+        const float bounds[4] = {KF.mnMinX, KF.mnMinY, KF.mnMaxX, KF.mnMaxY};
+        std::vector<int32_t> fused((size_t)points.n + 1, -1), replace((size_t)points.n + 1, -1);
+        int32_t nFused = 0;
+        oslam::throw_on(oslam_match_fuse_sim3_batch(sim3p_, 1, &pr, &kf, &pts, points.n, points.skip, &cam, bounds, KF.mvScaleFactors, KF.mnScaleLevels, KF.mfLogScaleFactor,
+                                                    fused.data(), replace.data(), &nFused));
+        if (addedKp) addedKp->assign((size_t)points.n, -1);
+        if (fusedKp) fusedKp->assign((size_t)points.n, -1);
+        if (nFused < 0) return 0;
+        for (int i = 0; i < points.n; i++) {
+            if (replace[i] == OSLAM_FUSE_ADDED) { if (addedKp) (*addedKp)[i] = fused[i]; }
+            else if (replace[i] != -1) vpReplacePoint[i] = replace[i];
+            if (fusedKp) (*fusedKp)[i] = fused[i];
+        }
+        return nFused;
+    }
+
     float mfNNratio;
     bool mbCheckOrientation;
 
 private:
+    // the handle SearchByProjection(pKF, Scw, ...) and Fuse(pKF, Scw, ...) share, made at the first call and again when a list is longer than it holds
+    void ensure_proj(int n_points) {
+        if (n_points < 0) throw std::runtime_error("ORBmatcher: negative point count");
+        if (sim3p_ && n_points <= sim3p_cap_) return;
+        oslam_sim3_proj_destroy(sim3p_);
+        sim3p_ = nullptr;
+        sim3p_cap_ = n_points > 16384 ? n_points : 16384;
+        oslam::throw_on(oslam_sim3_proj_create(&sim3p_, 1, 2400, sim3p_cap_, 0));
+    }
+    static oslam_sim3_proj_problem_t proj_problem(const Sim3ProjKeyFrameView& KF, const float Scw[16], const Sim3ProjPointsView& points, float th) {
+        oslam_sim3_proj_problem_t pr;
+        pr.n_kp = KF.N; pr.kp_off = 0; pr.n_pts = points.n; pr.pt_off = 0; pr.kp_out_off = 0; pr.pt_out_off = 0; pr.th = th;
+        memcpy(pr.Scw, Scw, sizeof(pr.Scw));
+        return pr;
+    }
     void ensure_bow() { if (!bow_) oslam::throw_on(oslam_bow_create(&bow_, 2400, 0)); }
     oslam_matcher_t* h_ = nullptr;
     oslam_bow_t* bow_ = nullptr;
     oslam_sim3_match_t* sim3m_ = nullptr;
+    oslam_sim3_proj_t* sim3p_ = nullptr;
+    int sim3p_cap_ = 0;
 };
 
 }  // namespace ORB_SLAM2

@@ -18,3 +18,5 @@ from .sim3_match import Sim3Matcher  # noqa: F401
 from . import sim3_match  # noqa: F401
 from .sim3_opt import Sim3Optimizer  # noqa: F401
 from . import sim3_opt  # noqa: F401
+from .sim3_project import Sim3Projector  # noqa: F401
+from . import sim3_project  # noqa: F401

@@ -9,9 +9,11 @@
 #include <mutex>
 
 #include "common.h"
+#include "keyframe_stage.h"
 #include "stage_layout.h"
 
 using oslam::set_error;
+using namespace oslam::kf_stage;   // the staged keyframe, its grid constants and gemm_row
 
 struct oslam_sim3_match {
     int device = 0, max_pairs = 0, max_kps = 0;
@@ -22,10 +24,6 @@ struct oslam_sim3_match {
 
 namespace {
 
-constexpr int kGridCols = 64, kGridRows = 48;   // reference include/Frame.h:43-44 (KeyFrame copies the Frame's grid, src/KeyFrame.cc:33-55)
-constexpr int kGridCells = kGridCols * kGridRows;
-constexpr int kThreads = 1024;
-constexpr int kMaxKps = 2400;                   // LDS budget, see lds_bytes()
 constexpr int kThHigh = 100;                    // ORBmatcher::TH_HIGH, src/ORBmatcher.cc:36
 constexpr int kSkip = -2;                       // vbAlreadyMatched, kept in the vnMatch arrays (never equal to a keypoint index)
 
@@ -46,21 +44,10 @@ size_t lds_bytes(int ncap) {
     return (size_t)ncap * 51 + (kGridCells + 1) * 4 + 16;
 }
 
-struct Lds {
-    uint32_t* desc;    // [ncap][8]
-    float2* xy;        // [ncap]
+struct Lds : Staged {
     int* m1;           // [ncap] vnMatch1 (kSkip: vbAlreadyMatched1)
     int* m2;           // [ncap] vnMatch2 (kSkip: vbAlreadyMatched2)
-    int* cell;         // [kGridCells + 1] end of every cell in items
-    uint16_t* items;   // [ncap] keypoints sorted by cell (ix major, iy minor), index order inside a cell
-    int8_t* oct;       // [ncap]
 };
-
-// cv::Mat 3x3 * 3x1 + 3x1 as matcher.hip restates it (gemm_row): the three products summed in float from left to right, the `+ c` in double, rounded once
-__device__ __forceinline__ float gemm_row(const float* a, const float* x, float cc) {
-    const float t0 = a[0] * x[0] + a[1] * x[1] + a[2] * x[2];
-    return (float)((double)t0 + (double)cc);
-}
 
 __device__ __forceinline__ bool finite_all(const float* v, int n) {
     bool ok = true;
@@ -68,68 +55,9 @@ __device__ __forceinline__ bool finite_all(const float* v, int n) {
     return ok;
 }
 
-// The target keyframe into LDS: xy, octave, descriptors, and mGrid (src/Frame.cc:455-470: cell = round((x - mnMinX) * inv), push_back in index order)
-__device__ void stage_target(const Sim3MatchArgs& a, const Lds& s, int off, int N, int* s_wtot) {
-    const int tid = threadIdx.x;
-    const oslam_keypoint_t* kps = a.rows.keysUn + off;
-    const uint32_t* gdesc = (const uint32_t*)(a.rows.desc + (size_t)off * 32);
-    __syncthreads();   // the readers of the keyframe staged before are done
-    for (int i = tid; i <= kGridCells; i += kThreads) s.cell[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < N; i += kThreads) {
-        const oslam_keypoint_t kp = kps[i];
-        s.xy[i] = make_float2(kp.x, kp.y);
-        s.oct[i] = (int8_t)min(max(kp.octave, -2), 127);   // (the level gate compares with levels 0 .. 15: -2 and 127 stand for everything beyond)
-        const int px = (int)roundf((kp.x - a.minX) * a.invW);
-        const int py = (int)roundf((kp.y - a.minY) * a.invH);
-        if (px >= 0 && px < kGridCols && py >= 0 && py < kGridRows) atomicAdd(&s.cell[px * kGridRows + py], 1);
-    }
-    for (int i = tid; i < N * 8; i += kThreads) s.desc[i] = gdesc[i];
-    __syncthreads();
-    {   // exclusive scan of the cell counts, kCellsPer per thread
-        constexpr int kCellsPer = kGridCells / kThreads;
-        static_assert(kCellsPer * kThreads == kGridCells, "the cell scan gives every thread the same number of cells");
-        const int lane = tid & 63, wv = tid >> 6;
-        const int base = tid * kCellsPer;
-        int cc[kCellsPer];
-        int incl = 0;
-#pragma unroll
-        for (int k = 0; k < kCellsPer; k++) { cc[k] = s.cell[base + k]; incl += cc[k]; }
-        const int local = incl;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += t;
-        }
-        if (lane == 63) s_wtot[wv] = incl;
-        __syncthreads();
-        int start = incl - local;
-        for (int i = 0; i < wv; i++) start += s_wtot[i];
-#pragma unroll
-        for (int k = 0; k < kCellsPer; k++) { s.cell[base + k] = start; start += cc[k]; }
-    }
-    __syncthreads();
-    // scatter with the cell starts as cursors (afterwards cell[c] = end of cell c = start of c + 1), then restore index order inside every cell
-    for (int i = tid; i < N; i += kThreads) {
-        const float2 p = s.xy[i];
-        const int px = (int)roundf((p.x - a.minX) * a.invW);
-        const int py = (int)roundf((p.y - a.minY) * a.invH);
-        if (px >= 0 && px < kGridCols && py >= 0 && py < kGridRows) {
-            const int pos = atomicAdd(&s.cell[px * kGridRows + py], 1);
-            s.items[pos] = (uint16_t)i;
-        }
-    }
-    __syncthreads();
-    for (int cell = tid; cell < kGridCells; cell += kThreads) {
-        const int st = cell > 0 ? s.cell[cell - 1] : 0, en = s.cell[cell];
-        for (int q = st + 1; q < en; q++) {   // insertion sort, cells hold a handful of points
-            const uint16_t v = s.items[q];
-            int p = q - 1;
-            while (p >= st && s.items[p] > v) { s.items[p + 1] = s.items[p]; p--; }
-            s.items[p + 1] = v;
-        }
-    }
-    __syncthreads();
+// The target keyframe (rows off .. off + N - 1) into LDS
+__device__ __forceinline__ void stage_rows(const Sim3MatchArgs& a, const Lds& s, int off, int N, int* s_wtot) {
+    stage_target(s, a.rows.keysUn + off, a.rows.desc + (size_t)off * 32, N, Grid{a.minX, a.minY, a.invW, a.invH}, s_wtot);
 }
 
 // One direction (:1148-1225 / :1228-1305): the map points of the source keyframe (rows off .. off + N - 1, pose Tsw) through (sR, t) into the staged target.
@@ -244,9 +172,9 @@ __global__ __launch_bounds__(kThreads) void k_search_by_sim3(Sim3MatchArgs a) {
         if (idx2 >= 0 && idx2 < n2) s.m2[idx2] = kSkip;   // (-2, other negative values and >= n2: matched, but not a keypoint of KF2)
     }
     // (stage_target begins with a barrier)
-    stage_target(a, s, off2, n2, s_wtot);
+    stage_rows(a, s, off2, n2, s_wtot);
     search_direction(a, s, s_scale, off1, n1, P.T1w, sR21, t21, P.th, s.m1);
-    stage_target(a, s, off1, n1, s_wtot);
+    stage_rows(a, s, off1, n1, s_wtot);
     search_direction(a, s, s_scale, off2, n2, P.T2w, sR12, P.t12, P.th, s.m2);
     __syncthreads();
     // agreement (:1308-1323)
