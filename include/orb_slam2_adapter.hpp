@@ -1,7 +1,7 @@
 // orb_slam2_adapter.hpp — header-only C++ adapter that re-exposes the reference's class API on top of the C ABI in oslam_hip.h:
 // ORB_SLAM2::ORBextractor (include/ORBextractor.h:45-110), ORB_SLAM2::ORBmatcher (include/ORBmatcher.h:41-83: both projection searches,
 // SearchByBoW, SearchForTriangulation, Fuse, SearchBySim3, DescriptorDistance), Frame::ComputeStereoMatches (src/Frame.cc:706), ORB_SLAM2::Optimizer
-// (include/Optimizer.h:38-57: PoseOptimization, LocalBundleAdjustment, BundleAdjustment, OptimizeSim3) and ObjectOptimizer::PoseOptimization2
+// (include/Optimizer.h:38-57: PoseOptimization, LocalBundleAdjustment, BundleAdjustment, OptimizeSim3, OptimizeEssentialGraph) and ObjectOptimizer::PoseOptimization2
 // (include/ObjectOptimizer.h:23), ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: loadFromTextFile, transform, score) ORB_SLAM2::PnPsolver (include/PnPsolver.h: SetRansacParameters, iterate, find) and ORB_SLAM2::Sim3Solver (include/Sim3Solver.h: SetRansacParameters, iterate, find, GetEstimatedRotation / Translation / Scale).  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
 // "view" of exactly the members it reads and writes (the gather loops are in INTEGRATION.md).  tests/adapter_program.cc uses nothing but
 // these classes; tests/test_adapter_gpu.py builds it, runs it and compares its outputs with the ctypes path.
@@ -13,7 +13,9 @@
 #pragma once
 #include <cstdint>
 #include <cstring>
+#include <algorithm>
 #include <map>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -524,6 +526,25 @@ struct Sim3 {                             // g2o::Sim3 as rotation().toRotationM
     double R[9], t[3], s;
 };
 
+// Flat view of what Optimizer::OptimizeEssentialGraph reads of the map (src/Optimizer.cc:781-1044).  The keyframes are the good ones (!isBad()) in
+// ascending mnId, re-indexed 0 .. nKF - 1; every list below names keyframes by that index and is a CSR pair: entries ptr[k] .. ptr[k + 1] - 1 belong to
+// keyframe k.  The driver does not close loops: this is an operator for a caller that does.
+struct EssentialGraphView {
+    int nKF;
+    float* Tcw;                              // [nKF][16] GetPose() in, SetPose() out
+    const int32_t* parent;                   // [nKF] GetParent(), -1 without one
+    const int32_t* children_ptr; const int32_t* children;       // what hasChild() answers true for
+    const int32_t* loop_ptr; const int32_t* loop_edges;         // GetLoopEdges()
+    const int32_t* covis_ptr; const int32_t* covisibles;        // GetCovisiblesByWeight(100), in its order, bad keyframes left out
+    const int32_t* conn_ptr; const int32_t* conn; const int32_t* conn_weight;   // LoopConnections[pKF] (empty for a keyframe that is no key) and pKF->GetWeight of each
+    const uint8_t* has_corrected; const Sim3* Corrected;        // [nKF] CorrectedSim3.find(pKF) != end(), and its value
+    const uint8_t* has_noncorrected; const Sim3* NonCorrected;  // [nKF] NonCorrectedSim3
+    int pLoopKF, pCurKF;
+    int nMP;                                 // the map points that are not bad
+    float* Xw;                               // [nMP][3] GetWorldPos() in, SetWorldPos() out
+    const int32_t* ref;                      // [nMP] mnCorrectedByKF == pCurKF->mnId ? mnCorrectedReference : GetReferenceKeyFrame(), as an index; -1 skips the point
+};
+
 class Optimizer {
 public:
     // int static OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2, const bool bFixScale)
@@ -585,6 +606,94 @@ public:
             oslam::throw_on(oslam_sim3_opt_create(&h, 1, cap, 0));
         }
         return h;
+    }
+    // The edges of OptimizeEssentialGraph (:847-983) as (i, j, kind) triples in the reference's order: i is setVertex(0), j setVertex(1), kind 0 a new loop
+    // connection (measured between the corrected Sim3s), 1 a spanning-tree, old-loop or covisibility edge (non-corrected where present).  The reference walks
+    // its std::map<KeyFrame*, ...> and std::set<KeyFrame*> in pointer order; here both run in ascending keyframe index.
+    static std::vector<int32_t> EssentialGraphEdges(const EssentialGraphView& G) {
+        const int minFeat = 100;
+        std::vector<int32_t> out;
+        std::set<std::pair<int32_t, int32_t>> sInsertedEdges;
+        auto sorted = [](const int32_t* v, int a, int b) { return std::set<int32_t>(v + a, v + b); };
+        for (int i = 0; i < G.nKF; i++) {   // :852-880
+            std::map<int32_t, int32_t> w;
+            for (int q = G.conn_ptr[i]; q < G.conn_ptr[i + 1]; q++) w[G.conn[q]] = G.conn_weight[q];
+            for (const auto& c : w) {
+                const int j = c.first;
+                if ((i != G.pCurKF || j != G.pLoopKF) && c.second < minFeat) continue;
+                out.insert(out.end(), {i, j, 0});
+                sInsertedEdges.insert(std::make_pair(std::min(i, j), std::max(i, j)));
+            }
+        }
+        for (int i = 0; i < G.nKF; i++) {   // :883-983
+            const int p = G.parent[i];
+            if (p >= 0) out.insert(out.end(), {i, p, 1});
+            const std::set<int32_t> sLoopEdges = sorted(G.loop_edges, G.loop_ptr[i], G.loop_ptr[i + 1]);
+            for (int l : sLoopEdges)
+                if (l < i) out.insert(out.end(), {i, l, 1});
+            const std::set<int32_t> ch = sorted(G.children, G.children_ptr[i], G.children_ptr[i + 1]);
+            for (int q = G.covis_ptr[i]; q < G.covis_ptr[i + 1]; q++) {
+                const int n = G.covisibles[q];
+                if (n != p && !ch.count(n) && !sLoopEdges.count(n) && n < i) {
+                    if (sInsertedEdges.count(std::make_pair(std::min(i, n), std::max(i, n)))) continue;
+                    out.insert(out.end(), {i, n, 1});
+                }
+            }
+        }
+        return out;
+    }
+    // void static OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const KeyFrameAndPose& NonCorrectedSim3, const KeyFrameAndPose&
+    // CorrectedSim3, const map<KeyFrame*, set<KeyFrame*>>& LoopConnections, const bool& bFixScale) (include/Optimizer.h, src/Optimizer.cc:781-1044): writes
+    // G.Tcw (SetPose) and G.Xw (SetWorldPos); UpdateNormalAndDepth (:1042) stays with the caller (the map-point operator).  Throws on an invalid graph.
+    static void OptimizeEssentialGraph(EssentialGraphView& G, bool bFixScale) {
+        const int n = G.nKF;
+        if (n <= 0) return;
+        const std::vector<int32_t> edges = EssentialGraphEdges(G);
+        const int E = (int)(edges.size() / 3);
+        std::vector<float> Scw((size_t)n * 13), Snc((size_t)n * 13, 0.f);
+        std::vector<uint8_t> fixed((size_t)n, 0);
+        auto put = [](float* o, const Sim3& S) {
+            o[0] = (float)S.s;
+            for (int k = 0; k < 9; k++) o[1 + k] = (float)S.R[k];
+            for (int k = 0; k < 3; k++) o[10 + k] = (float)S.t[k];
+        };
+        for (int k = 0; k < n; k++) {   // :809-844
+            float* o = Scw.data() + (size_t)k * 13;
+            if (G.has_corrected[k]) put(o, G.Corrected[k]);
+            else {
+                const float* T = G.Tcw + (size_t)k * 16;
+                o[0] = 1.f;
+                for (int r = 0; r < 3; r++) {
+                    for (int c = 0; c < 3; c++) o[1 + 3 * r + c] = T[4 * r + c];
+                    o[10 + r] = T[4 * r + 3];
+                }
+            }
+            if (G.has_noncorrected[k]) put(Snc.data() + (size_t)k * 13, G.NonCorrected[k]);
+            fixed[k] = k == G.pLoopKF ? 1 : 0;
+        }
+        oslam_essential_graph_problem_t pr;
+        memset(&pr, 0, sizeof(pr));
+        pr.n_kf = n; pr.n_edges = E; pr.fix_scale = bFixScale ? 1 : 0;
+        std::vector<int32_t> row_first((size_t)n);
+        int64_t blocks = 0;
+        oslam::throw_on(oslam_essential_graph_envelope(1, &pr, n, fixed.data(), E, edges.data(), row_first.data(), &blocks));
+        oslam_essential_graph_t* h = nullptr;
+        oslam::throw_on(oslam_essential_graph_create(&h, 1, n, E > 0 ? E : 1, blocks > 0 ? blocks : 1, 0));
+        std::vector<double> Sout((size_t)n * 13);
+        std::vector<float> Tout((size_t)n * 16);
+        int32_t status[4] = {0, 0, 0, 0};
+        int rc = oslam_optimize_essential_graph_batch(h, 1, &pr, n, Scw.data(), Snc.data(), G.has_noncorrected, fixed.data(), E, edges.data(), Sout.data(), Tout.data(), status, nullptr,
+                                                      nullptr);
+        if (rc == OSLAM_OK && status[0] == 0 && G.nMP > 0) {
+            std::vector<int32_t> pp((size_t)G.nMP, 0);
+            std::vector<float> Xout(G.Xw, G.Xw + (size_t)G.nMP * 3);
+            rc = oslam_essential_graph_correct_points(h, 1, &pr, n, Scw.data(), Sout.data(), status, G.nMP, pp.data(), G.ref, G.Xw, Xout.data());
+            if (rc == OSLAM_OK) memcpy(G.Xw, Xout.data(), Xout.size() * sizeof(float));
+        }
+        oslam_essential_graph_destroy(h);
+        oslam::throw_on(rc);
+        if (status[0] != 0) throw std::runtime_error("OptimizeEssentialGraph: invalid graph (a value that is not finite, a scale that is not positive, or no loop keyframe)");
+        memcpy(G.Tcw, Tout.data(), Tout.size() * sizeof(float));
     }
     // int static PoseOptimization(Frame* pFrame) (include/Optimizer.h:46)
     static int PoseOptimization(PoseFrameView& F) {

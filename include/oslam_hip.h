@@ -1143,6 +1143,111 @@ int oslam_match_fuse_sim3_batch_device(oslam_sim3_proj_t* h, int n_problems, con
                                        const float* scaleFactors, int nlevels, float logScaleFactor, int32_t* d_fused_kp, int32_t* d_replace, int32_t* d_n_fused,
                                        void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * OptimizeEssentialGraph — Optimizer::OptimizeEssentialGraph (include/Optimizer.h, src/Optimizer.cc:781-1044), called by LoopClosing::CorrectLoop
+ * (src/LoopClosing.cc:568), for batches of independent pose graphs: one per sequence that closes a loop on this step.  One launch whatever the batch
+ * size, one workgroup per graph.  An operator: the driver does not close loops and does not call it.
+ *
+ * A problem is n_kf keyframes at kf_offset of the packed per-keyframe arrays and n_edges edges at edge_offset of the packed edge array.  The caller
+ * passes the keyframes that are not bad, in ascending mnId, re-indexed 0 .. n_kf - 1.  Per keyframe (float at the ABI, fp64 from there on): Scw
+ * [13] = s, R[9] row-major, t[3]: CorrectedSim3[pKF] where present, otherwise (Rcw, tcw, 1) (:818-832); has_noncorrected (a byte) and Snc [13], read
+ * only where the byte is set: NonCorrectedSim3[pKF]; fixed (a byte): pKF == pLoopKF.  Per problem fix_scale (bFixScale).  Per edge (i, j, kind): i is
+ * setVertex(0), j is setVertex(1), and the measurement is formed on the device:
+ *   kind 0, a new loop connection (:857-867):           Sji = Scw[j] * Scw[i].inverse()
+ *   kind 1, spanning tree / old loop / covisibility (:889-972): Sji = (has_nc[j] ? Snc[j] : Scw[j]) * (has_nc[i] ? Snc[i] : Scw[i]).inverse()
+ * The information is the identity and there is no robust kernel.  The same pair may appear more than once (the reference's rules let duplicates
+ * through); every copy is an edge.  Every Sim3 is g2o::Sim3(Converter::toMatrix3d(R), Converter::toVector3d(t), s): r = Quaterniond(R), not normalised.
+ *
+ * The g2o pieces, restated from the published ORB_SLAM2 Thirdparty/g2o sources (types_seven_dof_expmap, sim3.h, base_binary_edge.hpp,
+ * optimization_algorithm_levenberg.cpp, block_solver.hpp); csrc/sim3_math.h holds the Sim3 ones, shared with OptimizeSim3:
+ *  - EdgeSim3::computeError: _error = (C * v0->estimate() * v1->estimate().inverse()).log(), 7 rows; chi2 = _error . _error.
+ *  - Sim3::log(): sigma = log(s), R = r.toRotationMatrix(), d = 0.5 (R00 + R11 + R22 - 1), eps = 1e-5, four branches on |sigma| < eps and d > 1 - eps:
+ *    omega = 0.5 deltaR(R) for d > 1 - eps, otherwise theta / (2 sqrt(1 - d d)) deltaR(R) with theta = acos(d); deltaR(R) = (R21 - R12, R02 - R20,
+ *    R10 - R01); A, B, C as in Sim3(Vector7d) (the published B of the |sigma| >= eps, small-angle branch unchanged); upsilon = W^-1 t with
+ *    W = A Omega + B Omega^2 + C I; result (omega, upsilon, sigma).
+ *  - EdgeSim3 overrides no linearizeOplus: BaseBinaryEdge's numeric Jacobian for both vertices, per non-fixed vertex and dimension d push,
+ *    oplus(+1e-9 e_d), computeError, pop, the same with -1e-9; the column is (1 / 2e-9) * (e+ - e-).  A fixed vertex gets no Jacobian and no block; an
+ *    edge between two fixed vertices adds to F only.
+ *  - VertexSim3Expmap::oplusImpl with _fix_scale: update[6] = 0, so column 6 of every Jacobian block is exactly zero, row and column 6 of every
+ *    vertex's diagonal block hold lambda alone, and x[6] = 0 / lambda = 0 (b[6] is a sum of exact zeros).
+ *  - OptimizationAlgorithmLevenberg with setUserLambdaInit(1e-16) and one optimize(20): lambda = 1e-16 and ni = 2 at iteration 0; per trial solve
+ *    (H + lambda I) x = b, oplus on every free vertex, F' = the plain chi2 of all edges (DBL_MAX after a failed factorisation, with x = 0),
+ *    rho = (F - F') / (x . (lambda x + b) + 1e-3); rho > 0 and F' finite accepts: lambda *= max(1 / 3, min(1 - (2 rho - 1)^3, 2 / 3)), ni = 2; otherwise
+ *    lambda *= ni, ni *= 2 and the estimates are popped; trials repeat while rho < 0, ten at most; the call stops on the tenth trial or rho == 0.
+ *  - BlockSolver_7_3: H = sum A^T A, b = sum A^T (-e) over the edges, A the 7 x 7 Jacobian of the edge in a free vertex; H(a, b) = A_a^T A_b.
+ *
+ * The system.  H is symmetric in 7 x 7 blocks, one block row per free vertex in the caller's order, stored as a block envelope: row f holds the blocks
+ * from its first column first[f] to the diagonal.  Cholesky fills nothing outside the envelope, so H + lambda I = L L^T is factored in place, again on
+ * every trial, by a right-looking block Cholesky: per block column the 7 x 7 diagonal block (scalar Cholesky, square roots), the blocks below it
+ * (L_IJ = A_IJ L_JJ^-T), the trailing update A_IK -= L_IJ L_KJ^T.  H, L and the working vectors live in device memory owned by the handle.
+ * row_first [n_kf_total] int32 (device entry point; the host entry point computes it): per keyframe k the smallest index m <= k of a keyframe that an
+ * edge joins to k (k itself without one), fixed or not; the row of a free keyframe starts at the first free keyframe at or after row_first[k].  The
+ * problem record names its share of the handle's storage: env_offset and env_blocks, in 7 x 7 blocks (98 doubles of device memory each).
+ *
+ * Normalisations:
+ *  1. Order of the sums: H and b are gathered per block row over the row's incident edges in edge order (the seven products of one edge's A^T A entry
+ *     from row 0 upwards); F and x . (lambda x + b): lane l of 256 adds its terms l, l + 256, ..., then the xor butterfly 32 .. 1 inside each wavefront,
+ *     then the four wavefronts' sums from 0 upwards.  The factorisation visits block columns in order and every entry has one owner lane per step.
+ *     No atomics: results are bit-identical between calls, batch compositions and entry points.
+ *  2. Block Cholesky without pivoting stands in for LinearSolverEigen's sparse Cholesky with its fill-reducing ordering; a pivot that is not positive
+ *     and finite is a failed factorisation.  With fix_scale the pivots of dimension 6 are lambda itself (1e-16 at first): sqrt(1e-16) is an ordinary number.
+ *  3. W.lu().solve(t) of Sim3::log is a 3 x 3 Gaussian elimination with row pivoting on the largest magnitude (Eigen's PartialPivLU), then back
+ *     substitution.  (2 rho - 1)^3 is two products; log, exp, acos, sin, cos and sqrt are the device's.
+ *  4. Invalid: a problem with a non-finite Scw (or Snc where has_noncorrected is set), s <= 0, an edge with i == j, an index outside the problem or a
+ *     kind other than 0 / 1, or no fixed keyframe among n_kf > 0 (the reference always fixes the loop keyframe; without one the gauge is free at
+ *     lambda = 1e-16) gets status {-1, 0, n_edges, 0}; its output rows keep the caller's bytes and the other problems are not affected.
+ *  5. n_kf == 0, n_edges == 0 or no free keyframe: no optimisation, status {0, n_free, n_edges, 0}, the outputs hold the inputs.
+ *  6. Scw_out of a keyframe the optimiser did not move (fixed ones included) is r.toRotationMatrix() of the quaternion built from the input R, t and s
+ *     widened to double: what the reference's recovery loop computes for it.
+ *
+ * Outputs: Scw_out [n_kf_total][13] double = R (row-major, r.toRotationMatrix()), t, s; Tcw_out [n_kf_total][16] float = [R | t * (1. / s)] with last
+ * row 0 0 0 1 (:992-1009); status [n_problems][4] int32 = 0 done / -1 invalid / -2 (device entry point) a record outside the arrays, a row_first
+ * that leaves an edge outside the envelope or an envelope larger than env_blocks: nothing else of the problem is written; n_free; n_edges;
+ * 256 * LM iterations + LM trials.  trace / trace_n: NULL, or [n_problems][OSLAM_ESSENTIAL_GRAPH_TRACE_ROWS][6] double and [n_problems] int32: per
+ * trial F before, F of the trial, rho, lambda of the trial, accepted, first trial of the call (the fields of oslam_poseopt_trace).
+ * Refusals: more problems, keyframes or edges than the handle was created for, or (host entry point) envelopes of more blocks than
+ * max_envelope_blocks_total: OSLAM_E_CAPACITY before anything is launched.  A record outside the arrays: OSLAM_E_INVALID from the host entry point.
+ * Problems of one call must not share keyframe rows, edge rows or envelope storage; calls on one handle must not overlap on the device.
+ *
+ * Point correction (:1013-1043), one elementwise kernel over the points of all problems: P' = Scw_out[r].inverse().map(Scw[r].map(P)) with
+ * map(x) = s (r x) + t, float in, fp64 arithmetic, float out.  Per point point_problem and ref = r, the index inside that problem of the keyframe
+ * the caller resolved from mnCorrectedByKF / mnCorrectedReference or GetReferenceKeyFrame().  A point with ref < 0 (bad), a problem index outside
+ * the call, ref >= n_kf or a problem whose status[0] is not 0 is skipped: its output bytes stay.  UpdateNormalAndDepth is the mappoint operator's.
+ * ---------------------------------------------------------------------------------------- */
+#define OSLAM_ESSENTIAL_GRAPH_TRACE_ROWS 200   /* 20 iterations of at most 10 trials */
+typedef struct oslam_essential_graph oslam_essential_graph_t;
+typedef struct oslam_essential_graph_problem {
+    int32_t n_kf, kf_offset;       /* keyframes kf_offset .. kf_offset + n_kf - 1 of the per-keyframe arrays */
+    int32_t n_edges, edge_offset;  /* edges edge_offset .. edge_offset + n_edges - 1 */
+    int32_t fix_scale;             /* bFixScale */
+    int32_t env_offset, env_blocks; /* device entry point: the problem's 7 x 7 blocks of the handle's storage; the host entry point fills them in */
+    int32_t reserved;
+} oslam_essential_graph_problem_t;
+/* max_envelope_blocks_total bounds the sum over a call's problems of the envelope's 7 x 7 blocks (< 2^31); the handle allocates about 800 bytes of device
+ * memory per block (H and the factor, 392 bytes each, and a column-list entry).  OSLAM_E_HIP without a device: there is no CPU fallback. */
+int oslam_essential_graph_create(oslam_essential_graph_t** out, int max_problems, int max_keyframes_total, int max_edges_total, long long max_envelope_blocks_total, int device);
+void oslam_essential_graph_destroy(oslam_essential_graph_t* h);
+/* Host arithmetic only: row_first [n_kf_total] and env_blocks [n_problems] (int64) of the problems as defined above. */
+int oslam_essential_graph_envelope(int n_problems, const oslam_essential_graph_problem_t* problems, int n_kf_total, const uint8_t* fixed, int n_edges_total, const int32_t* edges,
+                                   int32_t* row_first, int64_t* env_blocks);
+/* Host pointers, staged through one pinned / device block pair: one upload, one launch, one download, synchronous.  Scw, Snc [n_kf_total][13], edges
+ * [n_edges_total][3]; Scw_out, Tcw_out and status are read and written; trace and trace_n may both be NULL. */
+int oslam_optimize_essential_graph_batch(oslam_essential_graph_t* h, int n_problems, const oslam_essential_graph_problem_t* problems, int n_kf_total, const float* Scw,
+                                         const float* Snc, const uint8_t* has_noncorrected, const uint8_t* fixed, int n_edges_total, const int32_t* edges, double* Scw_out,
+                                         float* Tcw_out, int32_t* status, double* trace, int32_t* trace_n);
+/* The same over device arrays (the problem records, with env_offset / env_blocks, and row_first included), one launch, asynchronous on `stream`, no
+ * host synchronisation. */
+int oslam_optimize_essential_graph_batch_device(oslam_essential_graph_t* h, int n_problems, const oslam_essential_graph_problem_t* d_problems, int n_kf_total, const float* d_Scw,
+                                                const float* d_Snc, const uint8_t* d_has_noncorrected, const uint8_t* d_fixed, const int32_t* d_row_first, int n_edges_total,
+                                                const int32_t* d_edges, double* d_Scw_out, float* d_Tcw_out, int32_t* d_status, double* d_trace, int32_t* d_trace_n, void* stream);
+/* Point correction: P, P_out [n_points][3] float, point_problem, ref [n_points] int32; Scw the optimiser's input, Scw_out and status its outputs. */
+int oslam_essential_graph_correct_points(oslam_essential_graph_t* h, int n_problems, const oslam_essential_graph_problem_t* problems, int n_kf_total, const float* Scw,
+                                         const double* Scw_out, const int32_t* status, int n_points, const int32_t* point_problem, const int32_t* ref, const float* P,
+                                         float* P_out);
+int oslam_essential_graph_correct_points_device(oslam_essential_graph_t* h, int n_problems, const oslam_essential_graph_problem_t* d_problems, int n_kf_total, const float* d_Scw,
+                                                const double* d_Scw_out, const int32_t* d_status, int n_points, const int32_t* d_point_problem, const int32_t* d_ref,
+                                                const float* d_P, float* d_P_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

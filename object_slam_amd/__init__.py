@@ -20,3 +20,5 @@ from .sim3_opt import Sim3Optimizer  # noqa: F401
 from . import sim3_opt  # noqa: F401
 from .sim3_project import Sim3Projector  # noqa: F401
 from . import sim3_project  # noqa: F401
+from .essential_graph import EssentialGraphOptimizer, essential_graph_edges  # noqa: F401
+from . import essential_graph  # noqa: F401

@@ -12,9 +12,11 @@
 #include "common.h"
 #include "lane_ops.h"
 #include "se3_math.h"
+#include "sim3_math.h"
 #include "stage_layout.h"
 
 using oslam::set_error;
+using oslam::Sim3; using oslam::pack_sim3; using oslam::sim3_exp; using oslam::sim3_inv; using oslam::sim3_mul; using oslam::sim3_oplus;
 
 struct oslam_sim3_opt {
     int device = 0, max_problems = 0, max_corr = 0;
@@ -27,10 +29,8 @@ namespace {
 constexpr int kLanes = 64;
 constexpr int kTraceRows = OSLAM_SIM3_OPT_TRACE_ROWS;
 constexpr int kPert = 14;      // +delta, -delta for each of the 7 dimensions of VertexSim3Expmap
-constexpr int kPertN = 16;     // q[4] t[3] s of the Sim3 and of its inverse
+constexpr int kPertN = oslam::kSim3PackN;
 constexpr double kDBL_MAX = 1.7976931348623157e308;
-
-struct Sim3 { double q[4], t[3], s; };   // g2o::Sim3: r (x y z w), t, s
 
 struct Sim3OptArgs {
     const oslam_sim3_opt_problem_t* problems;
@@ -39,96 +39,6 @@ struct Sim3OptArgs {
     double* S12; uint8_t* inliers; int32_t* status;
     double* trace; int32_t* trace_n;
 };
-
-__device__ __forceinline__ void quat_mul(const double a[4], const double b[4], double r[4]) {   // Eigen quaternion product
-    const double ax = a[0], ay = a[1], az = a[2], aw = a[3], bx = b[0], by = b[1], bz = b[2], bw = b[3];
-    r[3] = aw * bw - ax * bx - ay * by - az * bz;
-    r[0] = aw * bx + ax * bw + ay * bz - az * by;
-    r[1] = aw * by + ay * bw + az * bx - ax * bz;
-    r[2] = aw * bz + az * bw + ax * by - ay * bx;
-}
-
-// Sim3(const Vector7d& update) of sim3.h: (omega, upsilon, sigma), four branches on |sigma| < eps and theta < eps
-__device__ Sim3 sim3_exp(const double u[7]) {
-    const double wx = u[0], wy = u[1], wz = u[2], sigma = u[6];
-    const double theta = sqrt(wx * wx + wy * wy + wz * wz);
-    const double W[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
-    double W2[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) W2[i * 3 + j] = W[i * 3] * W[j] + W[i * 3 + 1] * W[3 + j] + W[i * 3 + 2] * W[6 + j];
-    Sim3 S;
-    S.s = exp(sigma);
-    const double eps = 0.00001;
-    double A, B, C, ra, rb;   // R = I + ra Omega + rb Omega^2
-    const bool small_theta = theta < eps;
-    if (small_theta) { ra = 1.0; rb = 1.0; }
-    else { ra = sin(theta) / theta; rb = (1 - cos(theta)) / (theta * theta); }
-    if (fabs(sigma) < eps) {
-        C = 1;
-        if (small_theta) { A = 1. / 2.; B = 1. / 6.; }
-        else {
-            const double theta2 = theta * theta;
-            A = (1 - cos(theta)) / theta2;
-            B = (theta - sin(theta)) / (theta2 * theta);
-        }
-    } else {
-        C = (S.s - 1) / sigma;
-        const double sigma2 = sigma * sigma;
-        if (small_theta) {
-            A = ((sigma - 1) * S.s + 1) / sigma2;
-            B = ((0.5 * sigma2 - sigma + 1) * S.s) / (sigma2 * sigma);   // as published (the series of this branch would subtract 1 from the numerator)
-        } else {
-            const double a = S.s * sin(theta), b = S.s * cos(theta);
-            const double theta2 = theta * theta;
-            const double c = theta2 + sigma2;
-            A = (a * sigma + (1 - b) * theta) / (theta * c);
-            B = (C - ((b - 1) * sigma + a * theta) / c) * 1. / theta2;
-        }
-    }
-    double R[9], V[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-        const double I = (i % 4) == 0 ? 1.0 : 0.0;
-        R[i] = small_theta ? (I + W[i]) + W2[i] : (I + ra * W[i]) + rb * W2[i];
-        V[i] = (A * W[i] + B * W2[i]) + C * I;
-    }
-    oslam::quat_from_R(R, S.q);
-#pragma unroll
-    for (int i = 0; i < 3; i++) S.t[i] = V[i * 3] * u[3] + V[i * 3 + 1] * u[4] + V[i * 3 + 2] * u[5];
-    return S;
-}
-
-__device__ __forceinline__ Sim3 sim3_mul(const Sim3& a, const Sim3& b) {   // Sim3::operator*
-    Sim3 r;
-    quat_mul(a.q, b.q, r.q);
-    double rt[3];
-    oslam::quat_rot(a.q, b.t, rt);
-#pragma unroll
-    for (int i = 0; i < 3; i++) r.t[i] = a.s * rt[i] + a.t[i];
-    r.s = a.s * b.s;
-    return r;
-}
-
-__device__ __forceinline__ Sim3 sim3_inv(const Sim3& a) {   // Sim3::inverse
-    Sim3 r;
-    r.q[0] = -a.q[0]; r.q[1] = -a.q[1]; r.q[2] = -a.q[2]; r.q[3] = a.q[3];
-    const double m = -1. / a.s;
-    const double v[3] = {m * a.t[0], m * a.t[1], m * a.t[2]};
-    oslam::quat_rot(r.q, v, r.t);
-    r.s = 1. / a.s;
-    return r;
-}
-
-// VertexSim3Expmap::oplusImpl
-__device__ __forceinline__ Sim3 sim3_oplus(const Sim3& S, const double x[7], bool fix_scale) {
-    double u[7];
-#pragma unroll
-    for (int i = 0; i < 7; i++) u[i] = x[i];
-    if (fix_scale) u[6] = 0;
-    return sim3_mul(sim3_exp(u), S);
-}
 
 // obs - cam_map(project(S.map(P))): EdgeSim3ProjectXYZ with (S12, P3D2c, camera 1), EdgeInverseSim3ProjectXYZ with (S12.inverse(), P3D1c, camera 2)
 __device__ __forceinline__ void edge_error(const double q[4], const double t[3], double s, const double P[3], double fx, double fy, double cx, double cy, const double obs[2],
@@ -150,15 +60,6 @@ struct Camera2 { double fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2; };
 __device__ __forceinline__ void errors_at(const double* S, const Edge& E, const Camera2& K, double e[4]) {
     edge_error(S, S + 4, S[7], E.P2, K.fx1, K.fy1, K.cx1, K.cy1, E.o1, e);
     edge_error(S + 8, S + 12, S[15], E.P1, K.fx2, K.fy2, K.cx2, K.cy2, E.o2, e + 2);
-}
-
-__device__ __forceinline__ void pack_sim3(const Sim3& S, double* p) {
-    const Sim3 Si = sim3_inv(S);
-#pragma unroll
-    for (int k = 0; k < 4; k++) { p[k] = S.q[k]; p[8 + k] = Si.q[k]; }
-#pragma unroll
-    for (int k = 0; k < 3; k++) { p[4 + k] = S.t[k]; p[12 + k] = Si.t[k]; }
-    p[7] = S.s; p[15] = Si.s;
 }
 
 __device__ __forceinline__ void huber(double e2, double delta, double& rho0, double& rho1) {   // RobustKernelHuber::robustify
