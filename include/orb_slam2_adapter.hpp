@@ -2,7 +2,8 @@
 // ORB_SLAM2::ORBextractor (include/ORBextractor.h:45-110), ORB_SLAM2::ORBmatcher (include/ORBmatcher.h:41-83: both projection searches,
 // SearchByBoW, SearchForTriangulation, Fuse, SearchBySim3, DescriptorDistance), Frame::ComputeStereoMatches (src/Frame.cc:706), ORB_SLAM2::Optimizer
 // (include/Optimizer.h:38-57: PoseOptimization, LocalBundleAdjustment, BundleAdjustment, OptimizeSim3, OptimizeEssentialGraph) and ObjectOptimizer::PoseOptimization2
-// (include/ObjectOptimizer.h:23), ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: loadFromTextFile, transform, score) ORB_SLAM2::PnPsolver (include/PnPsolver.h: SetRansacParameters, iterate, find) and ORB_SLAM2::Sim3Solver (include/Sim3Solver.h: SetRansacParameters, iterate, find, GetEstimatedRotation / Translation / Scale).  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
+// (include/ObjectOptimizer.h:23), ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: loadFromTextFile, transform, score) ORB_SLAM2::PnPsolver (include/PnPsolver.h: SetRansacParameters, iterate, find) and ORB_SLAM2::Sim3Solver (include/Sim3Solver.h: SetRansacParameters, iterate, find, GetEstimatedRotation / Translation / Scale) and ORB_SLAM2::KeyFrameDatabase (include/KeyFrameDatabase.h: add, erase, clear,
+// DetectLoopCandidates, DetectRelocalizationCandidates).  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
 // "view" of exactly the members it reads and writes (the gather loops are in INTEGRATION.md).  tests/adapter_program.cc uses nothing but
 // these classes; tests/test_adapter_gpu.py builds it, runs it and compares its outputs with the ctypes path.
 //
@@ -972,6 +973,89 @@ private:
     oslam_sim3_params_t prm_;
     oslam_sim3_state_t st_;
     oslam_sim3_t* h_ = nullptr;
+};
+
+// Flat view of what KeyFrameDatabase reads of a KeyFrame: its id (the slot of the database on the device), its BowVector and, for the queries, the lists the
+// reference asks the keyframe for.
+struct KeyFrameDatabaseKeyFrameView {
+    int mnId;
+    const DBoW2::BowVector* mBowVec;
+    std::vector<int32_t> vpBestCovisibles;   // GetBestCovisibilityKeyFrames(10), ids; read by add and by UpdateCovisibility
+    std::vector<int32_t> spConnected;        // GetConnectedKeyFrames(), ids; read by DetectLoopCandidates
+};
+
+// ORB_SLAM2::KeyFrameDatabase (include/KeyFrameDatabase.h:41-71, src/KeyFrameDatabase.cc) for ONE database, over the oslam_kfdb_* functions of oslam_hip.h
+// (see there for the restated semantics and the reloc_score normalisation).  The database lives on the device; keyframes are named by mnId, which must stay
+// below maxKeyFrames.  The queries return ids where the reference returns KeyFrame pointers.
+class KeyFrameDatabase {
+public:
+    // KeyFrameDatabase(const ORBVocabulary &voc); poolWords 0: room for every keyframe at maxWords
+    explicit KeyFrameDatabase(const ORBVocabulary& voc, int maxKeyFrames = OSLAM_KFDB_MAX_KEYFRAMES, int maxWords = OSLAM_KFDB_MAX_WORDS, long long poolWords = 0) : mpVoc(&voc) {
+        if (poolWords <= 0) poolWords = (long long)maxKeyFrames * ((maxWords + OSLAM_KFDB_CHUNK - 1) / OSLAM_KFDB_CHUNK) * OSLAM_KFDB_CHUNK;
+        oslam::throw_on(oslam_kfdb_create(&h_, 1, maxKeyFrames, maxWords, poolWords, 0));
+        cand_.resize(maxKeyFrames); acc_.resize(maxKeyFrames);
+    }
+    ~KeyFrameDatabase() { oslam_kfdb_destroy(h_); }
+    KeyFrameDatabase(const KeyFrameDatabase&) = delete;
+    KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+
+    // void add(KeyFrame* pKF)
+    void add(const KeyFrameDatabaseKeyFrameView& KF) {
+        flatten(*KF.mBowVec);
+        const oslam_kfdb_add_t rec = {0, KF.mnId, 0, (int32_t)ids_.size()};
+        oslam::throw_on(oslam_kfdb_add(h_, 1, &rec, (int)ids_.size(), ids_.data(), vals_.data()));
+        UpdateCovisibility(KF);
+    }
+    // What the device keeps of KeyFrame::GetBestCovisibilityKeyFrames(10): call it when the keyframe's connections have changed (KeyFrame::UpdateConnections)
+    void UpdateCovisibility(const KeyFrameDatabaseKeyFrameView& KF) {
+        oslam_kfdb_covis_t rec = {0, KF.mnId, (int32_t)std::min<size_t>(KF.vpBestCovisibles.size(), OSLAM_KFDB_COVIS), {0}};
+        for (int i = 0; i < OSLAM_KFDB_COVIS; i++) rec.ids[i] = i < rec.n ? KF.vpBestCovisibles[i] : -1;
+        oslam::throw_on(oslam_kfdb_set_covisibility(h_, 1, &rec));
+    }
+    // void erase(KeyFrame* pKF)
+    void erase(const KeyFrameDatabaseKeyFrameView& KF) {
+        const oslam_kfdb_key_t rec = {0, KF.mnId};
+        oslam::throw_on(oslam_kfdb_erase(h_, 1, &rec));
+    }
+    void clear() {
+        const int32_t d = 0;
+        oslam::throw_on(oslam_kfdb_clear(h_, 1, &d));
+    }
+    // std::vector<KeyFrame*> DetectLoopCandidates(KeyFrame* pKF, float minScore); connScores, if given, receives the score of pKF against every connected
+    // keyframe that is in the database (-1 for the others): what DetectLoop computes minScore from
+    std::vector<int32_t> DetectLoopCandidates(const KeyFrameDatabaseKeyFrameView& KF, float minScore, std::vector<float>* connScores = nullptr) {
+        flatten(*KF.mBowVec);
+        const oslam_kfdb_query_t q = {0, KF.mnId, 0, (int32_t)ids_.size(), 0, (int32_t)KF.spConnected.size(), minScore, 0};
+        std::vector<float> cs(KF.spConnected.size());
+        int32_t n = 0;
+        oslam::throw_on(oslam_kfdb_detect_loop_candidates(h_, mpVoc->handle(), 1, &q, (int)ids_.size(), ids_.data(), vals_.data(), (int)KF.spConnected.size(),
+                                                          KF.spConnected.data(), cand_.data(), acc_.data(), &n, diag_, cs.data()));
+        if (connScores) *connScores = cs;
+        return std::vector<int32_t>(cand_.begin(), cand_.begin() + n);
+    }
+    // std::vector<KeyFrame*> DetectRelocalizationCandidates(Frame* F)
+    std::vector<int32_t> DetectRelocalizationCandidates(int mnId, const DBoW2::BowVector& mBowVec) {
+        flatten(mBowVec);
+        const oslam_kfdb_query_t q = {0, mnId, 0, (int32_t)ids_.size(), 0, 0, 0.0f, 0};
+        int32_t n = 0;
+        oslam::throw_on(oslam_kfdb_detect_relocalization_candidates(h_, mpVoc->handle(), 1, &q, (int)ids_.size(), ids_.data(), vals_.data(), cand_.data(), acc_.data(), &n, diag_));
+        return std::vector<int32_t>(cand_.begin(), cand_.begin() + n);
+    }
+    const float* accumulatedScores() const { return acc_.data(); }   // of the candidates the last query returned, in their order
+    const int32_t* diagnostics() const { return diag_; }            // lKFsSharingWords.size(), maxCommonWords, minCommonWords, nscores, lScoreAndMatch.size()
+
+private:
+    void flatten(const DBoW2::BowVector& v) {
+        ids_.clear(); vals_.clear();
+        for (const auto& e : v) { ids_.push_back(e.first); vals_.push_back(e.second); }   // (std::map order = word id ascending)
+    }
+    const ORBVocabulary* mpVoc;
+    oslam_kfdb_t* h_ = nullptr;
+    std::vector<uint32_t> ids_;
+    std::vector<double> vals_;
+    std::vector<int32_t> cand_;
+    std::vector<float> acc_;
+    int32_t diag_[5] = {0, 0, 0, 0, 0};
 };
 
 }  // namespace ORB_SLAM2

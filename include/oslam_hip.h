@@ -1248,6 +1248,102 @@ int oslam_essential_graph_correct_points_device(oslam_essential_graph_t* h, int 
                                                 const double* d_Scw_out, const int32_t* d_status, int n_points, const int32_t* d_point_problem, const int32_t* d_ref,
                                                 const float* d_P, float* d_P_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * KeyFrameDatabase — ORB_SLAM2::KeyFrameDatabase (include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc:33-309): the query both
+ * Tracking::Relocalization (src/Tracking.cc:1616) and LoopClosing::DetectLoop (src/LoopClosing.cc:143) begin with, for many independent databases
+ * (one per sequence) that live on the device.  Each query call is one launch, one workgroup per query.  An operator: the driver does not call it,
+ * and DetectLoop's consistency groups (src/LoopClosing.cc:156-227) are not part of it.
+ *
+ * State.  Database d has keyframe slots 0 .. max_keyframes - 1; the caller's keyframe id IS the slot.  A slot holds a present bit, the keyframe's
+ * BowVector in the layout of oslam_voc_vectors (word ids uint32 strictly ascending, values double, at most max_words), its add serial (a counter of
+ * the database, taken at add), its best-covisibility list (at most OSLAM_KFDB_COVIS = 10 keyframe ids in the caller's order: what
+ * GetBestCovisibilityKeyFrames(10) returns) and reloc_score (float).  Words are stored in chunks of OSLAM_KFDB_CHUNK = 128 words taken from a pool
+ * that all databases share; the pool's size is fixed at creation and erase / clear hand a keyframe's chunks back.
+ *
+ * There is no inverted file.  The reference's result is restated over the vectors themselves:
+ *  - words(kf) = |ids(query) n ids(kf)|; a keyframe is reached when words > 0 (a loop query: and it is not one of the connected ids).
+ *  - lKFsSharingWords (:86-104, :207-222) is filled walking the query's words in ascending order and each word's list in add order: its order is
+ *    ascending (smallest common word id, add serial).  Every later list is that order, filtered.
+ *  - minCommonWords = (int)(maxCommonWords * 0.8f) (:120, :235); a reached keyframe is scored when words > minCommonWords.
+ *  - score = the L1 score of oslam_voc_score (-0.5 * sum over common words of |a - b| - |a| - |b|, a the query's value) in fp64, cast to float.
+ *  - loop (:125-196): entries with si >= minScore; bestAccScore starts at minScore; a neighbour contributes when it was reached and scored by this
+ *    query (mnLoopQuery == id && mnLoopWords > minCommonWords).  reloc (:242-308): every scored keyframe; bestAccScore starts at 0; a neighbour
+ *    contributes when it was reached by this query, scored or not (:273).  The accumulation walks the covisibility list in order, in float; pBestKF
+ *    changes on strictly greater only; entries with acc > 0.75f * bestAccScore are kept and their pBestKF is output, the first occurrence of each.
+ * Normalisations:
+ *  1. reloc_score.  A reloc neighbour that was reached but not scored contributes the mRelocScore an EARLIER query left in it, and the reference
+ *     never initialises that field (src/KeyFrame.cc:35 names its neighbours, not it).  Here reloc_score is 0 at add, is rewritten whenever a reloc
+ *     query scores the keyframe, and persists across calls.
+ *  2. Every query counts as one with a fresh id (the reference's frame and keyframe ids never repeat): "reached by this query" never sees an
+ *     earlier query's mark.  query_id is carried for the caller and takes no part in the result.
+ *  3. Order of a score's sum: lane c of 16 adds the terms of the keyframe's common words at positions c, c + 16, ... of the keyframe's vector in
+ *     ascending position, then the xor butterfly 8, 4, 2, 1 over the 16 lanes.  It depends on the two vectors only: identical vectors give identical
+ *     scores, and results are bit-identical between calls, batch compositions and entry points.  No atomics on global memory.
+ *  4. Ids of a covisibility list, and connected ids, outside 0 .. max_keyframes - 1 or of a slot that is not present are skipped.
+ * Because of 1., two reloc queries on one database are sequential: a call holds at most one query per database.
+ *
+ * Mutations take arrays of records, are applied in record order on the handle's stream and return when they are applied.  A refused call changes
+ * nothing.  Queries: records name their words (word_off, n_words into ids / vals) and, for loop queries, their connected keyframe ids (conn_off,
+ * n_conn into conn) and min_score.  Outputs per query q: cand, cand_acc [q * max_keyframes ..]: candidate ids in the reference's order and their
+ * accumulated scores; n_cand [q] their number; diag [q * 5 ..] int32 = lKFsSharingWords.size(), maxCommonWords, minCommonWords, nscores,
+ * lScoreAndMatch.size(); loop queries also conn_score [n_conn_total] float: the score of the query against each connected id that is present,
+ * -1 for the others (what DetectLoop :125-139 takes its minScore from).  Only L1_NORM vocabularies (scoring 0), as for oslam_voc_score.
+ * ---------------------------------------------------------------------------------------- */
+#define OSLAM_KFDB_COVIS 10
+#define OSLAM_KFDB_CHUNK 128
+#define OSLAM_KFDB_MAX_KEYFRAMES 2048   /* per database: the per-slot scratch of a query lives in LDS */
+#define OSLAM_KFDB_MAX_WORDS 2400
+typedef struct oslam_kfdb oslam_kfdb_t;
+typedef struct oslam_kfdb_add {
+    int32_t database, keyframe;
+    int32_t word_off, n_words;     /* words word_off .. word_off + n_words - 1 of the call's ids / vals */
+} oslam_kfdb_add_t;
+typedef struct oslam_kfdb_key { int32_t database, keyframe; } oslam_kfdb_key_t;
+typedef struct oslam_kfdb_covis {
+    int32_t database, keyframe, n;
+    int32_t ids[OSLAM_KFDB_COVIS];
+} oslam_kfdb_covis_t;
+typedef struct oslam_kfdb_query {
+    int32_t database, query_id;
+    int32_t word_off, n_words;
+    int32_t conn_off, n_conn;      /* loop queries: spConnectedKeyFrames; ignored by reloc queries */
+    float min_score;               /* loop queries */
+    int32_t reserved;
+} oslam_kfdb_query_t;
+/* pool_words is rounded up to whole chunks; a keyframe of n words takes ceil(n / 128) chunks.  max_keyframes <= OSLAM_KFDB_MAX_KEYFRAMES, max_words <=
+ * OSLAM_KFDB_MAX_WORDS.  OSLAM_E_HIP without a device: there is no CPU fallback.  (KeyFrameDatabase::KeyFrameDatabase, :33-37) */
+int oslam_kfdb_create(oslam_kfdb_t** out, int n_databases, int max_keyframes, int max_words, long long pool_words, int device);
+void oslam_kfdb_destroy(oslam_kfdb_t* h);
+/* out[0] = free chunks of the pool, out[1] = all its chunks, out[2] = present keyframes over all databases. */
+int oslam_kfdb_info(const oslam_kfdb_t* h, int64_t out[3]);
+/* KeyFrameDatabase::add (:40-46).  OSLAM_E_INVALID: a slot that is present (or named twice in the call), ids not strictly ascending, a database
+ * outside the handle; OSLAM_E_CAPACITY: keyframe >= max_keyframes, n_words > max_words, or fewer free chunks than the call needs.  The new keyframe
+ * has an empty covisibility list and reloc_score 0. */
+int oslam_kfdb_add(oslam_kfdb_t* h, int n, const oslam_kfdb_add_t* recs, int n_words_total, const uint32_t* ids, const double* vals);
+/* KeyFrameDatabase::erase (:48-67); a slot that is not present is left alone. */
+int oslam_kfdb_erase(oslam_kfdb_t* h, int n, const oslam_kfdb_key_t* recs);
+/* KeyFrameDatabase::clear (:69-73) of each named database. */
+int oslam_kfdb_clear(oslam_kfdb_t* h, int n, const int32_t* databases);
+/* The list KeyFrame::GetBestCovisibilityKeyFrames(10) (src/KeyFrame.cc:193-201) returns for a present keyframe; replaces the one it had. */
+int oslam_kfdb_set_covisibility(oslam_kfdb_t* h, int n, const oslam_kfdb_covis_t* recs);
+/* KeyFrameDatabase::DetectLoopCandidates (:76-197) / DetectRelocalizationCandidates (:199-309).  Host pointers, staged through one pinned / device
+ * block pair: one upload, one launch, one download, synchronous.  Refused before anything runs: two queries on one database, ids not strictly
+ * ascending, a record outside the arrays (OSLAM_E_INVALID); n_words > max_words (OSLAM_E_CAPACITY). */
+int oslam_kfdb_detect_loop_candidates(oslam_kfdb_t* h, const oslam_voc_t* voc, int n_queries, const oslam_kfdb_query_t* queries, int n_words_total, const uint32_t* ids,
+                                      const double* vals, int n_conn_total, const int32_t* conn, int32_t* cand, float* cand_acc, int32_t* n_cand, int32_t* diag,
+                                      float* conn_score);
+int oslam_kfdb_detect_relocalization_candidates(oslam_kfdb_t* h, const oslam_voc_t* voc, int n_queries, const oslam_kfdb_query_t* queries, int n_words_total,
+                                                const uint32_t* ids, const double* vals, int32_t* cand, float* cand_acc, int32_t* n_cand, int32_t* diag);
+/* The same over device arrays, one launch, asynchronous on `stream`, no host synchronisation; the caller orders it after the mutations it depends on
+ * (they have completed when they return) and before the next call on the handle.  What the host entry points refuse per call is answered per query
+ * here: n_cand = -2 and nothing else of that query is written (both queries of a pair that names one database). */
+int oslam_kfdb_detect_loop_candidates_device(oslam_kfdb_t* h, const oslam_voc_t* voc, int n_queries, const oslam_kfdb_query_t* d_queries, int n_words_total,
+                                             const uint32_t* d_ids, const double* d_vals, int n_conn_total, const int32_t* d_conn, int32_t* d_cand, float* d_cand_acc,
+                                             int32_t* d_n_cand, int32_t* d_diag, float* d_conn_score, void* stream);
+int oslam_kfdb_detect_relocalization_candidates_device(oslam_kfdb_t* h, const oslam_voc_t* voc, int n_queries, const oslam_kfdb_query_t* d_queries, int n_words_total,
+                                                       const uint32_t* d_ids, const double* d_vals, int32_t* d_cand, float* d_cand_acc, int32_t* d_n_cand,
+                                                       int32_t* d_diag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

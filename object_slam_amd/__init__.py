@@ -22,3 +22,5 @@ from .sim3_project import Sim3Projector  # noqa: F401
 from . import sim3_project  # noqa: F401
 from .essential_graph import EssentialGraphOptimizer, essential_graph_edges  # noqa: F401
 from . import essential_graph  # noqa: F401
+from .keyframe_db import KeyFrameDatabase  # noqa: F401
+from . import keyframe_db  # noqa: F401
