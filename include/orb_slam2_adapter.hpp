@@ -1,5 +1,5 @@
 // orb_slam2_adapter.hpp — header-only C++ adapter that re-exposes the reference's class API on top of the C ABI in oslam_hip.h:
-// ORB_SLAM2::ORBextractor (include/ORBextractor.h:45-110), ORB_SLAM2::ORBmatcher (include/ORBmatcher.h:41-83: both projection searches,
+// ORB_SLAM2::ORBextractor (include/ORBextractor.h:45-110), ORB_SLAM2::ORBmatcher (include/ORBmatcher.h:41-83: the projection searches, the relocalisation one included,
 // SearchByBoW, SearchForTriangulation, Fuse, SearchBySim3, DescriptorDistance), Frame::ComputeStereoMatches (src/Frame.cc:706), ORB_SLAM2::Optimizer
 // (include/Optimizer.h:38-57: PoseOptimization, LocalBundleAdjustment, BundleAdjustment, OptimizeSim3, OptimizeEssentialGraph) and ObjectOptimizer::PoseOptimization2
 // (include/ObjectOptimizer.h:23), ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: loadFromTextFile, transform, score) ORB_SLAM2::PnPsolver (include/PnPsolver.h: SetRansacParameters, iterate, find) and ORB_SLAM2::Sim3Solver (include/Sim3Solver.h: SetRansacParameters, iterate, find, GetEstimatedRotation / Translation / Scale) and ORB_SLAM2::KeyFrameDatabase (include/KeyFrameDatabase.h: add, erase, clear,
@@ -166,6 +166,26 @@ struct Sim3ProjPointsView {
     const uint8_t* skip;                  // pMP->isBad() || spAlreadyFound.count(pMP) (:317 / :1005); NULL: no point is skipped
 };
 
+// Flat views of what ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1472-1599) reads of the frame and of the
+// keyframe's map-point slots (Tracking::Relocalization, src/Tracking.cc:1717, :1731)
+struct RelocFrameView {
+    int N;                                // mvKeysUn.size()
+    const oslam::KeyPoint* mvKeysUn;      // pt, octave and angle are read
+    const uint8_t* mDescriptors;          // N x 32
+    float Tcw[16];                        // mTcw, row-major
+    float fx, fy, cx, cy;
+    float mnMinX, mnMinY, mnMaxX, mnMaxY;
+    const float* mvScaleFactors; int mnScaleLevels; float mfLogScaleFactor;
+};
+struct RelocKeyFrameView {                // one entry per slot i of pKF->GetMapPointMatches()
+    int n;
+    const float* Xw;                      // [n][3] pMP->GetWorldPos()
+    const uint8_t* mDescriptors;          // n x 32 pMP->GetDescriptor()
+    const float* mfMaxDistance; const float* mfMinDistance;   // the members, as in Sim3MatchKeyFrameView
+    const float* angle;                   // pKF->mvKeysUn[i].angle
+    const uint8_t* skip;                  // pMP == NULL || pMP->isBad() || sAlreadyFound.count(pMP) (:1492-1494); the other rows of a skipped slot are not read
+};
+
 class ORBmatcher {
 public:
     static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 30;   // src/ORBmatcher.cc:37-39
@@ -173,7 +193,7 @@ public:
         : mfNNratio(nnratio), mbCheckOrientation(checkOri) {
         oslam::throw_on(oslam_matcher_create(&h_, 1, max_keypoints, max_queries, device));
     }
-    ~ORBmatcher() { oslam_matcher_destroy(h_); oslam_bow_destroy(bow_); oslam_sim3_match_destroy(sim3m_); oslam_sim3_proj_destroy(sim3p_); }
+    ~ORBmatcher() { oslam_matcher_destroy(h_); oslam_bow_destroy(bow_); oslam_sim3_match_destroy(sim3m_); oslam_sim3_proj_destroy(sim3p_); oslam_reloc_proj_destroy(relocp_); }
     ORBmatcher(const ORBmatcher&) = delete;
 
     // int SearchByProjection(Frame &F, const vector<MapPoint*> &vpMapPoints, const float th):
@@ -367,6 +387,37 @@ public:
         return nFused;
     }
 
+    // int SearchByProjection(Frame &CurrentFrame, KeyFrame* pKF, const set<MapPoint*> &sAlreadyFound, const float th, const int ORBdist) (:1472-1599).
+    // mvpMapPoints [F.N] is CurrentFrame.mvpMapPoints: -1 = NULL, any other value on entry = a point the frame holds; where the reference sets
+    // mvpMapPoints[bestIdx2] = pMP and the rotation histogram leaves it, the entry becomes the slot index i of the keyframe (pMP = vpMPs[i]).  Returns nmatches.
+    int SearchByProjection(const RelocFrameView& F, const RelocKeyFrameView& KF, std::vector<int32_t>& mvpMapPoints, float th, int ORBdist) {
+        if ((int)mvpMapPoints.size() != F.N) throw std::runtime_error("SearchByProjection: mvpMapPoints must have one entry per keypoint of the frame");
+        if (KF.n < 0) throw std::runtime_error("ORBmatcher: negative slot count");
+        if (!relocp_ || KF.n > relocp_cap_) {   // made at the first call and again when a keyframe has more slots than it holds
+            oslam_reloc_proj_destroy(relocp_);
+            relocp_ = nullptr;
+            relocp_cap_ = KF.n > 16384 ? KF.n : 16384;
+            oslam::throw_on(oslam_reloc_proj_create(&relocp_, 1, 2400, relocp_cap_, 0));
+        }
+        std::vector<uint8_t> has_mp((size_t)F.N + 1);
+        for (int k = 0; k < F.N; k++) has_mp[k] = mvpMapPoints[k] != -1;
+        oslam_reloc_proj_problem_t pr;
+        pr.n_kp = F.N; pr.kp_off = 0; pr.n_pts = KF.n; pr.pt_off = 0; pr.kp_out_off = 0; pr.pt_out_off = 0; pr.th = th; pr.ORBdist = ORBdist;
+        memcpy(pr.Tcw, F.Tcw, sizeof(pr.Tcw));
+        const oslam_reloc_proj_frame_rows_t fr = {F.N, reinterpret_cast<const oslam_keypoint_t*>(F.mvKeysUn), F.mDescriptors, has_mp.data()};
+        const oslam_reloc_proj_pt_rows_t pts = {KF.n, KF.Xw, KF.mDescriptors, KF.mfMaxDistance, KF.mfMinDistance, KF.angle};
+        const oslam_camera_t cam = {F.fx, F.fy, F.cx, F.cy, 0.f, 0.f};
+        const float bounds[4] = {F.mnMinX, F.mnMinY, F.mnMaxX, F.mnMaxY};
+        std::vector<int32_t> matched((size_t)F.N + 1, -1);
+        int32_t nmatches = 0;
+        oslam::throw_on(oslam_match_search_by_projection_reloc_batch(relocp_, 1, &pr, &fr, &pts, KF.n, KF.skip, F.N, &cam, bounds, F.mvScaleFactors, F.mnScaleLevels,
+                                                                     F.mfLogScaleFactor, mbCheckOrientation ? 1 : 0, matched.data(), &nmatches, nullptr, nullptr));
+        if (nmatches < 0) return 0;   // (a pose that is not finite: nothing matches)
+        for (int k = 0; k < F.N; k++)
+            if (matched[k] >= 0) mvpMapPoints[k] = matched[k];
+        return nmatches;
+    }
+
     float mfNNratio;
     bool mbCheckOrientation;
 
@@ -392,6 +443,8 @@ private:
     oslam_sim3_match_t* sim3m_ = nullptr;
     oslam_sim3_proj_t* sim3p_ = nullptr;
     int sim3p_cap_ = 0;
+    oslam_reloc_proj_t* relocp_ = nullptr;
+    int relocp_cap_ = 0;
 };
 
 }  // namespace ORB_SLAM2

@@ -1144,6 +1144,106 @@ int oslam_match_fuse_sim3_batch_device(oslam_sim3_proj_t* h, int n_problems, con
                                        void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Relocalisation projection — ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, const float th,
+ * const int ORBdist) (src/ORBmatcher.cc:1472-1599), which Tracking::Relocalization calls twice per candidate whose optimised pose has 10 to 49 inliers
+ * (src/Tracking.cc:1717 with th = 10, ORBdist = 100; :1731 with th = 3, ORBdist = 64), for batches of independent problems: one per (lost frame,
+ * candidate keyframe).  Relocalization rewrites all of mvpMapPoints before each use (:1694-1703), so the problems of a call do not see each other.  One
+ * launch, one workgroup per problem.  An operator: the driver does not relocalise and does not call it.
+ *
+ * A problem (oslam_reloc_proj_problem_t) is one frame (n_kp rows at kp_off of oslam_reloc_proj_frame_rows_t), its pose Tcw (row-major 4 x 4 float, rows
+ * 0-2 read: Rcw and tcw as they are, no scale is divided out), the map-point slots of one keyframe (n_pts rows at pt_off of oslam_reloc_proj_pt_rows_t),
+ * th and ORBdist.  Per frame row: mvKeysUn (x, y, octave and angle are read), mDescriptors and has_mp = (CurrentFrame.mvpMapPoints[i] != NULL) on entry.
+ * Per point row (slot i of pKF->GetMapPointMatches()): GetWorldPos, GetDescriptor, mfMaxDistance and mfMinDistance (the raw members) and kf_angle =
+ * pKF->mvKeysUn[i].angle; the rows of a slot that is skipped are not read.  skip [n_pt_out], at pt_out_off .. pt_out_off + n_pts - 1: pMP == NULL ||
+ * pMP->isBad() || sAlreadyFound.count(pMP) (:1492-1494), per problem and point; NULL = nothing is skipped.  One camera (fx, fy, cx, cy read), bounds[4] =
+ * mnMinX, mnMinY, mnMaxX, mnMaxY, mvScaleFactors, mnScaleLevels, mfLogScaleFactor and check_orientation (mbCheckOrientation) per call.
+ *
+ * Per slot i in index order (:1488-1575): skipped when skip is set; x3Dc = Rcw Xw + tcw; invzc = 1.0 / zc; u = fx * xc * invzc + cx, v likewise; rejected
+ * when u < mnMinX || u > mnMaxX || v < mnMinY || v > mnMaxY (both bounds inclusive, unlike IsInImage); there is NO test of the sign of z: a point behind
+ * the camera that projects inside the bounds is searched like any other, and z == 0 gives an infinite u (rejected by the bounds) or a NaN; dist3D =
+ * cv::norm(Xw - Ow) kept when 0.8f mfMinDistance <= dist3D <= 1.2f mfMaxDistance; level = PredictScale(dist3D, &CurrentFrame) (src/MapPoint.cc:505-520);
+ * radius = th * mvScaleFactors[level]; Frame::GetFeaturesInArea(u, v, radius, level - 1, level + 1) (src/Frame.cc:567-620): the cells of the window, the
+ * octave gate level - 1 <= octave <= level + 1 (bCheckLevels is always true here: maxLevel >= 1), the strict window fabs(dx) < r && fabs(dy) < r; a frame
+ * keypoint whose mvpMapPoints entry is not NULL (has_mp on entry, or claimed earlier in this call) is no candidate; bestDist starts at 256 and the first
+ * strictly smaller DescriptorDistance wins in the order cell column, cell row, keypoint index; accepted when bestDist <= ORBdist.  mvpMapPoints[bestIdx2]
+ * is written at once, so slot i sees the claims of every slot j < i.  Reproduced exactly by the fixpoint of the Sim3 projection section (every slot takes
+ * its best among the keypoints no lower slot claimed in the previous pass; passes repeat until no claim changes; slot i is final after pass i + 1, and
+ * the loop is cut after n_pts + 2 passes whatever the data).
+ * After the loop, with check_orientation (:1577-1596): per accepted slot rot = kf_angle[i] - frame.angle[bestIdx2] in float, + 360.0f when rot < 0.0;
+ * bin = round(rot * (1.0f / 30)) (the reference's factor 1 / HISTO_LENGTH, half away from zero); bin == 30 becomes 0; ComputeThreeMaxima (:1601-1642) over
+ * the sizes of the 30 bins (the first of equal sizes keeps its rank; max2 < 0.1f * (float)max1 drops ind2 and ind3, else max3 < 0.1f * (float)max1 drops
+ * ind3); every match whose bin is none of the three is removed.  A removed match has still blocked later slots during the loop: the fixpoint runs on
+ * the claims, the histogram once afterwards.
+ * Outputs: matched [n_kp_out], at kp_out_off .. kp_out_off + n_kp - 1: the slot i the call wrote to the frame keypoint and the histogram left there, -1
+ * elsewhere (also where the keypoint held a point on entry).  n_matches [n_problems]: the reference's return value.  n_removed [n_problems] (may be
+ * NULL): the matches the histogram took away.  n_passes [n_problems] (may be NULL): the passes of the fixpoint.
+ *
+ * Roundings: those of the Sim3 projection section where the expression is the same — the 3 x 3 * 3 x 1 + 3 x 1 product (gemm_row), Ow = -Rcw.t() * tcw,
+ * PO = Xw - Ow, cv::norm, the 0.8f / 1.2f gates, PredictScale (level 0 for a quotient that is not finite or does not fit an int), th * scale and the grid
+ * arithmetic (mfGridElementWidthInv = 64 / (mnMaxX - mnMinX) in float, floor and ceil of the float expressions).  New here:
+ *  - invzc = 1.0 / zc: a double quotient narrowed to float (the correctly rounded float quotient).
+ *  - u = fx * xc * invzc + cx: float, multiplied left to right ((fx * xc) * invzc), then the sum; not fx * (xc * invzc) as in the Sim3 section.
+ *  - rot, rot * factor and the comparison 0.1f * (float)max in float; round() half away from zero.
+ * Normalisations (declared, not pinned facts):
+ *  - A slot whose u or v is not finite has no candidates.  (A NaN passes the reference's bounds test and reaches GetFeaturesInArea, where
+ *    (int)floor(NaN) is INT_MIN on x86 and the function returns nothing; an infinity fails the bounds test.)
+ *  - Angles are degrees in [0, 360], as for oslam_match_project_last_frame, which makes 0 <= bin <= 12.  The reference asserts 0 <= bin < 30 and is
+ *    undefined beyond; here a match whose bin is outside 0 .. 29 (an angle outside the contract, or a NaN) is counted in no bin and removed.
+ *  - ORBdist outside 0 .. 255 is refused: with every candidate claimed bestDist stays 256, and a larger ORBdist would make the reference write
+ *    mvpMapPoints[-1].
+ *  - th is finite and not negative (the reference passes 10 and 3), and th * mvScaleFactors[level] small enough for the cell coordinates of
+ *    GetFeaturesInArea to fit an int.  Beyond that the reference's float-to-int conversions overflow (INT_MIN on x86: it finds nothing); the kernel's
+ *    conversions saturate instead, the walk stays inside the 64 x 48 cells and the strict window test decides.  The Sim3 projection section is alike.
+ * Refusals: more problems than max_problems, a frame above max_keypoints, more point rows or skip rows than max_points_total, or a negative count:
+ * OSLAM_E_CAPACITY, nothing is launched; rows outside the arrays, or an ORBdist outside 0 .. 255: OSLAM_E_INVALID.  The device entry point cannot read
+ * the records: there such a record gets count -2 and nothing else of it is written.  A problem whose Tcw (rows 0-2) is not finite gets count -1, its
+ * matched rows all -1 and n_removed = n_passes = 0; the other problems are not affected.  Point data that is not finite falls out through the
+ * reference's own comparisons and the normalisation above.  Problems of one call must not share output rows.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct oslam_reloc_proj oslam_reloc_proj_t;
+typedef struct oslam_reloc_proj_problem {
+    int32_t n_kp, kp_off;         /* the frame = rows kp_off .. kp_off + n_kp - 1 */
+    int32_t n_pts, pt_off;        /* the keyframe's map-point slots = rows pt_off .. pt_off + n_pts - 1 */
+    int32_t kp_out_off;           /* matched rows kp_out_off .. kp_out_off + n_kp - 1 */
+    int32_t pt_out_off;           /* skip rows pt_out_off .. pt_out_off + n_pts - 1 */
+    float Tcw[16];                /* CurrentFrame.mTcw */
+    float th;
+    int32_t ORBdist;
+} oslam_reloc_proj_problem_t;
+typedef struct oslam_reloc_proj_frame_rows {   /* n_rows entries each; the device entry point takes device pointers, desc 16-byte aligned */
+    int32_t n_rows;
+    const oslam_keypoint_t* keysUn;   /* CurrentFrame.mvKeysUn */
+    const uint8_t* desc;              /* [n_rows][32] CurrentFrame.mDescriptors */
+    const uint8_t* has_mp;            /* CurrentFrame.mvpMapPoints[i] != NULL on entry */
+} oslam_reloc_proj_frame_rows_t;
+typedef struct oslam_reloc_proj_pt_rows {      /* n_rows entries each; desc 16-byte aligned on the device */
+    int32_t n_rows;
+    const float* Xw;              /* [n_rows][3] GetWorldPos */
+    const uint8_t* desc;          /* [n_rows][32] GetDescriptor */
+    const float* maxDistance;     /* mfMaxDistance */
+    const float* minDistance;     /* mfMinDistance */
+    const float* kf_angle;        /* pKF->mvKeysUn[i].angle */
+} oslam_reloc_proj_pt_rows_t;
+/* max_keypoints <= 2400, the cap of the Sim3 projection handle: the frame is staged in LDS with the same 51 bytes per keypoint, and the angles the
+ * histogram needs are read from global memory, so this kernel needs no more.  max_points_total bounds the point rows and the skip rows of one call (the
+ * handle keeps 32 bytes of device memory per row).  OSLAM_E_HIP without a device: there is no CPU fallback. */
+int oslam_reloc_proj_create(oslam_reloc_proj_t** out, int max_problems, int max_keypoints, int max_points_total, int device);
+void oslam_reloc_proj_destroy(oslam_reloc_proj_t* h);
+/* Host pointers, staged through one pinned / device block pair: one upload, one launch, one download, synchronous.  skip, n_removed and n_passes may be
+ * NULL; the outputs are read and written (rows no problem owns keep what they held). */
+int oslam_match_search_by_projection_reloc_batch(oslam_reloc_proj_t* h, int n_problems, const oslam_reloc_proj_problem_t* problems, const oslam_reloc_proj_frame_rows_t* frame,
+                                                 const oslam_reloc_proj_pt_rows_t* pts, int n_pt_out, const uint8_t* skip, int n_kp_out, const oslam_camera_t* cam,
+                                                 const float bounds[4], const float* scaleFactors, int nlevels, float logScaleFactor, int check_orientation, int32_t* matched,
+                                                 int32_t* n_matches, int32_t* n_removed, int32_t* n_passes);
+/* The same over device arrays (frame and pts are host structs of device pointers; cam, bounds and scaleFactors are host pointers), one launch,
+ * asynchronous on `stream`, no host synchronisation.  Calls on one handle must not overlap on the device: the search keeps per-point state in the handle. */
+int oslam_match_search_by_projection_reloc_batch_device(oslam_reloc_proj_t* h, int n_problems, const oslam_reloc_proj_problem_t* d_problems,
+                                                        const oslam_reloc_proj_frame_rows_t* frame, const oslam_reloc_proj_pt_rows_t* pts, int n_pt_out, const uint8_t* d_skip,
+                                                        int n_kp_out, const oslam_camera_t* cam, const float bounds[4], const float* scaleFactors, int nlevels,
+                                                        float logScaleFactor, int check_orientation, int32_t* d_matched, int32_t* d_n_matches, int32_t* d_n_removed,
+                                                        int32_t* d_n_passes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * OptimizeEssentialGraph — Optimizer::OptimizeEssentialGraph (include/Optimizer.h, src/Optimizer.cc:781-1044), called by LoopClosing::CorrectLoop
  * (src/LoopClosing.cc:568), for batches of independent pose graphs: one per sequence that closes a loop on this step.  One launch whatever the batch
  * size, one workgroup per graph.  An operator: the driver does not close loops and does not call it.

@@ -24,3 +24,5 @@ from .essential_graph import EssentialGraphOptimizer, essential_graph_edges  # n
 from . import essential_graph  # noqa: F401
 from .keyframe_db import KeyFrameDatabase  # noqa: F401
 from . import keyframe_db  # noqa: F401
+from .reloc_project import RelocProjector  # noqa: F401
+from . import reloc_project  # noqa: F401
