@@ -1028,6 +1028,90 @@ private:
     oslam_sim3_t* h_ = nullptr;
 };
 
+// Flat view of what Initializer reads of a Frame: mvKeysUn and mK (src/Initializer.cc:34-38, :49)
+struct InitFrameView {
+    int N;                                // mvKeysUn.size()
+    const oslam::KeyPoint* mvKeysUn;
+    float fx, fy, cx, cy;
+};
+#ifdef OSLAM_ADAPTER_USE_OPENCV
+typedef cv::Point3f Point3f;
+#else
+struct Point3f { float x, y, z; };
+#endif
+
+// ORB_SLAM2::Initializer (include/Initializer.h:38-46) over oslam_init_* (oslam_hip.h, "Initializer").  R21 (3 x 3 row-major) and t21 are float arrays where
+// the reference has cv::Mat; they, vP3D and vbTriangulated are written only when Initialize returns true.  `seed` stands for DUtils::Random, which the
+// reference seeds with 0 (src/Initializer.cc:80).
+class Initializer {
+public:
+    Initializer(const InitFrameView& ReferenceFrame, float sigma = 1.0, int iterations = 200, uint32_t seed = 0) : mSigma(sigma), mMaxIterations(iterations), seed_(seed) {
+        K_[0] = ReferenceFrame.fx; K_[1] = ReferenceFrame.fy; K_[2] = ReferenceFrame.cx; K_[3] = ReferenceFrame.cy;
+        keys1_ = pack(ReferenceFrame);
+    }
+    ~Initializer() { oslam_init_destroy(h_); }
+    Initializer(const Initializer&) = delete;
+    Initializer& operator=(const Initializer&) = delete;
+
+    // Computes in parallel a fundamental matrix and a homography, selects a model and tries to recover the motion and the structure from motion
+    bool Initialize(const InitFrameView& CurrentFrame, const std::vector<int>& vMatches12, float R21[9], float t21[3], std::vector<Point3f>& vP3D,
+                    std::vector<bool>& vbTriangulated) {
+        const int n1 = (int)(keys1_.size() / 2);
+        if ((int)vMatches12.size() != n1) throw std::runtime_error("Initializer: vMatches12 must have one entry per key of the reference frame");
+        const std::vector<float> keys2 = pack(CurrentFrame);
+        const int n2 = CurrentFrame.N, cap = std::max(1, std::max(n1, n2));
+        if (!h_ || cap > cap_) {
+            oslam_init_destroy(h_);
+            h_ = nullptr;
+            oslam::throw_on(oslam_init_create(&h_, 1, cap, mMaxIterations));
+            cap_ = cap;
+        }
+        oslam_init_problem_t pr;
+        pr.n1 = n1; pr.off1 = 0; pr.n2 = n2; pr.off2 = 0; pr.fx = K_[0]; pr.fy = K_[1]; pr.cx = K_[2]; pr.cy = K_[3]; pr.sigma = mSigma; pr.seed = seed_;
+        pr.reserved[0] = 0; pr.reserved[1] = 0;
+        oslam_init_params_t prm;
+        prm.max_iterations = mMaxIterations; prm.min_parallax = 1.0f; prm.min_triangulated = 50; prm.reserved = 0;   // (src/Initializer.cc:116-118)
+        std::vector<int32_t> m12(vMatches12.begin(), vMatches12.end());
+        std::vector<float> P3D(3 * (size_t)n1, 0.f);
+        std::vector<uint8_t> tri(n1, 0);
+        float R[9], t[3];
+        oslam::throw_on(oslam_init_initialize_batch(h_, 1, &pr, n1, keys1_.data(), m12.data(), n2, keys2.data(), &prm, nullptr, R, t, P3D.data(), tri.data(), status, scores,
+                                                    nullptr, nullptr, nullptr, nullptr));
+        if (status[0] != 1) return false;
+        for (int k = 0; k < 9; k++) R21[k] = R[k];
+        for (int k = 0; k < 3; k++) t21[k] = t[k];
+        vP3D.resize(n1);
+        vbTriangulated.assign(n1, false);
+        for (int i = 0; i < n1; i++) {
+            vP3D[i].x = P3D[3 * (size_t)i]; vP3D[i].y = P3D[3 * (size_t)i + 1]; vP3D[i].z = P3D[3 * (size_t)i + 2];
+            vbTriangulated[i] = tri[i] != 0;
+        }
+        return true;
+    }
+    int32_t status[8] = {0, 0, 0, 0, -1, -1, -1, 0};   // of the last Initialize: returned, model, N, nGood, motion, best H / F iteration, nsimilar / secondBestGood
+    float scores[4] = {0, 0, 0, 0};                    // SH, SF, RH, parallax
+
+private:
+    static std::vector<float> pack(const InitFrameView& F) {
+        std::vector<float> k(2 * (size_t)F.N);
+        for (int i = 0; i < F.N; i++) {
+#ifdef OSLAM_ADAPTER_USE_OPENCV
+            k[2 * (size_t)i] = F.mvKeysUn[i].pt.x; k[2 * (size_t)i + 1] = F.mvKeysUn[i].pt.y;
+#else
+            k[2 * (size_t)i] = F.mvKeysUn[i].x; k[2 * (size_t)i + 1] = F.mvKeysUn[i].y;
+#endif
+        }
+        return k;
+    }
+    float mSigma;
+    int mMaxIterations;
+    uint32_t seed_;
+    float K_[4];
+    std::vector<float> keys1_;
+    oslam_init_t* h_ = nullptr;
+    int cap_ = 0;
+};
+
 // Flat view of what KeyFrameDatabase reads of a KeyFrame: its id (the slot of the database on the device), its BowVector and, for the queries, the lists the
 // reference asks the keyframe for.
 struct KeyFrameDatabaseKeyFrameView {

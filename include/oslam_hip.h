@@ -1444,6 +1444,93 @@ int oslam_kfdb_detect_relocalization_candidates_device(oslam_kfdb_t* h, const os
                                                        const uint32_t* d_ids, const double* d_vals, int32_t* d_cand, float* d_cand_acc, int32_t* d_n_cand,
                                                        int32_t* d_diag, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Initializer — ORB_SLAM2::Initializer (include/Initializer.h, src/Initializer.cc: homography / fundamental RANSAC, model selection, motion recovery),
+ * the numerical operator of Tracking::MonocularInitialization (src/Tracking.cc:661, :695), for batches of independent problems (one per sequence
+ * that is still initialising).  One shot: Initialize has no resumable state.  The tracking driver does not call it: oslam_slam.h is RGB-D / stereo
+ * only.  ORBmatcher::SearchForInitialization (src/ORBmatcher.cc:405), which produces vMatches12, is not part of the library yet.
+ *
+ * A problem is the n1 undistorted keys of the reference frame (mvKeysUn[i].pt, float [.][2]) at off1 of the packed keys-1 array, the n2 keys of the
+ * current frame at off2 of the keys-2 array, vMatches12 (int32, parallel to the keys-1 array: entry >= 0 is an index into the problem's keys 2,
+ * entry < 0 no match), the intrinsics, sigma and a seed.  Problems of one call must not share keys-1 entries.
+ * Initialize (:44-121):
+ *  - mvMatches12 (:54-63) is the match list compacted in key-1 order; N is its length and every draw indexes it.
+ *  - Normalize (:749-795) of ALL keys of each frame (not only the matched ones): mean, mean absolute deviation, T = [sX 0 -meanX sX; 0 sY -meanY sY; 0 0 1].
+ *  - per iteration eight indices by the swap-with-back rule (:82-97); ComputeH21 (:226-266: the right singular vector of the smallest singular value
+ *    of the 16 x 9 system) and ComputeF21 (:268-303: the null vector of the 8 x 9 system, then w(2) = 0 in a 3 x 3 SVD), both stored as CV_32F;
+ *    H21i = T2inv Hn T1, H12i = H21i.inv() (:160-161), F21i = T2t Fn T1 (:212).
+ *  - CheckHomography (:305-388, th 5.991) and CheckFundamental (:390-468, th 3.841, thScore 5.991) over all N matches in the reference's float
+ *    arithmetic; comparisons are strict; the first iteration of strictly highest score wins per model (:165, :216), starting from score 0.
+ *  - RH = SH / (SH + SF) in float; RH > 0.40 takes ReconstructH, anything else (a NaN included) ReconstructF (:112-118).
+ *  - ReconstructF (:470-570): E21 = Kt F21 K, DecomposeE (:909-929), four motions (R1 t, R2 t, R1 -t, R2 -t), nMinGood = max((int)(0.9 N), 50), the
+ *    0.7 maxGood similarity count, the == cascade.  ReconstructH (:572-732): Faugeras' eight motions, the d1/d2, d2/d3 < 1.00001 rejection, best /
+ *    second best in the order 0..7, the final four-way condition.  (N there is the number of inliers of the best iteration.)
+ *  - CheckRT (:798-907) per inlier match: the 4 x 4 DLT Triangulate (:734-747), the finiteness test, cosParallax, both depth tests with their 0.99998
+ *    exemption, both reprojection tests against 4 sigma^2, nGood, parallax = acos(sorted cosParallax[min(50, size - 1)]) 180 / pi; vbGood only where
+ *    cosParallax < 0.99998.
+ *
+ * Normalisations:
+ *  1. The generator: the reference seeds DUtils::Random with 0 (:80) and DUtils is not in the tree.  As normalisation 1 of the PnP solver with eight
+ *     draws (oslam_init_draw), or the caller's `samples` [n][max_iterations][8]: eight distinct indices of the compacted match list; anything else
+ *     gives both hypotheses of that iteration score 0, no inliers and a NaN matrix in the dump.
+ *  2. N < 8 (the reference indexes an empty list): status returned 0, model 0, no iteration is run and nothing else is written.
+ *  3. Sums: Normalize and the scores accumulate sequentially in float in the reference.  Here every term is the reference's float term; the sums are taken
+ *     in fp64 in a fixed order (which depends on the problem alone) and rounded to float once.
+ *  4. cvSVD's choices.  The sign and scale of a null vector: nothing downstream depends on them; the vector has unit norm and its component of largest
+ *     magnitude (the first of equals) is positive, which fixes the sign of the dumped H21i / F21i.  The order of the motions depends on the signs of
+ *     the singular vectors: in DecomposeE t = u.col(2) has its component of largest magnitude positive and R1 is the rotation of larger trace (R1 and
+ *     R2 differ by a half turn about t; u.col(2) and vt.row(2) are formed as cross products of the other two vectors, since E's third singular value is
+ *     zero); in ReconstructH every left singular vector has its component of largest magnitude positive and its right vector follows.  status[4] is
+ *     the winning motion's index under these conventions; the winner itself does not depend on them.  The 9 x 9 and 3 x 3 decompositions are fp64
+ *     Jacobi and rounded where the reference stores CV_32F; products of float matrices accumulate in fp64 and round once (cv::gemm).
+ *  5. Input validation: a key, intrinsic or sigma that is not finite, or a match index >= n2, gives status returned 0, model 0, N 0 and no iteration.
+ *  6. A model without a best iteration (every score 0 or NaN) has no matrix: if it is the chosen one, status returned 0 with that model and motion -1.
+ *  7. A returning problem gets all n1 entries of P3D and triangulated: zeros where the winning motion did not count the key (vP3D.resize, :808-809),
+ *     the point wherever CheckRT counted it (:889) and triangulated only where cosParallax < 0.99998 (:892-893).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct oslam_init oslam_init_t;
+typedef struct oslam_init_params {   /* Initializer(ReferenceFrame, 1.0, 200) (src/Tracking.cc:661); ReconstructF / H are called with (1.0, 50) (:116-118) */
+    int32_t max_iterations;
+    float min_parallax;
+    int32_t min_triangulated;
+    int32_t reserved;
+} oslam_init_params_t;
+typedef struct oslam_init_problem {
+    int32_t n1, off1;   /* keys off1 .. off1 + n1 - 1 of the keys-1 array (and of matches12, P3D, triangulated, match_inliers) */
+    int32_t n2, off2;   /* keys of the current frame in the keys-2 array */
+    float fx, fy, cx, cy;
+    float sigma;
+    uint32_t seed;
+    int32_t reserved[2];
+} oslam_init_problem_t;
+/* The eight indices iteration `iteration` of a problem with N >= 8 matches draws from `seed` (normalisation 1).  Host only, needs no device. */
+int oslam_init_draw(uint32_t seed, int iteration, int N, int32_t idx[8]);
+/* max_keys_total bounds the keys-1 and the keys-2 array of a call, max_iterations its params.max_iterations.  OSLAM_E_HIP without a device. */
+int oslam_init_create(oslam_init_t** out, int max_problems, int max_keys_total, int max_iterations);
+void oslam_init_destroy(oslam_init_t* h);
+/* Host pointers; one upload, two launches, one download, synchronous.  keys1 [n_keys1][2], matches12 [n_keys1], keys2 [n_keys2][2]; samples NULL or
+ * [n_problems][params.max_iterations][8] int32.  Outputs: R21 [n_problems][9] and t21 [n_problems][3] float; P3D [n_keys1][3] float and triangulated
+ * [n_keys1] bytes by key-1 index (normalisation 7); status [n_problems][8] int32 = returned (0 / 1), model used (0 none run, 1 H, 2 F), N, nGood of
+ * the winning motion (bestGood / maxGood), its index (0..7 for H, 0..3 for F, -1 none), best H iteration, best F iteration (-1 none), nsimilar (F) or
+ * secondBestGood (H); scores [n_problems][4] float = SH, SF, RH, parallax of that motion in degrees.  Dumps, each NULL or: iter_scores
+ * [n_problems][max_iterations][2] float (H, F; NaN where not run), hypotheses [n_problems][max_iterations][2][9] float (H21i, F21i; NaN where not run),
+ * iter_inliers [n_problems][max_iterations][2] int32 (-1 where not run), match_inliers [n_keys1][2] bytes (vbMatchesInliersH / F of the best
+ * iterations by key-1 index).  A problem that does not return keeps the caller's R21, t21, P3D and triangulated.  More problems, keys or iterations
+ * than the handle was created for: OSLAM_E_CAPACITY before anything is launched. */
+int oslam_init_initialize_batch(oslam_init_t* h, int n_problems, const oslam_init_problem_t* problems, int n_keys1, const float* keys1, const int32_t* matches12, int n_keys2,
+                                const float* keys2, const oslam_init_params_t* params, const int32_t* samples, float* R21, float* t21, float* P3D, uint8_t* triangulated,
+                                int32_t* status, float* scores, float* iter_scores, float* hypotheses, int32_t* iter_inliers, uint8_t* match_inliers);
+/* The same over device arrays (`params` is a host pointer), asynchronous on `stream`, no host synchronisation.  Dump entries of what is not run are left
+ * as they were.  A problem record that does not lie inside the key arrays gets status -1, 0, 0, 0, -1, -1, -1, 0 and nothing else. */
+int oslam_init_initialize_batch_device(oslam_init_t* h, int n_problems, const oslam_init_problem_t* d_problems, int n_keys1, const float* d_keys1, const int32_t* d_matches12,
+                                       int n_keys2, const float* d_keys2, const oslam_init_params_t* params, const int32_t* d_samples, float* d_R21, float* d_t21, float* d_P3D,
+                                       uint8_t* d_triangulated, int32_t* d_status, float* d_scores, float* d_iter_scores, float* d_hypotheses, int32_t* d_iter_inliers,
+                                       uint8_t* d_match_inliers, void* stream);
+/* Measurement: with timing on, every later call records events before, between and after its two launches on the call's stream;
+ * oslam_init_last_kernel_ms waits for the last call's events and gives the milliseconds of the hypothesis kernel and of the reconstruction kernel. */
+int oslam_init_set_timing(oslam_init_t* h, int on);
+int oslam_init_last_kernel_ms(oslam_init_t* h, float ms[2]);
+
 #ifdef __cplusplus
 }
 #endif

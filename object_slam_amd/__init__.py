@@ -26,3 +26,5 @@ from .keyframe_db import KeyFrameDatabase  # noqa: F401
 from . import keyframe_db  # noqa: F401
 from .reloc_project import RelocProjector  # noqa: F401
 from . import reloc_project  # noqa: F401
+from .initializer import Initializer  # noqa: F401
+from . import initializer  # noqa: F401

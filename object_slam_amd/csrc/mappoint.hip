@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "common.h"
+#include "small_svd.h"   // svd4_last_row, shared with initializer.hip
 
 namespace oslam {
 
@@ -936,91 +937,6 @@ __device__ __forceinline__ double dot3d(const float* a, const float* b) {
 }
 // cv::gemm small-matrix branch (float accumulation), optional + c
 __device__ __forceinline__ float rowmul3(const float* row, const float* x) { return row[0] * x[0] + row[1] * x[1] + row[2] * x[2]; }
-
-// one Jacobi rotation between rows I and J of At (and of Vt); returns whether it rotated
-template <int I, int J>
-__device__ __forceinline__ bool jacobi_pair(float (&At)[16], float (&Vt)[16], double (&W)[4]) {
-    double a = W[I], b = W[J], p = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) p += (double)At[I * 4 + k] * (double)At[J * 4 + k];
-    const float eps = 2.0f * 1.1920928955078125e-07f;
-    if (fabs(p) <= (double)eps * sqrt(a * b)) return false;
-    p *= 2;
-    const double beta = a - b, gamma = hypot(p, beta);
-    float c, s;
-    if (beta < 0) {
-        const double delta = (gamma - beta) * 0.5;
-        s = (float)sqrt(delta / gamma);
-        c = (float)(p / (gamma * (double)s * 2));
-    } else {
-        c = (float)sqrt((gamma + beta) / (gamma * 2));
-        s = (float)(p / (gamma * (double)c * 2));
-    }
-    a = b = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const float ai = At[I * 4 + k], aj = At[J * 4 + k];
-        const float t0 = c * ai + s * aj, t1 = -s * ai + c * aj;
-        At[I * 4 + k] = t0; At[J * 4 + k] = t1;
-        a += (double)t0 * (double)t0; b += (double)t1 * (double)t1;
-    }
-    W[I] = a; W[J] = b;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const float vi = Vt[I * 4 + k], vj = Vt[J * 4 + k];
-        Vt[I * 4 + k] = c * vi + s * vj;
-        Vt[J * 4 + k] = -s * vi + c * vj;
-    }
-    return true;
-}
-
-// last right singular vector of a 4x4 float matrix (row-major A), as cv::SVD::compute(...).vt.row(3)
-__device__ void svd4_last_row(const float (&A)[16], float (&out)[4]) {
-    float At[16], Vt[16];
-    double W[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        double sd = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) { At[i * 4 + k] = A[k * 4 + i]; sd += (double)At[i * 4 + k] * (double)At[i * 4 + k]; Vt[i * 4 + k] = (i == k) ? 1.f : 0.f; }
-        W[i] = sd;
-    }
-    for (int iter = 0; iter < 30; iter++) {
-        bool changed = false;
-        changed |= jacobi_pair<0, 1>(At, Vt, W);
-        changed |= jacobi_pair<0, 2>(At, Vt, W);
-        changed |= jacobi_pair<0, 3>(At, Vt, W);
-        changed |= jacobi_pair<1, 2>(At, Vt, W);
-        changed |= jacobi_pair<1, 3>(At, Vt, W);
-        changed |= jacobi_pair<2, 3>(At, Vt, W);
-        if (!changed) break;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        double sd = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) sd += (double)At[i * 4 + k] * (double)At[i * 4 + k];
-        W[i] = sqrt(sd);
-    }
-    // selection sort by decreasing W (strict <), tracking only which original row ends up last
-    int perm[4] = {0, 1, 2, 3};
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        int j = i;
-#pragma unroll
-        for (int k = i + 1; k < 4; k++)
-            if (W[j] < W[k]) j = k;
-        if (j != i) {
-            // static-index swap
-#pragma unroll
-            for (int k = i + 1; k < 4; k++)
-                if (k == j) { const double tw = W[i]; W[i] = W[k]; W[k] = tw; const int tp = perm[i]; perm[i] = perm[k]; perm[k] = tp; }
-        }
-    }
-    const int r = perm[3];
-#pragma unroll
-    for (int k = 0; k < 4; k++) out[k] = r == 0 ? Vt[k] : r == 1 ? Vt[4 + k] : r == 2 ? Vt[8 + k] : Vt[12 + k];
-}
 
 __device__ __forceinline__ bool tri_reproj_ok(const TriKfDev& kf, float mbf, float kx, float ky, float kur, bool bStereo, float x, float y, float z, float sig) {
     const float invz = (float)(1.0 / (double)z);

@@ -11,9 +11,11 @@
 #include "common.h"
 #include "lane_ops.h"
 #include "ransac_draw.h"   // the counter-based generator and the draw rule, shared with sim3.hip
+#include "small_svd.h"     // svd3, shared with initializer.hip
 #include "stage_layout.h"
 
 using oslam::set_error;
+using oslam::svd3;
 
 struct oslam_pnp {
     int max_problems = 0, max_corr = 0, max_iterations = 0, max_sets = 0;
@@ -27,7 +29,6 @@ namespace {
 constexpr int kG = 16;             // lanes per hypothesis / per EPnP
 constexpr int kHypPerBlock = 4;    // one wavefront
 constexpr int kJacobiSweeps = 10;  // cyclic Jacobi on the 12 x 12 MtM: fixed, so that NaN inputs cannot spin and every lane exchange is in uniform control flow
-constexpr int kSvd3Sweeps = 12;
 
 struct RansacAdj { int min_inliers; float epsilon; int iterations; int no_more; };
 
@@ -67,43 +68,6 @@ __device__ __forceinline__ Pt pt_load(const PnpPts& P, int i) {
     p.X = P.p3[3 * j]; p.Y = P.p3[3 * j + 1]; p.Z = P.p3[3 * j + 2];
     p.u = P.p2[2 * j]; p.v = P.p2[2 * j + 1];
     return p;
-}
-
-// A = U diag(w) V^T by one-sided Jacobi rotations on the columns (the method of cv::SVD), in registers.  Columns of U that belong to w = 0 are zero.
-__device__ inline void svd3(const double A[3][3], double U[3][3], double w[3], double V[3][3]) {
-    double B[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) { B[i][j] = A[i][j]; V[i][j] = i == j ? 1.0 : 0.0; }
-    for (int sweep = 0; sweep < kSvd3Sweeps; sweep++) {
-#pragma unroll
-        for (int pr = 0; pr < 3; pr++) {
-            const int i = pr == 2 ? 1 : 0, j = pr == 0 ? 1 : 2;
-            double a = 0, b = 0, g = 0;
-#pragma unroll
-            for (int k = 0; k < 3; k++) { a += B[k][i] * B[k][i]; b += B[k][j] * B[k][j]; g += B[k][i] * B[k][j]; }
-            if (fabs(g) > DBL_EPSILON * sqrt(a * b)) {
-                const double zeta = (b - a) / (2.0 * g);
-                const double t = (zeta < 0 ? -1.0 : 1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const double bi = B[k][i], bj = B[k][j];
-                    B[k][i] = c * bi - s * bj; B[k][j] = s * bi + c * bj;
-                    const double vi = V[k][i], vj = V[k][j];
-                    V[k][i] = c * vi - s * vj; V[k][j] = s * vi + c * vj;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        w[j] = sqrt(B[0][j] * B[0][j] + B[1][j] * B[1][j] + B[2][j] * B[2][j]);
-        const double inv = w[j] > 0 ? 1.0 / w[j] : 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; k++) U[k][j] = B[k][j] * inv;
-    }
 }
 
 // qr_solve (:860-950) for 6 rows: Householder QR, b <- Qt b, back substitution.  A singular column leaves X at zero (the reference returns with X unset).
