@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "common.h"
+#include "window_search.h"
 
 namespace oslam {
 
@@ -338,18 +339,8 @@ __global__ __launch_bounds__(kMatchThreads) void k_search_window(MatchCtx c, int
     if (local_nm) atomicAdd(&s_nm, local_nm);
     __syncthreads();
     if (c.check_ori) {
-        if (tid == 0) {   // ComputeThreeMaxima (:1601-1642)
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < kHistoLen; i++) {
-                const int s = s_hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                else if (s > max3) { max3 = s; ind3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
-            s_ind[0] = ind1; s_ind[1] = ind2; s_ind[2] = ind3;
-        }
+        static_assert(kHistoLen == oslam::kf_stage::kHistoLen, "three_maxima reads kHistoLen bins");
+        if (tid == 0) oslam::kf_stage::three_maxima(s_hist, s_ind);
         __syncthreads();
         int removed = 0;
         for (int j = tid; j < M; j += kMatchThreads) {
@@ -395,12 +386,7 @@ struct ProjectCtx {
     oslam_proj_query_t* out; int q_stride; int* n_q;
 };
 
-// cv::Mat 3x3*3x1+3x1 = one cv::gemm, flags==0, len==3: float accumulation (OpenCV small-matrix branch),
-// then (float)(t0*1.0 + c*1.0) in double
-__device__ __forceinline__ float gemm_row(const float* a, const float* x, float cc) {
-    const float t0 = a[0] * x[0] + a[1] * x[1] + a[2] * x[2];
-    return (float)((double)t0 + (double)cc);
-}
+using oslam::kf_stage::gemm_row;   // cv::Mat 3x3 * 3x1 + 3x1 as one cv::gemm
 
 __global__ __launch_bounds__(256) void k_project_last(ProjectCtx c) {
     const int b = blockIdx.y;

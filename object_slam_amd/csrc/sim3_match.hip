@@ -1,7 +1,8 @@
 // sim3_match.hip — ORBmatcher::SearchBySim3 (reference src/ORBmatcher.cc:1102-1326) for batches of independent keyframe pairs on gfx950
 // (include/oslam_hip.h, "SearchBySim3").  One launch, one workgroup per pair: the workgroup stages KF2 in LDS (keypoint xy, octave, descriptors and
-// the 64 x 48 cell table, as k_search_window of matcher.hip does), its threads stride over KF1's map points (:1148-1225), then it stages KF1 in the
-// same LDS and strides over KF2's map points (:1228-1305); vnMatch1 and vnMatch2 stay in LDS and the agreement (:1308-1323) follows after a barrier.
+// the 64 x 48 cell table: window_search.h, which also has the level, the window walk and the Hamming minimum), its threads stride over KF1's map points
+// (:1148-1225), then it stages KF1 in the same LDS and strides over KF2's map points (:1228-1305); vnMatch1 and vnMatch2 stay in LDS and the agreement
+// (:1308-1323) follows after a barrier.
 // No inter-workgroup synchronisation and no atomics on global memory: the result does not depend on the order the hardware runs anything in.
 // The roundings are those the header lists.  Product code; never includes oracle/.
 #include <climits>
@@ -9,11 +10,11 @@
 #include <mutex>
 
 #include "common.h"
-#include "keyframe_stage.h"
 #include "stage_layout.h"
+#include "window_search.h"
 
 using oslam::set_error;
-using namespace oslam::kf_stage;   // the staged keyframe, its grid constants and gemm_row
+using namespace oslam::kf_stage;   // the staged keyframe, the window search and gemm_row
 
 struct oslam_sim3_match {
     int device = 0, max_pairs = 0, max_kps = 0;
@@ -33,20 +34,7 @@ struct Sim3MatchArgs {
     oslam_sim3_match_rows_t rows;
     const int32_t* matched_in;
     int32_t* match12; int32_t* n_found;
-    float fx, fy, cx, cy;
-    float minX, minY, maxX, maxY, invW, invH;
-    float scale[OSLAM_MAX_LEVELS];
-    int nlevels; float logScale;
-};
-
-size_t lds_bytes(int ncap) {
-    // desc 32 + xy 8 + vnMatch1 4 + vnMatch2 4 + items 2 + octave 1 per keypoint, the cell table
-    return (size_t)ncap * 51 + (kGridCells + 1) * 4 + 16;
-}
-
-struct Lds : Staged {
-    int* m1;           // [ncap] vnMatch1 (kSkip: vbAlreadyMatched1)
-    int* m2;           // [ncap] vnMatch2 (kSkip: vbAlreadyMatched2)
+    WindowCam cam;
 };
 
 __device__ __forceinline__ bool finite_all(const float* v, int n) {
@@ -57,7 +45,7 @@ __device__ __forceinline__ bool finite_all(const float* v, int n) {
 
 // The target keyframe (rows off .. off + N - 1) into LDS
 __device__ __forceinline__ void stage_rows(const Sim3MatchArgs& a, const Lds& s, int off, int N, int* s_wtot) {
-    stage_target(s, a.rows.keysUn + off, a.rows.desc + (size_t)off * 32, N, Grid{a.minX, a.minY, a.invW, a.invH}, s_wtot);
+    stage_target(s, a.rows.keysUn + off, a.rows.desc + (size_t)off * 32, N, a.cam, s_wtot);
 }
 
 // One direction (:1148-1225 / :1228-1305): the map points of the source keyframe (rows off .. off + N - 1, pose Tsw) through (sR, t) into the staged target.
@@ -80,41 +68,15 @@ __device__ void search_direction(const Sim3MatchArgs& a, const Lds& s, const flo
         if (Pt[2] < 0.0f) continue;
         const float invz = (float)(1.0 / (double)Pt[2]);
         const float x = Pt[0] * invz, y = Pt[1] * invz;
-        const float u = a.fx * x + a.cx, v = a.fy * y + a.cy;
-        if (!(u >= a.minX && u < a.maxX && v >= a.minY && v < a.maxY)) continue;   // KeyFrame::IsInImage (src/KeyFrame.cc:610)
+        const float u = a.cam.fx * x + a.cam.cx, v = a.cam.fy * y + a.cam.cy;
+        if (!(u >= a.cam.minX && u < a.cam.maxX && v >= a.cam.minY && v < a.cam.maxY)) continue;   // KeyFrame::IsInImage (src/KeyFrame.cc:610)
         const float mfMax = a.rows.maxDistance[o];
         const float maxDistance = 1.2f * mfMax, minDistance = 0.8f * a.rows.minDistance[o];
         const float dist3D = (float)sqrt(((double)Pt[0] * (double)Pt[0] + (double)Pt[1] * (double)Pt[1]) + (double)Pt[2] * (double)Pt[2]);   // cv::norm
         if (dist3D < minDistance || dist3D > maxDistance) continue;
-        // MapPoint::PredictScale (src/MapPoint.cc:488-503) with the log convention of mappoint.hip
-        const float ratio = __fdiv_rn(mfMax, dist3D);
-        const float cl = ceilf(__fdiv_rn((float)log((double)ratio), a.logScale));
-        const int level = (cl >= 0.0f && cl < 2147483648.0f) ? min((int)cl, a.nlevels - 1) : 0;   // (what does not fit an int converts to INT_MIN on x86: level 0)
-        const float r = th * s_scale[level];
-        // KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:569-608)
-        const int nMinCellX = max(0, (int)floorf((u - a.minX - r) * a.invW));
-        const int nMaxCellX = min(kGridCols - 1, (int)ceilf((u - a.minX + r) * a.invW));
-        const int nMinCellY = max(0, (int)floorf((v - a.minY - r) * a.invH));
-        const int nMaxCellY = min(kGridRows - 1, (int)ceilf((v - a.minY + r) * a.invH));
-        if (nMinCellX >= kGridCols || nMaxCellX < 0 || nMinCellY >= kGridRows || nMaxCellY < 0) continue;
-        const uint4 q0 = ((const uint4*)(a.rows.mp_desc + o * 32))[0], q1 = ((const uint4*)(a.rows.mp_desc + o * 32))[1];
-        int bestDist = INT_MAX, bestIdx = -1;
-        for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
-            const int c0 = ix * kGridRows + nMinCellY;
-            const int st = c0 > 0 ? s.cell[c0 - 1] : 0, en = s.cell[ix * kGridRows + nMaxCellY];
-            for (int q = st; q < en; q++) {   // cells iy = min .. max of a column are contiguous
-                const int k = s.items[q];
-                const float2 p = s.xy[k];
-                if (!(fabsf(p.x - u) < r && fabsf(p.y - v) < r)) continue;
-                const int oct = s.oct[k];
-                if (oct < level - 1 || oct > level) continue;
-                const uint4 d0 = ((const uint4*)(s.desc + k * 8))[0], d1 = ((const uint4*)(s.desc + k * 8))[1];
-                const int dist = __popc(q0.x ^ d0.x) + __popc(q0.y ^ d0.y) + __popc(q0.z ^ d0.z) + __popc(q0.w ^ d0.w) + __popc(q1.x ^ d1.x) + __popc(q1.y ^ d1.y) +
-                                 __popc(q1.z ^ d1.z) + __popc(q1.w ^ d1.w);
-                if (dist < bestDist) { bestDist = dist; bestIdx = k; }
-            }
-        }
-        if (bestDist <= kThHigh) m_src[i] = bestIdx;
+        const int level = predict_level(mfMax, dist3D, a.cam);
+        const Nearest best = nearest_in_window<-1, 0>(s, a.cam, u, v, th * s_scale[level], level, a.rows.mp_desc + o * 32);
+        if (best.dist <= kThHigh) m_src[i] = best.idx;
     }
 }
 
@@ -136,14 +98,9 @@ __global__ __launch_bounds__(kThreads) void k_search_by_sim3(Sim3MatchArgs a) {
     }
 
     extern __shared__ __align__(16) uint8_t smem[];
-    Lds s;
-    s.desc = (uint32_t*)smem;
-    s.xy = (float2*)(s.desc + (size_t)a.ncap * 8);
-    s.m1 = (int*)(s.xy + a.ncap);
-    s.m2 = s.m1 + a.ncap;
-    s.cell = s.m2 + a.ncap;
-    s.items = (uint16_t*)(s.cell + kGridCells + 1);
-    s.oct = (int8_t*)(s.items + a.ncap);
+    const Lds s = carve(smem, a.ncap);
+    int* const m1 = s.v0;   // [ncap] vnMatch1 (kSkip: vbAlreadyMatched1)
+    int* const m2 = s.v1;   // [ncap] vnMatch2 (kSkip: vbAlreadyMatched2)
     __shared__ int s_wtot[kThreads / 64];
     __shared__ float s_scale[OSLAM_MAX_LEVELS];
     __shared__ int s_nfound;
@@ -162,26 +119,26 @@ __global__ __launch_bounds__(kThreads) void k_search_by_sim3(Sim3MatchArgs a) {
     for (int i = 0; i < 3; i++) t21[i] = -(sR21[3 * i] * P.t12[0] + sR21[3 * i + 1] * P.t12[1] + sR21[3 * i + 2] * P.t12[2]);
 
     // vbAlreadyMatched1 / 2 (:1129-1142), vnMatch1 / 2 (:1144-1145)
-    if (tid < OSLAM_MAX_LEVELS) s_scale[tid] = a.scale[tid];
+    if (tid < OSLAM_MAX_LEVELS) s_scale[tid] = a.cam.scale[tid];
     if (tid == 0) s_nfound = 0;
-    for (int i = tid; i < n2; i += kThreads) s.m2[i] = -1;
+    for (int i = tid; i < n2; i += kThreads) m2[i] = -1;
     __syncthreads();
     for (int i = tid; i < n1; i += kThreads) {
         const int idx2 = a.matched_in ? a.matched_in[out_off + i] : -1;
-        s.m1[i] = idx2 != -1 ? kSkip : -1;
-        if (idx2 >= 0 && idx2 < n2) s.m2[idx2] = kSkip;   // (-2, other negative values and >= n2: matched, but not a keypoint of KF2)
+        m1[i] = idx2 != -1 ? kSkip : -1;
+        if (idx2 >= 0 && idx2 < n2) m2[idx2] = kSkip;   // (-2, other negative values and >= n2: matched, but not a keypoint of KF2)
     }
     // (stage_target begins with a barrier)
     stage_rows(a, s, off2, n2, s_wtot);
-    search_direction(a, s, s_scale, off1, n1, P.T1w, sR21, t21, P.th, s.m1);
+    search_direction(a, s, s_scale, off1, n1, P.T1w, sR21, t21, P.th, m1);
     stage_rows(a, s, off1, n1, s_wtot);
-    search_direction(a, s, s_scale, off2, n2, P.T2w, sR12, P.t12, P.th, s.m2);
+    search_direction(a, s, s_scale, off2, n2, P.T2w, sR12, P.t12, P.th, m2);
     __syncthreads();
     // agreement (:1308-1323)
     int found = 0;
     for (int i1 = tid; i1 < n1; i1 += kThreads) {
-        const int idx2 = s.m1[i1];
-        const bool ok = idx2 >= 0 && s.m2[idx2] == i1;
+        const int idx2 = m1[i1];
+        const bool ok = idx2 >= 0 && m2[idx2] == i1;
         match12[i1] = ok ? idx2 : -1;
         found += ok ? 1 : 0;
     }
@@ -195,9 +152,7 @@ int check_call(const char* fn, const oslam_sim3_match* h, int n_pairs, const osl
     if (!h || !rows || !cam || !bounds || !scaleFactors) { set_error("%s: NULL argument", fn); return OSLAM_E_INVALID; }
     if (n_pairs < 0 || rows->n_rows < 0 || n_out < 0) { set_error("%s: %d pairs, %d rows, %d output rows: none may be negative", fn, n_pairs, rows->n_rows, n_out); return OSLAM_E_CAPACITY; }
     if (n_pairs > h->max_pairs) { set_error("%s: %d pairs exceed the handle's %d", fn, n_pairs, h->max_pairs); return OSLAM_E_CAPACITY; }
-    if (nlevels < 1 || nlevels > OSLAM_MAX_LEVELS) { set_error("%s: nlevels = %d outside [1, %d]", fn, nlevels, OSLAM_MAX_LEVELS); return OSLAM_E_INVALID; }
-    if (!(bounds[2] > bounds[0]) || !(bounds[3] > bounds[1])) { set_error("%s: empty image bounds", fn); return OSLAM_E_INVALID; }
-    if (!(logScaleFactor > 0.0f)) { set_error("%s: logScaleFactor must be positive", fn); return OSLAM_E_INVALID; }
+    OSLAM_CHECK(check_window(fn, bounds, nlevels, logScaleFactor));
     if (rows->n_rows > 0 && (!rows->keysUn || !rows->desc || !rows->has_mp || !rows->Xw || !rows->mp_desc || !rows->maxDistance || !rows->minDistance)) {
         set_error("%s: a per-keypoint array is NULL", fn);
         return OSLAM_E_INVALID;
@@ -218,22 +173,15 @@ int oslam_sim3_match_create(oslam_sim3_match_t** out, int max_pairs, int max_key
     if (!out) { set_error("oslam_sim3_match_create: out is NULL"); return OSLAM_E_INVALID; }
     *out = nullptr;
     if (max_pairs < 1 || max_keypoints < 1) { set_error("oslam_sim3_match_create: bad argument"); return OSLAM_E_INVALID; }
-    if (max_keypoints > kMaxKps) {
-        set_error("oslam_sim3_match_create: max_keypoints %d > %d (one keyframe's keypoints, descriptors and grid, and both match vectors, must fit 160 KiB of LDS)", max_keypoints, kMaxKps);
-        return OSLAM_E_INVALID;
-    }
+    OSLAM_CHECK(check_max_keypoints("oslam_sim3_match_create", max_keypoints, "one keyframe's", "both match vectors"));
     const int ndev = oslam_device_count();
     if (ndev <= 0) return oslam::no_device("oslam_sim3_match_create");
     if (device < 0 || device >= ndev) { set_error("oslam_sim3_match_create: device out of range"); return OSLAM_E_INVALID; }
     OSLAM_HIP_CHECK(hipSetDevice(device));
     oslam_sim3_match* h = new oslam_sim3_match;
     h->device = device; h->max_pairs = max_pairs; h->max_kps = max_keypoints; h->lds = lds_bytes(max_keypoints);
-    const hipError_t e = hipFuncSetAttribute((const void*)k_search_by_sim3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(kMaxKps));   // (the attribute belongs to the kernel, not to the handle)
-    if (e != hipSuccess) {
-        set_error("oslam_sim3_match_create: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-        delete h;
-        return OSLAM_E_HIP;
-    }
+    const int rc = allow_full_lds("oslam_sim3_match_create", {(const void*)k_search_by_sim3});
+    if (rc != OSLAM_OK) { delete h; return rc; }
     *out = h;
     return OSLAM_OK;
 }
@@ -249,12 +197,7 @@ int oslam_match_search_by_sim3_batch_device(oslam_sim3_match_t* h, int n_pairs, 
     Sim3MatchArgs a;
     a.pairs = d_pairs; a.n_pairs = n_pairs; a.n_rows = rows->n_rows; a.n_out = n_out; a.ncap = h->max_kps;
     a.rows = *rows; a.matched_in = d_matched_in; a.match12 = d_match12; a.n_found = d_n_found;
-    a.fx = cam->fx; a.fy = cam->fy; a.cx = cam->cx; a.cy = cam->cy;
-    a.minX = bounds[0]; a.minY = bounds[1]; a.maxX = bounds[2]; a.maxY = bounds[3];
-    a.invW = (float)kGridCols / (float)(a.maxX - a.minX);   // src/Frame.cc:160-161
-    a.invH = (float)kGridRows / (float)(a.maxY - a.minY);
-    for (int i = 0; i < OSLAM_MAX_LEVELS; i++) a.scale[i] = i < nlevels ? scaleFactors[i] : 0.f;
-    a.nlevels = nlevels; a.logScale = logScaleFactor;
+    fill_window_cam(a.cam, cam, bounds, scaleFactors, nlevels, logScaleFactor);
     hipLaunchKernelGGL(k_search_by_sim3, dim3(n_pairs), dim3(kThreads), h->lds, (hipStream_t)stream, a);
     OSLAM_HIP_CHECK(hipGetLastError());
     return OSLAM_OK;

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import KP_DTYPE, Handle, check, device_call, lib, optptr, ptr
-from .matcher import Camera
+from ._proj_common import _camera_args, _consecutive, _pack, _rows_of
 
 MAX_KEYPOINTS = 2400
 REFERENCE_TH = 7.5   # src/LoopClosing.cc:324
@@ -51,7 +51,7 @@ def pack_pairs(n1, off1, n2, off2, s12, R12, t12, T1w, T2w, th=REFERENCE_TH, out
     n = len(n1)
     pr = np.zeros(n, PAIR_DTYPE)
     pr["n1"], pr["off1"], pr["n2"], pr["off2"] = n1, np.asarray(off1, np.int32), np.asarray(n2, np.int32), np.asarray(off2, np.int32)
-    pr["out_off"] = (np.concatenate([[0], np.cumsum(np.maximum(n1, 0))[:-1]]) if n else 0) if out_off is None else np.asarray(out_off, np.int32)
+    pr["out_off"] = _consecutive(n1) if out_off is None else np.asarray(out_off, np.int32)
     pr["s12"] = np.asarray(s12, np.float32)
     pr["R12"] = np.asarray(R12, np.float32).reshape(n, 3, 3)
     pr["t12"] = np.asarray(t12, np.float32).reshape(n, 3)
@@ -63,13 +63,7 @@ def pack_pairs(n1, off1, n2, off2, s12, R12, t12, T1w, T2w, th=REFERENCE_TH, out
 
 def pack_rows(rows):
     """The seven per-keypoint arrays of `rows` (a dict with ROW_KEYS) as contiguous arrays of the ABI's types."""
-    out = {}
-    for k in ROW_KEYS:
-        dt, shape = _ROW_TYPES[k]
-        out[k] = np.ascontiguousarray(rows[k], dt).reshape((-1,) + shape)
-    n = len(out["has_mp"])
-    assert all(len(v) == n for v in out.values()), "the per-keypoint arrays differ in length"
-    return out
+    return _pack(rows, ROW_KEYS, _ROW_TYPES, "keypoint")
 
 
 class Sim3Matcher(Handle):
@@ -87,17 +81,14 @@ class Sim3Matcher(Handle):
         rows = pack_rows(rows)
         n, n_rows = len(pairs), len(rows["has_mp"])
         if n_out is None:
-            n_out = len(match12) if match12 is not None else len(matched_in) if matched_in is not None else int((pairs["out_off"] + np.maximum(pairs["n1"], 0)).max()) if n else 0
+            n_out = len(match12) if match12 is not None else len(matched_in) if matched_in is not None else _rows_of(pairs, "n1", "out_off")
         if matched_in is not None:
             matched_in = np.ascontiguousarray(matched_in, np.int32)
             assert matched_in.size == n_out
         match12 = np.full(n_out, -1, np.int32) if match12 is None else match12
         n_found = np.zeros(n, np.int32) if n_found is None else n_found
         assert match12.dtype == np.int32 and match12.size == n_out and match12.flags.c_contiguous and n_found.dtype == np.int32 and n_found.size == n and n_found.flags.c_contiguous
-        c = np.asarray(cam, np.float32).reshape(-1)
-        camera = Camera(c[0], c[1], c[2], c[3], 0.0, 0.0)
-        bnd = np.ascontiguousarray(bounds, np.float32).reshape(4)
-        sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+        camera, bnd, sf = _camera_args(cam, bounds, scale_factors)
         def args(a):
             r = Rows(n_rows, *[a(rows[k]) for k in ROW_KEYS])   # (byref keeps r alive until the call has returned)
             return (self.h, n, a(pairs), C.byref(r), n_out, a(matched_in), C.addressof(camera), ptr(bnd), ptr(sf), len(sf), float(log_scale_factor), a(match12), a(n_found))

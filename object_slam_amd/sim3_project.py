@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import KP_DTYPE, Handle, check, device_call, lib, optptr, ptr
-from .matcher import Camera
+from ._proj_common import _camera_args, _pack, _problem_head, _rows_of
 
 MAX_KEYPOINTS = 2400
 SEARCH_TH, FUSE_TH = 10.0, 4.0   # src/LoopClosing.cc:376, :600
@@ -55,31 +55,12 @@ def _bind(L):
     return L
 
 
-def _consecutive(n):
-    return np.concatenate([[0], np.cumsum(np.maximum(n, 0))[:-1]]) if len(n) else np.zeros(0, np.int64)
-
-
 def pack_problems(n_kp, kp_off, n_pts, pt_off, Scw, th, kp_out_off=None, pt_out_off=None):
     """PROBLEM_DTYPE records.  kp_out_off / pt_out_off default to consecutive output rows, n_kp / n_pts per problem in the order given."""
-    n_kp, n_pts = np.asarray(n_kp, np.int32).reshape(-1), np.asarray(n_pts, np.int32).reshape(-1)
-    n = len(n_kp)
-    pr = np.zeros(n, PROBLEM_DTYPE)
-    pr["n_kp"], pr["kp_off"], pr["n_pts"], pr["pt_off"] = n_kp, np.asarray(kp_off, np.int32), n_pts, np.asarray(pt_off, np.int32)
-    pr["kp_out_off"] = _consecutive(n_kp) if kp_out_off is None else np.asarray(kp_out_off, np.int32)
-    pr["pt_out_off"] = _consecutive(n_pts) if pt_out_off is None else np.asarray(pt_out_off, np.int32)
-    pr["Scw"] = np.asarray(Scw, np.float32).reshape(n, 4, 4)
+    pr = _problem_head(PROBLEM_DTYPE, n_kp, kp_off, n_pts, pt_off, kp_out_off, pt_out_off)
+    pr["Scw"] = np.asarray(Scw, np.float32).reshape(len(pr), 4, 4)
     pr["th"] = np.asarray(th, np.float32)
     return pr
-
-
-def _pack(rows, keys, types, what):
-    out = {}
-    for k in keys:
-        dt, shape = types[k]
-        out[k] = np.ascontiguousarray(rows[k], dt).reshape((-1,) + shape)
-    n = len(out[keys[0]])
-    assert all(len(v) == n for v in out.values()), "the per-%s arrays differ in length" % what
-    return out
 
 
 def pack_kf_rows(rows):
@@ -90,10 +71,6 @@ def pack_kf_rows(rows):
 def pack_pt_rows(rows):
     """The five per-point arrays of `rows` (a dict with PT_KEYS) as contiguous arrays of the ABI's types."""
     return _pack(rows, PT_KEYS, _PT_TYPES, "point")
-
-
-def _rows_of(pr, n_field, off_field):
-    return int((pr[off_field].astype(np.int64) + np.maximum(pr[n_field], 0)).max()) if len(pr) else 0
 
 
 class Sim3Projector(Handle):
@@ -111,10 +88,7 @@ class Sim3Projector(Handle):
             assert skip.size == n_pt_out
         for o, size in zip(outs, ([n_pt_out, n_pt_out, n] if fuse else [n_kp_out, n, n])):
             assert o is None or (o.dtype == np.int32 and o.size == size and o.flags.c_contiguous)
-        c = np.asarray(cam, np.float32).reshape(-1)
-        camera = Camera(c[0], c[1], c[2], c[3], 0.0, 0.0)
-        bnd = np.ascontiguousarray(bounds, np.float32).reshape(4)
-        sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+        camera, bnd, sf = _camera_args(cam, bounds, scale_factors)
         name = "oslam_match_fuse_sim3_batch" if fuse else "oslam_match_search_by_projection_sim3_batch"
 
         def args(a):

@@ -240,10 +240,11 @@ def hand_cases():
 
     # a window at level 7 (radius 35.8) with ten keypoints, all within ORBdist of all ten slots: keypoint j is j + 1 bits from the common descriptor, so slot j, which
     # finds keypoints 0 .. j - 1 claimed, takes keypoint j: a chain of ten, in windows with more candidates than the candidate cache of the kernel holds (7)
+    # (window_7: the last count the cache holds; window_8: the first that overflows it)
     B = rd()
-    n = CACHE_CASE_CANDIDATES
-    kps = [kpt(300 + 6 * j - 27, 300 + (j * 37) % 50 - 25, 7 if j % 2 else 6, fb(B, range(j + 1))) for j in range(n)]
-    cases.append(_case("big_window", kps, [pt(300, 300, B, level=7) for _ in range(n)], dict(matched=list(range(n)), n=n, removed=0)))
+    for name, n in (("window_7", 7), ("window_8", 8), ("big_window", CACHE_CASE_CANDIDATES)):
+        kps = [kpt(300 + 6 * j - 27, 300 + (j * 37) % 50 - 25, 7 if j % 2 else 6, fb(B, range(j + 1))) for j in range(n)]
+        cases.append(_case(name, kps, [pt(300, 300, B, level=7) for _ in range(n)], dict(matched=list(range(n)), n=n, removed=0)))
 
     # slot 0 takes keypoint 0 with rot = 90 (bin 3); slots 2 .. 12 take keypoints 1 .. 11 with rot = 0 (bin 0).  Bin sizes 11 and 1: 1 < 0.1f * 11, so the match
     # of slot 0 is removed.  Slot 1 wanted keypoint 0 too (distance 3, nothing else in its window) and was denied it during the loop: it stays without a

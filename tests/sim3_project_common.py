@@ -282,10 +282,11 @@ def hand_cases():
 
     # a window at level 7 (radius 35.8) with ten keypoints, all within TH_LOW of all ten points: keypoint j is j + 1 bits from the common descriptor, so point j, which
     # finds keypoints 0 .. j - 1 claimed, takes keypoint j: a chain of ten, in windows with more candidates than a candidate cache of the kernel holds
+    # (window_7: the last count the cache holds; window_8: the first that overflows it)
     B = rd()
-    n = CACHE_CASE_CANDIDATES
-    kps = [kpt(300 + 6 * j - 27, 300 + (j * 37) % 50 - 25, 7 if j % 2 else 6, fb(B, range(j + 1))) for j in range(n)]
-    cases.append(_case("big_window", "search", kps, [pt(300, 300, B, level=7) for _ in range(n)], dict(matched=list(range(n)), n=n)))
+    for name, n in (("window_7", 7), ("window_8", 8), ("big_window", CACHE_CASE_CANDIDATES)):
+        kps = [kpt(300 + 6 * j - 27, 300 + (j * 37) % 50 - 25, 7 if j % 2 else 6, fb(B, range(j + 1))) for j in range(n)]
+        cases.append(_case(name, "search", kps, [pt(300, 300, B, level=7) for _ in range(n)], dict(matched=list(range(n)), n=n)))
 
     # scw = 1, 0.5 and 2 with exact entries: Scw = s [I | t], t = (0.25, -0.5, 1); the same keyframe and points give the same answer
     t = (0.25, -0.5, 1.0)

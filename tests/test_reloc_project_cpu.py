@@ -52,6 +52,11 @@ def test_hand_cases_are_what_their_comments_say():
     det = {}
     rpc.run_problem(c, det)
     assert all(len(cl) == n for cl in det["cands"]) and rpc.replay_passes(c["frame"]["has_mp"], det["cands"])[0] >= n
+    for m in (7, 8):   # the cache boundary: every slot has exactly m candidates (7: the last count cached, 8: the first that overflows) and the replay takes m + 1 passes
+        c = CASES["window_%d" % m]
+        det = {}
+        rpc.run_problem(c, det)
+        assert len(det["cands"]) == m and all(len(cl) == m for cl in det["cands"]) and rpc.replay_passes(c["frame"]["has_mp"], det["cands"])[0] == m + 1
     c = CASES["removed_match_still_blocks"]
     assert pop(c["pts"]["desc"][1], c["frame"]["desc"][0]) == 3 and rpc.rot_bin(90.0, 0.0) == 3
     c = CASES["tie"]

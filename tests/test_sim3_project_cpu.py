@@ -43,6 +43,11 @@ def test_hand_cases_are_what_their_comments_say():
     c = CASES["big_window"]
     n = spc.CACHE_CASE_CANDIDATES
     assert n > 7 and all(pop(c["pts"]["desc"][i], c["kf"]["desc"][k]) == k + 1 for i in range(n) for k in range(n))
+    for m in (7, 8):   # the cache boundary: n keypoints against n points, every one a candidate (within TH_LOW, octave 6 or 7) of every point
+        c = CASES["window_%d" % m]
+        assert len(c["kf"]["state"]) == len(c["skip"]) == m and not c["kf"]["state"].any() and set(c["kf"]["keysUn"]["octave"].tolist()) == {6, 7}
+        assert max(np.abs(c["kf"]["keysUn"]["x"] - 300).max(), np.abs(c["kf"]["keysUn"]["y"] - 300).max()) < 35.0   # inside the window of radius 35.8
+        assert all(pop(c["pts"]["desc"][i], c["kf"]["desc"][k]) == k + 1 <= 50 for i in range(m) for k in range(m))
     assert np.float32(10.0) * spc.SF[7] > 35.0 and len(set(zip(*[v.tolist() for v in smc._grid_cells(c["kf"]["keysUn"], spc.BOUNDS, np.float32(0.1), np.float32(0.1))]))) > 4
     c = CASES["distance"]
     assert c["pts"]["Xw"][0, 2] == np.float32(1.2) * np.float32(3.0) and c["pts"]["Xw"][2, 2] == np.float32(0.8) * np.float32(5.0) == np.float32(4.0)
