@@ -48,22 +48,6 @@ struct Vocab {
     }
 };
 
-struct Timer {
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    long long c0 = thread_cpu_ns();
-    double cpu = 0;   // core-seconds of the last lap: this thread's CPU time + what the workers spent on its batches
-    double lap() {
-        auto t1 = std::chrono::steady_clock::now();
-        const double d = std::chrono::duration<double>(t1 - t0).count();
-        t0 = t1;
-        const long long c1 = thread_cpu_ns();
-        CpuAccount* a = thread_account();
-        cpu = 1e-9 * (double)((c1 - c0) + (a ? a->worker_ns.exchange(0, std::memory_order_relaxed) : 0));
-        c0 = c1;
-        return d;
-    }
-};
-
 // flat FeatureVector views for the BoW matchers (see oslam_hip.h): side 1 = (node asc, index order) list, side 2 = CSR over node ids
 struct BowViews {
     std::vector<int32_t> q_idx; std::vector<uint32_t> q_node;
@@ -298,7 +282,7 @@ static bool unproject_frame(const Ctx& c, const Frame& f, int i, float out[3]) {
 }
 
 // KeyFrame::KeyFrame(Frame&, ...) (src/KeyFrame.cc:30-58)
-static int new_keyframe(Seq& s, const Frame& f, float thDepth) {
+static int new_keyframe(Seq& s, const Frame& f) {
     s.mapVersion++;
     s.map.kfs.emplace_back();
     KeyFrm& k = s.map.kfs.back();
@@ -318,7 +302,6 @@ static int new_keyframe(Seq& s, const Frame& f, float thDepth) {
     s.counter.resize(s.map.kfs.size() + 8, 0);
     s.st[1]++;
     s.pendingKF.push_back(k.id);
-    (void)thDepth;
     s.map.jr_new_kf(k.id);
     return k.id;
 }
@@ -514,7 +497,42 @@ static void create_stereo_points(Ctx& c, Seq& s, Frame& f, int kf, bool all) {
     }
 }
 
-// Tracking::UpdateLocalKeyFrames (:1496-1604) + UpdateLocalPoints (:1470-1493)
+// mnTrackReferenceForFrame of the map points as a per-sequence BITMAP, cleared per walk: a walk visits 20-80 k keyframe slots and most of them hit an already
+// marked point; one bit per point id keeps the marks of a whole map (~20 k points) in 2.5 KB — first-level cache — where a stamped int per point was an 80 KB
+// array that every other sequence's walk had evicted.
+static void clear_point_marks(Seq& s) {
+    const size_t nw = (s.map.mps.size() + 63) / 64, np = s.map.mps.size();
+    if (s.mpMark.size() < nw) s.mpMark.resize(nw + nw / 2 + 4, 0ull);
+    if (s.mpPos.size() < np) s.mpPos.resize(np + np / 2 + 64, -1);
+    std::fill(s.mpMark.begin(), s.mpMark.end(), 0ull);
+}
+
+// Tracking::UpdateLocalPoints (:1470-1493): the points of the local keyframes in list order, each once.  A bad point is marked too (it is never pushed either
+// way), which leaves the list unchanged.
+static void local_points_walk(Seq& s) {
+    Map& m = s.map;
+    clear_point_marks(s);
+    uint64_t* mark = s.mpMark.data();
+    int* pos = s.mpPos.data();
+    s.localMPs.clear();
+    for (int k : s.localKFs) {
+        const KeyFrm& kf = m.kfs[k];
+        const int* kmp = kf.mp.data();
+        for (int i = 0; i < kf.N; i++) {
+            const int p = kmp[i];
+            if (p < 0) continue;
+            const uint64_t bit = 1ull << (p & 63);
+            uint64_t& wd = mark[p >> 6];
+            if (wd & bit) continue;
+            wd |= bit;
+            if (!m.pBad[p]) { pos[p] = (int)s.localMPs.size(); s.localMPs.push_back(p); }
+            else pos[p] = -1;
+        }
+    }
+    s.locKFs = s.localKFs; s.locVersion = s.mapVersion; s.locWalkFrame = s.cur->id;
+}
+
+// Tracking::UpdateLocalKeyFrames (:1496-1604), then UpdateLocalPoints unless the cached list stands or the table delivers it
 static void update_local_map(Seq& s) {
     Map& m = s.map;
     Frame& f = *s.cur;
@@ -597,78 +615,16 @@ static void update_local_map(Seq& s) {
     s.locReused = s.locVersion == s.mapVersion && s.locWalkFrame >= 0 && s.localKFs == s.locKFs;
     if (s.locReused) return;   // same ordered keyframe list over an unchanged map: the walk below would rebuild the same list
     if (s.locListDev) { s.locListPending = true; return; }   // (the table walks the keyframes' lists where they are resident: stage_local_map_lists)
-    // mnTrackReferenceForFrame of the map points as a per-sequence BITMAP, cleared per walk: the loop below visits 20-80 k keyframe slots and most of them hit
-    // an already marked point; one bit per point id keeps the marks of a whole map (~20 k points) in 2.5 KB — first-level cache — where a stamped int per point
-    // was an 80 KB array that every other sequence's walk had evicted.  A bad point is marked too (it is never pushed either way), which leaves the list unchanged.
-    {
-        const size_t nw = (m.mps.size() + 63) / 64;
-        if (s.mpMark.size() < nw) s.mpMark.resize(nw + nw / 2 + 4, 0ull);
-        if (s.mpPos.size() < m.mps.size()) s.mpPos.resize(m.mps.size() + m.mps.size() / 2 + 64, -1);
-        std::fill(s.mpMark.begin(), s.mpMark.end(), 0ull);
-    }
-    uint64_t* mark = s.mpMark.data();
-    int* pos = s.mpPos.data();
-    s.localMPs.clear();
-    for (int k : s.localKFs) {
-        const KeyFrm& kf = m.kfs[k];
-        const int* kmp = kf.mp.data();
-        for (int i = 0; i < kf.N; i++) {
-            const int p = kmp[i];
-            if (p < 0) continue;
-            const uint64_t bit = 1ull << (p & 63);
-            uint64_t& wd = mark[p >> 6];
-            if (wd & bit) continue;
-            wd |= bit;
-            if (!m.pBad[p]) { pos[p] = (int)s.localMPs.size(); s.localMPs.push_back(p); }
-            else pos[p] = -1;
-        }
-    }
-    s.locKFs = s.localKFs; s.locVersion = s.mapVersion; s.locWalkFrame = f.id;
+    local_points_walk(s);
 }
 
-// the walk above, on the host, for one sequence whose list the table could not deliver (overflow) — and the bookkeeping around a delivered list
-static void local_points_walk_host(Seq& s) {
-    const bool dev = s.locListDev;
-    s.locListDev = false; s.locListPending = false;
-    // (re-enter update_local_map's tail: the vote and the keyframe list are done; votePts were swapped by that call, so only the walk is repeated here)
-    Map& m = s.map;
-    Frame& f = *s.cur;
-    const size_t nw = (m.mps.size() + 63) / 64;
-    if (s.mpMark.size() < nw) s.mpMark.resize(nw + nw / 2 + 4, 0ull);
-    if (s.mpPos.size() < m.mps.size()) s.mpPos.resize(m.mps.size() + m.mps.size() / 2 + 64, -1);
-    std::fill(s.mpMark.begin(), s.mpMark.end(), 0ull);
-    uint64_t* mark = s.mpMark.data();
-    int* pos = s.mpPos.data();
-    s.localMPs.clear();
-    for (int k : s.localKFs) {
-        const KeyFrm& kf = m.kfs[k];
-        const int* kmp = kf.mp.data();
-        for (int i = 0; i < kf.N; i++) {
-            const int p = kmp[i];
-            if (p < 0) continue;
-            const uint64_t bit = 1ull << (p & 63);
-            uint64_t& wd = mark[p >> 6];
-            if (wd & bit) continue;
-            wd |= bit;
-            if (!m.pBad[p]) { pos[p] = (int)s.localMPs.size(); s.localMPs.push_back(p); }
-            else pos[p] = -1;
-        }
-    }
-    s.locKFs = s.localKFs; s.locVersion = s.mapVersion; s.locWalkFrame = f.id;
-    s.locListDev = dev;
-}
 static void local_points_from_list(Seq& s, int n) {   // s.localMPs[0 .. n) came from the table: marks and positions of the listed points (a bad point is in neither)
-    Map& m = s.map;
-    Frame& f = *s.cur;
-    const size_t nw = (m.mps.size() + 63) / 64;
-    if (s.mpMark.size() < nw) s.mpMark.resize(nw + nw / 2 + 4, 0ull);
-    if (s.mpPos.size() < m.mps.size()) s.mpPos.resize(m.mps.size() + m.mps.size() / 2 + 64, -1);
-    std::fill(s.mpMark.begin(), s.mpMark.end(), 0ull);
+    clear_point_marks(s);
     s.localMPs.resize(n);
     uint64_t* mark = s.mpMark.data();
     int* pos = s.mpPos.data();
     for (int q = 0; q < n; q++) { const int p = s.localMPs[q]; mark[p >> 6] |= 1ull << (p & 63); pos[p] = q; }
-    s.locKFs = s.localKFs; s.locVersion = s.mapVersion; s.locWalkFrame = f.id;
+    s.locKFs = s.localKFs; s.locVersion = s.mapVersion; s.locWalkFrame = s.cur->id;
     s.locListPending = false;
 }
 
@@ -676,16 +632,14 @@ static void local_points_from_list(Seq& s, int n) {   // s.localMPs[0 .. n) came
 static void fill_pose_job(Ctx& c, Seq& s, int si, oslam_job_pose_t& j) {
     Frame& f = *s.cur;
     const int N = f.N;
-    if (c.residentPts) {   // the table reads the map points' positions from its records and the keypoints from the frame it still holds: nothing to gather
-        s.jOutlier.assign(N, 0);
-        j.slot = si; j.N = N;
-        memcpy(j.Tcw_in, f.pose.Tcw.m, 64);
-        j.Xw = nullptr; j.obs = nullptr; j.invSigma2 = nullptr; j.has_mp = nullptr; j.mp_ids = f.mp.data();
-        j.outlier = s.jOutlier.data(); j.n_inliers = 0;
-        memcpy(j.Tcw_out, f.pose.Tcw.m, 64);
-        return;
-    }
-    s.jXw.assign((size_t)N * 3, 0.f); s.jObs.resize((size_t)N * 3); s.jInv.resize(N); s.jHas.assign(N, 0); s.jOutlier.assign(N, 0);
+    s.jOutlier.assign(N, 0);
+    j.slot = si; j.N = N;
+    memcpy(j.Tcw_in, f.pose.Tcw.m, 64);
+    j.outlier = s.jOutlier.data(); j.n_inliers = 0;
+    memcpy(j.Tcw_out, f.pose.Tcw.m, 64);
+    j.Xw = nullptr; j.obs = nullptr; j.invSigma2 = nullptr; j.has_mp = nullptr; j.mp_ids = f.mp.data();
+    if (c.residentPts) return;   // the table reads the map points' positions from its records and the keypoints from the frame it still holds: nothing to gather
+    s.jXw.assign((size_t)N * 3, 0.f); s.jObs.resize((size_t)N * 3); s.jInv.resize(N); s.jHas.assign(N, 0);
     for (int i = 0; i < N; i++) {
         prefetch_ahead(s.map.mps, f.mp, i, N);
         s.jObs[(size_t)i * 3] = f.keysUn[i].x; s.jObs[(size_t)i * 3 + 1] = f.keysUn[i].y; s.jObs[(size_t)i * 3 + 2] = f.uRight[i];
@@ -697,11 +651,7 @@ static void fill_pose_job(Ctx& c, Seq& s, int si, oslam_job_pose_t& j) {
             s.jXw[(size_t)i * 3] = x[0]; s.jXw[(size_t)i * 3 + 1] = x[1]; s.jXw[(size_t)i * 3 + 2] = x[2];
         }
     }
-    j.slot = si; j.N = N;
-    memcpy(j.Tcw_in, f.pose.Tcw.m, 64);
     j.Xw = s.jXw.data(); j.obs = s.jObs.data(); j.invSigma2 = s.jInv.data(); j.has_mp = s.jHas.data(); j.mp_ids = nullptr;
-    j.outlier = s.jOutlier.data(); j.n_inliers = 0;
-    memcpy(j.Tcw_out, f.pose.Tcw.m, 64);
 }
 
 // after PoseOptimization in TrackWithMotionModel / TrackReferenceKeyFrame: discard outliers (:858-879, :981-1008)
@@ -725,9 +675,7 @@ static bool finish_initial_pose(Seq& s, const oslam_job_pose_t& j) {
     return nmatchesMap >= 10;
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// Local mapping for the sequences that inserted a keyframe this step (LocalMapping::Run, src/LocalMapping.cc:48-113)
-// ------------------------------------------------------------------------------------------------------------------
+// ======== Local mapping for the sequences that inserted a keyframe this step (LocalMapping::Run, src/LocalMapping.cc:48-113) ========
 static void map_point_culling(Seq& s) {   // :171-206
     Map& m = s.map;
     const int cur = s.curKF;
@@ -856,38 +804,55 @@ static void fuse_apply_pairs(Seq& s, int k, const int32_t* pairs, int n) {
     for (int q = 0; q < n; q++) fuse_apply_one(s, k, pairs[2 * q], pairs[2 * q + 1], nullptr);
 }
 
+// ---- what the two passes of a step (tracking: TrackPass, local mapping: LmPass) share: handle, worker pool, stage timer ----
+// The time since the last charge goes to oslam_slam_stage_seconds / _cpu_seconds: charge_op files an operator call under its slot, charge_host host work under a total and its part.
+struct PassClock {
+    Ctx& c;
+    Pool& pool;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    long long c0 = thread_cpu_ns();
+    double cpu = 0;   // core-seconds of the last lap: this thread's CPU time + what the workers spent on its batches
+    explicit PassClock(Ctx& c_) : c(c_), pool(*c_.pool) {}
+    double lap() {
+        auto t1 = std::chrono::steady_clock::now();
+        const double d = std::chrono::duration<double>(t1 - t0).count();
+        t0 = t1;
+        const long long c1 = thread_cpu_ns();
+        CpuAccount* a = thread_account();
+        cpu = 1e-9 * (double)((c1 - c0) + (a ? a->worker_ns.exchange(0, std::memory_order_relaxed) : 0));
+        c0 = c1;
+        return d;
+    }
+    void charge_op(int slot) { c.sec[slot] += lap(); c.cpu[slot] += cpu; }
+    void charge_host(int total, int part) { const double d = lap(); c.sec[total] += d; c.sec[part] += d; c.cpu[total] += cpu; c.cpu[part] += cpu; }
+};
+
 // ---- one local-mapping pass: what all its steps work on ----
 static MpUpdate& map_updates(Ctx& c) { if (!c.updMap) c.updMap.reset(new MpUpdate); return *c.updMap; }
-struct LmPass {
-    Ctx& c;
+struct LmPass : PassClock {
     const std::vector<int>& who;   // the sequences of the pass; w below is an index into it
     const int nW, flags;           // flags: oslam_slam_config_t::local_mapping
-    Pool& pool;
     MpUpdate& upd;                 // the batched MapPoint updates of the pass
-    Timer tm;
-    LmPass(Ctx& c_, const std::vector<int>& who_) : c(c_), who(who_), nW((int)who_.size()), flags(c_.cfg.local_mapping), pool(*c_.pool), upd(map_updates(c_)) {}
+    LmPass(Ctx& c_, const std::vector<int>& who_) : PassClock(c_), who(who_), nW((int)who_.size()), flags(c_.cfg.local_mapping), upd(map_updates(c_)) {}
     Seq& seq(int w) const { return *c.seq[who[w]]; }
     // the points the sequences listed for an update (Seq::updList) become the items of `upd`: sequence order, then list order
     void merge_upd() { upd.clear(); for (int si : who) { Seq& s = *c.seq[si]; for (int p : s.updList) upd.add(si, p); s.updList.clear(); } }
-    // The time since the last charge goes to a stage of oslam_slam_stage_seconds.  charge: host work of the pass, to [7] and its part [stage] (9 ProcessNewKeyFrame,
-    // 10 CreateNewMapPoints, 11 SearchInNeighbors — and its part Ctx::fine[fine] —, 12 local-BA gather + write-back, 13 KeyFrameCulling); charge_op: an operator call,
-    // to [5] mp_update, [6] lba or [8] fuse / bow / triangulate, which are not part of [7].
+    // charge: host work of the pass, to [7] and its part [stage] (9 ProcessNewKeyFrame, 10 CreateNewMapPoints, 11 SearchInNeighbors — and its part Ctx::fine[fine] —,
+    // 12 local-BA gather + write-back, 13 KeyFrameCulling); charge_op: an operator call, to [5] mp_update, [6] lba or [8] fuse / bow / triangulate, which are not part of [7].
     void charge(int stage, int fine = -1) {
-        const double d = tm.lap();
-        c.sec[7] += d; c.sec[stage] += d; c.cpu[7] += tm.cpu; c.cpu[stage] += tm.cpu;
-        if (fine >= 0) c.fine[fine] += tm.cpu;
+        charge_host(7, stage);
+        if (fine >= 0) c.fine[fine] += cpu;
     }
-    void charge_op(int slot) { c.sec[slot] += tm.lap(); c.cpu[slot] += tm.cpu; }
 };
 
-// the change sets of the sequences' maps since the last call, to the table's mirror of the observation graph (oslam_slam_ops_t::map_journal)
-static int lm_send_journal(LmPass& L) {
-    Ctx& c = L.c;
-    std::vector<oslam_map_changes_t> chg(L.nW), chs;
-    std::vector<uint8_t> has(L.nW, 0);
+// the change sets of the maps of `who` since the last call, to the table's mirror of the observation graph (oslam_slam_ops_t::map_journal)
+static int send_journal(Ctx& c, Pool& pool, const std::vector<int>& who) {
+    const int n = (int)who.size();
+    std::vector<oslam_map_changes_t> chg(n), chs;
+    std::vector<uint8_t> has(n, 0);
     if (c.jrScratch.size() < (size_t)c.S) c.jrScratch.resize(c.S);
-    L.pool.parallel_for(L.nW, [&](int w) { Seq& s = L.seq(w); if (s.map.jr_pending()) { s.map.journal_changes(L.who[w], c.thDepth, c.jrScratch[L.who[w]], chg[w]); has[w] = 1; } });
-    for (int w = 0; w < L.nW; w++) if (has[w]) chs.push_back(chg[w]);
+    pool.parallel_for(n, [&](int w) { Seq& s = *c.seq[who[w]]; if (s.map.jr_pending()) { s.map.journal_changes(who[w], c.thDepth, c.jrScratch[who[w]], chg[w]); has[w] = 1; } });
+    for (int w = 0; w < n; w++) if (has[w]) chs.push_back(chg[w]);
     return chs.empty() ? OSLAM_OK : c.ops.map_journal(c.ops.ctx, (int)chs.size(), chs.data());
 }
 
@@ -1003,7 +968,7 @@ static int lm_request_cull(LmPass& L, CullRequest& cr) {
     cr.requested = true;
     if (!((L.flags & 16) && kCullDev && c.ops.map_journal && c.ops.kf_culling_counts)) { cr.collected = true; return OSLAM_OK; }
     int rc;
-    if ((rc = lm_send_journal(L))) return rc;
+    if ((rc = send_journal(L.c, L.pool, L.who))) return rc;
     cr.out.resize(L.nW); cr.ids.resize(L.nW);
     for (int w = 0; w < L.nW; w++) {
         Seq& s = L.seq(w);
@@ -1157,7 +1122,7 @@ static int finish_local_mapping(Ctx& c) {
     Ctx::PendingLM& pd = c.pend;
     if (!pd.active) return OSLAM_OK;
     pd.active = false;
-    Timer tm;
+    PassClock clock(c);
     int rc = OSLAM_OK;
     if (!pd.probs.empty()) {
         if (pd.submitted) rc = c.ops.lba_wait(c.ops.ctx);
@@ -1165,7 +1130,7 @@ static int finish_local_mapping(Ctx& c) {
         pd.submitted = false;
         if (rc) return rc;
     }
-    { c.sec[6] += tm.lap(); c.cpu[6] += tm.cpu; }
+    clock.charge_op(6);
     for (int si : pd.who) c.seq[si]->mapVersion++;   // poses, positions and the keyframe set of these sequences change: their cached local maps are stale
     return local_mapping_back(c, pd.who, pd.wins);
 }
@@ -1566,7 +1531,7 @@ static int sn_fuse_into_current(LmPass& L, std::vector<FuseSeq>& fs, bool& done)
     done = false;
     if (!(fuse_by_id(c) && c.ops.fuse_into_current && c.ops.map_journal)) return OSLAM_OK;
     for (int w = 0; w < nW; w++) if (!L.seq(w).map.jrOn) return OSLAM_OK;
-    if ((rc = lm_send_journal(L))) return rc;
+    if ((rc = send_journal(L.c, L.pool, L.who))) return rc;
     std::vector<oslam_job_fuse_cur_t> cj;
     std::vector<int> cw;
     std::vector<std::vector<int32_t>> cpairs(nW), dIds(nW);
@@ -1808,9 +1773,7 @@ static int run_local_mapping(Ctx& c, const std::vector<int>& who) {
     return local_mapping_back(c, who, std::vector<Ctx::Win*>());
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// Object layer (include/oslam_slam.h head comment)
-// ------------------------------------------------------------------------------------------------------------------
+// ======== Object layer (include/oslam_slam.h head comment) ========
 // Frame::BuildObject2DsRGBD / BuildObject2DsStereo (src/Frame.cc:240-312, :314-386) from the keypoint test bits: detection i takes, in keypoint order, the
 // keypoints still in the pool whose window lies in its mask and whose depth is in (0, mThDepth]; they leave the pool even if the detection then
 // fails the "> 5 keypoints" test and builds no Object2D (the erase at :283 comes before the test at :291).
@@ -1848,7 +1811,7 @@ static void track_objects(Seq& s) {
 }
 
 // ObjectOptimizer::PoseOptimization2 inputs (src/ObjectOptimizer.cc:685-767, :978-990): masks and map points of the matched objects, M_joint candidates
-static void fill_pose2_job(Ctx& c, Seq& s, int si) {
+static void fill_pose2_job(Ctx& c, Seq& s) {
     Frame& f = *s.cur;
     s.hasPose2 = false;
     s.jMaskPtrs.clear(); s.jObjXw.clear(); s.jObjOf.clear(); s.jJointKp.clear(); s.jJointObj.clear(); s.jObjIds.clear();
@@ -1884,7 +1847,6 @@ static void fill_pose2_job(Ctx& c, Seq& s, int si) {
     j.nJoint = (int)s.jJointKp.size(); j.joint_kp = s.jJointKp.data(); j.joint_obj = s.jJointObj.data();
     j.n_semantic = 0;
     s.hasPose2 = true;
-    (void)si;
 }
 
 // Tracking::UpdateCurrentObject (src/Tracking.cc:1079-1210) + Object3D::Update (src/ObjectTypes.cc:56-140), list logic only
@@ -1959,20 +1921,11 @@ static void stage_motion_model_prepare(Ctx& c, int i) {
     s.hasSL = true;
 }
 
+// SearchLocalPoints (:1408-1458) up to the operator's job, after UpdateLocalMap and the lists the table delivers (stage_local_map_lists)
 static void stage_local_map_prepare(Ctx& c, int i) {
     Seq& s = *c.seq[i];
     Frame& f = *s.cur;
-    s.hasLoc = false;
-    f.refKF = s.refKF;   // :446
     if (!s.ok) return;
-    update_local_map(s);
-}
-// (second half: after the table has delivered the lists of the sequences whose local map changed — stage_local_map_lists)
-static void stage_local_map_prepare_b(Ctx& c, int i) {
-    Seq& s = *c.seq[i];
-    Frame& f = *s.cur;
-    if (!s.ok) return;
-    // SearchLocalPoints (:1408-1458)
     Map& m = s.map;
     s.jBlocked.assign(f.N, 0);
     for (int k = 0; k < f.N; k++) {
@@ -1990,9 +1943,7 @@ static void stage_local_map_prepare_b(Ctx& c, int i) {
     if (!s.locReused) {
         s.locObs.resize(M + 1);
         if (c.residentPts) {   // the table gathers the points' arrays from its records: only Observations() > 0 is the driver's to tell
-            for (int q = 0; q < M; q++) {
-                s.locObs[q] = m.pNObs[s.localMPs[q]] > 0;
-            }
+            for (int q = 0; q < M; q++) s.locObs[q] = m.pNObs[s.localMPs[q]] > 0;
         } else {
             s.locPw.resize((size_t)M * 3 + 3); s.locPn.resize((size_t)M * 3 + 3); s.locMax.resize(M + 1); s.locMin.resize(M + 1);
             s.locDesc.resize((size_t)M * 32 + 32);
@@ -2036,13 +1987,8 @@ static int stage_local_map_lists(Ctx& c, const std::vector<int>& tracking) {
     static const bool check = getenv("OSLAM_SLAM_LOCLIST_CHECK") != nullptr;
     Pool& pool = *c.pool;
     const int n = (int)need.size();
-    std::vector<oslam_map_changes_t> chg(n), chs;
-    std::vector<uint8_t> has(n, 0);
-    if (c.jrScratch.size() < (size_t)c.S) c.jrScratch.resize(c.S);
-    pool.parallel_for(n, [&](int q) { Seq& s = *c.seq[need[q]]; if (s.map.jr_pending()) { s.map.journal_changes(need[q], c.thDepth, c.jrScratch[need[q]], chg[q]); has[q] = 1; } });
-    for (int q = 0; q < n; q++) if (has[q]) chs.push_back(chg[q]);
     int rc;
-    if (!chs.empty() && (rc = c.ops.map_journal(c.ops.ctx, (int)chs.size(), chs.data()))) return rc;
+    if ((rc = send_journal(c, pool, need))) return rc;
     std::vector<oslam_job_local_list_t> jobs(n);
     for (int q = 0; q < n; q++) {
         Seq& s = *c.seq[need[q]];
@@ -2053,10 +1999,10 @@ static int stage_local_map_lists(Ctx& c, const std::vector<int>& tracking) {
     if ((rc = c.ops.local_points_list(c.ops.ctx, n, jobs.data()))) return rc;
     pool.parallel_for(n, [&](int q) {
         Seq& s = *c.seq[need[q]];
-        if (jobs[q].overflow) { local_points_walk_host(s); return; }
+        if (jobs[q].overflow) { s.locListPending = false; local_points_walk(s); return; }   // (update_local_map's tail again: the vote and the keyframe list are done)
         if (check) {
             std::vector<int> got(s.localMPs.begin(), s.localMPs.begin() + jobs[q].n_ids);
-            local_points_walk_host(s);
+            s.locListPending = false; local_points_walk(s);
             if (got != s.localMPs) { fprintf(stderr, "OSLAM_SLAM_LOCLIST_CHECK: the table's local point list differs from the driver's walk (sequence %d frame %d: %zu against %zu points)\n", need[q], s.cur->id, got.size(), s.localMPs.size()); abort(); }
             return;
         }
@@ -2079,9 +2025,7 @@ static void stage_after_local_pose(Ctx& c, int i) {
         if (!f.outlier[k]) {
             s.map.pFound[p]++;
             if (s.map.pNObs[p] > 0) s.matchesInliers++;
-        } else if (c.stereo) {
-            f.mp[k] = -1;   // :1041-1042
-        }
+        } else if (c.stereo) f.mp[k] = -1;   // :1041-1042
     }
     s.st[13] = s.matchesInliers;
     if (f.id < s.lastRelocFrameId + c.maxFrames && s.matchesInliers < 50) s.ok = false;
@@ -2103,33 +2047,31 @@ static void stage_after_tracking(Ctx& c, int i) {
         }
         // NeedNewKeyFrame (:1242-1326) with an idle local mapper
         bool need = false;
-        {
-            const int nKFs = m.nKFsInMap;
-            if (!(f.id < s.lastRelocFrameId + c.maxFrames && nKFs > c.maxFrames)) {
-                const int nMinObs = nKFs <= 2 ? 2 : 3;
-                // KeyFrame::TrackedMapPoints depends on the map alone: one count per (reference keyframe, nMinObs, map version)
-                if (!(s.trkKF == s.refKF && s.trkMinObs == nMinObs && s.trkVersion == s.mapVersion)) {
-                    s.trkCount = m.tracked_map_points(s.refKF, nMinObs);
-                    s.trkKF = s.refKF; s.trkMinObs = nMinObs; s.trkVersion = s.mapVersion;
-                }
-                const int nRefMatches = s.trkCount;
-                int nNonTrackedClose = 0, nTrackedClose = 0;
-                for (int k = 0; k < f.N; k++)
-                    if (f.depth[k] > 0 && f.depth[k] < c.thDepth) {
-                        if (f.mp[k] >= 0 && !f.outlier[k]) nTrackedClose++;
-                        else nNonTrackedClose++;
-                    }
-                const bool bNeedToInsertClose = (nTrackedClose < 100) && (nNonTrackedClose > 70);
-                const float thRefRatio = nKFs < 2 ? 0.4f : 0.75f;
-                const bool c1a = f.id >= s.lastKFFrameId + c.maxFrames;
-                const bool c1b = f.id >= s.lastKFFrameId + c.minFrames;
-                const bool c1c = s.matchesInliers < nRefMatches * 0.25 || bNeedToInsertClose;
-                const bool c2 = (s.matchesInliers < nRefMatches * thRefRatio || bNeedToInsertClose) && s.matchesInliers > 15;
-                need = (c1a || c1b || c1c) && c2;
+        const int nKFs = m.nKFsInMap;
+        if (!(f.id < s.lastRelocFrameId + c.maxFrames && nKFs > c.maxFrames)) {
+            const int nMinObs = nKFs <= 2 ? 2 : 3;
+            // KeyFrame::TrackedMapPoints depends on the map alone: one count per (reference keyframe, nMinObs, map version)
+            if (!(s.trkKF == s.refKF && s.trkMinObs == nMinObs && s.trkVersion == s.mapVersion)) {
+                s.trkCount = m.tracked_map_points(s.refKF, nMinObs);
+                s.trkKF = s.refKF; s.trkMinObs = nMinObs; s.trkVersion = s.mapVersion;
             }
+            const int nRefMatches = s.trkCount;
+            int nNonTrackedClose = 0, nTrackedClose = 0;
+            for (int k = 0; k < f.N; k++)
+                if (f.depth[k] > 0 && f.depth[k] < c.thDepth) {
+                    if (f.mp[k] >= 0 && !f.outlier[k]) nTrackedClose++;
+                    else nNonTrackedClose++;
+                }
+            const bool bNeedToInsertClose = (nTrackedClose < 100) && (nNonTrackedClose > 70);
+            const float thRefRatio = nKFs < 2 ? 0.4f : 0.75f;
+            const bool c1a = f.id >= s.lastKFFrameId + c.maxFrames;
+            const bool c1b = f.id >= s.lastKFFrameId + c.minFrames;
+            const bool c1c = s.matchesInliers < nRefMatches * 0.25 || bNeedToInsertClose;
+            const bool c2 = (s.matchesInliers < nRefMatches * thRefRatio || bNeedToInsertClose) && s.matchesInliers > 15;
+            need = (c1a || c1b || c1c) && c2;
         }
         if (need) {   // CreateNewKeyFrame (:1328-1406)
-            const int kf = new_keyframe(s, f, c.thDepth);
+            const int kf = new_keyframe(s, f);
             s.refKF = kf; f.refKF = kf;
             create_stereo_points(c, s, f, kf, false);
             s.newKFs.push_back(kf);
@@ -2154,46 +2096,65 @@ static int run_pose_jobs(Ctx& c, const std::vector<int>& who) {
     return rc;
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// One lockstep step of Tracking::Track for all sequences
-// ------------------------------------------------------------------------------------------------------------------
-static int track_step(Ctx& c, const uint8_t* const* gray, const uint8_t* const* right, int gray_stride, const float* const* depth, int depth_pitch,
-                      int on_device, const double* stamps, const oslam_slam_objects_t* objs, int mask_stride, float* Tcw_out, int32_t* state_out,
-                      const uint16_t* const* depth16 = nullptr, float depth_factor = 1.f) {
-    const int S = c.S;
-    c.started = true;
-    oslam_drv::ShardScope shard_scope(c.shard);   // library code below the operator table (local-BA preparation, BoW views) uses this handle's worker set
-    AccountScope acct_scope(&c.acct);   // the workers bill the tasks of this thread's batches (driver and operator table) to this handle; unbound again on every return
-    c.acct.worker_ns.store(0, std::memory_order_relaxed);
-    Timer tm;
+// ======== One lockstep step of Tracking::Track for all sequences ========
+// What a step is given (filled by the oslam_slam_track_* entry points): the images of the S sequences in one of three kinds, the detections, the two outputs.
+struct TrackInput {
+    enum Kind { RGBD, RAW16, STEREO } kind;
+    const uint8_t* const* gray;                   // gray images; the left ones of a STEREO step
+    const uint8_t* const* right = nullptr;        // STEREO
+    const float* const* depth = nullptr;          // RGBD: metres
+    const uint16_t* const* depth16 = nullptr; float depth_factor = 1.f;   // RAW16: the 16-bit depth images, metres = value * depth_factor
+    int gray_stride, depth_pitch = 0, on_device;
+    const double* stamps;                         // NULL: the frame ids
+    const oslam_slam_objects_t* objs; int mask_stride;   // objs NULL: no detections
+    float* Tcw_out; int32_t* state_out;
+    TrackInput(Kind k, const uint8_t* const* g, int gs, int dev, const double* ts, const oslam_slam_objects_t* o, int ms, float* T, int32_t* st)
+        : kind(k), gray(g), gray_stride(gs), on_device(dev), stamps(ts), objs(o), mask_stride(ms), Tcw_out(T), state_out(st) {}
+};
+
+// ---- one tracking step: what all its steps work on ----
+struct TrackPass : PassClock {
+    const TrackInput& in;
+    const int S;
+    std::vector<int> tracking;   // sequences in the "system is initialised" branch (listed by tk_motion_model)
+    std::vector<int> mapping;    // sequences that inserted a keyframe in this step: the local-mapping pass that follows (listed by tk_after_tracking)
+    TrackPass(Ctx& c_, const TrackInput& in_) : PassClock(c_), in(in_), S(c_.S) {}
+    Seq& seq(int i) const { return *c.seq[i]; }
+    // charge: host work of the step, to [4] and its part [14] (initial pose, after tracking, pose storage) or [15] (local map); charge_op: an operator call, to
+    // [0] Frame::Frame + object keypoints, [1] search_last, [2] the pose operators, [3] search_local, [5] keyframe registration + mp_update, [8] bow.
+    void charge(int stage) { charge_host(4, stage); }
+};
+
+// Frame::Frame for every sequence (src/Frame.cc:61-172)
+static int tk_frames(TrackPass& T) {
+    Ctx& c = T.c; const TrackInput& in = T.in;
+    std::vector<int32_t> slots(T.S);
+    std::vector<oslam_slam_frame_t*> outs(T.S);
+    for (int i = 0; i < T.S; i++) { slots[i] = i; outs[i] = &T.seq(i).cur->view; }
     int rc;
-    Pool& pool = *c.pool;
-    // Frame::Frame for every sequence
-    {
-        std::vector<int32_t> slots(S);
-        std::vector<oslam_slam_frame_t*> outs(S);
-        for (int i = 0; i < S; i++) { slots[i] = i; outs[i] = &c.seq[i]->cur->view; }
-        if (right) rc = c.ops.frames_stereo(c.ops.ctx, S, slots.data(), gray, right, gray_stride, on_device, outs.data());
-        else if (depth16) rc = c.ops.frames_rgbd_raw16(c.ops.ctx, S, slots.data(), gray, gray_stride, depth16, depth_pitch, depth_factor, on_device, outs.data());
-        else rc = c.ops.frames_rgbd(c.ops.ctx, S, slots.data(), gray, gray_stride, depth, depth_pitch, on_device, outs.data());
-        if (rc) return rc;
-    }
-    { c.sec[0] += tm.lap(); c.cpu[0] += tm.cpu; }
-    std::vector<int> tracking;   // sequences in the "system is initialised" branch
-    pool.parallel_for(S, [&](int i) {
-        Seq& s = *c.seq[i];
-        if (s.resetRequested) s.reset();   // System::TrackRGBD: if(mbReset) mpTracker->Reset() before the frame is grabbed (src/System.cc:262-266)
+    if (in.kind == TrackInput::STEREO) rc = c.ops.frames_stereo(c.ops.ctx, T.S, slots.data(), in.gray, in.right, in.gray_stride, in.on_device, outs.data());
+    else if (in.kind == TrackInput::RAW16) rc = c.ops.frames_rgbd_raw16(c.ops.ctx, T.S, slots.data(), in.gray, in.gray_stride, in.depth16, in.depth_pitch, in.depth_factor, in.on_device, outs.data());
+    else rc = c.ops.frames_rgbd(c.ops.ctx, T.S, slots.data(), in.gray, in.gray_stride, in.depth, in.depth_pitch, in.on_device, outs.data());
+    if (rc) return rc;
+    T.charge_op(0);
+    return OSLAM_OK;
+}
+
+// System::TrackRGBD's reset (src/System.cc:262-266), the per-step scratch, and StereoInitialization (src/Tracking.cc:590-642) for the sequences not yet initialised
+static void tk_begin_frames(TrackPass& T) {
+    Ctx& c = T.c;
+    T.pool.parallel_for(T.S, [&](int i) {
+        Seq& s = T.seq(i);
+        if (s.resetRequested) s.reset();   // if(mbReset) mpTracker->Reset() before the frame is grabbed
         const int fid = s.nextFrameId++;
-        s.cur->begin(fid, stamps ? stamps[i] : (double)fid);
-        s.seenList.clear();
+        s.cur->begin(fid, T.in.stamps ? T.in.stamps[i] : (double)fid);
+        s.seenList.clear(); s.updList.clear();
         s.st[0]++;
         s.path = 0; s.ok = false; s.hasSL = s.hasLoc = false;
-        s.updList.clear();
         Frame& f = *s.cur;
         if (s.state == ST_NOT_INITIALIZED && f.N > 500) {
-            // StereoInitialization (:590-642)
             f.pose.set_frame(eye4());
-            const int kf = new_keyframe(s, f, c.thDepth);
+            const int kf = new_keyframe(s, f);
             // mpMap->AddKeyFrame (:601): counted when ProcessNewKeyFrame inserts it (same std::set entry in the reference)
             create_stereo_points(c, s, f, kf, true);
             s.newKFs.push_back(kf);
@@ -2207,36 +2168,58 @@ static int track_step(Ctx& c, const uint8_t* const* gray, const uint8_t* const* 
             s.path = -1;   // initialised in this step: not tracked
         }
     });
-    // Frame::BuildObject2DsRGBD / BuildObject2DsStereo (src/Frame.cc:179, :119): part of the Frame constructor, whatever the tracking state
-    {
-        std::vector<oslam_job_object_kps_t> oj;
-        std::vector<int> ojw;
-        c.mask_stride = mask_stride; c.masks_on_device = on_device;
-        for (int i = 0; i < S; i++) {
-            Seq& s = *c.seq[i];
-            s.det = (objs && objs[i].n > 0) ? &objs[i] : nullptr;
-            if (!s.det) continue;
-            if (s.det->n > OSLAM_SLAM_MAX_OBJECTS || !s.det->masks) { oslam::set_error("track: sequence %d has %d detections (max %d) or no masks", i, s.det->n, OSLAM_SLAM_MAX_OBJECTS); return OSLAM_E_INVALID; }
-            if (!c.ops.object_kps || !c.ops.pose_opt2) { oslam::set_error("track: this operator table has no semantic operators"); return OSLAM_E_INVALID; }
-            s.jInMask.assign(s.cur->N + 1, 0);
-            oslam_job_object_kps_t j;
-            j.slot = i; j.cur = &s.cur->view; j.n_masks = s.det->n; j.masks = s.det->masks; j.mask_stride = mask_stride; j.on_device = on_device; j.in_mask = s.jInMask.data();
-            oj.push_back(j); ojw.push_back(i);
-        }
-        if (!oj.empty()) {
-            if ((rc = c.ops.object_kps(c.ops.ctx, (int)oj.size(), oj.data()))) return rc;
-            pool.parallel_for((int)ojw.size(), [&](int q) { build_object2ds(c, *c.seq[ojw[q]]); });
-        }
-        { c.sec[0] += tm.lap(); c.cpu[0] += tm.cpu; }
+}
+
+// Frame::BuildObject2DsRGBD / BuildObject2DsStereo (src/Frame.cc:179, :119): part of the Frame constructor, whatever the tracking state
+static int tk_object_keypoints(TrackPass& T) {
+    Ctx& c = T.c; const TrackInput& in = T.in;
+    std::vector<oslam_job_object_kps_t> oj;
+    std::vector<int> ojw;
+    int rc;
+    c.mask_stride = in.mask_stride; c.masks_on_device = in.on_device;
+    for (int i = 0; i < T.S; i++) {
+        Seq& s = T.seq(i);
+        s.det = (in.objs && in.objs[i].n > 0) ? &in.objs[i] : nullptr;
+        if (!s.det) continue;
+        if (s.det->n > OSLAM_SLAM_MAX_OBJECTS || !s.det->masks) { oslam::set_error("track: sequence %d has %d detections (max %d) or no masks", i, s.det->n, OSLAM_SLAM_MAX_OBJECTS); return OSLAM_E_INVALID; }
+        if (!c.ops.object_kps || !c.ops.pose_opt2) { oslam::set_error("track: this operator table has no semantic operators"); return OSLAM_E_INVALID; }
+        s.jInMask.assign(s.cur->N + 1, 0);
+        oslam_job_object_kps_t j;
+        j.slot = i; j.cur = &s.cur->view; j.n_masks = s.det->n; j.masks = s.det->masks; j.mask_stride = in.mask_stride; j.on_device = in.on_device; j.in_mask = s.jInMask.data();
+        oj.push_back(j); ojw.push_back(i);
     }
-    for (int i = 0; i < S; i++) if (c.seq[i]->state == ST_OK && c.seq[i]->path != -1) tracking.push_back(i);
-    const int nT = (int)tracking.size();
-    // ---------------- initial pose: motion model or reference keyframe ----------------
-    pool.parallel_for(nT, [&](int q) { stage_motion_model_prepare(c, tracking[q]); });
+    if (!oj.empty()) {
+        if ((rc = c.ops.object_kps(c.ops.ctx, (int)oj.size(), oj.data()))) return rc;
+        T.pool.parallel_for((int)ojw.size(), [&](int q) { build_object2ds(c, T.seq(ojw[q])); });
+    }
+    T.charge_op(0);
+    return OSLAM_OK;
+}
+
+// PoseOptimization of the initial pose and its outliers (:858-879, :981-1008) for the filled jobs of `who`: Seq::ok, counted in stats [stat]; without it Seq::path = 2
+static int tk_initial_pose(TrackPass& T, const std::vector<int>& who, int stat) {
+    const int rc = run_pose_jobs(T.c, who);
+    if (rc) return rc;
+    T.charge_op(2);
+    T.pool.parallel_for((int)who.size(), [&](int q) {
+        Seq& s = T.seq(who[q]);
+        s.ok = finish_initial_pose(s, s.jPose);
+        if (s.ok) s.st[stat]++;
+        else s.path = 2;
+    });
+    return OSLAM_OK;
+}
+
+// TrackWithMotionModel (src/Tracking.cc:948-1009; CheckReplacedInLastFrame :820-835, UpdateLastFrame :882-946) where there is a velocity; without one, or where it fails, Seq::path = 2
+static int tk_motion_model(TrackPass& T) {
+    Ctx& c = T.c;
+    int rc;
+    for (int i = 0; i < T.S; i++) if (T.seq(i).state == ST_OK && T.seq(i).path != -1) T.tracking.push_back(i);
+    T.pool.parallel_for((int)T.tracking.size(), [&](int q) { stage_motion_model_prepare(c, T.tracking[q]); });
     std::vector<oslam_job_search_last_t> sl;
     std::vector<int> slw;
-    for (int i : tracking) if (c.seq[i]->hasSL) { sl.push_back(c.seq[i]->jSL); slw.push_back(i); }
-    { const double d_ = tm.lap(); c.sec[4] += d_; c.sec[14] += d_; c.cpu[4] += tm.cpu; c.cpu[14] += tm.cpu; }
+    for (int i : T.tracking) if (T.seq(i).hasSL) { sl.push_back(T.seq(i).jSL); slw.push_back(i); }
+    T.charge(14);
     if (!sl.empty()) {
         if ((rc = c.ops.search_last(c.ops.ctx, (int)sl.size(), sl.data()))) return rc;
         std::vector<oslam_job_search_last_t> again;
@@ -2248,206 +2231,193 @@ static int track_step(Ctx& c, const uint8_t* const* gray, const uint8_t* const* 
             for (size_t q = 0; q < again.size(); q++) sl[againAt[q]].nmatches = again[q].nmatches;
         }
     }
-    { c.sec[1] += tm.lap(); c.cpu[1] += tm.cpu; }
+    T.charge_op(1);
     std::vector<int> pjw;
-    for (size_t q = 0; q < sl.size(); q++) {
-        Seq& s = *c.seq[slw[q]];
-        if (sl[q].nmatches < 20) { s.path = 2; continue; }   // TrackWithMotionModel failed -> TrackReferenceKeyFrame (:365-366)
-        pjw.push_back(slw[q]);
+    for (size_t q = 0; q < sl.size(); q++) {   // fewer than 20 matches: TrackWithMotionModel failed -> TrackReferenceKeyFrame (:365-366)
+        if (sl[q].nmatches < 20) T.seq(slw[q]).path = 2;
+        else pjw.push_back(slw[q]);
     }
-    pool.parallel_for((int)pjw.size(), [&](int q) {
-        Seq& s = *c.seq[pjw[q]];
+    T.pool.parallel_for((int)pjw.size(), [&](int q) {
+        Seq& s = T.seq(pjw[q]);
         Frame& f = *s.cur; Frame& l = *s.last;
         for (int k = 0; k < f.N; k++) f.mp[k] = s.jMatch[k] >= 0 ? l.mp[s.jMatch[k]] : -1;
         fill_pose_job(c, s, pjw[q], s.jPose);
     });
-    { const double d_ = tm.lap(); c.sec[4] += d_; c.sec[14] += d_; c.cpu[4] += tm.cpu; c.cpu[14] += tm.cpu; }
-    if ((rc = run_pose_jobs(c, pjw))) return rc;
-    { c.sec[2] += tm.lap(); c.cpu[2] += tm.cpu; }
-    pool.parallel_for((int)pjw.size(), [&](int q) {
-        Seq& s = *c.seq[pjw[q]];
-        s.ok = finish_initial_pose(s, s.jPose);
-        if (s.ok) s.st[6]++;
-        else s.path = 2;
-    });
-    // TrackReferenceKeyFrame (:838-880) for the sequences without a motion model or whose motion-model tracking failed
-    {
-        std::vector<int> rk;
-        for (int i : tracking) if (c.seq[i]->path == 2) rk.push_back(i);
-        if (!rk.empty()) {
-            std::vector<oslam_job_bow_t> bj(rk.size());
-            std::vector<BowViews> bv(rk.size());
-            std::vector<std::vector<uint8_t>> flag(rk.size());
-            std::vector<std::vector<int32_t>> match(rk.size());
-            if (c.seq[rk[0]]->lazyDesc) {   // Frame::ComputeBoW below runs on the host: these frames' descriptors are fetched now
-                std::vector<int32_t> cnt(rk.size());
-                std::vector<uint8_t*> outd(rk.size());
-                for (size_t q = 0; q < rk.size(); q++) { Frame& f = *c.seq[rk[q]]->cur; cnt[q] = f.N; outd[q] = f.desc.data(); }
-                if ((rc = c.ops.frame_descriptors(c.ops.ctx, (int)rk.size(), rk.data(), cnt.data(), outd.data()))) return rc;
-            }
-            pool.parallel_for((int)rk.size(), [&](int q) {
-                Seq& s = *c.seq[rk[q]];
-                Frame& f = *s.cur;
-                KeyFrm& kf = s.map.kfs[s.refKF];
-                compute_bow(c, f.N, f.desc.data(), f.bowNode);
-                const BowViews& vk = s.bow_views(c, s.refKF);
-                bv[q].side2(f.bowNode);
-                flag[q].resize(kf.N);
-                for (int k = 0; k < kf.N; k++) flag[q][k] = kf.mp[k] >= 0 && !s.map.pBad[kf.mp[k]];
-                match[q].assign(f.N + 1, -1);
-                oslam_job_bow_t& j = bj[q];
-                memset(&j, 0, sizeof(j));
-                j.s1.N = kf.N; j.s1.keys = kf.keysUn.data(); j.s1.desc = kf.desc.data(); j.s1.uRight = nullptr; j.s1.flag = flag[q].data();
-                j.s1.nq = kf.N; j.s1.q_idx = vk.q_idx.data(); j.s1.q_node = vk.q_node.data();
-                j.s2.N = f.N; j.s2.keys = f.keysUn.data(); j.s2.desc = f.desc.data(); j.s2.uRight = nullptr; j.s2.has_mp = nullptr;
-                j.s2.nNodes = (int)bv[q].nodes.size(); j.s2.nodes = bv[q].nodes.data(); j.s2.start = bv[q].start.data(); j.s2.items = bv[q].items.data();
-                j.triangulation = 0; j.nnratio = 0.7f; j.checkOri = 1; j.match = match[q].data();
-            });
-            { const double d_ = tm.lap(); c.sec[4] += d_; c.sec[14] += d_; c.cpu[4] += tm.cpu; c.cpu[14] += tm.cpu; }
-            std::vector<oslam_kf_key_t> bkey(rk.size());
-            for (size_t q = 0; q < rk.size(); q++) bkey[q] = {rk[q], c.seq[rk[q]]->refKF, -2};   // side 2 = the current frame, still on the device
-            if ((rc = c.ops.bow_keyed ? c.ops.bow_keyed(c.ops.ctx, (int)bj.size(), bj.data(), bkey.data()) : c.ops.bow(c.ops.ctx, (int)bj.size(), bj.data()))) return rc;
-            { c.sec[8] += tm.lap(); c.cpu[8] += tm.cpu; }
-            pjw.clear();
-            for (size_t q = 0; q < rk.size(); q++) {
-                Seq& s = *c.seq[rk[q]];
-                Frame& f = *s.cur;
-                s.ok = false;
-                if (bj[q].nmatches < 15) continue;
-                const KeyFrm& kf = s.map.kfs[s.refKF];
-                for (int k = 0; k < f.N; k++) f.mp[k] = match[q][k] >= 0 ? kf.mp[match[q][k]] : -1;
-                f.pose.set_frame(s.last->pose.Tcw);
-                fill_pose_job(c, s, rk[q], s.jPose);
-                pjw.push_back(rk[q]);
-            }
-            if ((rc = run_pose_jobs(c, pjw))) return rc;
-            { c.sec[2] += tm.lap(); c.cpu[2] += tm.cpu; }
-            for (int i : pjw) {
-                Seq& s = *c.seq[i];
-                s.ok = finish_initial_pose(s, s.jPose);
-                if (s.ok) s.st[7]++;
-            }
-        }
+    T.charge(14);
+    return tk_initial_pose(T, pjw, 6);
+}
+
+// TrackReferenceKeyFrame (:838-880) for the sequences without a motion model or whose motion-model tracking failed (Seq::path == 2)
+static int tk_reference_keyframe(TrackPass& T) {
+    Ctx& c = T.c;
+    int rc;
+    std::vector<int> rk, pjw;
+    for (int i : T.tracking) if (T.seq(i).path == 2) rk.push_back(i);
+    if (rk.empty()) return OSLAM_OK;
+    const int n = (int)rk.size();
+    std::vector<oslam_job_bow_t> bj(n);
+    std::vector<BowViews> bv(n);
+    std::vector<std::vector<uint8_t>> flag(n);
+    std::vector<std::vector<int32_t>> match(n);
+    if (T.seq(rk[0]).lazyDesc) {   // Frame::ComputeBoW below runs on the host: these frames' descriptors are fetched now
+        std::vector<int32_t> cnt(n);
+        std::vector<uint8_t*> outd(n);
+        for (int q = 0; q < n; q++) { Frame& f = *T.seq(rk[q]).cur; cnt[q] = f.N; outd[q] = f.desc.data(); }
+        if ((rc = c.ops.frame_descriptors(c.ops.ctx, n, rk.data(), cnt.data(), outd.data()))) return rc;
     }
-    // ---------------- TrackLocalMap (:1011-1056) ----------------
-    pool.parallel_for(nT, [&](int q) { stage_local_map_prepare(c, tracking[q]); });
-    if ((rc = stage_local_map_lists(c, tracking))) return rc;
-    pool.parallel_for(nT, [&](int q) { stage_local_map_prepare_b(c, tracking[q]); });
-    std::vector<oslam_job_search_local_t> lj;
-    std::vector<int> ljw;
-    for (int i : tracking) if (c.seq[i]->hasLoc) { lj.push_back(c.seq[i]->jLoc); ljw.push_back(i); }
-    { const double d_ = tm.lap(); c.sec[4] += d_; c.sec[15] += d_; c.cpu[4] += tm.cpu; c.cpu[15] += tm.cpu; }
-    if (!lj.empty() && (rc = c.ops.search_local(c.ops.ctx, (int)lj.size(), lj.data()))) return rc;
-    { c.sec[3] += tm.lap(); c.cpu[3] += tm.cpu; }
-    pool.parallel_for((int)ljw.size(), [&](int q) {
-        Seq& s = *c.seq[ljw[q]];
+    T.pool.parallel_for(n, [&](int q) {   // SearchByBoW(reference keyframe, frame) (:846-849)
+        Seq& s = T.seq(rk[q]);
         Frame& f = *s.cur;
-        for (int e = 0, Me = lj[q].M; e < Me; e++) {
-            if (s.jInView[e]) s.map.pVisible[s.localMPs[e]]++;
-        }
+        KeyFrm& kf = s.map.kfs[s.refKF];
+        compute_bow(c, f.N, f.desc.data(), f.bowNode);
+        const BowViews& vk = s.bow_views(c, s.refKF);
+        bv[q].side2(f.bowNode);
+        flag[q].resize(kf.N);
+        for (int k = 0; k < kf.N; k++) flag[q][k] = kf.mp[k] >= 0 && !s.map.pBad[kf.mp[k]];
+        match[q].assign(f.N + 1, -1);
+        oslam_job_bow_t& j = bj[q];
+        memset(&j, 0, sizeof(j));
+        j.s1.N = kf.N; j.s1.keys = kf.keysUn.data(); j.s1.desc = kf.desc.data(); j.s1.uRight = nullptr; j.s1.flag = flag[q].data();
+        j.s1.nq = kf.N; j.s1.q_idx = vk.q_idx.data(); j.s1.q_node = vk.q_node.data();
+        j.s2.N = f.N; j.s2.keys = f.keysUn.data(); j.s2.desc = f.desc.data(); j.s2.uRight = nullptr; j.s2.has_mp = nullptr;
+        j.s2.nNodes = (int)bv[q].nodes.size(); j.s2.nodes = bv[q].nodes.data(); j.s2.start = bv[q].start.data(); j.s2.items = bv[q].items.data();
+        j.triangulation = 0; j.nnratio = 0.7f; j.checkOri = 1; j.match = match[q].data();
+    });
+    T.charge(14);
+    std::vector<oslam_kf_key_t> bkey(n);
+    for (int q = 0; q < n; q++) bkey[q] = {rk[q], T.seq(rk[q]).refKF, -2};   // side 2 = the current frame, still on the device
+    if ((rc = c.ops.bow_keyed ? c.ops.bow_keyed(c.ops.ctx, n, bj.data(), bkey.data()) : c.ops.bow(c.ops.ctx, n, bj.data()))) return rc;
+    T.charge_op(8);
+    for (int q = 0; q < n; q++) {
+        Seq& s = T.seq(rk[q]);
+        Frame& f = *s.cur;
+        s.ok = false;
+        if (bj[q].nmatches < 15) continue;
+        const KeyFrm& kf = s.map.kfs[s.refKF];
+        for (int k = 0; k < f.N; k++) f.mp[k] = match[q][k] >= 0 ? kf.mp[match[q][k]] : -1;
+        f.pose.set_frame(s.last->pose.Tcw);
+        fill_pose_job(c, s, rk[q], s.jPose);
+        pjw.push_back(rk[q]);
+    }
+    return tk_initial_pose(T, pjw, 7);
+}
+
+// TrackLocalMap (:1011-1056): UpdateLocalMap, SearchLocalPoints, PoseOptimization or — with matched objects — ObjectOptimizer::PoseOptimization2
+static int tk_local_map(TrackPass& T) {
+    Ctx& c = T.c;
+    int rc;
+    const int nT = (int)T.tracking.size();
+    T.pool.parallel_for(nT, [&](int q) {
+        Seq& s = T.seq(T.tracking[q]);
+        s.hasLoc = false;
+        s.cur->refKF = s.refKF;   // :446
+        if (s.ok) update_local_map(s);
+    });
+    if ((rc = stage_local_map_lists(c, T.tracking))) return rc;
+    T.pool.parallel_for(nT, [&](int q) { stage_local_map_prepare(c, T.tracking[q]); });
+    std::vector<oslam_job_search_local_t> lj;
+    std::vector<int> ljw, plain, sem;
+    for (int i : T.tracking) if (T.seq(i).hasLoc) { lj.push_back(T.seq(i).jLoc); ljw.push_back(i); }
+    T.charge(15);
+    if (!lj.empty() && (rc = c.ops.search_local(c.ops.ctx, (int)lj.size(), lj.data()))) return rc;
+    T.charge_op(3);
+    T.pool.parallel_for((int)ljw.size(), [&](int q) {
+        Seq& s = T.seq(ljw[q]);
+        Frame& f = *s.cur;
+        for (int e = 0, Me = lj[q].M; e < Me; e++) if (s.jInView[e]) s.map.pVisible[s.localMPs[e]]++;
         for (int k = 0; k < f.N; k++) if (s.jMatch[k] >= 0) f.mp[k] = s.localMPs[s.jMatch[k]];
         fill_pose_job(c, s, ljw[q], s.jPose);
         s.hasPose2 = false;
         if (s.det && !f.objs.empty()) {   // TrackObject (:453) then ObjectOptimizer::PoseOptimization2 (:1022); without matched objects it is PoseOptimization
             track_objects(s);
-            fill_pose2_job(c, s, ljw[q]);
+            fill_pose2_job(c, s);
         }
     });
-    { const double d_ = tm.lap(); c.sec[4] += d_; c.sec[15] += d_; c.cpu[4] += tm.cpu; c.cpu[15] += tm.cpu; }
-    {
-        std::vector<int> plain, sem;
-        for (int i : ljw) (c.seq[i]->hasPose2 ? sem : plain).push_back(i);
-        if ((rc = run_pose_jobs(c, plain))) return rc;
-        if (!sem.empty()) {
-            std::vector<oslam_job_pose2_t> pj(sem.size());
-            for (size_t q = 0; q < sem.size(); q++) pj[q] = c.seq[sem[q]]->jPose2;
-            if ((rc = c.ops.pose_opt2(c.ops.ctx, (int)pj.size(), pj.data()))) return rc;
-            for (size_t q = 0; q < sem.size(); q++) {
-                Seq& s = *c.seq[sem[q]];
-                s.jPose = pj[q].base;
-                s.sem[0] += pj[q].n_semantic; s.sem[1]++; s.sem[2] += pj[q].n_semantic > 0;
-            }
+    T.charge(15);
+    for (int i : ljw) (T.seq(i).hasPose2 ? sem : plain).push_back(i);
+    if ((rc = run_pose_jobs(c, plain))) return rc;
+    if (!sem.empty()) {
+        std::vector<oslam_job_pose2_t> pj(sem.size());
+        for (size_t q = 0; q < sem.size(); q++) pj[q] = T.seq(sem[q]).jPose2;
+        if ((rc = c.ops.pose_opt2(c.ops.ctx, (int)pj.size(), pj.data()))) return rc;
+        for (size_t q = 0; q < sem.size(); q++) {
+            Seq& s = T.seq(sem[q]);
+            s.jPose = pj[q].base;
+            s.sem[0] += pj[q].n_semantic; s.sem[1]++; s.sem[2] += pj[q].n_semantic > 0;
         }
     }
-    { c.sec[2] += tm.lap(); c.cpu[2] += tm.cpu; }
-    pool.parallel_for((int)ljw.size(), [&](int q) { stage_after_local_pose(c, ljw[q]); });
-    // ---------------- after tracking (:470-566) ----------------
-    pool.parallel_for(nT, [&](int q) { stage_after_tracking(c, tracking[q]); });
-    std::vector<int> mapping;
+    T.charge_op(2);
+    T.pool.parallel_for((int)ljw.size(), [&](int q) { stage_after_local_pose(c, ljw[q]); });
+    return OSLAM_OK;
+}
+
+// The part of Tracking::Track after TrackLocalMap (:470-566), then who goes to local mapping and which points created in this step wait for their MapPoint update
+static void tk_after_tracking(TrackPass& T) {
+    Ctx& c = T.c;
+    T.pool.parallel_for((int)T.tracking.size(), [&](int q) { stage_after_tracking(c, T.tracking[q]); });
     if (!c.updTrack) c.updTrack.reset(new MpUpdate);
-    MpUpdate& upd = *c.updTrack;
-    upd.clear();
-    for (int i = 0; i < S; i++) {
-        Seq& s = *c.seq[i];
-        if (!s.newKFs.empty()) mapping.push_back(i);
-        for (int p : s.updList) upd.add(i, p);
+    c.updTrack->clear();
+    for (int i = 0; i < T.S; i++) {
+        Seq& s = T.seq(i);
+        if (!s.newKFs.empty()) T.mapping.push_back(i);
+        for (int p : s.updList) c.updTrack->add(i, p);
     }
-    { const double d_ = tm.lap(); c.sec[4] += d_; c.sec[14] += d_; c.cpu[4] += tm.cpu; c.cpu[14] += tm.cpu; }
-    if (c.ops.register_keyframes) {   // the frames that became keyframes are still on the device: the table keeps them (include/oslam_slam.h)
-        std::vector<int32_t> rs, rk;
-        for (int i = 0; i < S; i++) {
-            for (int kf : c.seq[i]->pendingKF) { rs.push_back(i); rk.push_back(kf); }
-            c.seq[i]->pendingKF.clear();
-        }
-        if (!rs.empty() && (rc = c.ops.register_keyframes(c.ops.ctx, (int)rs.size(), rs.data(), rk.data()))) return rc;
-        if (!rs.empty() && c.ops.keyframe_raw_keys) {   // mvKeys of the new keyframes (KeyFrame::UnprojectStereo in CreateNewMapPoints reads them; no frame does)
-            std::vector<int32_t> cnt(rs.size());
-            std::vector<oslam_keypoint_t*> outp(rs.size());
-            for (size_t q = 0; q < rs.size(); q++) {
-                KeyFrm& k = c.seq[rs[q]]->map.kfs[rk[q]];
-                k.keys.resize(k.N);
-                cnt[q] = k.N; outp[q] = (oslam_keypoint_t*)k.keys.data();
-            }
-            if ((rc = c.ops.keyframe_raw_keys(c.ops.ctx, (int)rs.size(), rs.data(), cnt.data(), outp.data()))) return rc;
-            if (c.seq[rs[0]]->lazyDesc) {   // KeyFrame::mDescriptors of the new keyframes (the frames' own descriptors stay on the device)
-                std::vector<uint8_t*> outd(rs.size());
-                for (size_t q = 0; q < rs.size(); q++) {
-                    KeyFrm& k = c.seq[rs[q]]->map.kfs[rk[q]];
-                    k.desc.resize((size_t)k.N * 32);
-                    outd[q] = k.desc.data();
-                }
-                if ((rc = c.ops.keyframe_descriptors(c.ops.ctx, (int)rs.size(), rs.data(), cnt.data(), outd.data()))) return rc;
-            }
-        }
-        const auto bow_t0 = std::chrono::steady_clock::now();
-        bool bow_op = false;
-        if (!rs.empty() && c.realVoc) {   // KeyFrame::ComputeBoW with the loaded vocabulary; a table without voc_nodes_keyed leaves it to compute_bow (host descent)
-            if (c.ops.voc_nodes_keyed) {
-                std::vector<int32_t> cnt(rs.size());
-                std::vector<uint32_t*> outp(rs.size());
-                for (size_t q = 0; q < rs.size(); q++) {
-                    KeyFrm& k = c.seq[rs[q]]->map.kfs[rk[q]];
-                    k.bowNode.resize(k.N);
-                    cnt[q] = k.N; outp[q] = k.bowNode.data();
-                }
-                if ((rc = c.ops.voc_nodes_keyed(c.ops.ctx, c.realVoc, 4, (int)rs.size(), rs.data(), rk.data(), cnt.data(), outp.data()))) return rc;
-                bow_op = true;
-            }
-        } else if (!rs.empty() && c.ops.bow_nodes_keyed) {   // KeyFrame::ComputeBoW of the new keyframes from their resident descriptors (ProcessNewKeyFrame finds it done)
-            std::vector<int32_t> cnt(rs.size());
-            std::vector<uint32_t*> outp(rs.size());
-            for (size_t q = 0; q < rs.size(); q++) {
-                KeyFrm& k = c.seq[rs[q]]->map.kfs[rk[q]];
-                k.bowNode.resize(k.N);
-                cnt[q] = k.N; outp[q] = k.bowNode.data();
-            }
-            if ((rc = c.ops.bow_nodes_keyed(c.ops.ctx, (int)rs.size(), rs.data(), rk.data(), &c.voc.top[0][0], &c.voc.sub[0][0][0], cnt.data(), outp.data()))) return rc;
-            bow_op = true;
-        }
-        if (bow_op) {
-            c.bowSec += std::chrono::duration<double>(std::chrono::steady_clock::now() - bow_t0).count();
-            c.bowKFs += (long long)rs.size();
-            for (size_t q = 0; q < rs.size(); q++) c.bowDesc += c.seq[rs[q]]->map.kfs[rk[q]].N;
+    T.charge(14);
+}
+
+// the keypoint counts of the new keyframes (sequence rs[q], id rk[q]) and, with `member` of each sized to `per` elements a keypoint, where the table writes it
+template <class Out, class V>
+static std::vector<Out*> new_kf_outputs(Ctx& c, const std::vector<int32_t>& rs, const std::vector<int32_t>& rk, std::vector<V> KeyFrm::*member, size_t per, std::vector<int32_t>& cnt) {
+    std::vector<Out*> out(rs.size()); cnt.resize(rs.size());
+    for (size_t q = 0; q < rs.size(); q++) {
+        KeyFrm& k = c.seq[rs[q]]->map.kfs[rk[q]];
+        (k.*member).resize((size_t)k.N * per);
+        cnt[q] = k.N; out[q] = (Out*)(k.*member).data();
+    }
+    return out;
+}
+
+// The frames that became keyframes are still on the device: the table keeps them (register_keyframes) and hands back mvKeys (KeyFrame::UnprojectStereo in
+// CreateNewMapPoints reads them; no frame does), mDescriptors when the frames' own stay on the device, and KeyFrame::ComputeBoW from the resident descriptors
+// (ProcessNewKeyFrame finds it done).  A table without voc_nodes_keyed leaves the loaded vocabulary to compute_bow (host descent).
+static int tk_register_keyframes(TrackPass& T) {
+    Ctx& c = T.c;
+    if (!c.ops.register_keyframes) return OSLAM_OK;
+    std::vector<int32_t> rs, rk, cnt;
+    for (int i = 0; i < T.S; i++) {
+        for (int kf : T.seq(i).pendingKF) { rs.push_back(i); rk.push_back(kf); }
+        T.seq(i).pendingKF.clear();
+    }
+    if (rs.empty()) return OSLAM_OK;
+    const int n = (int)rs.size();
+    int rc;
+    if ((rc = c.ops.register_keyframes(c.ops.ctx, n, rs.data(), rk.data()))) return rc;
+    if (c.ops.keyframe_raw_keys) {
+        std::vector<oslam_keypoint_t*> keys = new_kf_outputs<oslam_keypoint_t>(c, rs, rk, &KeyFrm::keys, 1, cnt);
+        if ((rc = c.ops.keyframe_raw_keys(c.ops.ctx, n, rs.data(), cnt.data(), keys.data()))) return rc;
+        if (T.seq(rs[0]).lazyDesc) {
+            std::vector<uint8_t*> desc = new_kf_outputs<uint8_t>(c, rs, rk, &KeyFrm::desc, 32, cnt);
+            if ((rc = c.ops.keyframe_descriptors(c.ops.ctx, n, rs.data(), cnt.data(), desc.data()))) return rc;
         }
     }
-    if ((rc = upd.run(c, true, true))) return rc;   // descriptors / normals of the points created this step
-    { c.sec[5] += tm.lap(); c.cpu[5] += tm.cpu; }
-    // store relative poses (:569-585), swap frames
-    for (int i = 0; i < S; i++) {
-        Seq& s = *c.seq[i];
+    if (c.realVoc ? !c.ops.voc_nodes_keyed : !c.ops.bow_nodes_keyed) return OSLAM_OK;
+    const auto bow_t0 = std::chrono::steady_clock::now();
+    std::vector<uint32_t*> nodes = new_kf_outputs<uint32_t>(c, rs, rk, &KeyFrm::bowNode, 1, cnt);
+    if (c.realVoc) rc = c.ops.voc_nodes_keyed(c.ops.ctx, c.realVoc, 4, n, rs.data(), rk.data(), cnt.data(), nodes.data());
+    else rc = c.ops.bow_nodes_keyed(c.ops.ctx, n, rs.data(), rk.data(), &c.voc.top[0][0], &c.voc.sub[0][0][0], cnt.data(), nodes.data());
+    if (rc) return rc;
+    c.bowSec += std::chrono::duration<double>(std::chrono::steady_clock::now() - bow_t0).count();
+    c.bowKFs += n;
+    for (int q = 0; q < n; q++) c.bowDesc += cnt[q];
+    return OSLAM_OK;
+}
+
+// store the relative poses (:569-585), hand out poses and states, swap the frames
+static void tk_store_poses(TrackPass& T) {
+    for (int i = 0; i < T.S; i++) {
+        Seq& s = T.seq(i);
         Frame& f = *s.cur;
-        if (s.resetRequested) {
-            // Track() returned before the relative pose was stored and before mLastFrame was replaced
+        if (s.resetRequested) {   // Track() returned before the relative pose was stored and before mLastFrame was replaced
         } else if (f.pose.valid) {
             RelPose r;
             r.Tcr = mul4(f.pose.Tcw, s.map.kfs[f.refKF].pose.Twc);
@@ -2458,18 +2428,53 @@ static int track_step(Ctx& c, const uint8_t* const* gray, const uint8_t* const* 
             r.lost = s.state == ST_LOST;
             s.rel.push_back(r);
         }
-        if (Tcw_out) {
-            if (f.pose.valid) memcpy(Tcw_out + (size_t)i * 16, f.pose.Tcw.m, 64);
-            else memset(Tcw_out + (size_t)i * 16, 0, 64);
+        if (T.in.Tcw_out) {
+            if (f.pose.valid) memcpy(T.in.Tcw_out + (size_t)i * 16, f.pose.Tcw.m, 64);
+            else memset(T.in.Tcw_out + (size_t)i * 16, 0, 64);
         }
-        if (state_out) state_out[i] = s.state;
+        if (T.in.state_out) T.in.state_out[i] = s.state;
         if (s.state != ST_NOT_INITIALIZED) std::swap(s.cur, s.last);   // mLastFrame = Frame(mCurrentFrame)
     }
-    { const double d_ = tm.lap(); c.sec[4] += d_; c.sec[14] += d_; c.cpu[4] += tm.cpu; c.cpu[14] += tm.cpu; }
-    if ((rc = finish_local_mapping(c))) return rc;   // (deferred schedule: the second half of the previous step's pass, before this step's pass)
-    return run_local_mapping(c, mapping);
+    T.charge(14);
 }
 
+// Tracking::Track (src/Tracking.cc:310-587) for all sequences, then LocalMapping::Run for those that inserted a keyframe
+static int track_step(Ctx& c, const TrackInput& in) {
+    c.started = true;
+    oslam_drv::ShardScope shard_scope(c.shard);   // library code below the operator table (local-BA preparation, BoW views) uses this handle's worker set
+    AccountScope acct_scope(&c.acct);   // the workers bill the tasks of this thread's batches (driver and operator table) to this handle; unbound again on every return
+    c.acct.worker_ns.store(0, std::memory_order_relaxed);
+    TrackPass T(c, in);
+    int rc;
+    if ((rc = tk_frames(T))) return rc;
+    tk_begin_frames(T);
+    if ((rc = tk_object_keypoints(T))) return rc;
+    if ((rc = tk_motion_model(T))) return rc;          // initial pose: motion model ...
+    if ((rc = tk_reference_keyframe(T))) return rc;    // ... or reference keyframe
+    if ((rc = tk_local_map(T))) return rc;
+    tk_after_tracking(T);
+    if ((rc = tk_register_keyframes(T))) return rc;
+    if ((rc = c.updTrack->run(c, true, true))) return rc;   // descriptors / normals of the points created in this step (:630-632, :1389-1391)
+    T.charge_op(5);
+    tk_store_poses(T);
+    if ((rc = finish_local_mapping(c))) return rc;   // (deferred schedule: the second half of the previous step's pass, before this step's pass)
+    return run_local_mapping(c, T.mapping);
+}
+
+// the checks of the six oslam_slam_track_* entry points, in their order, then the step.  fn: the entry point's name, for the message
+static int track_checked(oslam_slam* h, const char* fn, const TrackInput& in) {
+    const bool stereo = in.kind == TrackInput::STEREO, raw16 = in.kind == TrackInput::RAW16;
+    const void* second = stereo ? (const void*)in.right : raw16 ? (const void*)in.depth16 : (const void*)in.depth;
+    if (!h || !in.gray || !second) { oslam::set_error("%s: bad argument", fn); return OSLAM_E_INVALID; }
+    const Ctx& c = h->c;
+    if (stereo && (!c.stereo || !c.ops.frames_stereo)) { oslam::set_error("%s needs cfg.sensor = 1 (STEREO) and a stereo-capable operator table", fn); return OSLAM_E_INVALID; }
+    if (!stereo && c.stereo) { oslam::set_error("%s on a STEREO handle", fn); return OSLAM_E_INVALID; }
+    if (raw16 && !c.ops.frames_rgbd_raw16) { oslam::set_error("%s: the operator table has no frames_rgbd_raw16", fn); return OSLAM_E_INVALID; }
+    if (in.objs && !raw16 && in.mask_stride < c.cfg.width) { oslam::set_error("%s: mask_stride < width", fn); return OSLAM_E_INVALID; }
+    if (in.objs && raw16 && in.mask_stride != 0 && in.mask_stride < c.cfg.width) { oslam::set_error("%s: mask_stride must be 0 (bitmaps) or >= width", fn); return OSLAM_E_INVALID; }
+    if (in.objs && raw16 && in.mask_stride == 0 && !in.on_device) { oslam::set_error("%s: one-bit masks must be device-accessible (on_device != 0)", fn); return OSLAM_E_INVALID; }
+    return track_step(h->c, in);
+}
 
 // consistency of the observation graph (stats[15]): observation indices in range, Observations() = sum over the list, no observations on
 // bad points, spanning-tree parents alive (covisibility lists may legitimately keep one-sided links to culled keyframes, src/KeyFrame.cc:367)
@@ -2562,27 +2567,23 @@ void oslam_slam_destroy(oslam_slam_t* h) {
 
 int oslam_slam_track_rgbd(oslam_slam_t* h, const uint8_t* const* gray, int gray_stride, const float* const* depth, int depth_pitch,
                           int on_device, const double* timestamps, float* Tcw_out, int32_t* state_out) {
-    if (!h || !gray || !depth) { oslam::set_error("oslam_slam_track_rgbd: bad argument"); return OSLAM_E_INVALID; }
-    if (h->c.stereo) { oslam::set_error("oslam_slam_track_rgbd on a STEREO handle"); return OSLAM_E_INVALID; }
-    return track_step(h->c, gray, nullptr, gray_stride, depth, depth_pitch, on_device, timestamps, nullptr, 0, Tcw_out, state_out);
+    TrackInput in(TrackInput::RGBD, gray, gray_stride, on_device, timestamps, nullptr, 0, Tcw_out, state_out);
+    in.depth = depth; in.depth_pitch = depth_pitch;
+    return track_checked(h, "oslam_slam_track_rgbd", in);
 }
 
 int oslam_slam_track_rgbd_objects(oslam_slam_t* h, const uint8_t* const* gray, int gray_stride, const float* const* depth, int depth_pitch, int on_device,
                                   const double* timestamps, const oslam_slam_objects_t* objs, int mask_stride, float* Tcw_out, int32_t* state_out) {
-    if (!h || !gray || !depth) { oslam::set_error("oslam_slam_track_rgbd_objects: bad argument"); return OSLAM_E_INVALID; }
-    if (h->c.stereo) { oslam::set_error("oslam_slam_track_rgbd_objects on a STEREO handle"); return OSLAM_E_INVALID; }
-    if (objs && mask_stride < h->c.cfg.width) { oslam::set_error("oslam_slam_track_rgbd_objects: mask_stride < width"); return OSLAM_E_INVALID; }
-    return track_step(h->c, gray, nullptr, gray_stride, depth, depth_pitch, on_device, timestamps, objs, mask_stride, Tcw_out, state_out);
+    TrackInput in(TrackInput::RGBD, gray, gray_stride, on_device, timestamps, objs, mask_stride, Tcw_out, state_out);
+    in.depth = depth; in.depth_pitch = depth_pitch;
+    return track_checked(h, "oslam_slam_track_rgbd_objects", in);
 }
 
 int oslam_slam_track_rgbd_raw16(oslam_slam_t* h, const uint8_t* const* gray, int gray_stride, const uint16_t* const* depth16, int depth_pitch, float depth_factor,
                                 int on_device, const double* timestamps, const oslam_slam_objects_t* objs, int mask_stride, float* Tcw_out, int32_t* state_out) {
-    if (!h || !gray || !depth16) { oslam::set_error("oslam_slam_track_rgbd_raw16: bad argument"); return OSLAM_E_INVALID; }
-    if (h->c.stereo) { oslam::set_error("oslam_slam_track_rgbd_raw16 on a STEREO handle"); return OSLAM_E_INVALID; }
-    if (!h->c.ops.frames_rgbd_raw16) { oslam::set_error("oslam_slam_track_rgbd_raw16: the operator table has no frames_rgbd_raw16"); return OSLAM_E_INVALID; }
-    if (objs && mask_stride != 0 && mask_stride < h->c.cfg.width) { oslam::set_error("oslam_slam_track_rgbd_raw16: mask_stride must be 0 (bitmaps) or >= width"); return OSLAM_E_INVALID; }
-    if (objs && mask_stride == 0 && !on_device) { oslam::set_error("oslam_slam_track_rgbd_raw16: one-bit masks must be device-accessible (on_device != 0)"); return OSLAM_E_INVALID; }
-    return track_step(h->c, gray, nullptr, gray_stride, nullptr, depth_pitch, on_device, timestamps, objs, mask_stride, Tcw_out, state_out, depth16, depth_factor);
+    TrackInput in(TrackInput::RAW16, gray, gray_stride, on_device, timestamps, objs, mask_stride, Tcw_out, state_out);
+    in.depth16 = depth16; in.depth_pitch = depth_pitch; in.depth_factor = depth_factor;
+    return track_checked(h, "oslam_slam_track_rgbd_raw16", in);
 }
 
 int oslam_slam_set_vocabulary(oslam_slam_t* h, const oslam_voc_t* voc) {
@@ -2636,17 +2637,16 @@ int oslam_slam_object_stats(oslam_slam_t* h, int seq, int64_t out[8]) {
 
 int oslam_slam_track_stereo(oslam_slam_t* h, const uint8_t* const* left, const uint8_t* const* right, int gray_stride, int on_device,
                             const double* timestamps, float* Tcw_out, int32_t* state_out) {
-    if (!h || !left || !right) { oslam::set_error("oslam_slam_track_stereo: bad argument"); return OSLAM_E_INVALID; }
-    if (!h->c.stereo || !h->c.ops.frames_stereo) { oslam::set_error("oslam_slam_track_stereo needs cfg.sensor = 1 (STEREO) and a stereo-capable operator table"); return OSLAM_E_INVALID; }
-    return track_step(h->c, left, right, gray_stride, nullptr, 0, on_device, timestamps, nullptr, 0, Tcw_out, state_out);
+    TrackInput in(TrackInput::STEREO, left, gray_stride, on_device, timestamps, nullptr, 0, Tcw_out, state_out);
+    in.right = right;
+    return track_checked(h, "oslam_slam_track_stereo", in);
 }
 
 int oslam_slam_track_stereo_objects(oslam_slam_t* h, const uint8_t* const* left, const uint8_t* const* right, int gray_stride, int on_device,
                                     const double* timestamps, const oslam_slam_objects_t* objs, int mask_stride, float* Tcw_out, int32_t* state_out) {
-    if (!h || !left || !right) { oslam::set_error("oslam_slam_track_stereo_objects: bad argument"); return OSLAM_E_INVALID; }
-    if (!h->c.stereo || !h->c.ops.frames_stereo) { oslam::set_error("oslam_slam_track_stereo_objects needs cfg.sensor = 1 (STEREO) and a stereo-capable operator table"); return OSLAM_E_INVALID; }
-    if (objs && mask_stride < h->c.cfg.width) { oslam::set_error("oslam_slam_track_stereo_objects: mask_stride < width"); return OSLAM_E_INVALID; }
-    return track_step(h->c, left, right, gray_stride, nullptr, 0, on_device, timestamps, objs, mask_stride, Tcw_out, state_out);
+    TrackInput in(TrackInput::STEREO, left, gray_stride, on_device, timestamps, objs, mask_stride, Tcw_out, state_out);
+    in.right = right;
+    return track_checked(h, "oslam_slam_track_stereo_objects", in);
 }
 
 static void twc_rows(const M4& Tcw, float* o) {   // Rwc = Rcw.t(), twc = -Rwc*tcw (src/System.cc:423-424)

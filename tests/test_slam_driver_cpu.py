@@ -385,3 +385,77 @@ def test_create_new_map_points_in_one_batch_equals_the_neighbour_rounds(oracle, 
     for q in range(S):
         st = a.stats(q)
         assert st == b.stats(q) and st["points_triangulated"] > 0, st
+
+
+def test_tracking_entry_points_refuse_bad_calls_with_their_codes_and_messages(oracle):
+    """Every refusal of the six oslam_slam_track_* entry points (include/oslam_slam.h), by return code and oslam_last_error() text: NULL handle or image arrays,
+    the wrong sensor kind, a table without frames_stereo / frames_rgbd_raw16, the mask_stride rules and the one-bit-mask rule of raw16 — in the order the checks
+    are made — on one RGB-D and one STEREO handle with S = 1 and no frame tracked.  The oracle's table has no frames_rgbd_raw16: the raw16 rules behind that
+    check are reached through a copy of the table whose entry is set (the refusals return before anything is called through it).  The refusals raised inside a
+    step (too many detections, detections without masks, a table without semantic operators) take one frame of the smallest scene, of which the handles
+    (a quarter of the scenes' image size, to keep Frame::Frame short) see the top left corner."""
+    from object_slam_amd import scene
+    L = slam.lib()
+    INVALID = -1
+    w2, h2 = W // 2, H // 2
+
+    def table(sensor, **entries):
+        cfg = slam.make_config(w2, h2, 1, sensor=sensor)
+        ops = oracle_ops(cfg)
+        for k, v in entries.items():
+            setattr(ops, k, v)
+        return slam.System(cfg, ops)
+
+    rgbd, stereo = table(slam.RGBD), table(slam.STEREO)
+    assert not oracle_ops(rgbd.cfg).frames_rgbd_raw16
+    raw = table(slam.RGBD, frames_rgbd_raw16=oracle_ops(rgbd.cfg).frames_rgbd)
+    no_stereo = table(slam.STEREO, frames_stereo=None)
+    img = (C.c_void_p * 1)(1)   # a non-NULL image table: no refusal below reads through it
+    objs = (slam.SlamObjects * 1)()
+    out = (slam.ptr(rgbd.Tcw), slam.ptr(rgbd.state))
+    i, f = C.c_int, C.c_float
+
+    def refused(text, fn, *args):
+        assert getattr(L, fn)(*args, *out) == INVALID, (fn, text)
+        assert L.oslam_last_error().decode() == text, (fn, L.oslam_last_error())
+
+    for h, a, b in ((None, img, img), (rgbd.h, None, img), (rgbd.h, img, None), (stereo.h, None, img)):   # (bad arguments come before the sensor kind)
+        refused("oslam_slam_track_rgbd: bad argument", "oslam_slam_track_rgbd", h, a, i(W), b, i(W), i(0), None)
+        refused("oslam_slam_track_rgbd_objects: bad argument", "oslam_slam_track_rgbd_objects", h, a, i(W), b, i(W), i(0), None, None, i(0))
+        refused("oslam_slam_track_rgbd_raw16: bad argument", "oslam_slam_track_rgbd_raw16", h, a, i(W), b, i(W), f(5000), i(0), None, None, i(0))
+    for h, a, b in ((None, img, img), (stereo.h, None, img), (stereo.h, img, None), (rgbd.h, img, None)):
+        refused("oslam_slam_track_stereo: bad argument", "oslam_slam_track_stereo", h, a, b, i(W), i(0), None)
+        refused("oslam_slam_track_stereo_objects: bad argument", "oslam_slam_track_stereo_objects", h, a, b, i(W), i(0), None, None, i(0))
+    # the wrong sensor kind (before the table's entries and the mask rules), and a STEREO handle over a table without frames_stereo
+    refused("oslam_slam_track_rgbd on a STEREO handle", "oslam_slam_track_rgbd", stereo.h, img, i(W), img, i(W), i(0), None)
+    refused("oslam_slam_track_rgbd_objects on a STEREO handle", "oslam_slam_track_rgbd_objects", stereo.h, img, i(W), img, i(W), i(0), None, objs, i(0))
+    refused("oslam_slam_track_rgbd_raw16 on a STEREO handle", "oslam_slam_track_rgbd_raw16", stereo.h, img, i(W), img, i(W), f(5000), i(0), None, objs, i(1))
+    for h in (rgbd.h, no_stereo.h):
+        refused("oslam_slam_track_stereo needs cfg.sensor = 1 (STEREO) and a stereo-capable operator table", "oslam_slam_track_stereo", h, img, img, i(W), i(0), None)
+        refused("oslam_slam_track_stereo_objects needs cfg.sensor = 1 (STEREO) and a stereo-capable operator table", "oslam_slam_track_stereo_objects",
+                h, img, img, i(W), i(0), None, objs, i(0))
+    # mask_stride < width counts as soon as detections are passed, whatever their number
+    refused("oslam_slam_track_rgbd_objects: mask_stride < width", "oslam_slam_track_rgbd_objects", rgbd.h, img, i(W), img, i(W), i(0), None, objs, i(w2 - 1))
+    refused("oslam_slam_track_stereo_objects: mask_stride < width", "oslam_slam_track_stereo_objects", stereo.h, img, img, i(W), i(0), None, objs, i(w2 - 1))
+    # raw16: the table's entry first, then mask_stride 0 (bitmaps) or >= width, then one-bit masks on the device only
+    refused("oslam_slam_track_rgbd_raw16: the operator table has no frames_rgbd_raw16", "oslam_slam_track_rgbd_raw16",
+            rgbd.h, img, i(W), img, i(W), f(5000), i(0), None, objs, i(1))
+    for ms in (1, w2 - 1, -1):
+        refused("oslam_slam_track_rgbd_raw16: mask_stride must be 0 (bitmaps) or >= width", "oslam_slam_track_rgbd_raw16",
+                raw.h, img, i(W), img, i(W), f(5000), i(0), None, objs, i(ms))
+    refused("oslam_slam_track_rgbd_raw16: one-bit masks must be device-accessible (on_device != 0)", "oslam_slam_track_rgbd_raw16",
+            raw.h, img, i(W), img, i(W), f(5000), i(0), None, objs, i(0))
+    # inside a step, after Frame::Frame: the detections of sequence 0
+    q = scene.make_rgbd_sequence(0, 1, speed=2.0, with_masks=False)   # frame 0 of slam_common.make_scene_streams(1, 1); its masks are not rendered: none is read
+    gp, dp = (C.c_void_p * 1)(slam.ptr(q["gray"][0]).value), (C.c_void_p * 1)(slam.ptr(q["depth"][0]).value)
+    masks = (C.c_void_p * 9)(*[gp[0]] * 9)
+    many, bare = (slam.SlamObjects * 1)(), (slam.SlamObjects * 1)()
+    many[0].n, many[0].masks = 9, C.cast(masks, C.POINTER(C.c_void_p))
+    bare[0].n = 1
+    step = (gp, i(W), dp, i(W), i(0), None)
+    refused("track: sequence 0 has 9 detections (max 8) or no masks", "oslam_slam_track_rgbd_objects", rgbd.h, *step, many, i(W))
+    refused("track: sequence 0 has 1 detections (max 8) or no masks", "oslam_slam_track_rgbd_objects", rgbd.h, *step, bare, i(W))
+    many[0].n = 8
+    plain = table(slam.RGBD, object_kps=None)
+    refused("track: this operator table has no semantic operators", "oslam_slam_track_rgbd_objects", plain.h, *step, many, i(W))
+    assert rgbd.stats(0)["frames"] == 2 and raw.stats(0)["frames"] == 0 and stereo.stats(0)["frames"] == 0   # only the refusals inside a step began a frame
