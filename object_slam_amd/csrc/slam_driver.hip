@@ -377,8 +377,7 @@ struct MpUpdate {
             const int i0 = ch * chunk, i1 = std::min(P, i0 + chunk);
             for (int i = i0; i < i1; i++) {
                 if (i + kPF < i1) prefetch_mp(&c.seq[items[i + kPF].seq]->map.mps[items[i + kPF].p]);
-                if (i + kPF / 2 < i1) __builtin_prefetch(c.seq[items[i + kPF / 2].seq]->map.mps[items[i + kPF / 2].p].obs.data());
-                if (do_normal && i + kPF / 2 < i1) __builtin_prefetch(c.seq[items[i + kPF / 2].seq]->map.mps[items[i + kPF / 2].p].okp.data());   // (the reference keyframe's octave is read from the list beside obs)
+                if (i + kPF / 2 < i1) __builtin_prefetch(c.seq[items[i + kPF / 2].seq]->map.mps[items[i + kPF / 2].p].obs.data());   // (the reference keyframe's octave is read from the same block)
                 const Map& m = c.seq[items[i].seq]->map;
                 const MapPt& p = m.mps[items[i].p];
                 const int n = start[i + 1] - start[i];
@@ -2727,8 +2726,8 @@ int oslam_slam_debug_point(oslam_slam_t* h, int seq, int id, uint8_t host[64], u
     const Map& m = h->c.seq[seq]->map;
     if (id < 0 || id >= (int)m.mps.size()) { oslam::set_error("oslam_slam_debug_point: no such point"); return OSLAM_E_INVALID; }
     const MapPt& p = m.mps[id];
-    static_assert(offsetof(MapPt, desc) == 32 && offsetof(MapPt, minD) == 24, "the first 64 bytes of MapPt are the resident record");
-    memcpy(host, &p, 64);
+    // the resident record: position, normal, minD, maxD, descriptor (the host record keeps them in two cache lines: slam_map.h)
+    memcpy(host, p.pos, 12); memcpy(host + 12, p.normal, 12); memcpy(host + 24, &p.minD, 4); memcpy(host + 28, &p.maxD, 4); memcpy(host + 32, p.desc, 32);
     *bad = m.pBad[id] || p.obs.empty();
     if (!h->c.ops.point_record) { oslam::set_error("oslam_slam_debug_point: the operator table keeps no resident map points"); return OSLAM_E_INVALID; }
     return h->c.ops.point_record(h->c.ops.ctx, seq, id, resident);

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/oslam_slam.h"
+#include "seq_arena.h"
 
 namespace oslam_drv {
 
@@ -110,23 +111,54 @@ struct Frame {
 };
 
 // The keypoint behind an observation: mvKeysUn.pt, mvuRight and octave of keypoint `second` of keyframe `first`, copied when the observation is added (a
-// keyframe's keypoints never change: include/KeyFrame.h:163-175 are const members).  Kept in a list PARALLEL to MapPt::obs: the loops that need the keypoint
-// (the local-BA graph gather, KeyFrameCulling, the observation counts) then stay inside the point's two lists instead of taking a dependent cache miss in the
-// keyframe's arrays per observation, and the loops that only need (keyframe, index) — UpdateLocalKeyFrames — keep walking 8 bytes per observation.
+// keyframe's keypoints never change: include/KeyFrame.h:163-175 are const members).  The loops that need the keypoint (the local-BA graph gather,
+// KeyFrameCulling, the observation counts) then stay inside the point's list instead of taking a dependent cache miss in the keyframe's arrays per observation.
 struct ObsKp { float x, y, ur; int octave; };
+typedef std::pair<int, int> Obs;   // (keyframe id, keypoint index)
 
-struct MapPt {
+// A point's observation list: ONE block of the map's arena (seq_arena.h) that holds `cap` Obs followed by `cap` ObsKp, the first n of each in use, ascending
+// keyframe id; capacities double from 2.  The loops that only need (keyframe, index) — UpdateLocalKeyFrames — walk 8 bytes per observation at the front of
+// the block, the keypoints follow in the next lines of the same block: one dependent access per point, one prefetch.  MapPt::obs and MapPt::okp are two
+// read-only views of the same three words (a union of standard-layout structs with a common initial sequence); Map's add_observation / erase_observation /
+// set_bad_point / replace_point are the only writers.
+struct ObsListRaw { char* blk; uint32_t n, cap; };
+struct ObsView {
+    char* blk; uint32_t n, cap;
+    size_t size() const { return n; }
+    bool empty() const { return n == 0; }
+    const Obs* data() const { return (const Obs*)blk; }
+    const Obs* begin() const { return data(); }
+    const Obs* end() const { return data() + n; }
+    const Obs& operator[](size_t i) const { return data()[i]; }
+    const Obs& front() const { return data()[0]; }
+};
+struct OkpView {
+    char* blk; uint32_t n, cap;
+    size_t size() const { return n; }
+    bool empty() const { return n == 0; }
+    const ObsKp* data() const { return (const ObsKp*)(blk + (size_t)cap * sizeof(Obs)); }
+    const ObsKp* begin() const { return data(); }
+    const ObsKp* end() const { return data() + n; }
+    const ObsKp& operator[](size_t i) const { return data()[i]; }
+    const ObsKp& front() const { return data()[0]; }
+};
+constexpr size_t obs_block_bytes(uint32_t cap) { return (size_t)cap * (sizeof(Obs) + sizeof(ObsKp)); }
+
+// Two cache lines.  The first holds what the per-frame loops of tracking and the list walks read (the list, position, viewing cone, reference keyframe, the
+// per-frame stamps), the second what only the MapPoint updates and CreateNewMapPoints touch.
+struct alignas(64) MapPt {
+    union { ObsListRaw lst = {nullptr, 0, 0}; ObsView obs; OkpView okp; };   // obs[i] = (keyframe id, keypoint index), okp[i] = the keypoint of obs[i]
     float pos[3];
     float normal[3] = {0, 0, 0};
     float minD = 0, maxD = 0;
-    uint8_t desc[32];
-    // (nObs, mnVisible, mnFound, mbBad, mpReplaced and mnLastFrameSeen live in Map's dense per-point arrays: Map::pNObs ...)
-    int firstKF = 0, firstFrame = 0, refKF = -1;
-    std::vector<std::pair<int, int>> obs;        // (keyframe id, keypoint index), ascending keyframe id
-    std::vector<ObsKp> okp;                      // okp[i] = the keypoint of obs[i]
+    int refKF = -1;
     int trackRefForFrame = 0;   // zero-initialised like the reference
     // driver scratch of SearchInNeighbors: position of the point in the current keyframe's point list (valid while fuseListStamp == current keyframe id + 1)
     int fuseListIdx = 0, fuseListStamp = 0;
+    // ---- second line ----
+    uint8_t desc[32];
+    // (nObs, mnVisible, mnFound, mbBad, mpReplaced and mnLastFrameSeen live in Map's dense per-point arrays: Map::pNObs ...)
+    int firstKF = 0, firstFrame = 0;
     // bookkeeping of the driver (not in the reference): obsVer counts the changes of the observation list; (updVer, updStep) = obsVer and the local-mapping
     // step of the last full update (descriptor + normal / depth), so that an update whose inputs cannot have changed since is not repeated
     int obsVer = 0, updVer = -1, updStep = -1;
@@ -135,25 +167,31 @@ struct MapPt {
         return -1;
     }
 };
+static_assert(sizeof(MapPt) == 128 && offsetof(MapPt, desc) == 64, "MapPt: two cache lines, the per-frame fields in the first");
 
-// The driver's per-frame loops gather MapPt records by index in keypoint / list order, i.e. at random over a table of several MB per sequence: each
-// loop requests the records of a later iteration early (a MapPt spans three cache lines; its observation list is a second, dependent access).
+// The point table and the dense per-point arrays: chunked arrays on the map's arena (no whole-table copy when they grow, the blocks lie with the rest of
+// the sequence's map).  64 records = 8 KiB per block of the table (half an arena chunk), 256 entries per block of a dense array: small blocks, because on
+// huge pages the unused tail of every last block is resident (seven arrays and the table in each of thousands of sequences).
+typedef ChunkVec<MapPt, 6> PtTable;
+static_assert((sizeof(MapPt) << 6) <= SeqArena::kMaxSmall, "a block of the point table is an arena block");
+template <class T> using PtArray = ChunkVec<T, 8>;
+
+// The driver's per-frame loops gather MapPt records by index in keypoint / list order, i.e. at random over a table of several hundred KB per sequence: each
+// loop requests the records of a later iteration early (a MapPt spans two cache lines; its observation list is a second, dependent access: one block).
 constexpr int kPF = 12;
-inline void prefetch_mp(const MapPt* p) { __builtin_prefetch(p); __builtin_prefetch((const char*)p + 64); __builtin_prefetch((const char*)p + 128); }
+inline void prefetch_mp(const MapPt* p) { __builtin_prefetch(p); __builtin_prefetch((const char*)p + 64); }
 template <class Ids>
-inline void prefetch_ahead(const std::vector<MapPt>& mps, const Ids& ids, size_t i, size_t n) {
+inline void prefetch_ahead(const PtTable& mps, const Ids& ids, size_t i, size_t n) {
     if (i + kPF < n) { const int q = ids[i + kPF]; if (q >= 0) prefetch_mp(&mps[q]); }
 }
 template <class Ids>
-inline void prefetch_obs_ahead(const std::vector<MapPt>& mps, const Ids& ids, size_t i, size_t n) {   // with prefetch_ahead: the list of a record requested kPF / 2 iterations ago
+inline void prefetch_obs_ahead(const PtTable& mps, const Ids& ids, size_t i, size_t n) {   // with prefetch_ahead: the list of a record requested kPF / 2 iterations ago
     prefetch_ahead(mps, ids, i, n);
     if (i + kPF / 2 < n) { const int q = ids[i + kPF / 2]; if (q >= 0) __builtin_prefetch(mps[q].obs.data()); }
 }
-
 template <class Ids>
-inline void prefetch_okp_ahead(const std::vector<MapPt>& mps, const Ids& ids, size_t i, size_t n) {   // prefetch_obs_ahead + the parallel keypoint list
+inline void prefetch_okp_ahead(const PtTable& mps, const Ids& ids, size_t i, size_t n) {   // (the keypoints lie in the same block as the observations)
     prefetch_obs_ahead(mps, ids, i, n);
-    if (i + kPF / 2 < n) { const int q = ids[i + kPF / 2]; if (q >= 0) __builtin_prefetch(mps[q].okp.data()); }
 }
 
 struct KeyFrm {
@@ -179,23 +217,29 @@ struct RelPose { M4 Tcr; int refKF; double stamp; bool lost; };
 
 // One sequence's Map + the map-side methods of KeyFrame / MapPoint.
 struct Map {
-    std::vector<MapPt> mps;
+    // Owns every block the point table, the dense per-point arrays and the observation lists live in; a reset (`map = Map()`) or the destructor hands its
+    // chunks back to the process-wide pool.  No lock: one thread at a time touches a sequence.  (Declared first: the containers below point into it.)
+    SeqArena arena;
+    PtTable mps;
     std::vector<KeyFrm> kfs;
+    Map() = default;
+    Map(Map&&) = default;
+    Map& operator=(Map&&) = default;
     int nKFsInMap = 0, nMPsInMap = 0;
     int64_t nCulledKF = 0, nCulledMP = 0;
 
     // ---- MapPoint (src/MapPoint.cc) ----
     // The scalars the per-frame loops of tracking read or bump for every matched / visible point, dense by point id: nObs (Observations()), mnVisible, mnFound,
     // mnLastFrameSeen, mpReplaced (-1: none) and mbBad.  A loop over a frame's points then touches 4 bytes at neighbouring ids (the points a keyframe created have
-    // consecutive ids) instead of one or two cache lines of a 170-byte MapPt record per point, whose maps (several MB per sequence, thousands of sequences per
+    // consecutive ids) instead of a cache line of a 128-byte MapPt record per point, whose maps (several MB per sequence, thousands of sequences per
     // rank) never stay in a cache from one frame to the next.
-    std::vector<int> pNObs, pVisible, pFound, pLastSeen, pReplaced;
-    std::vector<uint8_t> pBad;
+    PtArray<int> pNObs, pVisible, pFound, pLastSeen, pReplaced;
+    PtArray<uint8_t> pBad;
     // Octave histogram of a point's observations, byte o of pLvl[p] = observations whose keypoint has octave o (kept beside obs / okp by the four functions that
     // change the lists).  KeyFrameCulling asks "at least three OTHER observations at octave <= l + 1": the histogram answers it without walking the lists unless
     // exactly three observations qualify (then it matters whether the keyframe's own observation is one of them).  lvlOverflow: a count reached 255 or an octave
     // was >= 8 — the histogram is then not trusted for this map and the lists are walked as before.
-    std::vector<uint64_t> pLvl;
+    PtArray<uint64_t> pLvl;
     bool lvlOverflow = false;
     void lvl_add(int p, int oct) {
         if ((unsigned)oct >= 8u || ((pLvl[p] >> (8 * oct)) & 0xFFull) == 0xFFull) { lvlOverflow = true; return; }
@@ -279,11 +323,47 @@ struct Map {
         p.pos[0] = x[0]; p.pos[1] = x[1]; p.pos[2] = x[2];
         memset(p.desc, 0, 32);
         p.firstKF = refKF; p.firstFrame = refFrame; p.refKF = refKF;
-        mps.push_back(p);
-        pNObs.push_back(0); pVisible.push_back(1); pFound.push_back(1);   // src/MapPoint.cc:33-46
-        pLastSeen.push_back(0); pReplaced.push_back(-1); pBad.push_back(0); pLvl.push_back(0);
+        mps.push_back(arena, p);
+        pNObs.push_back(arena, 0); pVisible.push_back(arena, 1); pFound.push_back(arena, 1);   // src/MapPoint.cc:33-46
+        pLastSeen.push_back(arena, 0); pReplaced.push_back(arena, -1); pBad.push_back(arena, 0); pLvl.push_back(arena, 0);
         return (int)mps.size() - 1;
     }
+    // ---- the only writers of the observation lists ----
+    // entry `at` of the list becomes (e, o), the entries behind it move up by one (a full block is replaced by one of twice the capacity)
+    void list_insert(MapPt& m, size_t at, const Obs& e, const ObsKp& o) {
+        ObsListRaw& l = m.lst;
+        const size_t n = l.n;
+        if (l.n == l.cap) {
+            const uint32_t ncap = l.cap ? l.cap * 2 : 2;
+            char* nb = (char*)arena.alloc(obs_block_bytes(ncap));
+            Obs* no = (Obs*)nb; ObsKp* nk = (ObsKp*)(nb + (size_t)ncap * sizeof(Obs));
+            if (n) {
+                const Obs* oo = m.obs.data(); const ObsKp* ok = m.okp.data();
+                memcpy((void*)no, (const void*)oo, at * sizeof(Obs)); memcpy((void*)(no + at + 1), (const void*)(oo + at), (n - at) * sizeof(Obs));
+                memcpy(nk, ok, at * sizeof(ObsKp)); memcpy(nk + at + 1, ok + at, (n - at) * sizeof(ObsKp));
+            }
+            arena.dealloc(l.blk, obs_block_bytes(l.cap));
+            l.blk = nb; l.cap = ncap;
+        } else {
+            Obs* oo = (Obs*)l.blk; ObsKp* ok = (ObsKp*)(l.blk + (size_t)l.cap * sizeof(Obs));
+            memmove((void*)(oo + at + 1), (const void*)(oo + at), (n - at) * sizeof(Obs));
+            memmove(ok + at + 1, ok + at, (n - at) * sizeof(ObsKp));
+        }
+        ((Obs*)l.blk)[at] = e;
+        ((ObsKp*)(l.blk + (size_t)l.cap * sizeof(Obs)))[at] = o;
+        l.n++;
+    }
+    void list_erase(MapPt& m, size_t at) {   // (the block keeps its capacity)
+        ObsListRaw& l = m.lst;
+        Obs* oo = (Obs*)l.blk; ObsKp* ok = (ObsKp*)(l.blk + (size_t)l.cap * sizeof(Obs));
+        memmove((void*)(oo + at), (const void*)(oo + at + 1), (l.n - at - 1) * sizeof(Obs));
+        memmove(ok + at, ok + at + 1, (l.n - at - 1) * sizeof(ObsKp));
+        l.n--;
+    }
+    // the list leaves the point (which is empty afterwards); the caller walks it and gives it to list_drop
+    ObsListRaw list_detach(MapPt& m) { const ObsListRaw l = m.lst; m.lst = ObsListRaw{nullptr, 0, 0}; return l; }
+    void list_drop(const ObsListRaw& l) { arena.dealloc(l.blk, obs_block_bytes(l.cap)); }
+
     void add_observation(int p, int kf, int idx) {   // :196-207
         MapPt& m = mps[p];
         size_t at = 0;
@@ -291,8 +371,7 @@ struct Map {
         if (at < m.obs.size() && m.obs[at].first == kf) return;
         const KeyFrm& k = kfs[kf];
         const ObsKp o = {k.keysUn[idx].x, k.keysUn[idx].y, k.uRight[idx], k.keysUn[idx].octave};
-        m.obs.insert(m.obs.begin() + at, std::make_pair(kf, idx));
-        m.okp.insert(m.okp.begin() + at, o);
+        list_insert(m, at, std::make_pair(kf, idx), o);
         lvl_add(p, o.octave);
         pNObs[p] += o.ur >= 0 ? 2 : 1;
         m.obsVer++;
@@ -302,11 +381,11 @@ struct Map {
         MapPt& m = mps[p];
         if (!pBad[p]) { nMPsInMap--; nCulledMP++; }
         pBad[p] = 1;
-        std::vector<std::pair<int, int>> o;
-        o.swap(m.obs);
-        std::vector<ObsKp>().swap(m.okp);   // (a bad point never gets an observation again: its lists' memory goes back, 40 % of the points a sequence creates end here)
+        const ObsListRaw o = list_detach(m);   // (a bad point never gets an observation again: its block goes back to the arena, 40 % of the points a sequence creates end here)
         pLvl[p] = 0;
-        for (auto& e : o) { set_kf_mp(e.first, e.second, -1); jr_okf(JR_OKF_CLR, e.first, e.second, p); }
+        const Obs* oe = (const Obs*)o.blk;
+        for (uint32_t i = 0; i < o.n; i++) { set_kf_mp(oe[i].first, oe[i].second, -1); jr_okf(JR_OKF_CLR, oe[i].first, oe[i].second, p); }
+        list_drop(o);
         jr_pt(p);
     }
     void erase_observation(int p, int kf) {          // :209-239
@@ -314,11 +393,11 @@ struct Map {
         bool bad = false;
         for (size_t i = 0; i < m.obs.size(); i++)
             if (m.obs[i].first == kf) {
-                pNObs[p] -= m.okp[i].ur >= 0 ? 2 : 1;
+                const ObsKp o = m.okp[i];
+                pNObs[p] -= o.ur >= 0 ? 2 : 1;
                 jr_okf(JR_OKF_CLR, kf, m.obs[i].second, p);
-                m.obs.erase(m.obs.begin() + i);
-                lvl_sub(p, m.okp[i].octave);
-                m.okp.erase(m.okp.begin() + i);
+                list_erase(m, i);
+                lvl_sub(p, o.octave);
                 m.obsVer++;
                 if (m.refKF == kf && !m.obs.empty()) m.refKF = m.obs.front().first;
                 if (pNObs[p] <= 2) bad = true;
@@ -331,15 +410,15 @@ struct Map {
     bool replace_point(int p, int by) {
         if (p == by) return false;
         MapPt& m = mps[p];
-        std::vector<std::pair<int, int>> o;
-        o.swap(m.obs);
-        std::vector<ObsKp>().swap(m.okp);
+        const ObsListRaw o = list_detach(m);
         pLvl[p] = 0;
         if (!pBad[p]) { nMPsInMap--; }
         pBad[p] = 1;
         pReplaced[p] = by;
         const int nvisible = pVisible[p], nfound = pFound[p];
-        for (auto& e : o) {
+        const Obs* oe = (const Obs*)o.blk;
+        for (uint32_t i = 0; i < o.n; i++) {
+            const Obs e = oe[i];
             jr_okf(JR_OKF_CLR, e.first, e.second, p);
             if (mps[by].obs_index(e.first) < 0) {
                 set_kf_mp(e.first, e.second, by);
@@ -348,6 +427,7 @@ struct Map {
                 set_kf_mp(e.first, e.second, -1);
             }
         }
+        list_drop(o);
         jr_pt(p);
         pFound[by] += nfound;
         pVisible[by] += nvisible;
