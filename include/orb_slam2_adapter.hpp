@@ -1,6 +1,6 @@
 // orb_slam2_adapter.hpp — header-only C++ adapter that re-exposes the reference's class API on top of the C ABI in oslam_hip.h:
 // ORB_SLAM2::ORBextractor (include/ORBextractor.h:45-110), ORB_SLAM2::ORBmatcher (include/ORBmatcher.h:41-83: the projection searches, the relocalisation one included,
-// SearchByBoW, SearchForTriangulation, Fuse, SearchBySim3, DescriptorDistance), Frame::ComputeStereoMatches (src/Frame.cc:706), ORB_SLAM2::Optimizer
+// SearchForInitialization, SearchByBoW, SearchForTriangulation, Fuse, SearchBySim3, DescriptorDistance), Frame::ComputeStereoMatches (src/Frame.cc:706), ORB_SLAM2::Optimizer
 // (include/Optimizer.h:38-57: PoseOptimization, LocalBundleAdjustment, BundleAdjustment, OptimizeSim3, OptimizeEssentialGraph) and ObjectOptimizer::PoseOptimization2
 // (include/ObjectOptimizer.h:23), ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: loadFromTextFile, transform, score) ORB_SLAM2::PnPsolver (include/PnPsolver.h: SetRansacParameters, iterate, find) and ORB_SLAM2::Sim3Solver (include/Sim3Solver.h: SetRansacParameters, iterate, find, GetEstimatedRotation / Translation / Scale) and ORB_SLAM2::KeyFrameDatabase (include/KeyFrameDatabase.h: add, erase, clear,
 // DetectLoopCandidates, DetectRelocalizationCandidates).  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
@@ -186,6 +186,20 @@ struct RelocKeyFrameView {                // one entry per slot i of pKF->GetMap
     const uint8_t* skip;                  // pMP == NULL || pMP->isBad() || sAlreadyFound.count(pMP) (:1492-1494); the other rows of a skipped slot are not read
 };
 
+// Flat view of what ORBmatcher::SearchForInitialization (src/ORBmatcher.cc:405-520) reads of a Frame (Tracking::MonocularInitialization, src/Tracking.cc:681)
+struct InitMatchFrameView {
+    int N;                                // mvKeysUn.size()
+    const oslam::KeyPoint* mvKeysUn;      // pt, octave and angle are read
+    const uint8_t* mDescriptors;          // N x 32
+    float mnMinX, mnMinY, mnMaxX, mnMaxY;
+};
+#ifdef OSLAM_ADAPTER_USE_OPENCV
+typedef cv::Point2f Point2f;
+#else
+struct Point2f { float x, y; };
+#endif
+static_assert(sizeof(Point2f) == 2 * sizeof(float), "vbPrevMatched is handed over as float [.][2]");
+
 class ORBmatcher {
 public:
     static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 30;   // src/ORBmatcher.cc:37-39
@@ -193,7 +207,7 @@ public:
         : mfNNratio(nnratio), mbCheckOrientation(checkOri) {
         oslam::throw_on(oslam_matcher_create(&h_, 1, max_keypoints, max_queries, device));
     }
-    ~ORBmatcher() { oslam_matcher_destroy(h_); oslam_bow_destroy(bow_); oslam_sim3_match_destroy(sim3m_); oslam_sim3_proj_destroy(sim3p_); oslam_reloc_proj_destroy(relocp_); }
+    ~ORBmatcher() { oslam_matcher_destroy(h_); oslam_bow_destroy(bow_); oslam_sim3_match_destroy(sim3m_); oslam_sim3_proj_destroy(sim3p_); oslam_reloc_proj_destroy(relocp_); oslam_init_match_destroy(initm_); }
     ORBmatcher(const ORBmatcher&) = delete;
 
     // int SearchByProjection(Frame &F, const vector<MapPoint*> &vpMapPoints, const float th):
@@ -418,6 +432,34 @@ public:
         return nmatches;
     }
 
+    // int SearchForInitialization(Frame &F1, Frame &F2, std::vector<cv::Point2f> &vbPrevMatched, std::vector<int> &vnMatches12, int windowSize=10) (:405-520).
+    // vbPrevMatched [F1.N]: the carried points, read as the window centres and updated for the surviving matches; vnMatches12 is resized to F1.N.  The image
+    // bounds are F2's (the frame GetFeaturesInArea is asked of).  Returns nmatches.
+    int SearchForInitialization(const InitMatchFrameView& F1, const InitMatchFrameView& F2, std::vector<Point2f>& vbPrevMatched, std::vector<int>& vnMatches12, int windowSize = 10) {
+        if (F1.N < 0 || F2.N < 0) throw std::runtime_error("SearchForInitialization: negative key count");
+        if ((int)vbPrevMatched.size() != F1.N) throw std::runtime_error("SearchForInitialization: vbPrevMatched must have one entry per key of F1");
+        if (!initm_ || F1.N > initm_cap_) {   // made at the first call and again when F1 has more keys than it holds
+            oslam_init_match_destroy(initm_);
+            initm_ = nullptr;
+            initm_cap_ = F1.N > 16384 ? F1.N : 16384;
+            oslam::throw_on(oslam_init_match_create(&initm_, 1, 2400, initm_cap_, 0));
+        }
+        oslam_init_match_problem_t pr;
+        pr.n1 = F1.N; pr.off1 = 0; pr.n2 = F2.N; pr.off2 = 0; pr.windowSize = windowSize; pr.reserved = 0;
+        const oslam_init_match_f1_rows_t r1 = {F1.N, reinterpret_cast<const oslam_keypoint_t*>(F1.mvKeysUn), F1.mDescriptors};
+        const oslam_init_match_f2_rows_t r2 = {F2.N, reinterpret_cast<const oslam_keypoint_t*>(F2.mvKeysUn), F2.mDescriptors};
+        const float bounds[4] = {F2.mnMinX, F2.mnMinY, F2.mnMaxX, F2.mnMaxY};
+        std::vector<int32_t> m12((size_t)F1.N + 1, -1);
+        std::vector<float> prev(2 * (size_t)F1.N + 2);
+        if (F1.N) memcpy(prev.data(), vbPrevMatched.data(), 2 * (size_t)F1.N * sizeof(float));
+        int32_t nmatches = 0;
+        oslam::throw_on(oslam_match_search_for_initialization_batch(initm_, 1, &pr, &r1, &r2, bounds, mfNNratio, mbCheckOrientation ? 1 : 0, prev.data(), m12.data(), &nmatches,
+                                                                    nullptr, nullptr, nullptr));
+        if (F1.N) memcpy(vbPrevMatched.data(), prev.data(), 2 * (size_t)F1.N * sizeof(float));
+        vnMatches12.assign(m12.begin(), m12.begin() + F1.N);
+        return nmatches;
+    }
+
     float mfNNratio;
     bool mbCheckOrientation;
 
@@ -445,6 +487,8 @@ private:
     int sim3p_cap_ = 0;
     oslam_reloc_proj_t* relocp_ = nullptr;
     int relocp_cap_ = 0;
+    oslam_init_match_t* initm_ = nullptr;
+    int initm_cap_ = 0;
 };
 
 }  // namespace ORB_SLAM2

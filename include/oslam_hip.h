@@ -1448,7 +1448,7 @@ int oslam_kfdb_detect_relocalization_candidates_device(oslam_kfdb_t* h, const os
  * Initializer — ORB_SLAM2::Initializer (include/Initializer.h, src/Initializer.cc: homography / fundamental RANSAC, model selection, motion recovery),
  * the numerical operator of Tracking::MonocularInitialization (src/Tracking.cc:661, :695), for batches of independent problems (one per sequence
  * that is still initialising).  One shot: Initialize has no resumable state.  The tracking driver does not call it: oslam_slam.h is RGB-D / stereo
- * only.  ORBmatcher::SearchForInitialization (src/ORBmatcher.cc:405), which produces vMatches12, is not part of the library yet.
+ * only.  ORBmatcher::SearchForInitialization (src/ORBmatcher.cc:405), which produces vMatches12, is the "Initialisation search" section below.
  *
  * A problem is the n1 undistorted keys of the reference frame (mvKeysUn[i].pt, float [.][2]) at off1 of the packed keys-1 array, the n2 keys of the
  * current frame at off2 of the keys-2 array, vMatches12 (int32, parallel to the keys-1 array: entry >= 0 is an index into the problem's keys 2,
@@ -1530,6 +1530,93 @@ int oslam_init_initialize_batch_device(oslam_init_t* h, int n_problems, const os
  * oslam_init_last_kernel_ms waits for the last call's events and gives the milliseconds of the hypothesis kernel and of the reconstruction kernel. */
 int oslam_init_set_timing(oslam_init_t* h, int on);
 int oslam_init_last_kernel_ms(oslam_init_t* h, float ms[2]);
+
+/* ------------------------------------------------------------------------------------------
+ * Initialisation search — ORBmatcher::SearchForInitialization(Frame& F1, Frame& F2, vector<cv::Point2f>& vbPrevMatched, vector<int>& vnMatches12,
+ * int windowSize) (src/ORBmatcher.cc:405-520), which Tracking::MonocularInitialization calls with ORBmatcher(0.9, true) and windowSize = 100
+ * (src/Tracking.cc:680-681), for batches of independent problems: one per sequence that is still initialising.  It produces the vMatches12 that the
+ * Initializer above takes, in the layout it takes (matches12 [n_rows1], parallel to the frames-1 rows), so that the two operators chain on one stream
+ * with no host step.  One launch, one workgroup per problem.  An operator: the driver does not call it (oslam_slam.h is RGB-D / stereo only).
+ *
+ * A problem (oslam_init_match_problem_t) is F1 (n1 rows at off1 of oslam_init_match_f1_rows_t, and of prev_matched and matches12), F2 (n2 rows at off2
+ * of oslam_init_match_f2_rows_t) and windowSize.  Per row: mvKeysUn (x, y, octave and angle are read) and mDescriptors.  bounds[4] = mnMinX, mnMinY,
+ * mnMaxX, mnMaxY, nnratio (mfNNratio) and check_orientation (mbCheckOrientation) per call.  prev_matched [n_rows1][2] is vbPrevMatched, read and written.
+ *
+ * vMatchedDistance [n2] starts at INT_MAX and vnMatches21 [n2] at -1 (:415-416).  Per key i1 of F1 in index order (:418-487):
+ *  1. a key with octave > 0 does not search (:421-423).
+ *  2. F2.GetFeaturesInArea(vbPrevMatched[i1].x, .y, windowSize, 0, 0) (src/Frame.cc:567-620): the window is centred on the CARRIED point, not on the key;
+ *     r = (float)windowSize; the cell range is the floor and ceil of the float expressions, nothing when it lies outside the 64 x 48 grid; only F2 keys
+ *     of octave 0 are candidates (bCheckLevels is true: maxLevel >= 0); the strict window fabs(dx) < r && fabs(dy) < r; the visiting order is cell
+ *     column, cell row, key index.
+ *  3. per candidate i2: dist = DescriptorDistance; a candidate with vMatchedDistance[i2] <= dist is skipped entirely, it is neither best nor second
+ *     best (:444-445); else bestDist / bestDist2 / bestIdx2 update by strict < (:447-456): the first visited among equal distances is the best.
+ *  4. accepted when bestDist <= TH_LOW (50) and bestDist < (float)bestDist2 * mfNNratio (:459-461); bestDist2 stays INT_MAX without a second candidate.
+ *  5. on acceptance (:463-471): if vnMatches21[bestIdx2] >= 0 that earlier key is displaced (its vnMatches12 becomes -1); then vnMatches12[i1] =
+ *     bestIdx2, vnMatches21[bestIdx2] = i1, vMatchedDistance[bestIdx2] = bestDist.  A later key takes a keypoint from an earlier one only when it
+ *     is strictly nearer.
+ *  6. with check_orientation (:473-483): rot = F1.angle[i1] - F2.angle[bestIdx2] in float, + 360.0f when rot < 0; bin = round(rot * (1.0f / 30)), half
+ *     away from zero; 30 becomes 0; i1 is pushed to its bin at acceptance: a key displaced later stays there and counts towards the bin's size.
+ * After the loop, with check_orientation: ComputeThreeMaxima (:1601-1642, as in the relocalisation section) over the sizes of the 30 bins; the entries
+ * of every other bin that still hold a match lose it (:489-512).  A match removed here has still blocked and displaced others during the loop.
+ * Finally vbPrevMatched[i1] = F2.mvKeysUn[vnMatches12[i1]].pt for the surviving matches only (:514-517); every other entry keeps what it held.
+ * Outputs: matches12 [n_rows1] (all n1 entries of a problem are written: the keypoint of F2, or -1); prev_matched; n_matches [n_problems]: the
+ * reference's return value.  May be NULL: n_removed [n_problems]: the matches the histogram took away; n_displaced [n_problems]: the displacements of
+ * step 5; n_overflow [n_problems]: the keys whose candidate list did not fit the kernel's per-key cache (a cost figure: the result does not depend on
+ * it).
+ * The kernel finds every key's candidates in parallel and then replays steps 3-5 in key order by one wavefront, literally; it uses no atomics on
+ * global memory and its outputs are bit-identical from run to run.
+ *
+ * Roundings: r = (float)windowSize; the grid arithmetic of the relocalisation section; (float)bestDist < (float)bestDist2 * mfNNratio with the product
+ * and the comparison in float; rot, rot * factor and 0.1f * (float)max in float; round() half away from zero.
+ * Normalisations (declared, not pinned facts):
+ *  - An F1 key with octave < 0 does not search.  (The reference would search all levels: bCheckLevels is false for minLevel = maxLevel < 0.  The
+ *    extractor never produces such a key.)
+ *  - A carried point that is not finite has no candidates ((int)floor(NaN) is INT_MIN on x86 and GetFeaturesInArea returns nothing).
+ *  - Angles are degrees in [0, 360], as in the relocalisation section: a match whose bin falls outside 0 .. 29 (a NaN, an angle outside the
+ *    contract) is counted in no bin and removed.
+ *  - windowSize small enough for the cell coordinates to fit an int; beyond that the kernel's conversions saturate, the walk stays inside the grid
+ *    and the strict window test decides.
+ * Refusals: more problems than max_problems, an F2 above max_keypoints, more frames-1 rows than max_keys1_total, or a negative count:
+ * OSLAM_E_CAPACITY, nothing is launched; rows outside the arrays, windowSize < 0, or an nnratio that is not finite or <= 0: OSLAM_E_INVALID.  The
+ * device entry point cannot read the records: there such a record gets count -2 and nothing else of it is written.  Problems of one call must not
+ * share frames-1 rows (they may share frames-2 rows); rows no problem owns keep what they held.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct oslam_init_match oslam_init_match_t;
+typedef struct oslam_init_match_problem {
+    int32_t n1, off1;      /* F1 = frames-1 rows off1 .. off1 + n1 - 1 (and those of prev_matched and matches12) */
+    int32_t n2, off2;      /* F2 = frames-2 rows off2 .. off2 + n2 - 1 */
+    int32_t windowSize;
+    int32_t reserved;
+} oslam_init_match_problem_t;
+typedef struct oslam_init_match_f1_rows {   /* n_rows entries each; the device entry points take device pointers, desc 16-byte aligned */
+    int32_t n_rows;
+    const oslam_keypoint_t* keysUn;   /* F1.mvKeysUn */
+    const uint8_t* desc;              /* [n_rows][32] F1.mDescriptors */
+} oslam_init_match_f1_rows_t;
+typedef struct oslam_init_match_f2_rows {
+    int32_t n_rows;
+    const oslam_keypoint_t* keysUn;   /* F2.mvKeysUn */
+    const uint8_t* desc;              /* [n_rows][32] F2.mDescriptors */
+} oslam_init_match_f2_rows_t;
+/* max_keypoints <= 2400 bounds n2: F2 is staged in LDS with the 51 bytes per keypoint of the projection handles (the two int vectors are
+ * vMatchedDistance and vnMatches21).  max_keys1_total bounds the frames-1 rows of one call (the handle keeps 32 bytes of device memory per row; the
+ * bins are 30 counters in LDS).  OSLAM_E_HIP without a device: there is no CPU fallback. */
+int oslam_init_match_create(oslam_init_match_t** out, int max_problems, int max_keypoints, int max_keys1_total, int device);
+void oslam_init_match_destroy(oslam_init_match_t* h);
+/* Host pointers, staged through one pinned / device block pair: one upload, one launch, one download, synchronous.  n_removed, n_displaced and
+ * n_overflow may be NULL; prev_matched and the outputs are read and written (rows no problem owns keep what they held). */
+int oslam_match_search_for_initialization_batch(oslam_init_match_t* h, int n_problems, const oslam_init_match_problem_t* problems, const oslam_init_match_f1_rows_t* frames1,
+                                                const oslam_init_match_f2_rows_t* frames2, const float bounds[4], float nnratio, int check_orientation, float* prev_matched,
+                                                int32_t* matches12, int32_t* n_matches, int32_t* n_removed, int32_t* n_displaced, int32_t* n_overflow);
+/* The same over device arrays (frames1 and frames2 are host structs of device pointers; bounds is a host pointer), one launch, asynchronous on
+ * `stream`, no host synchronisation.  Calls on one handle must not overlap on the device: the search keeps per-key state in the handle. */
+int oslam_match_search_for_initialization_batch_device(oslam_init_match_t* h, int n_problems, const oslam_init_match_problem_t* d_problems,
+                                                       const oslam_init_match_f1_rows_t* frames1, const oslam_init_match_f2_rows_t* frames2, const float bounds[4], float nnratio,
+                                                       int check_orientation, float* d_prev_matched, int32_t* d_matches12, int32_t* d_n_matches, int32_t* d_n_removed,
+                                                       int32_t* d_n_displaced, int32_t* d_n_overflow, void* stream);
+/* Measurement: the shader-clock ticks workgroup 0 of the handle's last call spent in staging F2, in the candidate search, in the sequential replay and
+ * in the histogram and the outputs.  Waits for the device. */
+int oslam_init_match_last_phase_ticks(oslam_init_match_t* h, int64_t ticks[4]);
 
 #ifdef __cplusplus
 }

@@ -28,3 +28,5 @@ from .reloc_project import RelocProjector  # noqa: F401
 from . import reloc_project  # noqa: F401
 from .initializer import Initializer  # noqa: F401
 from . import initializer  # noqa: F401
+from .search_init import InitMatcher  # noqa: F401
+from . import search_init  # noqa: F401

@@ -4,7 +4,7 @@
 // visiting order as a keyframe's) and its threads stride over the keyframe's map-point slots, which stay in global memory.  The sequential claims of :1541 /
 // :1557 are reproduced with claim_fixpoint; the rotation histogram (:1577-1596) runs once on the final claims, so a match it removes has still blocked the
 // slots after it.  The staging, the level, the window walk, the claims and the handle are window_search.h's (shared with sim3_match.hip and
-// sim3_project.hip); the gates of a slot, ORBdist and the histogram are here.
+// sim3_project.hip); the gates of a slot, ORBdist and the histogram's use are here.
 // No inter-workgroup synchronisation and no atomics on global memory: the result does not depend on the order the hardware runs anything in (the LDS
 // atomics are minima and counts).  The roundings are those the header lists.  Product code; never includes oracle/.
 #include <climits>
@@ -58,16 +58,6 @@ __device__ int evaluate(const RelocArgs& a, const Staged& s, const float* s_scal
     // Frame::GetFeaturesInArea (src/Frame.cc:567-620) with minLevel = level - 1, maxLevel = level + 1
     const int level = predict_level(mfMax, dist, c);
     return nearest_unclaimed<-1, 1>(s, c, u, v, T.th * s_scale[level], level, a.pts.desc + o * 32, T.orbdist, i, claim, cache);
-}
-
-// bin of :1562-1567; -1 for what the reference's assert excludes
-__device__ __forceinline__ int rot_bin(float kf_angle, float fr_angle) {
-    float rot = kf_angle - fr_angle;
-    if (rot < 0.0f) rot += 360.0f;
-    const float b = roundf(rot * (1.0f / kHistoLen));
-    if (!(b >= 0.0f && b <= (float)kHistoLen)) return -1;
-    const int bin = (int)b;
-    return bin == kHistoLen ? 0 : bin;
 }
 
 __global__ __launch_bounds__(kThreads) void k_reloc_project(RelocArgs a) {

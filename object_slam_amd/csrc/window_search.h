@@ -1,10 +1,10 @@
-// The windowed projection search of the operators that run one workgroup of 1024 threads per problem (sim3_match.hip, sim3_project.hip, reloc_project.hip):
+// The windowed projection search of the operators that run one workgroup of 1024 threads per problem (sim3_match.hip, sim3_project.hip, reloc_project.hip, search_init.hip):
 //  - one keyframe or frame in LDS: keypoint xy, octave, the 32-byte descriptors and the 64 x 48 cell table in GetFeaturesInArea's visiting order (cell
 //    column, then cell row, then keypoint index), with the layout of the dynamic LDS block stated once;
 //  - the level a point is predicted at, the walk over its window and the Hamming distance;
 //  - the replay of the reference's sequential claims (a later point does not get a keypoint an earlier one took) as a fixpoint over two claim vectors, with
 //    a per-point candidate cache, and the handle and create function of the two operators that use it;
-//  - gemm_row and three_maxima, which matcher.hip takes from here too.
+//  - gemm_row and three_maxima, which matcher.hip takes from here too, and rot_bin.
 // What differs between the operators stays with them: the gates before the window (sign of z, bounds, distance, viewing angle), the thresholds and what
 // becomes of the matches.  The host arithmetic that needs no HIP is in window_search_host.h.
 #pragma once
@@ -280,6 +280,17 @@ __device__ __forceinline__ int write_claims(const int* claim, int n_kp, int32_t*
         found += ok ? 1 : 0;
     }
     return found;
+}
+
+// The rotation bin of a match (src/ORBmatcher.cc:475-480, :1562-1567): rot = angle1 - angle2 in float, + 360.0f when negative, round(rot * (1.0f / 30)) half away
+// from zero, 30 becomes 0; -1 for what the reference's assert excludes
+__device__ __forceinline__ int rot_bin(float angle1, float angle2) {
+    float rot = angle1 - angle2;
+    if (rot < 0.0f) rot += 360.0f;
+    const float b = roundf(rot * (1.0f / kHistoLen));
+    if (!(b >= 0.0f && b <= (float)kHistoLen)) return -1;
+    const int bin = (int)b;
+    return bin == kHistoLen ? 0 : bin;
 }
 
 // ORBmatcher::ComputeThreeMaxima (src/ORBmatcher.cc:1601-1642) over the sizes of the kHistoLen bins; one thread
