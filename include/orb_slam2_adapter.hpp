@@ -3,7 +3,8 @@
 // SearchForInitialization, SearchByBoW, SearchForTriangulation, Fuse, SearchBySim3, DescriptorDistance), Frame::ComputeStereoMatches (src/Frame.cc:706), ORB_SLAM2::Optimizer
 // (include/Optimizer.h:38-57: PoseOptimization, LocalBundleAdjustment, BundleAdjustment, OptimizeSim3, OptimizeEssentialGraph) and ObjectOptimizer::PoseOptimization2
 // (include/ObjectOptimizer.h:23), ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: loadFromTextFile, transform, score) ORB_SLAM2::PnPsolver (include/PnPsolver.h: SetRansacParameters, iterate, find) and ORB_SLAM2::Sim3Solver (include/Sim3Solver.h: SetRansacParameters, iterate, find, GetEstimatedRotation / Translation / Scale) and ORB_SLAM2::KeyFrameDatabase (include/KeyFrameDatabase.h: add, erase, clear,
-// DetectLoopCandidates, DetectRelocalizationCandidates).  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
+// DetectLoopCandidates, DetectRelocalizationCandidates) and ORB_SLAM2::ObjectMatcher (include/ObjectMatcher.h: MatchTwoFrame, MatchMapToFrame) with Frame::ExtractHSVHistogramsFromMask
+// (src/Frame.cc:388) as a free function.  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
 // "view" of exactly the members it reads and writes (the gather loops are in INTEGRATION.md).  tests/adapter_program.cc uses nothing but
 // these classes; tests/test_adapter_gpu.py builds it, runs it and compares its outputs with the ctypes path.
 //
@@ -1238,5 +1239,158 @@ private:
     std::vector<float> acc_;
     int32_t diag_[5] = {0, 0, 0, 0, 0};
 };
+
+// ---- the object layer: what Tracking::TrackObject (src/Tracking.cc:1058-1076) reads and writes ----
+struct Object2DView {                     // Object2D (include/ObjectTypes.h)
+    int label = 0;
+    float x = 0, y = 0, w = 0, h = 0;     // the 2-D box
+    const uint8_t* mask = nullptr;        // CV_8UC1, the frame's size
+    int mask_step = 0;
+    std::vector<float> kps;               // per mvFrameKpIndices entry: mvKeysUn[i].pt.x, .pt.y, mvDepth[i] (> 0)
+    float mHSVHistogram[OSLAM_OBJMATCH_BINS] = {};
+    int track_id = -1;
+};
+struct ObjectFrameView {                  // the members of a Frame the object layer touches
+    const uint8_t* imRGB = nullptr;       // CV_8UC3, read as B, G, R
+    int cols = 0, rows = 0, step = 0;
+    float mRwc[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, mOw[3] = {0, 0, 0};
+    float fx = 1, fy = 1, cx = 0, cy = 0;
+    std::vector<Object2DView> mvObject2Ds;
+    std::vector<int> mvpObject3Ds;        // per detection the Object3D's mTrackID, -1 = NULL
+    std::vector<int> mvObject3DLabels;    // per detection that Object3D's mLabel (MatchTwoFrame reads pObj3D->mLabel of the previous frame)
+};
+struct ObjectObservationView {            // ObjectObservation: ObjectCenterW and AppearanceVec (ObsCamPoseTcw only feeds the unused view vectors)
+    float ObjectCenterW[3];
+    float AppearanceVec[OSLAM_OBJMATCH_BINS];
+};
+struct Object3DView {
+    int mTrackID = -1;
+    int mLabel = 0;
+    std::vector<ObjectObservationView> mvObservations;
+};
+
+// ORB_SLAM2::ObjectMatcher (include/ObjectMatcher.h): MatchTwoFrame (src/ObjectMatcher.cc:47-440) and MatchMapToFrame (:442-801), one problem per call.
+class ObjectMatcher {
+public:
+    ObjectMatcher() {}
+    ~ObjectMatcher() { oslam_objmatch_destroy(h_); }
+    ObjectMatcher(const ObjectMatcher&) = delete;
+    ObjectMatcher& operator=(const ObjectMatcher&) = delete;
+    oslam_objmatch_params_t params = {0.8, 0.5, 0.3, 0.1};   // the literals of :430, :783 and :789
+
+    // void MatchTwoFrame(Frame &PreF, Frame &CurF): CurF.mvpObject3Ds and the track_id of the claimed detections are written.
+    void MatchTwoFrame(const ObjectFrameView& PreF, ObjectFrameView& CurF) {
+        const int nPre = (int)PreF.mvObject2Ds.size(), nCur = (int)CurF.mvObject2Ds.size();
+        if ((int)PreF.mvpObject3Ds.size() != nPre || (int)PreF.mvObject3DLabels.size() != nPre || (int)CurF.mvpObject3Ds.size() != nCur)
+            throw std::runtime_error("MatchTwoFrame: mvpObject3Ds must have one entry per detection");
+        ensure(1, 1, 1, 1, 1, std::max(nPre, nCur));
+        std::vector<int32_t> plabel(nPre), pid(nPre), clabel(nCur), cid(nCur);
+        std::vector<float> phist, pbox, chist, cbox;
+        for (int i = 0; i < nPre; i++) {
+            pid[i] = PreF.mvpObject3Ds[i]; plabel[i] = PreF.mvObject3DLabels[i];
+            append(PreF.mvObject2Ds[i], phist, pbox);
+        }
+        for (int j = 0; j < nCur; j++) {
+            cid[j] = CurF.mvpObject3Ds[j]; clabel[j] = CurF.mvObject2Ds[j].label;
+            append(CurF.mvObject2Ds[j], chist, cbox);
+        }
+        oslam_objmatch_det_rows_t pre = {}, cur = {};
+        pre.n_rows = nPre; pre.label = plabel.data(); pre.hist = phist.data(); pre.box = pbox.data(); pre.obj3d = pid.data();
+        cur.n_rows = nCur; cur.label = clabel.data(); cur.hist = chist.data(); cur.box = cbox.data(); cur.obj3d = cid.data();
+        oslam_objmatch_pair_problem_t pr = {};
+        pr.n_pre = nPre; pr.n_cur = nCur;
+        std::vector<float> sim((size_t)nPre * nCur), iou((size_t)nPre * nCur);
+        int32_t n = 0, status = 0;
+        oslam::throw_on(oslam_objmatch_match_two_frame(h_, 1, &pr, &pre, &cur, &params, nPre * nCur, sim.data(), iou.data(), &n, &status));
+        if (status != OSLAM_OBJMATCH_DONE) throw std::runtime_error("MatchTwoFrame: the problem was refused");
+        take_claims(CurF, cid);
+    }
+
+    // void MatchMapToFrame(vector<Object3D*> vpObject3Ds, Frame &F).  The reference's order is that of a std::set of pointers; pass ascending mTrackID.
+    void MatchMapToFrame(const std::vector<Object3DView>& vpObject3Ds, ObjectFrameView& F) {
+        const int nObj = (int)vpObject3Ds.size(), nCur = (int)F.mvObject2Ds.size();
+        if ((int)F.mvpObject3Ds.size() != nCur) throw std::runtime_error("MatchMapToFrame: mvpObject3Ds must have one entry per detection");
+        std::vector<int32_t> clabel(nCur), cid(nCur), koff(nCur), kn(nCur), oid(nObj), olabel(nObj), ooff(nObj), on(nObj);
+        std::vector<float> chist, cbox, kps, ocen, ohist;
+        for (int j = 0; j < nCur; j++) {
+            const Object2DView& d = F.mvObject2Ds[j];
+            cid[j] = F.mvpObject3Ds[j]; clabel[j] = d.label; koff[j] = (int)kps.size() / 3; kn[j] = (int)d.kps.size() / 3;
+            append(d, chist, cbox);
+            kps.insert(kps.end(), d.kps.begin(), d.kps.end());
+        }
+        for (int i = 0; i < nObj; i++) {
+            const Object3DView& o = vpObject3Ds[i];
+            oid[i] = o.mTrackID; olabel[i] = o.mLabel; ooff[i] = (int)ocen.size() / 3; on[i] = (int)o.mvObservations.size();
+            for (const ObjectObservationView& ob : o.mvObservations) {
+                ocen.insert(ocen.end(), ob.ObjectCenterW, ob.ObjectCenterW + 3);
+                ohist.insert(ohist.end(), ob.AppearanceVec, ob.AppearanceVec + OSLAM_OBJMATCH_BINS);
+            }
+        }
+        ensure(1, 1, nObj, (int)ocen.size() / 3, (int)kps.size() / 3, nCur);
+        oslam_objmatch_det_rows_t cur = {};
+        cur.n_rows = nCur; cur.label = clabel.data(); cur.hist = chist.data(); cur.obj3d = cid.data(); cur.kp_off = koff.data(); cur.kp_n = kn.data();
+        cur.n_kps = (int)kps.size() / 3; cur.kps = kps.data();
+        oslam_objmatch_obj_rows_t obj = {};
+        obj.n_rows = nObj; obj.obj3d_id = oid.data(); obj.label = olabel.data(); obj.obs_off = ooff.data(); obj.obs_n = on.data();
+        obj.n_obs = (int)ocen.size() / 3; obj.obs_center = ocen.data(); obj.obs_hist = ohist.data();
+        oslam_objmatch_map_problem_t pr = {};
+        pr.n_cur = nCur; pr.n_obj = nObj;
+        std::memcpy(pr.Rwc, F.mRwc, sizeof pr.Rwc); std::memcpy(pr.Ow, F.mOw, sizeof pr.Ow);
+        pr.fx = F.fx; pr.fy = F.fy; pr.cx = F.cx; pr.cy = F.cy;
+        const size_t ns = (size_t)nObj * nCur;
+        std::vector<float> sim(ns), mean(ns), mind(ns);
+        int32_t bySim = 0, byDist = 0, status = 0;
+        oslam::throw_on(oslam_objmatch_match_map_to_frame(h_, 1, &pr, &cur, &obj, &params, (int)ns, sim.data(), mean.data(), mind.data(), &bySim, &byDist, &status));
+        if (status != OSLAM_OBJMATCH_DONE) throw std::runtime_error("MatchMapToFrame: the problem was refused (an object without observations, a detection without keypoints)");
+        take_claims(F, cid);
+    }
+
+    // (used by ExtractHSVHistogramsFromMask below) the handle, grown to hold what a call needs
+    oslam_objmatch_t* ensure(int w, int h, int nObj, int nObs, int nKps, int nDet) {
+        if (nDet > OSLAM_OBJMATCH_MAX_DETECTIONS) throw std::runtime_error("ObjectMatcher: more than 32 detections in a frame");
+        if (h_ && w <= cap_[0] && h <= cap_[1] && nObj <= cap_[2] && nObs <= cap_[3] && nKps <= cap_[4]) return h_;
+        const int want[5] = {w, h, nObj, nObs, nKps}, least[5] = {640, 480, 64, 4096, 4096};
+        for (int k = 0; k < 5; k++) cap_[k] = std::max(cap_[k], std::max(least[k], k < 2 ? want[k] : want[k] + want[k] / 2));
+        oslam_objmatch_destroy(h_);
+        h_ = nullptr;
+        oslam::throw_on(oslam_objmatch_create(&h_, 1, cap_[0], cap_[1], OSLAM_OBJMATCH_MAX_DETECTIONS, cap_[2], cap_[3], cap_[4]));
+        return h_;
+    }
+
+private:
+    static void append(const Object2DView& d, std::vector<float>& hist, std::vector<float>& box) {
+        hist.insert(hist.end(), d.mHSVHistogram, d.mHSVHistogram + OSLAM_OBJMATCH_BINS);
+        const float b[4] = {d.x, d.y, d.w, d.h};
+        box.insert(box.end(), b, b + 4);
+    }
+    static void take_claims(ObjectFrameView& F, const std::vector<int32_t>& cid) {
+        for (size_t j = 0; j < cid.size(); j++) {
+            if (cid[j] != F.mvpObject3Ds[j]) F.mvObject2Ds[j].track_id = cid[j];   // :433-434, :786-787, :792-793
+            F.mvpObject3Ds[j] = cid[j];
+        }
+    }
+    oslam_objmatch_t* h_ = nullptr;
+    int cap_[5] = {0, 0, 0, 0, 0};
+};
+
+// cv::Mat Frame::ExtractHSVHistogramsFromMask(const cv::Mat &imRGB, cv::Mat &mask) (src/Frame.cc:388-414) for every detection of the frame at once: the image is
+// read once, mHSVHistogram of every Object2D is written.
+inline void ExtractHSVHistogramsFromMask(ObjectMatcher& matcher, ObjectFrameView& F) {
+    const int n = (int)F.mvObject2Ds.size();
+    if (n == 0) return;
+    if (!F.imRGB || F.cols < 1 || F.rows < 1 || F.step < 3 * F.cols) throw std::runtime_error("ExtractHSVHistogramsFromMask: no image");
+    oslam_objmatch_t* h = matcher.ensure(F.cols, F.rows, 1, 1, 1, n);
+    std::vector<uint8_t> masks((size_t)n * F.rows * F.cols);
+    for (int k = 0; k < n; k++) {
+        const Object2DView& d = F.mvObject2Ds[k];
+        if (!d.mask || d.mask_step < F.cols) throw std::runtime_error("ExtractHSVHistogramsFromMask: a detection without a mask");
+        for (int y = 0; y < F.rows; y++) std::memcpy(masks.data() + ((size_t)k * F.rows + y) * F.cols, d.mask + (size_t)y * d.mask_step, F.cols);
+    }
+    const oslam_objmatch_frame_t fr = {n, 0};
+    std::vector<int32_t> counts((size_t)n * OSLAM_OBJMATCH_BINS);
+    std::vector<float> hist((size_t)n * OSLAM_OBJMATCH_BINS);
+    oslam::throw_on(oslam_objmatch_hsv_histograms(h, 1, F.cols, F.rows, F.step, F.cols, F.imRGB, &fr, n, masks.data(), counts.data(), hist.data()));
+    for (int k = 0; k < n; k++) std::memcpy(F.mvObject2Ds[k].mHSVHistogram, hist.data() + (size_t)k * OSLAM_OBJMATCH_BINS, sizeof(float) * OSLAM_OBJMATCH_BINS);
+}
 
 }  // namespace ORB_SLAM2

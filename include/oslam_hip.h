@@ -1618,6 +1618,162 @@ int oslam_match_search_for_initialization_batch_device(oslam_init_match_t* h, in
  * in the histogram and the outputs.  Waits for the device. */
 int oslam_init_match_last_phase_ticks(oslam_init_match_t* h, int64_t ticks[4]);
 
+/* ------------------------------------------------------------------------------------------
+ * Object association — what Tracking::TrackObject (src/Tracking.cc:1058-1076) runs on every frame: Frame::ExtractHSVHistogramsFromMask
+ * (src/Frame.cc:388-414) per detection, ObjectMatcher::MatchTwoFrame(mLastFrame, mCurrentFrame) (src/ObjectMatcher.cc:47-440) and
+ * ObjectMatcher::MatchMapToFrame(GetAllObject3Ds(), mCurrentFrame) (:442-801), for batches of independent frames.  Operators: the driver does not call
+ * them, oslam_slam.h still takes the caller's track_id per detection.  Only the live code is built: the commented-out 3D-2D and ORB checks of
+ * MatchTwoFrame, and the 3D-2D counts, 3-D boxes and view vectors that MatchMapToFrame computes and never uses, are not.
+ *
+ * 1. Appearance (src/Frame.cc:388-414, constants include/Frame.h:123-127).  Per frame an 8-bit 3-channel interleaved image [H][stride], read as B, G, R
+ *    whatever the camera's order is (the reference always applies CV_BGR2HSV), and n masks [H][mask_stride] of bytes; a pixel counts for a mask when
+ *    its byte is non-zero (cv::calcHist's mask rule).  Frames of one call share W, H and the strides.  Per mask: counts [94] int32 and hist [94] float,
+ *    columns in the order the hconcat calls (:403-410) leave: V (32 bins), S (32), H (30).  OpenCV is not in the tree; its arithmetic is restated:
+ *     - RGB2HSV_b, hue range 180, hsv_shift = 12: sdiv[i] = saturate_cast<int>((255 << 12) / (1.0 * i)), hdiv[i] = saturate_cast<int>((180 << 12) /
+ *       (6.0 * i)), sdiv[0] = hdiv[0] = 0 (saturate_cast<int>(double) rounds to nearest even); v = max(b, g, r), vmin = min(b, g, r), diff = v - vmin;
+ *       s = (diff * sdiv[v] + (1 << 11)) >> 12; h = g - b when v == r, else b - r + 2 diff when v == g, else r - g + 4 diff;
+ *       h = (h * hdiv[diff] + (1 << 11)) >> 12 (arithmetic shift), + 180 when h < 0; the outputs are (uchar)h, (uchar)s, (uchar)v.
+ *     - calcHist, 8-bit, uniform: per channel a 256-entry table idx = cvFloor(j * a + b) in double, a = size / (high - low), b = -a * low; a value
+ *       whose idx lies outside [0, size) is not counted.  Built on the host once per handle.
+ *     - cv::normalize(NORM_L1): norm = the sum of the 94 counts as a double (three times the mask's pixel count), scale = norm > DBL_EPSILON ?
+ *       1.0 / norm : 0.0, hist[k] = (float)count[k] * (float)scale.  An empty mask gives zeros.
+ *    The image is read once per frame; each pixel is converted once and tested against every mask of its frame.  A workgroup owns a band of 32 rows and
+ *    counts with integer LDS atomics; a second pass sums the bands' counts in band order, in integers: counts and hist are bit-identical from run to run.
+ *
+ * 2. MatchTwoFrame.  A problem (oslam_objmatch_pair_problem_t) is the previous frame's objects in order (rows of `pre`: obj3d = the Object3D's id,
+ *    negative for NULL; label = the Object3D's mLabel; hist; box x, y, w, h) and the current frame's detections (rows of `cur`: label, hist, box and
+ *    obj3d = mvpObject3Ds, negative for NULL, read and written).  Per previous object in order (:59), NULL ones skipped (:62): every detection that is
+ *    not claimed (:98) and has the object's label (:101) gets
+ *     - CalCosineSimilarity(Pre, Cur) (:877-889) over bins 0..93 in order: xy += a * b in float; xx = (float)((double)xx + (double)a * (double)a)
+ *       (pow(float, 2) promotes to double), yy likewise; xy / (sqrtf(xx) * sqrtf(yy)) in float;
+ *     - the box IoU (:131-147) in float: corners x + w, y + h, areas w * h, std::max / std::min with the current box as first argument, 0 when
+ *       x1 >= x2 || y1 >= y2 (what :138 leaves unset reads as 0 through map::operator[]), else inter / (PreArea + CurArea - inter).
+ *    The winner is the detection of largest similarity (:271-283); it is claimed when MaxSimilarity > min_similarity && idx >= 0 && IoU[idx] > min_iou
+ *    (:430-435), the floats compared against the double thresholds.  A detection claimed for one object is hidden from the next.
+ *    similarity and iou [n_pre][n_cur] at off_score hold NaN where the reference computes nothing (a NULL object, a claimed detection, another label).
+ *    Normalisations (declared, not pinned facts):
+ *     - `for(int idx_pre; ...)` (:59) has no initialiser: 0.
+ *     - std::sort followed by back() leaves ties unspecified: what a stable sort gives, the largest index among equals.
+ *     - A NaN similarity (a histogram of zeros) makes the comparator of std::sort inconsistent: such a detection is never the winner.  Whichever the
+ *       reference picked, a NaN MaxSimilarity would claim nothing.
+ *
+ * 3. MatchMapToFrame.  A problem (oslam_objmatch_map_problem_t) is the frame's Rwc, Ow, fx, fy, cx, cy, its detections (rows of `cur`: label, hist,
+ *    obj3d read and written, and kp_n keypoints (u, v, z), z > 0, at kp_off of the flat array kps) and the map's objects in the caller's order (rows of
+ *    oslam_objmatch_obj_rows_t: id, label, obs_n observations at obs_off of obs_center [.][3] and obs_hist [.][94]).  Objects whose id is among the
+ *    frame's obj3d when the call begins are skipped (the snapshot of :451-459, not updated inside the loop), NULL objects too (:468).  Per object in
+ *    order, per detection that is not claimed (:507) and has the object's label (:512):
+ *     - similarity = the maximum over the observations of CalCosineSimilarity(observed, detection), starting from 0 with a strict > (:519-542);
+ *     - the centre of the unprojected keypoints (:567-573, Frame::UnprojectStereo src/Frame.cc:906-920): x = (u - cx) * z * invfx with invfx = 1.0f / fx,
+ *       y likewise; Rwc * x3Dc + Ow, every row accumulated in float in column order, then + Ow; the float sum over the keypoints in order, times
+ *       (float)(1.0 / n);
+ *     - Dist = (float)sqrt((double)dx * dx + (double)dy * dy + (double)dz * dz) on the float differences observed centre - centre; meanDist = the float
+ *       sum in observation order divided by (float)nObs (equal to the reference's division by a double: both operands are floats and a double
+ *       quotient rounds to the same float); minDist starts at FLT_MAX with a strict < (:577-594).
+ *    Two independent decisions (:783-794), both may fire for one object: MaxSimilarity > min_similarity && idx >= 0 && meanDist[idx] < max_mean_dist
+ *    claims the detection of largest similarity (largest index among equals), MinMinPosDist < max_min_dist && idx2 >= 0 claims the detection of
+ *    smallest minDist (smallest index among equals, as a stable sort followed by front()).  Claims hide detections from later objects.
+ *    similarity, mean_dist, min_dist [n_obj][n_cur] at off_score hold NaN where nothing is computed.
+ *    Normalisations: Map::GetAllObject3Ds iterates a std::set of pointers, so the reference's object order is the allocator's: here it is the
+ *    caller's order (the adapter passes ascending mTrackID).  Where OpenCV's own rounding is not known (Mat expressions, cv::norm) the lines above are
+ *    the specification.  A NaN score is never a winner.
+ *    Preconditions, each refused per problem: an object without observations and a detection without keypoints (both would divide 0 by 0), a range
+ *    outside its flat array.
+ *
+ * Refusals: more frames or problems than max_frames, a size above max_width x max_height, more detection rows than max_frames * max_detections, more
+ * object rows than max_frames * max_objects, more observations or keypoints than the handle was created for, or a negative count: OSLAM_E_CAPACITY
+ * before anything is launched.  A matcher problem that does not fit (counts above max_detections / max_objects, rows or scores outside the arrays, a
+ * broken precondition) gets a negative status[b] and nothing else of it is written; the other problems of the call are unaffected.  A frame record of
+ * the histogram call that does not fit: OSLAM_E_CAPACITY / OSLAM_E_INVALID from the host entry point; the device entry point cannot read the
+ * records and writes nothing for such a frame.  Problems of one call must not share `cur` rows or score entries; rows no problem owns keep what they
+ * held.  The kernels use no atomics on global memory.
+ * ---------------------------------------------------------------------------------------- */
+#define OSLAM_OBJMATCH_BINS 94             /* 32 V + 32 S + 30 H (include/Frame.h:127) */
+#define OSLAM_OBJMATCH_MAX_DETECTIONS 32   /* per frame */
+#define OSLAM_OBJMATCH_DONE 0
+#define OSLAM_OBJMATCH_REFUSED_RECORD (-1)           /* a count above the handle's, or a range outside the arrays */
+#define OSLAM_OBJMATCH_REFUSED_NO_OBSERVATION (-2)   /* an object without observations */
+#define OSLAM_OBJMATCH_REFUSED_NO_KEYPOINT (-3)      /* a detection without keypoints */
+typedef struct oslam_objmatch oslam_objmatch_t;
+typedef struct oslam_objmatch_params {   /* the literals of src/ObjectMatcher.cc:430, :783 and :789, as doubles: the reference compares floats against them */
+    double min_similarity;   /* 0.8 */
+    double min_iou;          /* 0.5 */
+    double max_mean_dist;    /* 0.3; "5.0 for outdoor" by the reference's own comment */
+    double max_min_dist;     /* 0.1 */
+} oslam_objmatch_params_t;
+typedef struct oslam_objmatch_frame {
+    int32_t n_masks, mask_off;   /* masks mask_off .. mask_off + n_masks - 1 of the masks array (and of counts and hist) */
+} oslam_objmatch_frame_t;
+typedef struct oslam_objmatch_det_rows {   /* n_rows entries each; the device entry points take device pointers */
+    int32_t n_rows;
+    const int32_t* label;    /* Object2D::label (for `pre`: the Object3D's mLabel) */
+    const float* hist;       /* [n_rows][94] mHSVHistogram */
+    const float* box;        /* [n_rows][4] x, y, w, h; MatchTwoFrame only */
+    int32_t* obj3d;          /* mvpObject3Ds as ids, negative = NULL; written for `cur` */
+    const int32_t* kp_off;   /* MatchMapToFrame only: the detection's keypoints kp_off .. kp_off + kp_n - 1 of kps */
+    const int32_t* kp_n;
+    int32_t n_kps;
+    const float* kps;        /* [n_kps][3] u, v (mvKeysUn) and z (mvDepth) */
+} oslam_objmatch_det_rows_t;
+typedef struct oslam_objmatch_obj_rows {
+    int32_t n_rows;
+    const int32_t* obj3d_id;   /* negative = NULL */
+    const int32_t* label;      /* Object3D::mLabel */
+    const int32_t* obs_off;    /* mvObservations = observations obs_off .. obs_off + obs_n - 1 */
+    const int32_t* obs_n;
+    int32_t n_obs;
+    const float* obs_center;   /* [n_obs][3] ObjectObservation::ObjectCenterW */
+    const float* obs_hist;     /* [n_obs][94] ObjectObservation::AppearanceVec */
+} oslam_objmatch_obj_rows_t;
+typedef struct oslam_objmatch_pair_problem {
+    int32_t n_pre, off_pre;   /* the previous frame's objects: rows of `pre` */
+    int32_t n_cur, off_cur;   /* the current frame's detections: rows of `cur` */
+    int32_t off_score;        /* similarity and iou [n_pre][n_cur] start here */
+    int32_t reserved[3];
+} oslam_objmatch_pair_problem_t;
+typedef struct oslam_objmatch_map_problem {
+    int32_t n_cur, off_cur;   /* the frame's detections: rows of `cur` */
+    int32_t n_obj, off_obj;   /* the map's objects: rows of the object rows */
+    int32_t off_score;        /* similarity, mean_dist and min_dist [n_obj][n_cur] start here */
+    int32_t reserved;
+    float Rwc[9], Ow[3];      /* Frame::mRwc row-major, Frame::mOw */
+    float fx, fy, cx, cy;
+} oslam_objmatch_map_problem_t;
+/* max_detections is per frame, 8 .. 32; max_width * max_height <= 2^29.  The handle keeps max_frames * ceil(max_height / 32) * max_detections * 94
+ * int32 of partial counts.  Uses the current device.  OSLAM_E_HIP without a device: there is no CPU fallback. */
+int oslam_objmatch_create(oslam_objmatch_t** out, int max_frames, int max_width, int max_height, int max_detections, int max_objects, int max_observations_total,
+                          int max_keypoints_total);
+void oslam_objmatch_destroy(oslam_objmatch_t* h);
+/* Frame::ExtractHSVHistogramsFromMask (src/Frame.cc:388-414) of every mask of every frame.  Host pointers; one upload, two launches, one download,
+ * synchronous.  images [n_frames][height][stride], masks [n_masks_total][height][mask_stride], counts and hist [n_masks_total][94]. */
+int oslam_objmatch_hsv_histograms(oslam_objmatch_t* h, int n_frames, int width, int height, int stride, int mask_stride, const uint8_t* images, const oslam_objmatch_frame_t* frames,
+                                  int n_masks_total, const uint8_t* masks, int32_t* counts, float* hist);
+/* The same over device arrays (d_images 4-byte aligned), asynchronous on `stream`, no host synchronisation.  Calls on one handle must not overlap on
+ * the device: the partial counts live in the handle. */
+int oslam_objmatch_hsv_histograms_device(oslam_objmatch_t* h, int n_frames, int width, int height, int stride, int mask_stride, const uint8_t* d_images,
+                                         const oslam_objmatch_frame_t* d_frames, int n_masks_total, const uint8_t* d_masks, int32_t* d_counts, float* d_hist, void* stream);
+/* ObjectMatcher::MatchTwoFrame (src/ObjectMatcher.cc:47-440).  Host pointers; one upload, one launch, one download, synchronous.  cur->obj3d is read
+ * and written; similarity and iou [n_scores]; n_assigned [n_problems]: the claims made; status [n_problems]: OSLAM_OBJMATCH_*. */
+int oslam_objmatch_match_two_frame(oslam_objmatch_t* h, int n_problems, const oslam_objmatch_pair_problem_t* problems, const oslam_objmatch_det_rows_t* pre,
+                                   const oslam_objmatch_det_rows_t* cur, const oslam_objmatch_params_t* params, int n_scores, float* similarity, float* iou, int32_t* n_assigned,
+                                   int32_t* status);
+/* The same over device arrays (pre, cur and params are host structs; the row pointers are device pointers), asynchronous on `stream`. */
+int oslam_objmatch_match_two_frame_device(oslam_objmatch_t* h, int n_problems, const oslam_objmatch_pair_problem_t* d_problems, const oslam_objmatch_det_rows_t* pre,
+                                          const oslam_objmatch_det_rows_t* cur, const oslam_objmatch_params_t* params, int n_scores, float* d_similarity, float* d_iou,
+                                          int32_t* d_n_assigned, int32_t* d_status, void* stream);
+/* ObjectMatcher::MatchMapToFrame (src/ObjectMatcher.cc:442-801).  n_by_similarity and n_by_distance [n_problems]: the claims of the rule of :783 and
+ * of the rule of :789. */
+int oslam_objmatch_match_map_to_frame(oslam_objmatch_t* h, int n_problems, const oslam_objmatch_map_problem_t* problems, const oslam_objmatch_det_rows_t* cur,
+                                      const oslam_objmatch_obj_rows_t* objects, const oslam_objmatch_params_t* params, int n_scores, float* similarity, float* mean_dist,
+                                      float* min_dist, int32_t* n_by_similarity, int32_t* n_by_distance, int32_t* status);
+int oslam_objmatch_match_map_to_frame_device(oslam_objmatch_t* h, int n_problems, const oslam_objmatch_map_problem_t* d_problems, const oslam_objmatch_det_rows_t* cur,
+                                             const oslam_objmatch_obj_rows_t* objects, const oslam_objmatch_params_t* params, int n_scores, float* d_similarity, float* d_mean_dist,
+                                             float* d_min_dist, int32_t* d_n_by_similarity, int32_t* d_n_by_distance, int32_t* d_status, void* stream);
+/* Measurement: with timing on, every later call records events before, between and after its launches on the call's stream;
+ * oslam_objmatch_last_kernel_ms waits for the last call's events and gives the milliseconds of the counting kernel and of the combine pass of a
+ * histogram call, or of the one kernel of a matcher call and 0. */
+int oslam_objmatch_set_timing(oslam_objmatch_t* h, int on);
+int oslam_objmatch_last_kernel_ms(oslam_objmatch_t* h, float ms[2]);
+
 #ifdef __cplusplus
 }
 #endif

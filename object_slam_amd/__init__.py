@@ -30,3 +30,5 @@ from .initializer import Initializer  # noqa: F401
 from . import initializer  # noqa: F401
 from .search_init import InitMatcher  # noqa: F401
 from . import search_init  # noqa: F401
+from .object_match import ObjectMatcher  # noqa: F401
+from . import object_match  # noqa: F401
