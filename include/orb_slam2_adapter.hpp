@@ -4,7 +4,8 @@
 // (include/Optimizer.h:38-57: PoseOptimization, LocalBundleAdjustment, BundleAdjustment, OptimizeSim3, OptimizeEssentialGraph) and ObjectOptimizer::PoseOptimization2
 // (include/ObjectOptimizer.h:23), ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: loadFromTextFile, transform, score) ORB_SLAM2::PnPsolver (include/PnPsolver.h: SetRansacParameters, iterate, find) and ORB_SLAM2::Sim3Solver (include/Sim3Solver.h: SetRansacParameters, iterate, find, GetEstimatedRotation / Translation / Scale) and ORB_SLAM2::KeyFrameDatabase (include/KeyFrameDatabase.h: add, erase, clear,
 // DetectLoopCandidates, DetectRelocalizationCandidates) and ORB_SLAM2::ObjectMatcher (include/ObjectMatcher.h: MatchTwoFrame, MatchMapToFrame) with Frame::ExtractHSVHistogramsFromMask
-// (src/Frame.cc:388) as a free function.  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
+// (src/Frame.cc:388) as a free function, and ORB_SLAM2::Object3D (include/ObjectTypes.h: Update, RejectOutliers, CalculateCenterAndSize) with RejectNewObjectOutliers
+// (the new-object path of Tracking::UpdateCurrentObject) and ObjectMapRegularization / MergeObject (src/Map.cc:67-157) as free functions.  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
 // "view" of exactly the members it reads and writes (the gather loops are in INTEGRATION.md).  tests/adapter_program.cc uses nothing but
 // these classes; tests/test_adapter_gpu.py builds it, runs it and compares its outputs with the ctypes path.
 //
@@ -14,6 +15,7 @@
 // 28-byte layout) and descriptors are cv::Mat CV_8U N x 32.
 #pragma once
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <algorithm>
 #include <map>
@@ -1240,7 +1242,14 @@ private:
     int32_t diag_[5] = {0, 0, 0, 0, 0};
 };
 
-// ---- the object layer: what Tracking::TrackObject (src/Tracking.cc:1058-1076) reads and writes ----
+// ---- the object layer: what Tracking::TrackObject (src/Tracking.cc:1058-1076) and Tracking::UpdateCurrentObject (:1079-1207) read and write ----
+struct MapPointView {                     // the members of a MapPoint the object layer reads; identity is the address, as in the reference
+    float mWorldPos[3] = {0, 0, 0};
+    bool mbBad = false;
+    std::map<int, int> mLabelCnt;         // MapPoint::AddLabelCnt (src/MapPoint.cc:82-94)
+    void AddLabelCnt(int label) { mLabelCnt[label]++; }
+    bool isBad() const { return mbBad; }
+};
 struct Object2DView {                     // Object2D (include/ObjectTypes.h)
     int label = 0;
     float x = 0, y = 0, w = 0, h = 0;     // the 2-D box
@@ -1249,6 +1258,7 @@ struct Object2DView {                     // Object2D (include/ObjectTypes.h)
     std::vector<float> kps;               // per mvFrameKpIndices entry: mvKeysUn[i].pt.x, .pt.y, mvDepth[i] (> 0)
     float mHSVHistogram[OSLAM_OBJMATCH_BINS] = {};
     int track_id = -1;
+    std::vector<int> mvFrameKpIndices;    // the frame's keypoints inside the detection (Object3D::Update, UpdateCurrentObject)
 };
 struct ObjectFrameView {                  // the members of a Frame the object layer touches
     const uint8_t* imRGB = nullptr;       // CV_8UC3, read as B, G, R
@@ -1258,6 +1268,8 @@ struct ObjectFrameView {                  // the members of a Frame the object l
     std::vector<Object2DView> mvObject2Ds;
     std::vector<int> mvpObject3Ds;        // per detection the Object3D's mTrackID, -1 = NULL
     std::vector<int> mvObject3DLabels;    // per detection that Object3D's mLabel (MatchTwoFrame reads pObj3D->mLabel of the previous frame)
+    std::vector<MapPointView*> mvpMapPoints;   // per keypoint, NULL = none; with mvbOutlier what Object3D::Update and UpdateCurrentObject read
+    std::vector<bool> mvbOutlier;
 };
 struct ObjectObservationView {            // ObjectObservation: ObjectCenterW and AppearanceVec (ObsCamPoseTcw only feeds the unused view vectors)
     float ObjectCenterW[3];
@@ -1391,6 +1403,187 @@ inline void ExtractHSVHistogramsFromMask(ObjectMatcher& matcher, ObjectFrameView
     std::vector<float> hist((size_t)n * OSLAM_OBJMATCH_BINS);
     oslam::throw_on(oslam_objmatch_hsv_histograms(h, 1, F.cols, F.rows, F.step, F.cols, F.imRGB, &fr, n, masks.data(), counts.data(), hist.data()));
     for (int k = 0; k < n; k++) std::memcpy(F.mvObject2Ds[k].mHSVHistogram, hist.data() + (size_t)k * OSLAM_OBJMATCH_BINS, sizeof(float) * OSLAM_OBJMATCH_BINS);
+}
+
+// ---- the object map: Object3D (include/ObjectTypes.h) and Map::ObjectMapRegularization (src/Map.cc:67-157) over oslam_hip.h's "Object map maintenance" ----
+#define OSLAM_MIN_OBJ3DMP_NUM 5   // MIN_OBJ3DMP_NUM (include/ObjectTypes.h)
+
+namespace objmap_detail {
+// one handle for the process: the calls are one problem each, synchronous
+inline oslam_objmap_t* handle() {
+    struct Holder {
+        oslam_objmap_t* h = nullptr;
+        ~Holder() { oslam_objmap_destroy(h); }
+    };
+    static Holder holder;
+    if (!holder.h) oslam::throw_on(oslam_objmap_create(&holder.h, 1, OSLAM_OBJMAP_MIN_CLUSTER_POINTS, OSLAM_OBJMAP_MAX_OBJECTS));
+    return holder.h;
+}
+inline void positions(const std::vector<MapPointView*>& vpMps, std::vector<float>& pos) {
+    pos.resize(3 * vpMps.size());
+    for (size_t i = 0; i < vpMps.size(); i++) std::memcpy(pos.data() + 3 * i, vpMps[i]->mWorldPos, sizeof(float) * 3);
+}
+// the rejection of one list; vpMps is reduced to the kept points (ReduceVector).  Returns the result record.
+inline oslam_objmap_result_t reject(std::vector<MapPointView*>& vpMps, int mode, int label) {
+    const int n = (int)vpMps.size();
+    std::vector<float> pos;
+    positions(vpMps, pos);
+    std::vector<int32_t> cnt(n, 0), sum(n, 0), cluster(n, -1);
+    if (mode == OSLAM_OBJMAP_MODE_UPDATE)
+        for (int i = 0; i < n; i++) {   // MapPoint::GetLabelProb (src/MapPoint.cc:109-137) as its two integers
+            const std::map<int, int>& m = vpMps[i]->mLabelCnt;
+            const auto it = m.find(label);
+            cnt[i] = it == m.end() ? 0 : it->second;
+            for (const auto& e : m) sum[i] += e.second;
+        }
+    std::vector<uint8_t> keep(n, 0);
+    oslam_objmap_problem_t pr = {0, n, mode, 0};
+    oslam_objmap_result_t res = {};
+    oslam::throw_on(oslam_objmap_reject_outliers(handle(), 1, &pr, n, pos.data(), cnt.data(), sum.data(), keep.data(), cluster.data(), &res));
+    if (res.status != OSLAM_OBJMAP_DONE) throw std::runtime_error("RejectOutliers: the problem was refused (more clustering points than the handle holds)");
+    size_t j = 0;
+    for (int i = 0; i < n; i++)
+        if (keep[i]) vpMps[j++] = vpMps[i];
+    vpMps.resize(j);
+    return res;
+}
+}  // namespace objmap_detail
+
+// The new-object path of Tracking::UpdateCurrentObject (src/Tracking.cc:1138-1199) on the detection's map points (:1120-1137): clustering, the shortcut, the
+// two rules and ReduceVector.  Returns whether an Object3D is to be created from what vpCandidateMps holds afterwards.
+inline bool RejectNewObjectOutliers(std::vector<MapPointView*>& vpCandidateMps) {
+    if (vpCandidateMps.empty()) return false;
+    const oslam_objmap_result_t res = objmap_detail::reject(vpCandidateMps, OSLAM_OBJMAP_MODE_NEW_OBJECT, 0);
+    return res.path == OSLAM_OBJMAP_PATH_SHORTCUT || (int)vpCandidateMps.size() > OSLAM_MIN_OBJ3DMP_NUM;
+}
+
+class Object3D {
+public:
+    static int& nNextId() { static int n = 0; return n; }
+    // Object3D(vector<MapPoint*> &vpObj3DMps, int Obj2DidxF, Frame* F) (src/ObjectTypes.cc:33-53); MapPoint::SetInsertedTime is bookkeeping nothing here reads
+    Object3D(const std::vector<MapPointView*>& vpObj3DMps, int Obj2DidxF, ObjectFrameView& F) : mvpMapPoints(vpObj3DMps) {
+        Object2DView& Obj2D = F.mvObject2Ds[Obj2DidxF];
+        mTrackID = nNextId()++;
+        mLabel = Obj2D.label;
+        Obj2D.track_id = mTrackID;
+        CalculateCenterAndSize();
+        AddObservation(Obj2D);
+    }
+    // void Update(int Obj2DidxF, Frame *F) (:55-139)
+    void Update(int Obj2DidxF, ObjectFrameView& F) {
+        mUpdateCnt++;
+        Object2DView& Obj2D = F.mvObject2Ds[Obj2DidxF];
+        Obj2D.track_id = mTrackID;
+        std::vector<MapPointView*> vpCandidateMps;
+        for (int idx : Obj2D.mvFrameKpIndices) {   // :65-88
+            MapPointView* pMp = F.mvpMapPoints[idx];
+            if (!pMp || pMp->isBad() || F.mvbOutlier[idx]) continue;
+            if (!std::count(mvpMapPoints.begin(), mvpMapPoints.end(), pMp)) vpCandidateMps.push_back(pMp);   // (a point twice in the detection is appended twice, as there)
+        }
+        for (MapPointView* p : vpCandidateMps) { mvpMapPoints.push_back(p); mnNewAddedMpNum++; }   // :89-97
+        RejectOutliers();           // :117-124
+        CalculateCenterAndSize();   // :130
+        AddObservation(Obj2D);      // :131-132
+        if (mUpdateCnt > 5 && mvpMapPoints.size() < 5) mbVaild = false;   // :135-138
+    }
+    // void RejectOutliers() (:152-162): RejectOutliersTEST5 above 3000 points, RejectOutliersTEST7 otherwise
+    void RejectOutliers() {
+        mnNewAddedMpNum = 0;
+        if (mvpMapPoints.empty()) return;
+        objmap_detail::reject(mvpMapPoints, OSLAM_OBJMAP_MODE_UPDATE, mLabel);
+    }
+    // void CalculateCenterAndSize() (:805-833); an empty list leaves the members as they are
+    void CalculateCenterAndSize() {
+        const int n = (int)mvpMapPoints.size();
+        if (n == 0) return;
+        std::vector<float> pos;
+        objmap_detail::positions(mvpMapPoints, pos);
+        oslam_objmap_problem_t pr = {0, n, 0, 0};
+        oslam_objmap_result_t res = {};
+        oslam::throw_on(oslam_objmap_center_and_size(objmap_detail::handle(), 1, &pr, n, pos.data(), &res));
+        std::memcpy(mCenterW, res.center, sizeof mCenterW);
+        mMaxXw = res.bbox[0]; mMaxYw = res.bbox[1]; mMaxZw = res.bbox[2]; mMinXw = res.bbox[3]; mMinYw = res.bbox[4]; mMinZw = res.bbox[5];
+    }
+    bool isVaild() const { return mbVaild; }
+    Object3DView view() const {   // what ObjectMatcher::MatchMapToFrame reads
+        Object3DView v;
+        v.mTrackID = mTrackID; v.mLabel = mLabel; v.mvObservations = mvObservations;
+        return v;
+    }
+
+    int mTrackID = -1, mLabel = 0, mUpdateCnt = 0, mnNewAddedMpNum = 0;
+    bool mbVaild = true;
+    float mCenterW[3] = {0, 0, 0};
+    float mMaxXw = 0, mMaxYw = 0, mMaxZw = 0, mMinXw = 0, mMinYw = 0, mMinZw = 0;
+    std::vector<MapPointView*> mvpMapPoints;
+    std::vector<ObjectObservationView> mvObservations;
+    Object3D* mpReplaced = nullptr;
+
+private:
+    void AddObservation(const Object2DView& Obj2D) {
+        ObjectObservationView obs;
+        std::memcpy(obs.ObjectCenterW, mCenterW, sizeof mCenterW);
+        std::memcpy(obs.AppearanceVec, Obj2D.mHSVHistogram, sizeof obs.AppearanceVec);
+        mvObservations.push_back(obs);
+    }
+};
+
+// void Map::MergeObject(vector<Object3D*> vpObj3DtoMerge) (src/Map.cc:114-157) with the target the device named: the list surgery on the host
+inline void MergeObject(const std::vector<Object3D*>& vpObj3DtoMerge, int target) {
+    std::vector<MapPointView*> vpNewMapPoints;
+    std::vector<ObjectObservationView> vNewObs;
+    for (Object3D* pObj3D : vpObj3DtoMerge) {
+        vpNewMapPoints.insert(vpNewMapPoints.end(), pObj3D->mvpMapPoints.begin(), pObj3D->mvpMapPoints.end());
+        vNewObs.insert(vNewObs.end(), pObj3D->mvObservations.begin(), pObj3D->mvObservations.end());
+    }
+    Object3D* pTargetObj3D = vpObj3DtoMerge[target];
+    pTargetObj3D->mvpMapPoints.swap(vpNewMapPoints);
+    pTargetObj3D->mvObservations.swap(vNewObs);
+    if (std::abs((int)pTargetObj3D->mvpMapPoints.size() - (int)vpNewMapPoints.size()) > 50) pTargetObj3D->RejectOutliers();
+    pTargetObj3D->CalculateCenterAndSize();
+    pTargetObj3D->mUpdateCnt++;
+    for (size_t idx = 0; idx < vpObj3DtoMerge.size(); idx++)
+        if ((int)idx != target) vpObj3DtoMerge[idx]->mpReplaced = pTargetObj3D;
+}
+
+// void Map::ObjectMapRegularization() (src/Map.cc:67-112) over GetAllObject3Ds() in the caller's order (the reference's is that of a std::set of pointers; pass
+// ascending mTrackID): the merge sets on the device, MergeObject per set in set order on the host.  Objects that were replaced are taken out of vpObj3Ds
+// (mspObject3Ds.erase) and returned; they stay alive, their mpReplaced names the target.
+inline std::vector<Object3D*> ObjectMapRegularization(std::vector<Object3D*>& vpObj3Ds) {
+    const int N = (int)vpObj3Ds.size();
+    std::vector<Object3D*> erased;
+    if (N < 2) return erased;
+    if (N > OSLAM_OBJMAP_MAX_OBJECTS) throw std::runtime_error("ObjectMapRegularization: more than 128 objects in the map");
+    std::vector<int32_t> label(N), track(N), target(N, -1);
+    std::vector<float> bbox(6 * (size_t)N), ratio((size_t)N * N);
+    std::vector<uint8_t> member((size_t)N * N, 0);
+    for (int i = 0; i < N; i++) {
+        const Object3D* o = vpObj3Ds[i];
+        label[i] = o->mLabel; track[i] = o->mTrackID;
+        const float b[6] = {o->mMaxXw, o->mMaxYw, o->mMaxZw, o->mMinXw, o->mMinYw, o->mMinZw};
+        std::memcpy(bbox.data() + 6 * (size_t)i, b, sizeof b);
+    }
+    oslam_objmap_merge_problem_t pr = {N, 0, 0, 0};
+    int32_t n_sets = 0, status = 0;
+    oslam::throw_on(oslam_objmap_merge_sets(objmap_detail::handle(), 1, &pr, N, label.data(), track.data(), bbox.data(), 6, N * N, ratio.data(), member.data(), target.data(), &n_sets, &status));
+    if (status != OSLAM_OBJMAP_DONE) throw std::runtime_error("ObjectMapRegularization: the problem was refused");
+    std::set<Object3D*> gone;
+    for (int s = 0; s < n_sets; s++) {
+        std::vector<Object3D*> vpObj3DtoMerge;
+        int t = -1;
+        for (int i = 0; i < N; i++)
+            if (member[(size_t)s * N + i]) {
+                if (i == target[s]) t = (int)vpObj3DtoMerge.size();
+                vpObj3DtoMerge.push_back(vpObj3Ds[i]);
+            }
+        MergeObject(vpObj3DtoMerge, t);
+        for (size_t k = 0; k < vpObj3DtoMerge.size(); k++)
+            if ((int)k != t) gone.insert(vpObj3DtoMerge[k]);
+    }
+    std::vector<Object3D*> left;
+    for (Object3D* o : vpObj3Ds) (gone.count(o) ? erased : left).push_back(o);
+    vpObj3Ds.swap(left);
+    return erased;
 }
 
 }  // namespace ORB_SLAM2

@@ -1774,6 +1774,118 @@ int oslam_objmatch_match_map_to_frame_device(oslam_objmatch_t* h, int n_problems
 int oslam_objmatch_set_timing(oslam_objmatch_t* h, int on);
 int oslam_objmatch_last_kernel_ms(oslam_objmatch_t* h, float ms[2]);
 
+/* ------------------------------------------------------------------------------------------
+ * Object map maintenance — what the reference does with an association once it has one: Object3D::RejectOutliers (src/ObjectTypes.cc:152-162) at the
+ * end of Object3D::Update (:117-124) and inside Map::MergeObject (src/Map.cc:138-139), the new-object path of Tracking::UpdateCurrentObject
+ * (src/Tracking.cc:1113-1199), Object3D::CalculateCenterAndSize (src/ObjectTypes.cc:805-833) and the merge sets of Map::ObjectMapRegularization
+ * (src/Map.cc:47-112), for batches of independent objects and maps.  Operators: the driver does not call them; oslam_slam.h still takes the caller's
+ * track_id and keeps Object3D::Update's list logic without the rejection.  PCL is not in the tree; what its Euclidean clustering computes is restated.
+ *
+ * Rows are map points: pos [.][3] float world position, label_cnt and label_sum int32 (the count of the object's label in the point's mLabelCnt and
+ * the sum over all labels).  A problem (oslam_objmap_problem_t) is one point list: rows off .. off + n - 1 in list order, and a mode.
+ *
+ * 1. oslam_objmap_reject_outliers.  One sequential scan in list order (RejectOutliersTEST5 :590-628, RejectOutliersTEST7 :661-764, Tracking.cc:1120-1137):
+ *     - mode UPDATE: a row is bad when GetLabelProb(mLabel) < 0.5 (:143-148, src/MapPoint.cc:109-137): (float)((double)label_cnt / (double)label_sum)
+ *       compared against the double 0.5, probability 0 when label_sum == 0.  Bad rows are dropped.  Mode NEW_OBJECT has no bad test.
+ *     - the other rows are the candidates: Center += PosW in float per component; square = (float)sqrt(x*x + y*y + z*z) with the squares and the sum
+ *       in double (cv::norm); SquareSum = SquareSum + square * square in float.
+ *     - Center = Center * (float)(1.0 / N) (Mat / double); CandidatesStdDev = (float)sqrt((double)SquareSum / (double)N - norm * norm) with norm the
+ *       double cv::norm of Center.  This simplified variance cancels far from the origin and can be negative: the root is NaN and every
+ *       `dist > 3 * StdDev` is false.
+ *    Path TEST5 (mode UPDATE and n > 3000): a candidate is dropped when dist > 3.0f * StdDev, dist = (float)sqrt of the double sum of the squared float
+ *    differences to Center.  Rows are streamed from global memory; n is unbounded.
+ *    Path TEST7 (mode UPDATE and n <= 3000; mode NEW_OBJECT always): the candidates with finite coordinates are clustered as
+ *    pcl::EuclideanClusterExtraction does with tolerance 0.1, minimum size 1, maximum 9999: the connected components of "d2 < (float)(0.1 * 0.1)",
+ *    d2 = dx*dx + dy*dy + dz*dz in float in that order (FLANN L2_Simple<float>), strict.  A cluster with (double)(float)((double)size / (double)N) < 0.1
+ *    and N > 15 is dropped whole; in every other cluster the 3-sigma rule above applies per point.  A candidate with a non-finite coordinate is in no
+ *    cluster: no rule drops it.  Path SHORTCUT (mode NEW_OBJECT, one cluster, N > 5: Tracking.cc:1158): everything is kept.
+ *    Per row: keep (uint8) and cluster (int32: the smallest row index, relative to the problem, of the row's component; -1 for a row in no cluster and
+ *    on path TEST5).  Per problem an oslam_objmap_result_t; center and bbox are those of the kept rows (item 2) and stay untouched when nothing is kept.
+ *    The clustering stages positions and one component label per point in LDS: n <= the handle's max_cluster_points.  Components are found by rounds of
+ *    (every point takes the smallest label among its neighbours; every component root hooks onto the smallest label seen by its members; pointer
+ *    jumping until every point names its root).  Roots that are no local minimum disappear each round, so a chain of any length needs O(log n) rounds;
+ *    `rounds` reports them.  The outcome does not depend on the order of anything: results are bit-identical from run to run.
+ *
+ * 2. oslam_objmap_center_and_size (CalculateCenterAndSize :805-833) of every row of a problem: the float sum in list order divided by (float)n
+ *    (Eigen::Vector3f / double), and per axis the minimum and maximum.  Writes n_kept = n, center and bbox of the result; nothing when n == 0.
+ *    bbox is in the order of ObjectMatcher's BBox3D (src/ObjectMatcher.cc:838): max x, max y, max z, min x, min y, min z.
+ *
+ * 3. oslam_objmap_merge_sets (Map::ObjectMapRegularization src/Map.cc:67-100, CheckIfMerge :47-65, Compute3DOverlapRatio
+ *    src/ObjectMatcher.cc:844-873).  A problem (oslam_objmap_merge_problem_t) is one map's objects in the caller's order (the adapter passes ascending
+ *    mTrackID): rows label, track_id and bbox (bbox_stride floats from one row to the next, so that the array may be the bbox members of result
+ *    records).  ratio [n][n] at off_pair, entries i < j written: the overlap ratio in float, std::max(a, b) = a < b ? b : a, std::min(a, b) = b < a ?
+ *    b : a, 0 when an axis has min >= max.  Pair (i, j) merges when the labels are equal, the track ids differ and (double)ratio > 0.4.  The merging
+ *    pairs are replayed in lexicographic order: a pair enters every existing set that holds either index, and opens a new set when there is none.
+ *    Sets are not merged transitively; an index can sit in several.  member [.][n] uint8 at off_pair: rows 0 .. n_sets - 1 written; target [.] at
+ *    off_obj: entries 0 .. n_sets - 1 written, the member of largest track_id, the first among equals (Map.cc:121-129).  n <= 128.
+ *
+ * Normalisations (readings of published sources that are not pinned here): the cv::norm, Mat / double, Eigen / double, L2_Simple and
+ * non-finite rules above; std::sort of a list holding NaN is undefined: minimum and maximum start at +inf / -inf and move on a strict < / >, so NaN
+ * is skipped and the first of equal values stays; every NaN written is the quiet NaN 0x7fc00000; MergeObject's MaxTrackID starts at -1, so a set of
+ * negative track ids has no defined target: the first member.
+ *
+ * Refusals: more problems than max_problems or a negative count: OSLAM_E_CAPACITY; NULL pointers: OSLAM_E_INVALID.  The host entry points read the
+ * records: a negative n, an unknown mode or rows outside the arrays are OSLAM_E_INVALID, a clustering problem above max_cluster_points or a map above
+ * max_objects OSLAM_E_CAPACITY, before anything is launched.  The device entry points cannot: such a problem gets a negative status and nothing else
+ * of it is written.  Problems of one call must not share rows; rows no problem owns are never written.  No atomics on global memory.
+ * ---------------------------------------------------------------------------------------- */
+#define OSLAM_OBJMAP_MODE_UPDATE 0        /* Object3D::RejectOutliers */
+#define OSLAM_OBJMAP_MODE_NEW_OBJECT 1    /* Tracking::UpdateCurrentObject's new-object path */
+#define OSLAM_OBJMAP_PATH_TEST5 0
+#define OSLAM_OBJMAP_PATH_TEST7 1
+#define OSLAM_OBJMAP_PATH_SHORTCUT 2
+#define OSLAM_OBJMAP_TEST5_ABOVE 3000     /* src/ObjectTypes.cc:154 */
+#define OSLAM_OBJMAP_MIN_CLUSTER_POINTS 3000
+#define OSLAM_OBJMAP_MAX_CLUSTER_POINTS 4000   /* 16 bytes of LDS per point */
+#define OSLAM_OBJMAP_MAX_OBJECTS 128      /* per map: a set is a lane of one wavefront, its members two 64-bit words */
+#define OSLAM_OBJMAP_DONE 0
+#define OSLAM_OBJMAP_REFUSED_RECORD (-1)     /* a negative n, an unknown mode, rows outside the arrays */
+#define OSLAM_OBJMAP_REFUSED_CAPACITY (-2)   /* a clustering problem above max_cluster_points, a map above max_objects */
+typedef struct oslam_objmap oslam_objmap_t;
+typedef struct oslam_objmap_problem {
+    int32_t off, n;   /* rows off .. off + n - 1, in list order */
+    int32_t mode;     /* OSLAM_OBJMAP_MODE_* (center_and_size ignores it) */
+    int32_t reserved;
+} oslam_objmap_problem_t;
+typedef struct oslam_objmap_result {
+    int32_t status;        /* OSLAM_OBJMAP_* */
+    int32_t n_candidates, n_clusters, n_kept;
+    int32_t path;          /* OSLAM_OBJMAP_PATH_* */
+    int32_t rounds;        /* of the component search */
+    float std_dev, candidates_center[3];
+    float center[3], bbox[6];   /* of the kept rows; max x, y, z, min x, y, z */
+    int32_t reserved;
+} oslam_objmap_result_t;
+typedef struct oslam_objmap_merge_problem {
+    int32_t n, off_obj;   /* the map's objects: rows off_obj .. off_obj + n - 1; target entries from off_obj */
+    int32_t off_pair;     /* ratio [n][n] floats and member [.][n] bytes start here */
+    int32_t reserved;
+} oslam_objmap_merge_problem_t;
+/* max_cluster_points 3000 .. 4000, max_objects 1 .. 128.  Uses the current device.  OSLAM_E_HIP without a device: there is no CPU fallback. */
+int oslam_objmap_create(oslam_objmap_t** out, int max_problems, int max_cluster_points, int max_objects);
+void oslam_objmap_destroy(oslam_objmap_t* h);
+/* Item 1.  Host pointers; one upload, one launch, one download, synchronous.  pos [n_rows][3], label_cnt, label_sum, keep, cluster [n_rows] (the label
+ * arrays may be NULL when every problem is of mode NEW_OBJECT), results [n_problems]. */
+int oslam_objmap_reject_outliers(oslam_objmap_t* h, int n_problems, const oslam_objmap_problem_t* problems, int n_rows, const float* pos, const int32_t* label_cnt,
+                                 const int32_t* label_sum, uint8_t* keep, int32_t* cluster, oslam_objmap_result_t* results);
+/* The same over device arrays, asynchronous on `stream`, no host synchronisation.  The records cannot be read here, so the label arrays are required. */
+int oslam_objmap_reject_outliers_device(oslam_objmap_t* h, int n_problems, const oslam_objmap_problem_t* d_problems, int n_rows, const float* d_pos, const int32_t* d_label_cnt,
+                                        const int32_t* d_label_sum, uint8_t* d_keep, int32_t* d_cluster, oslam_objmap_result_t* d_results, void* stream);
+/* Item 2. */
+int oslam_objmap_center_and_size(oslam_objmap_t* h, int n_problems, const oslam_objmap_problem_t* problems, int n_rows, const float* pos, oslam_objmap_result_t* results);
+int oslam_objmap_center_and_size_device(oslam_objmap_t* h, int n_problems, const oslam_objmap_problem_t* d_problems, int n_rows, const float* d_pos,
+                                        oslam_objmap_result_t* d_results, void* stream);
+/* Item 3.  label, track_id, target [n_rows]; bbox: row r at bbox + r * bbox_stride floats, bbox_stride >= 6; ratio [n_pairs] float and member [n_pairs]
+ * uint8; n_sets and status [n_problems]. */
+int oslam_objmap_merge_sets(oslam_objmap_t* h, int n_problems, const oslam_objmap_merge_problem_t* problems, int n_rows, const int32_t* label, const int32_t* track_id,
+                            const float* bbox, int bbox_stride, int n_pairs, float* ratio, uint8_t* member, int32_t* target, int32_t* n_sets, int32_t* status);
+int oslam_objmap_merge_sets_device(oslam_objmap_t* h, int n_problems, const oslam_objmap_merge_problem_t* d_problems, int n_rows, const int32_t* d_label,
+                                   const int32_t* d_track_id, const float* d_bbox, int bbox_stride, int n_pairs, float* d_ratio, uint8_t* d_member, int32_t* d_target,
+                                   int32_t* d_n_sets, int32_t* d_status, void* stream);
+/* Measurement, as oslam_objmatch_set_timing: the milliseconds of the last call's one kernel, and 0. */
+int oslam_objmap_set_timing(oslam_objmap_t* h, int on);
+int oslam_objmap_last_kernel_ms(oslam_objmap_t* h, float ms[2]);
+
 #ifdef __cplusplus
 }
 #endif

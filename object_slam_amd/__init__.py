@@ -32,3 +32,5 @@ from .search_init import InitMatcher  # noqa: F401
 from . import search_init  # noqa: F401
 from .object_match import ObjectMatcher  # noqa: F401
 from . import object_match  # noqa: F401
+from .object_map import ObjectMap  # noqa: F401
+from . import object_map  # noqa: F401
