@@ -16,11 +16,54 @@
 
 #include "../../include/oslam_slam.h"
 #include "common.h"
+#include "kf_record_layout.h"
 #include "slam_pool.h"
+#include "stage_layout.h"
 
 namespace {
 
-#define OPS_CHECK(x) OSLAM_CHECK(x)
+using oslam::StageLayout;
+using oslam::copy_elems;
+
+// One growing device array of fixed-size records per slot, and the device copy of the [S] pointers (the kernels index table[slot][record])
+class SlotTable {
+public:
+    SlotTable(size_t rec_bytes, bool zero_fill) : rec_bytes_(rec_bytes), zero_fill_(zero_fill) {}
+    void resize(int S) { blocks_.resize(S); cap_.resize(S, 0); dirty_ = true; }
+    size_t capacity(int slot) const { return cap_[slot]; }   // in records
+    uint8_t* block(int slot) const { return blocks_[slot]; }
+    uint8_t** device_table() const { return d_tab_.as<uint8_t*>(); }
+    int ensure(int slot, size_t need, hipStream_t strm) {
+        if (need <= cap_[slot]) return OSLAM_OK;
+        // 16 K records per sequence to start with, doubling: a growth costs an allocation, a device copy, a stream synchronisation and a free (measured on the
+        // 64-byte map-point records: 0.9 ms each, 22 s of the 64 s the MapPoint-update operator took in a 225-step run of 8 x 1024 sequences when the tables
+        // started at 4 K records x 1.5)
+        const size_t ncap = std::max<size_t>(need * 2, 16384);
+        oslam::DeviceBuffer nb;
+        OSLAM_CHECK(nb.alloc(ncap * rec_bytes_));
+        if (zero_fill_) OSLAM_HIP_CHECK(hipMemsetAsync(nb.ptr(), 0, ncap * rec_bytes_, strm));
+        if (blocks_[slot]) {
+            OSLAM_HIP_CHECK(hipMemcpyAsync(nb.ptr(), blocks_[slot], cap_[slot] * rec_bytes_, hipMemcpyDeviceToDevice, strm));
+            OSLAM_HIP_CHECK(hipStreamSynchronize(strm));
+        }
+        blocks_.put(slot, std::move(nb)); cap_[slot] = ncap; dirty_ = true;
+        return OSLAM_OK;
+    }
+    int sync(hipStream_t strm) {   // the device pointer table follows the host's
+        if (!dirty_) return OSLAM_OK;
+        if (!d_tab_.ptr()) OSLAM_CHECK(d_tab_.alloc(sizeof(uint8_t*) * blocks_.size()));
+        OSLAM_HIP_CHECK(hipMemcpyAsync(d_tab_.ptr(), blocks_.data(), sizeof(uint8_t*) * blocks_.size(), hipMemcpyHostToDevice, strm));
+        OSLAM_HIP_CHECK(hipStreamSynchronize(strm));   // (the host table is pageable memory: the copy must have read it before it can change again)
+        dirty_ = false;
+        return OSLAM_OK;
+    }
+private:
+    const size_t rec_bytes_;
+    const bool zero_fill_;
+    oslam::DeviceBlocks blocks_; std::vector<size_t> cap_;   // [S] device arrays and their capacity in records
+    oslam::DeviceBuffer d_tab_;                              // uint8_t* [S]
+    bool dirty_ = true;
+};
 
 struct LbaService;
 struct LbaJob {   // one handle's submission to the local-BA service (below)
@@ -71,9 +114,12 @@ struct HipOps {
     // keyframe_raw_keys / keyframe_descriptors, frame_descriptors reads the current frames' rows from the extractor's batch arrays
     bool lazy_rows = false;
     oslam::PinnedBuffer kfk; std::vector<int32_t> kfk_slots;
+    oslam::Field<oslam_keypoint_t> kfk_keys{}; oslam::Field<uint8_t> kfk_desc{};   // rows of cap keypoints / cap descriptors, one per keyframe of kfk_slots
     static constexpr int kFuseCurStride = 16384, kFuseCurPairs = 2048;   // candidates / matches per job of fuse_into_current (beyond: overflow, the driver's own path)
     oslam::DeviceBuffer fc; uint32_t fc_stamp = 0;   // scratch of fuse_into_current / local_points_list
-    struct MpuPending { bool on = false; oslam_job_mp_update_t* j = nullptr; size_t P = 0, rBest = 0, rOut = 0, rOut5 = 0; double dtotal = 0; std::function<int()> launch; } mpu_pend;
+    struct MpuPending {   // (the fields of the result block the job was built on: dnB while it is pending)
+        bool on = false; oslam_job_mp_update_t* j = nullptr; oslam::Field<int32_t> rBest{}; oslam::Field<uint8_t> rOut{}; oslam::Field<float> rOut5{}; double dtotal = 0; std::function<int()> launch;
+    } mpu_pend;
     int mpu_launch_pending() { if (mpu_pend.on && mpu_pend.launch) { std::function<int()> f; f.swap(mpu_pend.launch); return f(); } return OSLAM_OK; }
     void swap_staging() { std::swap(up, upB); std::swap(dn, dnB); std::swap(tev0, tevB0); std::swap(tev1, tevB1); }
     oslam::DeviceBuffer d_lq, d_inview;                  // oslam_proj_query_t, uint8_t: one entry per local query
@@ -93,7 +139,7 @@ struct HipOps {
         if (d_loc.ptr() && loc_st == want) return OSLAM_OK;
         OSLAM_HIP_CHECK(hipStreamSynchronize(strm));
         loc_st = want;
-        OPS_CHECK(d_loc.alloc(65 * loc_st * S));
+        OSLAM_CHECK(d_loc.alloc(65 * loc_st * S));
         loc_id.assign(S, 0);
         return OSLAM_OK;
     }
@@ -109,11 +155,8 @@ struct HipOps {
     std::vector<uint8_t*> h_rec_desc;
     // a record = mvKeysUn, descriptors, mvuRight and — built once at registration (oslam_kf_grid_build_device) — the feature grid: cell ends + candidates sorted by cell
     // (+ the mirror of the observation graph, round 5: the keyframe's point list, "which point observes keypoint i" and the usable-depth bits: oslam_slam_ops_t::map_journal)
-    size_t rec_core_bytes() const {
-        return oslam::align_up((size_t)cap * sizeof(oslam_keypoint_t), 256) + oslam::align_up((size_t)cap * 32, 256) + oslam::align_up((size_t)cap * 4, 256) +
-               oslam::align_up((size_t)3072 * 2, 256) + oslam::align_up((size_t)cap * 16, 256);
-    }
-    size_t rec_bytes() const { return rec_core_bytes() + oslam::align_up((size_t)cap * 4, 256) + oslam::align_up((size_t)cap * 8, 256) + oslam::align_up(((size_t)cap + 31) / 32 * 4, 256); }
+    oslam::KfRecordLayout rec_lay;                        // follows cap (kf_record_layout.h)
+    size_t rec_bytes() const { return rec_lay.bytes; }
     std::vector<uint32_t> okf_seq;                        // [S] event counter of the mirror's okf cells (a cell keeps the event with the largest number)
     size_t mir_used = 0;                                  // bytes of the mirror's upload block in use by the flush / count request in flight
     oslam::PinnedBuffer cull;                             // pinned result block of kf_culling_counts
@@ -124,36 +167,16 @@ struct HipOps {
         if (bytes > mir.cap()) OSLAM_HIP_CHECK(hipStreamSynchronize(strm));
         return mir.grow(bytes, 1 << 20);
     }
-    int32_t* rec_mp(int r) const { return (int32_t*)(rec_ptr(r) + rec_core_bytes()); }
     // per-point scalars of the mirror: 32-byte records per slot, grown like the map-point table: (Observations(), isBad(), octave histogram) in the first 16 bytes,
     // then the transient marks of SearchInNeighbors' second direction (k_fusecur_*: 64-bit first-occurrence key, stamp of the current keyframe's points)
-    static constexpr size_t kPtAuxBytes = 32;
-    oslam::DeviceBlocks pt_aux; std::vector<size_t> pt_aux_cap;
-    oslam::DeviceBuffer d_pt_aux, d_rec_chunk; size_t rec_chunk_n = 0;   // uint8_t* [S], uint8_t* [chunks]: device copies of the two pointer tables
-    bool pt_aux_dirty = true;
-    void size_pt_aux() { if ((int)pt_aux.size() < S) { pt_aux.resize(S); pt_aux_cap.resize(S, 0); pt_aux_dirty = true; } }
-    int ensure_pt_aux(int slot, size_t need) {
-        size_pt_aux();
-        if (need <= pt_aux_cap[slot]) return OSLAM_OK;
-        const size_t ncap = std::max<size_t>(need * 2, 16384);
-        oslam::DeviceBuffer nb;
-        OPS_CHECK(nb.alloc(ncap * kPtAuxBytes));
-        OSLAM_HIP_CHECK(hipMemsetAsync(nb.ptr(), 0, ncap * kPtAuxBytes, strm));
-        if (pt_aux[slot]) {
-            OSLAM_HIP_CHECK(hipMemcpyAsync(nb.ptr(), pt_aux[slot], pt_aux_cap[slot] * kPtAuxBytes, hipMemcpyDeviceToDevice, strm));
-            OSLAM_HIP_CHECK(hipStreamSynchronize(strm));
-        }
-        pt_aux.put(slot, std::move(nb)); pt_aux_cap[slot] = ncap; pt_aux_dirty = true;
-        return OSLAM_OK;
-    }
+    SlotTable pt_aux{32, /*zero_fill*/ true};
+    oslam::DeviceBuffer d_rec_chunk; size_t rec_chunk_n = 0;   // uint8_t* [chunks]: device copy of the record chunk pointers
     int sync_mirror_tables() {   // device copies of the per-slot aux pointers and of the record chunk pointers
-        size_pt_aux();
-        if (!d_pt_aux.ptr()) { OPS_CHECK(d_pt_aux.alloc(sizeof(uint8_t*) * S)); pt_aux_dirty = true; }
-        if (pt_aux_dirty) { OSLAM_HIP_CHECK(hipMemcpyAsync(d_pt_aux.ptr(), pt_aux.data(), sizeof(uint8_t*) * S, hipMemcpyHostToDevice, strm)); OSLAM_HIP_CHECK(hipStreamSynchronize(strm)); pt_aux_dirty = false; }
+        OSLAM_CHECK(pt_aux.sync(strm));
         if (sizeof(uint8_t*) * rec_chunks.size() > d_rec_chunk.cap()) {
             OSLAM_HIP_CHECK(hipStreamSynchronize(strm));
             rec_chunk_n = 0;
-            OPS_CHECK(d_rec_chunk.alloc(sizeof(uint8_t*) * (rec_chunks.size() * 2 + 64)));
+            OSLAM_CHECK(d_rec_chunk.alloc(sizeof(uint8_t*) * (rec_chunks.size() * 2 + 64)));
         }
         if (rec_chunk_n < rec_chunks.size()) {
             OSLAM_HIP_CHECK(hipMemcpyAsync(d_rec_chunk.as<uint8_t*>() + rec_chunk_n, rec_chunks.data() + rec_chunk_n, sizeof(uint8_t*) * (rec_chunks.size() - rec_chunk_n), hipMemcpyHostToDevice, strm));
@@ -162,41 +185,16 @@ struct HipOps {
         }
         return OSLAM_OK;
     }
-    uint8_t* rec_ptr(int r) const { return rec_chunks[r / kRecChunk] + (size_t)(r % kRecChunk) * rec_bytes(); }
-    const oslam_keypoint_t* rec_keys(int r) const { return (const oslam_keypoint_t*)rec_ptr(r); }
-    const uint8_t* rec_desc(int r) const { return rec_ptr(r) + oslam::align_up((size_t)cap * sizeof(oslam_keypoint_t), 256); }
-    const float* rec_ur(int r) const { return (const float*)(rec_desc(r) + oslam::align_up((size_t)cap * 32, 256)); }
-    uint16_t* rec_cell_end(int r) const { return (uint16_t*)((const uint8_t*)rec_ur(r) + oslam::align_up((size_t)cap * 4, 256)); }
-    float* rec_cand(int r) const { return (float*)((uint8_t*)rec_cell_end(r) + oslam::align_up((size_t)3072 * 2, 256)); }
+    uint8_t* rec_ptr(int r) const { return rec_chunks[r / kRecChunk] + (size_t)(r % kRecChunk) * rec_lay.bytes; }
+    const oslam_keypoint_t* rec_keys(int r) const { return at(rec_lay.keys, rec_ptr(r)); }
+    const uint8_t* rec_desc(int r) const { return at(rec_lay.desc, rec_ptr(r)); }
+    const float* rec_ur(int r) const { return at(rec_lay.ur, rec_ptr(r)); }
+    uint16_t* rec_cell_end(int r) const { return at(rec_lay.cell_end, rec_ptr(r)); }
+    float* rec_cand(int r) const { return at(rec_lay.cand, rec_ptr(r)); }
     int rec_lookup(int slot, int kf) const { return (slot >= 0 && slot < (int)rec_of_kf.size() && kf >= 0 && kf < (int)rec_of_kf[slot].size()) ? rec_of_kf[slot][kf] : -1; }
     // Resident map points: one growing array of 64-byte records per slot (position, normal, distances, descriptor), written by every MapPoint update
-    oslam::DeviceBlocks mp_tab; std::vector<size_t> mp_cap;     // [S] device arrays and their capacity in records
-    oslam::DeviceBuffer d_mp_tab;                               // uint8_t* [S]: device copy of the pointers
-    bool mp_tab_on = true, mp_tab_dirty = true;
-    int ensure_mp_records(int slot, size_t need) {
-        if ((int)mp_tab.size() < S) { mp_tab.resize(S); mp_cap.resize(S, 0); }
-        if (need <= mp_cap[slot]) return OSLAM_OK;
-        // 16 K records (1 MB) per sequence to start with, doubling: a growth costs an allocation, a device copy, a stream synchronisation and a free (measured:
-        // 0.9 ms each, 22 s of the 64 s the MapPoint-update operator took in a 225-step run of 8 x 1024 sequences when the tables started at 4 K records x 1.5)
-        const size_t ncap = std::max<size_t>(need * 2, 16384);
-        oslam::DeviceBuffer nb;
-        OPS_CHECK(nb.alloc(ncap * 64));
-        if (mp_tab[slot]) {
-            OSLAM_HIP_CHECK(hipMemcpyAsync(nb.ptr(), mp_tab[slot], mp_cap[slot] * 64, hipMemcpyDeviceToDevice, strm));
-            OSLAM_HIP_CHECK(hipStreamSynchronize(strm));
-        }
-        mp_tab.put(slot, std::move(nb)); mp_cap[slot] = ncap; mp_tab_dirty = true;
-        return OSLAM_OK;
-    }
-    int sync_mp_table() {   // the device pointer table follows the host's
-        if ((int)mp_tab.size() < S) { mp_tab.resize(S); mp_cap.resize(S, 0); mp_tab_dirty = true; }
-        if (!mp_tab_dirty) return OSLAM_OK;
-        if (!d_mp_tab.ptr()) OPS_CHECK(d_mp_tab.alloc(sizeof(uint8_t*) * (size_t)S));
-        OSLAM_HIP_CHECK(hipMemcpyAsync(d_mp_tab.ptr(), mp_tab.data(), sizeof(uint8_t*) * (size_t)S, hipMemcpyHostToDevice, strm));
-        OSLAM_HIP_CHECK(hipStreamSynchronize(strm));   // (mp_tab is pageable host memory: the copy must have read it before it can change again)
-        mp_tab_dirty = false;
-        return OSLAM_OK;
-    }
+    SlotTable mp_tab{64, /*zero_fill*/ false};
+    bool mp_tab_on = true;
     oslam::DeviceBuffer d_maskstage;                      // uint8_t: host masks of a stage, packed H x W
     // One-bit-per-pixel form of the step's masks (oslam_mask_bits_device), built by object_kps and reused by pose_opt2 of the SAME step: keyed by the
     // caller's mask pointer, valid while step_epoch (advanced by every Frame::Frame stage) equals bits_epoch
@@ -238,15 +236,9 @@ struct HipOps {
         OSLAM_HIP_CHECK(hipDeviceSynchronize());
         d_lq.release(); d_inview.release();
         const size_t ncap = entries + entries / 2 + 1024;
-        OPS_CHECK(d_lq.alloc(ncap * sizeof(oslam_proj_query_t)));
+        OSLAM_CHECK(d_lq.alloc(ncap * sizeof(oslam_proj_query_t)));
         return d_inview.alloc(ncap);
     }
-};
-
-// bump layout of the staging blocks
-struct Layout {
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t at = off; off += oslam::align_up(bytes ? bytes : 1, 256); return at; }
 };
 
 int h_max_keypoints(void* p) { return ((HipOps*)p)->cap; }
@@ -263,33 +255,33 @@ static int download_frames(HipOps* o, int n, const oslam_keypoint_t* d_kp, const
                            const float* d_dp, oslam_slam_frame_t* const* out) {
     o->d_kp = d_kp; o->d_desc = d_desc; o->d_cnt = d_cnt; o->cur_uRight = d_uR;
     const size_t cap = o->cap;
-    Layout L;
-    const size_t oCnt = L.take(4 * (size_t)n), oSt = L.take(8), oKeys = L.take(sizeof(oslam_keypoint_t) * cap * n), oKeysUn = L.take(sizeof(oslam_keypoint_t) * cap * n),
-                 oDesc = L.take(32 * cap * n), oUr = L.take(4 * cap * n), oDp = L.take(4 * cap * n);
-    OPS_CHECK(o->ensure_dn(L.off));
+    StageLayout R;
+    const auto rCnt = R.add<int32_t>(n), rSt = R.add<int32_t>(2); const auto rKeys = R.add<oslam_keypoint_t>(cap * n), rKeysUn = R.add<oslam_keypoint_t>(cap * n);
+    const auto rDesc = R.add<uint8_t>(32 * cap * n); const auto rUr = R.add<float>(cap * n), rDp = R.add<float>(cap * n);
+    OSLAM_CHECK(o->ensure_dn(R.total()));
     uint8_t* D = o->dn.bytes();
-    OSLAM_HIP_CHECK(hipMemcpyAsync(D + oCnt, d_cnt, 4 * (size_t)n, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(D + oSt, d_st, 4, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(D + oSt + 4, o->d_status.as<int32_t>(), 4, hipMemcpyDeviceToHost, o->strm));
-    if (!o->lazy_rows) OSLAM_HIP_CHECK(hipMemcpyAsync(D + oKeys, d_kp, sizeof(oslam_keypoint_t) * cap * n, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(D + oKeysUn, o->d_keysUn.as<oslam_keypoint_t>(), sizeof(oslam_keypoint_t) * cap * n, hipMemcpyDeviceToHost, o->strm));
-    if (!o->lazy_rows) OSLAM_HIP_CHECK(hipMemcpyAsync(D + oDesc, d_desc, 32 * cap * n, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(D + oUr, d_uR, 4 * cap * n, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(D + oDp, d_dp, 4 * cap * n, hipMemcpyDeviceToHost, o->strm));
+    int32_t* st = at(rSt, D);   // (extractor's overflow flag, status word of the depth lookup / the right extractor)
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rCnt, D), d_cnt, rCnt.bytes, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(st, d_st, sizeof(*st), hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(st + 1, o->d_status.as<int32_t>(), sizeof(*st), hipMemcpyDeviceToHost, o->strm));
+    if (!o->lazy_rows) OSLAM_HIP_CHECK(hipMemcpyAsync(at(rKeys, D), d_kp, rKeys.bytes, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rKeysUn, D), o->d_keysUn.as<oslam_keypoint_t>(), rKeysUn.bytes, hipMemcpyDeviceToHost, o->strm));
+    if (!o->lazy_rows) OSLAM_HIP_CHECK(hipMemcpyAsync(at(rDesc, D), d_desc, rDesc.bytes, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rUr, D), d_uR, rUr.bytes, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rDp, D), d_dp, rDp.bytes, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
-    const int32_t* st = (const int32_t*)(D + oSt);
     if (st[0]) { oslam::set_error("extractor arena overflow"); return OSLAM_E_CAPACITY; }
     if (st[1]) { oslam::set_error("keypoint outside the depth image / right extractor arena overflow"); return OSLAM_E_INVALID; }
-    const int32_t* cnt = (const int32_t*)(D + oCnt);
+    const int32_t* cnt = at(rCnt, D);
     o->pool->parallel_for(n, [&](int i) {
         oslam_slam_frame_t* f = out[i];
-        const size_t N = cnt[i], at = (size_t)i * cap;
+        const size_t N = cnt[i];
         f->N = (int)N;
-        if (!o->lazy_rows) memcpy(f->keys, D + oKeys + at * sizeof(oslam_keypoint_t), N * sizeof(oslam_keypoint_t));
-        memcpy(f->keysUn, D + oKeysUn + at * sizeof(oslam_keypoint_t), N * sizeof(oslam_keypoint_t));
-        if (!o->lazy_rows) memcpy(f->desc, D + oDesc + at * 32, N * 32);
-        memcpy(f->uRight, D + oUr + at * 4, N * 4);
-        memcpy(f->depth, D + oDp + at * 4, N * 4);
+        if (!o->lazy_rows) copy_elems(f->keys, row(rKeys, D, cap, i), N);
+        copy_elems(f->keysUn, row(rKeysUn, D, cap, i), N);
+        if (!o->lazy_rows) copy_elems(f->desc, row(rDesc, D, 32 * cap, i), 32 * N);
+        copy_elems(f->uRight, row(rUr, D, cap, i), N);
+        copy_elems(f->depth, row(rDp, D, cap, i), N);
     });
     return OSLAM_OK;
 }
@@ -308,41 +300,44 @@ static int frames_impl(HipOps* o, int n, const uint8_t* const* gray, int gray_st
     const void* const* dsrc = depth16 ? (const void* const*)depth16 : (const void* const*)depth;
     if (on_device) {   // two pointer tables up, ONE gather launch for the gray images (instead of 2n two-dimensional copies).  "Device" pointers only have to be
         // device-accessible: with pinned host images the gather and the depth lookup read them over PCIe where they are.
-        OPS_CHECK(o->ensure_up(16 * (size_t)n + 512));
-        memcpy(o->up.h.bytes(), gray, 8 * (size_t)n); memcpy(o->up.h.bytes() + 8 * (size_t)n + 256 - (8 * (size_t)n) % 256, dsrc, 8 * (size_t)n);
-        const size_t oD = 8 * (size_t)n + 256 - (8 * (size_t)n) % 256;
-        OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), o->up.h.bytes(), oD + 8 * (size_t)n, hipMemcpyHostToDevice, o->strm));
-        OPS_CHECK(oslam_frame_gather_images_device((const void* const*)o->up.d.bytes(), n, gray_stride, W, H, o->d_gray.bytes(), gimg, (int)o->gray_pitch, o->strm));
-        depth_table = (const void* const*)(o->up.d.bytes() + oD);   // the depth images are read where they are: only the values at the keypoints are needed
+        StageLayout L;
+        const auto fGray = L.add<const void*>(n), fDepth = L.add<const void*>(n);
+        OSLAM_CHECK(o->ensure_up(L.total()));
+        put(fGray, o->up.h.bytes(), (const void* const*)gray); put(fDepth, o->up.h.bytes(), dsrc);
+        OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), o->up.h.bytes(), fDepth.end(), hipMemcpyHostToDevice, o->strm));
+        OSLAM_CHECK(oslam_frame_gather_images_device(at(fGray, o->up.d.bytes()), n, gray_stride, W, H, o->d_gray.bytes(), gimg, (int)o->gray_pitch, o->strm));
+        depth_table = at(fDepth, o->up.d.bytes());   // the depth images are read where they are: only the values at the keypoints are needed
     } else {
         // host images: rows packed into the pinned block in the device layout (parallel), then ONE copy per plane (a pageable 2-D copy is row-by-row);
         // raw 16-bit depth is scaled here the way convertTo scales it (one float multiplication per pixel)
-        OPS_CHECK(o->ensure_up((gimg + dimg * 4) * n));
+        StageLayout L;
+        const auto fGray = L.add<uint8_t>(gimg * n); const auto fDepth = L.add<float>(dimg * n);
+        OSLAM_CHECK(o->ensure_up(L.total()));
         uint8_t* U = o->up.h.bytes();
         o->pool->parallel_for(n, [&](int i) {
             for (int r = 0; r < H; r++) {
-                memcpy(U + gimg * i + o->gray_pitch * r, gray[i] + (size_t)gray_stride * r, W);
-                float* drow = (float*)(U + gimg * n + (dimg * i + (size_t)W * r) * 4);
+                copy_elems(row(fGray, U, gimg, i) + o->gray_pitch * r, gray[i] + (size_t)gray_stride * r, (size_t)W);
+                float* drow = row(fDepth, U, dimg, i) + (size_t)W * r;
                 if (depth16) { const uint16_t* srow = depth16[i] + (size_t)depth_pitch * r; for (int x = 0; x < W; x++) drow[x] = (float)srow[x] * depth_factor; }
-                else memcpy(drow, depth[i] + (size_t)depth_pitch * r, (size_t)W * 4);
+                else copy_elems(drow, depth[i] + (size_t)depth_pitch * r, (size_t)W);
             }
         });
-        OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_gray.bytes(), U, gimg * n, hipMemcpyHostToDevice, o->strm));
-        OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_depth.as<float>(), U + gimg * n, dimg * 4 * n, hipMemcpyHostToDevice, o->strm));
+        OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_gray.bytes(), at(fGray, U), fGray.bytes, hipMemcpyHostToDevice, o->strm));
+        OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_depth.as<float>(), at(fDepth, U), fDepth.bytes, hipMemcpyHostToDevice, o->strm));
     }
     o->t_begin();
-    OPS_CHECK(oslam_orb_extract_batch_device(o->orb, o->d_gray.bytes(), n, (int)o->gray_pitch, gimg, o->strm));
+    OSLAM_CHECK(oslam_orb_extract_batch_device(o->orb, o->d_gray.bytes(), n, (int)o->gray_pitch, gimg, o->strm));
     const oslam_keypoint_t* d_kp; const uint8_t* d_desc; const int32_t* d_cnt; const int32_t* d_st;
-    OPS_CHECK(oslam_orb_results_device(o->orb, &d_kp, &d_desc, &d_cnt, &d_st));
-    OPS_CHECK(oslam_frame_undistort_batch_device(d_kp, o->d_keysUn.as<oslam_keypoint_t>(), d_cnt, 0, o->cap, n, o->K4, o->cfg.dist, o->cfg.ndist, o->strm));
-    if (depth_table && depth16) OPS_CHECK(oslam_frame_stereo_from_rgbd_batch_ptrs_u16_device(d_kp, o->d_keysUn.as<oslam_keypoint_t>(), d_cnt, 0, o->cap, n, (const uint16_t* const*)depth_table, H, W, depth_pitch,
+    OSLAM_CHECK(oslam_orb_results_device(o->orb, &d_kp, &d_desc, &d_cnt, &d_st));
+    OSLAM_CHECK(oslam_frame_undistort_batch_device(d_kp, o->d_keysUn.as<oslam_keypoint_t>(), d_cnt, 0, o->cap, n, o->K4, o->cfg.dist, o->cfg.ndist, o->strm));
+    if (depth_table && depth16) OSLAM_CHECK(oslam_frame_stereo_from_rgbd_batch_ptrs_u16_device(d_kp, o->d_keysUn.as<oslam_keypoint_t>(), d_cnt, 0, o->cap, n, (const uint16_t* const*)depth_table, H, W, depth_pitch,
                                                                                               depth_factor, o->cfg.bf, o->d_uRight.as<float>(), o->d_mvDepth.as<float>(), o->d_status.as<int32_t>(), o->strm));
-    else if (depth_table) OPS_CHECK(oslam_frame_stereo_from_rgbd_batch_ptrs_device(d_kp, o->d_keysUn.as<oslam_keypoint_t>(), d_cnt, 0, o->cap, n, (const float* const*)depth_table, H, W, depth_pitch, o->cfg.bf,
+    else if (depth_table) OSLAM_CHECK(oslam_frame_stereo_from_rgbd_batch_ptrs_device(d_kp, o->d_keysUn.as<oslam_keypoint_t>(), d_cnt, 0, o->cap, n, (const float* const*)depth_table, H, W, depth_pitch, o->cfg.bf,
                                                                                    o->d_uRight.as<float>(), o->d_mvDepth.as<float>(), o->d_status.as<int32_t>(), o->strm));
-    else OPS_CHECK(oslam_frame_stereo_from_rgbd_batch_device(d_kp, o->d_keysUn.as<oslam_keypoint_t>(), d_cnt, 0, o->cap, n, o->d_depth.as<float>(), H, W, W, dimg, o->cfg.bf, o->d_uRight.as<float>(),
+    else OSLAM_CHECK(oslam_frame_stereo_from_rgbd_batch_device(d_kp, o->d_keysUn.as<oslam_keypoint_t>(), d_cnt, 0, o->cap, n, o->d_depth.as<float>(), H, W, W, dimg, o->cfg.bf, o->d_uRight.as<float>(),
                                                              o->d_mvDepth.as<float>(), o->d_status.as<int32_t>(), o->strm));
     o->t_end();
-    OPS_CHECK(download_frames(o, n, d_kp, d_desc, d_cnt, d_st, o->d_uRight.as<float>(), o->d_mvDepth.as<float>(), out));
+    OSLAM_CHECK(download_frames(o, n, d_kp, d_desc, d_cnt, d_st, o->d_uRight.as<float>(), o->d_mvDepth.as<float>(), out));
     if (o->timing) { double bytes = 0; for (int i = 0; i < n; i++) bytes += (double)oslam_orb_algorithmic_bytes(o->orb, out[i]->N); o->t_collect(0, 14, bytes); }
     return OSLAM_OK;
 }
@@ -373,40 +368,43 @@ int h_frames_stereo(void* p, int n, const int32_t* slots, const uint8_t* const* 
     const int W = o->cfg.width, H = o->cfg.height;
     const size_t gimg = o->gray_pitch * H;
     if (on_device) {
-        OPS_CHECK(o->ensure_up(16 * (size_t)n + 512));
-        const size_t oD = 8 * (size_t)n + 256 - (8 * (size_t)n) % 256;
-        memcpy(o->up.h.bytes(), left, 8 * (size_t)n); memcpy(o->up.h.bytes() + oD, right, 8 * (size_t)n);
-        OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), o->up.h.bytes(), oD + 8 * (size_t)n, hipMemcpyHostToDevice, o->strm));
-        OPS_CHECK(oslam_frame_gather_images_device((const void* const*)o->up.d.bytes(), n, gray_stride, W, H, o->d_gray.bytes(), gimg, (int)o->gray_pitch, o->strm));
-        OPS_CHECK(oslam_frame_gather_images_device((const void* const*)(o->up.d.bytes() + oD), n, gray_stride, W, H, o->d_grayR.bytes(), gimg, (int)o->gray_pitch, o->strm));
+        StageLayout L;
+        const auto fLeft = L.add<const void*>(n), fRight = L.add<const void*>(n);
+        OSLAM_CHECK(o->ensure_up(L.total()));
+        put(fLeft, o->up.h.bytes(), (const void* const*)left); put(fRight, o->up.h.bytes(), (const void* const*)right);
+        OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), o->up.h.bytes(), fRight.end(), hipMemcpyHostToDevice, o->strm));
+        OSLAM_CHECK(oslam_frame_gather_images_device(at(fLeft, o->up.d.bytes()), n, gray_stride, W, H, o->d_gray.bytes(), gimg, (int)o->gray_pitch, o->strm));
+        OSLAM_CHECK(oslam_frame_gather_images_device(at(fRight, o->up.d.bytes()), n, gray_stride, W, H, o->d_grayR.bytes(), gimg, (int)o->gray_pitch, o->strm));
     } else {
-        OPS_CHECK(o->ensure_up(2 * gimg * n));
+        StageLayout L;
+        const auto fLeft = L.add<uint8_t>(gimg * n), fRight = L.add<uint8_t>(gimg * n);
+        OSLAM_CHECK(o->ensure_up(L.total()));
         uint8_t* U = o->up.h.bytes();
         o->pool->parallel_for(n, [&](int i) {
             for (int r = 0; r < H; r++) {
-                memcpy(U + gimg * i + o->gray_pitch * r, left[i] + (size_t)gray_stride * r, W);
-                memcpy(U + gimg * (n + i) + o->gray_pitch * r, right[i] + (size_t)gray_stride * r, W);
+                copy_elems(row(fLeft, U, gimg, i) + o->gray_pitch * r, left[i] + (size_t)gray_stride * r, (size_t)W);
+                copy_elems(row(fRight, U, gimg, i) + o->gray_pitch * r, right[i] + (size_t)gray_stride * r, (size_t)W);
             }
         });
-        OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_gray.bytes(), U, gimg * n, hipMemcpyHostToDevice, o->strm));
-        OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_grayR.bytes(), U + gimg * n, gimg * n, hipMemcpyHostToDevice, o->strm));
+        OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_gray.bytes(), at(fLeft, U), fLeft.bytes, hipMemcpyHostToDevice, o->strm));
+        OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_grayR.bytes(), at(fRight, U), fRight.bytes, hipMemcpyHostToDevice, o->strm));
     }
     o->t_begin();
-    OPS_CHECK(oslam_orb_extract_batch_device(o->orb, o->d_gray.bytes(), n, (int)o->gray_pitch, gimg, o->strm));
-    OPS_CHECK(oslam_orb_extract_batch_device(o->orbR, o->d_grayR.bytes(), n, (int)o->gray_pitch, gimg, o->strm));
+    OSLAM_CHECK(oslam_orb_extract_batch_device(o->orb, o->d_gray.bytes(), n, (int)o->gray_pitch, gimg, o->strm));
+    OSLAM_CHECK(oslam_orb_extract_batch_device(o->orbR, o->d_grayR.bytes(), n, (int)o->gray_pitch, gimg, o->strm));
     const oslam_keypoint_t* d_kp; const uint8_t* d_desc; const int32_t* d_cnt; const int32_t* d_st;
     const oslam_keypoint_t* d_kpR; const uint8_t* d_descR; const int32_t* d_cntR; const int32_t* d_stR;
-    OPS_CHECK(oslam_orb_results_device(o->orb, &d_kp, &d_desc, &d_cnt, &d_st));
-    OPS_CHECK(oslam_orb_results_device(o->orbR, &d_kpR, &d_descR, &d_cntR, &d_stR));
-    OPS_CHECK(oslam_frame_undistort_batch_device(d_kp, o->d_keysUn.as<oslam_keypoint_t>(), d_cnt, 0, o->cap, n, o->K4, o->cfg.dist, o->cfg.ndist, o->strm));
-    OPS_CHECK(oslam_stereo_match_batch_device(o->stereo, o->orb, o->orbR, n, o->cap, d_kp, d_desc, d_cnt, 0, d_kpR, d_descR, d_cntR, 0, o->cfg.nLevels, o->cfg.bf,
+    OSLAM_CHECK(oslam_orb_results_device(o->orb, &d_kp, &d_desc, &d_cnt, &d_st));
+    OSLAM_CHECK(oslam_orb_results_device(o->orbR, &d_kpR, &d_descR, &d_cntR, &d_stR));
+    OSLAM_CHECK(oslam_frame_undistort_batch_device(d_kp, o->d_keysUn.as<oslam_keypoint_t>(), d_cnt, 0, o->cap, n, o->K4, o->cfg.dist, o->cfg.ndist, o->strm));
+    OSLAM_CHECK(oslam_stereo_match_batch_device(o->stereo, o->orb, o->orbR, n, o->cap, d_kp, d_desc, d_cnt, 0, d_kpR, d_descR, d_cntR, 0, o->cfg.nLevels, o->cfg.bf,
                                               o->cfg.bf / o->cfg.fx, o->strm));
     const float* d_uR; const float* d_dp;
-    OPS_CHECK(oslam_stereo_results_device(o->stereo, &d_uR, &d_dp, nullptr));
+    OSLAM_CHECK(oslam_stereo_results_device(o->stereo, &d_uR, &d_dp, nullptr));
     o->t_end();
     OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_status.as<int32_t>(), d_stR, 4, hipMemcpyDeviceToDevice, o->strm));   // right extractor's overflow flag rides in the second status word
     (void)slots;
-    OPS_CHECK(download_frames(o, n, d_kp, d_desc, d_cnt, d_st, d_uR, d_dp, out));
+    OSLAM_CHECK(download_frames(o, n, d_kp, d_desc, d_cnt, d_st, d_uR, d_dp, out));
     if (o->timing) { double bytes = 0; for (int i = 0; i < n; i++) bytes += 2.0 * (double)oslam_orb_algorithmic_bytes(o->orb, out[i]->N); o->t_collect(0, 28, bytes); }
     return OSLAM_OK;
 }
@@ -430,52 +428,53 @@ int h_search_last(void* p, int n, oslam_job_search_last_t* jobs) {
     // by id: positions and descriptors of the last frame's map points come from the resident records, its keypoints from the previous step's buffer
     bool by_id = o->mp_tab_on;
     for (int i = 0; i < n && by_id; i++) by_id = jobs[i].mp_ids != nullptr;
-    if (by_id) OPS_CHECK(o->sync_mp_table());
+    if (by_id) OSLAM_CHECK(o->mp_tab.sync(o->strm));
     else for (int i = 0; i < n; i++) if (!jobs[i].Xw || !jobs[i].last_keysUn || !jobs[i].mp_desc) { oslam::set_error("search_last: job without arrays and without usable map-point ids"); return OSLAM_E_INVALID; }
-    Layout L;
-    const size_t oN = L.take(4 * S), oTc = L.take(64 * S), oTl = L.take(64 * S), oHas = L.take(cap * S), oIds = L.take(by_id ? 4 * cap * S : 0);
-    const size_t head = L.off;
-    const size_t oXw = L.take(12 * cap * S), oKeys = L.take(by_id ? 0 : sizeof(oslam_keypoint_t) * cap * S), oDesc = L.take(32 * cap * S);
-    OPS_CHECK(o->ensure_up(L.off));
+    StageLayout L;
+    const auto fN = L.add<int32_t>(S); const auto fTc = L.add<float>(16 * S), fTl = L.add<float>(16 * S); const auto fHas = L.add<uint8_t>(cap * S);
+    const auto fIds = L.add<int32_t>(cap * S, by_id);
+    const size_t head = L.total();   // by id nothing behind this travels: the device fills Xw and the descriptors itself
+    const auto fXw = L.add<float>(3 * cap * S); const auto fKeys = L.add<oslam_keypoint_t>(cap * S, !by_id); const auto fDesc = L.add<uint8_t>(32 * cap * S);
+    OSLAM_CHECK(o->ensure_up(L.total()));
     uint8_t* U = o->up.h.bytes();
-    memset(U + oN, 0, 4 * S);
+    memset(at(fN, U), 0, fN.bytes);
     o->pool->parallel_for(n, [&](int i) {
         const oslam_job_search_last_t& j = jobs[i];
         const size_t b = j.slot, N = j.Nlast;
-        ((int32_t*)(U + oN))[b] = j.Nlast;
-        memcpy(U + oTc + 64 * b, j.Tcw, 64); memcpy(U + oTl + 64 * b, j.Tlw, 64);
-        memcpy(U + oHas + cap * b, j.has_mp, N);
-        if (by_id) { memcpy(U + oIds + 4 * cap * b, j.mp_ids, 4 * N); return; }
-        memcpy(U + oXw + 12 * cap * b, j.Xw, 12 * N);
-        memcpy(U + oKeys + sizeof(oslam_keypoint_t) * cap * b, j.last_keysUn, sizeof(oslam_keypoint_t) * N);
-        memcpy(U + oDesc + 32 * cap * b, j.mp_desc, 32 * N);
+        at(fN, U)[b] = j.Nlast;
+        copy_elems(row(fTc, U, 16, b), j.Tcw, 16); copy_elems(row(fTl, U, 16, b), j.Tlw, 16);
+        copy_elems(row(fHas, U, cap, b), j.has_mp, N);
+        if (by_id) { copy_elems(row(fIds, U, cap, b), j.mp_ids, N); return; }
+        copy_elems(row(fXw, U, 3 * cap, b), j.Xw, 3 * N);
+        copy_elems(row(fKeys, U, cap, b), j.last_keysUn, N);
+        copy_elems(row(fDesc, U, 32 * cap, b), j.mp_desc, 32 * N);
     });
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), U, by_id ? head : L.off, hipMemcpyHostToDevice, o->strm));
     uint8_t* Dv = o->up.d.bytes();
-    if (by_id) OPS_CHECK(oslam_mp_table_gather_device((int)S, (int)cap, (const int32_t*)(Dv + oN), (const int32_t*)(Dv + oIds), o->d_mp_tab.as<uint8_t*>(), (float*)(Dv + oXw), Dv + oDesc, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, by_id ? head : L.total(), hipMemcpyHostToDevice, o->strm));
+    if (by_id) OSLAM_CHECK(oslam_mp_table_gather_device((int)S, (int)cap, at(fN, Dv), at(fIds, Dv), o->mp_tab.device_table(), at(fXw, Dv), at(fDesc, Dv), o->strm));
     oslam_match_frames_t fr;
     frames_view(o, fr, nullptr);
     oslam_match_last_t la;
-    la.Xw = (const float*)(Dv + oXw); la.has_mp = Dv + oHas; la.keys = by_id ? o->d_keysUn_prev.as<oslam_keypoint_t>() : (const oslam_keypoint_t*)(Dv + oKeys); la.mp_desc = Dv + oDesc;
-    la.kp_stride = (int)cap; la.n_kps = (const int32_t*)(Dv + oN); la.n_kps_const = 0;
+    la.Xw = at(fXw, Dv); la.has_mp = at(fHas, Dv); la.keys = by_id ? o->d_keysUn_prev.as<oslam_keypoint_t>() : at(fKeys, Dv); la.mp_desc = at(fDesc, Dv);
+    la.kp_stride = (int)cap; la.n_kps = at(fN, Dv); la.n_kps_const = 0;
     o->t_begin();
-    OPS_CHECK(oslam_match_project_last_batch_device(o->m_last, &la, (const float*)(Dv + oTc), (const float*)(Dv + oTl), &o->cam, &fr, o->scale, o->cfg.nLevels,
-                                                    jobs[0].th, 0, (int)S, o->strm));
+    OSLAM_CHECK(oslam_match_project_last_batch_device(o->m_last, &la, at(fTc, Dv), at(fTl, Dv), &o->cam, &fr, o->scale, o->cfg.nLevels, jobs[0].th, 0, (int)S, o->strm));
     const int32_t* d_km; const int32_t* d_nm; const int32_t* d_nq;
-    OPS_CHECK(oslam_match_results_device(o->m_last, nullptr, nullptr, &d_km, &d_nm, nullptr, &d_nq));
-    OPS_CHECK(oslam_match_search_batch_device(o->m_last, &fr, nullptr, (int)cap, d_nq, 0, (int)S, 0.9f, 0, 1, 100, o->strm));
+    OSLAM_CHECK(oslam_match_results_device(o->m_last, nullptr, nullptr, &d_km, &d_nm, nullptr, &d_nq));
+    OSLAM_CHECK(oslam_match_search_batch_device(o->m_last, &fr, nullptr, (int)cap, d_nq, 0, (int)S, 0.9f, 0, 1, 100, o->strm));
     o->t_end();
-    Layout R;
-    const size_t rKm = R.take(4 * cap * S), rNm = R.take(4 * S);
-    OPS_CHECK(o->ensure_dn(R.off));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rKm, d_km, 4 * cap * S, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rNm, d_nm, 4 * S, hipMemcpyDeviceToHost, o->strm));
+    StageLayout R;
+    const auto rKm = R.add<int32_t>(cap * S), rNm = R.add<int32_t>(S);
+    OSLAM_CHECK(o->ensure_dn(R.total()));
+    uint8_t* D = o->dn.bytes();
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rKm, D), d_km, rKm.bytes, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rNm, D), d_nm, rNm.bytes, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(3, 2, 0);
     o->pool->parallel_for(n, [&](int i) {
         oslam_job_search_last_t& j = jobs[i];
-        memcpy(j.kp_match, o->dn.bytes() + rKm + 4 * cap * j.slot, 4 * (size_t)j.cur->N);
-        j.nmatches = ((const int32_t*)(o->dn.bytes() + rNm))[j.slot];
+        copy_elems(j.kp_match, row(rKm, D, cap, j.slot), (size_t)j.cur->N);
+        j.nmatches = at(rNm, D)[j.slot];
     });
     return OSLAM_OK;
 }
@@ -499,9 +498,9 @@ int h_search_local(void* p, int n, oslam_job_search_local_t* jobs) {
         oslam_matcher_destroy(o->m_map);
         o->m_map = nullptr;
         o->max_local = (int)oslam::align_up((size_t)maxM + maxM / 2, 64);
-        OPS_CHECK(oslam_matcher_create(&o->m_map, o->S, o->cap, o->max_local, o->cfg.device));
+        OSLAM_CHECK(oslam_matcher_create(&o->m_map, o->S, o->cap, o->max_local, o->cfg.device));
     }
-    OPS_CHECK(o->ensure_loc());
+    OSLAM_CHECK(o->ensure_loc());
     const size_t st = oslam::align_up((size_t)std::max(maxM, 1), 64), lst = o->loc_st;
     const bool resident = getenv("OSLAM_SLAM_NO_RESIDENT_LOCAL") == nullptr;
     // jobs whose packed arrays are not the ones the slot holds: their arrays travel (packed back to back) and one launch scatters them into the slots
@@ -515,7 +514,7 @@ int h_search_local(void* p, int n, oslam_job_search_local_t* jobs) {
         fresh.push_back(i);
         by_id = by_id && j.local_ids != nullptr;
     }
-    if (by_id && !fresh.empty()) OPS_CHECK(o->sync_mp_table());
+    if (by_id && !fresh.empty()) OSLAM_CHECK(o->mp_tab.sync(o->strm));
     int freshMaxM = 0;
     for (int i : fresh) {
         const oslam_job_search_local_t& j = jobs[i];
@@ -524,80 +523,81 @@ int h_search_local(void* p, int n, oslam_job_search_local_t* jobs) {
         fbytes += by_id ? oslam::align_up(4 * (size_t)j.M, 16) + oslam::align_up((size_t)j.M, 64) : oslam::align_up(65 * (size_t)j.M + 6 * 16, 64);   // (six sub-arrays, each on a 16-byte boundary)
         freshMaxM = std::max(freshMaxM, j.M);
     }
-    Layout L;
-    const size_t oM = L.take(4 * S), oTc = L.take(64 * S), oTh = L.take(4 * S), oBl = L.take(cap * S), oSk = L.take(st * S),
-                 oSeg = L.take(by_id ? sizeof(oslam_local_gather_t) * fresh.size() : sizeof(CopySegH) * 6 * fresh.size());
-    const size_t small_bytes = L.off;
-    const size_t oF = L.take(fbytes);
-    OPS_CHECK(o->ensure_up(L.off));
-    OPS_CHECK(o->ensure_lq(st * S));
-    uint8_t* U = o->up.h.bytes();
-    uint8_t* Dv = o->up.d.bytes();
-    memset(U + oM, 0, 4 * S);
-    memset(U + oTh, 0, 4 * S);
+    StageLayout L;
+    const auto fM = L.add<int32_t>(S); const auto fTc = L.add<float>(16 * S), fTh = L.add<float>(S); const auto fBl = L.add<uint8_t>(cap * S), fSk = L.add<uint8_t>(st * S);
+    const auto fGat = L.add<oslam_local_gather_t>(fresh.size(), by_id);   // one of the two: the gather records of jobs that name their points,
+    const auto fSeg = L.add<CopySegH>(6 * fresh.size(), !by_id);          // or six copy segments per job that carries its arrays
+    const size_t small_bytes = L.total();   // without fresh jobs nothing behind this travels
+    const auto fF = L.add<uint8_t>(fbytes);
+    OSLAM_CHECK(o->ensure_up(L.total()));
+    OSLAM_CHECK(o->ensure_lq(st * S));
+    uint8_t *U = o->up.h.bytes(), *Dv = o->up.d.bytes();
+    memset(at(fM, U), 0, fM.bytes);
+    memset(at(fTh, U), 0, fTh.bytes);
     o->pool->parallel_for(n, [&](int i) {
         const oslam_job_search_local_t& j = jobs[i];
         const size_t b = j.slot, M = j.M;
-        ((int32_t*)(U + oM))[b] = j.M;
-        ((float*)(U + oTh))[b] = j.th;
-        memcpy(U + oTc + 64 * b, j.Tcw, 64);
-        memcpy(U + oBl + cap * b, j.blocked, (size_t)j.cur->N);
-        if (j.skip) memcpy(U + oSk + st * b, j.skip, M);
-        else memset(U + oSk + st * b, 0, M);
+        at(fM, U)[b] = j.M;
+        at(fTh, U)[b] = j.th;
+        copy_elems(row(fTc, U, 16, b), j.Tcw, 16);
+        copy_elems(row(fBl, U, cap, b), j.blocked, (size_t)j.cur->N);
+        if (j.skip) copy_elems(row(fSk, U, st, b), j.skip, M);
+        else memset(row(fSk, U, st, b), 0, M);
     });
     o->pool->parallel_for((int)fresh.size(), [&](int q) {
         const oslam_job_search_local_t& j = jobs[fresh[q]];
         const size_t b = j.slot, M = j.M;
-        uint8_t* at = U + oF + foff[q];
+        uint8_t* dst_h = at(fF, U) + foff[q];   // the job's share of the packed field: sub-arrays of several types, each on a 16-byte boundary
         if (by_id) {
-            const size_t ooff = oslam::align_up(4 * M, 16);
-            memcpy(at, j.local_ids, 4 * M); memcpy(at + ooff, j.obs_gt0, M);
-            ((oslam_local_gather_t*)(U + oSeg))[q] = {(int32_t)b, (int32_t)M, (uint32_t)foff[q], (uint32_t)(foff[q] + ooff)};
+            const size_t ooff = oslam::align_up(M * sizeof(*j.local_ids), 16);
+            memcpy(dst_h, j.local_ids, M * sizeof(*j.local_ids)); memcpy(dst_h + ooff, j.obs_gt0, M);
+            at(fGat, U)[q] = {(int32_t)b, (int32_t)M, (uint32_t)foff[q], (uint32_t)(foff[q] + ooff)};
             o->loc_id[b] = j.content_id;
             return;
         }
-        const uint8_t* dv = Dv + oF + foff[q];
-        CopySegH* sg = (CopySegH*)(U + oSeg) + 6 * (size_t)q;
+        const uint8_t* dv = at(fF, Dv) + foff[q];
+        CopySegH* sg = at(fSeg, U) + 6 * (size_t)q;
         const void* src[6] = {j.Pw, j.Pn, j.maxDist, j.minDist, j.obs_gt0, j.mp_desc};
-        const size_t bytes[6] = {12 * M, 12 * M, 4 * M, 4 * M, M, 32 * M};
+        const size_t bytes[6] = {3 * M * sizeof(*j.Pw), 3 * M * sizeof(*j.Pn), M * sizeof(*j.maxDist), M * sizeof(*j.minDist), M * sizeof(*j.obs_gt0), 32 * M * sizeof(*j.mp_desc)};
         uint8_t* dst[6] = {(uint8_t*)(o->loc_Pw() + 3 * lst * b), (uint8_t*)(o->loc_Pn() + 3 * lst * b), (uint8_t*)(o->loc_Max() + lst * b),
                            (uint8_t*)(o->loc_Min() + lst * b), o->loc_Obs() + lst * b, o->loc_Desc() + 32 * lst * b};
         size_t off = 0;
         for (int k = 0; k < 6; k++) {   // sources and destinations are 16-byte aligned: the copy kernel moves 16 bytes per lane
-            memcpy(at + off, src[k], bytes[k]);
+            memcpy(dst_h + off, src[k], bytes[k]);
             sg[k].src = dv + off; sg[k].dst = dst[k]; sg[k].bytes = (uint32_t)bytes[k]; sg[k].pad = 0;
             off += oslam::align_up(bytes[k], 16);
         }
         o->loc_id[b] = j.content_id;
     });
-    OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, fresh.empty() ? small_bytes : L.off, hipMemcpyHostToDevice, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, fresh.empty() ? small_bytes : L.total(), hipMemcpyHostToDevice, o->strm));
     o->t_begin();   // (the gather of repacked local maps counts with the searches it feeds)
     if (!fresh.empty() && by_id)
-        OPS_CHECK(oslam_mp_table_local_gather_device((int)fresh.size(), freshMaxM, (const oslam_local_gather_t*)(Dv + oSeg), Dv + oF, o->d_mp_tab.as<uint8_t*>(), (int)lst, o->loc_Pw(), o->loc_Pn(),
-                                                     o->loc_Max(), o->loc_Min(), o->loc_Obs(), o->loc_Desc(), o->strm));
-    else if (!fresh.empty()) OPS_CHECK(oslam_copy_segments_device(Dv + oSeg, 6 * (int)fresh.size(), o->strm));   // (a zero-byte segment's workgroup returns at once)
-    OPS_CHECK(oslam_frame_is_in_frustum_batch_resident_device((int)S, (int)lst, (int)st, (const int32_t*)(Dv + oM), o->loc_Pw(), o->loc_Pn(), o->loc_Max(), o->loc_Min(),
-                                                              o->loc_Obs(), o->loc_Desc(), Dv + oSk, (const float*)(Dv + oTc), (const float*)(Dv + oTh), o->K5,
-                                                              o->bounds, 0.5f, o->logScale, o->scale, o->cfg.nLevels, o->d_lq.as<oslam_proj_query_t>(), o->d_inview.bytes(), o->strm));
+        OSLAM_CHECK(oslam_mp_table_local_gather_device((int)fresh.size(), freshMaxM, at(fGat, Dv), at(fF, Dv), o->mp_tab.device_table(), (int)lst, o->loc_Pw(), o->loc_Pn(),
+                                                       o->loc_Max(), o->loc_Min(), o->loc_Obs(), o->loc_Desc(), o->strm));
+    else if (!fresh.empty()) OSLAM_CHECK(oslam_copy_segments_device(at(fSeg, Dv), 6 * (int)fresh.size(), o->strm));   // (a zero-byte segment's workgroup returns at once)
+    OSLAM_CHECK(oslam_frame_is_in_frustum_batch_resident_device((int)S, (int)lst, (int)st, at(fM, Dv), o->loc_Pw(), o->loc_Pn(), o->loc_Max(), o->loc_Min(), o->loc_Obs(), o->loc_Desc(),
+                                                                at(fSk, Dv), at(fTc, Dv), at(fTh, Dv), o->K5, o->bounds, 0.5f, o->logScale, o->scale, o->cfg.nLevels,
+                                                                o->d_lq.as<oslam_proj_query_t>(), o->d_inview.bytes(), o->strm));
     oslam_match_frames_t fr;
-    frames_view(o, fr, Dv + oBl);
-    OPS_CHECK(oslam_match_search_batch_device(o->m_map, &fr, o->d_lq.as<oslam_proj_query_t>(), (int)st, (const int32_t*)(Dv + oM), 0, (int)S, 0.8f, 1, 0, 100, o->strm));
+    frames_view(o, fr, at(fBl, Dv));
+    OSLAM_CHECK(oslam_match_search_batch_device(o->m_map, &fr, o->d_lq.as<oslam_proj_query_t>(), (int)st, at(fM, Dv), 0, (int)S, 0.8f, 1, 0, 100, o->strm));
     o->t_end();
     const int32_t* d_km; const int32_t* d_nm;
-    OPS_CHECK(oslam_match_results_device(o->m_map, nullptr, nullptr, &d_km, &d_nm, nullptr, nullptr));
-    Layout R;
-    const size_t rKm = R.take(4 * cap * S), rNm = R.take(4 * S), rIn = R.take(st * S);
-    OPS_CHECK(o->ensure_dn(R.off));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rKm, d_km, 4 * cap * S, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rNm, d_nm, 4 * S, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rIn, o->d_inview.bytes(), st * S, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_CHECK(oslam_match_results_device(o->m_map, nullptr, nullptr, &d_km, &d_nm, nullptr, nullptr));
+    StageLayout R;
+    const auto rKm = R.add<int32_t>(cap * S), rNm = R.add<int32_t>(S); const auto rIn = R.add<uint8_t>(st * S);
+    OSLAM_CHECK(o->ensure_dn(R.total()));
+    uint8_t* D = o->dn.bytes();
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rKm, D), d_km, rKm.bytes, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rNm, D), d_nm, rNm.bytes, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rIn, D), o->d_inview.bytes(), rIn.bytes, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(3, 2, 0);
     o->pool->parallel_for(n, [&](int i) {
         oslam_job_search_local_t& j = jobs[i];
-        memcpy(j.kp_match, o->dn.bytes() + rKm + 4 * cap * j.slot, 4 * (size_t)j.cur->N);
-        memcpy(j.in_view, o->dn.bytes() + rIn + st * j.slot, (size_t)j.M);
-        j.nmatches = ((const int32_t*)(o->dn.bytes() + rNm))[j.slot];
+        copy_elems(j.kp_match, row(rKm, D, cap, j.slot), (size_t)j.cur->N);
+        copy_elems(j.in_view, row(rIn, D, st, j.slot), (size_t)j.M);
+        j.nmatches = at(rNm, D)[j.slot];
     });
     return OSLAM_OK;
 }
@@ -613,45 +613,45 @@ int h_pose_opt(void* p, int n, oslam_job_pose_t* jobs) {
     // by id: the positions come from the resident map-point records, obs / invSigma2 from the frames of this step that are still on the device
     bool by_id = o->mp_tab_on;
     for (int i = 0; i < n && by_id; i++) by_id = jobs[i].mp_ids != nullptr && jobs[i].slot >= 0 && jobs[i].slot < o->S;
-    if (by_id) OPS_CHECK(o->sync_mp_table());
+    if (by_id) OSLAM_CHECK(o->mp_tab.sync(o->strm));
     else for (int i = 0; i < n; i++) if (!jobs[i].Xw || !jobs[i].obs || !jobs[i].invSigma2 || !jobs[i].has_mp) { oslam::set_error("pose_opt: job without arrays and without usable map-point ids"); return OSLAM_E_INVALID; }
-    Layout L;
-    const size_t oN = L.take(4 * B), oT = L.take(64 * B), oSl = L.take(by_id ? 4 * B : 0), oIds = L.take(by_id ? 4 * cap * B : 0);
-    const size_t head = L.off;
-    const size_t oXw = L.take(12 * cap * B), oObs = L.take(12 * cap * B), oInv = L.take(4 * cap * B), oHas = L.take(cap * B);
-    OPS_CHECK(o->ensure_up(L.off));
+    StageLayout L;
+    const auto fN = L.add<int32_t>(B); const auto fT = L.add<float>(16 * B); const auto fSl = L.add<int32_t>(B, by_id), fIds = L.add<int32_t>(cap * B, by_id);
+    const size_t head = L.total();   // by id nothing behind this travels: the device fills the four arrays itself
+    const auto fXw = L.add<float>(3 * cap * B), fObs = L.add<float>(3 * cap * B), fInv = L.add<float>(cap * B); const auto fHas = L.add<uint8_t>(cap * B);
+    OSLAM_CHECK(o->ensure_up(L.total()));
     uint8_t* U = o->up.h.bytes();
     o->pool->parallel_for(n, [&](int i) {
         const oslam_job_pose_t& j = jobs[i];
         const size_t N = j.N;
-        ((int32_t*)(U + oN))[i] = j.N;
-        memcpy(U + oT + 64 * i, j.Tcw_in, 64);
-        if (by_id) { ((int32_t*)(U + oSl))[i] = j.slot; memcpy(U + oIds + 4 * cap * i, j.mp_ids, 4 * N); return; }
-        memcpy(U + oXw + 12 * cap * i, j.Xw, 12 * N); memcpy(U + oObs + 12 * cap * i, j.obs, 12 * N);
-        memcpy(U + oInv + 4 * cap * i, j.invSigma2, 4 * N); memcpy(U + oHas + cap * i, j.has_mp, N);
+        at(fN, U)[i] = j.N;
+        copy_elems(row(fT, U, 16, i), j.Tcw_in, 16);
+        if (by_id) { at(fSl, U)[i] = j.slot; copy_elems(row(fIds, U, cap, i), j.mp_ids, N); return; }
+        copy_elems(row(fXw, U, 3 * cap, i), j.Xw, 3 * N); copy_elems(row(fObs, U, 3 * cap, i), j.obs, 3 * N);
+        copy_elems(row(fInv, U, cap, i), j.invSigma2, N); copy_elems(row(fHas, U, cap, i), j.has_mp, N);
     });
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), U, by_id ? head : L.off, hipMemcpyHostToDevice, o->strm));
     uint8_t* Dv = o->up.d.bytes();
+    OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, by_id ? head : L.total(), hipMemcpyHostToDevice, o->strm));
     if (by_id)
-        OPS_CHECK(oslam_pose_inputs_gather_device(n, (int)cap, (const int32_t*)(Dv + oSl), (const int32_t*)(Dv + oN), (const int32_t*)(Dv + oIds), o->d_mp_tab.as<uint8_t*>(), o->d_keysUn.as<oslam_keypoint_t>(),
-                                                  o->cur_uRight, (int)cap, o->invSigma2, o->cfg.nLevels, (float*)(Dv + oXw), (float*)(Dv + oObs), (float*)(Dv + oInv), Dv + oHas, o->strm));
+        OSLAM_CHECK(oslam_pose_inputs_gather_device(n, (int)cap, at(fSl, Dv), at(fN, Dv), at(fIds, Dv), o->mp_tab.device_table(), o->d_keysUn.as<oslam_keypoint_t>(), o->cur_uRight, (int)cap,
+                                                    o->invSigma2, o->cfg.nLevels, at(fXw, Dv), at(fObs, Dv), at(fInv, Dv), at(fHas, Dv), o->strm));
     o->t_begin();
-    OPS_CHECK(oslam_pose_optimize_batch_device(o->po, n, (int)cap, (const int32_t*)(Dv + oN), 0, (const float*)(Dv + oT), (const float*)(Dv + oXw),
-                                               (const float*)(Dv + oObs), (const float*)(Dv + oInv), Dv + oHas, o->K5, o->strm));
+    OSLAM_CHECK(oslam_pose_optimize_batch_device(o->po, n, (int)cap, at(fN, Dv), 0, at(fT, Dv), at(fXw, Dv), at(fObs, Dv), at(fInv, Dv), at(fHas, Dv), o->K5, o->strm));
     o->t_end();
     const float* d_T; const uint8_t* d_out; const int32_t* d_ni; const int32_t* d_stats;
-    OPS_CHECK(oslam_poseopt_results_device(o->po, &d_T, &d_out, &d_ni, &d_stats));
-    Layout R;
-    const size_t rT = R.take(64 * B), rO = R.take(cap * B), rN = R.take(4 * B), rS = R.take(8 * B);
-    OPS_CHECK(o->ensure_dn(R.off));
-    if (o->timing) OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rS, d_stats, 8 * B, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rT, d_T, 64 * B, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rO, d_out, cap * B, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rN, d_ni, 4 * B, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_CHECK(oslam_poseopt_results_device(o->po, &d_T, &d_out, &d_ni, &d_stats));
+    StageLayout R;
+    const auto rT = R.add<float>(16 * B); const auto rO = R.add<uint8_t>(cap * B); const auto rN = R.add<int32_t>(B), rS = R.add<int32_t>(2 * B);
+    OSLAM_CHECK(o->ensure_dn(R.total()));
+    uint8_t* D = o->dn.bytes();
+    if (o->timing) OSLAM_HIP_CHECK(hipMemcpyAsync(at(rS, D), d_stats, rS.bytes, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rT, D), d_T, rT.bytes, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rO, D), d_out, rO.bytes, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rN, D), d_ni, rN.bytes, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     if (o->timing) {   // 700 flop per edge and linearisation, 90 per edge and trial evaluation
         double flop = 0;
-        const int32_t* stt = (const int32_t*)(o->dn.bytes() + rS);
+        const int32_t* stt = at(rS, D);
         for (int i = 0; i < n; i++) {
             int ne = 0;
             for (int k = 0; k < jobs[i].N; k++) ne += by_id ? jobs[i].mp_ids[k] >= 0 : jobs[i].has_mp[k] != 0;
@@ -661,9 +661,9 @@ int h_pose_opt(void* p, int n, oslam_job_pose_t* jobs) {
     }
     o->pool->parallel_for(n, [&](int i) {
         oslam_job_pose_t& j = jobs[i];
-        memcpy(j.Tcw_out, o->dn.bytes() + rT + 64 * i, 64);
-        memcpy(j.outlier, o->dn.bytes() + rO + cap * i, (size_t)j.N);
-        j.n_inliers = ((const int32_t*)(o->dn.bytes() + rN))[i];
+        copy_elems(j.Tcw_out, row(rT, D, 16, i), 16);
+        copy_elems(j.outlier, row(rO, D, cap, i), (size_t)j.N);
+        j.n_inliers = at(rN, D)[i];
     });
     return OSLAM_OK;
 }
@@ -674,7 +674,7 @@ static int stage_masks(HipOps* o, int total, const std::vector<const uint8_t*>& 
     ptrs.resize(total);
     if (on_device) { for (int m = 0; m < total; m++) ptrs[m] = src[m]; pitch = mask_stride; return OSLAM_OK; }
     pitch = (int)W;
-    OPS_CHECK(o->ensure_masks(W * H * (size_t)total));
+    OSLAM_CHECK(o->ensure_masks(W * H * (size_t)total));
     for (int m = 0; m < total; m++) {
         OSLAM_HIP_CHECK(hipMemcpy2DAsync(o->d_maskstage.bytes() + W * H * m, W, src[m], mask_stride, W, H, hipMemcpyHostToDevice, o->strm));
         ptrs[m] = o->d_maskstage.bytes() + W * H * m;
@@ -704,40 +704,43 @@ int h_object_kps(void* p, int n, oslam_job_object_kps_t* jobs) {
     int pitch = 0;
     const bool caller_bits = jobs[0].mask_stride == 0;   // one-bit-per-pixel images packed by the caller (oslam_slam_track_rgbd_raw16), device-accessible
     if (caller_bits && !jobs[0].on_device) { oslam::set_error("object_kps: one-bit masks must be device-accessible"); return OSLAM_E_INVALID; }
-    if (!caller_bits) OPS_CHECK(stage_masks(o, total, src, jobs[0].mask_stride, jobs[0].on_device, ptrs, pitch));
-    Layout L;
-    const size_t oPtr = L.take(8 * (size_t)total), oM0 = L.take(4 * S), oNm = L.take(4 * S), oSeg = L.take(caller_bits ? sizeof(CopySegH) * (size_t)total : 0);
-    OPS_CHECK(o->ensure_up(L.off));
+    if (!caller_bits) OSLAM_CHECK(stage_masks(o, total, src, jobs[0].mask_stride, jobs[0].on_device, ptrs, pitch));
+    StageLayout L;
+    const auto fPtr = L.add<const uint8_t*>(total); const auto fM0 = L.add<int32_t>(S), fNm = L.add<int32_t>(S); const auto fSeg = L.add<CopySegH>(total, caller_bits);
+    OSLAM_CHECK(o->ensure_up(L.total()));
     uint8_t* U = o->up.h.bytes();
     const size_t bits_bytes = (size_t)o->cfg.height * ((o->cfg.width + 63) / 64) * 8;
     if (caller_bits) {
-        OPS_CHECK(o->ensure_maskbits((size_t)total * o->cfg.height * ((o->cfg.width + 63) / 64)));
-        CopySegH* sg = (CopySegH*)(U + oSeg);
+        OSLAM_CHECK(o->ensure_maskbits((size_t)total * o->cfg.height * ((o->cfg.width + 63) / 64)));
+        CopySegH* sg = at(fSeg, U);
         for (int m = 0; m < total; m++) { sg[m].src = src[m]; sg[m].dst = o->d_maskbits.bytes() + bits_bytes * m; sg[m].bytes = (uint32_t)bits_bytes; sg[m].pad = 0; }
-    } else memcpy(U + oPtr, ptrs.data(), 8 * (size_t)total);
-    memcpy(U + oM0, mask0.data(), 4 * S); memcpy(U + oNm, nmask.data(), 4 * S);
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), U, L.off, hipMemcpyHostToDevice, o->strm));
+    } else put(fPtr, U, ptrs.data());
+    put(fM0, U, mask0.data()); put(fNm, U, nmask.data());
     uint8_t* Dv = o->up.d.bytes();
+    OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, L.total(), hipMemcpyHostToDevice, o->strm));
     o->t_begin();
     if (caller_bits || !getenv("OSLAM_SLAM_NO_MASK_BITS")) {   // one pass over the mask bytes; the test (and pose_opt2's boundary lists later in this step) read bitmaps
         const int H = o->cfg.height, W = o->cfg.width;
-        OPS_CHECK(o->ensure_maskbits((size_t)total * H * ((W + 63) / 64)));
-        if (caller_bits) OPS_CHECK(oslam_copy_segments_device(Dv + oSeg, total, o->strm));   // the caller's bitmaps (pinned host memory: read over PCIe) into the step's bitmap array
-        else OPS_CHECK(oslam_mask_bits_device((const uint8_t* const*)(Dv + oPtr), total, H, W, pitch, o->d_maskbits.as<uint64_t>(), o->strm));
-        OPS_CHECK(oslam_frame_object_kp_test_bits_batch_device(o->d_keysUn.as<oslam_keypoint_t>(), (int)cap, o->d_cnt, (int)S, o->d_maskbits.as<uint64_t>(), (const int32_t*)(Dv + oM0), (const int32_t*)(Dv + oNm), H, W,
-                                                               o->d_objbits.bytes(), o->strm));
+        OSLAM_CHECK(o->ensure_maskbits((size_t)total * H * ((W + 63) / 64)));
+        if (caller_bits) OSLAM_CHECK(oslam_copy_segments_device(at(fSeg, Dv), total, o->strm));   // the caller's bitmaps (pinned host memory: read over PCIe) into the step's bitmap array
+        else OSLAM_CHECK(oslam_mask_bits_device(at(fPtr, Dv), total, H, W, pitch, o->d_maskbits.as<uint64_t>(), o->strm));
+        OSLAM_CHECK(oslam_frame_object_kp_test_bits_batch_device(o->d_keysUn.as<oslam_keypoint_t>(), (int)cap, o->d_cnt, (int)S, o->d_maskbits.as<uint64_t>(), at(fM0, Dv), at(fNm, Dv), H, W,
+                                                                 o->d_objbits.bytes(), o->strm));
         o->bits_of_ptr.clear();
         for (int m = 0; m < total; m++) o->bits_of_ptr[src[m]] = m;
         o->bits_epoch = o->step_epoch;
     } else
-    OPS_CHECK(oslam_frame_object_kp_test_batch_device(o->d_keysUn.as<oslam_keypoint_t>(), (int)cap, o->d_cnt, (int)S, (const uint8_t* const*)(Dv + oPtr), (const int32_t*)(Dv + oM0),
-                                                      (const int32_t*)(Dv + oNm), o->cfg.height, o->cfg.width, pitch, o->d_objbits.bytes(), o->strm));
+    OSLAM_CHECK(oslam_frame_object_kp_test_batch_device(o->d_keysUn.as<oslam_keypoint_t>(), (int)cap, o->d_cnt, (int)S, at(fPtr, Dv), at(fM0, Dv), at(fNm, Dv), o->cfg.height, o->cfg.width, pitch,
+                                                        o->d_objbits.bytes(), o->strm));
     o->t_end();
-    OPS_CHECK(o->ensure_dn(cap * S));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes(), o->d_objbits.bytes(), cap * S, hipMemcpyDeviceToHost, o->strm));
+    StageLayout R;
+    const auto rIn = R.add<uint8_t>(cap * S);
+    OSLAM_CHECK(o->ensure_dn(R.total()));
+    uint8_t* D = o->dn.bytes();
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rIn, D), o->d_objbits.bytes(), rIn.bytes, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(7, 2, 0);
-    for (int i = 0; i < n; i++) memcpy(jobs[i].in_mask, o->dn.bytes() + cap * jobs[i].slot, (size_t)jobs[i].cur->N);
+    for (int i = 0; i < n; i++) copy_elems(jobs[i].in_mask, row(rIn, D, cap, jobs[i].slot), (size_t)jobs[i].cur->N);
     return OSLAM_OK;
 }
 
@@ -771,75 +774,75 @@ int h_pose_opt2(void* p, int n, oslam_job_pose2_t* jobs) {
         else bidx[m] = it->second;
     }
     if (tObj && !use_bits && jobs[0].mask_stride == 0) { oslam::set_error("pose_opt2: one-bit masks without the step's bitmaps (object_kps must run first)"); return OSLAM_E_INVALID; }
-    if (tObj && !use_bits) OPS_CHECK(stage_masks(o, tObj, src, jobs[0].mask_stride, jobs[0].on_device, ptrs, pitch));
+    if (tObj && !use_bits) OSLAM_CHECK(stage_masks(o, tObj, src, jobs[0].mask_stride, jobs[0].on_device, ptrs, pitch));
     bool by_id = o->mp_tab_on;
     for (int i = 0; i < n && by_id; i++) by_id = jobs[i].base.mp_ids != nullptr && jobs[i].base.slot >= 0 && jobs[i].base.slot < o->S && (jobs[i].nObjMp == 0 || jobs[i].objmp_ids != nullptr);
-    if (by_id) OPS_CHECK(o->sync_mp_table());
+    if (by_id) OSLAM_CHECK(o->mp_tab.sync(o->strm));
     else for (int i = 0; i < n; i++) if ((jobs[i].nObjMp > 0 && !jobs[i].objmp_Xw) || !jobs[i].base.Xw || !jobs[i].base.obs || !jobs[i].base.invSigma2 || !jobs[i].base.has_mp) { oslam::set_error("pose_opt2: job without arrays and without usable map-point ids"); return OSLAM_E_INVALID; }
-    Layout L;
+    StageLayout L;
     // (the arrays the device builds itself when the frames are served by id sit behind everything that is uploaded)
-    const size_t oN = L.take(4 * B), oT = L.take(64 * B), oSl = L.take(by_id ? 4 * B : 0), oIds = L.take(by_id ? 4 * cap * B : 0),
-                 oFr = L.take(sizeof(oslam_sem_frame_t) * B), oPtr = L.take(8 * (size_t)tObj), oMx = L.take(by_id ? 0 : 12 * (size_t)tMp), oMo = L.take(4 * (size_t)tMp),
-                 oJk = L.take(4 * (size_t)tJ), oJo = L.take(4 * (size_t)tJ), oBi = L.take(4 * (size_t)tObj), oMi = L.take(by_id ? 4 * (size_t)tMp : 0),
-                 oMs = L.take(by_id ? 4 * (size_t)tMp : 0);
-    const size_t head = L.off;
-    const size_t oMxDev = by_id ? L.take(12 * (size_t)tMp) : oMx;   // object map-point positions: uploaded, or gathered from the records
-    const size_t oXw = L.take(12 * cap * B), oObs = L.take(12 * cap * B), oInv = L.take(4 * cap * B), oHas = L.take(cap * B);
-    OPS_CHECK(o->ensure_up(L.off));
+    const auto fN = L.add<int32_t>(B); const auto fT = L.add<float>(16 * B); const auto fSl = L.add<int32_t>(B, by_id), fIds = L.add<int32_t>(cap * B, by_id);
+    const auto fFr = L.add<oslam_sem_frame_t>(B); const auto fPtr = L.add<const uint8_t*>(tObj); const auto fMx = L.add<float>(3 * (size_t)tMp, !by_id);
+    const auto fMo = L.add<int32_t>(tMp), fJk = L.add<int32_t>(tJ), fJo = L.add<int32_t>(tJ), fBi = L.add<int32_t>(tObj);
+    const auto fMi = L.add<int32_t>(tMp, by_id), fMs = L.add<int32_t>(tMp, by_id);
+    const size_t head = L.total();   // by id nothing behind this travels
+    const auto fMxDev = by_id ? L.add<float>(3 * (size_t)tMp) : fMx;   // object map-point positions: uploaded, or gathered from the records
+    const auto fXw = L.add<float>(3 * cap * B), fObs = L.add<float>(3 * cap * B), fInv = L.add<float>(cap * B); const auto fHas = L.add<uint8_t>(cap * B);
+    OSLAM_CHECK(o->ensure_up(L.total()));
     uint8_t* U = o->up.h.bytes();
-    memcpy(U + oFr, fr.data(), sizeof(oslam_sem_frame_t) * B);
-    if (use_bits) memcpy(U + oBi, bidx.data(), 4 * (size_t)tObj);
-    if (tObj && !use_bits) memcpy(U + oPtr, ptrs.data(), 8 * (size_t)tObj);
+    put(fFr, U, fr.data());
+    if (use_bits) put(fBi, U, bidx.data());
+    if (tObj && !use_bits) put(fPtr, U, ptrs.data());
     o->pool->parallel_for(n, [&](int i) {
         const oslam_job_pose2_t& j2 = jobs[i];
         const oslam_job_pose_t& j = j2.base;
-        const size_t N = j.N;
-        ((int32_t*)(U + oN))[i] = j.N;
-        memcpy(U + oT + 64 * i, j.Tcw_in, 64);
-        if (by_id) { ((int32_t*)(U + oSl))[i] = j.slot; memcpy(U + oIds + 4 * cap * i, j.mp_ids, 4 * N); }
+        const size_t N = j.N, m0 = fr[i].objmp0, j0 = fr[i].joint0;
+        at(fN, U)[i] = j.N;
+        copy_elems(row(fT, U, 16, i), j.Tcw_in, 16);
+        if (by_id) { at(fSl, U)[i] = j.slot; copy_elems(row(fIds, U, cap, i), j.mp_ids, N); }
         else {
-            memcpy(U + oXw + 12 * cap * i, j.Xw, 12 * N); memcpy(U + oObs + 12 * cap * i, j.obs, 12 * N);
-            memcpy(U + oInv + 4 * cap * i, j.invSigma2, 4 * N); memcpy(U + oHas + cap * i, j.has_mp, N);
+            copy_elems(row(fXw, U, 3 * cap, i), j.Xw, 3 * N); copy_elems(row(fObs, U, 3 * cap, i), j.obs, 3 * N);
+            copy_elems(row(fInv, U, cap, i), j.invSigma2, N); copy_elems(row(fHas, U, cap, i), j.has_mp, N);
         }
         if (j2.nObjMp) {
-            memcpy(U + oMo + 4 * (size_t)fr[i].objmp0, j2.objmp_obj, 4 * (size_t)j2.nObjMp);
+            copy_elems(at(fMo, U) + m0, j2.objmp_obj, (size_t)j2.nObjMp);
             if (by_id) {
-                memcpy(U + oMi + 4 * (size_t)fr[i].objmp0, j2.objmp_ids, 4 * (size_t)j2.nObjMp);
-                int32_t* sl = (int32_t*)(U + oMs) + fr[i].objmp0;
+                copy_elems(at(fMi, U) + m0, j2.objmp_ids, (size_t)j2.nObjMp);
+                int32_t* sl = at(fMs, U) + m0;
                 for (int q = 0; q < j2.nObjMp; q++) sl[q] = j.slot;
-            } else memcpy(U + oMx + 12 * (size_t)fr[i].objmp0, j2.objmp_Xw, 12 * (size_t)j2.nObjMp);
+            } else copy_elems(at(fMx, U) + 3 * m0, j2.objmp_Xw, 3 * (size_t)j2.nObjMp);
         }
-        if (j2.nJoint) { memcpy(U + oJk + 4 * (size_t)fr[i].joint0, j2.joint_kp, 4 * (size_t)j2.nJoint); memcpy(U + oJo + 4 * (size_t)fr[i].joint0, j2.joint_obj, 4 * (size_t)j2.nJoint); }
+        if (j2.nJoint) { copy_elems(at(fJk, U) + j0, j2.joint_kp, (size_t)j2.nJoint); copy_elems(at(fJo, U) + j0, j2.joint_obj, (size_t)j2.nJoint); }
     });
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), U, by_id ? head : L.off, hipMemcpyHostToDevice, o->strm));
     uint8_t* Dv = o->up.d.bytes();
+    OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, by_id ? head : L.total(), hipMemcpyHostToDevice, o->strm));
     if (by_id) {
-        OPS_CHECK(oslam_pose_inputs_gather_device(n, (int)cap, (const int32_t*)(Dv + oSl), (const int32_t*)(Dv + oN), (const int32_t*)(Dv + oIds), o->d_mp_tab.as<uint8_t*>(), o->d_keysUn.as<oslam_keypoint_t>(),
-                                                  o->cur_uRight, (int)cap, o->invSigma2, o->cfg.nLevels, (float*)(Dv + oXw), (float*)(Dv + oObs), (float*)(Dv + oInv), Dv + oHas, o->strm));
-        OPS_CHECK(oslam_mp_table_positions_device(tMp, (const int32_t*)(Dv + oMs), (const int32_t*)(Dv + oMi), o->d_mp_tab.as<uint8_t*>(), (float*)(Dv + oMxDev), o->strm));
+        OSLAM_CHECK(oslam_pose_inputs_gather_device(n, (int)cap, at(fSl, Dv), at(fN, Dv), at(fIds, Dv), o->mp_tab.device_table(), o->d_keysUn.as<oslam_keypoint_t>(), o->cur_uRight, (int)cap,
+                                                    o->invSigma2, o->cfg.nLevels, at(fXw, Dv), at(fObs, Dv), at(fInv, Dv), at(fHas, Dv), o->strm));
+        OSLAM_CHECK(oslam_mp_table_positions_device(tMp, at(fMs, Dv), at(fMi, Dv), o->mp_tab.device_table(), at(fMxDev, Dv), o->strm));
     }
     o->t_begin();
-    if (use_bits) OPS_CHECK(oslam_poseopt_use_mask_bits(o->po, o->d_maskbits.as<uint64_t>(), (const int32_t*)(Dv + oBi)));
-    OPS_CHECK(oslam_pose_optimize2_batch_device(o->po, n, (int)cap, (const int32_t*)(Dv + oN), (const float*)(Dv + oT), (const float*)(Dv + oXw), (const float*)(Dv + oObs),
-                                                (const float*)(Dv + oInv), Dv + oHas, o->K5, (const oslam_sem_frame_t*)(Dv + oFr), tObj, use_bits ? nullptr : (const uint8_t* const*)(Dv + oPtr),
-                                                o->cfg.height, o->cfg.width, pitch, tMp, (const float*)(Dv + oMxDev), (const int32_t*)(Dv + oMo), tJ, (const int32_t*)(Dv + oJk),
-                                                (const int32_t*)(Dv + oJo), o->bounds, o->invSigma2[0], o->strm));
+    if (use_bits) OSLAM_CHECK(oslam_poseopt_use_mask_bits(o->po, o->d_maskbits.as<uint64_t>(), at(fBi, Dv)));
+    OSLAM_CHECK(oslam_pose_optimize2_batch_device(o->po, n, (int)cap, at(fN, Dv), at(fT, Dv), at(fXw, Dv), at(fObs, Dv), at(fInv, Dv), at(fHas, Dv), o->K5, at(fFr, Dv), tObj,
+                                                  use_bits ? nullptr : at(fPtr, Dv), o->cfg.height, o->cfg.width, pitch, tMp, at(fMxDev, Dv), at(fMo, Dv), tJ, at(fJk, Dv), at(fJo, Dv), o->bounds,
+                                                  o->invSigma2[0], o->strm));
     o->t_end();
     const float* d_T; const uint8_t* d_out; const int32_t* d_ni; const int32_t* d_stats; const int32_t* d_ns;
-    OPS_CHECK(oslam_poseopt_results_device(o->po, &d_T, &d_out, &d_ni, &d_stats));
-    OPS_CHECK(oslam_poseopt_semantic_results_device(o->po, &d_ns));
-    Layout R;
-    const size_t rT = R.take(64 * B), rO = R.take(cap * B), rN = R.take(4 * B), rS = R.take(8 * B), rNs = R.take(4 * B);
-    OPS_CHECK(o->ensure_dn(R.off));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rT, d_T, 64 * B, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rO, d_out, cap * B, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rN, d_ni, 4 * B, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rS, d_stats, 8 * B, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes() + rNs, d_ns, 4 * B, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_CHECK(oslam_poseopt_results_device(o->po, &d_T, &d_out, &d_ni, &d_stats));
+    OSLAM_CHECK(oslam_poseopt_semantic_results_device(o->po, &d_ns));
+    StageLayout R;
+    const auto rT = R.add<float>(16 * B); const auto rO = R.add<uint8_t>(cap * B); const auto rN = R.add<int32_t>(B), rS = R.add<int32_t>(2 * B), rNs = R.add<int32_t>(B);
+    OSLAM_CHECK(o->ensure_dn(R.total()));
+    uint8_t* D = o->dn.bytes();
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rT, D), d_T, rT.bytes, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rO, D), d_out, rO.bytes, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rN, D), d_ni, rN.bytes, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rS, D), d_stats, rS.bytes, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rNs, D), d_ns, rNs.bytes, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     if (o->timing) {
         double flop = 0;
-        const int32_t* stt = (const int32_t*)(o->dn.bytes() + rS);
+        const int32_t* stt = at(rS, D);
         for (int i = 0; i < n; i++) {
             int ne = jobs[i].nObjMp + jobs[i].nJoint;   // upper bound of the semantic edges
             for (int k = 0; k < jobs[i].base.N; k++) ne += by_id ? jobs[i].base.mp_ids[k] >= 0 : jobs[i].base.has_mp[k] != 0;
@@ -849,10 +852,10 @@ int h_pose_opt2(void* p, int n, oslam_job_pose2_t* jobs) {
     }
     o->pool->parallel_for(n, [&](int i) {
         oslam_job_pose_t& j = jobs[i].base;
-        memcpy(j.Tcw_out, o->dn.bytes() + rT + 64 * i, 64);
-        memcpy(j.outlier, o->dn.bytes() + rO + cap * i, (size_t)j.N);
-        j.n_inliers = ((const int32_t*)(o->dn.bytes() + rN))[i];
-        jobs[i].n_semantic = ((const int32_t*)(o->dn.bytes() + rNs))[i];
+        copy_elems(j.Tcw_out, row(rT, D, 16, i), 16);
+        copy_elems(j.outlier, row(rO, D, cap, i), (size_t)j.N);
+        j.n_inliers = at(rN, D)[i];
+        jobs[i].n_semantic = at(rNs, D)[i];
     });
     return OSLAM_OK;
 }
@@ -870,7 +873,7 @@ int h_keyframe_raw_keys(void* p, int n, const int32_t* slots, const int32_t* cou
     const size_t cap = o->cap;
     for (int i = 0; i < n; i++) {
         if (slots[i] != o->kfk_slots[i] || counts[i] < 0 || (size_t)counts[i] > cap) { oslam::set_error("keyframe_raw_keys: not the keyframes of the last register_keyframes call"); return OSLAM_E_INVALID; }
-        memcpy(out[i], o->kfk.bytes() + (size_t)i * cap * sizeof(oslam_keypoint_t), (size_t)counts[i] * sizeof(oslam_keypoint_t));
+        copy_elems(out[i], row(o->kfk_keys, o->kfk.bytes(), cap, i), (size_t)counts[i]);
     }
     return OSLAM_OK;
 }
@@ -881,10 +884,9 @@ int h_keyframe_descriptors(void* p, int n, const int32_t* slots, const int32_t* 
         return OSLAM_E_INVALID;
     }
     const size_t cap = o->cap;
-    const uint8_t* base = o->kfk.bytes() + (size_t)n * cap * sizeof(oslam_keypoint_t);
     for (int i = 0; i < n; i++) {
         if (slots[i] != o->kfk_slots[i] || counts[i] < 0 || (size_t)counts[i] > cap) { oslam::set_error("keyframe_descriptors: not the keyframes of the last register_keyframes call"); return OSLAM_E_INVALID; }
-        memcpy(out[i], base + (size_t)i * cap * 32, (size_t)counts[i] * 32);
+        copy_elems(out[i], row(o->kfk_desc, o->kfk.bytes(), 32 * cap, i), 32 * (size_t)counts[i]);
     }
     return OSLAM_OK;
 }
@@ -895,18 +897,21 @@ int h_frame_descriptors(void* p, int n, const int32_t* slots, const int32_t* cou
     if (n == 0) return OSLAM_OK;
     if (!o->d_desc) { oslam::set_error("frame_descriptors: no frame has been built yet"); return OSLAM_E_INVALID; }
     const size_t cap = o->cap;
-    OPS_CHECK(o->ensure_dn((size_t)n * cap * 32));
+    StageLayout L, R;
+    const auto fSeg = L.add<CopySegH>(n); const auto rDesc = R.add<uint8_t>(32 * cap * n);
+    OSLAM_CHECK(o->ensure_dn(R.total()));
+    uint8_t* D = o->dn.bytes();
     std::vector<CopySegH> segs(n);
     for (int i = 0; i < n; i++) {
         if (slots[i] < 0 || slots[i] >= o->S || counts[i] < 0 || (size_t)counts[i] > cap) { oslam::set_error("frame_descriptors: bad slot / count"); return OSLAM_E_INVALID; }
-        segs[i] = {o->d_desc + 32 * cap * slots[i], o->dn.bytes() + (size_t)i * cap * 32, (uint32_t)(cap * 32), 0};
+        segs[i] = {o->d_desc + 32 * cap * slots[i], row(rDesc, D, 32 * cap, i), (uint32_t)(cap * 32), 0};
     }
-    OPS_CHECK(o->ensure_up(segs.size() * sizeof(CopySegH)));
-    memcpy(o->up.h.bytes(), segs.data(), segs.size() * sizeof(CopySegH));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), o->up.h.bytes(), segs.size() * sizeof(CopySegH), hipMemcpyHostToDevice, o->strm));
-    OPS_CHECK(oslam_copy_segments_device(o->up.d.bytes(), (int)segs.size(), o->strm));
+    OSLAM_CHECK(o->ensure_up(L.total()));
+    put(fSeg, o->up.h.bytes(), segs.data());
+    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), o->up.h.bytes(), fSeg.bytes, hipMemcpyHostToDevice, o->strm));
+    OSLAM_CHECK(oslam_copy_segments_device(at(fSeg, o->up.d.bytes()), (int)segs.size(), o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
-    for (int i = 0; i < n; i++) memcpy(out[i], o->dn.bytes() + (size_t)i * cap * 32, (size_t)counts[i] * 32);
+    for (int i = 0; i < n; i++) copy_elems(out[i], row(rDesc, D, 32 * cap, i), 32 * (size_t)counts[i]);
     return OSLAM_OK;
 }
 // The deferred form: only the one-launch path (k_mp_update_fused) is deferred — it needs no staging beyond the job block and writes its results into a pinned
@@ -924,14 +929,14 @@ int h_mp_update_collect(void* p) {
     HipOps* o = (HipOps*)p;
     if (!o->mpu_pend.on) return OSLAM_OK;
     OSLAM_HIP_CHECK(hipSetDevice(o->cfg.device));
-    OPS_CHECK(o->mpu_launch_pending());
+    OSLAM_CHECK(o->mpu_launch_pending());
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     HipOps::MpuPending& q = o->mpu_pend;
     q.on = false;
     o->swap_staging();   // (the deferred job's event pair and result block)
     o->t_collect(6, 1, q.dtotal);
-    if (q.j->do_desc) { memcpy(q.j->best_idx, o->dn.bytes() + q.rBest, 4 * q.P); memcpy(q.j->out_desc, o->dn.bytes() + q.rOut, 32 * q.P); }
-    if (q.j->do_normal) memcpy(q.j->out5, o->dn.bytes() + q.rOut5, 20 * q.P);
+    if (q.j->do_desc) { get(q.rBest, o->dn.bytes(), q.j->best_idx); get(q.rOut, o->dn.bytes(), q.j->out_desc); }
+    if (q.j->do_normal) get(q.rOut5, o->dn.bytes(), q.j->out5);
     o->swap_staging();
     return OSLAM_OK;
 }
@@ -958,7 +963,6 @@ static int mp_update_impl(HipOps* o, oslam_job_mp_update_t* j, const int32_t* ob
     // the descriptor selection has its own observation list when some observations sit in culled keyframes (oslam_job_mp_update_t::desc_start)
     const int32_t* dstart = j->desc_start ? j->desc_start : j->obs_start;
     const size_t dtotal = (size_t)dstart[P];
-    Layout L;
     // with resident keyframes the observations' descriptors are gathered on the device from (record, keypoint) pairs: 8 bytes per observation travel
     // instead of 32, and the caller did not have to collect them
     std::vector<int32_t>& rec = o->mpu_rec;   // (keeps its capacity: 8 bytes per observation, up to ~10 MB per call after a local BA)
@@ -989,25 +993,27 @@ static int mp_update_impl(HipOps* o, oslam_job_mp_update_t* j, const int32_t* ob
             if (sl < 0 || sl >= o->S || id < 0) { oslam::set_error("mp_update: bad item"); return OSLAM_E_INVALID; }
             mx[sl] = std::max(mx[sl], id);
         }
-        for (int sl = 0; sl < o->S; sl++) if (mx[sl] >= 0) OPS_CHECK(o->ensure_mp_records(sl, (size_t)mx[sl] + 1));
-        OPS_CHECK(o->sync_mp_table());
+        for (int sl = 0; sl < o->S; sl++) if (mx[sl] >= 0) OSLAM_CHECK(o->mp_tab.ensure(sl, (size_t)mx[sl] + 1, o->strm));
+        OSLAM_CHECK(o->mp_tab.sync(o->strm));
     }
     lap_(1);
-    const size_t oItems = L.take(table ? 8 * P : 0);
-    const size_t oStart = L.take(4 * (P + 1)), oDStart = L.take(j->desc_start ? 4 * (P + 1) : 0), oRec = L.take(keyed ? 8 * dtotal : 0), oOw = L.take(12 * total),
-                 oPos = L.take(12 * P), oRef = L.take(12 * P), oLsf = L.take(4 * P), oDescUp = L.take(keyed ? 0 : 32 * dtotal);
-    const size_t in_bytes = L.off;
-    const size_t oDesc = keyed ? L.take(32 * dtotal) : oDescUp;
-    const size_t oBest = L.take(4 * P), oOut = L.take(32 * P), oOut5 = L.take(20 * P);
-    OPS_CHECK(o->ensure_up(L.off));
-    uint8_t* U = o->up.h.bytes();
-    uint8_t* Dv = o->up.d.bytes();
-    memcpy(U + oStart, j->obs_start, 4 * (P + 1));
-    if (table) memcpy(U + oItems, j->items, 8 * P);
-    if (j->desc_start) memcpy(U + oDStart, j->desc_start, 4 * (P + 1));
-    if (keyed) memcpy(U + oRec, rec.data(), 8 * dtotal);
-    else if (j->do_desc) memcpy(U + oDesc, j->obs_desc, 32 * dtotal);
-    if (j->do_normal) { memcpy(U + oOw, j->obs_Ow, 12 * total); memcpy(U + oPos, j->Pos, 12 * P); memcpy(U + oRef, j->OwRef, 12 * P); memcpy(U + oLsf, j->levelScaleFactor, 4 * P); }
+    const bool has_ds = j->desc_start != nullptr;
+    StageLayout L;
+    const auto fItems = L.add<int32_t>(2 * P, table); const auto fStart = L.add<int32_t>(P + 1), fDStartOwn = L.add<int32_t>(P + 1, has_ds), fRec = L.add<int32_t>(2 * dtotal, keyed);
+    const auto fOw = L.add<float>(3 * total), fPos = L.add<float>(3 * P), fRef = L.add<float>(3 * P), fLsf = L.add<float>(P);
+    const auto fDescUp = L.add<uint8_t>(32 * dtotal, !keyed);   // the observations' descriptors as the caller collected them
+    const size_t in_bytes = L.total();                          // what the kernels read from the host: nothing behind this travels
+    const auto fDesc = keyed ? L.add<uint8_t>(32 * dtotal) : fDescUp;   // keyed: gathered on the device from the resident keyframes
+    const auto fBest = L.add<int32_t>(P); const auto fOut = L.add<uint8_t>(32 * P); const auto fOut5 = L.add<float>(5 * P);
+    const auto fDStart = has_ds ? fDStartOwn : fStart;
+    OSLAM_CHECK(o->ensure_up(L.total()));
+    uint8_t *U = o->up.h.bytes(), *Dv = o->up.d.bytes();
+    put(fStart, U, j->obs_start);
+    if (table) put(fItems, U, j->items);
+    if (has_ds) put(fDStartOwn, U, j->desc_start);
+    if (keyed) put(fRec, U, rec.data());
+    else if (j->do_desc) put(fDesc, U, j->obs_desc);
+    if (j->do_normal) { put(fOw, U, j->obs_Ow); put(fPos, U, j->Pos); put(fRef, U, j->OwRef); put(fLsf, U, j->levelScaleFactor); }
     lap_(2);
     // The job block is read by the kernels where it is (pinned, mapped into the device's address space) unless it carries the observations' descriptors, which
     // k_distinctive reads many times: every array of the keyed form is read once or twice, and the copy engine hop + its dependency cost more than the PCIe
@@ -1016,11 +1022,12 @@ static int mp_update_impl(HipOps* o, oslam_job_mp_update_t* j, const int32_t* ob
     // then hold the device 20 % longer and the whole bench loses 4 %)
     constexpr size_t kZeroCopyMaxBytes = 262144;
     const bool upload = (j->do_desc && !keyed) || in_bytes > kZeroCopyMaxBytes;
-    const uint8_t* In = upload ? Dv : U;
+    uint8_t* const In = upload ? Dv : U;   // the block the kernels read the job from: at(field, In) serves both
     if (upload) OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, in_bytes, hipMemcpyHostToDevice, o->strm));
-    Layout R;
-    const size_t rBest = R.take(4 * P), rOut = R.take(32 * P), rOut5 = R.take(20 * P);
-    OPS_CHECK(o->ensure_dn(R.off));
+    StageLayout R;
+    const auto rBest = R.add<int32_t>(P); const auto rOut = R.add<uint8_t>(32 * P); const auto rOut5 = R.add<float>(5 * P);
+    OSLAM_CHECK(o->ensure_dn(R.total()));
+    uint8_t* const D = o->dn.bytes();
     // The small keyed jobs (every Fuse round's descriptor updates, the new keyframe's and the new points' updates) in ONE launch: k_mp_update_fused reads the
     // observations' descriptors from the resident keyframes, writes the results straight into the (device-accessible) result block and into the resident records.
     // Large jobs and jobs that carry their descriptors take the separate kernels below.
@@ -1029,56 +1036,54 @@ static int mp_update_impl(HipOps* o, oslam_job_mp_update_t* j, const int32_t* ob
     if (fused) {
         // (the deferred form does not even enqueue the kernel here: it is launched right in front of the next operator's own kernel — the next Fuse round's search —
         // or by mp_update_collect, so that ONE wait covers both and nothing runs on the card while the driver does the round's bookkeeping)
-        const bool do_desc = j->do_desc != 0, do_normal = j->do_normal != 0, has_ds = j->desc_start != nullptr;
-        uint8_t* const dn = o->dn.bytes();
+        const bool do_desc = j->do_desc != 0, do_normal = j->do_normal != 0;
         hipEvent_t e0 = o->tev0, e1 = o->tev1;
+        // (the closure keeps the blocks it was built on — In, D — by value: swap_staging() exchanges the handle's members underneath it)
         std::function<int()> launch = [=]() -> int {
             if (o->timing) (void)hipEventRecord(e0, o->strm);
-            const int rcl = oslam_mp_update_fused_device((int)P, do_desc, do_normal, (const int32_t*)(In + oStart), (const int32_t*)(In + (has_ds ? oDStart : oStart)),
-                                                         keyed ? (const int32_t*)(In + oRec) : nullptr, o->d_rec_desc.as<uint8_t*>(), (const float*)(In + oOw), (const float*)(In + oPos),
-                                                         (const float*)(In + oRef), (const float*)(In + oLsf), o->scale[o->cfg.nLevels - 1], table ? (const int32_t*)(In + oItems) : nullptr,
-                                                         table ? o->d_mp_tab.as<uint8_t*>() : nullptr, (int32_t*)(dn + rBest), dn + rOut, (float*)(dn + rOut5), o->strm);
+            const int rcl = oslam_mp_update_fused_device((int)P, do_desc, do_normal, at(fStart, In), at(fDStart, In), at(fRec, In), o->d_rec_desc.as<uint8_t*>(), at(fOw, In), at(fPos, In),
+                                                         at(fRef, In), at(fLsf, In), o->scale[o->cfg.nLevels - 1], at(fItems, In), table ? o->mp_tab.device_table() : nullptr,
+                                                         at(rBest, D), at(rOut, D), at(rOut5, D), o->strm);
             if (o->timing) (void)hipEventRecord(e1, o->strm);
             return rcl;
         };
         if (defer) {   // (h_mp_update_collect finishes it)
-            o->mpu_pend.on = true; o->mpu_pend.j = j; o->mpu_pend.P = P; o->mpu_pend.rBest = rBest; o->mpu_pend.rOut = rOut; o->mpu_pend.rOut5 = rOut5; o->mpu_pend.dtotal = (double)dtotal;
+            o->mpu_pend.on = true; o->mpu_pend.j = j; o->mpu_pend.rBest = rBest; o->mpu_pend.rOut = rOut; o->mpu_pend.rOut5 = rOut5; o->mpu_pend.dtotal = (double)dtotal;
             o->mpu_pend.launch = launch;
             return OSLAM_OK;
         }
-        OPS_CHECK(launch());
+        OSLAM_CHECK(launch());
         lap_(3);
         OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
         lap_(4);
         o->t_collect(6, 1, (double)dtotal);
-        if (j->do_desc) { memcpy(j->best_idx, o->dn.bytes() + rBest, 4 * P); memcpy(j->out_desc, o->dn.bytes() + rOut, 32 * P); }
-        if (j->do_normal) memcpy(j->out5, o->dn.bytes() + rOut5, 20 * P);
+        if (j->do_desc) { get(rBest, D, j->best_idx); get(rOut, D, j->out_desc); }
+        if (j->do_normal) get(rOut5, D, j->out5);
         lap_(5);
         return OSLAM_OK;
     }
     o->t_begin();
-    if (keyed) OPS_CHECK(oslam_gather_descriptors_device(o->d_rec_desc.as<uint8_t*>(), (const int32_t*)(In + oRec), (int)dtotal, Dv + oDesc, o->strm));
+    if (keyed) OSLAM_CHECK(oslam_gather_descriptors_device(o->d_rec_desc.as<uint8_t*>(), at(fRec, In), (int)dtotal, at(fDesc, Dv), o->strm));
     if (j->do_desc) {
-        OSLAM_HIP_CHECK(hipMemsetAsync(Dv + oOut, 0, 32 * P, o->strm));
-        OPS_CHECK(oslam_mp_distinctive_descriptors_device((int)P, (const int32_t*)(In + (j->desc_start ? oDStart : oStart)), Dv + oDesc, (int32_t*)(Dv + oBest), Dv + oOut, o->strm));
-        OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn.bytes() + rBest, Dv + oBest, 4 * P, o->strm));
-        OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn.bytes() + rOut, Dv + oOut, 32 * P, o->strm));
+        OSLAM_HIP_CHECK(hipMemsetAsync(at(fOut, Dv), 0, fOut.bytes, o->strm));
+        OSLAM_CHECK(oslam_mp_distinctive_descriptors_device((int)P, at(fDStart, In), at(fDesc, Dv), at(fBest, Dv), at(fOut, Dv), o->strm));
+        OSLAM_HIP_CHECK(oslam::copy_to_host_async(at(rBest, D), at(fBest, Dv), rBest.bytes, o->strm));
+        OSLAM_HIP_CHECK(oslam::copy_to_host_async(at(rOut, D), at(fOut, Dv), rOut.bytes, o->strm));
     }
     if (j->do_normal) {
-        OPS_CHECK(oslam_mp_update_normal_depth_device((int)P, (const float*)(In + oPos), (const int32_t*)(In + oStart), (const float*)(In + oOw), (const float*)(In + oRef),
-                                                      (const float*)(In + oLsf), o->scale[o->cfg.nLevels - 1], (float*)(Dv + oOut5), o->strm));
-        OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn.bytes() + rOut5, Dv + oOut5, 20 * P, o->strm));
+        OSLAM_CHECK(oslam_mp_update_normal_depth_device((int)P, at(fPos, In), at(fStart, In), at(fOw, In), at(fRef, In), at(fLsf, In), o->scale[o->cfg.nLevels - 1], at(fOut5, Dv), o->strm));
+        OSLAM_HIP_CHECK(oslam::copy_to_host_async(at(rOut5, D), at(fOut5, Dv), rOut5.bytes, o->strm));
     }
     if (table)
-        OPS_CHECK(oslam_mp_table_write_device((int)P, (const int32_t*)(In + oItems), o->d_mp_tab.as<uint8_t*>(), (const int32_t*)(In + oStart), (const int32_t*)(In + (j->desc_start ? oDStart : oStart)),
-                                              (const float*)(In + oPos), (const float*)(Dv + oOut5), Dv + oOut, j->do_desc, j->do_normal, o->strm));
+        OSLAM_CHECK(oslam_mp_table_write_device((int)P, at(fItems, In), o->mp_tab.device_table(), at(fStart, In), at(fDStart, In), at(fPos, In), at(fOut5, Dv), at(fOut, Dv), j->do_desc, j->do_normal,
+                                                o->strm));
     o->t_end();
     lap_(3);
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     lap_(4);
     o->t_collect(6, (keyed ? 1 : 0) + (j->do_desc ? 2 : 0) + (j->do_normal ? 1 : 0) + (table ? 1 : 0), (double)dtotal);
-    if (j->do_desc) { memcpy(j->best_idx, o->dn.bytes() + rBest, 4 * P); memcpy(j->out_desc, o->dn.bytes() + rOut, 32 * P); }
-    if (j->do_normal) memcpy(j->out5, o->dn.bytes() + rOut5, 20 * P);
+    if (j->do_desc) { get(rBest, D, j->best_idx); get(rOut, D, j->out_desc); }
+    if (j->do_normal) get(rOut5, D, j->out5);
     lap_(5);
     return OSLAM_OK;
 }
@@ -1102,49 +1107,51 @@ int h_mp_update_windows(void* p, int n, oslam_job_mp_window_t* wins) {
         for (int i = 0; i < n; i++) {
             int mx = -1;
             for (int j = 0; j < wins[i].nP; j++) mx = std::max(mx, wins[i].pt_ids[j]);
-            if (mx >= 0) OPS_CHECK(o->ensure_mp_records(wins[i].slot, (size_t)mx + 1));
+            if (mx >= 0) OSLAM_CHECK(o->mp_tab.ensure(wins[i].slot, (size_t)mx + 1, o->strm));
         }
-        OPS_CHECK(o->sync_mp_table());
+        OSLAM_CHECK(o->mp_tab.sync(o->strm));
     }
-    Layout L;
-    const size_t oItems = L.take(8 * P), oE0 = L.take(4 * P), oNe = L.take(4 * P), oKb = L.take(4 * P), oRef = L.take(4 * P), oLsf = L.take(4 * P), oSkip = L.take(P), oPos = L.take(12 * P),
-                 oEkf = L.take(4 * E), oEr = L.take(E), oOw = L.take(12 * K);
-    const size_t in_bytes = L.off;
-    const size_t oOut = L.take(20 * P);
-    OPS_CHECK(o->ensure_up(L.off));
-    uint8_t* U = o->up.h.bytes();
-    uint8_t* Dv = o->up.d.bytes();
+    StageLayout L;
+    const auto fItems = L.add<int32_t>(2 * P), fE0 = L.add<int32_t>(P), fNe = L.add<int32_t>(P), fKb = L.add<int32_t>(P), fRef = L.add<int32_t>(P); const auto fLsf = L.add<float>(P);
+    const auto fSkip = L.add<uint8_t>(P); const auto fPos = L.add<float>(3 * P); const auto fEkf = L.add<int32_t>(E); const auto fEr = L.add<uint8_t>(E);
+    const auto fOw = L.add<float>(3 * K);
+    const size_t in_bytes = L.total();   // the result array behind this does not travel
+    const auto fOut = L.add<float>(5 * P);
+    OSLAM_CHECK(o->ensure_up(L.total()));
+    uint8_t *U = o->up.h.bytes(), *Dv = o->up.d.bytes();
     std::vector<size_t> pb(n + 1, 0), eb(n + 1, 0), kb(n + 1, 0);
     for (int i = 0; i < n; i++) { pb[i + 1] = pb[i] + wins[i].nP; eb[i + 1] = eb[i] + wins[i].nE; kb[i + 1] = kb[i] + wins[i].nK; }
     o->pool->parallel_for(n, [&](int i) {
         const oslam_job_mp_window_t& w = wins[i];
-        int32_t* it = (int32_t*)(U + oItems) + 2 * pb[i];
-        int32_t* e0 = (int32_t*)(U + oE0) + pb[i];
-        int32_t* ne = (int32_t*)(U + oNe) + pb[i];
-        int32_t* kq = (int32_t*)(U + oKb) + pb[i];
+        int32_t* it = at(fItems, U) + 2 * pb[i];
+        int32_t* e0 = at(fE0, U) + pb[i];
+        int32_t* ne = at(fNe, U) + pb[i];
+        int32_t* kq = at(fKb, U) + pb[i];
         for (int j = 0; j < w.nP; j++) {
             it[2 * j] = w.slot; it[2 * j + 1] = w.pt_ids[j];
             e0[j] = (int32_t)eb[i] + w.pt_start[j]; ne[j] = w.pt_start[j + 1] - w.pt_start[j]; kq[j] = (int32_t)kb[i];
         }
-        memcpy((int32_t*)(U + oRef) + pb[i], w.ref_kf, 4 * (size_t)w.nP);
-        memcpy((float*)(U + oLsf) + pb[i], w.lsf, 4 * (size_t)w.nP);
-        memcpy(U + oSkip + pb[i], w.skip, (size_t)w.nP);
-        memcpy((float*)(U + oPos) + 3 * pb[i], w.pos, 12 * (size_t)w.nP);
-        memcpy((int32_t*)(U + oEkf) + eb[i], w.edge_kf, 4 * (size_t)w.nE);
-        memcpy(U + oEr + eb[i], w.erase, (size_t)w.nE);
-        memcpy((float*)(U + oOw) + 3 * kb[i], w.Ow, 12 * (size_t)w.nK);
+        copy_elems(at(fRef, U) + pb[i], w.ref_kf, (size_t)w.nP);
+        copy_elems(at(fLsf, U) + pb[i], w.lsf, (size_t)w.nP);
+        copy_elems(at(fSkip, U) + pb[i], w.skip, (size_t)w.nP);
+        copy_elems(at(fPos, U) + 3 * pb[i], w.pos, 3 * (size_t)w.nP);
+        copy_elems(at(fEkf, U) + eb[i], w.edge_kf, (size_t)w.nE);
+        copy_elems(at(fEr, U) + eb[i], w.erase, (size_t)w.nE);
+        copy_elems(at(fOw, U) + 3 * kb[i], w.Ow, 3 * (size_t)w.nK);
     });
     OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, in_bytes, hipMemcpyHostToDevice, o->strm));
     o->t_begin();
-    OPS_CHECK(oslam_mp_update_windows_device((int)P, (const int32_t*)(Dv + oItems), table ? o->d_mp_tab.as<uint8_t*>() : nullptr, (const int32_t*)(Dv + oE0), (const int32_t*)(Dv + oNe),
-                                             (const int32_t*)(Dv + oKb), (const int32_t*)(Dv + oRef), (const float*)(Dv + oLsf), Dv + oSkip, (const float*)(Dv + oPos),
-                                             (const int32_t*)(Dv + oEkf), Dv + oEr, (const float*)(Dv + oOw), o->scale[o->cfg.nLevels - 1], (float*)(Dv + oOut), o->strm));
+    OSLAM_CHECK(oslam_mp_update_windows_device((int)P, at(fItems, Dv), table ? o->mp_tab.device_table() : nullptr, at(fE0, Dv), at(fNe, Dv), at(fKb, Dv), at(fRef, Dv), at(fLsf, Dv), at(fSkip, Dv),
+                                               at(fPos, Dv), at(fEkf, Dv), at(fEr, Dv), at(fOw, Dv), o->scale[o->cfg.nLevels - 1], at(fOut, Dv), o->strm));
     o->t_end();
-    OPS_CHECK(o->ensure_dn(20 * P));
-    OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn.bytes(), Dv + oOut, 20 * P, o->strm));
+    StageLayout R;
+    const auto rOut = R.add<float>(5 * P);
+    OSLAM_CHECK(o->ensure_dn(R.total()));
+    uint8_t* D = o->dn.bytes();
+    OSLAM_HIP_CHECK(oslam::copy_to_host_async(at(rOut, D), at(fOut, Dv), rOut.bytes, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(6, 1, (double)E);
-    o->pool->parallel_for(n, [&](int i) { memcpy(wins[i].out5, o->dn.bytes() + 20 * pb[i], 20 * (size_t)wins[i].nP); });
+    o->pool->parallel_for(n, [&](int i) { copy_elems(wins[i].out5, at(rOut, D) + 5 * pb[i], 5 * (size_t)wins[i].nP); });
     return OSLAM_OK;
 }
 
@@ -1342,7 +1349,7 @@ int h_lba(void* p, int n, const oslam_lba_problem_t* pr) {
     if (!rc && q.stats != pr[0].stats && pr[0].stats) memcpy(pr[0].stats, q.stats, 16);
     if (!rc && o->timing) {
         double ms = 0; long long launches = 0;
-        OPS_CHECK(oslam_lba_kernel_time(o->ba1, 1, &ms, &launches));
+        OSLAM_CHECK(oslam_lba_kernel_time(o->ba1, 1, &ms, &launches));
         o->kt[6] += ms; o->kt[7] += (double)launches; o->kt[8] += q.stats[0] >= 0 ? lba_flop(q, q.stats) : 0.0;
     }
     return rc;
@@ -1379,7 +1386,7 @@ int h_register_keyframes(void* p, int n, const int32_t* slots, const int32_t* kf
     OSLAM_HIP_CHECK(hipSetDevice(o->cfg.device));
     if (n == 0) return OSLAM_OK;
     if ((int)o->rec_of_kf.size() < o->S) o->rec_of_kf.resize(o->S);
-    const size_t cap = o->cap, rb = o->rec_bytes();
+    const size_t cap = o->cap;
     std::vector<CopySegH> segs;
     for (int i = 0; i < n; i++) {
         const int slot = slots[i], kf = kf_ids[i];
@@ -1395,7 +1402,7 @@ int h_register_keyframes(void* p, int n, const int32_t* slots, const int32_t* kf
             r = o->n_rec++;
             if (r / HipOps::kRecChunk >= (int)o->rec_chunks.size()) {
                 oslam::DeviceBuffer c;
-                OPS_CHECK(c.alloc(rb * HipOps::kRecChunk));
+                OSLAM_CHECK(c.alloc(o->rec_bytes() * HipOps::kRecChunk));
                 o->rec_chunks.push_back(std::move(c));
             }
             o->h_rec_desc.push_back((uint8_t*)o->rec_desc(r));
@@ -1409,43 +1416,45 @@ int h_register_keyframes(void* p, int n, const int32_t* slots, const int32_t* kf
     if (o->lazy_rows && (!o->d_kp || !o->d_desc)) { oslam::set_error("register_keyframes: no frame has been built yet"); return OSLAM_E_INVALID; }
     if (o->lazy_rows) {   // mvKeys and mDescriptors of the new keyframes: written by the same launch into a pinned block the device can address
                           // (keyframe_raw_keys / keyframe_descriptors hand them out)
-        const size_t need = (size_t)n * cap * (sizeof(oslam_keypoint_t) + 32);
-        if (need > o->kfk.cap()) OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
-        OPS_CHECK(o->kfk.grow(need, 4096));
-        o->kfk_slots.assign(slots, slots + n);
+        StageLayout K;
+        const auto kKeys = K.add<oslam_keypoint_t>(cap * n); const auto kDesc = K.add<uint8_t>(32 * cap * n);
+        if (K.total() > o->kfk.cap()) OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
+        OSLAM_CHECK(o->kfk.grow(K.total(), 4096));
+        o->kfk_slots.assign(slots, slots + n); o->kfk_keys = kKeys; o->kfk_desc = kDesc;
         for (int i = 0; i < n; i++)
-            segs.push_back({(const uint8_t*)(o->d_kp + cap * slots[i]), o->kfk.bytes() + (size_t)i * cap * sizeof(oslam_keypoint_t), (uint32_t)(cap * sizeof(oslam_keypoint_t)), 0});
-        uint8_t* const desc_rows = o->kfk.bytes() + (size_t)n * cap * sizeof(oslam_keypoint_t);
-        for (int i = 0; i < n; i++) segs.push_back({o->d_desc + 32 * cap * slots[i], desc_rows + (size_t)i * cap * 32, (uint32_t)(cap * 32), 0});
+            segs.push_back({(const uint8_t*)(o->d_kp + cap * slots[i]), (uint8_t*)row(o->kfk_keys, o->kfk.bytes(), cap, i), (uint32_t)(cap * sizeof(oslam_keypoint_t)), 0});
+        for (int i = 0; i < n; i++) segs.push_back({o->d_desc + 32 * cap * slots[i], row(o->kfk_desc, o->kfk.bytes(), 32 * cap, i), (uint32_t)(cap * 32), 0});
     }
-    const size_t oJobs = oslam::align_up(segs.size() * sizeof(CopySegH), 256), up_bytes = oJobs + (size_t)n * sizeof(oslam_kf_grid_job_t);
-    OPS_CHECK(o->ensure_up(up_bytes));
-    memcpy(o->up.h.bytes(), segs.data(), segs.size() * sizeof(CopySegH));
-    oslam_kf_grid_job_t* gj = (oslam_kf_grid_job_t*)(o->up.h.bytes() + oJobs);
+    StageLayout L;
+    const auto fSeg = L.add<CopySegH>(segs.size()); const auto fJobs = L.add<oslam_kf_grid_job_t>(n);
+    OSLAM_CHECK(o->ensure_up(L.total()));
+    uint8_t *U = o->up.h.bytes(), *Dv = o->up.d.bytes();
+    put(fSeg, U, segs.data());
+    oslam_kf_grid_job_t* gj = at(fJobs, U);
     for (int i = 0; i < n; i++) {
         const int r = o->rec_of_kf[slots[i]][kf_ids[i]];
         gj[i].keys = o->rec_keys(r); gj[i].uRight = o->rec_ur(r); gj[i].cell_end = o->rec_cell_end(r); gj[i].cand = o->rec_cand(r); gj[i].slot = slots[i]; gj[i].pad_ = 0;
     }
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), o->up.h.bytes(), up_bytes, hipMemcpyHostToDevice, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, fJobs.end(), hipMemcpyHostToDevice, o->strm));
     o->t_begin();
-    OPS_CHECK(oslam_copy_segments_device(o->up.d.bytes(), (int)segs.size(), o->strm));
+    OSLAM_CHECK(oslam_copy_segments_device(at(fSeg, Dv), (int)segs.size(), o->strm));
     // KeyFrame::mGrid of the new keyframes (fixed from here on): sorted once, read by every later Fuse against them
-    OPS_CHECK(oslam_kf_grid_build_device(n, (const oslam_kf_grid_job_t*)(o->up.d.bytes() + oJobs), o->d_cnt, o->bounds, (int)cap, o->d_status.as<int32_t>() + 8, o->strm));
+    OSLAM_CHECK(oslam_kf_grid_build_device(n, at(fJobs, Dv), o->d_cnt, o->bounds, (int)cap, o->d_status.as<int32_t>() + 8, o->strm));
     o->t_end();
     // descriptor-array table for the observation gathers
     if ((size_t)o->n_rec * sizeof(uint8_t*) > o->d_rec_desc.cap()) {
         OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
-        OPS_CHECK(o->d_rec_desc.alloc(((size_t)o->n_rec * 2 + 1024) * sizeof(uint8_t*)));
+        OSLAM_CHECK(o->d_rec_desc.alloc(((size_t)o->n_rec * 2 + 1024) * sizeof(uint8_t*)));
         o->rec_desc_n = 0;
     }
     OSLAM_HIP_CHECK(hipMemcpyAsync(o->d_rec_desc.as<uint8_t*>() + o->rec_desc_n, o->h_rec_desc.data() + o->rec_desc_n, (size_t)(o->n_rec - o->rec_desc_n) * sizeof(uint8_t*),
                                    hipMemcpyHostToDevice, o->strm));
     o->rec_desc_n = o->n_rec;
-    OPS_CHECK(o->ensure_dn(4));
+    OSLAM_CHECK(o->ensure_dn(4));
     OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn.bytes(), o->d_status.as<int32_t>() + 8, 4, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));   // the records are complete when this returns
     o->t_collect(7, 2, 0);
-    if (*(const int32_t*)o->dn.bytes() != 0) { oslam::set_error("register_keyframes: a keyframe has more keypoints than the extractor's capacity"); return OSLAM_E_CAPACITY; }
+    if (*o->dn.as<int32_t>() != 0) { oslam::set_error("register_keyframes: a keyframe has more keypoints than the extractor's capacity"); return OSLAM_E_CAPACITY; }
     return OSLAM_OK;
 }
 
@@ -1547,7 +1556,7 @@ __global__ __launch_bounds__(64) void k_cull_counts(const CullCand* cands, uint8
 
 static MirrorGeom mirror_geom(const HipOps* o) {
     MirrorGeom g;
-    g.rec_bytes = o->rec_bytes(); g.core_bytes = o->rec_core_bytes(); g.okf_off = oslam::align_up((size_t)o->cap * 4, 256); g.good_off = g.okf_off + oslam::align_up((size_t)o->cap * 8, 256);
+    g.rec_bytes = o->rec_lay.bytes; g.core_bytes = o->rec_lay.core_bytes(); g.okf_off = o->rec_lay.okf_from_mp(); g.good_off = o->rec_lay.good_from_mp();
     g.cap = o->cap; g.chunk = HipOps::kRecChunk;
     return g;
 }
@@ -1556,7 +1565,6 @@ int h_map_journal(void* p, int n, const oslam_map_changes_t* ch) {
     HipOps* o = (HipOps*)p;
     OSLAM_HIP_CHECK(hipSetDevice(o->cfg.device));
     if (n <= 0) return OSLAM_OK;
-    o->size_pt_aux();
     if ((int)o->okf_seq.size() < o->S) o->okf_seq.resize(o->S, 0u);
     if (o->mir_used) { OSLAM_HIP_CHECK(oslam::stream_wait(o->strm)); o->mir_used = 0; }   // (a flush without a collected count request before it: its block must have landed)
     size_t nbulk = 0, ncell = 0, nokf = 0, npt = 0, bw = 0;
@@ -1578,11 +1586,11 @@ int h_map_journal(void* p, int n, const oslam_map_changes_t* ch) {
         for (int q = 0; q < c.n_points; q++) m = std::max<long long>(m, (long long)c.points[5 * q]);
         maxp[i] = m;
     });
-    for (int i = 0; i < n; i++) if (maxp[i] >= 0) OPS_CHECK(o->ensure_pt_aux(ch[i].slot, (size_t)maxp[i] + 1));
-    Layout L;
-    const size_t aB = L.take(sizeof(MirrorBulk) * nbulk), aW = L.take(4 * bw), aC = L.take(16 * ncell), aO = L.take(16 * nokf), aP = L.take(32 * npt);
-    OPS_CHECK(o->ensure_mir(L.off + (1 << 20)));   // (+ room for the count request that usually follows)
-    OPS_CHECK(o->sync_mirror_tables());
+    for (int i = 0; i < n; i++) if (maxp[i] >= 0) OSLAM_CHECK(o->pt_aux.ensure(ch[i].slot, (size_t)maxp[i] + 1, o->strm));
+    StageLayout L;
+    const auto fB = L.add<MirrorBulk>(nbulk); const auto fW = L.add<uint32_t>(bw); const auto fC = L.add<int4>(ncell); const auto fO = L.add<uint4>(nokf), fP = L.add<uint4>(2 * npt);
+    OSLAM_CHECK(o->ensure_mir(L.total() + (1 << 20)));   // (+ room for the count request that usually follows)
+    OSLAM_CHECK(o->sync_mirror_tables());
     // event numbers: the new keyframes of a flush take the slot's counter, its observation events counter + 1 + position
     std::vector<uint32_t> seq0(n);
     for (int i = 0; i < n; i++) { seq0[i] = o->okf_seq[ch[i].slot]; o->okf_seq[ch[i].slot] += 1u + (uint32_t)ch[i].n_events; }
@@ -1591,17 +1599,17 @@ int h_map_journal(void* p, int n, const oslam_map_changes_t* ch) {
     o->pool->parallel_for(n, [&](int i) {
         const oslam_map_changes_t& c = ch[i];
         const int slot = c.slot;
-        MirrorBulk* B = (MirrorBulk*)(U + aB) + oB[i];
-        uint32_t* PW = (uint32_t*)(U + aW);
-        int4* Cc = (int4*)(U + aC) + oC[i];
-        uint4* Oo = (uint4*)(U + aO) + oO[i];
-        uint4* Pp = (uint4*)(U + aP) + 2 * oP[i];
+        MirrorBulk* B = at(fB, U) + oB[i];
+        uint32_t* PW = at(fW, U);
+        int4* Cc = at(fC, U) + oC[i];
+        uint4* Oo = at(fO, U) + oO[i];
+        uint4* Pp = at(fP, U) + 2 * oP[i];
         size_t wo = oW[i];
         for (int k = 0; k < c.n_new; k++) {
             const oslam_map_new_kf_t& e = c.new_kfs[k];
             B[k].r = o->rec_lookup(slot, e.kf); B[k].N = e.N; B[k].word_off = (uint32_t)wo; B[k].seq = seq0[i];
-            memcpy(PW + wo, e.mp, 4 * (size_t)e.N);
-            memcpy(PW + wo + e.N, e.good, 4 * (((size_t)e.N + 31) / 32));
+            memcpy(PW + wo, e.mp, sizeof(*PW) * (size_t)e.N);   // (point ids as words: the kernel reads them back as int32)
+            memcpy(PW + wo + e.N, e.good, sizeof(*PW) * (((size_t)e.N + 31) / 32));
             wo += (size_t)e.N + ((size_t)e.N + 31) / 32;
         }
         for (int q = 0; q < c.n_cells; q++) Cc[q] = make_int4(o->rec_lookup(slot, c.cells[3 * q]), c.cells[3 * q + 1], c.cells[3 * q + 2], 0);
@@ -1615,13 +1623,14 @@ int h_map_journal(void* p, int n, const oslam_map_changes_t* ch) {
             Pp[2 * q + 1] = make_uint4(c.points[5 * q + 3], c.points[5 * q + 4], 0u, 0u);
         }
     });
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->mir.d.bytes(), o->mir.h.bytes(), L.off, hipMemcpyHostToDevice, o->strm));
-    o->mir_used = L.off;
+    uint8_t* Dv = o->mir.d.bytes();
+    OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, L.total(), hipMemcpyHostToDevice, o->strm));
+    o->mir_used = L.total();
     const MirrorGeom g = mirror_geom(o);
-    if (nbulk) hipLaunchKernelGGL(k_mirror_bulk, dim3((unsigned)nbulk), dim3(256), 0, o->strm, (const MirrorBulk*)(o->mir.d.bytes() + aB), (const uint32_t*)(o->mir.d.bytes() + aW), o->d_rec_chunk.as<uint8_t*>(), g);
+    if (nbulk) hipLaunchKernelGGL(k_mirror_bulk, dim3((unsigned)nbulk), dim3(256), 0, o->strm, at(fB, Dv), at(fW, Dv), o->d_rec_chunk.as<uint8_t*>(), g);
     const size_t nops = ncell + nokf + npt;
-    if (nops) hipLaunchKernelGGL(k_mirror_ops, dim3((unsigned)((nops + 255) / 256)), dim3(256), 0, o->strm, (const int4*)(o->mir.d.bytes() + aC), (int)ncell, (const uint4*)(o->mir.d.bytes() + aO), (int)nokf,
-                                 (const uint4*)(o->mir.d.bytes() + aP), (int)npt, o->d_rec_chunk.as<uint8_t*>(), o->d_pt_aux.as<uint8_t*>(), g);
+    if (nops) hipLaunchKernelGGL(k_mirror_ops, dim3((unsigned)((nops + 255) / 256)), dim3(256), 0, o->strm, at(fC, Dv), (int)ncell, at(fO, Dv), (int)nokf, at(fP, Dv), (int)npt,
+                                 o->d_rec_chunk.as<uint8_t*>(), o->pt_aux.device_table(), g);
     OSLAM_HIP_CHECK(hipGetLastError());
     // (no wait: the consumer that follows on this stream — kf_culling_counts — synchronises; the mirror's upload block is not touched before the next flush, and
     // every operator of the step after this one waits for the stream before it returns)
@@ -1637,29 +1646,30 @@ int h_kf_culling_counts(void* p, int n, const oslam_job_cull_t* jobs, float thDe
     for (int i = 0; i < n; i++) { if (jobs[i].slot < 0 || jobs[i].slot >= o->S || jobs[i].n < 0 || !jobs[i].out) { oslam::set_error("kf_culling_counts: bad job"); return OSLAM_E_INVALID; } total += (size_t)jobs[i].n; }
     if (total == 0) return OSLAM_OK;
     // the request goes behind the flush in the mirror's upload block (both may be in flight together)
-    const size_t base = oslam::align_up(o->mir_used, 256), oC = base, oOut = oslam::align_up(oC + sizeof(CullCand) * total, 256), end = oOut + 16 * total;
+    StageLayout L;
+    const auto fC = L.add<CullCand>(total); const auto fOut = L.add<int32_t>(4 * total);
+    const size_t base = oslam::align_up(o->mir_used, 256), end = base + fOut.end();
     if (end > o->mir.cap()) {   // (rare: the block is grown with nothing in flight; the flush, if any, has completed by then)
         OSLAM_HIP_CHECK(hipStreamSynchronize(o->strm));
         o->mir_used = 0;
-        OPS_CHECK(o->ensure_mir(sizeof(CullCand) * total + 16 * total + 1024));
+        OSLAM_CHECK(o->ensure_mir(L.total() + 1024));
         return h_kf_culling_counts(p, n, jobs, thDepth);
     }
-    if (16 * total > o->cull.cap()) OSLAM_HIP_CHECK(hipStreamSynchronize(o->strm));
-    OPS_CHECK(o->cull.reserve(16 * total, 32 * total + 4096));
-    CullCand* cc = (CullCand*)(o->mir.h.bytes() + oC);
-    size_t at = 0;
-    o->size_pt_aux();
+    if (fOut.bytes > o->cull.cap()) OSLAM_HIP_CHECK(hipStreamSynchronize(o->strm));
+    OSLAM_CHECK(o->cull.reserve(fOut.bytes, 2 * fOut.bytes + 4096));
+    uint8_t *U = o->mir.h.bytes() + base, *Dv = o->mir.d.bytes() + base;
+    CullCand* cc = at(fC, U);
+    size_t k = 0;
     for (int i = 0; i < n; i++) {
-        if (!o->pt_aux[jobs[i].slot]) OPS_CHECK(o->ensure_pt_aux(jobs[i].slot, 1));
-        for (int q = 0; q < jobs[i].n; q++, at++) { cc[at].rec = o->rec_lookup(jobs[i].slot, jobs[i].kf_ids[q]); cc[at].slot = jobs[i].slot; }
+        OSLAM_CHECK(o->pt_aux.ensure(jobs[i].slot, 1, o->strm));   // (a slot the mirror has not seen yet: an empty block the kernels may index)
+        for (int q = 0; q < jobs[i].n; q++, k++) { cc[k].rec = o->rec_lookup(jobs[i].slot, jobs[i].kf_ids[q]); cc[k].slot = jobs[i].slot; }
         o->cull_pending.push_back({jobs[i].out, jobs[i].n});
     }
-    OPS_CHECK(o->sync_mirror_tables());
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->mir.d.bytes() + oC, o->mir.h.bytes() + oC, sizeof(CullCand) * total, hipMemcpyHostToDevice, o->strm));
-    hipLaunchKernelGGL(k_cull_counts, dim3((unsigned)total), dim3(64), 0, o->strm, (const CullCand*)(o->mir.d.bytes() + oC), o->d_rec_chunk.as<uint8_t*>(), o->d_pt_aux.as<uint8_t*>(),
-                       mirror_geom(o), (int32_t*)(o->mir.d.bytes() + oOut));
+    OSLAM_CHECK(o->sync_mirror_tables());
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(fC, Dv), cc, fC.bytes, hipMemcpyHostToDevice, o->strm));
+    hipLaunchKernelGGL(k_cull_counts, dim3((unsigned)total), dim3(64), 0, o->strm, at(fC, Dv), o->d_rec_chunk.as<uint8_t*>(), o->pt_aux.device_table(), mirror_geom(o), at(fOut, Dv));
     OSLAM_HIP_CHECK(hipGetLastError());
-    OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->cull.bytes(), o->mir.d.bytes() + oOut, 16 * total, o->strm));
+    OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->cull.bytes(), at(fOut, Dv), fOut.bytes, o->strm));
     o->mir_used = end;
     return OSLAM_OK;   // (results: h_kf_culling_collect)
 }
@@ -1669,8 +1679,8 @@ int h_kf_culling_collect(void* p) {
     OSLAM_HIP_CHECK(hipSetDevice(o->cfg.device));
     if (o->cull_pending.empty()) { o->mir_used = 0; return OSLAM_OK; }
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));   // (usually already drained: the MapPoint-update operator between request and collection synchronises the same stream)
-    size_t at = 0;
-    for (const HipOps::CullPending& c : o->cull_pending) { memcpy(c.out, o->cull.bytes() + 16 * at, 16 * (size_t)c.n); at += (size_t)c.n; }
+    size_t k = 0;
+    for (const HipOps::CullPending& c : o->cull_pending) { copy_elems(c.out, o->cull.as<int32_t>() + 4 * k, 4 * (size_t)c.n); k += (size_t)c.n; }
     o->cull_pending.clear();
     o->mir_used = 0;
     return OSLAM_OK;
@@ -1783,73 +1793,73 @@ int h_fuse_into_current(void* p, int n, oslam_job_fuse_cur_t* jobs) {
         nrec += (size_t)j.n_targets; maxT = std::max(maxT, j.n_targets);
     }
     if (o->cap > 0xFFFF) { oslam::set_error("fuse_into_current: more than 65535 keypoints per keyframe"); return OSLAM_E_CAPACITY; }
-    OPS_CHECK(o->sync_mp_table());
-    o->size_pt_aux();
-    for (int i = 0; i < n; i++) if (!o->pt_aux[jobs[i].slot]) OPS_CHECK(o->ensure_pt_aux(jobs[i].slot, 1));
-    OPS_CHECK(o->sync_mirror_tables());
+    OSLAM_CHECK(o->mp_tab.sync(o->strm));
+    for (int i = 0; i < n; i++) OSLAM_CHECK(o->pt_aux.ensure(jobs[i].slot, 1, o->strm));
+    OSLAM_CHECK(o->sync_mirror_tables());
     // job block (pinned, read in place) | device scratch: candidate ids, flags, match table, counts
     const size_t B = n;
-    Layout L;
-    const size_t oJ = L.take(sizeof(FuseCurJob) * B), oR = L.take(4 * std::max<size_t>(nrec, 1)), oSl = L.take(4 * B), oT = L.take(64 * B), oOw = L.take(12 * B), oRef = L.take(sizeof(oslam_kf_grid_ref_t) * B);
-    OPS_CHECK(o->ensure_up(L.off));
-    const size_t sIds = 0, sEx = oslam::align_up(sIds + 4 * (size_t)stride * B, 256), sQm = oslam::align_up(sEx + (size_t)stride * B, 256), sM = oslam::align_up(sQm + 4 * (size_t)stride * B, 256),
-                 sM1 = oslam::align_up(sM + 8 * B, 256), sEnd = sM1 + 4 * B;
-    if (sEnd > o->fc.cap()) OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
-    OPS_CHECK(o->fc.grow(sEnd, 0));
-    Layout R;
-    const size_t rCnt = R.take(12 * B), rPairs = R.take(8 * (size_t)maxPairs * B);
+    StageLayout L;
+    const auto fJ = L.add<FuseCurJob>(B); const auto fR = L.add<int32_t>(nrec), fSl = L.add<int32_t>(B); const auto fT = L.add<float>(16 * B), fOw = L.add<float>(3 * B);
+    const auto fRef = L.add<oslam_kf_grid_ref_t>(B);
+    OSLAM_CHECK(o->ensure_up(L.total()));
+    StageLayout Sc;   // the scratch block
+    const auto sIds = Sc.add<int32_t>((size_t)stride * B); const auto sEx = Sc.add<uint8_t>((size_t)stride * B);
+    const auto sQm = Sc.add<int32_t>((size_t)stride * B), sM = Sc.add<int32_t>(2 * B), sM1 = Sc.add<int32_t>(B);
+    if (Sc.total() > o->fc.cap()) OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
+    OSLAM_CHECK(o->fc.grow(Sc.total(), 0));
     bool dbg = false;
     for (int i = 0; i < n; i++) dbg = dbg || (jobs[i].dbg_cap > 0 && jobs[i].dbg_ids && jobs[i].dbg_excl);
-    const size_t rIds = R.take(dbg ? 4 * (size_t)stride * B : 0), rEx = R.take(dbg ? (size_t)stride * B : 0);
-    OPS_CHECK(o->ensure_dn(R.off));
+    StageLayout R;
+    const auto rCnt = R.add<int32_t>(3 * B), rPairs = R.add<int32_t>(2 * (size_t)maxPairs * B), rIds = R.add<int32_t>((size_t)stride * B, dbg);
+    const auto rEx = R.add<uint8_t>((size_t)stride * B, dbg);
+    OSLAM_CHECK(o->ensure_dn(R.total()));
     uint8_t* U = o->up.h.bytes();
-    FuseCurJob* fj = (FuseCurJob*)(U + oJ);
-    int32_t* recs = (int32_t*)(U + oR);
-    size_t at = 0;
+    FuseCurJob* fj = at(fJ, U);
+    int32_t* recs = at(fR, U);
+    size_t nr = 0;
     for (int i = 0; i < n; i++) {
         const oslam_job_fuse_cur_t& j = jobs[i];
         const int cr = o->rec_lookup(j.slot, j.kf);
         if (cr < 0) { oslam::set_error("fuse_into_current: the current keyframe is not resident"); return OSLAM_E_INVALID; }
-        fj[i].slot = j.slot; fj[i].cur_rec = cr; fj[i].nT = j.n_targets; fj[i].t_off = (int32_t)at;
-        for (int t = 0; t < j.n_targets; t++) recs[at++] = o->rec_lookup(j.slot, j.targets[t]);   // (-1: not resident — cannot happen for a keyframe of the map; skipped)
-        ((int32_t*)(U + oSl))[i] = j.slot;
-        memcpy(U + oT + 64 * i, j.Tcw, 64); memcpy(U + oOw + 12 * i, j.Ow, 12);
-        oslam_kf_grid_ref_t& ref = ((oslam_kf_grid_ref_t*)(U + oRef))[i];
+        fj[i].slot = j.slot; fj[i].cur_rec = cr; fj[i].nT = j.n_targets; fj[i].t_off = (int32_t)nr;
+        for (int t = 0; t < j.n_targets; t++) recs[nr++] = o->rec_lookup(j.slot, j.targets[t]);   // (-1: not resident — cannot happen for a keyframe of the map; skipped)
+        at(fSl, U)[i] = j.slot;
+        copy_elems(row(fT, U, 16, i), j.Tcw, 16); copy_elems(row(fOw, U, 3, i), j.Ow, 3);
+        oslam_kf_grid_ref_t& ref = at(fRef, U)[i];
         ref.cell_end = o->rec_cell_end(cr); ref.cand = o->rec_cand(cr); ref.desc = o->rec_desc(cr);
     }
     const uint32_t stamp = ++o->fc_stamp;
     const MirrorGeom g = mirror_geom(o);
-    uint8_t* D = o->fc.bytes();
+    uint8_t *Dc = o->fc.bytes(), *D = o->dn.bytes();
     o->t_begin();
-    hipLaunchKernelGGL(k_fusecur_mark, dim3((unsigned)((g.cap + 255) / 256), (unsigned)(maxT + 1), (unsigned)n), dim3(256), 0, o->strm, (const FuseCurJob*)(U + oJ), (const int32_t*)(U + oR),
-                       o->d_rec_chunk.as<uint8_t*>(), o->d_pt_aux.as<uint8_t*>(), g, stamp);
-    hipLaunchKernelGGL(k_fusecur_list, dim3((unsigned)n), dim3(1024), 0, o->strm, (const FuseCurJob*)(U + oJ), (const int32_t*)(U + oR), o->d_rec_chunk.as<uint8_t*>(),
-                       o->d_pt_aux.as<uint8_t*>(), g, stamp, stride, (int32_t*)(D + sIds), D + sEx, (int32_t*)(D + sM));
+    // (the job block is pinned and read in place: the kernels get pointers into U)
+    hipLaunchKernelGGL(k_fusecur_mark, dim3((unsigned)((g.cap + 255) / 256), (unsigned)(maxT + 1), (unsigned)n), dim3(256), 0, o->strm, at(fJ, U), at(fR, U), o->d_rec_chunk.as<uint8_t*>(),
+                       o->pt_aux.device_table(), g, stamp);
+    hipLaunchKernelGGL(k_fusecur_list, dim3((unsigned)n), dim3(1024), 0, o->strm, at(fJ, U), at(fR, U), o->d_rec_chunk.as<uint8_t*>(), o->pt_aux.device_table(), g, stamp, stride, at(sIds, Dc),
+                       at(sEx, Dc), at(sM, Dc));
     OSLAM_HIP_CHECK(hipGetLastError());
     // (k_fuse_search reads M at d_M[b]; the list kernel's table holds [M, overflow] pairs: the search gets a compacted copy)
-    hipLaunchKernelGGL(k_fusecur_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o->strm, (const int32_t*)(D + sM), n, (int32_t*)(D + sM1));
-    OPS_CHECK(oslam_fuse_search_device(n, stride, (const oslam_kf_grid_ref_t*)(U + oRef), (const int32_t*)(U + oSl), (const int32_t*)(D + sM1), (const int32_t*)(D + sIds), D + sEx,
-                                       o->d_mp_tab.as<uint8_t*>(), (const float*)(U + oT), (const float*)(U + oOw), o->K5, o->bounds, jobs[0].th, o->logScale, o->scale, o->invSigma2, o->cfg.nLevels,
-                                       (int32_t*)(D + sQm), o->strm));
-    hipLaunchKernelGGL(k_fusecur_pairs, dim3((unsigned)n), dim3(1024), 0, o->strm, (const int32_t*)(D + sM), (const int32_t*)(D + sIds), (const int32_t*)(D + sQm), stride, maxPairs,
-                       (int32_t*)(o->dn.bytes() + rPairs), (int32_t*)(o->dn.bytes() + rCnt));
+    hipLaunchKernelGGL(k_fusecur_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o->strm, at(sM, Dc), n, at(sM1, Dc));
+    OSLAM_CHECK(oslam_fuse_search_device(n, stride, at(fRef, U), at(fSl, U), at(sM1, Dc), at(sIds, Dc), at(sEx, Dc), o->mp_tab.device_table(), at(fT, U), at(fOw, U), o->K5, o->bounds, jobs[0].th,
+                                         o->logScale, o->scale, o->invSigma2, o->cfg.nLevels, at(sQm, Dc), o->strm));
+    hipLaunchKernelGGL(k_fusecur_pairs, dim3((unsigned)n), dim3(1024), 0, o->strm, at(sM, Dc), at(sIds, Dc), at(sQm, Dc), stride, maxPairs, at(rPairs, D), at(rCnt, D));
     OSLAM_HIP_CHECK(hipGetLastError());
     if (dbg) {
-        OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn.bytes() + rIds, D + sIds, 4 * (size_t)stride * B, o->strm));
-        OSLAM_HIP_CHECK(oslam::copy_to_host_async(o->dn.bytes() + rEx, D + sEx, (size_t)stride * B, o->strm));
+        OSLAM_HIP_CHECK(oslam::copy_to_host_async(at(rIds, D), at(sIds, Dc), rIds.bytes, o->strm));
+        OSLAM_HIP_CHECK(oslam::copy_to_host_async(at(rEx, D), at(sEx, Dc), rEx.bytes, o->strm));
     }
     o->t_end();
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(4, 4, 0);
-    const int32_t* cnt = (const int32_t*)(o->dn.bytes() + rCnt);
+    const int32_t* cnt = at(rCnt, D);
     for (int i = 0; i < n; i++) {
         oslam_job_fuse_cur_t& j = jobs[i];
         j.n_pairs = cnt[3 * i]; j.n_candidates = cnt[3 * i + 1]; j.overflow = (cnt[3 * i + 2] != 0 || j.n_pairs > maxPairs || j.n_pairs > j.max_pairs) ? 1 : 0;
-        if (!j.overflow) memcpy(j.pairs, o->dn.bytes() + rPairs + 8 * (size_t)maxPairs * i, 8 * (size_t)j.n_pairs);
+        if (!j.overflow) copy_elems(j.pairs, row(rPairs, D, 2 * (size_t)maxPairs, i), 2 * (size_t)j.n_pairs);
         if (j.dbg_cap > 0 && j.dbg_ids && j.dbg_excl) {
             const int m = std::min(j.n_candidates, j.dbg_cap);
-            memcpy(j.dbg_ids, o->dn.bytes() + rIds + 4 * (size_t)stride * i, 4 * (size_t)m);
-            memcpy(j.dbg_excl, o->dn.bytes() + rEx + (size_t)stride * i, (size_t)m);
+            copy_elems(j.dbg_ids, row(rIds, D, stride, i), (size_t)m);
+            copy_elems(j.dbg_excl, row(rEx, D, stride, i), (size_t)m);
         }
     }
     return OSLAM_OK;
@@ -1871,44 +1881,44 @@ int h_local_points_list(void* p, int n, oslam_job_local_list_t* jobs) {
         nrec += (size_t)j.n_kfs; maxT = std::max(maxT, j.n_kfs);
     }
     if (o->cap > 0xFFFF) { oslam::set_error("local_points_list: more than 65535 keypoints per keyframe"); return OSLAM_E_CAPACITY; }
-    o->size_pt_aux();
-    for (int i = 0; i < n; i++) if (!o->pt_aux[jobs[i].slot]) OPS_CHECK(o->ensure_pt_aux(jobs[i].slot, 1));
-    OPS_CHECK(o->sync_mirror_tables());
+    for (int i = 0; i < n; i++) OSLAM_CHECK(o->pt_aux.ensure(jobs[i].slot, 1, o->strm));
+    OSLAM_CHECK(o->sync_mirror_tables());
     const size_t B = n;
-    Layout L;
-    const size_t oJ = L.take(sizeof(FuseCurJob) * B), oR = L.take(4 * std::max<size_t>(nrec, 1));
-    OPS_CHECK(o->ensure_up(L.off));
-    const size_t sEx = 0, sEnd = (size_t)stride * B;
-    if (sEnd > o->fc.cap()) OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
-    OPS_CHECK(o->fc.grow(sEnd, 0));
-    Layout R;
-    const size_t rM = R.take(8 * B), rIds = R.take(4 * (size_t)stride * B);
-    OPS_CHECK(o->ensure_dn(R.off));
-    uint8_t* U = o->up.h.bytes();
-    FuseCurJob* fj = (FuseCurJob*)(U + oJ);
-    int32_t* recs = (int32_t*)(U + oR);
-    size_t at = 0;
+    StageLayout L;
+    const auto fJ = L.add<FuseCurJob>(B); const auto fR = L.add<int32_t>(nrec);
+    OSLAM_CHECK(o->ensure_up(L.total()));
+    StageLayout Sc;   // the scratch block: the "already observed" flags nobody reads here
+    const auto sEx = Sc.add<uint8_t>((size_t)stride * B);
+    if (Sc.total() > o->fc.cap()) OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
+    OSLAM_CHECK(o->fc.grow(Sc.total(), 0));
+    StageLayout R;
+    const auto rM = R.add<int32_t>(2 * B), rIds = R.add<int32_t>((size_t)stride * B);
+    OSLAM_CHECK(o->ensure_dn(R.total()));
+    uint8_t *U = o->up.h.bytes(), *D = o->dn.bytes();
+    FuseCurJob* fj = at(fJ, U);
+    int32_t* recs = at(fR, U);
+    size_t nr = 0;
     for (int i = 0; i < n; i++) {
         const oslam_job_local_list_t& j = jobs[i];
-        fj[i].slot = j.slot; fj[i].cur_rec = -1; fj[i].nT = j.n_kfs; fj[i].t_off = (int32_t)at;
-        for (int t = 0; t < j.n_kfs; t++) recs[at++] = o->rec_lookup(j.slot, j.kfs[t]);
+        fj[i].slot = j.slot; fj[i].cur_rec = -1; fj[i].nT = j.n_kfs; fj[i].t_off = (int32_t)nr;
+        for (int t = 0; t < j.n_kfs; t++) recs[nr++] = o->rec_lookup(j.slot, j.kfs[t]);
     }
     const uint32_t stamp = ++o->fc_stamp;
     const MirrorGeom g = mirror_geom(o);
     o->t_begin();
-    hipLaunchKernelGGL(k_fusecur_mark, dim3((unsigned)((g.cap + 255) / 256), (unsigned)(maxT + 1), (unsigned)n), dim3(256), 0, o->strm, (const FuseCurJob*)(U + oJ), (const int32_t*)(U + oR),
-                       o->d_rec_chunk.as<uint8_t*>(), o->d_pt_aux.as<uint8_t*>(), g, stamp);
-    hipLaunchKernelGGL(k_fusecur_list, dim3((unsigned)n), dim3(1024), 0, o->strm, (const FuseCurJob*)(U + oJ), (const int32_t*)(U + oR), o->d_rec_chunk.as<uint8_t*>(),
-                       o->d_pt_aux.as<uint8_t*>(), g, stamp, stride, (int32_t*)(o->dn.bytes() + rIds), o->fc.bytes() + sEx, (int32_t*)(o->dn.bytes() + rM));
+    hipLaunchKernelGGL(k_fusecur_mark, dim3((unsigned)((g.cap + 255) / 256), (unsigned)(maxT + 1), (unsigned)n), dim3(256), 0, o->strm, at(fJ, U), at(fR, U), o->d_rec_chunk.as<uint8_t*>(),
+                       o->pt_aux.device_table(), g, stamp);
+    hipLaunchKernelGGL(k_fusecur_list, dim3((unsigned)n), dim3(1024), 0, o->strm, at(fJ, U), at(fR, U), o->d_rec_chunk.as<uint8_t*>(), o->pt_aux.device_table(), g, stamp, stride, at(rIds, D),
+                       at(sEx, o->fc.bytes()), at(rM, D));
     OSLAM_HIP_CHECK(hipGetLastError());
     o->t_end();
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(3, 2, 0);
-    const int32_t* Mn = (const int32_t*)(o->dn.bytes() + rM);
+    const int32_t* Mn = at(rM, D);
     for (int i = 0; i < n; i++) {
         oslam_job_local_list_t& j = jobs[i];
         j.n_ids = Mn[2 * i]; j.overflow = (Mn[2 * i + 1] != 0 || j.n_ids > j.cap) ? 1 : 0;
-        if (!j.overflow) memcpy(j.ids, o->dn.bytes() + rIds + 4 * (size_t)stride * i, 4 * (size_t)j.n_ids);
+        if (!j.overflow) copy_elems(j.ids, row(rIds, D, stride, i), (size_t)j.n_ids);
     }
     return OSLAM_OK;
 }
@@ -1918,74 +1928,51 @@ int h_resident_points(void* p) { return ((HipOps*)p)->mp_tab_on ? 1 : 0; }
 int h_point_record(void* p, int slot, int id, uint8_t out[64]) {
     HipOps* o = (HipOps*)p;
     OSLAM_HIP_CHECK(hipSetDevice(o->cfg.device));
-    if (slot < 0 || slot >= (int)o->mp_tab.size() || id < 0 || (size_t)id >= o->mp_cap[slot]) { oslam::set_error("point_record: no such record"); return OSLAM_E_INVALID; }
+    if (slot < 0 || slot >= o->S || id < 0 || (size_t)id >= o->mp_tab.capacity(slot)) { oslam::set_error("point_record: no such record"); return OSLAM_E_INVALID; }
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
-    OSLAM_HIP_CHECK(hipMemcpy(out, o->mp_tab[slot] + (size_t)id * 64, 64, hipMemcpyDeviceToHost));
+    OSLAM_HIP_CHECK(hipMemcpy(out, o->mp_tab.block(slot) + (size_t)id * 64, 64, hipMemcpyDeviceToHost));
     return OSLAM_OK;
 }
 
-// KeyFrame::ComputeBoW node assignment of registered keyframes from their resident descriptors (see oslam_slam_ops_t::bow_nodes_keyed)
+// KeyFrame::ComputeBoW node assignment of registered keyframes from their resident descriptors (see oslam_slam_ops_t::bow_nodes_keyed), and the same for a
+// loaded vocabulary (oslam_slam_ops_t::voc_nodes_keyed: oslam_voc_transform_device over the resident descriptors, node ids only).  One staging block serves
+// both: the generated tree's words (top, sub) travel with the job, a loaded vocabulary is on the device already.
+static int nodes_keyed_impl(HipOps* o, const char* who, const oslam_voc_t* voc, int levelsup, const uint64_t* top, const uint64_t* sub, int n, const int32_t* slots, const int32_t* kf_ids,
+                            const int32_t* counts, uint32_t* const* out) {
+    OSLAM_HIP_CHECK(hipSetDevice(o->cfg.device));
+    if (n == 0) return OSLAM_OK;
+    const size_t cap = o->cap;
+    StageLayout L, R;
+    const auto fPtr = L.add<const uint8_t*>(n); const auto fCnt = L.add<int32_t>(n);
+    const auto fTop = L.add<uint64_t>(10 * 4, !voc), fSub = L.add<uint64_t>(10 * 10 * 4, !voc);   // top[10][4], sub[10][10][4]: 256-bit centres
+    const size_t in_bytes = L.total();   // the result array behind this does not travel
+    const auto fOut = L.add<uint32_t>(cap * (size_t)n), rOut = R.add<uint32_t>(cap * (size_t)n);
+    OSLAM_CHECK(o->ensure_up(L.total()));
+    OSLAM_CHECK(o->ensure_dn(R.total()));
+    uint8_t *U = o->up.h.bytes(), *Dv = o->up.d.bytes(), *D = o->dn.bytes();
+    for (int i = 0; i < n; i++) {
+        const int r = o->rec_lookup(slots[i], kf_ids[i]);
+        if (r < 0 || counts[i] < 0 || counts[i] > (int)cap) { oslam::set_error("%s: keyframe not resident / bad count", who); return OSLAM_E_INVALID; }
+        at(fPtr, U)[i] = o->rec_desc(r);
+        at(fCnt, U)[i] = counts[i];
+    }
+    put(fTop, U, top); put(fSub, U, sub);
+    OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, in_bytes, hipMemcpyHostToDevice, o->strm));
+    o->t_begin();
+    if (voc) OSLAM_CHECK(oslam_voc_transform_device(voc, at(fPtr, Dv), at(fCnt, Dv), n, (int)cap, levelsup, nullptr, at(fOut, Dv), nullptr, o->strm));
+    else OSLAM_CHECK(oslam_bow_nodes_device(at(fPtr, Dv), at(fCnt, Dv), n, (int)cap, at(fTop, Dv), at(fSub, Dv), at(fOut, Dv), o->strm));
+    o->t_end();
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rOut, D), at(fOut, Dv), rOut.bytes, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
+    o->t_collect(7, 1, 0);
+    o->pool->parallel_for(n, [&](int i) { copy_elems(out[i], row(rOut, D, cap, i), (size_t)counts[i]); });
+    return OSLAM_OK;
+}
 int h_bow_nodes_keyed(void* p, int n, const int32_t* slots, const int32_t* kf_ids, const uint64_t* top, const uint64_t* sub, const int32_t* counts, uint32_t* const* out) {
-    HipOps* o = (HipOps*)p;
-    OSLAM_HIP_CHECK(hipSetDevice(o->cfg.device));
-    if (n == 0) return OSLAM_OK;
-    const size_t cap = o->cap;
-    Layout L;
-    const size_t oPtr = L.take(8 * (size_t)n), oCnt = L.take(4 * (size_t)n), oTop = L.take(320), oSub = L.take(3200);
-    const size_t in_bytes = L.off;
-    const size_t oOut = L.take(4 * cap * (size_t)n);
-    OPS_CHECK(o->ensure_up(L.off));
-    OPS_CHECK(o->ensure_dn(4 * cap * (size_t)n));
-    uint8_t* U = o->up.h.bytes();
-    for (int i = 0; i < n; i++) {
-        const int r = o->rec_lookup(slots[i], kf_ids[i]);
-        if (r < 0 || counts[i] < 0 || counts[i] > (int)cap) { oslam::set_error("bow_nodes: keyframe not resident / bad count"); return OSLAM_E_INVALID; }
-        ((const uint8_t**)(U + oPtr))[i] = o->rec_desc(r);
-        ((int32_t*)(U + oCnt))[i] = counts[i];
-    }
-    memcpy(U + oTop, top, 320); memcpy(U + oSub, sub, 3200);
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), U, in_bytes, hipMemcpyHostToDevice, o->strm));
-    uint8_t* Dv = o->up.d.bytes();
-    o->t_begin();
-    OPS_CHECK(oslam_bow_nodes_device((const uint8_t* const*)(Dv + oPtr), (const int32_t*)(Dv + oCnt), n, (int)cap, (const uint64_t*)(Dv + oTop), (const uint64_t*)(Dv + oSub),
-                                     (uint32_t*)(Dv + oOut), o->strm));
-    o->t_end();
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes(), Dv + oOut, 4 * cap * (size_t)n, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
-    o->t_collect(7, 1, 0);
-    o->pool->parallel_for(n, [&](int i) { memcpy(out[i], o->dn.bytes() + 4 * cap * (size_t)i, 4 * (size_t)counts[i]); });
-    return OSLAM_OK;
+    return nodes_keyed_impl((HipOps*)p, "bow_nodes", nullptr, 0, top, sub, n, slots, kf_ids, counts, out);
 }
-
-// The same for a loaded vocabulary (oslam_slam_ops_t::voc_nodes_keyed): oslam_voc_transform_device over the resident descriptors, node ids only
 int h_voc_nodes_keyed(void* p, const oslam_voc_t* voc, int levelsup, int n, const int32_t* slots, const int32_t* kf_ids, const int32_t* counts, uint32_t* const* out) {
-    HipOps* o = (HipOps*)p;
-    OSLAM_HIP_CHECK(hipSetDevice(o->cfg.device));
-    if (n == 0) return OSLAM_OK;
-    const size_t cap = o->cap;
-    Layout L;
-    const size_t oPtr = L.take(8 * (size_t)n), oCnt = L.take(4 * (size_t)n);
-    const size_t in_bytes = L.off;
-    const size_t oOut = L.take(4 * cap * (size_t)n);
-    OPS_CHECK(o->ensure_up(L.off));
-    OPS_CHECK(o->ensure_dn(4 * cap * (size_t)n));
-    uint8_t* U = o->up.h.bytes();
-    for (int i = 0; i < n; i++) {
-        const int r = o->rec_lookup(slots[i], kf_ids[i]);
-        if (r < 0 || counts[i] < 0 || counts[i] > (int)cap) { oslam::set_error("voc_nodes: keyframe not resident / bad count"); return OSLAM_E_INVALID; }
-        ((const uint8_t**)(U + oPtr))[i] = o->rec_desc(r);
-        ((int32_t*)(U + oCnt))[i] = counts[i];
-    }
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->up.d.bytes(), U, in_bytes, hipMemcpyHostToDevice, o->strm));
-    uint8_t* Dv = o->up.d.bytes();
-    o->t_begin();
-    OPS_CHECK(oslam_voc_transform_device(voc, (const uint8_t* const*)(Dv + oPtr), (const int32_t*)(Dv + oCnt), n, (int)cap, levelsup, nullptr, (uint32_t*)(Dv + oOut), nullptr, o->strm));
-    o->t_end();
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes(), Dv + oOut, 4 * cap * (size_t)n, hipMemcpyDeviceToHost, o->strm));
-    OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
-    o->t_collect(7, 1, 0);
-    o->pool->parallel_for(n, [&](int i) { memcpy(out[i], o->dn.bytes() + 4 * cap * (size_t)i, 4 * (size_t)counts[i]); });
-    return OSLAM_OK;
+    return nodes_keyed_impl((HipOps*)p, "voc_nodes", voc, levelsup, nullptr, nullptr, n, slots, kf_ids, counts, out);
 }
 
 int h_bow_keyed(void* p, int n, oslam_job_bow_t* jobs, const oslam_kf_key_t* keys) {
@@ -2013,15 +2000,15 @@ int h_kernel_times(void* p, int enable, double* out) {
     if (enable && !o->tev0) { OSLAM_HIP_CHECK(hipEventCreate(&o->tev0)); OSLAM_HIP_CHECK(hipEventCreate(&o->tev1)); OSLAM_HIP_CHECK(hipEventCreate(&o->tevB0)); OSLAM_HIP_CHECK(hipEventCreate(&o->tevB1)); }
     {   // the BoW matchers and the triangulation run on their handles' own streams
         double ms = 0; long long ln = 0;
-        OPS_CHECK(oslam_bow_kernel_time(o->bow, enable, &ms, &ln));
+        OSLAM_CHECK(oslam_bow_kernel_time(o->bow, enable, &ms, &ln));
         o->kt[15] += ms; o->kt[16] += (double)ln;
-        OPS_CHECK(oslam_mappoint_kernel_time(o->mp, enable, &ms, &ln));
+        OSLAM_CHECK(oslam_mappoint_kernel_time(o->mp, enable, &ms, &ln));
         o->kt[15] += ms; o->kt[16] += (double)ln;
     }
     if (out) memcpy(out, o->kt, sizeof(o->kt));
     memset(o->kt, 0, sizeof(o->kt));
     o->timing = enable;
-    OPS_CHECK(oslam_lba_kernel_time(o->ba1, enable, nullptr, nullptr));
+    OSLAM_CHECK(oslam_lba_kernel_time(o->ba1, enable, nullptr, nullptr));
     return OSLAM_OK;
 }
 
@@ -2045,55 +2032,57 @@ static int fuse_impl(HipOps* o, int n, oslam_job_fuse_t* jobs, const oslam_kf_ke
         oslam_matcher_destroy(o->m_map);
         o->m_map = nullptr;
         o->max_local = (int)oslam::align_up((size_t)maxM + maxM / 2, 64);
-        OPS_CHECK(oslam_matcher_create(&o->m_map, o->S, o->cap, o->max_local, o->cfg.device));
+        OSLAM_CHECK(oslam_matcher_create(&o->m_map, o->S, o->cap, o->max_local, o->cfg.device));
     }
     const size_t st = oslam::align_up((size_t)maxM, 64);
-    Layout L;
+    StageLayout L;
     // upload block: counts, queries, the segment table of the resident keyframes, and (last, so that a fully resident batch does not ship them) the
     // keypoint / stereo / descriptor arrays of the keyframes that are not resident
-    const size_t oN = L.take(4 * B), oM = L.take(4 * B), oQ = L.take(sizeof(oslam_proj_query_t) * st * B), oSeg = L.take(sizeof(CopySegH) * 3 * B);
-    const size_t small_bytes = L.off;
-    const size_t oKeys = L.take(sizeof(oslam_keypoint_t) * cap * B), oUr = L.take(4 * cap * B), oDesc = L.take(32 * cap * B);
-    OPS_CHECK(o->ensure_up(L.off));
-    uint8_t* U = o->up.h.bytes();
-    uint8_t* Dv = o->up.d.bytes();
+    const auto fN = L.add<int32_t>(B), fM = L.add<int32_t>(B); const auto fQ = L.add<oslam_proj_query_t>(st * B); const auto fSeg = L.add<CopySegH>(3 * B);
+    const size_t small_bytes = L.total();
+    const auto fKeys = L.add<oslam_keypoint_t>(cap * B); const auto fUr = L.add<float>(cap * B); const auto fDesc = L.add<uint8_t>(32 * cap * B);
+    OSLAM_CHECK(o->ensure_up(L.total()));
+    uint8_t *U = o->up.h.bytes(), *Dv = o->up.d.bytes();
     std::vector<int> rec(n, -1);
     int nres = 0;
     if (keys) for (int i = 0; i < n; i++) { rec[i] = o->rec_lookup(keys[i].slot, keys[i].kf1); nres += rec[i] >= 0; }
-    CopySegH* segs = (CopySegH*)(U + oSeg);
+    CopySegH* segs = at(fSeg, U);
     for (int i = 0, q = 0; i < n; i++)
-        if (rec[i] >= 0) {
+        if (rec[i] >= 0) {   // device-to-device, into the rows the upload leaves alone
             const size_t N = jobs[i].N;
-            segs[q++] = {(const uint8_t*)o->rec_keys(rec[i]), Dv + oKeys + sizeof(oslam_keypoint_t) * cap * i, (uint32_t)(sizeof(oslam_keypoint_t) * N), 0};
-            segs[q++] = {(const uint8_t*)o->rec_ur(rec[i]), Dv + oUr + 4 * cap * i, (uint32_t)(4 * N), 0};
-            segs[q++] = {o->rec_desc(rec[i]), Dv + oDesc + 32 * cap * i, (uint32_t)(32 * N), 0};
+            segs[q++] = {(const uint8_t*)o->rec_keys(rec[i]), (uint8_t*)row(fKeys, Dv, cap, i), (uint32_t)(N * sizeof(oslam_keypoint_t)), 0};
+            segs[q++] = {(const uint8_t*)o->rec_ur(rec[i]), (uint8_t*)row(fUr, Dv, cap, i), (uint32_t)(N * sizeof(float)), 0};
+            segs[q++] = {o->rec_desc(rec[i]), row(fDesc, Dv, 32 * cap, i), (uint32_t)(32 * N), 0};
         }
     o->pool->parallel_for(n, [&](int i) {
         const oslam_job_fuse_t& j = jobs[i];
         const size_t N = j.N, M = j.M;
-        ((int32_t*)(U + oN))[i] = j.N; ((int32_t*)(U + oM))[i] = j.M;
+        at(fN, U)[i] = j.N; at(fM, U)[i] = j.M;
         if (rec[i] < 0) {
-            memcpy(U + oKeys + sizeof(oslam_keypoint_t) * cap * i, j.keysUn, sizeof(oslam_keypoint_t) * N);
-            memcpy(U + oUr + 4 * cap * i, j.uRight, 4 * N); memcpy(U + oDesc + 32 * cap * i, j.desc, 32 * N);
+            copy_elems(row(fKeys, U, cap, i), j.keysUn, N);
+            copy_elems(row(fUr, U, cap, i), j.uRight, N); copy_elems(row(fDesc, U, 32 * cap, i), j.desc, 32 * N);
         }
-        memcpy(U + oQ + sizeof(oslam_proj_query_t) * st * i, j.queries, sizeof(oslam_proj_query_t) * M);
+        copy_elems(row(fQ, U, st, i), j.queries, M);
     });
-    OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, nres == n ? small_bytes : L.off, hipMemcpyHostToDevice, o->strm));
+    OSLAM_HIP_CHECK(hipMemcpyAsync(Dv, U, nres == n ? small_bytes : L.total(), hipMemcpyHostToDevice, o->strm));
     o->t_begin();
-    if (nres) OPS_CHECK(oslam_copy_segments_device(Dv + oSeg, 3 * nres, o->strm));
+    if (nres) OSLAM_CHECK(oslam_copy_segments_device(at(fSeg, Dv), 3 * nres, o->strm));
     oslam_match_frames_t fr;
-    fr.keysUn = (const oslam_keypoint_t*)(Dv + oKeys); fr.kp_stride = (int)cap; fr.uRight = (const float*)(Dv + oUr); fr.desc = Dv + oDesc; fr.blocked = nullptr;
-    fr.n_kps = (const int32_t*)(Dv + oN); fr.n_kps_const = 0;
+    fr.keysUn = at(fKeys, Dv); fr.kp_stride = (int)cap; fr.uRight = at(fUr, Dv); fr.desc = at(fDesc, Dv); fr.blocked = nullptr;
+    fr.n_kps = at(fN, Dv); fr.n_kps_const = 0;
     fr.minX = o->bounds[0]; fr.minY = o->bounds[1]; fr.maxX = o->bounds[2]; fr.maxY = o->bounds[3];
-    OPS_CHECK(oslam_match_fuse_batch_device(o->m_map, &fr, (const oslam_proj_query_t*)(Dv + oQ), (int)st, (const int32_t*)(Dv + oM), 0, n, o->invSigma2, o->cfg.nLevels, o->strm));
+    OSLAM_CHECK(oslam_match_fuse_batch_device(o->m_map, &fr, at(fQ, Dv), (int)st, at(fM, Dv), 0, n, o->invSigma2, o->cfg.nLevels, o->strm));
     o->t_end();
     const int32_t* d_qm;
-    OPS_CHECK(oslam_match_results_device(o->m_map, &d_qm, nullptr, nullptr, nullptr, nullptr, nullptr));
-    OPS_CHECK(o->ensure_dn(4 * st * B));
-    OSLAM_HIP_CHECK(hipMemcpyAsync(o->dn.bytes(), d_qm, 4 * st * B, hipMemcpyDeviceToHost, o->strm));
+    OSLAM_CHECK(oslam_match_results_device(o->m_map, &d_qm, nullptr, nullptr, nullptr, nullptr, nullptr));
+    StageLayout R;
+    const auto rQm = R.add<int32_t>(st * B);
+    OSLAM_CHECK(o->ensure_dn(R.total()));
+    uint8_t* D = o->dn.bytes();
+    OSLAM_HIP_CHECK(hipMemcpyAsync(at(rQm, D), d_qm, rQm.bytes, hipMemcpyDeviceToHost, o->strm));
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(4, 2, 0);
-    o->pool->parallel_for(n, [&](int i) { memcpy(jobs[i].q_match, o->dn.bytes() + 4 * st * i, 4 * (size_t)jobs[i].M); });
+    o->pool->parallel_for(n, [&](int i) { copy_elems(jobs[i].q_match, row(rQm, D, st, i), (size_t)jobs[i].M); });
     return OSLAM_OK;
 }
 
@@ -2112,36 +2101,37 @@ int h_fuse_points_keyed(void* p, int n, oslam_job_fuse_pts_t* jobs) {
         if (rec[i] < 0 || jobs[i].M < 0 || jobs[i].N < 0 || jobs[i].N > (int)cap) { oslam::set_error("fuse_points: keyframe not resident / bad size"); return OSLAM_E_INVALID; }
         maxM = std::max(maxM, jobs[i].M);
     }
-    OPS_CHECK(o->mpu_launch_pending());   // (the previous round's descriptor updates, if they were deferred: in front of this search, behind one wait)
+    OSLAM_CHECK(o->mpu_launch_pending());   // (the previous round's descriptor updates, if they were deferred: in front of this search, behind one wait)
     // gates + window search of every candidate in ONE launch, straight from the resident records and their grids (oslam_fuse_search_device)
-    OPS_CHECK(o->sync_mp_table());
+    OSLAM_CHECK(o->mp_tab.sync(o->strm));
     const size_t st = oslam::align_up((size_t)maxM, 64);
-    Layout L;
-    const size_t oM = L.take(4 * B), oSl = L.take(4 * B), oT = L.take(64 * B), oOw = L.take(12 * B), oRef = L.take(sizeof(oslam_kf_grid_ref_t) * B),
-                 oIds = L.take(4 * st * B), oEx = L.take(st * B);
-    OPS_CHECK(o->ensure_up(L.off));
-    OPS_CHECK(o->ensure_dn(4 * st * B));   // the match table: written by the kernel itself
+    StageLayout L;
+    const auto fM = L.add<int32_t>(B), fSl = L.add<int32_t>(B); const auto fT = L.add<float>(16 * B), fOw = L.add<float>(3 * B); const auto fRef = L.add<oslam_kf_grid_ref_t>(B);
+    const auto fIds = L.add<int32_t>(st * B); const auto fEx = L.add<uint8_t>(st * B);
+    OSLAM_CHECK(o->ensure_up(L.total()));
+    StageLayout R;
+    const auto rQm = R.add<int32_t>(st * B);   // the match table: written by the kernel itself
+    OSLAM_CHECK(o->ensure_dn(R.total()));
     // The job block (~5 KB per job) is read by the kernel where it is — the pinned staging block is mapped into the device's address space — instead of
     // being copied first: one dependent copy-engine hop less per SearchInNeighbors round.
-    uint8_t* U = o->up.h.bytes();
+    uint8_t *U = o->up.h.bytes(), *D = o->dn.bytes();
     o->pool->parallel_for(n, [&](int i) {
         const oslam_job_fuse_pts_t& j = jobs[i];
         const size_t M = j.M;
-        ((int32_t*)(U + oM))[i] = j.M; ((int32_t*)(U + oSl))[i] = j.slot;
-        memcpy(U + oT + 64 * i, j.Tcw, 64); memcpy(U + oOw + 12 * i, j.Ow, 12);
-        memcpy(U + oIds + 4 * st * i, j.ids, 4 * M); memcpy(U + oEx + st * i, j.excl, M);
-        oslam_kf_grid_ref_t& ref = ((oslam_kf_grid_ref_t*)(U + oRef))[i];
+        at(fM, U)[i] = j.M; at(fSl, U)[i] = j.slot;
+        copy_elems(row(fT, U, 16, i), j.Tcw, 16); copy_elems(row(fOw, U, 3, i), j.Ow, 3);
+        copy_elems(row(fIds, U, st, i), j.ids, M); copy_elems(row(fEx, U, st, i), j.excl, M);
+        oslam_kf_grid_ref_t& ref = at(fRef, U)[i];
         ref.cell_end = o->rec_cell_end(rec[i]); ref.cand = o->rec_cand(rec[i]); ref.desc = o->rec_desc(rec[i]);
     });
     o->t_begin();
     // (every query writes its one result: straight into the pinned result block, no copy kernel behind it)
-    OPS_CHECK(oslam_fuse_search_device(n, (int)st, (const oslam_kf_grid_ref_t*)(U + oRef), (const int32_t*)(U + oSl), (const int32_t*)(U + oM),
-                                       (const int32_t*)(U + oIds), U + oEx, o->d_mp_tab.as<uint8_t*>(), (const float*)(U + oT), (const float*)(U + oOw), o->K5,
-                                       o->bounds, jobs[0].th, o->logScale, o->scale, o->invSigma2, o->cfg.nLevels, (int32_t*)o->dn.bytes(), o->strm));
+    OSLAM_CHECK(oslam_fuse_search_device(n, (int)st, at(fRef, U), at(fSl, U), at(fM, U), at(fIds, U), at(fEx, U), o->mp_tab.device_table(), at(fT, U), at(fOw, U), o->K5, o->bounds, jobs[0].th,
+                                         o->logScale, o->scale, o->invSigma2, o->cfg.nLevels, at(rQm, D), o->strm));
     o->t_end();
     OSLAM_HIP_CHECK(oslam::stream_wait(o->strm));
     o->t_collect(4, 1, 0);
-    o->pool->parallel_for(n, [&](int i) { memcpy(jobs[i].q_match, o->dn.bytes() + 4 * st * i, 4 * (size_t)jobs[i].M); });
+    o->pool->parallel_for(n, [&](int i) { copy_elems(jobs[i].q_match, row(rQm, D, st, i), (size_t)jobs[i].M); });
     return OSLAM_OK;
 }
 
@@ -2166,7 +2156,7 @@ int h_triangulate(void* p, int n, oslam_job_triangulate_t* jobs) {
     if (M == 0) return OSLAM_OK;
     std::vector<uint8_t> ok(M);
     std::vector<float> x3(3 * (size_t)M);
-    OPS_CHECK(oslam_mp_triangulate_pairs(o->mp, n, k1.data(), k2.data(), ps.data(), i1.data(), i2.data(), o->scale, o->sigma2, o->cfg.nLevels,
+    OSLAM_CHECK(oslam_mp_triangulate_pairs(o->mp, n, k1.data(), k2.data(), ps.data(), i1.data(), i2.data(), o->scale, o->sigma2, o->cfg.nLevels,
                                          1.5f * o->cfg.scaleFactor, ok.data(), x3.data()));
     for (int i = 0; i < n; i++) {
         memcpy(jobs[i].ok, &ok[ps[i]], (size_t)jobs[i].M);
@@ -2201,12 +2191,14 @@ int oslam_slam_make_hip_ops(const oslam_slam_config_t* cfg, oslam_slam_ops_t* op
     memset(ops, 0, sizeof(*ops));
     HipOps* o = new HipOps;
     o->cfg = *cfg; o->S = cfg->n_sequences;
+    o->mp_tab.resize(o->S); o->pt_aux.resize(o->S);
     o->pool = new oslam_drv::Pool(cfg->host_threads > 1 ? cfg->host_threads : 1, /*own_workers*/ false);
     if (hipStreamCreateWithFlags(&o->strm, hipStreamNonBlocking) != hipSuccess) o->strm = nullptr;
     const int dev = cfg->device;
     int rc = oslam_orb_create(&o->orb, cfg->nFeatures, cfg->scaleFactor, cfg->nLevels, cfg->iniThFAST, cfg->minThFAST, cfg->width, cfg->height, o->S, dev);
     if (!rc) {
         o->cap = oslam_orb_max_keypoints(o->orb);
+        o->rec_lay = oslam::KfRecordLayout(o->cap);
         o->max_local = getenv("OSLAM_SLAM_MAX_LOCAL") ? atoi(getenv("OSLAM_SLAM_MAX_LOCAL")) : 8192;   // first reservation; grows on demand
         rc = oslam_matcher_create(&o->m_last, o->S, o->cap, o->cap, dev);
     }

@@ -1,6 +1,7 @@
-// Layout of the fields inside one staging block (a StagePair's pinned half and its device mirror) of the host-pointer entry points.  A field's element
-// type and count are stated ONCE, in add<T>(count); its offset, the memcpy into the pinned block, the typed device pointer and the memcpy out all follow
-// from the Field that add returns.  Pure host arithmetic: no HIP, no runtime call, and it owns nothing (device_buffer.h owns the blocks).
+// Layout of the fields inside one staging block (a StagePair's pinned half and its device mirror, or a pinned download block) of the host-pointer entry
+// points and of the driver's operator table.  A field's element type and count are stated ONCE, in add<T>(count); its offset, the memcpy into the pinned
+// block, the typed device pointer and the memcpy out all follow from the Field that add returns.  Pure host arithmetic: no HIP, no runtime call, and it
+// owns nothing (device_buffer.h owns the blocks).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -33,5 +34,10 @@ template <class T> void put(const Field<T>& f, uint8_t* host_base, const T* src)
 template <class T> void get(const Field<T>& f, const uint8_t* host_base, T* dst) { if (f.bytes) memcpy(dst, host_base + f.off, f.bytes); }
 // the field inside the block at `base` (the device mirror, or the pinned block for a partial copy-back); NULL for an optional array that is absent
 template <class T> T* at(const Field<T>& f, uint8_t* base) { return f.present ? reinterpret_cast<T*>(base + f.off) : nullptr; }
+// row b of a field laid out as rows of `stride` elements (slot-major: one row per slot, a job fills the row of its slot); NULL for an absent field
+template <class T> T* row(const Field<T>& f, uint8_t* base, size_t stride, size_t b) { return f.present ? at(f, base) + stride * b : nullptr; }
+// n elements between a host array and a part of a field in a pinned block (a row, a job's share of a packed field), either way: both sides have the
+// field's element type and the length in bytes follows from it
+template <class T> void copy_elems(T* dst, const T* src, size_t n) { if (n) memcpy(dst, src, n * sizeof(T)); }
 
 }  // namespace oslam

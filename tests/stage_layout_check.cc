@@ -1,10 +1,12 @@
 // Unit checks of object_slam_amd/csrc/stage_layout.h (host C++, no HIP, no GPU): the layout rules every host-pointer entry point of the batched
-// solver operators relies on, one case pinned by hand, and the put / get round trip.  Exit status 0 = all checks passed.
+// solver operators and every operator of the driver's table relies on, one case pinned by hand, the put / get round trip, the row helper of the
+// slot-major fields, and the byte layout of the resident keyframe record (kf_record_layout.h) at two capacities.  Exit status 0 = all checks passed.
 #include <cstdint>
 #include <cstdio>
 #include <vector>
 
 #include "../include/oslam_hip.h"
+#include "../object_slam_amd/csrc/kf_record_layout.h"
 #include "../object_slam_amd/csrc/stage_layout.h"
 
 using oslam::Field;
@@ -112,10 +114,57 @@ static void check_round_trip() {
     CHECK(at(fB, blk.data())[99] == 99 * 99 - 50 && at(fA, blk.data())[2] == 3.25f);
 }
 
+// a slot-major field: 3 rows of stride 5 of a 12-byte element behind a 4-byte field, worked out by hand; an absent field has no rows
+static void check_rows() {
+    struct P3 { float x, y, z; };
+    static_assert(sizeof(P3) == 12, "12-byte element");
+    StageLayout lay;
+    const auto fHead = lay.add<int32_t>(1);
+    const auto fRows = lay.add<P3>(3 * 5);
+    const auto fNone = lay.add<P3>(3 * 5, false);
+    CHECK(fHead.off == 0 && fRows.off == 256 && lay.total() == 512);
+    std::vector<uint8_t> blk(lay.total(), 0xAB);
+    CHECK((uint8_t*)row(fRows, blk.data(), 5, 2) == blk.data() + 256 + 2 * 5 * 12);
+    CHECK((uint8_t*)row(fRows, blk.data(), 5, 0) == (uint8_t*)at(fRows, blk.data()));
+    CHECK(row(fNone, blk.data(), 5, 2) == nullptr && row(fNone, blk.data(), 5, 0) == nullptr);
+    // a job's share of its row, in and out: 4 of the 5 elements; the fifth and the neighbouring rows stay as they were
+    const P3 src[4] = {{1, 2, 3}, {4, 5, 6}, {7, 8, 9}, {10, 11, 12}};
+    oslam::copy_elems(row(fRows, blk.data(), 5, 1), src, 4);
+    oslam::copy_elems(row(fRows, blk.data(), 5, 1), (const P3*)nullptr, 0);   // nothing to copy: no read through the NULL pointer
+    for (size_t i = 0; i < blk.size(); i++) if (i < 256 + 5 * 12 || i >= 256 + 5 * 12 + 4 * 12) CHECK(blk[i] == 0xAB);
+    P3 back[4] = {};
+    oslam::copy_elems(back, (const P3*)row(fRows, blk.data(), 5, 1), 4);
+    for (int i = 0; i < 4; i++) CHECK(back[i].x == src[i].x && back[i].y == src[i].y && back[i].z == src[i].z);
+}
+
+// the resident keyframe record: offsets worked out by hand from the chain of align_up(.., 256) links the operator table had before kf_record_layout.h
+// (28-byte keypoints, 32-byte descriptors, 3072 16-bit cell ends, 16-byte candidates, int32 point list, 64-bit observer cells, one depth bit per keypoint)
+static void check_kf_record() {
+    static_assert(sizeof(oslam_keypoint_t) == 28, "the offsets below are for 28-byte keypoints");
+    struct Want { size_t cap, keys, desc, ur, cell_end, cand, mp, okf, good, bytes, okf_from_mp, good_from_mp; };
+    const Want want[2] = {
+        {1000, 0, 28160, 60160, 64256, 70400, 86528, 90624, 98816, 99072, 4096, 12288},
+        // 1033 (no multiple of 64): 28924 -> 28928, 33056 -> 33280, 4132 -> 4352, 6144, 16528 -> 16640, 4132 -> 4352, 8264 -> 8448, 33 words = 132 -> 256
+        {1033, 0, 28928, 62208, 66560, 72704, 89344, 93696, 102144, 102400, 4352, 12800},
+    };
+    for (const Want& w : want) {
+        const oslam::KfRecordLayout r(w.cap);
+        CHECK(r.keys.off == w.keys && r.desc.off == w.desc && r.ur.off == w.ur && r.cell_end.off == w.cell_end && r.cand.off == w.cand);
+        CHECK(r.mp.off == w.mp && r.core_bytes() == w.mp && r.okf.off == w.okf && r.good.off == w.good && r.bytes == w.bytes);
+        CHECK(r.okf_from_mp() == w.okf_from_mp && r.good_from_mp() == w.good_from_mp);
+        CHECK(r.keys.bytes == w.cap * 28 && r.desc.bytes == w.cap * 32 && r.ur.bytes == w.cap * 4 && r.cell_end.bytes == 6144 && r.cand.bytes == w.cap * 16);
+        CHECK(r.mp.bytes == w.cap * 4 && r.okf.bytes == w.cap * 8 && r.good.bytes == (w.cap + 31) / 32 * 4);
+        check_rules({span(r.keys), span(r.desc), span(r.ur), span(r.cell_end), span(r.cand), span(r.mp), span(r.okf), span(r.good)}, r.bytes);
+    }
+    CHECK(oslam::KfRecordLayout().bytes == 6144);   // a handle without a capacity yet: only the grid's fixed cell table
+}
+
 int main() {
     check_sim3_case();
     check_general();
     check_round_trip();
+    check_rows();
+    check_kf_record();
     if (g_failed) { fprintf(stderr, "%d checks failed\n", g_failed); return 1; }
     printf("stage_layout_check: ok\n");
     return 0;

@@ -406,6 +406,30 @@ def test_resident_local_maps_and_keyframes_leave_the_run_unchanged(monkeypatch):
     assert a.stats(0) == b.stats(0) and a.stats(1) == b.stats(1)
 
 
+def test_each_resident_store_alone_leaves_the_run_unchanged(monkeypatch):
+    """The two stores switched off one at a time (the test above switches everything off together, which never reaches these combinations): without the
+    resident keyframes but with the map-point records the MapPoint updates carry their observations' descriptors (the separate kernels, and the record
+    writer reading the uploaded job block); without the map-point records but with the resident keyframes Fuse runs through fuse_keyed (the keyframes'
+    arrays copied device-to-device into the staging block's rows) and the keyed MapPoint updates write no records.  Both runs must equal the default
+    run bit for bit, over a run that reaches local BA and fuses points."""
+    from slam_common import make_scene_streams, run_scene
+    n, S = 16, 2
+    seqs = make_scene_streams(S, n, speed=2.0)
+    a = slam.System(slam.make_config(W, H, S))
+    pa, sa = run_scene(a, seqs, n)
+    for q in range(S):
+        st = a.stats(q)
+        assert st["local_bas"] >= 1 and st["points_fused"] > 0 and st["points_triangulated"] > 0, st
+    for knob in ("OSLAM_SLAM_NO_RESIDENT_KF", "OSLAM_SLAM_NO_RESIDENT_POINTS"):
+        with monkeypatch.context() as m:
+            m.setenv(knob, "1")
+            b = slam.System(slam.make_config(W, H, S))
+            pb, sb = run_scene(b, seqs, n)
+        assert np.array_equal(sa, sb) and np.array_equal(pa, pb), knob
+        for q in range(S):
+            assert a.stats(q) == b.stats(q), (knob, q)
+
+
 def test_create_new_map_points_in_one_batch_equals_the_neighbour_rounds(monkeypatch):
     """LocalMapping::CreateNewMapPoints searches and triangulates ALL neighbours of a keyframe in one batch from the state before the pass and applies the results
     in neighbour order with the reference's skip test (a keypoint that has received a point) at application time; OSLAM_SLAM_CNMP_ROUNDS=1 keeps one lockstep round
