@@ -1,6 +1,6 @@
 // orb_slam2_adapter.hpp — header-only C++ adapter that re-exposes the reference's class API on top of the C ABI in oslam_hip.h:
 // ORB_SLAM2::ORBextractor (include/ORBextractor.h:45-110), ORB_SLAM2::ORBmatcher (include/ORBmatcher.h:41-83: the projection searches, the relocalisation one included,
-// SearchForInitialization, SearchByBoW, SearchForTriangulation, Fuse, SearchBySim3, DescriptorDistance), Frame::ComputeStereoMatches (src/Frame.cc:706), ORB_SLAM2::Optimizer
+// SearchForInitialization, SearchByBoW (both overloads), SearchForTriangulation, Fuse, SearchBySim3, DescriptorDistance), Frame::ComputeStereoMatches (src/Frame.cc:706), ORB_SLAM2::Optimizer
 // (include/Optimizer.h:38-57: PoseOptimization, LocalBundleAdjustment, BundleAdjustment, OptimizeSim3, OptimizeEssentialGraph) and ObjectOptimizer::PoseOptimization2
 // (include/ObjectOptimizer.h:23), ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: loadFromTextFile, transform, score) ORB_SLAM2::PnPsolver (include/PnPsolver.h: SetRansacParameters, iterate, find) and ORB_SLAM2::Sim3Solver (include/Sim3Solver.h: SetRansacParameters, iterate, find, GetEstimatedRotation / Translation / Scale) and ORB_SLAM2::KeyFrameDatabase (include/KeyFrameDatabase.h: add, erase, clear,
 // DetectLoopCandidates, DetectRelocalizationCandidates) and ORB_SLAM2::ObjectMatcher (include/ObjectMatcher.h: MatchTwoFrame, MatchMapToFrame) with Frame::ExtractHSVHistogramsFromMask
@@ -293,6 +293,22 @@ public:
         int32_t nm = 0;
         oslam::throw_on(oslam_match_search_by_bow(bow_, &s1, &s2, mfNNratio, mbCheckOrientation ? 1 : 0, match_f.data(), &nm));
         match_f.resize(F.N);
+        return nm;
+    }
+
+    // int SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint*> &vpMatches12) (:522-655), the first step of LoopClosing::ComputeSim3: match12[i] = keypoint
+    // of KF2 whose map point goes to vpMatches12[i] (-1 none, -2 removed by the rotation check); kfN_has_good_mp[i] = the map point exists and is not bad
+    int SearchByBoW(const FrameView& KF1, const FeatureVector& fv1, const uint8_t* kf1_has_good_mp, const FrameView& KF2, const FeatureVector& fv2,
+                    const uint8_t* kf2_has_good_mp, std::vector<int32_t>& match12) {
+        ensure_bow();
+        oslam_bow_side1_t s1 = {KF1.N, reinterpret_cast<const oslam_keypoint_t*>(KF1.mvKeysUn), KF1.mDescriptors, nullptr, kf1_has_good_mp,
+                                (int32_t)fv1.q_idx.size(), fv1.q_idx.data(), fv1.q_node.data()};
+        oslam_bow_side2_t s2 = {KF2.N, reinterpret_cast<const oslam_keypoint_t*>(KF2.mvKeysUn), KF2.mDescriptors, nullptr, kf2_has_good_mp,
+                                (int32_t)fv2.nodes.size(), fv2.nodes.data(), fv2.start.data(), fv2.items.data()};
+        match12.assign(KF1.N + 1, -1);
+        int32_t nm = 0;
+        oslam::throw_on(oslam_match_search_by_bow_kf(bow_, &s1, &s2, mfNNratio, mbCheckOrientation ? 1 : 0, match12.data(), &nm));
+        match12.resize(KF1.N);
         return nm;
     }
 
@@ -853,6 +869,100 @@ public:
     static oslam_lba_t* lba_handle() {
         static thread_local oslam_lba_t* h = nullptr;
         if (!h) oslam::throw_on(oslam_lba_create(&h, 1, 128, 4096, 32768, 0));
+        return h;
+    }
+};
+
+// Flat view of what LoopClosing::CorrectLoop's propagation touches (src/LoopClosing.cc:436-517).  The keyframes are mvpCurrentConnectedKFs in ascending mnId,
+// re-indexed 0 .. nKF - 1; the points are those any of them observes.  The driver does not close loops: this is an operator for a caller that does.
+struct LoopCorrectionView {
+    int nKF, pCurKF;
+    float* Tiw;                              // [nKF][16] GetPose() in, SetPose() out
+    Sim3 Scw;                                // mg2oScw (ComputeScw)
+    const int32_t* mp_ptr; const int32_t* mp;   // CSR: GetMapPointMatches() of keyframe k as indices into the points, -1 = NULL
+    int nMP;
+    float* Xw;                               // [nMP][3] GetWorldPos() in, SetWorldPos() out
+    const uint8_t* bad;                      // [nMP] isBad()
+    Sim3* Corrected; Sim3* NonCorrected;     // [nKF] out: CorrectedSim3, NonCorrectedSim3 (what OptimizeEssentialGraph takes)
+    int32_t* mnCorrectedReference;           // [nMP] out: the keyframe that corrected the point (mnCorrectedByKF == pCurKF->mnId) or -1
+};
+// Flat view of the map update after global BA (src/LoopClosing.cc:677-738): every keyframe of the map in ascending mnId, every map point.
+struct GlobalBAUpdateView {
+    int nKF;
+    const int32_t* parent;                   // [nKF] GetParent(), -1 for a member of mvpKeyFrameOrigins
+    const uint8_t* kf_in_ba;                 // [nKF] mnBAGlobalForKF == nLoopKF
+    float* Tcw;                              // [nKF][16] GetPose() in (mTcwBefGBA afterwards: keep a copy), SetPose() out
+    const float* TcwGBA;                     // [nKF][16] mTcwGBA, read where kf_in_ba is set
+    uint8_t* reached;                        // [nKF] out: the walk from the origins came by
+    int nMP;
+    float* Xw;                               // [nMP][3] GetWorldPos() in, SetWorldPos() out
+    const float* PosGBA;                     // [nMP][3] mPosGBA, read where mp_in_ba is set
+    const uint8_t* mp_in_ba; const uint8_t* bad;   // [nMP] mnBAGlobalForKF == nLoopKF, isBad()
+    const int32_t* ref;                      // [nMP] GetReferenceKeyFrame() as an index
+};
+
+// The arithmetic of ORB_SLAM2::LoopClosing (include/LoopClosing.h) that is not one of the other classes' operators.  Static, as the state lives with the caller.
+class LoopClosing {
+public:
+    // mg2oScw = gScm * gSmw and mScw = Converter::toCvMat(mg2oScw) (src/LoopClosing.cc:334-336); gScm as OptimizeSim3 returned it, Tmw = pKF->GetPose()
+    static Sim3 ComputeScw(const Sim3& gScm, const float Tmw[16], float mScw[16]) {
+        Sim3 out;
+        static_assert(sizeof(Sim3) == 13 * sizeof(double), "Sim3 is the 13 doubles R, t, s of the ABI");
+        oslam::throw_on(oslam_loop_compose_scw(handle(1, 1, 1), 1, gScm.R, Tmw, out.R, mScw));
+        return out;
+    }
+    // :436-517: fills V.Corrected / V.NonCorrected / V.mnCorrectedReference, writes V.Xw (SetWorldPos) and V.Tiw (SetPose).  UpdateNormalAndDepth and
+    // UpdateConnections stay with the caller.  Throws on an invalid problem.
+    static void PropagateCorrection(LoopCorrectionView& V) {
+        const int n = V.nKF, E = n > 0 ? V.mp_ptr[n] : 0;
+        if (n <= 0) return;
+        oslam_loop_correct_problem_t pr;
+        memset(&pr, 0, sizeof(pr));
+        pr.n_kf = n; pr.cur = V.pCurKF; pr.n_points = V.nMP; pr.n_entries = E;
+        std::vector<int32_t> kfe((size_t)n * 2), cref((size_t)V.nMP + 1, -1);
+        for (int k = 0; k < n; k++) { kfe[2 * (size_t)k] = V.mp_ptr[k]; kfe[2 * (size_t)k + 1] = V.mp_ptr[k + 1] - V.mp_ptr[k]; }
+        std::vector<double> Sc((size_t)n * 13), Sn((size_t)n * 13);
+        std::vector<float> Tout((size_t)n * 16), Xout(V.Xw, V.Xw + (size_t)V.nMP * 3);
+        Xout.resize((size_t)V.nMP * 3 + 3);
+        int32_t status[4] = {0, 0, 0, 0};
+        oslam::throw_on(oslam_loop_propagate(handle(n, E, V.nMP), 1, &pr, n, V.Tiw, V.Scw.R, kfe.data(), E, V.mp, V.nMP, V.Xw, V.bad, Sc.data(), Sn.data(), Tout.data(),
+                                             Xout.data(), cref.data(), status));
+        if (status[0] != 0) throw std::runtime_error("PropagateCorrection: invalid problem (a value that is not finite, a scale that is not positive, or an index outside its table)");
+        memcpy(V.Tiw, Tout.data(), Tout.size() * sizeof(float));
+        if (V.nMP) { memcpy(V.Xw, Xout.data(), (size_t)V.nMP * 3 * sizeof(float)); memcpy(V.mnCorrectedReference, cref.data(), (size_t)V.nMP * sizeof(int32_t)); }
+        memcpy(V.Corrected, Sc.data(), Sc.size() * sizeof(double));
+        memcpy(V.NonCorrected, Sn.data(), Sn.size() * sizeof(double));
+    }
+    // :677-738: writes V.Tcw (SetPose), V.reached and V.Xw (SetWorldPos).  Throws on an invalid map (a parent outside the map, a cycle, a root outside the BA).
+    static void UpdateMapAfterGlobalBA(GlobalBAUpdateView& V) {
+        const int n = V.nKF;
+        if (n <= 0) return;
+        oslam_loop_gba_problem_t pr;
+        memset(&pr, 0, sizeof(pr));
+        pr.n_kf = n; pr.n_points = V.nMP;
+        std::vector<float> Tout((size_t)n * 16), Xout(V.Xw, V.Xw + (size_t)V.nMP * 3);
+        Xout.resize((size_t)V.nMP * 3 + 3);
+        int32_t status[4] = {0, 0, 0, 0};
+        oslam::throw_on(oslam_loop_update_after_gba(handle(n, 1, V.nMP), 1, &pr, n, V.parent, V.kf_in_ba, V.Tcw, V.TcwGBA, V.nMP, V.Xw, V.PosGBA, V.mp_in_ba, V.bad, V.ref,
+                                                    Tout.data(), V.reached, Xout.data(), status));
+        if (status[0] != 0) throw std::runtime_error("UpdateMapAfterGlobalBA: invalid map (a parent outside the map, a cycle, a root outside the BA or a value that is not finite)");
+        memcpy(V.Tcw, Tout.data(), Tout.size() * sizeof(float));
+        if (V.nMP) memcpy(V.Xw, Xout.data(), (size_t)V.nMP * 3 * sizeof(float));
+    }
+
+private:
+    static oslam_loop_correct_t* handle(int nKF, int nEntries, int nMP) {   // one handle per thread, grown on demand
+        static thread_local oslam_loop_correct_t* h = nullptr;
+        static thread_local int capK = 0, capE = 0, capP = 0;
+        if (!h || nKF > capK || nEntries > capE || nMP > capP) {
+            oslam_loop_correct_destroy(h);
+            h = nullptr;
+            capK = nKF > capK ? nKF : capK; capE = nEntries > capE ? nEntries : capE; capP = nMP > capP ? nMP : capP;
+            if (capK < 256) capK = 256;
+            if (capE < 65536) capE = 65536;
+            if (capP < 65536) capP = 65536;
+            oslam::throw_on(oslam_loop_correct_create(&h, 1, capK, capE, capP, 0));
+        }
         return h;
     }
 };

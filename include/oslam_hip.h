@@ -265,6 +265,14 @@ int oslam_match_debug_get_queries(oslam_matcher_t* h, int b, int q_stride, int n
  * SearchForTriangulation: side1.flag[i] = pKF1->GetMapPoint(i) != NULL (skipped); side2.has_mp likewise;
  *   F12 row-major 3x3 (cv::Mat CV_32F), (ex, ey) = epipole in image 2 (:663-670); match12[i] = keypoint of KF2 or -1.
  *   (vbMatched2 is never set in the reference, :722 — queries are independent and so they are here.)
+ * SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12) (:522-655), what LoopClosing::ComputeSim3 begins with for every
+ *   candidate (src/LoopClosing.cc:266, ORBmatcher(0.75, true)): side1.flag[i] = pMP1 && !pMP1->isBad(); side2.has_mp[k] = pMP2 && !pMP2->isBad()
+ *   (NULL = none: no candidate, zero matches).  It differs from the (KeyFrame*, Frame&) overload in this: a side-2 keypoint is a candidate only if
+ *   has_mp[k] is set and no earlier query, in side-1 list order, has been accepted on it (vbMatched2, :576, set at :603: the sequential claim is
+ *   reproduced as above); acceptance is bestDist1 < TH_LOW, strict (:598; <= at :240); the ratio test is (float)bestDist1 < nnratio *
+ *   (float)bestDist2; the rotation histogram bins by idx1 with both angles from mvKeysUn; vbMatched2 of a match that the rotation check removes stays
+ *   set (nothing reads it afterwards).  match12 [s1.N]: the side-2 keypoint whose map point goes to vpMatches12[idx1], -1 none, -2 removed by the
+ *   rotation check; nmatches = the return value (what :268 compares with 20).
  * ---------------------------------------------------------------------------------------- */
 typedef struct oslam_bow oslam_bow_t;
 typedef struct oslam_bow_side1 {
@@ -283,9 +291,13 @@ int oslam_match_search_for_triangulation(oslam_bow_t* h, const oslam_bow_side1_t
                                          const float F12[9], float ex, float ey, const float* scaleFactors,
                                          const float* levelSigma2, int nlevels, int bOnlyStereo, int checkOri,
                                          int32_t* match12, int32_t* nmatches);
+int oslam_match_search_by_bow_kf(oslam_bow_t* h, const oslam_bow_side1_t* kf1, const oslam_bow_side2_t* kf2, float nnratio, int checkOri,
+                                 int32_t* match12, int32_t* nmatches);
 
 /* Batch of independent pairs, one workgroup each in one launch (the batch-of-sequences layout).  triangulation == 0: SearchByBoW, match
- * [s2.N]; != 0: SearchForTriangulation (bOnlyStereo = false), match [s1.N].  nmatches is written per job. */
+ * [s2.N]; == 2: SearchByBoW(KeyFrame*, KeyFrame*), match [s1.N]; any other value: SearchForTriangulation (bOnlyStereo = false), match [s1.N].
+ * nmatches is written per job; jobs of all three modes may share a launch.  oracle/'s operator table knows modes 0 and 1 only: mode 2 is checked
+ * against the Python restatement of tests/loop_closing_common.py. */
 typedef struct oslam_bow_job {
     oslam_bow_side1_t s1; oslam_bow_side2_t s2;
     int32_t triangulation;
@@ -1347,6 +1359,102 @@ int oslam_essential_graph_correct_points(oslam_essential_graph_t* h, int n_probl
 int oslam_essential_graph_correct_points_device(oslam_essential_graph_t* h, int n_problems, const oslam_essential_graph_problem_t* d_problems, int n_kf_total, const float* d_Scw,
                                                 const double* d_Scw_out, const int32_t* d_status, int n_points, const int32_t* d_point_problem, const int32_t* d_ref,
                                                 const float* d_P, float* d_P_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * LoopClosing: map corrections — the arithmetic of LoopClosing (include/LoopClosing.h, src/LoopClosing.cc) that the operators above do not cover, for
+ * batches of independent sequences: mg2oScw (:334-336), CorrectLoop's Sim3 propagation with its point correction and corrected poses (:436-517), and the
+ * map update after global BA (:677-738).  Operators: the driver does not close loops and calls none of this.  One handle, created for a maximum number
+ * of problems, keyframes, (keyframe, keypoint) entries and points in all problems of a call.  Every Sim3 is g2o::Sim3 over Eigen::Quaterniond as
+ * csrc/sim3_math.h and se3_math.h restate it; quaternions are not normalised; fp64 from the float inputs on.
+ *
+ * compose_scw (:334-336), one lane per problem.  Scm [13] double = R row-major, t, s (the S12 output of OptimizeSim3); Tmw [16] float = the matched
+ *   keyframe's pose.  gScm = Sim3(Quaterniond(R), t, s); gSmw = Sim3(Quaterniond(toMatrix3d(Rmw)), toVector3d(tmw), 1.0); Scw = gScm * gSmw.
+ *   Outputs Scw [13] double = r.toRotationMatrix(), t, s and mScw [16] float = Converter::toCvMat(Sim3) = [(float)(s R) | (float)t; 0 0 0 1]
+ *   (src/Converter.cc:56-62), what the Sim3 SearchByProjection operator takes at :376.  No status: non-finite inputs give non-finite outputs.
+ *   Normalisation: the reference keeps the quaternion of gScm that OptimizeSim3 left; here it is rebuilt from the R that operator returns.
+ *
+ * propagate (:436-517).  A problem is one sequence that closes a loop: n_kf keyframes = mvpCurrentConnectedKFs IN ASCENDING mnId at kf_offset of the
+ *   per-keyframe arrays, cur = the index of mpCurrentKF among them, its points (a table of n_points rows at point_offset: P [3] float and a bad byte)
+ *   and its entries (n_entries at entry_offset).  Per keyframe Tiw [16] float and kf_entries [2] int32 = first, count: its GetMapPointMatches() as
+ *   `count` entries from `first` (relative to entry_offset), each the index of a point in the problem's table or -1 for a NULL pointer (NULL entries
+ *   may also be left out).  Scw [n_problems][13] double as compose_scw writes it.
+ *   Roundings:
+ *    - Twc of the current keyframe as KeyFrame::SetPose computes it (src/KeyFrame.cc:74-81): Rwc = Rcw.t(), Ow = -Rwc * tcw = the three float products
+ *      summed in float from left to right, negated; last row 0 0 0 1.
+ *    - Tic = Tiw * Twc (:456), a CV_32F 4 x 4 product: every entry is the float sum, left to right, of its four float products (cv::gemm's small-matrix
+ *      branch; the rule of the 3-term products elsewhere in this header extended to four terms, restated from memory of OpenCV 3.2 and unpinned).
+ *    - g2oSic = Sim3(Quaterniond(toMatrix3d(Ric)), toVector3d(tic), 1.0); Corrected[i] = g2oSic * Scw for i != cur, Corrected[cur] = Scw (rebuilt from
+ *      its 13 doubles); NonCorrected[i] = Sim3(Quaterniond(Riw), tiw, 1.0).
+ *    - Points: P' = Corrected[k].inverse().map(NonCorrected[k].map(P)), map(x) = s (r x) + t; float in (toVector3d), fp64, float out (toCvMat).
+ *    - Poses (:505-513): Tiw_out = [r.toRotationMatrix() | t * (1. / s)] rounded to float, last row 0 0 0 1.
+ *   Normalisation: the reference walks CorrectedSim3, a std::map<KeyFrame*, ...>, in pointer order, and a point seen by several keyframes is corrected
+ *   by the first that reaches it (mnCorrectedByKF, :489, :499).  Here the order is ascending keyframe index: a point that is not bad is corrected by the
+ *   smallest-index keyframe that holds it (one integer atomicMin per entry into a claim word per point, then one pass over the points).
+ *   UpdateNormalAndDepth (:501) is the mappoint operator's, as for the essential graph's point correction; the reference calls it in mid-loop, with
+ *   half of the poses updated, and again after the graph optimisation.
+ *   Outputs: Scorr_out, Snc_out [n_kf_total][13] double = R, t, s; Tiw_out [n_kf_total][16] float; P_out [n_points_total][3] float, written for
+ *   corrected points only (the others keep the caller's bytes); corrected_ref [n_points_total] int32 = the in-problem index of the keyframe that
+ *   corrected the point (mnCorrectedReference) or -1, written for every point of a valid problem: the `ref` of oslam_essential_graph_correct_points;
+ *   status [n_problems][4] int32 = 0 / -1 / -2, n_kf, points corrected, entries read (the entries >= 0 of the problem's keyframes).
+ *   Invalid: a non-finite pose or Scw, s <= 0, cur outside the problem, a keyframe's entries outside the problem's, or an entry below -1 or outside the
+ *   point table: status {-1, n_kf, 0, 0}, none of the problem's rows is written, the other problems are not affected.  A record outside the arrays:
+ *   OSLAM_E_INVALID from the host entry point, status {-2, 0, 0, 0} from the device one.  More than the handle was created for: OSLAM_E_CAPACITY before
+ *   anything is launched.  Problems of one call must not share rows; calls on one handle must not overlap on the device.  Three launches whatever the
+ *   batch: every problem is spread over 32 workgroups in each.
+ *
+ * update_after_gba (:677-738).  A problem is a whole map: n_kf keyframes in ascending mnId with parent [n_kf] int32 (-1: a member of
+ *   mvpKeyFrameOrigins), kf_in_ba bytes (mnBAGlobalForKF == nLoopKF), Tcw [16] float (the poses now = mTcwBefGBA afterwards) and TcwGBA [16] float (read
+ *   only where kf_in_ba is set); its points P, PosGBA (read where pt_in_ba is set), bad, ref = the in-problem index of GetReferenceKeyFrame().
+ *   Keyframes (:680-701): a keyframe with kf_in_ba keeps its TcwGBA; any other gets TcwGBA[c] = (Tcw[c] * Twc[p]) * TcwGBA[p] with Twc[p] from the
+ *   parent's pose BEFORE the update by SetPose's arithmetic above, both products the CV_32F 4 x 4 product above, rounded in this parenthesisation.
+ *   The reference's queue order does not change the result: each keyframe has one parent and only old poses enter Tchildc.  The kernel sweeps by depth
+ *   (round 1 the roots, round r + 1 the keyframes whose parent was settled by round r: at most n_kf rounds by construction).  A keyframe that no root
+ *   reaches (the reference's walk starts at the origins) has reached = 0 and Tcw_out = Tcw; with one parent per keyframe it lies on or behind a cycle, which
+ *   the host entry point refuses (below), so only the device entry point can report one.
+ *   Points (:706-738): bad: skipped; pt_in_ba: P_out = PosGBA; otherwise, when ref is a keyframe of the problem that was reached: Xc = Rcw_before * P +
+ *   tcw_before, P_out = Rwc_new * Xc + twc_new, both the float R x + t of one cv::gemm (the float sum of the three products, the + t in double,
+ *   rounded once), Twc_new = SetPose(Tcw_out[ref]); otherwise the point keeps its bytes.
+ *   Outputs: Tcw_out [16] float, reached bytes, P_out, status [n_problems][4] = 0 / -1 / -2, keyframes propagated (reached, not in the BA), points
+ *   written (both kinds), depth rounds used (those that settled a keyframe, the roots' round included).
+ *   Invalid (status {-1, 0, 0, 0}, no row written): a parent outside [-1, n_kf), a keyframe that is its own parent, a root without kf_in_ba (the
+ *   reference would read an unset mTcwGBA), a non-finite Tcw, or TcwGBA where kf_in_ba is set.  The host entry point also walks `parent` before it
+ *   launches anything (csrc/loop_parent_check.h) and refuses a problem with a cycle (problem.refuse, which the device entry point honours): the sweep
+ *   is bounded with a cycle too, but it would report the cycle's keyframes as unreached.  Two launches: one workgroup per map for the sweep, which is a
+ *   chain of dependent 4 x 4 products, and 32 per map for the points.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct oslam_loop_correct oslam_loop_correct_t;
+typedef struct oslam_loop_correct_problem {
+    int32_t n_kf, kf_offset;          /* keyframes kf_offset .. kf_offset + n_kf - 1 of the per-keyframe arrays */
+    int32_t cur;                      /* mpCurrentKF among them */
+    int32_t n_points, point_offset;   /* the problem's point table */
+    int32_t n_entries, entry_offset;  /* the problem's share of `entries` */
+    int32_t reserved;
+} oslam_loop_correct_problem_t;
+typedef struct oslam_loop_gba_problem {
+    int32_t n_kf, kf_offset, n_points, point_offset;
+    int32_t refuse;                   /* not 0: status -1 and nothing else (the host entry point sets it for a `parent` with a cycle) */
+    int32_t reserved[3];
+} oslam_loop_gba_problem_t;
+/* OSLAM_E_HIP without a device: there is no CPU fallback. */
+int oslam_loop_correct_create(oslam_loop_correct_t** out, int max_problems, int max_keyframes_total, int max_entries_total, int max_points_total, int device);
+void oslam_loop_correct_destroy(oslam_loop_correct_t* h);
+/* Host pointers, staged through one pinned / device block pair and synchronous; the _device forms take device arrays, are asynchronous on `stream` and
+ * do not synchronise the host.  Output arrays are read and written: what a call does not write keeps the caller's bytes. */
+int oslam_loop_compose_scw(oslam_loop_correct_t* h, int n, const double* Scm, const float* Tmw, double* Scw, float* mScw);
+int oslam_loop_compose_scw_device(oslam_loop_correct_t* h, int n, const double* d_Scm, const float* d_Tmw, double* d_Scw, float* d_mScw, void* stream);
+int oslam_loop_propagate(oslam_loop_correct_t* h, int n_problems, const oslam_loop_correct_problem_t* problems, int n_kf_total, const float* Tiw, const double* Scw,
+                         const int32_t* kf_entries, int n_entries_total, const int32_t* entries, int n_points_total, const float* P, const uint8_t* bad, double* Scorr_out,
+                         double* Snc_out, float* Tiw_out, float* P_out, int32_t* corrected_ref, int32_t* status);
+int oslam_loop_propagate_device(oslam_loop_correct_t* h, int n_problems, const oslam_loop_correct_problem_t* d_problems, int n_kf_total, const float* d_Tiw, const double* d_Scw,
+                                const int32_t* d_kf_entries, int n_entries_total, const int32_t* d_entries, int n_points_total, const float* d_P, const uint8_t* d_bad,
+                                double* d_Scorr_out, double* d_Snc_out, float* d_Tiw_out, float* d_P_out, int32_t* d_corrected_ref, int32_t* d_status, void* stream);
+int oslam_loop_update_after_gba(oslam_loop_correct_t* h, int n_problems, const oslam_loop_gba_problem_t* problems, int n_kf_total, const int32_t* parent, const uint8_t* kf_in_ba,
+                                const float* Tcw, const float* TcwGBA, int n_points_total, const float* P, const float* PosGBA, const uint8_t* pt_in_ba, const uint8_t* bad,
+                                const int32_t* ref, float* Tcw_out, uint8_t* reached, float* P_out, int32_t* status);
+int oslam_loop_update_after_gba_device(oslam_loop_correct_t* h, int n_problems, const oslam_loop_gba_problem_t* d_problems, int n_kf_total, const int32_t* d_parent,
+                                       const uint8_t* d_kf_in_ba, const float* d_Tcw, const float* d_TcwGBA, int n_points_total, const float* d_P, const float* d_PosGBA,
+                                       const uint8_t* d_pt_in_ba, const uint8_t* d_bad, const int32_t* d_ref, float* d_Tcw_out, uint8_t* d_reached, float* d_P_out,
+                                       int32_t* d_status, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * KeyFrameDatabase — ORB_SLAM2::KeyFrameDatabase (include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc:33-309): the query both

@@ -34,3 +34,5 @@ from .object_match import ObjectMatcher  # noqa: F401
 from . import object_match  # noqa: F401
 from .object_map import ObjectMap  # noqa: F401
 from . import object_map  # noqa: F401
+from .loop_correct import LoopCorrector  # noqa: F401
+from . import loop_correct  # noqa: F401

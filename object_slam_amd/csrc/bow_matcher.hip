@@ -1,5 +1,6 @@
 // gfx950 BoW-guided matchers: ORBmatcher::SearchByBoW(KeyFrame*, Frame&, ...) (reference
-// src/ORBmatcher.cc:159-288) and ORBmatcher::SearchForTriangulation (:657-823).  The DBoW2 vocabulary
+// src/ORBmatcher.cc:159-288), ORBmatcher::SearchForTriangulation (:657-823) and the KeyFrame-pair
+// ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, ...) (:522-655).  The DBoW2 vocabulary
 // is not part of the reference tree, so the FeatureVectors are inputs: side 1 as a flat list in the
 // std::map iteration order (node ascending, indices in vector order), side 2 as CSR over its sorted
 // node ids.  One 1024-thread workgroup per keyframe/frame pair; side-2 descriptors live in LDS.
@@ -19,7 +20,7 @@ constexpr int kBowMaxKps = 2400;
 constexpr int kBowHisto = 30;
 
 struct BowCtx {
-    int mode;   // 0 SearchByBoW, 1 SearchForTriangulation
+    int mode;   // 0 SearchByBoW(KF, F), 1 SearchForTriangulation, 2 SearchByBoW(KF1, KF2)
     int nq; const int* q_idx1; const uint32_t* q_node;
     int N1; const oslam_keypoint_t* keys1; const uint8_t* desc1; const float* uRight1; const uint8_t* flag1;
     int N2; const oslam_keypoint_t* keys2; const uint8_t* desc2; const float* uRight2; const uint8_t* has_mp2;
@@ -57,7 +58,7 @@ __device__ __forceinline__ void bow_body(const BowCtx& c, const int ncap) {
     else for (int i = tid; i < c.N1; i += kBowThreads) c.out[i] = -1;
     __syncthreads();
 
-    const int maxit = c.mode == 0 ? nq + 2 : 1;
+    const int maxit = c.mode != 1 ? nq + 2 : 1;   // modes 0 and 2 iterate the sequential claim to its fixed point
     for (int it = 0; it < maxit; it++) {
         for (int i = tid; i < N2; i += kBowThreads) s_Bcur[i] = 0x7fffffff;
         if (tid == 0) s_changed = 0;
@@ -65,7 +66,7 @@ __device__ __forceinline__ void bow_body(const BowCtx& c, const int ncap) {
         for (int q = tid; q < nq; q += kBowThreads) {
             const int idx1 = c.q_idx1[q];
             int best = -1;
-            bool ok = c.mode == 0 ? (c.flag1[idx1] != 0) : (c.flag1[idx1] == 0);
+            bool ok = c.mode != 1 ? (c.flag1[idx1] != 0) : (c.flag1[idx1] == 0);
             const bool bStereo1 = c.mode == 1 && c.uRight1[idx1] >= 0;
             if (c.mode == 1 && c.bOnlyStereo && !bStereo1) ok = false;
             const int nd = ok ? bow_find_node(c, c.q_node[q]) : -1;
@@ -74,11 +75,13 @@ __device__ __forceinline__ void bow_body(const BowCtx& c, const int ncap) {
                 const uint32_t* qp = (const uint32_t*)(c.desc1 + (size_t)idx1 * 32);
 #pragma unroll
                 for (int w = 0; w < 8; w++) qd[w] = qp[w];
-                if (c.mode == 0) {
+                if (c.mode != 1) {
+                    const bool kfPair = c.mode == 2;
                     int bestDist1 = 256, bestDist2 = 256;
                     for (int t = c.start[nd]; t < c.start[nd + 1]; t++) {
                         const int k = c.items[t];
-                        if (s_Bprev[k] < q) continue;   // vpMapPointMatches[realIdxF] already set (:211-212)
+                        if (s_Bprev[k] < q) continue;   // vpMapPointMatches[realIdxF] already set (:211-212) / vbMatched2[idx2] (:576)
+                        if (kfPair && !c.has_mp2[k]) continue;   // !pMP2 || pMP2->isBad() (:576-580)
                         const uint32_t* d = s_desc + k * 8;
                         int dist = 0;
 #pragma unroll
@@ -86,7 +89,8 @@ __device__ __forceinline__ void bow_body(const BowCtx& c, const int ncap) {
                         if (dist < bestDist1) { bestDist2 = bestDist1; bestDist1 = dist; best = k; }
                         else if (dist < bestDist2) bestDist2 = dist;
                     }
-                    if (!(bestDist1 <= 50 && (float)bestDist1 < c.nnratio * (float)bestDist2)) best = -1;
+                    // TH_LOW: <= at :240, strict < at :598
+                    if (!(bestDist1 <= (kfPair ? 49 : 50) && (float)bestDist1 < c.nnratio * (float)bestDist2)) best = -1;
                 } else {
                     const oslam_keypoint_t kp1 = c.keys1[idx1];
                     // epipolar line l = x1' F12 (:142-145)
@@ -118,7 +122,7 @@ __device__ __forceinline__ void bow_body(const BowCtx& c, const int ncap) {
                 }
             }
             c.q_best[q] = best;
-            if (c.mode == 0 && best >= 0) atomicMin(&s_Bcur[best], q);
+            if (c.mode != 1 && best >= 0) atomicMin(&s_Bcur[best], q);
         }
         __syncthreads();
         int diff = 0;
@@ -131,7 +135,7 @@ __device__ __forceinline__ void bow_body(const BowCtx& c, const int ncap) {
         { int* t = s_Bcur; s_Bcur = s_Bprev; s_Bprev = t; }
     }
 
-    // results + rotation consistency (:264-283 / :785-805)
+    // results + rotation consistency (:264-283 / :785-805 / :634-652)
     if (tid < kBowHisto) s_hist[tid] = 0;
     if (tid == 0) s_nm = 0;
     __syncthreads();
@@ -178,7 +182,7 @@ __device__ __forceinline__ void bow_body(const BowCtx& c, const int ncap) {
             if (bin == kBowHisto) bin = 0;
             if (bin != s_ind[0] && bin != s_ind[1] && bin != s_ind[2]) {
                 removed++;
-                if (c.mode == 0) c.out[k] = -2; else c.out[idx1] = -1;
+                if (c.mode == 0) c.out[k] = -2; else c.out[idx1] = c.mode == 2 ? -2 : -1;
             }
         }
         if (removed) atomicSub(&s_nm, removed);
@@ -313,6 +317,11 @@ int oslam_match_search_by_bow(oslam_bow_t* h, const oslam_bow_side1_t* kf, const
     return bow_run(h, 0, kf, frame, nnratio, checkOri, nullptr, 0.f, 0.f, nullptr, nullptr, 0, 0, match_f, nmatches);
 }
 
+int oslam_match_search_by_bow_kf(oslam_bow_t* h, const oslam_bow_side1_t* kf1, const oslam_bow_side2_t* kf2, float nnratio, int checkOri,
+                                 int32_t* match12, int32_t* nmatches) {
+    return bow_run(h, 2, kf1, kf2, nnratio, checkOri, nullptr, 0.f, 0.f, nullptr, nullptr, 0, 0, match12, nmatches);
+}
+
 int oslam_match_search_for_triangulation(oslam_bow_t* h, const oslam_bow_side1_t* kf1, const oslam_bow_side2_t* kf2, const float F12[9], float ex,
                                          float ey, const float* scaleFactors, const float* levelSigma2, int nlevels, int bOnlyStereo,
                                          int checkOri, int32_t* match12, int32_t* nmatches) {
@@ -322,7 +331,7 @@ int oslam_match_search_for_triangulation(oslam_bow_t* h, const oslam_bow_side1_t
 
 }  // extern "C"
 
-// Batch of independent pairs (SearchByBoW and / or SearchForTriangulation), one workgroup each in ONE launch: all inputs are packed into one
+// Batch of independent pairs (SearchByBoW of either overload and / or SearchForTriangulation), one workgroup each in ONE launch: all inputs are packed into one
 // pinned block and reach the device in one copy; the results come back in one copy after one synchronisation.
 static int bow_batch(oslam_bow_t* h, int n, oslam_bow_job_t* jobs, const oslam_bow_resident_t* res, const float* scaleFactors, const float* levelSigma2, int nlevels);
 
@@ -342,7 +351,7 @@ static int bow_batch(oslam_bow_t* h, int n, oslam_bow_job_t* jobs, const oslam_b
     if (!h || n < 0 || (n > 0 && !jobs)) { set_error("NULL argument"); return OSLAM_E_INVALID; }
     if (n == 0) return OSLAM_OK;
     bool anyTri = false;
-    for (int i = 0; i < n; i++) anyTri = anyTri || jobs[i].triangulation;
+    for (int i = 0; i < n; i++) anyTri = anyTri || (jobs[i].triangulation && jobs[i].triangulation != 2);   // 2 = SearchByBoW(KF1, KF2): no scale tables
     if (anyTri && (!scaleFactors || !levelSigma2 || nlevels < 1 || nlevels > OSLAM_MAX_LEVELS)) { set_error("bad scale tables"); return OSLAM_E_INVALID; }
     struct Off { size_t q_idx, q_node, keys1, desc1, ur1, flag1, keys2, desc2, ur2, mp2, nodes, start, items, out, qbest, nm; int nitems, nout; };
     std::vector<Off> off(n);
@@ -398,7 +407,7 @@ static int bow_batch(oslam_bow_t* h, int n, oslam_bow_job_t* jobs, const oslam_b
         memcpy(H + o.items, s2.items, (size_t)o.nitems * 4);
         BowCtx& c = cs[i];
         memset(&c, 0, sizeof(c));
-        c.mode = j.triangulation ? 1 : 0; c.nq = s1.nq; c.q_idx1 = (const int*)(D + o.q_idx); c.q_node = (const uint32_t*)(D + o.q_node);
+        c.mode = j.triangulation == 2 ? 2 : (j.triangulation ? 1 : 0); c.nq = s1.nq; c.q_idx1 = (const int*)(D + o.q_idx); c.q_node = (const uint32_t*)(D + o.q_node);
         c.N1 = s1.N; c.keys1 = o.keys1 ? (const oslam_keypoint_t*)(D + o.keys1) : res[i].d_keys1; c.desc1 = o.desc1 ? D + o.desc1 : res[i].d_desc1;
         c.uRight1 = o.ur1 ? (const float*)(D + o.ur1) : res[i].d_uRight1; c.flag1 = D + o.flag1;
         c.N2 = s2.N; c.keys2 = o.keys2 ? (const oslam_keypoint_t*)(D + o.keys2) : res[i].d_keys2; c.desc2 = o.desc2 ? D + o.desc2 : res[i].d_desc2;

@@ -175,7 +175,7 @@ def feature_vector(node_of_kp):
 
 
 class BowMatcher(_lib.Handle):
-    """SearchByBoW(KeyFrame*, Frame&) and SearchForTriangulation (reference src/ORBmatcher.cc:159, :657) with
+    """SearchByBoW(KeyFrame*, Frame&), SearchByBoW(KeyFrame*, KeyFrame*) and SearchForTriangulation (reference src/ORBmatcher.cc:159, :522, :657) with
     caller-supplied FeatureVectors (the DBoW2 vocabulary is not part of the reference tree)."""
 
     def __init__(self, max_keypoints=2400, device=0):
@@ -209,6 +209,15 @@ class BowMatcher(_lib.Handle):
         nm = C.c_int(0)
         check(self.L.oslam_match_search_by_bow(self.h, C.byref(s1), C.byref(s2), C.c_float(nnratio), int(checkOri), ptr(out), C.byref(nm)))
         return nm.value, out[:s2.N]
+
+    def SearchByBoWKF(self, keys1, desc1, valid1, node1, keys2, desc2, valid2, node2, nnratio=0.75, checkOri=True):
+        """SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12) (src/ORBmatcher.cc:522-655): valid1 / valid2 = the keypoint has a map point that is not
+        bad.  Returns (nmatches, match12 [N1] = keypoint of KF2 whose map point goes to vpMatches12[i], -1 none, -2 removed by the rotation check)."""
+        s1, s2, keep = self._sides(keys1, desc1, None, valid1, node1, keys2, desc2, None, valid2, node2)
+        out = np.full(max(s1.N, 1), -1, np.int32)
+        nm = C.c_int(0)
+        check(self.L.oslam_match_search_by_bow_kf(self.h, C.byref(s1), C.byref(s2), C.c_float(nnratio), int(checkOri), ptr(out), C.byref(nm)))
+        return nm.value, out[:s1.N]
 
     def SearchForTriangulation(self, keys1, desc1, uR1, hasmp1, node1, keys2, desc2, uR2, hasmp2, node2, F12, ex, ey, scaleFactors,
                                levelSigma2, bOnlyStereo=False, checkOri=True):
