@@ -336,7 +336,8 @@ int oslam_stereo_match_batch_device(oslam_stereo_t* h, oslam_orb_t* orbL, oslam_
                                     const int32_t* d_nR, int nR_const, int nlevels, float bf, float b, void* stream);
 /* Device results of the last batch: d_uRight / d_depth [batch][kp_stride] (the stride of that call; entries beyond a pair's left count are
  * unspecified), d_n_matched [batch] = left keypoints that had a match BEFORE the median-SAD cut (the size of vDistIdx, src/Frame.cc:866; the cut then
- * resets some of them to -1), or -1 when the kernel rejected the pair (a count above the handle's capacity). */
+ * resets some of them to -1), or -1 when the kernel rejected the pair (a negative device count, or one above kp_stride: the pair owns kp_stride rows
+ * of the input arrays and of the results); the uRight / depth rows of a rejected pair are not written. */
 int oslam_stereo_results_device(const oslam_stereo_t* h, const float** d_uRight, const float** d_depth,
                                 const int32_t** d_n_matched);
 

@@ -44,16 +44,52 @@ struct StereoCtx {
 constexpr int kStereoMaxRows = 4096;      // level-0 height limit of the extractor
 constexpr int kRowItemsPerKp = 24;        // capacity of the row table: items per right keypoint (band of 2 * 2 * scale + 1 rows; 17 at 1.2^7)
 
-__device__ __forceinline__ bool stereo_counts(const StereoCtx& c, int bidx, int ncap, int& N, int& Nr) {
+// An entry owns kp_stride rows of the caller's arrays and of the results (kp_stride <= the handle's capacity, checked on the host): a device count above
+// that would read, and write, the next entry's rows — or past the arrays for the last entry — so it refuses the entry (n_matched = -1).
+__device__ __forceinline__ bool stereo_counts(const StereoCtx& c, int bidx, int& N, int& Nr) {
     N = c.nL ? c.nL[bidx] : c.nL_const;
     Nr = c.nR ? c.nR[bidx] : c.nR_const;
-    return !(N > ncap || Nr > ncap || N < 0 || Nr < 0);
+    return !(N > c.kp_stride || Nr > c.kp_stride || N < 0 || Nr < 0);
+}
+
+// One aligned word of a pyramid level whose bytes are [lo, hi).  The SAD kernel fetches whole words around its windows; level 0 of the device entry point is
+// the caller's buffer at the caller's stride, and there a word can reach outside it: the word that holds the first or last window byte when the buffer's
+// ends are not 4-byte aligned, or a word behind the last window byte (a window on the last row of the last image).  Such a word is put together from the
+// bytes inside; the bytes outside are never among the window's, so no result depends on them.
+__device__ __forceinline__ uint32_t stereo_word(const uint8_t* p, const uint8_t* lo, const uint8_t* hi) {
+    if (p >= lo && p + 4 <= hi) return *(const uint32_t*)p;
+    uint32_t v = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (p + k >= lo && p + k < hi) v |= (uint32_t)p[k] << (8 * k);
+    return v;
+}
+
+__device__ __forceinline__ const uint8_t* stereo_word0(const uint8_t* a) { return (const uint8_t*)((unsigned long long)a & ~3ull); }
+
+// The test that decides between k_stereo_sad's plain word loads and stereo_word: do the 4 / 6 aligned words of the first and of the last window row (hence of
+// all rows) of this match lie inside the bytes of its two levels?  Same positions as k_stereo_sad computes (:794-799).  It runs in k_stereo_scan, one thread
+// per left keypoint, and travels in a spare bit of the best index: inside the SAD kernel, which waits on a chain of dependent loads in every wavefront, the
+// same test lengthened the kernel measurably.  A match that k_stereo_sad drops at its own guards is tested too; the addresses are only compared.
+constexpr int kStereoEdgeBit = 0x4000;
+static_assert(kStereoMaxKps < kStereoEdgeBit, "the best index shares a short with the edge bit");
+__device__ __forceinline__ bool stereo_words_inside(const StereoCtx& c, int bidx, const oslam_keypoint_t& kp, float uR0) {
+    const int oct = kp.octave, w = 5, L = 5;
+    const float sf = c.invScale[oct];
+    const int cy = (int)roundf(kp.y * sf), cxL = (int)roundf(kp.x * sf), cxR0 = (int)roundf(uR0 * sf);
+    const uint8_t* imL = c.L.lv[oct] + (oct == 0 ? c.img0_stride_L : c.pyr_stride_L) * bidx;
+    const uint8_t* imR = c.R.lv[oct] + (oct == 0 ? c.img0_stride_R : c.pyr_stride_R) * bidx;
+    const int pL = c.L.pitch[oct], pR = c.R.pitch[oct];
+    const uint8_t* endL = imL + (long long)(c.L.h[oct] - 1) * pL + c.L.w[oct];
+    const uint8_t* endR = imR + (long long)(c.R.h[oct] - 1) * pR + c.R.w[oct];
+    return stereo_word0(imL + (long long)(cy - w) * pL + cxL - w) >= imL && stereo_word0(imL + (long long)(cy + w) * pL + cxL - w) + 16 <= endL &&
+           stereo_word0(imR + (long long)(cy - w) * pR + cxR0 - L - w) >= imR && stereo_word0(imR + (long long)(cy + w) * pR + cxR0 - L - w) + 24 <= endR;
 }
 
 __global__ __launch_bounds__(kStereoThreads) void k_stereo_scan(StereoCtx c, int ncap) {
     const int bidx = blockIdx.x, tid = threadIdx.x;
     int N, Nr;
-    const bool ok = stereo_counts(c, bidx, ncap, N, Nr);
+    const bool ok = stereo_counts(c, bidx, N, Nr);
     const oslam_keypoint_t* kpL = c.kpL + (long long)bidx * c.kp_stride;
     const oslam_keypoint_t* kpR = c.kpR + (long long)bidx * c.kp_stride;
     const uint32_t* dL = (const uint32_t*)(c.descL + (long long)bidx * c.kp_stride * 32);
@@ -159,20 +195,25 @@ __global__ __launch_bounds__(kStereoThreads) void k_stereo_scan(StereoCtx c, int
                     if (row >= s_minr[iR] && row <= s_maxr[iR]) consider(iR);
             }
             const int bestDist = bestKey >> 16;
-            if (bestDist < 100 && bestDist < thOrbDist) best = bestKey & 0xFFFF;
+            if (bestDist < 100 && bestDist < thOrbDist) {
+                best = bestKey & 0xFFFF;
+                if (!stereo_words_inside(c, bidx, kp, s_x[best])) best |= kStereoEdgeBit;
+            }
         }
         best_out[iL] = (short)best;
     }
 }
 
 // ---- SAD refinement (:792-863), one wavefront per left keypoint ----
-__global__ __launch_bounds__(256) void k_stereo_sad(StereoCtx c, int ncap) {
+__global__ __launch_bounds__(256) void k_stereo_sad(StereoCtx c) {
     const int bidx = blockIdx.y, lane = threadIdx.x & 63;
     const int iL = blockIdx.x * 4 + (threadIdx.x >> 6);
     int N, Nr;
-    if (!stereo_counts(c, bidx, ncap, N, Nr) || iL >= N) return;
-    const int bestIdxR = c.best[(long long)bidx * c.kp_stride + iL];
-    if (bestIdxR < 0) return;
+    if (!stereo_counts(c, bidx, N, Nr) || iL >= N) return;
+    const int bestRaw = c.best[(long long)bidx * c.kp_stride + iL];
+    if (bestRaw < 0) return;
+    const int bestIdxR = bestRaw & (kStereoEdgeBit - 1);
+    const bool inside = !(bestRaw & kStereoEdgeBit);   // stereo_words_inside, decided by k_stereo_scan
     const oslam_keypoint_t kp = c.kpL[(long long)bidx * c.kp_stride + iL];
     const float uR0 = c.kpR[(long long)bidx * c.kp_stride + bestIdxR].x;
     float* uRight = c.uRight + (long long)bidx * c.kp_stride;
@@ -195,26 +236,31 @@ __global__ __launch_bounds__(256) void k_stereo_sad(StereoCtx c, int ncap) {
         // lanes hold the 121 left-patch values (2 per lane).  The 11 x 11 left patch and the 11 x 21 right strip are fetched ONCE per wavefront as aligned
         // words (44 + 66 words: three load instructions) into LDS and the lanes pick their bytes there.  Round 4 had every lane load its 35 bytes from global
         // memory itself: 35 byte-gather instructions per keypoint, and the kernel — the largest of the stereo workload, 1.98 ms per 256 frames — ran at the
-        // texture addresser's rate (rocprofv3: profiles/r05_stereo_bench_kernel_stats_before.csv).  A keypoint lies >= 19 pixels inside its level and the
-        // guard above keeps the strip inside the row, so the words that hold the first / last bytes are inside the image buffer.
+        // texture addresser's rate (rocprofv3: profiles/r05_stereo_bench_kernel_stats_before.csv).  The guard above keeps the windows inside the level; the
+        // words around them can still reach outside the level's bytes (caller-supplied keypoints at the border of a caller-owned level 0): `inside`, stereo_word.
+        const uint8_t* endL = imL + (long long)(c.L.h[oct] - 1) * pL + c.L.w[oct];
+        const uint8_t* endR = imR + (long long)(c.R.h[oct] - 1) * pR + c.R.w[oct];
         __shared__ uint32_t s_pat[4][112];
         uint32_t* sp = s_pat[threadIdx.x >> 6];
         const uint8_t* spb = (const uint8_t*)sp;
-        {
+        auto fill = [&](auto word) {   // word(p, lo, hi): the aligned word at p of the level [lo, hi)
             if (lane < 44) {
                 const uint8_t* a = imL + (long long)(cy + (lane >> 2) - w) * pL + cxL - w;
-                sp[lane] = *(const uint32_t*)((const uint8_t*)((unsigned long long)a & ~3ull) + 4 * (lane & 3));
+                sp[lane] = word(stereo_word0(a) + 4 * (lane & 3), imL, endL);
             }
             const int r = lane / 6, wd = lane - 6 * r;   // right strip rows 0 .. 10 (lanes 0 .. 63 cover words 0 .. 63; lanes 0, 1 add words 64, 65)
             const uint8_t* a = imR + (long long)(cy + r - w) * pR + cxR0 - L - w;
-            sp[44 + lane] = *(const uint32_t*)((const uint8_t*)((unsigned long long)a & ~3ull) + 4 * wd);
+            sp[44 + lane] = word(stereo_word0(a) + 4 * wd, imR, endR);
             if (lane < 2) {
                 const uint8_t* a2 = imR + (long long)(cy + 10 - w) * pR + cxR0 - L - w;
-                sp[44 + 64 + lane] = *(const uint32_t*)((const uint8_t*)((unsigned long long)a2 & ~3ull) + 4 * (4 + lane));
+                sp[44 + 64 + lane] = word(stereo_word0(a2) + 4 * (4 + lane), imR, endR);
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
+        };
+        // two copies of the three loads, not one test per load: the loads of the usual path stay back to back, as before (inside: from k_stereo_scan)
+        if (inside) fill([](const uint8_t* p, const uint8_t*, const uint8_t*) { return *(const uint32_t*)p; });
+        else fill([](const uint8_t* p, const uint8_t* lo, const uint8_t* hi) { return stereo_word(p, lo, hi); });
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
         auto left_px = [&](int dy, int dx) -> int {    // imL[(cy + dy) * pL + cxL + dx]
             const unsigned sh = (unsigned)((unsigned long long)(imL + (long long)(cy + dy) * pL + cxL - w) & 3ull);
             return (int)spb[(dy + w) * 16 + sh + dx + w];
@@ -277,10 +323,10 @@ __global__ __launch_bounds__(256) void k_stereo_sad(StereoCtx c, int ncap) {
 }
 
 // ---- median-SAD outlier cut (:866-879): median = element size/2 of the distance-sorted list, found by bisection on the value ----
-__global__ __launch_bounds__(kStereoThreads) void k_stereo_cut(StereoCtx c, int ncap) {
+__global__ __launch_bounds__(kStereoThreads) void k_stereo_cut(StereoCtx c) {
     const int bidx = blockIdx.x, tid = threadIdx.x;
     int N, Nr;
-    if (!stereo_counts(c, bidx, ncap, N, Nr)) return;
+    if (!stereo_counts(c, bidx, N, Nr)) return;
     const int M = c.n_matched[bidx];
     if (M <= 0) return;
     float* uRight = c.uRight + (long long)bidx * c.kp_stride;
@@ -406,8 +452,8 @@ int oslam_stereo_match_batch_device(oslam_stereo_t* h, oslam_orb_t* orbL, oslam_
     c.uRight = h->d_uRight.as<float>(); c.depth = h->d_depth.as<float>(); c.sad = h->d_sad.as<int>(); c.n_matched = h->d_nm.as<int>(); c.best = h->d_best.as<short>(); c.row_items = h->d_items.as<unsigned short>();
     if (c.L.h[0] > kStereoMaxRows) { set_error("image height %d above the stereo row table (%d)", c.L.h[0], kStereoMaxRows); return OSLAM_E_CAPACITY; }
     hipLaunchKernelGGL(k_stereo_scan, dim3(batch), dim3(kStereoThreads), h->lds, (hipStream_t)stream, c, h->max_kps);
-    hipLaunchKernelGGL(k_stereo_sad, dim3((kp_stride + 3) / 4, batch), dim3(256), 0, (hipStream_t)stream, c, h->max_kps);
-    hipLaunchKernelGGL(k_stereo_cut, dim3(batch), dim3(kStereoThreads), 0, (hipStream_t)stream, c, h->max_kps);
+    hipLaunchKernelGGL(k_stereo_sad, dim3((kp_stride + 3) / 4, batch), dim3(256), 0, (hipStream_t)stream, c);
+    hipLaunchKernelGGL(k_stereo_cut, dim3(batch), dim3(kStereoThreads), 0, (hipStream_t)stream, c);
     OSLAM_HIP_CHECK(hipGetLastError());
     return OSLAM_OK;
 }

@@ -288,7 +288,6 @@ void ComputeStereoMatches(int N, const KeyPoint* keysL, const uint8_t* descL, in
             const Image& imL = pyrL[kpL.octave];
             const Image& imR = pyrR[kpL.octave];
             const int cy = (int)scaledvL, cxL = (int)scaleduL;
-            const float centerL = imL.row(cy)[cxL];
             int bestDist2 = INT32_MAX;
             int bestincR = 0;
             const int L = 5;
@@ -302,6 +301,7 @@ void ComputeStereoMatches(int N, const KeyPoint* keysL, const uint8_t* descL, in
             if (cy - w < 0 || cy + w >= imL.h || cxL - w < 0 || cxL + w >= imL.w || (int)scaleduR0 - L - w < 0 ||
                 (int)scaleduR0 + L + w >= imR.w)
                 continue;
+            const float centerL = imL.row(cy)[cxL];   // read behind the guard: (cy, cxL) itself can lie outside the level (a keypoint on the last row rounds up)
             for (int incR = -L; incR <= +L; incR++) {
                 const int cxR = (int)(scaleduR0 + incR);
                 const float centerR = imR.row(cy)[cxR];
