@@ -3,7 +3,7 @@
 // SearchForInitialization, SearchByBoW (both overloads), SearchForTriangulation, Fuse, SearchBySim3, DescriptorDistance), Frame::ComputeStereoMatches (src/Frame.cc:706), ORB_SLAM2::Optimizer
 // (include/Optimizer.h:38-57: PoseOptimization, LocalBundleAdjustment, BundleAdjustment, OptimizeSim3, OptimizeEssentialGraph) and ObjectOptimizer::PoseOptimization2
 // (include/ObjectOptimizer.h:23), ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: loadFromTextFile, transform, score) ORB_SLAM2::PnPsolver (include/PnPsolver.h: SetRansacParameters, iterate, find) and ORB_SLAM2::Sim3Solver (include/Sim3Solver.h: SetRansacParameters, iterate, find, GetEstimatedRotation / Translation / Scale) and ORB_SLAM2::KeyFrameDatabase (include/KeyFrameDatabase.h: add, erase, clear,
-// DetectLoopCandidates, DetectRelocalizationCandidates) and ORB_SLAM2::ObjectMatcher (include/ObjectMatcher.h: MatchTwoFrame, MatchMapToFrame) with Frame::ExtractHSVHistogramsFromMask
+// DetectLoopCandidates, DetectRelocalizationCandidates) and ORB_SLAM2::LoopClosing (include/LoopClosing.h: DetectLoop) and ORB_SLAM2::ObjectMatcher (include/ObjectMatcher.h: MatchTwoFrame, MatchMapToFrame) with Frame::ExtractHSVHistogramsFromMask
 // (src/Frame.cc:388) as a free function, and ORB_SLAM2::Object3D (include/ObjectTypes.h: Update, RejectOutliers, CalculateCenterAndSize) with RejectNewObjectOutliers
 // (the new-object path of Tracking::UpdateCurrentObject) and ObjectMapRegularization / MergeObject (src/Map.cc:67-157) as free functions.  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
 // "view" of exactly the members it reads and writes (the gather loops are in INTEGRATION.md).  tests/adapter_program.cc uses nothing but
@@ -902,7 +902,8 @@ struct GlobalBAUpdateView {
 };
 
 // The arithmetic of ORB_SLAM2::LoopClosing (include/LoopClosing.h) that is not one of the other classes' operators.  Static, as the state lives with the caller.
-class LoopClosing {
+// LoopClosing itself (below KeyFrameDatabase, which its DetectLoop needs) derives from it: callers write LoopClosing::ComputeScw and so on.
+class LoopClosingArithmetic {
 public:
     // mg2oScw = gScm * gSmw and mScw = Converter::toCvMat(mg2oScw) (src/LoopClosing.cc:334-336); gScm as OptimizeSim3 returned it, Tmw = pKF->GetPose()
     static Sim3 ComputeScw(const Sim3& gScm, const float Tmw[16], float mScw[16]) {
@@ -1337,6 +1338,9 @@ public:
     }
     const float* accumulatedScores() const { return acc_.data(); }   // of the candidates the last query returned, in their order
     const int32_t* diagnostics() const { return diag_; }            // lKFsSharingWords.size(), maxCommonWords, minCommonWords, nscores, lScoreAndMatch.size()
+    oslam_kfdb_t* handle() const { return h_; }                      // for LoopClosing below, which detects over this database
+    const ORBVocabulary* vocabulary() const { return mpVoc; }
+    int maxKeyFrames() const { return (int)cand_.size(); }
 
 private:
     void flatten(const DBoW2::BowVector& v) {
@@ -1350,6 +1354,67 @@ private:
     std::vector<int32_t> cand_;
     std::vector<float> acc_;
     int32_t diag_[5] = {0, 0, 0, 0, 0};
+};
+
+// ORB_SLAM2::LoopClosing (include/LoopClosing.h, src/LoopClosing.cc) as far as DetectLoop (:104-230) goes, for ONE sequence: over one KeyFrameDatabase of this
+// file and one detector of oslam_hip.h ("LoopClosing::DetectLoop": the restated consistency update and its normalisations).  The connected keyframes of every
+// keyframe and mvConsistentGroups live on the device; candidates are ids where the reference has KeyFrame pointers.  pDB must outlive this object.
+// The static ComputeScw, PropagateCorrection and UpdateMapAfterGlobalBA come from LoopClosingArithmetic.
+class LoopClosing : public LoopClosingArithmetic {
+public:
+    // LoopClosing(Map*, KeyFrameDatabase* pDB, ORBVocabulary* pVoc, bool bFixScale): mnCovisibilityConsistencyTh = 3 (:44), mLastLoopKFid = 0 (:41)
+    explicit LoopClosing(KeyFrameDatabase* pDB, int maxGroups = OSLAM_LOOPDET_MAX_GROUPS, int nCovisibilityConsistencyTh = 3) : mpKeyFrameDB(pDB) {
+        oslam::throw_on(oslam_loopdet_create(&h_, pDB->handle(), maxGroups, nCovisibilityConsistencyTh));
+        const size_t K = (size_t)pDB->maxKeyFrames();
+        cand_.resize(K); acc_.resize(K); enough_.resize(K);
+    }
+    ~LoopClosing() { oslam_loopdet_destroy(h_); }
+    LoopClosing(const LoopClosing&) = delete;
+    LoopClosing& operator=(const LoopClosing&) = delete;
+
+    // What the device keeps of KeyFrame::GetConnectedKeyFrames() of keyframe mnId: call it for both ends whenever a connection is added or erased
+    // (KeyFrame::AddConnection / EraseConnection / UpdateConnections)
+    void SetConnectedKeyFrames(int mnId, const std::vector<int32_t>& ids) {
+        const oslam_loopdet_conn_t rec = {0, mnId, 0, (int32_t)ids.size()};
+        oslam::throw_on(oslam_loopdet_set_connected(h_, 1, &rec, (int)ids.size(), ids.data()));
+    }
+    // bool DetectLoop() for mpCurrentKF = KF (its mBowVec, spConnected and, for the add, vpBestCovisibles): the gate (:115), minScore and the query
+    // (:125-142), the consistency groups (:144-212), mpKeyFrameDB->add (:117, :147, :216); fills mvpEnoughConsistentCandidates
+    bool DetectLoop(const KeyFrameDatabaseKeyFrameView& KF) {
+        mvpEnoughConsistentCandidates.clear();
+        mvpCandidateKFs.clear();
+        if ((long)KF.mnId < (long)mLastLoopKFid + 10) {
+            mpKeyFrameDB->add(KF);
+            return false;
+        }
+        ids_.clear(); vals_.clear();
+        for (const auto& e : *KF.mBowVec) { ids_.push_back(e.first); vals_.push_back(e.second); }
+        const oslam_kfdb_query_t q = {0, KF.mnId, 0, (int32_t)ids_.size(), 0, (int32_t)KF.spConnected.size(), 0.0f, 0};
+        std::vector<float> cs(KF.spConnected.size());
+        int32_t n = 0, ne = 0, diag[5];
+        oslam::throw_on(oslam_loopdet_detect(h_, mpKeyFrameDB->vocabulary()->handle(), 1, &q, (int)ids_.size(), ids_.data(), vals_.data(), (int)KF.spConnected.size(),
+                                             KF.spConnected.data(), cand_.data(), acc_.data(), &n, diag, cs.data(), &mMinScore, enough_.data(), &ne, &mnGroups));
+        if (ne < 0) throw std::runtime_error(ne == -3 ? "LoopClosing::DetectLoop: more consistent groups than the detector holds" : "LoopClosing::DetectLoop: refused");
+        mvpCandidateKFs.assign(cand_.begin(), cand_.begin() + n);
+        mvpEnoughConsistentCandidates.assign(enough_.begin(), enough_.begin() + ne);
+        mpKeyFrameDB->add(KF);
+        return !mvpEnoughConsistentCandidates.empty();
+    }
+    std::vector<int32_t> mvpEnoughConsistentCandidates;   // ids
+    std::vector<int32_t> mvpCandidateKFs;                 // vpCandidateKFs of the last DetectLoop that was not gated
+    long unsigned int mLastLoopKFid = 0;                  // CorrectLoop sets it (:585)
+    float minScore() const { return mMinScore; }          // of the last DetectLoop that was not gated
+    int consistentGroups() const { return mnGroups; }     // mvConsistentGroups.size() after it
+
+private:
+    KeyFrameDatabase* mpKeyFrameDB;
+    oslam_loopdet_t* h_ = nullptr;
+    std::vector<uint32_t> ids_;
+    std::vector<double> vals_;
+    std::vector<int32_t> cand_, enough_;
+    std::vector<float> acc_;
+    float mMinScore = 1.0f;
+    int32_t mnGroups = 0;
 };
 
 // ---- the object layer: what Tracking::TrackObject (src/Tracking.cc:1058-1076) and Tracking::UpdateCurrentObject (:1079-1207) read and write ----

@@ -1461,7 +1461,7 @@ int oslam_loop_update_after_gba_device(oslam_loop_correct_t* h, int n_problems, 
  * KeyFrameDatabase — ORB_SLAM2::KeyFrameDatabase (include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc:33-309): the query both
  * Tracking::Relocalization (src/Tracking.cc:1616) and LoopClosing::DetectLoop (src/LoopClosing.cc:143) begin with, for many independent databases
  * (one per sequence) that live on the device.  Each query call is one launch, one workgroup per query.  An operator: the driver does not call it,
- * and DetectLoop's consistency groups (src/LoopClosing.cc:156-227) are not part of it.
+ * and DetectLoop's consistency groups (src/LoopClosing.cc:153-212) live in a detector over this handle: "LoopClosing::DetectLoop" below.
  *
  * State.  Database d has keyframe slots 0 .. max_keyframes - 1; the caller's keyframe id IS the slot.  A slot holds a present bit, the keyframe's
  * BowVector in the layout of oslam_voc_vectors (word ids uint32 strictly ascending, values double, at most max_words), its add serial (a counter of
@@ -1554,7 +1554,82 @@ int oslam_kfdb_detect_relocalization_candidates_device(oslam_kfdb_t* h, const os
                                                        int32_t* d_diag, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Initializer — ORB_SLAM2::Initializer (include/Initializer.h, src/Initializer.cc: homography / fundamental RANSAC, model selection, motion recovery),
+ * LoopClosing::DetectLoop — the step that decides whether a loop exists (src/LoopClosing.cc:104-230), for many independent sequences: a detector
+ * handle over a BORROWED oslam_kfdb_t.  It takes n_databases, K = max_keyframes, the device and the stream from the kfdb, which must outlive it.
+ * An operator: the driver does not call it.  No CPU fallback.
+ *
+ * State per database, resident on the device, W = ceil(K / 32):
+ *  - Connected rows: K rows of W uint32 words; row k is the bitset of KeyFrame::GetConnectedKeyFrames() of keyframe k (bit i of word i / 32 = id i),
+ *    zero at creation.  A row does not depend on keyframe k (or any id in it) being present in the kfdb: the reference keeps pointers to bad
+ *    keyframes in these sets.  The caller keeps both sides of a connection current, as AddConnection / EraseConnection do.
+ *    Memory: n_databases * K * W * 4 bytes (512 KB per database at K = 2048).
+ *  - mvConsistentGroups (:159-212): up to max_groups groups, each a W-word bitset and an int32 consistency counter, in list order; two banks, a
+ *    group count and the current bank per database.  An update writes the other bank and flips the bank only when it succeeds: a refused query
+ *    changes nothing.
+ *
+ * The consistency update (:144-226, given the candidates c_0 .. c_{n-1} and the previous groups prev_0 .. prev_{m-1} with counters n_g), as sets:
+ *  1. group_i = row(c_i) u {c_i} (:165-166).
+ *  2. C(i, g) holds iff group_i n prev_g is not empty (:175-183).
+ *  3. first(g) = the smallest i with C(i, g) (vbConsistentGroup, :189-194).
+ *  4. The new list, for i ascending: for g ascending with first(g) == i push (group_i, n_g + 1); then, if no g has C(i, g), push (group_i, 0)
+ *     (:204-208).
+ *  5. Candidate i is "enough" iff some g has C(i, g) and n_g + 1 >= consistency_th (:195-199); each candidate once, in ascending i.
+ * n_cand == 0 clears the groups (:145-151).  A candidate id that repeats in the input is two candidates, literally.
+ *
+ * Normalisations:
+ *  1. minScore (:127-139) is min(1.0f, the scores of the query's connected ids that are PRESENT in the kfdb): "present in the database" stands in
+ *     for !isBad(); a connected keyframe that is not in the database takes no part.  The minimum is exact and independent of execution order.
+ *  2. Ids of a connected row outside 0 .. K - 1 are skipped (normalisation 4 of the kfdb).
+ * Two things stay with the caller, because they are host bookkeeping over the kfdb's host free list: the gate mnId < mLastLoopKFid + 10 (:115) and
+ * mpKeyFrameDB->add(mpCurrentKF) (:117, :147, :216).
+ *
+ * One workgroup per query; no atomics on global memory, nothing that depends on the order the hardware runs anything in; results are bit-identical
+ * between calls, batch compositions and entry points.  Per-query refusals, all of which leave the state unchanged: n_enough = -2 (a database outside
+ * the handle, two queries on one database in one call, a record outside the arrays or n_cand > K, a candidate id outside 0 .. K - 1, a query the
+ * kfdb refused); n_enough = -3 (the new list would exceed max_groups).  Nothing else of such a query is written.
+ * ---------------------------------------------------------------------------------------- */
+#define OSLAM_LOOPDET_MAX_GROUPS 64
+typedef struct oslam_loopdet oslam_loopdet_t;
+typedef struct oslam_loopdet_conn {
+    int32_t database, keyframe;
+    int32_t off, n;                /* ids off .. off + n - 1 of the call's ids */
+} oslam_loopdet_conn_t;
+typedef struct oslam_loopdet_update {
+    int32_t database;
+    int32_t cand_off, n_cand;      /* vpCandidateKFs: ids cand_off .. cand_off + n_cand - 1 of the call's cand */
+} oslam_loopdet_update_t;
+/* LoopClosing::LoopClosing (:37-46): consistency_th is mnCovisibilityConsistencyTh (3 at :44), >= 1; 1 <= max_groups <= OSLAM_LOOPDET_MAX_GROUPS.
+ * Rows and groups start empty. */
+int oslam_loopdet_create(oslam_loopdet_t** out, oslam_kfdb_t* kfdb, int max_groups, int consistency_th);
+void oslam_loopdet_destroy(oslam_loopdet_t* h);
+/* KeyFrame::GetConnectedKeyFrames (src/KeyFrame.cc:159-166) of each named keyframe: replaces whole rows, in record order (a keyframe named twice
+ * keeps its last row).  Synchronous.  OSLAM_E_INVALID: a database or keyframe outside the handle, a record outside ids. */
+int oslam_loopdet_set_connected(oslam_loopdet_t* h, int n, const oslam_loopdet_conn_t* recs, int n_ids_total, const int32_t* ids);
+/* Clears the rows and the groups of each named database: the partner of oslam_kfdb_clear (LoopClosing::ResetIfRequested, :635-645). */
+int oslam_loopdet_reset(oslam_loopdet_t* h, int n, const int32_t* databases);
+/* mvConsistentGroups of one database in list order: *n_out groups, consistency_out [max_groups], bits_out [max_groups * W]. */
+int oslam_loopdet_get_groups(oslam_loopdet_t* h, int database, int32_t* n_out, int32_t* consistency_out, uint32_t* bits_out);
+/* :144-226 given the candidates.  Outputs per query q: enough [q * K ..] (mvpEnoughConsistentCandidates, in candidate order), n_enough [q],
+ * n_groups [q] (mvConsistentGroups.size() afterwards).  Host pointers: one upload, one launch, one download, synchronous; a call that holds what
+ * would be answered with -2 is refused as a whole with OSLAM_E_INVALID before anything runs. */
+int oslam_loopdet_update_consistency(oslam_loopdet_t* h, int n_queries, const oslam_loopdet_update_t* recs, int n_cand_total, const int32_t* cand, int32_t* enough,
+                                     int32_t* n_enough, int32_t* n_groups);
+/* The same over device arrays, asynchronous on `stream`, no host synchronisation. */
+int oslam_loopdet_update_consistency_device(oslam_loopdet_t* h, int n_queries, const oslam_loopdet_update_t* d_recs, int n_cand_total, const int32_t* d_cand,
+                                            int32_t* d_enough, int32_t* d_n_enough, int32_t* d_n_groups, void* stream);
+/* :122-226 for the current keyframe of each database: the loop query of the kfdb with its bound derived from the connected scores (the record's
+ * min_score is ignored), then the consistency update over that query's candidates; two launches on one stream, nothing returns to the host in
+ * between.  Outputs: those of oslam_kfdb_detect_loop_candidates, min_score [q], and those of oslam_loopdet_update_consistency.  Refusals as for
+ * oslam_kfdb_detect_loop_candidates; a query the kfdb refuses on the device (n_cand = -2) gives n_enough = -2 and leaves the groups unchanged. */
+int oslam_loopdet_detect(oslam_loopdet_t* h, const oslam_voc_t* voc, int n_queries, const oslam_kfdb_query_t* queries, int n_words_total, const uint32_t* ids,
+                         const double* vals, int n_conn_total, const int32_t* conn, int32_t* cand, float* cand_acc, int32_t* n_cand, int32_t* diag, float* conn_score,
+                         float* min_score, int32_t* enough, int32_t* n_enough, int32_t* n_groups);
+int oslam_loopdet_detect_device(oslam_loopdet_t* h, const oslam_voc_t* voc, int n_queries, const oslam_kfdb_query_t* d_queries, int n_words_total, const uint32_t* d_ids,
+                                const double* d_vals, int n_conn_total, const int32_t* d_conn, int32_t* d_cand, float* d_cand_acc, int32_t* d_n_cand, int32_t* d_diag,
+                                float* d_conn_score, float* d_min_score, int32_t* d_enough, int32_t* d_n_enough, int32_t* d_n_groups, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Initializer —ORB_SLAM2::Initializer (include/Initializer.h, src/Initializer.cc: homography / fundamental RANSAC, model selection, motion recovery),
  * the numerical operator of Tracking::MonocularInitialization (src/Tracking.cc:661, :695), for batches of independent problems (one per sequence
  * that is still initialising).  One shot: Initialize has no resumable state.  The tracking driver does not call it: oslam_slam.h is RGB-D / stereo
  * only.  ORBmatcher::SearchForInitialization (src/ORBmatcher.cc:405), which produces vMatches12, is the "Initialisation search" section below.

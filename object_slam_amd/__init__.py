@@ -36,3 +36,5 @@ from .object_map import ObjectMap  # noqa: F401
 from . import object_map  # noqa: F401
 from .loop_correct import LoopCorrector  # noqa: F401
 from . import loop_correct  # noqa: F401
+from .loop_detect import LoopDetector  # noqa: F401
+from . import loop_detect  # noqa: F401

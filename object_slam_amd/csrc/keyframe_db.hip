@@ -4,7 +4,8 @@
 // vector in LDS, a count pass over the word ids of every present slot (16 lanes per keyframe, binary search in LDS), the workgroup maximum, a score
 // pass over the survivors and the connected ids, a bitonic sort of the survivors by (smallest common word, add serial) in LDS, then accumulation,
 // threshold and dedup.  No inverted file, no atomics on global memory, nothing whose result depends on the order the hardware runs anything in (the
-// LDS atomics are integer max / min / add, and list positions taken with them are sorted afterwards).  Product code; never includes oracle/.
+// LDS atomics are integer max / min / add, and list positions taken with them are sorted afterwards).  For loop_detect.hip a loop query can derive its
+// bound from the connected scores itself (kfdb_state.h: kfdb_launch_query with a min_score array).  Product code; never includes oracle/.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -12,9 +13,11 @@
 #include <vector>
 
 #include "common.h"
+#include "kfdb_state.h"
 #include "lane_ops.h"
 #include "stage_layout.h"
 
+using oslam::KfdbState;   // (the resident state and the handle: kfdb_state.h, shared with loop_detect.hip)
 using oslam::set_error;
 
 namespace {
@@ -22,37 +25,6 @@ namespace {
 constexpr int kThreads = 512, kGroup = 16, kGroups = kThreads / kGroup;
 constexpr int kChunk = OSLAM_KFDB_CHUNK, kCovis = OSLAM_KFDB_COVIS;
 constexpr int kMutThreads = 256;
-
-// the resident state as the kernels see it; S = n_db * K slots, slot of (d, k) = d * K + k
-struct KfdbState {
-    int32_t* nwords;      // [S] words of the slot's vector; -1: not present
-    uint32_t* serial;     // [S] add serial
-    float* reloc;         // [S] reloc_score
-    int32_t* covis;       // [S][kCovis], -1 = no entry
-    int32_t* chunks;      // [S][MC] chunk indices of the slot's words
-    uint32_t* pool_ids;   // [n_chunks][kChunk]
-    double* pool_vals;    // [n_chunks][kChunk]
-    int n_db, K, MW, MC;
-};
-
-}  // namespace
-
-struct oslam_kfdb {
-    int device = 0, P = 1;
-    size_t lds = 0;
-    KfdbState st{};
-    oslam::DeviceBuffer nwords, serial, reloc, covis, chunks, pool_ids, pool_vals;
-    // the host's side of the state: what the refusals are decided on, and the allocator
-    std::vector<int32_t> h_nwords, h_chunks, free_chunks;
-    std::vector<uint32_t> next_serial;
-    long long n_chunks = 0, n_present = 0;
-    hipStream_t stream = nullptr;
-    oslam::StagePair io;
-    std::mutex mu;
-    ~oslam_kfdb() { if (stream) (void)hipStreamDestroy(stream); }
-};
-
-namespace {
 
 struct AddRec { int32_t slot, n_words, word_off, chunk_off; uint32_t serial; };
 
@@ -95,6 +67,7 @@ struct QueryArgs {
     int n_q, n_words_total, n_conn_total, loop, P;
     const uint32_t* ids; const double* vals; const int32_t* conn;
     int32_t* cand; float* cand_acc; int32_t* n_cand; int32_t* diag; float* conn_score;
+    float* min_score;   // not NULL: the bound of a loop query is derived from its connected scores and written here
 };
 
 size_t lds_bytes(int K, int MW, int P) {
@@ -133,7 +106,7 @@ __global__ __launch_bounds__(kThreads) void k_kfdb_query(QueryArgs a) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const oslam_kfdb_query_t Q = a.q[b];
     const int K = a.st.K, MW = a.st.MW, MC = a.st.MC;
-    const bool loop = a.loop != 0;
+    const bool loop = a.loop != 0, derive = loop && a.min_score != nullptr;
     const int nq = Q.n_words, ncn = loop ? Q.n_conn : 0;
 
     extern __shared__ __align__(16) uint8_t smem[];
@@ -148,13 +121,13 @@ __global__ __launch_bounds__(kThreads) void k_kfdb_query(QueryArgs a) {
     int* s_best = (int*)(s_acc + K);                                      // [K] pBestKF of entry e
     int* s_first = s_best + K;                                            // [K] first retained entry whose pBestKF is the slot
     uint8_t* s_flag = (uint8_t*)(s_first + K);                            // [K] kConn | kScored
-    __shared__ int s_bad, s_max, s_nshare, s_nscore, s_m;
+    __shared__ int s_bad, s_max, s_nshare, s_nscore, s_m, s_minkey;
     __shared__ float s_red[kThreads];
 
     // ---- the record, the query vector ----
     bool ok = Q.database >= 0 && Q.database < a.st.n_db && nq >= 0 && nq <= MW && Q.word_off >= 0 && Q.word_off <= a.n_words_total - nq;
     if (loop) ok = ok && ncn >= 0 && Q.conn_off >= 0 && Q.conn_off <= a.n_conn_total - ncn;
-    if (tid == 0) { s_bad = ok ? 0 : 1; s_max = 0; s_nshare = 0; s_nscore = 0; s_m = 0; }
+    if (tid == 0) { s_bad = ok ? 0 : 1; s_max = 0; s_nshare = 0; s_nscore = 0; s_m = 0; s_minkey = 0x3f800000; }   // (the bits of 1.0f)
     __syncthreads();
     if (ok) {
         for (int i = tid; i < a.n_q; i += kThreads)
@@ -264,7 +237,19 @@ __global__ __launch_bounds__(kThreads) void k_kfdb_query(QueryArgs a) {
     __syncthreads();
     for (int j = tid; j < ncn; j += kThreads) {
         const int id = a.conn[Q.conn_off + j];
-        a.conn_score[Q.conn_off + j] = (id >= 0 && id < K && s_words[id] >= 0) ? s_score[id] : -1.0f;
+        const bool present = id >= 0 && id < K && s_words[id] >= 0;
+        a.conn_score[Q.conn_off + j] = present ? s_score[id] : -1.0f;
+        if (derive && present) {   // an integer minimum over keys that order as the floats do (-0 below +0): exact, in any order
+            const int bits = __float_as_int(s_score[id]);
+            atomicMin(&s_minkey, bits < 0 ? bits ^ 0x7fffffff : bits);
+        }
+    }
+    float minScore = Q.min_score;
+    if (derive) {   // (uniform) minScore = min(1, the scores of the connected keyframes that are present) (src/LoopClosing.cc:127-139)
+        __syncthreads();
+        const int key = s_minkey;
+        minScore = __int_as_float(key < 0 ? key ^ 0x7fffffff : key);
+        if (tid == 0) a.min_score[b] = minScore;
     }
 
     // ---- lScoreAndMatch: the scored keyframes (loop: with si >= minScore), then sorted by (smallest common word, add serial) ----
@@ -273,7 +258,7 @@ __global__ __launch_bounds__(kThreads) void k_kfdb_query(QueryArgs a) {
         for (int k = tid; k < K; k += kThreads) {
             if (!(s_flag[k] & kScored)) continue;
             ln++;
-            if (loop && !(s_score[k] >= Q.min_score)) continue;
+            if (loop && !(s_score[k] >= minScore)) continue;
             const int pos = atomicAdd(&s_m, 1);   // (any position: the sort below orders the entries, and their keys differ)
             s_key[pos] = ((unsigned long long)s_minw[k] << 32) | a.st.serial[base + k];
             s_ent[pos] = k;
@@ -302,7 +287,7 @@ __global__ __launch_bounds__(kThreads) void k_kfdb_query(QueryArgs a) {
         }
 
     // ---- accumulate by covisibility (:148-173, :262-287) ----
-    float lbest = loop ? Q.min_score : 0.0f;   // bestAccScore
+    float lbest = loop ? minScore : 0.0f;   // bestAccScore
     for (int e = tid; e < M; e += kThreads) {
         const int slot = s_ent[e];
         float bestScore = s_score[slot], acc = bestScore;
@@ -369,7 +354,9 @@ int check_l1(const char* fn, const oslam_voc_t* voc) {
     return OSLAM_OK;
 }
 
-int check_query_call(const char* fn, const oslam_kfdb* h, const oslam_voc_t* voc, int n_queries, int n_words_total, int n_conn_total) {
+}  // namespace
+
+int oslam::kfdb_check_query_call(const char* fn, const oslam_kfdb* h, const oslam_voc_t* voc, int n_queries, int n_words_total, int n_conn_total) {
     if (!h) { set_error("%s: NULL handle", fn); return OSLAM_E_INVALID; }
     OSLAM_CHECK(check_l1(fn, voc));
     if (n_queries < 0 || n_words_total < 0 || n_conn_total < 0) { set_error("%s: a count is negative", fn); return OSLAM_E_INVALID; }
@@ -377,39 +364,19 @@ int check_query_call(const char* fn, const oslam_kfdb* h, const oslam_voc_t* voc
     return OSLAM_OK;
 }
 
-int launch_query(oslam_kfdb* h, bool loop, int n_queries, const oslam_kfdb_query_t* d_queries, int n_words_total, const uint32_t* d_ids, const double* d_vals, int n_conn_total,
-                 const int32_t* d_conn, int32_t* d_cand, float* d_cand_acc, int32_t* d_n_cand, int32_t* d_diag, float* d_conn_score, hipStream_t stream) {
+int oslam::kfdb_launch_query(oslam_kfdb* h, bool loop, int n_queries, const oslam_kfdb_query_t* d_queries, int n_words_total, const uint32_t* d_ids, const double* d_vals,
+                             int n_conn_total, const int32_t* d_conn, int32_t* d_cand, float* d_cand_acc, int32_t* d_n_cand, int32_t* d_diag, float* d_conn_score,
+                             float* d_min_score, hipStream_t stream) {
     QueryArgs a;
     a.st = h->st; a.q = d_queries; a.n_q = n_queries; a.n_words_total = n_words_total; a.n_conn_total = n_conn_total; a.loop = loop ? 1 : 0; a.P = h->P;
-    a.ids = d_ids; a.vals = d_vals; a.conn = d_conn; a.cand = d_cand; a.cand_acc = d_cand_acc; a.n_cand = d_n_cand; a.diag = d_diag; a.conn_score = d_conn_score;
+    a.ids = d_ids; a.vals = d_vals; a.conn = d_conn; a.cand = d_cand; a.cand_acc = d_cand_acc; a.n_cand = d_n_cand; a.diag = d_diag; a.conn_score = d_conn_score; a.min_score = d_min_score;
     hipLaunchKernelGGL(k_kfdb_query, dim3(n_queries), dim3(kThreads), h->lds, stream, a);
     OSLAM_HIP_CHECK(hipGetLastError());
     return OSLAM_OK;
 }
 
-int query_device(const char* fn, oslam_kfdb* h, const oslam_voc_t* voc, bool loop, int n_queries, const oslam_kfdb_query_t* d_queries, int n_words_total, const uint32_t* d_ids,
-                 const double* d_vals, int n_conn_total, const int32_t* d_conn, int32_t* d_cand, float* d_cand_acc, int32_t* d_n_cand, int32_t* d_diag, float* d_conn_score,
-                 void* stream) {
-    OSLAM_CHECK(check_query_call(fn, h, voc, n_queries, n_words_total, n_conn_total));
-    if (n_queries == 0) return OSLAM_OK;
-    if (!d_queries || !d_cand || !d_cand_acc || !d_n_cand || !d_diag || (n_words_total > 0 && (!d_ids || !d_vals)) || (loop && n_conn_total > 0 && (!d_conn || !d_conn_score))) {
-        set_error("%s: NULL argument", fn);
-        return OSLAM_E_INVALID;
-    }
-    OSLAM_HIP_CHECK(hipSetDevice(h->device));
-    return launch_query(h, loop, n_queries, d_queries, n_words_total, d_ids, d_vals, n_conn_total, d_conn, d_cand, d_cand_acc, d_n_cand, d_diag, d_conn_score, (hipStream_t)stream);
-}
-
-int query_host(const char* fn, oslam_kfdb* h, const oslam_voc_t* voc, bool loop, int n_queries, const oslam_kfdb_query_t* queries, int n_words_total, const uint32_t* ids,
-               const double* vals, int n_conn_total, const int32_t* conn, int32_t* cand, float* cand_acc, int32_t* n_cand, int32_t* diag, float* conn_score) {
-    OSLAM_CHECK(check_query_call(fn, h, voc, n_queries, n_words_total, n_conn_total));
-    if (n_queries == 0) return OSLAM_OK;
-    if (!queries || !cand || !cand_acc || !n_cand || !diag || (n_words_total > 0 && (!ids || !vals)) || (loop && n_conn_total > 0 && (!conn || !conn_score))) {
-        set_error("%s: NULL argument", fn);
-        return OSLAM_E_INVALID;
-    }
-    std::lock_guard<std::mutex> lock(h->mu);
-    const int K = h->st.K;
+int oslam::kfdb_check_queries(const char* fn, const oslam_kfdb* h, bool loop, int n_queries, const oslam_kfdb_query_t* queries, int n_words_total, const uint32_t* ids,
+                              int n_conn_total) {
     std::vector<uint8_t> seen(h->st.n_db, 0);
     for (int q = 0; q < n_queries; q++) {
         const oslam_kfdb_query_t& Q = queries[q];
@@ -422,6 +389,38 @@ int query_host(const char* fn, oslam_kfdb* h, const oslam_voc_t* voc, bool loop,
         for (int i = 1; i < Q.n_words; i++)
             if (ids[Q.word_off + i - 1] >= ids[Q.word_off + i]) { set_error("%s: query %d's word ids are not strictly ascending at %d", fn, q, i); return OSLAM_E_INVALID; }
     }
+    return OSLAM_OK;
+}
+
+namespace {
+
+using oslam::kfdb_check_query_call;
+
+int query_device(const char* fn, oslam_kfdb* h, const oslam_voc_t* voc, bool loop, int n_queries, const oslam_kfdb_query_t* d_queries, int n_words_total, const uint32_t* d_ids,
+                 const double* d_vals, int n_conn_total, const int32_t* d_conn, int32_t* d_cand, float* d_cand_acc, int32_t* d_n_cand, int32_t* d_diag, float* d_conn_score,
+                 void* stream) {
+    OSLAM_CHECK(kfdb_check_query_call(fn, h, voc, n_queries, n_words_total, n_conn_total));
+    if (n_queries == 0) return OSLAM_OK;
+    if (!d_queries || !d_cand || !d_cand_acc || !d_n_cand || !d_diag || (n_words_total > 0 && (!d_ids || !d_vals)) || (loop && n_conn_total > 0 && (!d_conn || !d_conn_score))) {
+        set_error("%s: NULL argument", fn);
+        return OSLAM_E_INVALID;
+    }
+    OSLAM_HIP_CHECK(hipSetDevice(h->device));
+    return oslam::kfdb_launch_query(h, loop, n_queries, d_queries, n_words_total, d_ids, d_vals, n_conn_total, d_conn, d_cand, d_cand_acc, d_n_cand, d_diag, d_conn_score, nullptr,
+                                    (hipStream_t)stream);
+}
+
+int query_host(const char* fn, oslam_kfdb* h, const oslam_voc_t* voc, bool loop, int n_queries, const oslam_kfdb_query_t* queries, int n_words_total, const uint32_t* ids,
+               const double* vals, int n_conn_total, const int32_t* conn, int32_t* cand, float* cand_acc, int32_t* n_cand, int32_t* diag, float* conn_score) {
+    OSLAM_CHECK(kfdb_check_query_call(fn, h, voc, n_queries, n_words_total, n_conn_total));
+    if (n_queries == 0) return OSLAM_OK;
+    if (!queries || !cand || !cand_acc || !n_cand || !diag || (n_words_total > 0 && (!ids || !vals)) || (loop && n_conn_total > 0 && (!conn || !conn_score))) {
+        set_error("%s: NULL argument", fn);
+        return OSLAM_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lock(h->mu);
+    const int K = h->st.K;
+    OSLAM_CHECK(oslam::kfdb_check_queries(fn, h, loop, n_queries, queries, n_words_total, ids, n_conn_total));
     OSLAM_HIP_CHECK(hipSetDevice(h->device));
     const size_t nq = (size_t)n_queries, W = (size_t)n_words_total, NC = loop ? (size_t)n_conn_total : 0;
     oslam::StageLayout lay;   // one block, inputs then outputs: one upload, one download
@@ -439,8 +438,8 @@ int query_host(const char* fn, oslam_kfdb* h, const oslam_voc_t* voc, bool loop,
     // the caller's output rows travel too: what the kernel does not write comes back as it was
     put(fCand, ph, cand); put(fAcc, ph, cand_acc); put(fN, ph, n_cand); put(fDiag, ph, diag); put(fCs, ph, conn_score);
     OSLAM_HIP_CHECK(hipMemcpyAsync(pd, ph, lay.total(), hipMemcpyHostToDevice, h->stream));
-    OSLAM_CHECK(launch_query(h, loop, n_queries, at(fQ, pd), n_words_total, at(fIds, pd), at(fVals, pd), (int)NC, at(fConn, pd), at(fCand, pd), at(fAcc, pd), at(fN, pd),
-                             at(fDiag, pd), at(fCs, pd), h->stream));
+    OSLAM_CHECK(oslam::kfdb_launch_query(h, loop, n_queries, at(fQ, pd), n_words_total, at(fIds, pd), at(fVals, pd), (int)NC, at(fConn, pd), at(fCand, pd), at(fAcc, pd),
+                                         at(fN, pd), at(fDiag, pd), at(fCs, pd), nullptr, h->stream));
     OSLAM_HIP_CHECK(hipMemcpyAsync(ph + fCand.off, pd + fCand.off, lay.total() - fCand.off, hipMemcpyDeviceToHost, h->stream));
     OSLAM_HIP_CHECK(hipStreamSynchronize(h->stream));
     get(fCand, ph, cand); get(fAcc, ph, cand_acc); get(fN, ph, n_cand); get(fDiag, ph, diag); get(fCs, ph, conn_score);
