@@ -3,7 +3,7 @@
 // SearchForInitialization, SearchByBoW (both overloads), SearchForTriangulation, Fuse, SearchBySim3, DescriptorDistance), Frame::ComputeStereoMatches (src/Frame.cc:706), ORB_SLAM2::Optimizer
 // (include/Optimizer.h:38-57: PoseOptimization, LocalBundleAdjustment, BundleAdjustment, OptimizeSim3, OptimizeEssentialGraph) and ObjectOptimizer::PoseOptimization2
 // (include/ObjectOptimizer.h:23), ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: loadFromTextFile, transform, score) ORB_SLAM2::PnPsolver (include/PnPsolver.h: SetRansacParameters, iterate, find) and ORB_SLAM2::Sim3Solver (include/Sim3Solver.h: SetRansacParameters, iterate, find, GetEstimatedRotation / Translation / Scale) and ORB_SLAM2::KeyFrameDatabase (include/KeyFrameDatabase.h: add, erase, clear,
-// DetectLoopCandidates, DetectRelocalizationCandidates) and ORB_SLAM2::LoopClosing (include/LoopClosing.h: DetectLoop) and ORB_SLAM2::ObjectMatcher (include/ObjectMatcher.h: MatchTwoFrame, MatchMapToFrame) with Frame::ExtractHSVHistogramsFromMask
+// DetectLoopCandidates, DetectRelocalizationCandidates) and ORB_SLAM2::LoopClosing (include/LoopClosing.h: DetectLoop, the LoopConnections loop of CorrectLoop) over ORB_SLAM2::KeyFrameGraph (KeyFrame's covisibility members, MapPoint's observations, Tracking::UpdateLocalKeyFrames) and ORB_SLAM2::ObjectMatcher (include/ObjectMatcher.h: MatchTwoFrame, MatchMapToFrame) with Frame::ExtractHSVHistogramsFromMask
 // (src/Frame.cc:388) as a free function, and ORB_SLAM2::Object3D (include/ObjectTypes.h: Update, RejectOutliers, CalculateCenterAndSize) with RejectNewObjectOutliers
 // (the new-object path of Tracking::UpdateCurrentObject) and ObjectMapRegularization / MergeObject (src/Map.cc:67-157) as free functions.  The reference methods walk Frame / KeyFrame / MapPoint pointer graphs; here every method takes a flat
 // "view" of exactly the members it reads and writes (the gather loops are in INTEGRATION.md).  tests/adapter_program.cc uses nothing but
@@ -1356,6 +1356,148 @@ private:
     int32_t diag_[5] = {0, 0, 0, 0, 0};
 };
 
+// ORB_SLAM2::KeyFrame's covisibility members (include/KeyFrame.h: AddConnection, EraseConnection, UpdateConnections, GetConnectedKeyFrames,
+// GetVectorCovisibleKeyFrames, GetBestCovisibilityKeyFrames, GetCovisiblesByWeight, GetWeight, ChangeParent, GetParent), MapPoint's observation list
+// (include/MapPoint.h: AddObservation, EraseObservation, SetBadFlag) and Tracking::UpdateLocalKeyFrames (src/Tracking.cc:1496-1604) for ONE sequence: one
+// graph of a covisibility handle of oslam_hip.h ("Covisibility graph": the restated semantics and its three normalisations).  Keyframes and points are ids
+// where the reference has pointers; the graph lives on the device.  Bookkeeping calls are queued and sent, in order, before the next call that reads.
+class KeyFrameGraph {
+public:
+    // a graph of its own: one handle with one graph
+    KeyFrameGraph(int maxKeyFrames, int maxPoints, int obsCap = 16) : K_(maxKeyFrames), graph_(0), own_(true), overflow_(1) {
+        oslam::throw_on(oslam_covis_create(&h_, 1, maxKeyFrames, maxPoints, obsCap, 0));
+    }
+    // graph `graph` of a handle of nGraphs graphs and maxKeyFrames keyframes that the caller keeps alive
+    KeyFrameGraph(oslam_covis_t* h, int nGraphs, int graph, int maxKeyFrames) : h_(h), K_(maxKeyFrames), graph_(graph), own_(false), overflow_(nGraphs) {}
+    ~KeyFrameGraph() { if (own_) oslam_covis_destroy(h_); }
+    KeyFrameGraph(const KeyFrameGraph&) = delete;
+    KeyFrameGraph& operator=(const KeyFrameGraph&) = delete;
+
+    // void MapPoint::AddObservation(KeyFrame* pKF, size_t idx)
+    void AddObservation(int pMP, int pKF, int idx) { push(OSLAM_COVIS_EV_OBS_ADD, pMP, pKF, idx); }
+    // void MapPoint::EraseObservation(KeyFrame* pKF): the caller decides on nObs <= 2 and then calls SetBadFlag
+    void EraseObservation(int pMP, int pKF) { push(OSLAM_COVIS_EV_OBS_ERASE, pMP, pKF, 0); }
+    // void MapPoint::SetBadFlag()
+    void SetBadFlag(int pMP) { push(OSLAM_COVIS_EV_POINT_BAD, pMP, 0, 0); }
+    // void KeyFrame::AddConnection(KeyFrame* pKF, const int &weight) / EraseConnection(KeyFrame* pKF) / ChangeParent(KeyFrame* pKF); mbBad = true of a keyframe
+    void AddConnection(int kf, int other, int weight) { push(OSLAM_COVIS_EV_CONN_ADD, kf, other, weight); }
+    void EraseConnection(int kf, int other) { push(OSLAM_COVIS_EV_CONN_ERASE, kf, other, 0); }
+    void ChangeParent(int kf, int parent) { push(OSLAM_COVIS_EV_PARENT_SET, kf, parent, 0); }
+    void SetKeyFrameBad(int kf) { push(OSLAM_COVIS_EV_KF_BAD, kf, 0, 0); }
+    // sends what is queued; throws when an observation list was full (normalisation 3)
+    void Flush() {
+        if (events_.empty()) return;
+        const int rc = oslam_covis_apply(h_, (int)events_.size(), events_.data(), overflow_.data());
+        events_.clear();
+        oslam::throw_on(rc);
+        if (overflow_[graph_] > 0) throw std::runtime_error("KeyFrameGraph: an observation list is full");
+    }
+
+    // void KeyFrame::UpdateConnections() of keyframe kf over vpMapPoints = its mvpMapPoints as point ids (-1 = NULL).  Returns false when the counter was
+    // empty ("This should not happen", :323); mvNewLinks receives the keys of the row afterwards minus the ordered list before minus exclude.
+    bool UpdateConnections(int kf, const std::vector<int32_t>& vpMapPoints, const std::vector<int32_t>& exclude = std::vector<int32_t>()) {
+        std::vector<std::vector<int32_t> > links;
+        const std::vector<int32_t> st = UpdateConnections(std::vector<int32_t>(1, kf), std::vector<std::vector<int32_t> >(1, vpMapPoints), exclude, &links);
+        mvNewLinks = links[0];
+        return st[0] == 0;
+    }
+    // the same for several keyframes in the order given, each leaving `exclude` out of its new links: one call.  Returns the status of each.
+    std::vector<int32_t> UpdateConnections(const std::vector<int32_t>& kfs, const std::vector<std::vector<int32_t> >& pointsOfEach, const std::vector<int32_t>& exclude,
+                                           std::vector<std::vector<int32_t> >* newLinks) {
+        Flush();
+        const size_t n = kfs.size();
+        std::vector<oslam_covis_update_t> recs(n);
+        std::vector<int32_t> pts;
+        for (size_t i = 0; i < n; i++) {
+            recs[i] = oslam_covis_update_t{graph_, kfs[i], (int32_t)pts.size(), (int32_t)pointsOfEach[i].size(), 0, (int32_t)exclude.size()};
+            pts.insert(pts.end(), pointsOfEach[i].begin(), pointsOfEach[i].end());
+        }
+        std::vector<int32_t> status(n), ids(n * K_), ws(n * K_), nOrd(n), parent(n), links(n * K_), nLinks(n);
+        oslam::throw_on(oslam_covis_update_connections(h_, (int)n, recs.data(), (int)pts.size(), pts.data(), (int)exclude.size(), exclude.data(), status.data(), ids.data(),
+                                                       ws.data(), nOrd.data(), parent.data(), links.data(), nLinks.data()));
+        if (newLinks) newLinks->clear();
+        for (size_t i = 0; i < n; i++) {
+            if (status[i] < 0) throw std::runtime_error("KeyFrame::UpdateConnections: an observation list it read had overflowed");
+            if (newLinks) newLinks->push_back(std::vector<int32_t>(links.begin() + i * K_, links.begin() + i * K_ + nLinks[i]));
+        }
+        return status;
+    }
+    std::vector<int32_t> mvNewLinks;   // of the last single UpdateConnections
+
+    // std::vector<KeyFrame*> KeyFrame::GetVectorCovisibleKeyFrames() / GetBestCovisibilityKeyFrames(const int &N) / GetCovisiblesByWeight(const int &w)
+    std::vector<int32_t> GetVectorCovisibleKeyFrames(int kf) { return covisibles(kf, K_, 0); }
+    std::vector<int32_t> GetBestCovisibilityKeyFrames(int kf, int N) { return covisibles(kf, N, 0); }
+    std::vector<int32_t> GetCovisiblesByWeight(int kf, int w) { return covisibles(kf, K_, w); }
+    const std::vector<int32_t>& orderedWeights() const { return weights_; }   // mvOrderedWeights of the entries the last of the three returned
+    // std::set<KeyFrame*> KeyFrame::GetConnectedKeyFrames(), ascending: what LoopClosing::SetConnectedKeyFrames and KeyFrameDatabaseKeyFrameView::spConnected take
+    std::vector<int32_t> GetConnectedKeyFrames(int kf) {
+        Flush();
+        const oslam_covis_key_t rec = {graph_, kf};
+        std::vector<uint32_t> bits((K_ + 31) / 32);
+        oslam::throw_on(oslam_covis_connected_rows(h_, 1, &rec, bits.data()));
+        std::vector<int32_t> out;
+        for (int i = 0; i < K_; i++)
+            if ((bits[i >> 5] >> (i & 31)) & 1u) out.push_back(i);
+        return out;
+    }
+    // int KeyFrame::GetWeight(KeyFrame* pKF)
+    int GetWeight(int kf, int other) {
+        Flush();
+        std::vector<int32_t> w((size_t)K_ * K_);
+        oslam::throw_on(oslam_covis_get_state(h_, graph_, w.data(), nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr));
+        return w[(size_t)kf * K_ + other];
+    }
+    // KeyFrame* KeyFrame::GetParent(): -1 for NULL
+    int GetParent(int kf) {
+        Flush();
+        std::vector<int32_t> p(K_);
+        oslam::throw_on(oslam_covis_get_state(h_, graph_, nullptr, p.data(), nullptr, 0, nullptr, nullptr, nullptr, nullptr));
+        return p[kf];
+    }
+    // void Tracking::UpdateLocalKeyFrames() for mCurrentFrame.mvpMapPoints = vpMapPoints (ids, -1 = NULL; the bad ones become -1, :1513).  Returns false when
+    // the vote was empty (:1518: nothing else changes); otherwise mvpLocalKeyFrames is replaced and mpReferenceKF set when a keyframe won the vote.
+    bool UpdateLocalKeyFrames(std::vector<int32_t>& vpMapPoints) {
+        Flush();
+        const oslam_covis_local_t rec = {graph_, 0, (int32_t)vpMapPoints.size()};
+        std::vector<int32_t> list(K_);
+        std::vector<uint8_t> null(vpMapPoints.size());
+        int32_t n = 0, ref = -1;
+        oslam::throw_on(oslam_covis_local_keyframes(h_, 1, &rec, (int)vpMapPoints.size(), vpMapPoints.data(), list.data(), &n, &ref, null.data()));
+        if (n < -1) throw std::runtime_error("Tracking::UpdateLocalKeyFrames: an observation list it read had overflowed");
+        for (size_t i = 0; i < null.size(); i++)
+            if (null[i]) vpMapPoints[i] = -1;
+        if (n < 0) return false;
+        mvpLocalKeyFrames.assign(list.begin(), list.begin() + n);
+        if (ref >= 0) mpReferenceKF = ref;
+        return true;
+    }
+    std::vector<int32_t> mvpLocalKeyFrames;
+    int mpReferenceKF = -1;
+
+    oslam_covis_t* handle() const { return h_; }
+    int graph() const { return graph_; }
+
+private:
+    void push(int32_t type, int32_t a, int32_t b, int32_t c) { events_.push_back(oslam_covis_event_t{graph_, type, a, b, c}); }
+    std::vector<int32_t> covisibles(int kf, int maxN, int minW) {
+        Flush();
+        const oslam_covis_query_t rec = {graph_, kf, maxN, minW};
+        std::vector<int32_t> ids(K_);
+        weights_.assign(K_, 0);
+        int32_t n = 0;
+        oslam::throw_on(oslam_covis_covisibles(h_, 1, &rec, ids.data(), weights_.data(), &n));
+        ids.resize(n); weights_.resize(n);
+        return ids;
+    }
+    oslam_covis_t* h_ = nullptr;
+    int K_;
+    int32_t graph_;
+    bool own_;
+    std::vector<int32_t> overflow_;   // oslam_covis_apply answers for every graph of the handle
+    std::vector<oslam_covis_event_t> events_;
+    std::vector<int32_t> weights_;
+};
+
 // ORB_SLAM2::LoopClosing (include/LoopClosing.h, src/LoopClosing.cc) as far as DetectLoop (:104-230) goes, for ONE sequence: over one KeyFrameDatabase of this
 // file and one detector of oslam_hip.h ("LoopClosing::DetectLoop": the restated consistency update and its normalisations).  The connected keyframes of every
 // keyframe and mvConsistentGroups live on the device; candidates are ids where the reference has KeyFrame pointers.  pDB must outlive this object.
@@ -1399,6 +1541,17 @@ public:
         mvpEnoughConsistentCandidates.assign(enough_.begin(), enough_.begin() + ne);
         mpKeyFrameDB->add(KF);
         return !mvpEnoughConsistentCandidates.empty();
+    }
+    // The loop of CorrectLoop that collects LoopConnections (:547-565): for each pKFi of mvpCurrentConnectedKFs in order, UpdateConnections, then
+    // GetConnectedKeyFrames() minus its previous neighbours minus mvpCurrentConnectedKFs.  pointsOfEach[i] = mvpMapPoints of connectedKFs[i] as point ids.
+    // The result is what Optimizer::OptimizeEssentialGraph takes as LoopConnections.
+    static std::map<int32_t, std::set<int32_t> > LoopConnections(KeyFrameGraph& graph, const std::vector<int32_t>& connectedKFs,
+                                                                 const std::vector<std::vector<int32_t> >& pointsOfEach) {
+        std::vector<std::vector<int32_t> > links;
+        graph.UpdateConnections(connectedKFs, pointsOfEach, connectedKFs, &links);
+        std::map<int32_t, std::set<int32_t> > out;
+        for (size_t i = 0; i < connectedKFs.size(); i++) out[connectedKFs[i]] = std::set<int32_t>(links[i].begin(), links[i].end());
+        return out;
     }
     std::vector<int32_t> mvpEnoughConsistentCandidates;   // ids
     std::vector<int32_t> mvpCandidateKFs;                 // vpCandidateKFs of the last DetectLoop that was not gated

@@ -1629,6 +1629,130 @@ int oslam_loopdet_detect_device(oslam_loopdet_t* h, const oslam_voc_t* voc, int 
                                 float* d_conn_score, float* d_min_score, int32_t* d_enough, int32_t* d_n_enough, int32_t* d_n_groups, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Covisibility graph — the point-side observation lists and KeyFrame's covisibility bookkeeping (src/KeyFrame.cc:123-208, :289-398, :553-567;
+ * src/MapPoint.cc:201-271) for many independent sequences, one graph per sequence, resident on the device, with KeyFrame::UpdateConnections
+ * (src/KeyFrame.cc:289-379), the covisibility queries and Tracking::UpdateLocalKeyFrames (src/Tracking.cc:1496-1604) as kernels over it.  It produces
+ * what oslam_kfdb_set_covisibility (GetBestCovisibilityKeyFrames(10)), oslam_loopdet_set_connected (GetConnectedKeyFrames()) and the edge list of
+ * OptimizeEssentialGraph (GetCovisiblesByWeight(100), parents, LoopConnections) take.  An operator: the driver does not call it.  No CPU fallback.
+ *
+ * State per graph, K = max_keyframes, P = max_points, C = obs_cap, W = ceil(K / 32):
+ *  - mObservations of every point slot: up to C entries (keyframe id, keypoint index) in ascending keyframe id, a count, mbBad and an overflow bit.
+ *  - mConnectedKeyFrameWeights of every keyframe: a row of K int32 weights, 0 = absent.
+ *  - per keyframe OSLAM_COVIS_KF_ORDERED_ALL: which part of the row is mvpOrderedConnectedKeyFrames.  Clear (after the keyframe's own
+ *    UpdateConnections): the entries >= 15, or the single maximum when none is (:341-352).  Set (after an UpdateBestCovisibles, i.e. an AddConnection
+ *    with a new or changed weight or an EraseConnection that erased): every entry.  The ordered list depends on this history, not on the row alone.
+ *  - per keyframe OSLAM_COVIS_KF_CONNECTED (= !mbFirstConnection), OSLAM_COVIS_KF_IS_BAD (mbBad) and mpParent (-1 = none).
+ * Bytes per graph: 8 P C + 4 P + 4 K K + 8 K (K = 2048, P = 200000, C = 16: 43.2 MB; K = 200, P = 20000, C = 16: 2.8 MB).
+ *
+ * Normalisations:
+ *  1. Wherever the reference walks a std::map<KeyFrame*, ...> or std::set<KeyFrame*> in pointer order, ids ascend (csrc/slam_map.h:3).  sort(vPairs)
+ *     with push_front therefore gives descending weight with ties in descending id.
+ *  2. Children are the keyframes whose mpParent it is: ChangeParent moves a child (the reference leaves it in the old parent's mspChildrens, which it
+ *     only does while that parent is being erased).
+ *  3. An observation list holds at most C entries.  An OBS_ADD that meets a full list changes nothing but the point's overflow bit and is counted;
+ *     whatever reads such a point afterwards answers -3 and changes nothing.  POINT_BAD clears the bit with the list.
+ *
+ * Whatever changes a graph runs in one workgroup (events: one wavefront) per graph, which takes the records of its graph in record order; graphs are
+ * independent and records of different graphs may interleave in any way.  The queries run one workgroup per record.  No atomics on global memory,
+ * nothing that depends on the order the hardware runs anything in: results are bit-identical between calls, batch compositions and entry points.
+ * The host-pointer entry points are synchronous and refuse a call that holds an id outside the handle, a record outside its arrays or an unknown
+ * event type as a whole with OSLAM_E_INVALID before anything runs.  The _device entry points take device arrays, are asynchronous on `stream` and do
+ * no host synchronisation; there an event with such an id is skipped and such a record answers -2.  Calls on one handle are sequential: they share its
+ * state (the host entry points hold the handle's lock; _device callers order their streams themselves).
+ * ---------------------------------------------------------------------------------------- */
+#define OSLAM_COVIS_MAX_KEYFRAMES 2048
+#define OSLAM_COVIS_MAX_OBS 64
+#define OSLAM_COVIS_PT_BAD 1u              /* point flags, as oslam_covis_get_state returns them */
+#define OSLAM_COVIS_PT_OVERFLOW 2u
+#define OSLAM_COVIS_KF_ORDERED_ALL 1u      /* keyframe flags */
+#define OSLAM_COVIS_KF_CONNECTED 2u
+#define OSLAM_COVIS_KF_IS_BAD 4u
+enum {
+    OSLAM_COVIS_EV_OBS_ADD = 0,      /* (point, keyframe, keypoint index): MapPoint::AddObservation (src/MapPoint.cc:201-212); nothing if the point has
+                                      * an observation in the keyframe; the bad bit is not looked at */
+    OSLAM_COVIS_EV_OBS_ERASE = 1,    /* (point, keyframe): MapPoint::EraseObservation (:214-240) without the nObs <= 2 -> SetBadFlag rule, which stays
+                                      * with the caller (who knows nObs's stereo weights) and sends POINT_BAD */
+    OSLAM_COVIS_EV_POINT_BAD = 2,    /* (point): MapPoint::SetBadFlag (:254-263): the bad bit, an empty list, no overflow bit */
+    OSLAM_COVIS_EV_CONN_ADD = 3,     /* (keyframe, other, weight > 0): KeyFrame::AddConnection (src/KeyFrame.cc:123-136), the early return of an equal
+                                      * weight included, which leaves OSLAM_COVIS_KF_ORDERED_ALL alone */
+    OSLAM_COVIS_EV_CONN_ERASE = 4,   /* (keyframe, other): KeyFrame::EraseConnection (:553-567) */
+    OSLAM_COVIS_EV_KF_BAD = 5,       /* (keyframe): mbBad = true alone; SetBadFlag's erasures and spanning-tree repair (:466-537) are the caller's events */
+    OSLAM_COVIS_EV_PARENT_SET = 6    /* (keyframe, parent): KeyFrame::ChangeParent (:393-398) */
+};
+typedef struct oslam_covis oslam_covis_t;
+typedef struct oslam_covis_event {
+    int32_t graph, type;
+    int32_t a, b, c;               /* the operands in the order the event lists them; unused ones are ignored */
+} oslam_covis_event_t;
+typedef struct oslam_covis_update {
+    int32_t graph, keyframe;
+    int32_t pts_off, n_pts;        /* mvpMapPoints as point ids, -1 = empty slot: points pts_off .. pts_off + n_pts - 1 of the call's points */
+    int32_t excl_off, n_excl;      /* keyframe ids left out of new_links: exclude excl_off .. excl_off + n_excl - 1 */
+} oslam_covis_update_t;
+typedef struct oslam_covis_query {
+    int32_t graph, keyframe;
+    int32_t max_n, min_w;          /* at most max_n entries; min_w > 0: GetCovisiblesByWeight(min_w) */
+} oslam_covis_query_t;
+typedef struct oslam_covis_key {
+    int32_t graph, keyframe;
+} oslam_covis_key_t;
+typedef struct oslam_covis_local {
+    int32_t graph;
+    int32_t pts_off, n_pts;        /* mCurrentFrame.mvpMapPoints as point ids, -1 = NULL */
+} oslam_covis_local_t;
+/* n_graphs graphs in the state of a new map: no observation, no connection, no parent, nothing bad.  1 <= max_keyframes <= OSLAM_COVIS_MAX_KEYFRAMES,
+ * 1 <= obs_cap <= OSLAM_COVIS_MAX_OBS. */
+int oslam_covis_create(oslam_covis_t** out, int n_graphs, int max_keyframes, int max_points, int obs_cap, int device);
+void oslam_covis_destroy(oslam_covis_t* h);
+/* Returns each named graph to the created state (Map::clear, src/Map.cc:260). */
+int oslam_covis_reset(oslam_covis_t* h, int n, const int32_t* graphs);
+/* The events of each graph in record order (the bookkeeping of src/MapPoint.cc:201-271 and src/KeyFrame.cc:123-136, :393-398, :553-567; MapPoint::Replace,
+ * :280, is the caller's sequence of them).  n_overflow_out [n_graphs]: per graph the OBS_ADDs of this call that met a full list (0 for a graph
+ * without events). */
+int oslam_covis_apply(oslam_covis_t* h, int n_events, const oslam_covis_event_t* events, int32_t* n_overflow_out);
+int oslam_covis_apply_device(oslam_covis_t* h, int n_events, const oslam_covis_event_t* d_events, int32_t* d_n_overflow_out, void* stream);
+/* KeyFrame::UpdateConnections (src/KeyFrame.cc:289-379, the product's host restatement is csrc/slam_map.h:473-509) of each record's keyframe over its
+ * mvpMapPoints; the records of one graph in record order, a later one seeing the AddConnections of an earlier one.  A duplicate point id counts once
+ * per occurrence, as the reference's loop over vpMP does.  Outputs per record r:
+ *   status [r]        0; 1: the counter was empty and nothing changed (:323); -3: a point with the overflow bit was read and nothing changed
+ *                     (n_ordered = n_new_links = 0 then); -2 (_device only): a record outside the handle or the arrays
+ *   ordered_ids / ordered_w [r * K ..], n_ordered [r]   mvpOrderedConnectedKeyFrames / mvOrderedWeights afterwards
+ *   parent [r]        mpParent afterwards
+ *   new_links [r * K ..], n_new_links [r]   the keys of the row AFTER the update, minus the ordered list BEFORE it, minus the exclude ids, ascending:
+ *                     LoopConnections[pKFi] of src/LoopClosing.cc:549-565 with exclude = mvpCurrentConnectedKFs */
+int oslam_covis_update_connections(oslam_covis_t* h, int n, const oslam_covis_update_t* recs, int n_points_total, const int32_t* points, int n_excl_total,
+                                   const int32_t* exclude, int32_t* status, int32_t* ordered_ids, int32_t* ordered_w, int32_t* n_ordered, int32_t* parent,
+                                   int32_t* new_links, int32_t* n_new_links);
+int oslam_covis_update_connections_device(oslam_covis_t* h, int n, const oslam_covis_update_t* d_recs, int n_points_total, const int32_t* d_points, int n_excl_total,
+                                          const int32_t* d_exclude, int32_t* d_status, int32_t* d_ordered_ids, int32_t* d_ordered_w, int32_t* d_n_ordered,
+                                          int32_t* d_parent, int32_t* d_new_links, int32_t* d_n_new_links, void* stream);
+/* The ordered list with its weights: ids / weights [r * K ..], n_out [r].  max_n = K, min_w = 0: GetVectorCovisibleKeyFrames (src/KeyFrame.cc:168-172);
+ * max_n = N: GetBestCovisibilityKeyFrames(N) (:174-182; N = 10 gives the layout of oslam_kfdb_covis_t::ids); min_w = w: GetCovisiblesByWeight(w)
+ * (:184-199), its quirk included: when EVERY weight is >= w, upper_bound returns end() and the answer is empty (:192-193). */
+int oslam_covis_covisibles(oslam_covis_t* h, int n, const oslam_covis_query_t* recs, int32_t* ids, int32_t* weights, int32_t* n_out);
+int oslam_covis_covisibles_device(oslam_covis_t* h, int n, const oslam_covis_query_t* d_recs, int32_t* d_ids, int32_t* d_weights, int32_t* d_n_out, void* stream);
+/* GetConnectedKeyFrames() (src/KeyFrame.cc:159-166) as bitset rows: bits [r * W ..], bit i of word i / 32 = id i — the row oslam_loopdet_set_connected
+ * builds from ids. */
+int oslam_covis_connected_rows(oslam_covis_t* h, int n, const oslam_covis_key_t* recs, uint32_t* bits);
+int oslam_covis_connected_rows_device(oslam_covis_t* h, int n, const oslam_covis_key_t* d_recs, uint32_t* d_bits, void* stream);
+/* Tracking::UpdateLocalKeyFrames (src/Tracking.cc:1496-1604; the driver's host restatement is csrc/slam_driver.hip:534), whole: the vote over the points
+ * that are not bad, the voters that are not bad in ascending id, pKFmax by the strict '>', then for each of those voters in order, while the list has
+ * at most 80 entries: the first keyframe of GetBestCovisibilityKeyFrames(10) that is neither bad nor included, the first such child in ascending id,
+ * and the parent if it is not included — which leaves the OUTER loop (the break of :1593).  Outputs per record r: list [r * K ..], n_list [r]
+ * (mvpLocalKeyFrames), ref_kf [r] (mpReferenceKF; -1: no voter that is not bad, the reference keeps the old one), null_out [pts_off + i] = 1 where the
+ * reference sets mvpMapPoints[i] = NULL (:1513), else 0.  n_list = -1: the vote was empty (:1518), list and ref_kf are not written; -3: a point with
+ * the overflow bit was read; -2 (_device only): a record outside the handle or the arrays. */
+int oslam_covis_local_keyframes(oslam_covis_t* h, int n, const oslam_covis_local_t* recs, int n_points_total, const int32_t* points, int32_t* list, int32_t* n_list,
+                                int32_t* ref_kf, uint8_t* null_out);
+int oslam_covis_local_keyframes_device(oslam_covis_t* h, int n, const oslam_covis_local_t* d_recs, int n_points_total, const int32_t* d_points, int32_t* d_list,
+                                       int32_t* d_n_list, int32_t* d_ref_kf, uint8_t* d_null_out, void* stream);
+/* A plain readback of one graph (synchronous): weights [K * K] (GetWeight, src/KeyFrame.cc:201-208), parents [K], kf_flags [K] (OSLAM_COVIS_KF_*) —
+ * each may be NULL — and for each of n_points point ids: obs [i * C * 2 ..] as (keyframe, index) pairs, obs_count [i], point_flags [i]
+ * (OSLAM_COVIS_PT_*). */
+int oslam_covis_get_state(oslam_covis_t* h, int graph, int32_t* weights, int32_t* parents, uint32_t* kf_flags, int n_points, const int32_t* points, int32_t* obs,
+                          int32_t* obs_count, uint32_t* point_flags);
+
+/* ------------------------------------------------------------------------------------------
  * Initializer —ORB_SLAM2::Initializer (include/Initializer.h, src/Initializer.cc: homography / fundamental RANSAC, model selection, motion recovery),
  * the numerical operator of Tracking::MonocularInitialization (src/Tracking.cc:661, :695), for batches of independent problems (one per sequence
  * that is still initialising).  One shot: Initialize has no resumable state.  The tracking driver does not call it: oslam_slam.h is RGB-D / stereo

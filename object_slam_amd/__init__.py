@@ -38,3 +38,5 @@ from .loop_correct import LoopCorrector  # noqa: F401
 from . import loop_correct  # noqa: F401
 from .loop_detect import LoopDetector  # noqa: F401
 from . import loop_detect  # noqa: F401
+from .covisibility import CovisibilityGraph  # noqa: F401
+from . import covisibility  # noqa: F401

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "liboslam_hip.so")
-SOURCES = ["orb_extractor.hip", "matcher.hip", "pose_opt.hip", "lba.hip", "stereo.hip", "bow_matcher.hip", "mappoint.hip", "frame.hip", "slam_driver.hip", "slam_ops_hip.hip", "vocabulary.hip", "pnp.hip", "sim3.hip", "sim3_match.hip", "sim3_opt.hip", "sim3_project.hip", "essential_graph.hip", "keyframe_db.hip", "reloc_project.hip", "initializer.hip", "search_init.hip", "object_match.hip", "object_map.hip", "loop_correct.hip", "loop_detect.hip"]
+SOURCES = ["orb_extractor.hip", "matcher.hip", "pose_opt.hip", "lba.hip", "stereo.hip", "bow_matcher.hip", "mappoint.hip", "frame.hip", "slam_driver.hip", "slam_ops_hip.hip", "vocabulary.hip", "pnp.hip", "sim3.hip", "sim3_match.hip", "sim3_opt.hip", "sim3_project.hip", "essential_graph.hip", "keyframe_db.hip", "reloc_project.hip", "initializer.hip", "search_init.hip", "object_match.hip", "object_map.hip", "loop_correct.hip", "loop_detect.hip", "covisibility.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = (os.environ["OSLAM_EXTRA_FLAGS"].split() if os.environ.get("OSLAM_EXTRA_FLAGS") else []) + (["-DOSLAM_LBA_PROFILE"] if os.environ.get("OSLAM_LBA_PROFILE") else []) + (["-DOSLAM_FAST_PROFILE"] if os.environ.get("OSLAM_FAST_PROFILE") else []) + (["-DOSLAM_MATCH_PROFILE"] if os.environ.get("OSLAM_MATCH_PROFILE") else []) + (["-DOSLAM_MATCH_ABLATE=" + os.environ["OSLAM_MATCH_ABLATE"]] if os.environ.get("OSLAM_MATCH_ABLATE") else []) + ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17",
          "-ffp-contract=off",  # host AND device: reference float expressions round once per operator
