@@ -235,7 +235,10 @@ typedef struct oslam_job_triangulate {     /* oslam_mp_triangulate for one (curr
 
 /* Changes of one sequence's map for the table's device mirror (oslam_slam_ops_t::map_journal).  Everything that only needs its final state carries CURRENT values;
  * the observation events are in program order and for one (kf, idx) the LAST one decides (an erase clears the cell whoever held it).
- *   reset        != 0: the sequence started a new map before these changes (Tracking::Reset): ids restart at 0
+ *   reset        != 0: the sequence started a new map before these changes (Tracking::Reset): ids restart at 0.  A table may ignore it (the HIP table does) as long as
+ *                nothing of the old map can show: register_keyframes with id 0 has returned the old records, the bulk record of a new keyframe rewrites every cell,
+ *                holder and depth bit of the record it reuses, and a point id a cell of the new map names is in `points` of the same or an earlier change set
+ *                of that map (tests/test_mirror_cases_gpu.py: reset_smaller_N; every case of that file starts on reused records and reused point ids)
  *   new_kfs      n_new keyframes created since the last call: id, keypoint count, KeyFrame::mvpMapPoints as it is now, and one bit per keypoint
  *                !(mvDepth[i] > mThDepth || mvDepth[i] < 0) (src/LocalMapping.cc:663-667; keypoints, depths and mThDepth never change)
  *   cells        n_cells x (kf, idx, p): KeyFrame::mvpMapPoints[idx] is now p (-1: none)                        (src/KeyFrame.cc:201-230)
@@ -257,7 +260,16 @@ typedef struct oslam_job_cull { int32_t slot, n; const int32_t* kf_ids; int32_t*
  * (mnFuseCandidateForKF) — from its mirror of the observation graph (map_journal), runs ORBmatcher::Fuse's gates and search for them and returns the matches:
  * pairs[2 q] = map point, pairs[2 q + 1] = keypoint of the current keyframe, in candidate order; the driver applies them (Replace / AddObservation) as it applies the
  * match table of fuse_points_keyed.  overflow != 0: more candidates or matches than the table's bounds — the driver then takes its own path for the whole call.
- * dbg_ids / dbg_excl (optional, tests): the candidate list and its "bad or already observed by the keyframe" flags, at most dbg_cap entries. */
+ * dbg_ids / dbg_excl (optional, tests): the candidate list and its "bad or already observed by the keyframe" flags, at most dbg_cap entries.
+ * PRECONDITION: every point that observes the current keyframe is in its point list.  "Already observed by the keyframe" (MapPoint::IsInKeyFrame, src/ORBmatcher.cc:849)
+ * is answered from the keyframe's mvpMapPoints mirror, not from mObservations: a point that kept an observation of the current keyframe after another point took its
+ * keypoint (two claims on one keypoint, src/LocalMapping.cc:440-446) is in no cell and would be searched although the reference skips it; the mirror cannot represent
+ * that state, so the table cannot report it either.  The driver calls fuse_into_current for a keyframe once, in the pass that created it, and up to that call every
+ * observation of the keyframe was added together with its cell on a keypoint whose cell was empty: CreateNewKeyFrame's and ProcessNewKeyFrame's points come from
+ * the frame's own list, CreateNewMapPoints skips a keypoint of the current keyframe that has received a point (`if(pMP1) continue`, src/ORBmatcher.cc:711-716), the
+ * first direction of SearchInNeighbors fuses INTO the neighbours, and MapPoint::Replace moves an observation and its cell together.  Two claims on one keypoint do
+ * arise on the NEIGHBOUR side of CreateNewMapPoints, i.e. on keyframes that are never current again.  OSLAM_SLAM_FUSECUR_CHECK=1 compares the flags with
+ * mObservations at every call; tests/test_mirror_cases_gpu.py pins what the table answers outside the precondition (the flag of the cell list). */
 typedef struct oslam_job_fuse_cur {
     int32_t slot, kf;
     int32_t n_targets; const int32_t* targets;
@@ -387,6 +399,9 @@ typedef struct oslam_slam_ops {
 int oslam_slam_create(oslam_slam_t** out, const oslam_slam_config_t* cfg);
 /* Same driver over a caller-supplied operator table (ownership of ops->ctx passes to the handle). Test seam. */
 int oslam_slam_create_with_ops(oslam_slam_t** out, const oslam_slam_config_t* cfg, const oslam_slam_ops_t* ops);
+/* The HIP operator table oslam_slam_create binds, alone: *ops is filled for cfg (OSLAM_E_HIP without a device: there is no CPU table).  The caller owns the table
+ * and ends it with ops->destroy(ops->ctx).  Test seam: the operator-level tests call the table's functions without a driver. */
+int oslam_slam_make_hip_ops(const oslam_slam_config_t* cfg, oslam_slam_ops_t* ops);
 void oslam_slam_destroy(oslam_slam_t* h);
 /* The ORB vocabulary of the system (mpVocabulary, src/System.cc:64-76), shared by all sequences of the handle.  Allowed only before the first frame
  * (OSLAM_E_INVALID afterwards).  The vocabulary is borrowed: it must outlive the handle.  NULL, or never calling this, keeps the substitute vocabulary

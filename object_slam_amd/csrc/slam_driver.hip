@@ -12,7 +12,7 @@
 #include "slam_map.h"
 #include "slam_pool.h"
 
-int oslam_slam_make_hip_ops(const oslam_slam_config_t* cfg, oslam_slam_ops_t* out);   // slam_ops_hip.hip
+// (oslam_slam_make_hip_ops: declared in include/oslam_slam.h, defined in slam_ops_hip.hip)
 
 namespace oslam_drv {
 

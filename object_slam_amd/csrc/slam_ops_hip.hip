@@ -1650,6 +1650,7 @@ int h_kf_culling_counts(void* p, int n, const oslam_job_cull_t* jobs, float thDe
     const auto fC = L.add<CullCand>(total); const auto fOut = L.add<int32_t>(4 * total);
     const size_t base = oslam::align_up(o->mir_used, 256), end = base + fOut.end();
     if (end > o->mir.cap()) {   // (rare: the block is grown with nothing in flight; the flush, if any, has completed by then)
+        // (tests/test_mirror_cases_gpu.py reaches this branch with a request larger than any block ensure_mir has made before it in that module: the block only grows)
         OSLAM_HIP_CHECK(hipStreamSynchronize(o->strm));
         o->mir_used = 0;
         OSLAM_CHECK(o->ensure_mir(L.total() + 1024));
@@ -2183,7 +2184,7 @@ void h_destroy(void* p) {
 
 }  // namespace
 
-int oslam_slam_make_hip_ops(const oslam_slam_config_t* cfg, oslam_slam_ops_t* ops) {
+extern "C" int oslam_slam_make_hip_ops(const oslam_slam_config_t* cfg, oslam_slam_ops_t* ops) {
     if (oslam_device_count() <= 0 || hipSetDevice(cfg->device) != hipSuccess) {
         oslam::set_error("oslam_slam_create: no HIP device (the tracking driver has no CPU fallback)");
         return OSLAM_E_HIP;

@@ -1,7 +1,10 @@
 // Host-side unit checks of the driver's map bookkeeping (object_slam_amd/csrc/slam_map.h) against the behaviour of the reference's
 // KeyFrame / MapPoint methods (src/KeyFrame.cc:123-567, src/MapPoint.cc:196-318), on a hand-built map.  No GPU, no oracle.
+// `slam_map_check replay <script>` replays a scripted operation sequence with the change log on and prints the arrays of Map::journal_changes at every flush
+// (tests/test_mirror_cases_cpu.py compares them with the change sets of the Python model of tests/mirror_common.py, which feeds the device mirror's tests).
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "../object_slam_amd/csrc/slam_map.h"
 
@@ -24,7 +27,67 @@ static int add_kf(Map& m, int nkp, bool stereo) {
 }
 static void observe(Map& m, int p, int kf, int idx) { m.add_observation(p, kf, idx); m.kfs[kf].mp[idx] = p; }
 
-int main() {
+// One operation per line (tests/mirror_common.py REPLAY_SCRIPT): K kf | P | A p kf idx | M kf idx p | E p kf | B p | R p q | X kf | Z | F.  Keypoint i of every
+// keyframe: octave i % 8; class (i / 8) % 5: 0-2 stereo at 2 m, 3 stereo at 100 m (beyond mThDepth), 4 no depth.
+static int replay(const char* path) {
+    FILE* f = fopen(path, "r");
+    if (!f) { fprintf(stderr, "cannot open %s\n", path); return 2; }
+    const int NK = 64;
+    const float thDepth = 40.0f * 40.0f / 520.908620f;
+    Map m;
+    m.jrOn = true;
+    Map::JrScratch sc;
+    char op[8];
+    while (fscanf(f, "%7s", op) == 1) {
+        int a = 0, b = 0, c = 0;
+        switch (op[0]) {
+        case 'K': {
+            if (fscanf(f, "%d", &a) != 1) return 2;
+            CHECK(a == (int)m.kfs.size());
+            add_kf(m, NK, true);
+            KeyFrm& k = m.kfs.back();
+            for (int i = 0; i < NK; i++) {
+                const int cls = (i / 8) % 5;
+                k.keysUn[i].octave = k.keys[i].octave = i % 8;
+                k.uRight[i] = cls == 4 ? -1.f : 10.f; k.depth[i] = cls == 4 ? -1.f : (cls == 3 ? 100.f : 2.f);
+            }
+            if (k.id > 0) { k.parent = 0; m.kfs[0].children.insert(k.id); }
+            m.jr_new_kf(k.id);
+            break; }
+        case 'P': { const float x[3] = {0, 0, 2}; m.new_point(x, 0, 0); m.nMPsInMap++; break; }
+        case 'A': if (fscanf(f, "%d %d %d", &a, &b, &c) != 3) return 2; m.add_observation(a, b, c); break;
+        case 'M': if (fscanf(f, "%d %d %d", &a, &b, &c) != 3) return 2; m.set_kf_mp(a, b, c); break;
+        case 'E': if (fscanf(f, "%d %d", &a, &b) != 2) return 2; m.erase_observation(a, b); break;
+        case 'B': if (fscanf(f, "%d", &a) != 1) return 2; m.set_bad_point(a); break;
+        case 'R': if (fscanf(f, "%d %d", &a, &b) != 2) return 2; m.replace_point(a, b); break;
+        case 'X': if (fscanf(f, "%d", &a) != 1) return 2; m.set_bad_keyframe(a); break;
+        case 'Z': m = Map(); m.jrOn = true; m.jrReset = true; break;   // (Seq::reset of csrc/slam_driver.hip)
+        case 'F': {
+            oslam_map_changes_t ch;
+            m.journal_changes(0, thDepth, sc, ch);
+            printf("flush reset=%d\n", ch.reset);
+            for (int k = 0; k < ch.n_new; k++) {
+                const oslam_map_new_kf_t& e = ch.new_kfs[k];
+                printf("new %d %d :", e.kf, e.N);
+                for (int i = 0; i < e.N; i++) printf(" %d", e.mp[i]);
+                printf(" :");
+                for (int i = 0; i < (e.N + 31) / 32; i++) printf(" %u", e.good[i]);
+                printf("\n");
+            }
+            for (int i = 0; i < ch.n_cells; i++) printf("cell %d %d %d\n", ch.cells[3 * i], ch.cells[3 * i + 1], ch.cells[3 * i + 2]);
+            for (int i = 0; i < ch.n_events; i++) printf("event %u %u %u\n", ch.events[3 * i], ch.events[3 * i + 1], ch.events[3 * i + 2]);
+            for (int i = 0; i < ch.n_points; i++) printf("point %u %u %u %u %u\n", ch.points[5 * i], ch.points[5 * i + 1], ch.points[5 * i + 2], ch.points[5 * i + 3], ch.points[5 * i + 4]);
+            CHECK(!m.lvlOverflow);
+            break; }
+        default: fprintf(stderr, "bad operation %s\n", op); return 2;
+        }
+    }
+    fclose(f);
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc == 3 && !strcmp(argv[1], "replay")) return replay(argv[2]);
     Map m;
     std::vector<int> counter(64, 0);
     const int NK = 50;   // slots 40..49 stay free for the single-point scenarios

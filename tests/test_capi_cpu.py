@@ -58,11 +58,14 @@ def test_ctypes_mirrors_have_the_sizes_of_the_headers(tmp_path):
     import subprocess
     from object_slam_amd import extractor, mappoint, matcher, optimizer, slam
     from object_slam_amd._lib import lib
+    import mirror_common   # (the test-side mirrors of the operator table's job structs)
     pairs = [("oslam_slam_config_t", slam.SlamConfig), ("oslam_slam_ops_t", slam.SlamOps), ("oslam_slam_objects_t", slam.SlamObjects),
              ("oslam_tri_kf_t", mappoint.TriKF), ("oslam_camera_t", matcher.Camera), ("oslam_match_frames_t", matcher.MatchFrames),
              ("oslam_match_last_t", matcher.MatchLast), ("oslam_bow_side1_t", matcher.BowSide1), ("oslam_bow_side2_t", matcher.BowSide2),
              ("oslam_bow_job_t", matcher.BowJob), ("oslam_bow_resident_t", matcher.BowResident),
-             ("oslam_semantic_t", optimizer.Semantic), ("oslam_lba_problem_t", optimizer.LbaProblem), ("oslam_orb_plan_t", extractor.OrbPlan)]
+             ("oslam_semantic_t", optimizer.Semantic), ("oslam_lba_problem_t", optimizer.LbaProblem), ("oslam_orb_plan_t", extractor.OrbPlan)] + mirror_common.MIRRORS
+    assert set(n for n, _ in mirror_common.MIRRORS) >= {"oslam_slam_frame_t", "oslam_map_new_kf_t", "oslam_map_changes_t", "oslam_job_cull_t", "oslam_job_fuse_cur_t",
+                                                     "oslam_job_local_list_t", "oslam_job_mp_update_t"}
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     src = tmp_path / "sizes.c"
     src.write_text('#include <stdio.h>\n#include "oslam_hip.h"\n#include "oslam_slam.h"\nint main(void) {\n'
@@ -75,3 +78,4 @@ def test_ctypes_mirrors_have_the_sizes_of_the_headers(tmp_path):
     out = (C.c_int32 * 4)()
     assert lib().oslam_slam_struct_sizes(out) == 0
     assert (out[0], out[1], out[2]) == (c_sizes["oslam_slam_config_t"], c_sizes["oslam_slam_ops_t"], c_sizes["oslam_slam_objects_t"])
+    assert out[3] == c_sizes["oslam_map_changes_t"]
